@@ -19,16 +19,29 @@ K times, streamed continuously).
 TIMED SPAN = the reference's own FPS span (src/aicamera_tracker.py:175,201-207 with the `.to(device)` of
 yolo_detector.py:91 inside): frame bytes in (page-locked) HOST memory -> track tuples on the host.  Every
 launch group's frames cross PCIe on a copy stream under the previous group's compute
-(aic_pipeline_run_from_host_passes).  The rate with the clip already resident in HBM is reported beside it
-(`config.hbm_resident_fps`), as are per-frame latency (handed to the pipeline -> tuples on the host, p50 / p99)
-and throughput for launch groups of 16 / 64 / 128 / 256 / 512 frames.
+(aic_pipeline_run_from_host_passes).  Per-frame latency of the timed run (handed to the pipeline -> tuples on
+the host, p50 / p99) is reported beside it.
 
-One JSON line on rank 0.  `roofline`: the dominant kernel class conv_igemm (MFMA implicit GEMM), achieved =
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line; `ms_per_step` is the wall time of one timed step.  What takes
+work of its own is measured only with --full (the --no-* switches then leave out single parts of it): the rate
+with the clip already resident in HBM (`config.hbm_resident_fps`), throughput for launch groups of 16 / 64 / 128 /
+256 / 512 frames, the other stream arrangement, the own-detections legs, the per-frame plugin loop, and
+
+`roofline`: the dominant kernel class conv_igemm (MFMA implicit GEMM), achieved =
 algorithmic conv FLOPs / the time during which a conv launch bracket was open on either launch stream (union of
 the brackets' intervals, paired HIP events per stream on the device clock, recorded over the timed region); the
 figure over the SUMMED bracket durations is reported beside it (the two agree with --single-stream).  `cpu_baseline`: the oracle chain (torch-CPU fp32 nets + NumPy/SciPy DeepSORT) timed
 on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only): >= 200 frames on all
-cores with a per-stage split, plus a 1-thread leg.
+cores with a per-stage split, plus a 1-thread leg.  Without --full both are null.
+
+--dump-outputs DIR (rank 0): what the timed call returned for the last step -- per-frame confirmed-track counts,
+the track rows (x1, y1, x2, y2, track id, class id; rows past a frame's count zeroed), per-frame detection counts --
+and the ReID embeddings of its final launch group, as DIR/<name>.npy in float64 / float32, 64 MB at most in all
+(an array that does not fit is replaced by a seeded sample of its rows, the row indices beside it).  The inputs
+are a function of the arguments only (seeded scene, engine files written by the build), so two builds can be
+compared output for output at the same arguments.  --steps and --warmup are among them: the tracker carries its
+state from step to step, and a different number of steps before the last one moves a few of its boxes by a pixel.
 """
 import os
 
@@ -75,7 +88,37 @@ def parse(argv=None):
     p.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL over xGMI; gloo for CPU rehearsals)")
     p.add_argument("--gallery-exchange", type=int, default=0, help="configs[4]: all-gather a ReID gallery shard every K frames of stream time (0 = off)")
     p.add_argument("--dry-run", action="store_true", help="no GPU work: rank/affinity/rendezvous/reduction path only (CPU rehearsal of the N > 1 launch)")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true", help="also the side measurements, roofline (HIP events in the timed region) and CPU baseline")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+def live_rows(nt, rows):
+    """Track rows of a step with the rows past each frame's count zeroed (the buffer keeps stale rows there)."""
+    live = np.arange(rows.shape[1])[None, :] < np.minimum(nt, rows.shape[1])[:, None]
+    return np.where(live[..., None], rows, 0)
+
+
+DUMP_BUDGET = 60 << 20      # bytes of array data; with the .npy headers the files stay under 64 MB
+
+
+def write_outputs(dirname, arrays):
+    """arrays: (name, array) pairs, small ones first.  An array larger than what is left of DUMP_BUDGET is replaced by a fixed, seeded
+    sample of its rows (sorted), whose indices are written beside it as <name>_sample_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, a in arrays:
+        if a.nbytes > left:
+            k = int(left // (a[:1].nbytes + 8))
+            idx = np.sort(np.random.default_rng(0).choice(len(a), size=min(k, len(a)), replace=False)).astype(np.float64)
+            np.save(os.path.join(dirname, name + "_sample_rows.npy"), idx)
+            left -= idx.nbytes
+            a = a[idx.astype(np.int64)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def host_cores():
@@ -351,8 +394,13 @@ def main():
     TP = importlib.import_module("ai-camera_amd.pipeline").TrackingPipeline
 
     def trained_path():
+        # the headline's detector: a failure here must stop the run, not swap the workload's weights for the seeded ones
+        if args.model != "n":
+            return None
+        if args.detector == "trained":
+            return ef.ensure_trained_detector(ROOT)
         try:
-            return ef.ensure_trained_detector(ROOT) if args.model == "n" else None
+            return ef.ensure_trained_detector(ROOT)                 # only the --full own-detections leg uses it
         except Exception:
             return None
     if rank == 0:
@@ -408,7 +456,8 @@ def main():
         pipe.upload(0, host_frames)
     if args.warmup > 0:
         run_steps(args.warmup)
-    if not args.no_prof:
+    profile = args.full and not args.no_prof    # the roofline's HIP events: only where the roofline is reported
+    if profile:
         L.call("aic_prof_reset", dev)
         L.call("aic_prof_enable", dev, 1)       # class 0 = conv_igemm only
     pipe.stats(reset=True)
@@ -418,10 +467,16 @@ def main():
     sync_all()
     dt = time.perf_counter() - t0
     n_tracks_total = int(nt.sum()) * args.steps                  # rows of the last pass; every pass is in steady state
+    dump = None
+    if args.dump_outputs and rank == 0:         # copies now: nt / rows / nd are views of buffers the side measurements reuse
+        emb, crops = pipe.group_embeddings()
+        dump = [("track_counts", nt.astype(np.float64)), ("detection_counts", nd.astype(np.float64)),
+                ("track_rows", live_rows(nt, rows).astype(np.float64)),
+                ("reid_crops_per_frame_last_group", crops.astype(np.float64)), ("reid_embeddings_last_group", emb)]
     host = pipe.stats()
     g_frames, g_lat = pipe.group_times()
-    prof = L.prof_read(dev) if not args.no_prof else None
-    if not args.no_prof:
+    prof = L.prof_read(dev) if profile else None
+    if profile:
         L.call("aic_prof_enable", dev, 0)
     exchanges = exchange.stop() if exchange else None
     cnt = pipe.counters()                                        # what the library did, not what the flags asked for
@@ -442,7 +497,7 @@ def main():
 
     # side measurements (rank 0, N = 1): the other span, and the launch-group-size curve with per-frame latency
     side = {}
-    if rank == 0 and world == 1 and not args.no_curve:
+    if rank == 0 and world == 1 and args.full and not args.no_curve:
         try:
             t1 = time.perf_counter()
             if args.resident:
@@ -484,9 +539,9 @@ def main():
     # (the headline's load).  Same clip, same engines, from host memory; filter on the device (default) and on the host beside it.
     own = None
     own_trained = None
-    if rank == 0 and world == 1 and not args.no_own and ypath_trained and args.width == 1280 and args.height == 720:
+    if rank == 0 and world == 1 and args.full and not args.no_own and ypath_trained and args.width == 1280 and args.height == 720:
         own_trained = own_detections_trained(args, L, TP, pipe, ypath_trained, rpath, host_frames, sc, R, frames_per_step, max_persons, dev, fps)
-    if rank == 0 and world == 1 and not args.no_own:
+    if rank == 0 and world == 1 and args.full and not args.no_own:
         try:
             cfg = importlib.import_module("ai-camera_amd.config")
             old_cls = set(cfg.CLASSES_TO_TRACK)
@@ -558,7 +613,7 @@ def main():
             own = {"error": str(e)}
 
     plug = None
-    if rank == 0 and world == 1 and not args.no_plugin:
+    if rank == 0 and world == 1 and args.full and not args.no_plugin:
         try:
             plug = plugin_loop(args, ypath_trained, rpath, sc, dev, own=True) if ypath_trained else plugin_loop(args, ypath, rpath, sc, dev)
         except Exception as e:
@@ -605,7 +660,7 @@ def main():
                     "kernel_ms_per_step": round(busy_ms / args.steps, 3), "kernel_ms_per_step_summed": round(c["ms"] / args.steps, 3),
                     "algorithmic_gflop_per_frame": round(flops_frame / 1e9, 3)}
         cpu = None
-        if world == 1 and args.cpu_frames != 0:
+        if world == 1 and args.full and args.cpu_frames != 0:
             try:
                 cpu = cpu_baseline(args, ypath_headline, rpath)
             except Exception as e:   # the baseline must never hide the GPU number
@@ -645,6 +700,8 @@ def main():
                        "side_error": side.get("error")},
             "roofline": roof, "cpu_baseline": cpu,
         }
+        if dump is not None:
+            write_outputs(args.dump_outputs, dump)
         print(json.dumps(out), flush=True)
     if pinned is True:
         TP.unpin(host_frames)

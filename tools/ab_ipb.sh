@@ -1,5 +1,5 @@
 #!/bin/bash
-B="--no-curve --no-own --no-plugin --cpu-frames 0"
+B="--full --no-curve --no-own --no-plugin --cpu-frames 0"     # --full: the roofline read below
 # images per block of the fused BasicBlock kernel (AICAM_BLK_IPB): headline bench + the layer alone (tools/conv_bench.py, res = 2), two rounds.   gpurun -- bash tools/ab_ipb.sh
 for i in 1 2; do
 for ipb in 16 15 20 12 30; do

@@ -3,7 +3,7 @@
 # ("new") and under other.so ("old") copied over it, interleaved; the in-tree file is restored at the end.  CB="H W CIN COUT K items reps res":
 # tools/conv_bench.py on that shape under each as well.
 cd "$(dirname "$0")/.."
-B="--no-curve --no-own --no-plugin --cpu-frames 0"
+B="--full --no-curve --no-own --no-plugin --cpu-frames 0"     # --full: the roofline read below
 L=ai-camera_amd/libaicam.so
 cp $L /tmp/ab_new_lib.so
 for i in $(seq 1 ${2:-3}); do

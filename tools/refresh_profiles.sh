@@ -8,7 +8,7 @@ R=$PWD
 TAG=${1:-r05}
 O=$R/gpurun_out/refresh_$TAG
 rm -rf $O && mkdir -p $O
-B="--cpu-frames 0 --no-curve --no-own --no-plugin"     # the traces describe the headline workload only
+B="--full --cpu-frames 0 --no-curve --no-own --no-plugin"     # the traces describe the headline workload only (--full: with the roofline's HIP events)
 cd /tmp && export TMPDIR=/tmp
 # the bench command itself (from-host span, default = two streams) under the kernel trace: the UNION of its conv kernels' intervals must agree
 # with the HIP-event figure of the bench line (roofline.kernel_ms_per_step); tools/prof_layers.py prints it
@@ -30,7 +30,7 @@ cp $(ls $T/*_kernel_stats.csv | head -1) $O/kernel_stats.csv
 cp $(ls $T1/*_kernel_stats.csv | head -1) $O/kernel_stats_single_stream.csv
 python tools/pmc_traffic.py $O/fetch $O/write "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), bench.py --steps 1 --warmup 1 --resident with AICAM_NO_TAPER=1 (full 512-frame launch groups only); FETCH_SIZE x2 (gfx950 correction of MI355X_MICROARCH.md)" $TAG > $O/pmc_traffic.txt
 # the bench line last: its roofline.traffic reads the profiles/pmc_traffic.json written just above
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-300
 rm -rf $O/trace $O/trace1 $O/fetch $O/write $O/sqa $O/sqb          # the raw traces stay on the box (tens of MB); the summaries travel back
 for f in bench.json bench_under_rocprof.json bench_single_stream_under_rocprof.json kernel_stats.csv kernel_stats_single_stream.csv kernel_summary.txt conv_layers.txt sq_counters.txt; do cp $O/$f profiles/${TAG}_$f; done
