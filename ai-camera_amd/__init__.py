@@ -14,10 +14,12 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
     if name in _LAZY:
         return _importlib.import_module(f"{__name__}.{name}")
+    if name == "BYTETracker":
+        return _importlib.import_module(f"{__name__}.bytetrack").BYTETracker
     raise AttributeError(name)

@@ -36,6 +36,12 @@ class TrackerParams(C.Structure):
                 ("feature_dim", C.c_int32), ("first_track_id", C.c_int32)]
 
 
+class ByteTrackParams(C.Structure):
+    _fields_ = [("track_thresh", C.c_double), ("low_thresh", C.c_double), ("new_track_thresh", C.c_double),
+                ("match_thresh", C.c_double), ("track_buffer", C.c_int32), ("frame_rate", C.c_int32),
+                ("fuse_score", C.c_int32), ("max_tracks", C.c_int32), ("first_track_id", C.c_int32)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -128,6 +134,13 @@ _SIGS = {
     "aic_prof_reset": (_I, [_I]),
     "aic_prof_read": (_I, [_I, _I, _P, _P, _P, _P]),
     "aic_prof_read_union": (_I, [_I, _I, _P]),
+    "aic_bytetrack_create": (_I, [_I, _P, _P]),
+    "aic_bytetrack_destroy": (_I, [_P]),
+    "aic_bytetrack_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_bytetrack_update_batch": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "aic_bytetrack_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aic_bytetrack_counters": (_I, [_P, _P, _P, _P]),
+    "aic_pipeline_create_bytetrack": (_I, [_P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

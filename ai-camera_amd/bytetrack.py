@@ -1,0 +1,113 @@
+"""ByteTrack (BYTETracker.update of the ByteTrack authors' yolox/tracker/byte_tracker.py) on the device.
+
+No appearance model: one frame costs the detector and a small association.  The recurrence runs in
+csrc/kernels_bytetrack.hip (k frames per launch, the track table resident in HBM); its specification is
+tests/bytetrack_oracle.py, the deliberate changes from upstream are listed in DESIGN.md ("ByteTrack").
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from . import config
+
+
+def bytetrack_params(track_thresh=0.5, track_buffer=30, match_thresh=0.8, mot20=False, frame_rate=30, low_thresh=0.1,
+                     max_tracks=512, first_track_id=1, new_track_thresh=None):
+    """aic_bytetrack_params (ByteTrack's MOT17 defaults); new_track_thresh defaults to track_thresh + 0.1."""
+    return L.ByteTrackParams(track_thresh=float(track_thresh), low_thresh=float(low_thresh),
+                             new_track_thresh=float(track_thresh + 0.1 if new_track_thresh is None else new_track_thresh),
+                             match_thresh=float(match_thresh), track_buffer=int(track_buffer), frame_rate=int(frame_rate),
+                             fuse_score=0 if mot20 else 1, max_tracks=int(max_tracks), first_track_id=int(first_track_id))
+
+
+class BYTETracker:
+    """update(boxes_xyxy, scores, class_ids) -> [(x1, y1, x2, y2, track_id, class_name, conf), ...] as DeepSORT.update, for the
+    activated tracks of the tracked list (ByteTrack's output_stracks).  Association is class-agnostic, as upstream."""
+
+    def __init__(self, track_thresh=0.5, track_buffer=30, match_thresh=0.8, mot20=False, frame_rate=30, low_thresh=0.1, device=0,
+                 max_tracks=512, first_track_id=1):
+        self.params = bytetrack_params(track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh, max_tracks,
+                                       first_track_id)
+        self.max_tracks = max_tracks
+        self._h = C.c_void_p()
+        L.call("aic_bytetrack_create", config.resolve_device(device), C.byref(self.params), C.byref(self._h))
+        self.frame_id = 0
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            L.load().aic_bytetrack_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def option(self, key, value):
+        """"lsap_fast" (0/1), "epoch_frames" (0..16): same results either way."""
+        L.call("aic_bytetrack_option", self._h, key.encode(), int(value))
+
+    def update_batch_arrays(self, frames, cap_rows=None):
+        """frames: list of (boxes_xyxy [n,4], scores [n], class_ids [n]).  Returns per frame (rows [m,6] int32, conf [m] fp32)."""
+        k = len(frames)
+        if k == 0:
+            return []
+        boxes = [np.asarray(b, dtype=np.float32).reshape(-1, 4) for b, _, _ in frames]
+        scores = [np.asarray(s, dtype=np.float32).reshape(-1) for _, s, _ in frames]
+        cids = [np.asarray(c).reshape(-1).astype(np.int32) for _, _, c in frames]
+        counts = np.array([len(b) for b in boxes], dtype=np.int32)
+        for b, s, c in zip(boxes, scores, cids):
+            if not (len(b) == len(s) == len(c)):
+                raise ValueError("boxes, scores and class ids differ in length")
+        cap = int(cap_rows if cap_rows is not None else self.max_tracks or 512)
+        xyxy = np.ascontiguousarray(np.concatenate(boxes) if counts.sum() else np.zeros((0, 4), np.float32))
+        conf = np.ascontiguousarray(np.concatenate(scores) if counts.sum() else np.zeros(0, np.float32))
+        cls = np.ascontiguousarray(np.concatenate(cids) if counts.sum() else np.zeros(0, np.int32))
+        n_out = np.zeros(k, np.int32)
+        out6 = np.zeros((k, cap, 6), np.int32)
+        oconf = np.zeros((k, cap), np.float32)
+        L.call("aic_bytetrack_update_batch", self._h, k, L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), cap, L.ptr(n_out),
+               L.ptr(out6), L.ptr(oconf))
+        self.frame_id += k
+        res = []
+        for f in range(k):
+            m = min(int(n_out[f]), cap)
+            res.append((out6[f, :m].copy(), oconf[f, :m].copy()))
+        return res
+
+    @staticmethod
+    def _tuples(rows, conf):
+        return [(r[0], r[1], r[2], r[3], r[4], config.class_name(r[5]), cf) for r, cf in zip(rows.tolist(), conf.tolist())]
+
+    def update(self, boxes_xyxy, scores, class_ids):
+        """One frame (BYTETracker.update). Empty inputs (np.array([])) are accepted."""
+        rows, conf = self.update_batch_arrays([(boxes_xyxy, scores, class_ids)])[0]
+        return self._tuples(rows, conf)
+
+    def update_batch(self, boxes_xyxy, scores, class_ids):
+        """k frames in one call (per-frame lists of arrays): a list of k update() results."""
+        return [self._tuples(r, c) for r, c in self.update_batch_arrays(list(zip(boxes_xyxy, scores, class_ids)))]
+
+    def counters(self):
+        """Assignment problems since creation: read off as the unique optimum / through the LSAP, and the largest extended side met."""
+        nf, nl, ms = C.c_int64(), C.c_int64(), C.c_int32()
+        L.call("aic_bytetrack_counters", self._h, C.byref(nf), C.byref(nl), C.byref(ms))
+        return dict(n_fast=nf.value, n_lsap=nl.value, max_side=ms.value)
+
+    def export(self):
+        """Live tracks in list order (tracked list, then lost list): dict of arrays + n_tracked (the tracked list's length)."""
+        n, nt = C.c_int32(), C.c_int32()
+        L.call("aic_bytetrack_export", self._h, 0, None, None, None, None, None, None, None, None, None, C.byref(n), C.byref(nt))
+        m = n.value
+        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
+                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
+                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32))
+        L.call("aic_bytetrack_export", self._h, m, *(L.ptr(out[k]) for k in ("track_id", "state", "is_activated", "start_frame",
+                                                                           "end_frame", "cls", "score", "mean", "cov")),
+               C.byref(n), C.byref(nt))
+        out["n_tracked"] = nt.value
+        return out

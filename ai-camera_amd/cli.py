@@ -47,7 +47,10 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--no_save", action="store_true")
     p.add_argument("--yolo_engine", type=str, default=str(config.YOLO_ENGINE_PATH))
     p.add_argument("--reid_engine", type=str, default=str(config.REID_ENGINE_PATH))
-    p.add_argument("--conf_thresh", type=float, default=config.YOLO_CONF_THRESHOLD)
+    p.add_argument("--conf_thresh", type=float, default=None,
+                   help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1)")
+    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack"),
+                   help="bytetrack: no ReID model, ByteTrack's association on the device")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
@@ -142,6 +145,16 @@ class FrameWriter:
             json.dump(dict(self.meta, frames=self.frames), open(str(self.path) + ".json", "w"))
 
 
+class _FrameFree:
+    """The loop's tracker call with ByteTrack: update(boxes, scores, class_ids, frame) -- the frame is not needed (no ReID)."""
+
+    def __init__(self, tracker):
+        self.tracker = tracker
+
+    def update(self, boxes, scores, class_ids, frame):
+        return self.tracker.update(boxes, scores, class_ids)
+
+
 def main(argv=None):
     args = parse_arguments(argv)
     cv2 = probe_cv2()
@@ -149,6 +162,9 @@ def main(argv=None):
         print("OpenCV (cv2) is not importable: video files / webcams / --show_display are unavailable; codec-free sources and raw outputs are used.")
     print("Initializing YOLOv8 Detector...")
     name, frames, size = frame_source(args.input, args.webcam_id, cv2)
+    bytetrack = args.tracker == "bytetrack"
+    if args.conf_thresh is None:             # ByteTrack's bands need the detector's low band (low_thresh = 0.1)
+        args.conf_thresh = 0.1 if bytetrack else config.YOLO_CONF_THRESHOLD
     pipe = detector = tracker = None
     try:
         if args.batch > 1:
@@ -157,15 +173,24 @@ def main(argv=None):
             # clipped (the per-frame path and the reference, deepsort_tracker.py:126-141, emit every confirmed track)
             from .hip_engine import HipEngine
             dev_id = config.resolve_device(args.device)
-            reid = HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
+            reid = None if bytetrack else HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
             pipe = TrackingPipeline(args.yolo_engine, reid, (size[1], size[0]), batch=args.batch, ring_frames=args.batch,
-                                    max_persons=512, max_tracks=512, device=dev_id, dtype=args.dtype, conf_thresh=args.conf_thresh)
+                                    max_persons=512, max_tracks=512, device=dev_id, dtype=args.dtype, conf_thresh=args.conf_thresh,
+                                    tracker=args.tracker)
         else:
             detector = YOLODetector(engine_path=args.yolo_engine, conf_threshold=args.conf_thresh, device=args.device, dtype=args.dtype)
     except Exception as e:   # aicamera_tracker.py:94-97
         print(f"Error initializing YOLO Detector: {e}")
         return 1
-    if pipe is None:
+    if pipe is None and bytetrack:
+        print("Initializing ByteTrack Tracker...")
+        try:
+            from .bytetrack import BYTETracker
+            tracker = _FrameFree(BYTETracker(device=args.device))
+        except Exception as e:
+            print(f"Error initializing ByteTrack Tracker: {e}")
+            return 1
+    elif pipe is None:
         print("Initializing DeepSORT Tracker...")
         try:
             tracker = DeepSORT(reid_model_path=args.reid_engine, device=args.device, dtype=args.dtype)
@@ -216,7 +241,7 @@ def main(argv=None):
             frame_idx += 1
             display_fps = frame_idx / total if total > 0 else 0.0
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
-                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + DeepSORT", f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
+                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
                 if args.show_display and cv2 is not None:
                     cv2.imshow("AICamera Tracking", vis)
                     if cv2.waitKey(1) & 0xFF == ord("q"):

@@ -14,6 +14,7 @@
 // src/tracker/deepsort_tracker.py:88-101).
 #include "engine.hpp"
 #include "tracker.hpp"
+#include "bytetrack_host.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -181,21 +182,35 @@ struct Pipeline {
     int plan_slot = 0, copies_issued = 0;
     int host_slot0 = 0;
 
-    Pipeline(Model* y, Model* r, const aic_pipeline_params& p)
-        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, p.tracker)), trk(trk_handle->t) {
-        AIC_REQUIRE(y->kind == KIND_YOLO && r->kind == KIND_REID, AIC_ERR_INVALID, "pipeline needs a YOLO and a ReID engine");
-        AIC_REQUIRE(y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
+    // ByteTrack (aic_pipeline_create_bytetrack): no ReID model (reid == nullptr); crop, ReID and the embedding copies are not issued and
+    // the association is the ByteTrack epoch kernel on the tracker stream.  The DeepSORT tracker object below then exists but is never run.
+    std::unique_ptr<ByteTracker> bt;
+
+    static aic_tracker_params tracker_params(const aic_pipeline_params& p, bool bytetrack) {
+        if (!bytetrack) return p.tracker;
+        aic_tracker_params t{};                                   // unused: small, fixed (the caller's p.tracker is ignored)
+        t.max_cosine_distance = 0.2, t.max_iou_distance = 0.7, t.nn_budget = 1, t.max_age = 1, t.n_init = 1, t.max_tracks = 1;
+        t.feature_dim = 0, t.first_track_id = 1;
+        return t;
+    }
+
+    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1)
+        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp != nullptr))), trk(trk_handle->t) {
+        AIC_REQUIRE(y->kind == KIND_YOLO && (btp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
+                    btp ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine" : "pipeline needs a YOLO and a ReID engine");
+        AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
         AIC_REQUIRE(p.batch <= y->max_items, AIC_ERR_CAPACITY, "batch exceeds the YOLO engine's max_items");
         AIC_REQUIRE(p.max_det > 0 && p.max_det <= y->max_det_cap, AIC_ERR_CAPACITY, "max_det out of range");
         dev->use();
+        if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
         frame_bytes = (size_t)p.frame_h * p.frame_w * 3;
         ring.alloc(frame_bytes * p.ring_frames + 64);     // + slack: the crop kernel's 12-byte tap loads may run past the last frame's last byte
-        dim = r->out_dim;
+        dim = r ? r->out_dim : 0;
         inj_count.assign(p.ring_frames, 0);
         inj_boxes.assign((size_t)p.ring_frames * p.max_persons * 4, 0.f);
         inj_conf.assign((size_t)p.ring_frames * p.max_persons, 0.f);
@@ -238,7 +253,7 @@ struct Pipeline {
         fd.n = 0;
         fd.tlwh.clear(), fd.xyxy.clear(), fd.conf.clear(), fd.cls.clear();
         for (int i = 0; i < n; ++i) {
-            if (!(conf[i] >= prm.min_confidence) || !tracked_class(cls[i])) continue;
+            if ((!bt && !(conf[i] >= prm.min_confidence)) || !tracked_class(cls[i])) continue;   // ByteTrack: its bands filter the scores
             const float* b = boxes_xyxy + (size_t)i * 4;
             fd.tlwh.insert(fd.tlwh.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});   // deepsort_tracker.py:185-186
             fd.xyxy.insert(fd.xyxy.end(), b, b + 4);                                    // crops use the xyxy box (:148)
@@ -279,9 +294,11 @@ struct Pipeline {
         if (lane[1].yolo) return;
         dev->use();
         const int yi = std::min(yolo->max_items, std::max(dual_max, 1));
-        const int ri = std::min(reid->max_items, std::max(yi * prm.max_persons, 64));
         yolo2.reset(new Model(*dev, yolo->blob_copy->data(), yolo->blob_copy->size(), yolo->dtype, yi));
-        reid2.reset(new Model(*dev, reid->blob_copy->data(), reid->blob_copy->size(), reid->dtype, ri));
+        if (reid) {                                               // (ByteTrack: no ReID model, no second copy of it)
+            const int ri = std::min(reid->max_items, std::max(yi * prm.max_persons, 64));
+            reid2.reset(new Model(*dev, reid->blob_copy->data(), reid->blob_copy->size(), reid->dtype, ri));
+        }
         Lane l{yolo2.get(), reid2.get(), nullptr, nullptr, nullptr};
         HIP_CHECK(hipStreamCreateWithFlags(&l.s_main, hipStreamNonBlocking));
         HIP_CHECK(hipStreamCreateWithFlags(&l.s_det, hipStreamNonBlocking));
@@ -300,7 +317,7 @@ struct Pipeline {
         if (host_frames) {   // the reference's span: H2D of the group's frames on the copy stream, under the previous groups' compute
             issue_copies(group_index + copy_ahead);
             HIP_CHECK(hipStreamWaitEvent(s, ev_copy[group_index % NCOPY], 0));
-            if (split_streams) HIP_CHECK(hipStreamWaitEvent(c.ln->s_reid, ev_copy[group_index % NCOPY], 0));
+            if (split_streams && reid) HIP_CHECK(hipStreamWaitEvent(c.ln->s_reid, ev_copy[group_index % NCOPY], 0));
         }
         const uint8_t* f0 = ring.p + (size_t)slot * frame_bytes;
         if (pipe_times) HIP_CHECK(hipEventRecord(c.t_begin, s));
@@ -323,7 +340,7 @@ struct Pipeline {
         // consumer thread, that mode's critical thread), so the stream-ordered filter only saves a round trip where the association stays
         // on the device too.  The choice reads state the consumer wrote before it released this context: the same frames always take the
         // same path.  dev_filter 2: always on the device.
-        if (!prm.inject && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16 && getenv("AICAM_NO_FUSE_CROP") == nullptr) {
+        if (!prm.inject && reid && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16 && getenv("AICAM_NO_FUSE_CROP") == nullptr) {
             c.ln->reid->in_pix4 = c.ln->reid->input_pix4_ok();
             c.filt_dev = c.ln->reid->in_pix4;
         }
@@ -367,7 +384,7 @@ struct Pipeline {
         }
         int n_max = 0;
         for (int f = 0; f < frames; ++f) n_max = std::max(n_max, c.dets[f].n);
-        const bool dev_mode = use_device(n_max, c.tracks_after);
+        const bool dev_mode = bt || use_device(n_max, c.tracks_after);   // ByteTrack: always the epoch kernel's detection arrays
         c.dev_mode = dev_mode;
         if (dev_mode) {   // what the epoch kernels read: frame_n[frames] | frame_d0[frames] | tlwh[nc,4] | conf[nc] | cls[nc]
             c.m_n = 0, c.m_d0 = (size_t)frames * 4, c.m_tlwh = (((size_t)frames * 8 + 15) / 16) * 16;
@@ -390,8 +407,8 @@ struct Pipeline {
         }
         // crop + ReID on their own stream: in inject mode they do not depend on the detector, and their CU-filling
         // launches backfill the CUs that YOLO's thin layers (50-400 blocks per launch) leave idle
-        hipStream_t sr = split_streams ? c.ln->s_reid : s;
-        if (nc) {
+        hipStream_t sr = split_streams && reid ? c.ln->s_reid : s;
+        if (nc && reid) {                                          // (ByteTrack: no crops, no ReID, no embeddings)
             HIP_CHECK(hipMemcpyAsync(c.d_boxes.p, c.h_boxes.p, (size_t)nc * 16, hipMemcpyHostToDevice, sr));
             HIP_CHECK(hipMemcpyAsync(c.d_frame_of.p, c.h_frame_of.p, (size_t)nc * 4, hipMemcpyHostToDevice, sr));
             // the engine's host-side launch state (in_pix4, crop_src, n_items_dev) is shared with the consumer thread, which may be running
@@ -422,7 +439,7 @@ struct Pipeline {
             HIP_CHECK(hipMemcpyAsync(c.h_valid.p, c.d_valid.p, (size_t)nc * 4, hipMemcpyDeviceToHost, sr));
         }
         if (dev_mode) HIP_CHECK(hipMemcpyAsync(c.d_meta.p, c.h_meta.p, c.m_bytes, hipMemcpyHostToDevice, sr));
-        if (split_streams) {
+        if (split_streams && reid) {
             HIP_CHECK(hipEventRecord(c.ev_reid, sr));
             HIP_CHECK(hipStreamWaitEvent(s, c.ev_reid, 0));
         }
@@ -696,6 +713,56 @@ struct Pipeline {
         n_frames_done += c.frames;
     }
 
+    // Stage B of a ByteTrack pipeline: the group's frames through the ByteTrack epochs on the tracker stream (no embeddings, no read-back
+    // of them); the host picks up the group's output rows at the end.
+    void stage_b_bytetrack(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
+                           float* det_boxes, float* det_scores, int32_t* det_labels) {
+        const double t0 = now();
+        n_assoc_dev += c.frames;
+        hipStream_t s = dev->s_trk;
+        const int mp = prm.max_persons;
+        const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
+        const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
+        if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
+        HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's detection arrays are in HBM
+        const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
+        for (int f = 0; f < c.frames; ++f)
+            AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "ByteTrack: more than 512 detections in one frame");
+        EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
+                       reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
+                       reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), nullptr, nullptr, nullptr};
+        EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
+                     mp, nullptr, nullptr, 0};
+        bt->run_epochs(dets, c.frames, out, s);
+        HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
+        const double t1 = now();
+        t_track += t1 - t0;
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipEventSynchronize(c.ev_det));              // the detector's outputs of the group are on the host
+        bt->check_epochs();
+        const double t2 = now();
+        t_wait += t2 - t1;
+        const int* on = reinterpret_cast<const int*>(c.h_out.p);
+        const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
+        const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
+        const size_t md = prm.max_det;
+        for (int f = 0; f < c.frames; ++f) {
+            const int o = out_base + f;
+            const int k = std::min(on[f], mp);
+            if (n_tracks) n_tracks[o] = on[f];
+            if (on[f] > mp) n_rows_clipped += 1;
+            if (tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, tracks6 + (size_t)o * mp * 6);
+            if (track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, track_conf + (size_t)o * mp);
+            if (n_dets) n_dets[o] = c.h_numdets.p[f];
+            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
+            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
+            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
+        }
+        last_chunk = (int)(&c - &ck[0]);
+        t_track += now() - t2;
+        n_frames_done += c.frames;
+    }
+
     // passes > 1: the same ring range is walked `passes` times back to back as ONE continuous stream (outputs of a
     // later pass overwrite the rows of the earlier one): only the very last group of the call has an un-overlapped tail.
     void run(int slot, int count, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets, float* det_boxes,
@@ -705,7 +772,7 @@ struct Pipeline {
         dev->use();
         if (count <= 0) return;
         // the association epoch kernel holds one CU while the next group's convs run: persistent conv grids leave it free
-        set_conv_cu_budget(dev_assoc && trk.dev_capable() ? dev->n_cu - 1 : dev->n_cu);
+        set_conv_cu_budget(bt || (dev_assoc && trk.dev_capable()) ? dev->n_cu - 1 : dev->n_cu);
         tracks_seen = trk.on_device ? tracks_seen.load() : (int)trk.tracks.size();
         for (auto& c : ck) c.tracks_after = tracks_seen;
         // Launch groups: full batches, then the last batch tapered (1/2, 1/4, ... down to 16 frames): stage B of the
@@ -736,10 +803,10 @@ struct Pipeline {
         // lane of every group: odd groups that are small enough take lane 1 (their context's previous group has been released, and the
         // other context's group -- on lane 0 or busy elsewhere -- does not share a buffer or a stream with them)
         std::vector<int> glane(nchunks, 0);
-        if (dual_max > 0 && yolo->blob_copy && reid->blob_copy) {
+        if (dual_max > 0 && yolo->blob_copy && (!reid || reid->blob_copy)) {
             bool any = false;
             for (int k = 0; k < nchunks; ++k)
-                if ((k & 1) && glen[k] <= std::min(dual_max, yolo->max_items) && glen[k] * prm.max_persons <= reid->max_items) { glane[k] = 1; any = true; }
+                if ((k & 1) && glen[k] <= std::min(dual_max, yolo->max_items) && (!reid || glen[k] * prm.max_persons <= reid->max_items)) { glane[k] = 1; any = true; }
             if (any) {
                 try {
                     ensure_lane1();
@@ -798,7 +865,8 @@ struct Pipeline {
                 final_group = k == nchunks - 1;
                 if (ck[k % nck].filt_dev) prepare_b(ck[k % nck]);
                 ck[k % nck].prev_dev_mode = ck[k % nck].dev_mode;
-                if (ck[k % nck].dev_mode) {
+                if (bt) stage_b_bytetrack(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
+                else if (ck[k % nck].dev_mode) {
                     trk.dev_assoc = true;
                     stage_b_device(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
                 } else {
@@ -830,7 +898,10 @@ struct Pipeline {
 
 using namespace aic;
 
-struct aic_pipeline { Pipeline p; aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q) : p(y, r, q) {} };
+struct aic_pipeline {
+    Pipeline p;
+    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1) : p(y, r, q, b, first_id) {}
+};
 
 extern "C" {
 
@@ -838,6 +909,15 @@ int aic_pipeline_create(aic_model* yolo, aic_model* reid, const aic_pipeline_par
     return guarded([&] {
         AIC_REQUIRE(yolo && reid && p && out, AIC_ERR_INVALID, "NULL argument");
         *out = new aic_pipeline(&yolo->m, &reid->m, *p);
+    });
+}
+
+int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p, const aic_bytetrack_params* bp, aic_pipeline** out) {
+    return guarded([&] {
+        AIC_REQUIRE(yolo && p && bp && out, AIC_ERR_INVALID, "NULL argument");
+        int first = 1;
+        const BtParams b = bytetrack_params(*bp, &first);
+        *out = new aic_pipeline(&yolo->m, nullptr, *p, &b, first);
     });
 }
 
@@ -944,6 +1024,7 @@ int aic_host_unregister(void* ptr) {
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out) {
     return guarded([&] {
         AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline has no DeepSORT tracker");
         *out = p->p.trk_handle.get();   // owned by the pipeline: do not destroy
     });
 }
@@ -962,6 +1043,7 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
 int aic_pipeline_exchange_enable(aic_pipeline* p, float* shard0_dev, float* shard1_dev, int t_max, int every_groups) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "the gallery exchange needs DeepSORT's appearance galleries (this pipeline runs ByteTrack)");
         Pipeline& q = p->p;
         q.dev->use();
         std::lock_guard<std::mutex> lk(q.x_mu);
@@ -1052,6 +1134,8 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
             if (!value) p->p.head_ramp = false;
         }
         else if (k == "split_streams") p->p.split_streams = value != 0;
+        else if (p->p.bt && (k == "device_assoc" || k == "device_assoc_limit" || k == "device_filter"))
+            AIC_REQUIRE(false, AIC_ERR_INVALID, "option " + k + " applies to DeepSORT pipelines only (this one runs ByteTrack)");
         else if (k == "device_assoc") {
             AIC_REQUIRE(value >= 0 && value <= 2, AIC_ERR_INVALID, "device_assoc: 0 host, 1 auto, 2 always on the device");
             p->p.dev_assoc = value;
@@ -1120,6 +1204,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
                                   int32_t* n_rows, int32_t* n_frames, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n_rows && n_frames && dim, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline computes no embeddings");
         Pipeline& q = p->p;
         *dim = q.dim, *n_rows = 0, *n_frames = 0;
         if (q.last_chunk < 0) return;
@@ -1140,6 +1225,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
 int aic_pipeline_last_embeddings(aic_pipeline* p, float* emb, int cap_rows, int32_t* n, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n && dim, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline computes no embeddings");
         *n = p->p.last_emb_n, *dim = p->p.dim;
         AIC_REQUIRE(p->p.last_emb_n <= cap_rows, AIC_ERR_CAPACITY, "embedding capacity too small");
         if (emb) std::copy(p->p.last_emb.begin(), p->p.last_emb.end(), emb);

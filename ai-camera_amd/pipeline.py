@@ -15,20 +15,45 @@ from .hip_engine import HipEngine
 
 class TrackingPipeline:
     def __init__(self, yolo_engine, reid_engine, frame_hw, batch=8, ring_frames=None, max_persons=32, device=0,
-                 dtype="fp16", conf_thresh=config.YOLO_CONF_THRESHOLD, iou_thresh=config.YOLO_NMS_THRESHOLD,
+                 dtype="fp16", conf_thresh=None, iou_thresh=config.YOLO_NMS_THRESHOLD,
                  max_det=config.YOLO_MAX_DET, min_confidence=config.DEEPSORT_MIN_CONFIDENCE, inject=False,
                  max_cosine_distance=config.DEEPSORT_MAX_DIST, nn_budget=config.DEEPSORT_NN_BUDGET,
                  max_iou_distance=config.DEEPSORT_MAX_IOU_DISTANCE, max_age=config.DEEPSORT_MAX_AGE,
-                 n_init=config.DEEPSORT_N_INIT, max_tracks=512):
+                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", **bytetrack_params):
+        """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
+        not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
+        conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band."""
+        if tracker not in ("deepsort", "bytetrack"):
+            raise ValueError(f"tracker must be 'deepsort' or 'bytetrack', not {tracker!r}")
+        if tracker == "deepsort" and bytetrack_params:
+            raise TypeError(f"unexpected arguments for a DeepSORT pipeline: {sorted(bytetrack_params)}")
+        self.tracker_kind = tracker
         self.frame_h, self.frame_w = int(frame_hw[0]), int(frame_hw[1])
         self.batch = int(batch)
         self.ring_frames = int(ring_frames or 4 * batch)
         self.max_persons, self.max_det = int(max_persons), int(max_det)
         self.yolo = yolo_engine if isinstance(yolo_engine, HipEngine) else HipEngine(
             yolo_engine, device=device, dtype=dtype, max_items=self.batch, warm_up=False)
+        lo, hi = config.track_class_mask()
+        if tracker == "bytetrack":
+            from .bytetrack import bytetrack_params as _btp
+            self.reid = None
+            self.bytetrack_params = _btp(max_tracks=max_tracks, **bytetrack_params)
+            if conf_thresh is None:
+                conf_thresh = self.bytetrack_params.low_thresh
+            tp = L.TrackerParams(0.2, 0.7, 1, 1, 1, 1, 0, 1)          # ignored by aic_pipeline_create_bytetrack
+            self.params = L.PipelineParams(self.frame_h, self.frame_w, self.batch, self.ring_frames, self.max_persons,
+                                           float(conf_thresh), float(iou_thresh), self.max_det, 0.0,
+                                           int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
+            self._h = C.c_void_p()
+            L.call("aic_pipeline_create_bytetrack", self.yolo._h, C.byref(self.params), C.byref(self.bytetrack_params),
+                   C.byref(self._h))
+            self.tracker_core = None
+            return
+        if conf_thresh is None:
+            conf_thresh = config.YOLO_CONF_THRESHOLD
         self.reid = reid_engine if isinstance(reid_engine, HipEngine) else HipEngine(
             reid_engine, device=device, dtype=dtype, max_items=self.batch * self.max_persons, warm_up=False)
-        lo, hi = config.track_class_mask()
         tp = L.TrackerParams(float(max_cosine_distance), float(max_iou_distance), int(nn_budget or 0), int(max_age),
                              int(n_init), int(max_tracks), int(self.reid.out_dim), 1)
         self.params = L.PipelineParams(self.frame_h, self.frame_w, self.batch, self.ring_frames, self.max_persons,

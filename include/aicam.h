@@ -51,6 +51,7 @@ extern "C" {
 typedef struct aic_model aic_model;       /* one engine file resident on one GPU          */
 typedef struct aic_tracker aic_tracker;   /* DeepSORT core state of one video stream      */
 typedef struct aic_pipeline aic_pipeline; /* detector + ReID + tracker over resident frames */
+typedef struct aic_bytetrack aic_bytetrack; /* ByteTrack state of one video stream          */
 
 /* ------------------------------------------------------------------ library / device */
 const char* aic_last_error(void);
@@ -252,6 +253,45 @@ int aic_tracker_last_matches(aic_tracker* t, int32_t* track_id, int32_t* det, in
 int aic_tracker_last_costs(aic_tracker* t, float* app, float* maha, float* iou, int cap, int32_t* t_n,
                            int32_t* d_n);
 
+/* ------------------------------------------------------------------ ByteTrack
+ * BYTETracker.update() of the ByteTrack authors (yolox/tracker/byte_tracker.py, matching.py) on the device, k frames per launch
+ * (csrc/kernels_bytetrack.hip; specification: tests/bytetrack_oracle.py, deviations: DESIGN.md "ByteTrack").  No appearance model.
+ * Defaults are ByteTrack's MOT17 settings; every threshold is rounded to fp32 once. */
+typedef struct aic_bytetrack_params {
+    double track_thresh;     /* 0.5: high band s > track_thresh                                          */
+    double low_thresh;       /* 0.1: second band low_thresh < s < track_thresh                            */
+    double new_track_thresh; /* a new track needs s >= this; 0 -> track_thresh + 0.1                      */
+    double match_thresh;     /* 0.8: first association                                                    */
+    int32_t track_buffer;    /* 30                                                                        */
+    int32_t frame_rate;      /* 30: max_time_lost = int(frame_rate / 30 * track_buffer)                   */
+    int32_t fuse_score;      /* 1 (= not mot20): IoU distance fused with the detection score               */
+    int32_t max_tracks;      /* live tracks (0 -> 512, at most 512)                                       */
+    int32_t first_track_id;  /* 1: ids are counted per tracker                                            */
+} aic_bytetrack_params;
+
+/* AIC_ERR_INVALID for a threshold outside (0, 1], low_thresh >= track_thresh, max_tracks over 512, ... (checked before the device). */
+int aic_bytetrack_create(int device, const aic_bytetrack_params* p, aic_bytetrack** out);
+int aic_bytetrack_destroy(aic_bytetrack* t);
+/* "lsap_fast" = 0: every assignment problem goes through the wave LSAP (default 1: a unique optimum is read off the costs);
+ * "epoch_frames" = 1..16: frames per epoch launch (0 = default 16).  Same results either way. */
+int aic_bytetrack_option(aic_bytetrack* t, const char* key, int value);
+/* k consecutive frames, each one BYTETracker.update(): counts[k]; the rows of all frames concatenated: boxes_xyxy[sum,4], conf[sum],
+ * class id[sum].  Per frame (any may be NULL): n_out[k] output tracks (the TRUE count), out6[k,cap_rows,6] = {x1,y1,x2,y2
+ * (round-half-even ints), track_id, class_id} + out_conf[k,cap_rows] (the track's score), as aic_tracker_update_batch.
+ * AIC_ERR_CAPACITY when a frame has more than 512 detections, the live tracks outgrow max_tracks, or an assignment problem's extended
+ * side (tracks + detections) exceeds 512; nothing is dropped, and the tracker refuses further updates after such an error. */
+int aic_bytetrack_update_batch(aic_bytetrack* t, int k, const int32_t* counts, const float* boxes_xyxy, const float* conf,
+                               const int32_t* cls, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf);
+/* Live tracks in list order (the tracked list, then the lost list): state 1 Tracked / 2 Lost, start / end frame (end = the last
+ * frame the track was updated), mean[n,8], cov[n,8,8].  n_tracks = all live tracks, n_tracked = the length of the tracked list; only the
+ * first `cap` are stored.  Any pointer may be NULL. */
+/* Assignment problems since creation settled by the unique-optimum check / by the wave LSAP, and the largest extended side met. */
+int aic_bytetrack_counters(aic_bytetrack* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side);
+/* After an update failed (AIC_ERR_CAPACITY) the tracker has no consistent state: export fails with AIC_ERR_INVALID. */
+int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* state, int32_t* is_activated, int32_t* start_frame,
+                         int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* n_tracks,
+                         int32_t* n_tracked);
+
 /* ------------------------------------------------------------------ end-to-end pipeline
  * The loop body of src/aicamera_tracker.py:169-207 (detect + track, the reference's own FPS
  * span) over frames that are already resident in HBM, batched: detection and ReID of
@@ -274,6 +314,14 @@ typedef struct aic_pipeline_params {
 
 int aic_pipeline_create(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p,
                         aic_pipeline** out);
+/* A detector-only pipeline with ByteTrack as its tracker (no ReID engine): launch groups run upload -> letterbox -> detector -> NMS ->
+ * class-mask filter -> ByteTrack epochs on the tracker stream; crop, ReID and embedding copies are not issued.  inject = 1 feeds the
+ * planted boxes, inject = 0 the detector's detections filtered by track_class_mask only (min_confidence and p->tracker are ignored: the
+ * ByteTrack bands filter the scores, so conf_thresh should be at most low_thresh).  run / run_passes / run_from_host(_passes) and the
+ * per-frame outputs behave as for DeepSORT.  aic_pipeline_tracker, the embedding read-backs, the gallery exchange and the options
+ * "device_assoc", "device_assoc_limit", "device_filter" fail with AIC_ERR_INVALID on such a pipeline. */
+int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p, const aic_bytetrack_params* bp,
+                                  aic_pipeline** out);
 int aic_pipeline_destroy(aic_pipeline* p);
 /* Copy `count` u8 BGR frames into ring slots [slot, slot+count). */
 int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames_bgr, int count);
