@@ -12,7 +12,7 @@ namespace aic {
 
 // CUs the persistent (one-block-per-CU) conv kernels size their grids for: all of them, minus the one the association epoch
 // kernel occupies for ~1 ms at a time while the tracker runs on the device (a 256th persistent block would otherwise sit in
-// the queue until that CU or another block's whole share of the images is done).  AICAM_CONV_CUS overrides.
+// the queue until that CU or another block's whole share of the images is done).
 int conv_cu_budget();
 void set_conv_cu_budget(int cus);
 
@@ -104,12 +104,8 @@ __device__ __forceinline__ void mma_tiles_mid(floatx4 (&mid)[MT][NT], const floa
 // The TOP level was tried in double as well (two registers per output, tiles of at most 8 MFMA tiles): the same statistics -- YOLOv8m boxes
 // against the fp64 evaluation, 33 600 coordinates: rms 5.3e-5 px, 99.9th percentile 5.2e-4, one or two coordinates above 1e-3 (max 1.05e-3 /
 // 1.48e-3: which anchor it is changes with every rounding pattern) -- so what is left is the fp32 rounding of 83 layers of activations, not
-// the accumulation.  fp32 it stays (-DAICAM_F32_TOP_F64: the double form, A/B).
-#ifdef AICAM_F32_TOP_F64
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-#else
+// the accumulation.  fp32 it stays.
 typedef float doublex4 __attribute__((ext_vector_type(4)));
-#endif
 template <int MT, int NT>
 __device__ __forceinline__ void flush_mid(doublex4 (&accd)[MT][NT], floatx4 (&mid)[MT][NT]) {
 #pragma unroll
@@ -138,9 +134,6 @@ __device__ __forceinline__ void fast_divmod(int m, int d, float inv, int& q, int
 
 template <int ACT> __device__ __forceinline__ float act_fast(float v) {
     if constexpr (ACT == 1) {   // SiLU = v * sigmoid(v); v_exp_f32 + v_rcp_f32 (<= 1 ulp each)
-#ifdef AICAM_SILU_AS_RELU          // SIZING build only (VERDICT r4 #2c: what would a free activation be worth?) -- wrong results by design
-        return fmaxf(v, 0.0f);
-#endif
         return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
     } else if constexpr (ACT == 2) {
         return fmaxf(v, 0.0f);
@@ -344,12 +337,10 @@ __device__ __forceinline__ void epilogue_wide_phased(const ConvArgs& a, floatx4 
 // thin 1x1 layers ran 7 - 30 % slower: profiles/r03, first refresh).
 template <typename T, int MT, int NT, int ACT, int RES, bool F32OUT, bool PHASED = false>
 __device__ __forceinline__ void epilogue_wide(const ConvArgs& a, floatx4 (&acc)[MT][NT], const int (&mrow)[MT], int n_base, int q) {
-#ifndef AICAM_EPI_SERIAL                                   // (-DAICAM_EPI_SERIAL: the tile-by-tile form everywhere, A/B builds)
     if constexpr (PHASED && sizeof(T) == 2 && !F32OUT) {
         epilogue_wide_phased<MT, NT, ACT, RES>(a, acc, mrow, n_base, q);
         return;
     }
-#endif
     constexpr int NP = NT / 2;
     const float* __restrict__ bias = a.bias;
     const T* __restrict__ rg = reinterpret_cast<const T*>(a.res);
@@ -644,7 +635,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 // Workgroups go to the 8 XCDs round-robin (block b -> XCD b % 8), each with its own L2.  Tiles that are neighbours in the
 // image share halo rows and weights: this bijection gives XCD x one contiguous run of tiles, so a halo fetched by one block is an
-// L2 hit for the next instead of a second HBM / Infinity-Cache read through another XCD.  (g_xcd_map: AICAM_NO_XCD_MAP=1 -> identity)
+// L2 hit for the next instead of a second HBM / Infinity-Cache read through another XCD.  (on = 0: identity)
 __device__ __forceinline__ int xcd_tile(int b, int nb, int on) {
     if (!on) return b;
     const int x = b & 7, base = nb >> 3, rem = nb & 7;
@@ -666,10 +657,6 @@ __device__ __forceinline__ bool xcd_tile_xy_live(int on, int nbx_live, int& bx, 
     const int t = xcd_tile(lin, nlive, on);
     by = t / nbx_live, bx = t - by * nbx_live;
     return true;
-}
-inline int xcd_map_on() {
-    static const int v = getenv("AICAM_NO_XCD_MAP") == nullptr;
-    return v;
 }
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
@@ -717,11 +704,6 @@ __device__ __forceinline__ int lane_here() {
     return l;
 }
 
-
-inline int conv_impl() {   // AICAM_CONV=v1 selects the register-staged kernel (A/B and fallback)
-    static int v = [] { const char* e = getenv("AICAM_CONV"); return (e && e[0] == 'v' && e[1] == '1') ? 1 : 2; }();
-    return v;
-}
 
 // ---- host entry points of the other conv units; each returns false when the layer is not one of its shapes
 bool conv_try_pp_patch(int dtype, const ConvArgs& a, hipStream_t s);   // kernels_conv_pp.hip: v5 ping-pong patch (3x3/s1, Cout 128 / 256k)

@@ -192,7 +192,7 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
     // rounding of the branch: not bit-identical to the unfolded graph, 8e-5 from it and as far from the fp32 oracle as it is
     // (tests/test_gpu_nets.py::test_downsample_branch_folded_into_last_conv).
     // AICAM_NO_DS_FOLD=1: off.
-    if (dtype == AIC_F16 && !getenv("AICAM_NO_DS_FOLD") && !getenv("AICAM_NO_FUSE")) {
+    if (dtype == AIC_F16 && !getenv("AICAM_NO_DS_FOLD")) {
         for (size_t j = 0; j < ops.size(); ++j) {
             int* c = ops[j].v;
             if (c[0] != OP_CONV || c[14] != 1 || ops[j].fuse || c[15] >= nw || c[13] != 0 || c[16] != 0) continue;
@@ -235,7 +235,7 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
     // (YOLOv8's neck: up(P5) | P4 -> 12.c2f.cv1, up(12) | P3 -> 15.c2f.cv1), into that conv: it reads those channels from the
     // half-resolution tensor at (y >> 1, x >> 1) (ConvArgs::xs).  Same values in the same K order: bit-identical
     // (tests/test_gpu_nets.py::test_upsample_folded_into_its_reader).  AICAM_NO_UP_FOLD=1: off.
-    if (!getenv("AICAM_NO_UP_FOLD") && !getenv("AICAM_NO_FUSE")) {
+    if (!getenv("AICAM_NO_UP_FOLD")) {
         auto overlap = [](int a0, int an, int b0, int bn) { return a0 < b0 + bn && b0 < a0 + an; };
         for (size_t i = 0; i < ops.size(); ++i) {
             const int* u = ops[i].v;
@@ -280,7 +280,7 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
     // channels are the two sets side by side in one new buffer; their readers take channel slices of it.  The map is read once
     // instead of twice and the GEMM is 144 wide instead of 64 and 80 (levels with maps up to 40 x 40, see below).  Per output channel nothing changes (same K order, same
     // epilogue): the head is bit-identical (tests/test_gpu_nets.py::test_merged_detect_branch_heads).  AICAM_NO_MERGE=1: off.
-    if (dtype == AIC_F16 && !getenv("AICAM_NO_MERGE") && !getenv("AICAM_NO_FUSE")) {
+    if (dtype == AIC_F16 && !getenv("AICAM_NO_MERGE")) {
         for (size_t i = 0; i < ops.size(); ++i) {
             int* c = ops[i].v;
             if (c[0] != OP_CONV || c[14] != 0 || ops[i].fuse || c[15] >= nw) continue;
@@ -338,7 +338,7 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
         }
     }
     // ---- fusion: conv3x3/1 (3->64)+ReLU followed by max-pool 3x3/2 of exactly that tensor (ReID stem)
-    if (dtype == AIC_F16 && !getenv("AICAM_NO_FUSE")) {
+    if (dtype == AIC_F16) {
         for (size_t i = 0; i + 1 < ops.size(); ++i) {
             const int* c = ops[i].v;
             const int* p = ops[i + 1].v;
@@ -356,7 +356,7 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
     // ---- fusion: a SiLU conv with 64 or 80 output channels whose output feeds exactly one 1x1/1/0 conv and nothing else (YOLOv8's
     // detect branches: 22.box*.1 -> .2, 22.cls*.1 -> .2).  The 1x1 runs in the first conv's epilogue on the tile in registers;
     // the intermediate tensor is never written.  Marked here (graph properties); run_range() asks conv_tail_supported() for the rest.
-    if (dtype == AIC_F16 && !getenv("AICAM_NO_FUSE")) {
+    if (dtype == AIC_F16) {
         for (size_t i = 0; i + 1 < ops.size(); ++i) {
             const int* c = ops[i].v;
             const int* p = ops[i + 1].v;
@@ -374,21 +374,6 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
             for (auto& o : outs)
                 if (o.v[0] == c[4] || (kind == KIND_YOLO && o.v[1] == c[4])) other_reader = true;
             if (!other_reader) ops[i].fuse = 3;          // the follower keeps fuse = 0: it runs on its own whenever the lead cannot take it
-        }
-    }
-    {   // sub-batching plan: the maximal prefix of ops whose outputs are >= min_kb per item
-        const char* e_items = getenv("AICAM_SB_ITEMS");
-        const char* e_kb = getenv("AICAM_SB_MINKB");
-        sub_items = e_items ? atoi(e_items) : 0;   // off by default: measured no gain on MI355X (profiles/)
-        const size_t min_bytes = (size_t)(e_kb ? atoi(e_kb) : 200) * 1024;
-        lead_ops = 0;
-        if (sub_items > 0) {
-            while (lead_ops < ops.size()) {
-                const OpDesc& o = ops[lead_ops];
-                const BufDesc& db = bufs[o.fuse == 1 ? ops[lead_ops + 1].v[4] : o.v[4]];
-                if (o.fuse != 2 && db.per_item < min_bytes) break;
-                ++lead_ops;
-            }
         }
     }
     if (kind == KIND_YOLO) {
@@ -414,7 +399,6 @@ Model::~Model() {
     for (int i = 0; i < 2; ++i) {
         if (side_fork[i]) (void)hipEventDestroy(side_fork[i]);
         if (side_join[i]) (void)hipEventDestroy(side_join[i]);
-        if (side_stream[i] && side_stream[i] != dev->s_det && side_stream[i] != dev->s_reid) (void)hipStreamDestroy(side_stream[i]);
     }
 }
 
@@ -427,7 +411,7 @@ void Model::plan_side_heads() {
     side_heads.clear();
     static const int opt = [] { const char* e = getenv("AICAM_SIDE_HEADS"); return e ? atoi(e) : 2; }();
     side_max_items = opt;
-    if (kind != KIND_YOLO || opt <= 0 || outs.size() < 2 || (lead_ops > 0 && sub_items > 0)) return;
+    if (kind != KIND_YOLO || opt <= 0 || outs.size() < 2) return;
     struct Slice { int buf, c0, cn; };
     const size_t no = ops.size();
     std::vector<std::vector<Slice>> rd(no);
@@ -500,8 +484,7 @@ void Model::plan_side_heads() {
     if (getenv("AICAM_SIDE_DBG"))
         for (const SideHead& h : side_heads) fprintf(stderr, "[aicam] side head: ops [%zu, %zu) of %zu fork behind op %zu\n", h.a, h.b, no, h.cut);
     for (size_t i = 0; i < side_heads.size(); ++i) {
-        side_stream[i] = getenv("AICAM_SIDE_OWN") ? nullptr : (i == 0 ? dev->s_det : dev->s_reid);
-        if (!side_stream[i]) HIP_CHECK(hipStreamCreateWithFlags(&side_stream[i], hipStreamNonBlocking));
+        side_stream[i] = i == 0 ? dev->s_det : dev->s_reid;
         HIP_CHECK(hipEventCreateWithFlags(&side_fork[i], hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&side_join[i], hipEventDisableTiming));
     }
@@ -510,23 +493,23 @@ void Model::plan_side_heads() {
 void Model::run_ops(size_t op0, int n, hipStream_t s) {
     const bool prof_conv = (dev->prof_mask >> PROF_CONV) & 1u;            // the HIP-event brackets describe one stream: measured runs stay on it
     if (!side_ok || side_heads.empty() || n > side_max_items || prof_conv || n_items_dev || op0 > side_heads[0].cut || s != dev->s_main) {
-        run_range(op0, ops.size(), 0, n, s);
+        run_range(op0, ops.size(), n, s);
         return;
     }
     size_t at = op0;
     try {
     for (size_t i = 0; i < side_heads.size(); ++i) {                      // main stream up to each fork, the level's ops behind it on their stream
         const SideHead& h = side_heads[i];
-        run_range(at, h.cut, 0, n, s);
+        run_range(at, h.cut, n, s);
         at = h.cut;
         HIP_CHECK(hipEventRecord(side_fork[i], s));
         HIP_CHECK(hipStreamWaitEvent(side_stream[i], side_fork[i], 0));
-        run_range(h.a, h.b, 0, n, side_stream[i]);
+        run_range(h.a, h.b, n, side_stream[i]);
         HIP_CHECK(hipEventRecord(side_join[i], side_stream[i]));
     }
     for (size_t i = 0; i <= side_heads.size(); ++i) {                     // the rest of the list, around the sets
         const size_t e = i < side_heads.size() ? side_heads[i].a : ops.size();
-        if (at < e) run_range(at, e, 0, n, s);
+        if (at < e) run_range(at, e, n, s);
         if (i < side_heads.size()) at = std::max(at, side_heads[i].b);
     }
     for (size_t i = 0; i < side_heads.size(); ++i) HIP_CHECK(hipStreamWaitEvent(s, side_join[i], 0));
@@ -538,34 +521,22 @@ void Model::run_ops(size_t op0, int n, hipStream_t s) {
 }
 
 bool Model::input_pix4_ok() const {
-    static const bool off = getenv("AICAM_NO_PIX4") != nullptr;
-    return !off && kind == KIND_REID && dtype == AIC_F16 && !ops.empty() && ops[0].fuse == 1 && !(lead_ops > 0 && sub_items > 0) &&
-           reid_stem2_usable(in_h, in_w);
+    return kind == KIND_REID && dtype == AIC_F16 && !ops.empty() && ops[0].fuse == 1 && reid_stem2_usable(in_h, in_w);
 }
 
 void Model::run(int n, hipStream_t s) {
     AIC_REQUIRE(n >= 0 && n <= max_items, AIC_ERR_CAPACITY, "batch exceeds the engine's max_items");
     if (n == 0) return;
     cls_reduced = box_decoded = 0;
-    AIC_REQUIRE(!n_items_dev || !(lead_ops > 0 && sub_items > 0), AIC_ERR_INVALID, "a device-side item count cannot be combined with sub-batching");
-    if (lead_ops > 0 && sub_items > 0 && n > sub_items + sub_items / 2) {
-        // producer -> consumer tensors of the first layers exceed the 256 MiB Infinity Cache at full batch:
-        // walk them in sub-batches so each layer reads what the previous one just wrote from cache, not HBM
-        for (int i0 = 0; i0 < n; i0 += sub_items) run_range(0, lead_ops, i0, std::min(sub_items, n - i0), s);
-        run_range(lead_ops, ops.size(), 0, n, s);
-    } else {
-        run_ops(0, n, s);
-    }
+    run_ops(0, n, s);
 }
 
 void Model::run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hipStream_t s) {
     AIC_REQUIRE(n >= 0 && n <= max_items, AIC_ERR_CAPACITY, "batch exceeds the engine's max_items");
     if (n == 0) return;
-    static const bool no_fuse = getenv("AICAM_NO_FUSE_LB") != nullptr;
     const int* v = ops[0].v;
-    const bool stem = kind == KIND_YOLO && dtype == AIC_F16 && !no_fuse && ops[0].fuse == 0 && v[0] == OP_CONV && v[1] == 0 && v[2] == 0 &&
-                      v[3] == 3 && v[6] == 16 && v[7] == 3 && v[8] == 3 && v[9] == 2 && v[10] == 1 && v[11] == 1 && v[14] == 0 &&
-                      !(lead_ops > 0 && sub_items > 0);
+    const bool stem = kind == KIND_YOLO && dtype == AIC_F16 && ops[0].fuse == 0 && v[0] == OP_CONV && v[1] == 0 && v[2] == 0 &&
+                      v[3] == 3 && v[6] == 16 && v[7] == 3 && v[8] == 3 && v[9] == 2 && v[10] == 1 && v[11] == 1 && v[14] == 0;
     if (stem) {
         const ConvWeights& w = weights[v[15]];
         const BufDesc& db = bufs[v[4]];
@@ -588,8 +559,7 @@ void Model::run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hip
     run(n, s);
 }
 
-void Model::run_range(size_t op0, size_t op1, int i0, int n, hipStream_t s) {
-    auto at = [&](const BufDesc& b) { return static_cast<char*>(b.p) + (size_t)i0 * b.per_item; };
+void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
     // HIP-event timing of the conv kernel brackets RUNS of consecutive conv launches (one event pair per
     // run, not per launch: two event records per launch cost 13 % of end-to-end throughput); the summed
     // time therefore includes the ~1-2 us dependent-launch gaps inside a run (a conservative `achieved`).
@@ -599,43 +569,41 @@ void Model::run_range(size_t op0, size_t op1, int i0, int n, hipStream_t s) {
     for (size_t oi = op0; oi < op1; ++oi) {
         const OpDesc& o = ops[oi];
         const int* v = o.v;
-        BufDesc sb = bufs[v[1]];
-        BufDesc db = bufs[v[4]];
-        sb.p = at(sb), db.p = at(db);
+        const BufDesc& sb = bufs[v[1]];
+        const BufDesc& db = bufs[v[4]];
         if (o.fuse == 2) continue;
         if (o.fuse == 1 || v[0] != OP_CONV) span_close();
         if (o.fuse == 1) {
             const ConvWeights& w = weights[v[15]];
             const int* pv = ops[oi + 1].v;
-            BufDesc pb = bufs[pv[4]];
-            pb.p = at(pb);
+            const BufDesc& pb = bufs[pv[4]];
             const double fl = 2.0 * n * sb.h * sb.w * 64.0 * 27.0;
             Prof pr(*dev, PROF_CONV_DIRECT, s, fl, (double)n * (sb.h * sb.w * 16.0 + pb.h * pb.w * 128.0));
             launch_reid_stem_pool(sb.p, w.w.p, w.bias.p, pb.p, n, sb.h, sb.w, w.Kp, pb.c, pv[5], in_pix4 ? 4 : 8, s,
-                                  (crop_src.frames && in_pix4 && i0 == 0) ? &crop_src : nullptr, n_items_dev);
+                                  (crop_src.frames && in_pix4) ? &crop_src : nullptr, n_items_dev);
             continue;
         }
         if (v[0] == OP_CONV) {
             double fl = 0, by = 0;
             auto conv_args = [&](size_t k) {
                 const int* u = ops[k].v;
-                BufDesc xb = bufs[u[1]], yb = bufs[u[4]];
-                xb.p = at(xb), yb.p = at(yb);
+                const BufDesc& xb = bufs[u[1]];
+                const BufDesc& yb = bufs[u[4]];
                 const ConvWeights& w = weights[u[15]];
                 ConvArgs a{};
                 a.x = xb.p, a.w = w.w.p, a.bias = w.bias.p, a.y = yb.p;
                 a.x_cs = xb.c, a.x_coff = u[2], a.H = xb.h, a.W = xb.w, a.Cin = w.cin_eff;
                 a.y_cs = yb.c, a.y_coff = u[5], a.Ho = yb.h, a.Wo = yb.w, a.Cout = w.cout;
                 a.res = nullptr, a.r_cs = 0, a.r_coff = 0, a.res_mode = u[14], a.act = u[11];
-                if (u[14]) { a.res = at(bufs[u[12]]), a.r_cs = bufs[u[12]].c, a.r_coff = u[13]; }
+                if (u[14]) { a.res = bufs[u[12]].p, a.r_cs = bufs[u[12]].c, a.r_coff = u[13]; }
                 a.KH = w.kh, a.KW = w.kw, a.stride = u[9], a.pad = u[10];
                 if (ops[k].xs_buf >= 0) {               // folded 2x upsample: the first channels come from the half-resolution tensor
                     const BufDesc& bs = bufs[ops[k].xs_buf];
-                    a.xs = at(bs), a.xs_cs = bs.c, a.xs_coff = ops[k].xs_coff, a.Hs = bs.h, a.Ws = bs.w, a.Cs = ops[k].xs_c;
+                    a.xs = bs.p, a.xs_cs = bs.c, a.xs_coff = ops[k].xs_coff, a.Hs = bs.h, a.Ws = bs.w, a.Cs = ops[k].xs_c;
                 }
                 if (u[16]) {                            // folded 1x1 second source
                     const BufDesc& b2 = bufs[u[16] - 1];
-                    a.x2 = at(b2), a.x2_cs = b2.c, a.x2_coff = u[17], a.H2 = b2.h, a.W2 = b2.w, a.s2 = u[19], a.Cin2 = u[18];
+                    a.x2 = b2.p, a.x2_cs = b2.c, a.x2_coff = u[17], a.H2 = b2.h, a.W2 = b2.w, a.s2 = u[19], a.Cin2 = u[18];
                     fl += 2.0 * n * yb.h * yb.w * (double)w.cout * u[18];
                     by += ((double)n * yb.h * yb.w * u[18] + (double)w.cout * u[18]) * (dtype == AIC_F16 ? 2 : 4);
                 }
@@ -699,13 +667,13 @@ void Model::run_range(size_t op0, size_t op1, int i0, int n, hipStream_t s) {
                         for (size_t l = 0; l < outs.size() && (is_cls || is_box); ++l) {
                             const int* ov = outs[l].v;
                             const BufDesc& ob = bufs[ov[is_cls ? 1 : 0]];
-                            if (static_cast<char*>(ob.p) + (size_t)i0 * ob.per_item == static_cast<char*>(t.y) && ov[3] * ov[4] == t.Ho * t.Wo) {
+                            if (ob.p == t.y && ov[3] * ov[4] == t.Ho * t.Wo) {
                                 at.t_hw = ov[3] * ov[4], at.t_a0 = a0, at.t_na = n_anchors;
                                 if (is_cls) {
-                                    at.t_max = d_maxlogit.p + (size_t)i0 * n_anchors, at.t_arg = d_labels.p + (size_t)i0 * n_anchors;
+                                    at.t_max = d_maxlogit.p, at.t_arg = d_labels.p;
                                     cls_reduced |= 1u << l;
                                 } else {
-                                    at.t_box = d_boxes.p + (size_t)i0 * n_anchors * 4, at.t_w = ov[4], at.t_stride = ov[2];
+                                    at.t_box = d_boxes.p, at.t_w = ov[4], at.t_stride = ov[2];
                                     box_decoded |= 1u << l;
                                 }
                             }
@@ -724,7 +692,7 @@ void Model::run_range(size_t op0, size_t op1, int i0, int n, hipStream_t s) {
         } else {
             EltArgs a{};
             a.src = sb.p, a.dst = db.p, a.n = n, a.h = sb.h, a.w = sb.w, a.c = v[3];
-            if (emb_host_out && oi + 1 == ops.size() && v[0] == OP_L2NORM && i0 == 0 && v[4] == outs[0].v[0]) a.dst = emb_host_out;
+            if (emb_host_out && oi + 1 == ops.size() && v[0] == OP_L2NORM && v[4] == outs[0].v[0]) a.dst = emb_host_out;
             a.s_cs = sb.c, a.s_coff = v[2], a.d_cs = db.c, a.d_coff = v[5];
             a.n_dev = n_items_dev;
             Prof pr(*dev, PROF_MISC, s, 0, 0);
@@ -1075,8 +1043,7 @@ int aic_detect(aic_model* mm, const uint8_t* frames, int batch, int h, int w, in
         m.side_ok = true;
         m.run_frames(df, batch, g, s);
         m.side_ok = false;
-        static const bool direct = getenv("AICAM_NO_DET_HOST_OUT") == nullptr;
-        if (direct && batch <= 4 && num_dets && boxes && scores && labels) {
+        if (batch <= 4 && num_dets && boxes && scores && labels) {
             // the per-frame plugin loop: the NMS kernel stores what it keeps into page-locked host memory itself
             const size_t per = (size_t)max_det * 24;
             m.h_det.ensure((size_t)batch * (4 + per) + 16);
@@ -1119,10 +1086,8 @@ int aic_reid_embed(aic_model* mm, const uint8_t* frame, int h, int w, int mem, c
         m.d_valid.ensure(n);
         HIP_CHECK(hipMemcpyAsync(m.d_crop_boxes.p, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
         m.in_pix4 = m.input_pix4_ok();
-        static const bool fuse_crop = getenv("AICAM_NO_FUSE_CROP") == nullptr;
-        static const bool direct = getenv("AICAM_NO_EMB_HOST_OUT") == nullptr;
         const BufDesc& eb = m.bufs[m.outs[0].v[0]];
-        if (direct && fuse_crop && n <= m.max_items && n <= 512 && m.in_pix4 && m.in_h <= 192 && mem != AIC_DEVICE && eb.f32 &&
+        if (n <= m.max_items && n <= 512 && m.in_pix4 && m.in_h <= 192 && mem != AIC_DEVICE && eb.f32 &&
             eb.c == m.out_dim && m.outs[0].v[2] == 0 && m.ops.back().v[0] == OP_L2NORM && m.ops.back().v[5] == 0) {
             // the per-frame plugin loop: embeddings and crop validity are stored into page-locked host memory by the kernels that produce them
             const size_t eb_bytes = (size_t)n * m.out_dim * 4;
@@ -1144,7 +1109,7 @@ int aic_reid_embed(aic_model* mm, const uint8_t* frame, int h, int w, int mem, c
         }
         for (int c0 = 0; c0 < n; c0 += m.max_items) {   // launch groups of max_items: every detection is embedded (deepsort_tracker.py:104-113)
             const int k = std::min(m.max_items, n - c0);
-            if (fuse_crop && m.in_pix4 && m.in_h <= 192 && mem != AIC_DEVICE) {
+            if (m.in_pix4 && m.in_h <= 192 && mem != AIC_DEVICE) {
                 // crop + resize + normalise inside the stem kernel, as the pipeline does it (same arithmetic, pixel for pixel): one launch fewer
                 // per call of the per-frame plugin loop, and no crop tensor.  (A caller's own device buffer keeps the separate crop kernel:
                 // the fused form's aligned 12-byte reads want 16 bytes of slack behind the frame, which only our staging buffer promises.)

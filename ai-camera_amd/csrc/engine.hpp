@@ -79,7 +79,7 @@ struct Model {
     void run(int n_items, hipStream_t s);
     // u8 BGR frames -> letterbox -> the whole graph; fp16 YOLO engines fuse the letterbox into the stem conv
     void run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hipStream_t s);
-    void run_range(size_t op0, size_t op1, int i0, int n, hipStream_t s);
+    void run_range(size_t op0, size_t op1, int n, hipStream_t s);
     // Launches of a FEW frames (the per-frame plugin loop: one 640 x 640 image is 6 - 150 workgroups per layer on 256 CUs, ~10 us per dependent
     // launch): the detect branches of every level but the last leave the main stream -- level l's ops (those from which only output l is
     // reachable) run on a side stream from the moment their feature map exists, beside the rest of the neck, and the main stream joins them
@@ -93,8 +93,6 @@ struct Model {
     void plan_side_heads();
     void run_ops(size_t op0, int n, hipStream_t s);     // ops [op0, end) of the whole batch: the side-head schedule where it applies, else run_range
     ~Model();
-    size_t lead_ops = 0;   // leading ops whose activations are large: run in sub-batches (Infinity-Cache residency)
-    int sub_items = 0;
     // YOLO post-processing on the buffers left by run()
     DetArgs det_args(int batch, float conf, float iou, int max_det, const LetterboxGeom* g);
     // host_out: the kept detections (counts, original-pixel boxes, scores, labels) are stored straight into this page-locked host block by

@@ -191,8 +191,6 @@ void launch_gallery_append(float* gal, int gmax, int dim, const int* slot, const
                            const float* feat, int count, hipStream_t s);
 
 // fused per-frame tracker kernels
-void launch_trk_assoc(float* mean, float* cov, const int* slots, int t, int do_predict, const float* det_tlwh,
-                      const float* det_xyah, int n, float* app, float* d2, float* iouc, hipStream_t s);
 void launch_cosine_min_mfma(const float* gal_n, const int* slots, const int* glen, int t, int gmax, int dim, const float* det_n,
                             const unsigned char* has_feat, int n, float* cost, hipStream_t s);
 void launch_trk_assoc_all(float* mean, float* cov, const int* slots, const int* glen, int t, int do_predict, const float* det_tlwh,

@@ -13,202 +13,18 @@
 // Per K-step each tile row holds 64 B (32 halves / 16 floats).  LDS image: row*64 +
 // 16*(chunk ^ ((row>>1)&3)) -- an XOR swizzle that is conflict-free for the ds_read_b128
 // lane groups of gfx950 (checked exhaustively against the group table of
-// MI355X_MICROARCH.md §LDS) and for the staging ds_write_b128.  Global->register->LDS staging
-// with the next step's loads issued before the current step's MFMAs (register double buffer):
-// zero-padding, image borders and the K tail are resolved per 16-byte chunk at load time.
+// MI355X_MICROARCH.md §LDS).
 #include "conv_common.hpp"
 
 namespace aic {
 
-static int g_conv_cus = [] { const char* e = getenv("AICAM_CONV_CUS"); return e ? std::max(1, atoi(e)) : 256; }();
+static int g_conv_cus = 256;
 int conv_cu_budget() { return g_conv_cus; }
-void set_conv_cu_budget(int cus) { if (getenv("AICAM_CONV_CUS") == nullptr) g_conv_cus = std::max(1, cus); }
-
-
-// 4 waves per block arranged WM x WN; each wave owns MT x NT tiles of 16 pixels x 16 channels.
-template <typename T, int MT, int NT, int WM, int WN>
-__global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
-    constexpr int CH = 16 / (int)sizeof(T);   // elements per 16-byte chunk
-    constexpr int BKE = 4 * CH;                // K elements per step
-    constexpr int BM = WM * MT * 16;           // pixels per block
-    constexpr int BN = WN * NT * 16;           // output channels per block
-    constexpr int A_PER = BM / 64;             // 16-byte chunks of the pixel tile per thread
-    constexpr int B_PER = (BN + 63) / 64;      // ... of the weight tile
-    constexpr int TILE = (BM + BN) * 64;       // bytes per stage
-    static_assert(WM * WN == 4 && BM % 64 == 0, "block is 4 waves; pixel tile a multiple of 64");
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int t = threadIdx.x;
-    const int kc = t & 3;        // which 16-byte chunk of the 64-byte K-step this thread stages
-    const int r0 = t >> 2;       // first tile row this thread stages
-    const int m0 = blockIdx.x * BM;
-    const int n0 = blockIdx.y * BN;
-    const int M = a.n_dev ? min(a.M, min(a.n_dev[0], a.M / (a.Ho * a.Wo)) * (a.Ho * a.Wo)) : a.M;
-    if (m0 >= M) return;
-
-    const T* __restrict__ xg = reinterpret_cast<const T*>(a.x);
-    const T* __restrict__ wg = reinterpret_cast<const T*>(a.w);
-
-    // ---- per-thread description of the pixel rows it gathers
-    size_t pix_base[A_PER];
-    int ih0[A_PER], iw0[A_PER];
-    const int HoWo = a.Ho * a.Wo;
-#pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-        const int m = m0 + r0 + 64 * i;
-        if (m < M) {
-            const int img = m / HoWo;
-            const int rem = m - img * HoWo;
-            const int oh = rem / a.Wo;
-            const int ow = rem - oh * a.Wo;
-            pix_base[i] = (size_t)img * a.H * a.W;
-            ih0[i] = oh * a.stride - a.pad;
-            iw0[i] = ow * a.stride - a.pad;
-        } else {
-            pix_base[i] = 0;
-            ih0[i] = -(1 << 28);   // never in range -> zero rows
-            iw0[i] = 0;
-        }
-    }
-    // ---- position of this thread's chunk inside K: (kh, kw, c)
-    int c_in = kc * CH, kw = 0, kh = 0;
-    while (c_in >= a.Cin) {
-        c_in -= a.Cin;
-        if (++kw == a.KW) { kw = 0; ++kh; }
-    }
-
-    uint4 a_reg[A_PER], b_reg[B_PER];
-    const int nsteps = a.Kp / BKE;
-
-    auto load_step = [&](int step) {
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int ih = ih0[i] + kh, iw = iw0[i] + kw;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (kh < a.KH && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-                const size_t off = (pix_base[i] + (size_t)ih * a.W + iw) * a.x_cs + a.x_coff + c_in;
-                v = *reinterpret_cast<const uint4*>(xg + off);
-            }
-            a_reg[i] = v;
-        }
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) {
-            const int row = r0 + 64 * j;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (row < BN) v = *reinterpret_cast<const uint4*>(wg + (size_t)(n0 + row) * a.Kp + step * BKE + kc * CH);
-            b_reg[j] = v;
-        }
-        // advance (kh, kw, c) by one K-step
-        c_in += BKE;
-        while (c_in >= a.Cin) {
-            c_in -= a.Cin;
-            if (++kw == a.KW) { kw = 0; ++kh; }
-        }
-    };
-    auto store_step = [&](int stage) {
-        char* base = smem + stage * TILE;
-#pragma unroll
-        for (int i = 0; i < A_PER; ++i) {
-            const int row = r0 + 64 * i;
-            *reinterpret_cast<uint4*>(base + lds_off(row, kc)) = a_reg[i];
-        }
-#pragma unroll
-        for (int j = 0; j < B_PER; ++j) {
-            const int row = r0 + 64 * j;
-            if (row < BN) *reinterpret_cast<uint4*>(base + BM * 64 + lds_off(row, kc)) = b_reg[j];
-        }
-    };
-
-    const int lane = t & 63, wv = t >> 6;
-    const int wm = wv / WN, wn = wv % WN;
-    const int q = lane >> 4, r = lane & 15;
-
-    floatx4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-    load_step(0);
-    store_step(0);
-    __syncthreads();
-
-    typedef typename Frag<T>::type frag_t;
-    for (int step = 0; step < nsteps; ++step) {
-        const int cur = step & 1;
-        const bool more = step + 1 < nsteps;
-        if (more) load_step(step + 1);   // global loads in flight under the MFMAs below
-        const char* base = smem + cur * TILE;
-        frag_t xf[MT], wf[NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int row = (wm * MT + i) * 16 + r;
-            xf[i] = *reinterpret_cast<const frag_t*>(base + lds_off(row, q));
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int row = (wn * NT + j) * 16 + r;
-            wf[j] = *reinterpret_cast<const frag_t*>(base + BM * 64 + lds_off(row, q));
-        }
-        mma_tiles<T, MT, NT>(acc, wf, xf);
-        if (more) store_step(cur ^ 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: bias, residual, activation; 4 consecutive channels per lane
-    const float* __restrict__ bias = a.bias;
-    const T* __restrict__ rg = reinterpret_cast<const T*>(a.res);
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int m = m0 + (wm * MT + i) * 16 + r;
-        if (m >= M) continue;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int n = n0 + (wn * NT + j) * 16 + 4 * q;
-            if (n >= a.Cout) continue;
-            const floatx4 b4 = *reinterpret_cast<const floatx4*>(bias + n);
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + b4[e];
-            float rv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (a.res_mode) {
-                const T* rp = rg + (size_t)m * a.r_cs + a.r_coff + n;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) rv[e] = (n + e < a.Cout) ? (float)rp[e] : 0.f;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = v[e];
-                if (a.res_mode == 1) x += rv[e];
-                x = act_apply(x, a.act);
-                if (a.res_mode == 2) x += rv[e];
-                v[e] = x;
-            }
-            const size_t yoff = (size_t)m * a.y_cs + a.y_coff + n;
-            if (n + 4 <= a.Cout) {
-                if (a.out_f32) {
-                    *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(a.y) + yoff) = floatx4{v[0], v[1], v[2], v[3]};
-                } else if constexpr (sizeof(T) == 2) {
-                    half4 h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-                    *reinterpret_cast<half4*>(reinterpret_cast<half_t*>(a.y) + yoff) = h;
-                } else {
-                    *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(a.y) + yoff) = floatx4{v[0], v[1], v[2], v[3]};
-                }
-            } else {
-                for (int e = 0; e < 4 && n + e < a.Cout; ++e) {
-                    if (a.out_f32 || sizeof(T) == 4) reinterpret_cast<float*>(a.y)[yoff + e] = v[e];
-                    else reinterpret_cast<half_t*>(a.y)[yoff + e] = (half_t)v[e];
-                }
-            }
-        }
-    }
-}
-
+void set_conv_cu_budget(int cus) { g_conv_cus = std::max(1, cus); }
 
 
 // ------------------------------------------------------------------------------------------------
-// v2: same tiling and MFMA mapping, but the operand tiles travel HBM/L2 -> LDS by LDS-DMA
+// v2: the tiling and MFMA mapping above; the operand tiles travel HBM/L2 -> LDS by LDS-DMA
 // (global_load_lds_dwordx4, 1 KiB per wave-instruction, no VGPR staging and no ds_write pass) into an
 // NSTAGE-deep ring, NSTAGE-1 K-steps in flight.  Per K-step: counted s_waitcnt vmcnt (never 0 in
 // the loop) -> one raw s_barrier -> issue the loads of step+NSTAGE-1 -> MFMAs of the current step.
@@ -567,29 +383,12 @@ static void launch_variant(const ConvArgs& a, hipStream_t s) {
     //  accumulators provably stay put, as in kernels_conv_sp.hip.)
     if constexpr (sizeof(T) == 2 && WM * WN == 4) {
         // launches of a few tiles (the per-frame plugin loop): one synchronisation per group of K-steps, bit-identical (kernels_conv_wide.hip)
-        if (conv_impl() == 2 && conv_try_wide<MT, NT, WM, WN>(a, s)) return;
+        if (conv_try_wide<MT, NT, WM, WN>(a, s)) return;
     }
-    if (conv_impl() == 2) {
-        // ring depth by K: a layer whose whole K is 2 .. 6 steps (YOLOv8n's 1x1 convs: K = 64 .. 192) gains nothing from a 4-deep ring, and
-        // the LDS it costs halves the blocks a CU holds (80 KB per 256 x 64 tile: 2 blocks; 2 stages: 40 KB, 4 blocks).  AICAM_DMA_NSTAGE=n
-        // forces a depth (A/B), AICAM_DMA_NS_K=k sets the largest K-step count that takes the shallow ring
-        static const int force = [] { const char* e = getenv("AICAM_DMA_NSTAGE"); return e ? atoi(e) : 0; }();
-        static const int ns_k = [] { const char* e = getenv("AICAM_DMA_NS_K"); return e ? atoi(e) : 0; }();
-        const int nsteps = a.Kp / (sizeof(T) == 2 ? 32 : 16);
-        // (A deeper ring for the small launches -- 8 stages where a 64 x 64 tile's K loop runs 0.41 us per step -- was measured in round 5 on the
-        //  per-frame plugin loop: 1 101 against 1 075 us of conv time per frame.  Their K loop is not waiting for memory: it is ~90 instructions
-        //  per step for four MFMAs -- the chunk-major walks rebuild every row pointer every step.)
-        const int ns = force ? force : (nsteps <= ns_k ? 2 : 4);
-        if (ns == 2) launch_dma<T, MT, NT, WM, WN, 2>(a, s);
-        else if (ns == 3) launch_dma<T, MT, NT, WM, WN, 3>(a, s);
-        else launch_dma<T, MT, NT, WM, WN, 4>(a, s);
-        return;
-    }
-    constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
-    dim3 grid(ceil_div(a.M, BM), ceil_div(a.Cout, BN));
-    const size_t lds = 2 * (size_t)(BM + BN) * 64;
-    hipLaunchKernelGGL((conv_igemm_kernel<T, MT, NT, WM, WN>), grid, dim3(256), lds, s, a);
-    KCHECK();
+    // (A deeper ring for the small launches -- 8 stages where a 64 x 64 tile's K loop runs 0.41 us per step -- was measured in round 5 on the
+    //  per-frame plugin loop: 1 101 against 1 075 us of conv time per frame.  Their K loop is not waiting for memory: it is ~90 instructions
+    //  per step for four MFMAs -- the chunk-major walks rebuild every row pointer every step.)
+    launch_dma<T, MT, NT, WM, WN, 4>(a, s);
 }
 
 template <typename T>
@@ -614,31 +413,29 @@ static void launch_conv_t(const ConvArgs& a_in, hipStream_t s) {
         else launch_variant<T, 4, 1, 4, 1>(a, s);                                       // 256 px x 16 ch
         return;
     } else {
-    if (conv_impl() == 2 && conv_try_pp_patch(DT, a, s)) return;
-    if (conv_impl() == 2 && !a.x2 && DT == AIC_F16 && conv_try_pm_patch(a, s)) return;
-    if (conv_impl() == 2 && !a.x2 && conv_try_patch(DT, a, s)) return;        // (a second source: the ping-pong patch kernel above or the LDS-DMA implicit GEMMs below)
+    if (conv_try_pp_patch(DT, a, s)) return;
+    if (!a.x2 && DT == AIC_F16 && conv_try_pm_patch(a, s)) return;
+    if (!a.x2 && conv_try_patch(DT, a, s)) return;        // (a second source: the ping-pong patch kernel above or the LDS-DMA implicit GEMMs below)
     if (c % 128 == 0 || c > 160) {
-        static const bool t256 = getenv("AICAM_NO_T256") == nullptr;   // +12% on ReID layer3/4 over 256x128 (profiles/)
-        if (conv_impl() == 2 && conv_try_pp(DT, a, s)) return;   // one-block-per-CU ping-pong kernels (kernels_conv_pp.hip)
-        if (t256 && conv_impl() == 2 && c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= 200) launch_dma<T, 8, 4, 2, 4, 4>(a, s);   // 8 waves: 256 px x 256 ch
-        else if (conv_impl() == 2 && (blocks128 / 2) * ceil_div(c, 128) >= 384) launch_dma<T, 4, 4, 4, 2, 3>(a, s);   // 8 waves: 256 px x 128 ch
+        if (conv_try_pp(DT, a, s)) return;   // one-block-per-CU ping-pong kernels (kernels_conv_pp.hip)
+        if (c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= 200) launch_dma<T, 8, 4, 2, 4, 4>(a, s);   // 8 waves: 256 px x 256 ch (+12% on ReID layer3/4 over 256x128, profiles/)
+        else if ((blocks128 / 2) * ceil_div(c, 128) >= 384) launch_dma<T, 4, 4, 4, 2, 3>(a, s);   // 8 waves: 256 px x 128 ch
         else if (blocks128 * ceil_div(c, 128) >= 128) launch_variant<T, 4, 4, 2, 2>(a, s);   // 128 px x 128 ch
-        else if ((long)ceil_div(a.M, 64) * ceil_div(c, 64) > 256 && conv_impl() == 2 && conv_try_wide<4, 4, 2, 2>(a, s)) return;   // too many 64 x 64 tiles for the wide-step kernel, few enough 128 x 128 ones
+        else if ((long)ceil_div(a.M, 64) * ceil_div(c, 64) > 256 && conv_try_wide<4, 4, 2, 2>(a, s)) return;   // too many 64 x 64 tiles for the wide-step kernel, few enough 128 x 128 ones
         else launch_variant<T, 2, 2, 2, 2>(a, s);                                       // 64 px x 64 ch (small maps)
-    } else if (c == 144 && conv_impl() == 2) {
+    } else if (c == 144) {
         // the merged first convs of a YOLOv8 detect level (64 box + 80 class channels, Model::Model; fp16 only): one 144-wide tile,
         // the map is read once.  4 waves, one per SIMD: 36 accumulator tiles per wave on the 256-pixel tile need the whole register file
         if (ceil_div(a.M, 256) >= 512) launch_dma<T, 4, 9, 4, 1, 4>(a, s);          // 256 px x 144 ch
         else if (!conv_try_wide<2, 9, 4, 1>(a, s)) launch_dma<T, 2, 9, 4, 1, 4>(a, s);   // 128 px x 144 ch (a few tiles: kernels_conv_wide.hip)
     } else if (c % 80 == 0) {
         // YOLOv8's class branches (Cout = nc = 80).  512 px x 80 ch on 8 waves once there are tiles for every CU:
-        // 428 -> 499 TFLOP/s on cls0.1 (80 -> 80, 3x3 at 80 x 80), +7..16 % on the others (tools/conv_bench.py); AICAM_C80=0: off
-        static const bool big80 = [] { const char* e = getenv("AICAM_C80"); return !e || atoi(e) != 0; }();
-        if (big80 && conv_impl() == 2 && ceil_div(a.M, 512) >= 256) launch_dma<T, 4, 5, 8, 1, 3>(a, s);
+        // 428 -> 499 TFLOP/s on cls0.1 (80 -> 80, 3x3 at 80 x 80), +7..16 % on the others (tools/conv_bench.py)
+        if (ceil_div(a.M, 512) >= 256) launch_dma<T, 4, 5, 8, 1, 3>(a, s);
         else launch_variant<T, 2, 5, 4, 1>(a, s);                                       // 128 px x 80 ch
     } else if (c % 64 == 0) {
         if (blocks128 >= 512) launch_variant<T, 4, 4, 4, 1>(a, s);                      // 256 px x 64 ch
-        else if (blocks128 * ceil_div(c, 64) > 256 && conv_impl() == 2 && conv_try_wide<4, 4, 4, 1>(a, s)) return;   // (as above: 256 px tiles where the 128 px grid is too large for the wide-step kernel)
+        else if (blocks128 * ceil_div(c, 64) > 256 && conv_try_wide<4, 4, 4, 1>(a, s)) return;   // (as above: 256 px tiles where the 128 px grid is too large for the wide-step kernel)
         else launch_variant<T, 2, 4, 4, 1>(a, s);                                       // 128 px x 64 ch
     } else if (c % 48 == 0) {
         launch_variant<T, 2, 3, 4, 1>(a, s);                                            // 128 px x 48 ch
@@ -655,7 +452,7 @@ static void launch_conv_t(const ConvArgs& a_in, hipStream_t s) {
 // choices the conv gets on its own.
 bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail) {
     static const bool off = getenv("AICAM_NO_TAIL") != nullptr;
-    if (off || dtype != AIC_F16 || conv_impl() != 2) return false;
+    if (off || dtype != AIC_F16) return false;
     if ((lead.Cout != 64 && lead.Cout != 80) || lead.act != 1 || lead.res_mode != 0 || lead.out_f32) return false;
     if (lead.xs || lead.x2) return false;                          // split / second sources are walked by the plain kernels only
     if (tail.KH != 1 || tail.KW != 1 || tail.stride != 1 || tail.pad != 0 || tail.res_mode != 0) return false;
@@ -668,9 +465,7 @@ bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail) 
 // A split source is walked by the memory-order fast path of conv_igemm_dma_kernel only: a 1x1 / 1 / 0 conv without tail whose Cout
 // keeps it away from the ping-pong kernels (K of these layers is short anyway) and from the direct kernels.
 bool conv_xs_supported(int dtype, const ConvArgs& a, int cs) {
-    static const bool off = getenv("AICAM_NO_XS") != nullptr;
     const int bke = dtype == AIC_F16 ? 32 : 16;
-    if (off || conv_impl() != 2) return false;
     if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.w_tail || a.x2 || a.Cin % bke || cs <= 0 || cs % bke || cs >= a.Cin) return false;
     if (a.H % 2 || a.W % 2) return false;
     return a.Kp < 16 * bke;                                       // (conv_try_pp takes K >= 16 steps: it has no split-source walk)
@@ -679,10 +474,8 @@ bool conv_xs_supported(int dtype, const ConvArgs& a, int cs) {
 // A second source rides on the chunk-major walk of conv_igemm_dma_kernel / conv_igemm_pp_kernel: the layer must be one that every
 // batch size sends there in that order -- a ping-pong-patch SHAPE (k_order 1) whose Cout takes the 128-multiple branch of launch_conv_t.
 bool conv_x2_supported(int dtype, const ConvArgs& a, int cin2) {
-    static const bool off = getenv("AICAM_NO_X2") != nullptr;
     const int bke = dtype == AIC_F16 ? 32 : 16;
-    if (off || conv_impl() != 2 || getenv("AICAM_K_TAP_MAJOR")) return false;
-    const int shape = conv_pp_patch_shape(dtype, a);             // 2: 512 x 128 tile, 3 / 4: 256 x 256 on 16 x 8 / 8 x 4 maps (shape 1, Cout 64, has no such kernel)
+    const int shape = conv_pp_patch_shape(dtype, a);             // 2: 512 x 128 tile, 3 / 4: 256 x 256 on 16 x 8 / 8 x 4 maps
     if (shape < 2 || a.Cout % 128 || a.w_tail || a.out_f32 || cin2 <= 0 || cin2 % bke) return false;
     return cin2 / bke < a.Cin / bke;                             // its chunk e rides behind the window's chunk e + 1
 }
@@ -704,17 +497,13 @@ static void launch_conv_tail(const ConvArgs& a, hipStream_t s) {
 void launch_conv_igemm(int dtype, const ConvArgs& a0, hipStream_t s) {
     if (a0.M <= 0) return;
     ConvArgs a = a0;
-    a.xcd_map = xcd_map_on();
-    static const bool tap_major_everywhere = getenv("AICAM_K_TAP_MAJOR") != nullptr;   // A/B: the pre-round-3 behaviour (batch-dependent bits)
-    a.k_order = 0;
-    if (conv_impl() == 2 && !tap_major_everywhere) {
-        // the 64-channel weights-resident kernels (fp16): any 3x3 / 1 / 1 layer with Cin = Cout = 64 whose map they tile
-        // (ReLU, with or without the BasicBlock's residual: the only forms those kernels have)
-        const bool c64 = dtype == AIC_F16 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 64 && a.Cout == 64 && a.Kp == 576 &&
-                         a.act == 2 && a.res_mode <= 1 && !a.out_f32 && !a.w_tail &&
-                         a.Ho == a.H && a.Wo == a.W && ((a.W % 32 == 0 && a.H % 8 == 0) || (a.W == 32 && a.H % 4 == 0));
-        a.k_order = conv_pp_patch_shape(dtype, a) ? 1 : (c64 ? 2 : (conv_s2_patch_shape(a) ? 3 : 0));      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
-    }
+    a.xcd_map = 1;
+    // the 64-channel weights-resident kernels (fp16): any 3x3 / 1 / 1 layer with Cin = Cout = 64 whose map they tile
+    // (ReLU, with or without the BasicBlock's residual: the only forms those kernels have)
+    const bool c64 = dtype == AIC_F16 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 64 && a.Cout == 64 && a.Kp == 576 &&
+                     a.act == 2 && a.res_mode <= 1 && !a.out_f32 && !a.w_tail &&
+                     a.Ho == a.H && a.Wo == a.W && ((a.W % 32 == 0 && a.H % 8 == 0) || (a.W == 32 && a.H % 4 == 0));
+    a.k_order = conv_pp_patch_shape(dtype, a) ? 1 : (c64 ? 2 : (conv_s2_patch_shape(a) ? 3 : 0));      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
     if (a.x2) AIC_REQUIRE(a.k_order == 1 && a.Cout % 128 == 0 && !a.w_tail, AIC_ERR_INVALID, "conv with a second source: unsupported shape (check conv_x2_supported)");
     if (a.xs) AIC_REQUIRE(a.k_order == 0 && a.KH == 1 && a.KW == 1 && !a.w_tail && a.Kp < 16 * (dtype == AIC_F16 ? 32 : 16), AIC_ERR_INVALID,
                           "conv with a split source: unsupported shape (check conv_xs_supported)");

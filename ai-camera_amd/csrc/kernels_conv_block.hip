@@ -282,26 +282,20 @@ bool conv_try_c64_block(const ConvArgs& c1, const ConvArgs& c2, hipStream_t s) {
     a.x_cs = c1.x_cs, a.x_coff = c1.x_coff, a.y_cs = c2.y_cs, a.y_coff = c2.y_coff, a.H = c1.H;
     a.n_img = c1.M / (c1.H * c1.W);
     a.n_dev = c1.n_dev;
-    // images per block: n_img / 256 = one persistent block per CU, or AICAM_BLK_IPB for shorter-lived blocks (each pays 3 steps
-    // of pipeline fill and a weight reload; in exchange the CU takes other streams' waiting blocks in between)
-    // Default 16 images per block (960 blocks for a 15 360-crop group): same box, interleaved, round 3: 9 490 / 9 482 frames/s with one
+    // images per block: shorter-lived blocks than one persistent block per CU (each pays 3 steps of pipeline fill and a weight
+    // reload; in exchange the CU takes other streams' waiting blocks in between).  16 images per block (960 blocks for a 15 360-crop group): same box, interleaved, round 3: 9 490 / 9 482 frames/s with one
     // persistent block per CU (0), 9 553 / 9 624 with 16 -- the NMS blocks of the side stream hold whole CUs for ~2 ms at the start of
     // the ReID trunk, and a persistent block that starts late finishes late; shorter-lived blocks just flow around them.
     // Round 5: 960 blocks are 3.75 rounds of 256 CUs -- the last round runs three quarters full.  12 .. 16 images per block, whichever
     // wastes least of the last round (15 360 crops: 12 -> 1 280 blocks = 5 rounds; the layer alone 2 065 -> 2 000 us per conv, same box).
-    static const int ipb_env = [] { const char* e = getenv("AICAM_BLK_IPB"); return e ? atoi(e) : -1; }();
     // (the CUs the blocks are dealt over: the budget leaves ONE out for the tracker's epoch block while it runs, which does not make 1 280
     //  blocks six rounds -- counted against the whole chip)
     const int cus = (conv_cu_budget() + 7) / 8 * 8;
-    if (ipb_env > 0) a.ipb = ipb_env;
-    else if (ipb_env == 0) a.ipb = (a.n_img + std::min(cus, a.n_img) - 1) / std::min(cus, a.n_img);
-    else {
-        long best = -1;
-        for (int ipb = 12; ipb <= 16; ++ipb) {
-            const long blocks = (a.n_img + ipb - 1) / ipb, rounds = (blocks + cus - 1) / cus;
-            const long waste = (rounds * cus - blocks) * 1000 / (rounds * cus);           // idle share of the CUs' block slots, per mille
-            if (best < 0 || waste < best) best = waste, a.ipb = ipb;
-        }
+    long best = -1;
+    for (int ipb = 12; ipb <= 16; ++ipb) {
+        const long blocks = (a.n_img + ipb - 1) / ipb, rounds = (blocks + cus - 1) / cus;
+        const long waste = (rounds * cus - blocks) * 1000 / (rounds * cus);           // idle share of the CUs' block slots, per mille
+        if (best < 0 || waste < best) best = waste, a.ipb = ipb;
     }
     constexpr size_t lds = (size_t)(20 + 16) * 34 * 128 + 1024 + 512;
     static bool attr = false;

@@ -35,22 +35,14 @@ constexpr int TR = TH + 2, TC = TW + 2;          // 10 x 34: m.cv1 region
 // mixes lanes of two planes (q and q + 1), and with equal bank phases the 16 pixels it covers fall on 16 disjoint bank quads.  T's
 // natural pitch (10 x 34 x 16 = 5 440 B = 16 banks off) put the two planes' pixels on top of each other: 2-way conflicts on every
 // tap read of m.cv2 (SQ_LDS_BANK_CONFLICT 48 % of the kernel's LDS cycles in round 2).
-#ifdef AICAM_C2F_OLD_LAYOUT
-constexpr int PX = XR * XC * 16, PT = TR * TC * 16, PY = TH * TW * 16;
-#else
 constexpr int PX = XR * XC * 16, PT = (TR * TC * 16 + 255) / 256 * 256, PY = TH * TW * 16;
-#endif
 static_assert(PX % 256 == 0 && PY % 256 == 0, "plane pitch");
 // X is written by S1 four planes of a pixel at a time (consecutive lanes = the four 16-byte channel groups of one pixel: a coalesced
 // 64-byte global read) -- with equal bank phases that is a 4-way store conflict.  Plane g therefore keeps pixel p in slot
 // p ^ 2g (inside its aligned group of 8): a store group (2 pixels x 4 planes) hits 8 distinct slots, and a read of 16 consecutive
 // pixels of plane q (S2) still covers the same aligned 16 slots, each once.
 __device__ __forceinline__ int x_slot(int p, int g) {
-#ifdef AICAM_C2F_OLD_LAYOUT
-    return p;
-#else
     return (p & ~7) | ((p & 7) ^ (2 * g));
-#endif
 }
 static_assert((XR * XC) % 8 == 0, "swizzle group");
 constexpr int LDS_X = 0, LDS_T = 0, LDS_Y1 = LDS_T + 2 * PT, LDS_Y0A = 4 * PX, LDS_Y0B = LDS_Y0A + 2 * PY;
@@ -247,7 +239,7 @@ bool conv_try_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, 
     a.w3 = reinterpret_cast<const half_t*>(m2.w), a.w4 = reinterpret_cast<const half_t*>(c2.w);
     a.b1 = c1.bias, a.b2 = m1.bias, a.b3 = m2.bias, a.b4 = c2.bias;
     a.x_cs = c1.x_cs, a.x_coff = c1.x_coff, a.y_cs = c2.y_cs, a.y_coff = c2.y_coff, a.H = H, a.W = W;
-    a.n_img = c1.M / (H * W), a.xcd_map = xcd_map_on();
+    a.n_img = c1.M / (H * W), a.xcd_map = 1;
     static bool attr = false;
     if (!attr) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f16_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));

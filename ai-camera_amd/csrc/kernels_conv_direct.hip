@@ -129,8 +129,7 @@ static void launch_c16(const ConvArgs& a, hipStream_t s) {
 }
 
 static bool try_c16(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_C16") != nullptr;
-    if (off || a.KH != 3 || a.KW != 3 || a.pad != 1 || a.Cin != 16 || a.act != 1 || a.out_f32 || (a.res_mode != 0 && a.res_mode != 2)) return false;
+    if (a.KH != 3 || a.KW != 3 || a.pad != 1 || a.Cin != 16 || a.act != 1 || a.out_f32 || (a.res_mode != 0 && a.res_mode != 2)) return false;
     if (a.Wo % 32 || a.Ho % 8 || a.Kp != 160 || (a.x_cs | a.x_coff | a.y_cs | a.y_coff | a.r_cs | a.r_coff) % 8) return false;
     if (a.stride == 1 && (a.Ho != a.H || a.Wo != a.W)) return false;
     if (a.stride == 2 && (a.Ho != (a.H + 1) / 2 || a.Wo != (a.W + 1) / 2)) return false;
@@ -259,16 +258,14 @@ static void launch_c32s2_tail(const ConvArgs& a, hipStream_t s) {
 }
 
 static bool try_c32s2_tail(const ConvArgs& a, hipStream_t s) {
-    static const int mode = [] { const char* e = getenv("AICAM_C32S2"); return e ? atoi(e) : 2; }();   // waves per block: 2 (default) or 4; 0: off (AICAM_NO_C32S2=1 as well)
     static const bool off = getenv("AICAM_NO_C32S2") != nullptr;
-    if (off || mode <= 0 || !a.w_tail || a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin != 32 || a.Cout != 64 || a.Kp != 288) return false;
+    if (off || !a.w_tail || a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin != 32 || a.Cout != 64 || a.Kp != 288) return false;
     if (a.act != 1 || a.res_mode != 0 || a.out_f32 || a.k_order != 0 || a.xs || a.x2 || a.n_dev || a.t_max || a.t_box) return false;
     if (a.t_cout > 64 || a.t_cout % 8 || a.t_kp != 64 || a.cout_pad < 64) return false;
     if (a.Ho % 16 || a.Wo % 16 || a.Ho != (a.H + 1) / 2 || a.Wo != (a.W + 1) / 2 || (a.x_cs | a.x_coff | a.t_y_cs | a.t_y_coff) % 8) return false;
     const long blocks = (long)(a.M / (a.Ho * a.Wo)) * (a.Wo / 16) * (a.Ho / 16);
     if (blocks < 512 || (long)a.M * std::max(a.t_y_cs, 1) >= (1l << 31)) return false;     // a few tiles: the wide-step kernel (one block per CU there)
-    if (mode == 4) launch_c32s2_tail<4>(a, s);
-    else launch_c32s2_tail<2>(a, s);
+    launch_c32s2_tail<2>(a, s);
     return true;
 }
 
@@ -583,8 +580,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_resident_kernel(const ConvArg
 }
 
 static bool try_c64_resident(const ConvArgs& a, hipStream_t s) {
-    static const int on = [] { const char* e = getenv("AICAM_C64R"); return e ? atoi(e) : 2; }();   // 0: off, 1: layers without residual only, 2 (default): also with residual (612 -> 774 TFLOP/s against the 4-wave patch kernel)
-    if (!on || (a.res_mode != 0 && on < 2) || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin != 64 || a.Cout != 64 || a.out_f32 || a.Kp != 576) return false;
+    // with or without the residual: 612 -> 774 TFLOP/s against the 4-wave patch kernel
+    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin != 64 || a.Cout != 64 || a.out_f32 || a.Kp != 576) return false;
     if (a.W % 32 || a.H % 8 || a.Ho != a.H || a.Wo != a.W || a.M < 1500000 || (long)a.M * a.x_cs >= (1l << 31) ||
         (long)a.M * a.y_cs >= (1l << 31) || (a.res_mode != 0 && (long)a.M * a.r_cs >= (1l << 31))) return false;
     if ((a.x_cs | a.x_coff | a.y_cs | a.y_coff | a.r_cs | a.r_coff) % 8) return false;
@@ -596,8 +593,7 @@ static bool try_c64_resident(const ConvArgs& a, hipStream_t s) {
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr = true;
         }
-        static const int split = [] { const char* e = getenv("AICAM_C64R_SPLIT"); return e ? std::max(1, atoi(e)) : 1; }();
-        const int nblk = conv_cu_budget() * split;
+        const int nblk = conv_cu_budget();
         hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, n_tiles, tiles_x, tiles_y, nblk);
         KCHECK();
     };
@@ -811,11 +807,9 @@ template <typename T>
 static bool try_patch(const ConvArgs& a, hipStream_t s) {
     // Measured on MI355X (profiles/): the patch form wins where Cout is small and M is large (ReID layer1);
     // for Cout >= 128 the 8-wave im2col tile is faster, and small maps are launch-bound either way.
-    static const bool off = getenv("AICAM_NO_PATCH") != nullptr;
-    static const bool all = getenv("AICAM_PATCH_ALL") != nullptr;
     static const bool c32 = getenv("AICAM_NO_PATCH_C32") == nullptr;   // Cin = Cout = 32 (YOLOv8n P3 bottlenecks): 244 -> 460 TFLOP/s
-    if (off || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8) return false;
-    if (a.M < 200000 && !all) return false;
+    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8) return false;
+    if (a.M < 200000) return false;
     if (a.k_order == 1) return false;                                       // (cc, kh, kw): only the implicit-GEMM kernels walk K that way
     const bool wide = a.Wo % 32 == 0 || (a.Wo % 16 != 0 && a.Wo >= 32);   // 8 x 32 tiles unless 16 x 16 tiles cover the map exactly
     if (a.k_order == 2) {                                                   // fp16, Cin = Cout = 64, W % 32 == 0 (launch_conv_igemm): the resident kernels' order
@@ -1016,7 +1010,7 @@ bool conv_try_pm_patch_tail(const ConvArgs& a, hipStream_t s) {
 // without a tail: 64 -> 64 on 40-row maps in 40 x 8 strips (YOLOv8n's P4 bottlenecks: eight layers on conv3x3_patch_kernel's 8 x 32 tiles,
 // which cover 1.6 maps).  On maps its 16 x 16 tiles cover exactly this form is no faster than that kernel (measured: 22.box0.0 348 against 354 us).
 bool conv_try_pm_patch(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_PATCH_C80") != nullptr || getenv("AICAM_NO_PM_STRIPS") != nullptr;
+    static const bool off = getenv("AICAM_NO_PATCH_C80") != nullptr;
     if (off || a.w_tail || !pm_patch_shape(a) || a.act != 1 || (a.res_mode != 0 && a.res_mode != 2)) return false;
     if (a.Cin == 64 && a.Cout == 64 && a.Kp == 576 && a.cout_pad >= 64 && a.Ho == 40 && a.Wo % 8 == 0) return launch_pm_patch<8, 9, 4, false, 40, 8, 5>(a, s);
     // (32 -> 32 on 80 x 80 maps -- YOLOv8n's P3 bottlenecks, which conv3x3_patch_kernel's 8 x 32 tiles cover 1.2 times -- as
@@ -1024,17 +1018,15 @@ bool conv_try_pm_patch(const ConvArgs& a, hipStream_t s) {
     //  four layers of 4.c2f.  They do not wait for their tiles: they read and write 64-byte slices of a 256-byte-pitch concat buffer.  Not kept.)
     // 128 -> 144 on 40-row maps: the merged first convs of YOLOv8n's 40 x 40 detect level (22.box1.0 + 22.cls1.0), which the implicit GEMM runs on a
     // 256 x 144 tile with 36 accumulator tiles per wave, one wave per SIMD.  Sixteen chunks per pixel at a pitch of 17 (272 bytes: the 16 lanes of a
-    // fragment read sit four banks apart), nine channel tiles (the odd last one keeps the identity map), one block per CU.  AICAM_NO_PM144=1: off
-    static const bool no144 = getenv("AICAM_NO_PM144") != nullptr;
-    if (!no144 && a.res_mode == 0 && a.Cin == 128 && a.Cout == 144 && a.Kp == 1152 && a.cout_pad >= 144 && a.Ho == 40 && a.Wo % 8 == 0)
+    // fragment read sit four banks apart), nine channel tiles (the odd last one keeps the identity map), one block per CU.
+    if (a.res_mode == 0 && a.Cin == 128 && a.Cout == 144 && a.Kp == 1152 && a.cout_pad >= 144 && a.Ho == 40 && a.Wo % 8 == 0)
         return launch_pm_patch<16, 17, 9, false, 40, 8, 5>(a, s);
     return false;
 }
 
 // the Cout = 64 patch kernel with a 1x1 tail (same eligibility as try_patch)
 bool conv_try_patch_tail(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_PATCH") != nullptr;
-    if (off || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8 || a.M < 200000 || a.Cout != 64 || a.k_order != 0) return false;
+    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8 || a.M < 200000 || a.Cout != 64 || a.k_order != 0) return false;
     const bool wide = a.Wo % 32 == 0 || (a.Wo % 16 != 0 && a.Wo >= 32);
     if (wide) return launch_patch<half_t, 4, 4, 4, 1, 8, 32, 3, 3, true>(a, s);
     return launch_patch<half_t, 4, 4, 4, 1, 16, 16, 3, 3, true>(a, s);
@@ -1376,8 +1368,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 bool reid_stem2_usable(int H, int W) {
-    static const bool v1 = [] { const char* e = getenv("AICAM_STEM"); return e && e[0] == 'v' && e[1] == '1'; }();
-    return !v1 && W == 64 && H % 16 == 0 && (size_t)(H + 2) * 66 * 8 <= 150 * 1024;
+    return W == 64 && H % 16 == 0 && (size_t)(H + 2) * 66 * 8 <= 150 * 1024;
 }
 
 void launch_reid_stem_pool(const void* x, const void* w, const float* bias, void* y, int n, int H, int W, int Kp, int y_cs,

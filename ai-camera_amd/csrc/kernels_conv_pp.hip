@@ -208,9 +208,7 @@ __global__ __launch_bounds__(512) void conv_igemm_pp_kernel(const ConvArgs a) {
                 for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const frag_t*>(base + woff[j]);
 #pragma unroll
                 for (int i = 0; i < MT; ++i) xf[i] = *reinterpret_cast<const frag_t*>(base + xoff[i]);
-#ifndef AICAM_PP_READS_LAST
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 issue((u + NSTAGE - 2) % NSTAGE);
                 wait_vmcnt<(NSTAGE - 3) * LPS>();      // step+1 has landed (this wave's part)
                 __builtin_amdgcn_s_barrier();
@@ -314,7 +312,7 @@ static void launch_pp(const ConvArgs& a, hipStream_t s) {
 // into disjoint bank ranges (pitch * 16 B = TW * 16 B mod 256).
 // (ppp_ipix_pad, lane_here: conv_common.hpp -- shared with the software-pipelined form, kernels_conv_sp.hip)
 template <typename T, int MT, int NT, int WM, int WN, int TH, int TW, int NSTAGE, bool X2 = false>
-__global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ny, int run, int pf) {
+__global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ny, int run) {
     constexpr int CH = 16 / (int)sizeof(T);
     constexpr int BKE = 4 * CH;
     constexpr int RP = 128;
@@ -332,18 +330,11 @@ __global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a,
     constexpr int EOFF = RING + NSTAGE * WSTAGE, NE = BM / 128;        // second source: buffer offset, LDS-DMA passes per chunk
     static_assert(WM * WN == 8 && BM % TPIX == 0 && NPASS <= 11 - NSTAGE && TW % 4 == 0 && NSTAGE >= 4, "geometry");
     static_assert(!X2 || (NSTAGE == 4 && NPASS <= 5 && (NE == 2 || NE == 4) && MT % 2 == 0), "second source: slots at taps 6..8, counted waits of the 4-stage ring");
-    // LEAN (4-stage ring, no second source): a LOAD segment whose tap has no patch pass due issues its weight loads only.  The form before
-    // kept every segment at B_PER + 1 loads with a zero-page load into a dummy slot, so that ONE counted wait fitted all taps; an LDS-DMA
-    // costs 60-185 cycles to issue, 9 - NPASS of a chunk's nine were stand-ins, and a wave's LOAD and COMPUTE segments are serial.  The
-    // wait of a segment still lets exactly its OWN loads stay in flight -- B_PER or B_PER + 1, a compile-time property of the tap.
-    // Measured: nothing (layer2 / 3 / 4 shapes against the build before both changes, same box each: +2.4 / +1.8 / +1.8 % with the cheaper
-    // integer work of issue_patch AND this, +2.5 / +1.6 / +1.7 % with the integer work alone): a zero-page LDS-DMA is cheap to issue after
-    // all.  Kept as a build switch (-DAICAM_PPP_LEAN), off.
-#if defined(AICAM_PPP_LEAN) && !defined(AICAM_PPP_PF_BUILD)
-    constexpr bool LEAN = !X2 && NSTAGE == 4;
-#else
-    constexpr bool LEAN = false;
-#endif
+    // (A LOAD segment whose tap has no patch pass due issuing its weight loads only, instead of a zero-page load into a dummy slot that keeps
+    // every segment at B_PER + 1 loads so that ONE counted wait fits all taps -- an LDS-DMA costs 60-185 cycles to issue, 9 - NPASS of a chunk's
+    // nine are stand-ins, and a wave's LOAD and COMPUTE segments are serial.  Measured: nothing (layer2 / 3 / 4 shapes against the build before,
+    // same box each: +2.4 / +1.8 / +1.8 % with the cheaper integer work of issue_patch AND this, +2.5 / +1.6 / +1.7 % with the integer work
+    // alone): a zero-page LDS-DMA is cheap to issue after all.  Not kept.)
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -405,30 +396,6 @@ __global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a,
         asm volatile("" : "+v"(src));
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + 2 * PBUF + wv * 1024), 16, 0, 0);
     };
-    // A residual tile is 128 KB that the epilogue pulls from HBM with nothing left to hide it behind.  Optional (pf != 0, see launch_pp_patch:
-    // measured, no net gain, off): the spare LDS-DMA slots of the tile's LAST chunk (bit `tap` of pf) carry it towards the L2 a few K-steps
-    // ahead: pass k, thread t touches 128-byte line k * 512 + t of the tile's rows, the 16 bytes land in the dummy slot and are never read.
-    // Same instruction count per segment: the counted waits do not change.
-    constexpr int LPP = BN * (int)sizeof(T) / 128 > 0 ? BN * (int)sizeof(T) / 128 : 1, NRP = BM * LPP / 512;
-    auto issue_res = [&](int k) {
-        const int L = k * 512 + wv * 64 + lane_here();
-        const int m = L / LPP, part = L - m * LPP;
-        int il, ly, lx;
-        if constexpr (G == 1) {
-            il = m / TPIX;
-            const int rem = m - il * TPIX;
-            ly = rem / TW, lx = rem - ly * TW;
-        } else {
-            const int tl = m >> 4, rr = m & 15;
-            il = (tl / TH) * G + rr / TW, ly = tl % TH, lx = rr % TW;
-        }
-        const int img = img0 + il;
-        const T* src = (k < NRP && m < BM && img < n_img) ? reinterpret_cast<const T*>(a.res) + (((img * a.Ho + oy0 + ly) * a.Wo + ox0 + lx) * a.r_cs + a.r_coff + n0 + part * (128 / (int)sizeof(T)))
-                                                          : zero;
-        asm volatile("" : "+v"(src));
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + 2 * PBUF + wv * 1024), 16, 0, 0);
-    };
-
     // ---- weight stream: row r0 + RP*j of the tile's channel tile, K offset of step (chunk c, tap) = tap*Cin + c*BKE.  The stream runs
     // NSTAGE - 2 steps ahead of the compute and simply continues with the next tile of the run (n0_w: the channel tile it fetches for)
     const int slot = t & 3, r0 = t >> 2;
@@ -509,10 +476,9 @@ __global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a,
 #pragma unroll
     for (int st = 0; st < NSTAGE - 2; ++st) {
         issue_w();
-        if (st && !LEAN) issue_dummy();        // (not LEAN) every set in flight has LPS loads: the counted waits below rely on it
+        if (st) issue_dummy();                 // every set in flight has LPS loads: the counted waits below rely on it
     }
-    if constexpr (LEAN) wait_vmcnt<B_PER>();   // patch chunk 0 and the weights of step 0 have landed (this wave's part): only step 1's weights may be in flight
-    else wait_vmcnt<(NSTAGE - 3) * LPS>();
+    wait_vmcnt<(NSTAGE - 3) * LPS>();
     __builtin_amdgcn_s_barrier();
     PP_STAMP(1);
 
@@ -588,20 +554,13 @@ __global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a,
             issue_w();
             constexpr bool SLOT = tap >= 1 && tap <= NPASS;          // this tap's segment carries a patch pass
             if (SLOT && more) issue_patch(SLOT ? tap - 1 : 0, BUF ^ 1, noff, p_im, p_oy, p_ox);
-            else if constexpr (!EP && (SLOT || !LEAN)) {              // LEAN: a tap without a pass issues NO stand-in (its wait is one lower)
-#ifdef AICAM_PPP_PF_BUILD                               // (the residual prefetch experiment: measured, no net gain; not in the default build's K loop)
-                if (!X2 && !inner && ((pf >> tap) & 1)) issue_res(__builtin_popcount(pf & ((1 << tap) - 1)));
-                else
-#endif
-                issue_dummy();
-            }
+            else if constexpr (!EP) issue_dummy();
             if constexpr (EP) {
                 if constexpr (NE == 4) {
                     if (tap == 6) { issue_e(0, c, c < ns2); issue_e(1, c, c < ns2); } else issue_e(tap - 5, c, c < ns2);
                 } else issue_e(tap - 7, c, c < ns2);
             }
-            if constexpr (LEAN) wait_vmcnt<B_PER + (SLOT ? 1 : 0)>();         // everything older than THIS segment's own loads has landed
-            else if constexpr (X2 && NE == 4 && tap == 6) wait_vmcnt<(NSTAGE - 3) * LPS + 1>();
+            if constexpr (X2 && NE == 4 && tap == 6) wait_vmcnt<(NSTAGE - 3) * LPS + 1>();
             else wait_vmcnt<(NSTAGE - 3) * LPS>();
             __builtin_amdgcn_s_barrier();
             // ---- COMPUTE segment
@@ -677,15 +636,14 @@ static bool launch_pp_patch(const ConvArgs& a, hipStream_t s) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    // tiles per block: at most AICAM_PPP_RUN (default 6).  Same box, 15 360 crops: layer2 conv1 1 993 (one tile per block, the kernel before) ->
+    // tiles per block: at most 6.  Same box, 15 360 crops: layer2 conv1 1 993 (one tile per block, the kernel before) ->
     // 1 975 / 1 945 / 1 912 us at runs of 1 / 4 / 6; with a residual 2 257 -> 2 256 (its 9 us epilogue is what is left); layer3 / 4 -2 % / 0
-    static const int run_max = [] { const char* e = getenv("AICAM_PPP_RUN"); return e ? std::max(1, atoi(e)) : 6; }();
     const int ny = ceil_div(a.Cout, BN);
     const long ntiles = (long)ceil_div(n_img, NI) * tiles_x * tiles_y * ny;
     int run = 1;                                  // (second source: one tile per block)  the longest run that does not add a round of tiles (256 CUs, one block each) and leaves >= 4 rounds of blocks
     {
         long best = -1;
-        for (int r = 1; r <= (X2 ? 1 : run_max); ++r) {
+        for (int r = 1; r <= (X2 ? 1 : 6); ++r) {
             const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
             if (r > 1 && rounds < 4) break;
             const long cost = rounds * r;                 // tile times until the last block ends
@@ -697,37 +655,28 @@ static bool launch_pp_patch(const ConvArgs& a, hipStream_t s) {
         const int on = 1;
         HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_pp_times_on), &on, sizeof(int)));
     }
-    // residual prefetch: taps of the last chunk whose spare LDS-DMA slot carries a pass of the residual tile (AICAM_PPP_PF=0xC0: taps 6 and 7).
-    // OFF by default: measured on the 512 x 128 tile (AICAM_PP_TIMES, one tile per block) it takes 2 us off the epilogue (9.2 -> 7.2 us) and puts
-    // 2.5 us onto the K loop (27.6 -> 30.3 us) -- the pass is a load from HBM in the in-order vmcnt queue, and the next segment's counted wait
-    // stands behind it where it used to stand behind a zero-page hit; layer2 / 3 / 4 conv2 alone: 2 432 / 2 021 / 1 894 us off, 2 452 / 2 019 / 1 889 on
-    static const int pf_env = [] { const char* e = getenv("AICAM_PPP_PF"); return e ? (int)strtol(e, nullptr, 0) : 0; }();
-    constexpr int NPASS_ = NPASS;
-    const int pf = (!X2 && a.res_mode != 0 && a.res && sizeof(T) == 2 && BN * sizeof(T) % 128 == 0) ? (pf_env & 0x1ff & ~(((1 << NPASS_) - 1) << 1)) : 0;
+    // (A residual prefetch -- the spare LDS-DMA slots of the tile's last chunk carrying passes of the residual tile towards the L2 -- was measured
+    // on the 512 x 128 tile (AICAM_PP_TIMES, one tile per block): 2 us off the epilogue (9.2 -> 7.2 us), 2.5 us onto the K loop (27.6 -> 30.3 us)
+    // -- the pass is a load from HBM in the in-order vmcnt queue, and the next segment's counted wait stands behind it where it used to stand
+    // behind a zero-page hit; layer2 / 3 / 4 conv2 alone: 2 432 / 2 021 / 1 894 us without, 2 452 / 2 019 / 1 889 with.  Not kept.)
     const int nblk = (int)ceil_div(ntiles, (long)run);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, tiles_x, tiles_y, ny, run, pf);
+    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, tiles_x, tiles_y, ny, run);
     if (times) { KCHECK(); pp_times_report(s, nblk); }
     KCHECK();
     return true;
 }
 
-// 3x3/s1/p1 layers whose map tiles exactly: pick the tile by map shape and Cout (ReID layer1..4 shapes and their multiples).
-// bit 0: Cout 64 (slower than the 4-wave patch kernel: 16 MFMAs per segment), 1: Cout 128, 2: Cout % 256, 3: deeper ring (no gain)
-static int ppp_mode() {
-    static const int mode = [] { const char* e = getenv("AICAM_PPP"); return e ? atoi(e) : 6; }();
-    return mode;
-}
-// The layer SHAPES this kernel takes (a property of the graph, not of the batch): 1 = Cout 64 tile, 2 = Cout 128, 3 = Cout % 256 on
-// 16 x 8 tiles, 4 = on 8 x 4 tiles; 0 = not one of them.  Such a layer is walked chunk-major by EVERY conv kernel (ConvArgs::k_order = 1).
+// 3x3/s1/p1 layers whose map tiles exactly: pick the tile by map shape and Cout (ReID layer2..4 shapes and their multiples).  (A Cout 64 tile
+// was slower than the 4-wave patch kernel -- 16 MFMAs per segment -- and a deeper weight ring gained nothing.)
+// The layer SHAPES this kernel takes (a property of the graph, not of the batch): 2 = Cout 128, 3 = Cout % 256 on 16 x 8 tiles, 4 = on
+// 8 x 4 tiles; 0 = not one of them.  Such a layer is walked chunk-major by EVERY conv kernel (ConvArgs::k_order = 1).
 template <typename T>
 static int pp_patch_shape(const ConvArgs& a) {
     constexpr int BKE = 64 / (int)sizeof(T);
-    const int mode = ppp_mode();
-    if (!mode || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin % (2 * BKE) || a.Ho != a.H || a.Wo != a.W) return 0;
+    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin % (2 * BKE) || a.Ho != a.H || a.Wo != a.W) return 0;
     const int c = a.Cout;
-    if (c == 64 && (mode & 1)) return (a.H % 16 == 0 && a.W % 32 == 0) ? 1 : 0;
-    if (c == 128 && (mode & 2)) return (a.H % 32 == 0 && a.W % 16 == 0) ? 2 : 0;
-    if (c % 256 == 0 && (mode & 4)) return (a.H % 16 == 0 && a.W % 8 == 0) ? 3 : ((a.H % 8 == 0 && a.W % 4 == 0) ? 4 : 0);
+    if (c == 128) return (a.H % 32 == 0 && a.W % 16 == 0) ? 2 : 0;
+    if (c % 256 == 0) return (a.H % 16 == 0 && a.W % 8 == 0) ? 3 : ((a.H % 8 == 0 && a.W % 4 == 0) ? 4 : 0);
     return 0;
 }
 
@@ -738,7 +687,6 @@ static bool try_pp_patch(const ConvArgs& a, hipStream_t s) {
     if (!shape) return false;
     if ((long)a.M * a.x_cs >= (1l << 31)) return false;                       // 32-bit element offsets inside the kernel
     const int c = a.Cout;
-    const bool deep = ppp_mode() & 8;
     if (a.x2) {                                     // a second source (conv_x2_supported: shapes 2, 3 and 4)
         if (shape == 2 && a.M / 512 >= pp_min) return launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 4, true>(a, s);
         if (shape == 3 && (long)(a.M / 256) * (c / 256) >= pp_min) return launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 4, true>(a, s);
@@ -749,11 +697,10 @@ static bool try_pp_patch(const ConvArgs& a, hipStream_t s) {
         if ((shape == 2 && a.M / 512 >= pp_min) || (shape >= 3 && (long)(a.M / 256) * (c / 256) >= pp_min))
             if (conv_try_sp_patch(a, shape, s)) return true;
     }
-    if (shape == 1 && a.M / 512 >= pp_min) return deep ? launch_pp_patch<T, 4, 4, 8, 1, 16, 32, 6>(a, s) : launch_pp_patch<T, 4, 4, 8, 1, 16, 32, 4>(a, s);
-    if (shape == 2 && a.M / 512 >= pp_min) return deep ? launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 6>(a, s) : launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 4>(a, s);
+    if (shape == 2 && a.M / 512 >= pp_min) return launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 4>(a, s);
     if (shape >= 3 && (long)(a.M / 256) * (c / 256) >= pp_min) {
-        if (shape == 3) return deep ? launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 6>(a, s) : launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 4>(a, s);
-        return deep ? launch_pp_patch<T, 8, 4, 2, 4, 8, 4, 5>(a, s) : launch_pp_patch<T, 8, 4, 2, 4, 8, 4, 4>(a, s);
+        if (shape == 3) return launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 4>(a, s);
+        return launch_pp_patch<T, 8, 4, 2, 4, 8, 4, 4>(a, s);
     }
     return false;
 }
@@ -771,14 +718,12 @@ int conv_pp_patch_shape(int dtype, const ConvArgs& a) {
 // measured on MI355X (tools/conv_bench.py, profiles/): +17..19% on ReID layer3/4, +14% on layer2, a loss at K < 512.
 template <typename T>
 static bool try_pp(const ConvArgs& a, hipStream_t s) {
-    static const bool pp = getenv("AICAM_NO_PP") == nullptr;
     static const int pp_min = [] { const char* e = getenv("AICAM_PP_MIN"); return e ? atoi(e) : 200; }();
     // 18 K-steps: ReID layer2.0.conv1 (3x3 / 2, 64 -> 128, K = 576) takes the 512 x 128 ping-pong tile: 1 058 -> 948 us per 7 680 crops
     // against the 8-wave 256 x 128 LDS-DMA tile (tools/conv_bench.py 64 32 64 128 3 7680 1 0 2); below that the short loop loses
-    static const int pp128_k = [] { const char* e = getenv("AICAM_PP128_K"); return e ? atoi(e) : 18; }();
     constexpr int BKE_ = 64 / (int)sizeof(T);
     const int c = a.Cout;
-    if (!pp || a.Cin % BKE_ != 0 || !(a.Kp >= 16 * BKE_ || pp_min == 0)) return false;
+    if (a.Cin % BKE_ != 0 || !(a.Kp >= 16 * BKE_ || pp_min == 0)) return false;
     if constexpr (sizeof(T) == 2) {                 // stride-2 3x3 layers of the patch kernels' maps: the space-to-depth patch form (kernels_conv_sp.hip)
         if (a.k_order == 3 && ((c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= pp_min) || (c == 128 && ceil_div(a.M, 512) >= pp_min)))
             if (conv_try_s2_patch(a, s)) return true;
@@ -787,7 +732,7 @@ static bool try_pp(const ConvArgs& a, hipStream_t s) {
         launch_pp<T, 8, 4, 2, 4, 4>(a, s);
         return true;
     }
-    if (c == 128 && (a.Kp >= pp128_k * BKE_ || pp_min == 0) && ceil_div(a.M, 512) >= pp_min) {              // 512 px x 128 ch
+    if (c == 128 && (a.Kp >= 18 * BKE_ || pp_min == 0) && ceil_div(a.M, 512) >= pp_min) {              // 512 px x 128 ch
         launch_pp<T, 8, 4, 4, 2, 4>(a, s);
         return true;
     }

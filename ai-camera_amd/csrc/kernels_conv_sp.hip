@@ -38,7 +38,7 @@
 
 namespace aic {
 
-template <int MT, int NT, int WM, int WN, int TH, int TW, bool SKEW>
+template <int MT, int NT, int WM, int WN, int TH, int TW>
 __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a, int ny, int run) {
     typedef half_t T;
     constexpr int NSTAGE = 4;
@@ -62,7 +62,6 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
 
     const int t = threadIdx.x;
     const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-    const bool late = SKEW && wv >= 4;
     const int HW = a.H * a.W;
     const int n_img = a.n_dev ? min(a.M / HW, a.n_dev[0]) : a.M / HW;     // device-side item count: the grid was sized for a bound
     // tiles: (image group, channel tile), channel tile fastest; a block takes a run of `run` consecutive tiles
@@ -217,10 +216,6 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
                 if constexpr (tap < NPASS) issue_patch(tapc, BUF ^ 1);
                 else issue_dummy();
             }
-            if constexpr (SKEW && i == MT / 2 - 1) {          // mid-body barrier: waves 4 .. 7 run half a body behind (see the tile loop)
-                __builtin_amdgcn_s_waitcnt(0x0F70 | LPS);     // vmcnt(LPS): everything older than this body's own loads has landed
-                __builtin_amdgcn_s_barrier();
-            }
             __builtin_amdgcn_sched_barrier(0);
         });
         // the waits as BUILTINS, not inline asm: the compiler's own wait-count pass must see them, or it protects the first MFMA of the next
@@ -239,16 +234,11 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
 #pragma unroll
         for (int i = 0; i < MT; ++i) read_x(i, 0, 0);
         __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0)
-        // SKEW: waves 4 .. 7 run half a body behind waves 0 .. 3 (one extra barrier here, one for the early half behind the loop).  Every wave
-        // waits for its older loads in front of BOTH barriers of a body, so a late wave's part of step k + 1 has landed before barrier 2k - 1
-        // (its mid-body k - 1), which an early wave passes before it reads step k + 1 in body k
-        if (late) __builtin_amdgcn_s_barrier();
         for (int c = 0; c < nchunks; c += 4) {     // Cin / 32 is a multiple of 4 for every layer that reaches this kernel
             static_for<4>([&](auto c4c) {
                 static_for<9>([&](auto tapc) { body(c + decltype(c4c)::value, c4c, tapc); });
             });
         }
-        if (SKEW && !late) __builtin_amdgcn_s_barrier();      // every wave has executed the same number of barriers: both halves store together
         if (!has_next) wait_vmcnt<0>();
         // the MFMAs are inline asm: the compiler does not know that the accumulators come out of the matrix pipe (up to 18 wait states
         // before a VALU may read them); the barrier and the row arithmetic below are far more than that, two s_nop make it independent of them
@@ -289,20 +279,18 @@ static bool launch_sp_patch(const ConvArgs& a, hipStream_t s) {
     if (a.H != TH || a.W != TW || a.Ho != a.H || a.Wo != a.W || a.Cout % BN) return false;            // whole-image tiles, whole channel tiles
     if ((long)a.M * a.x_cs * 2 >= (1l << 32) || (long)a.Cout * a.Kp * 2 >= (1l << 32)) return false;   // 32-bit byte strides inside the kernel
     const int n_img = a.M / (a.Ho * a.Wo);
-    static const bool skew = getenv("AICAM_SP_SKEW") != nullptr;
-    auto kfn = skew ? conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW, true> : conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW, false>;
+    auto kfn = conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW>;
     static bool attr = false;
     if (!attr) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    static const int run_max = [] { const char* e = getenv("AICAM_PPP_RUN"); return e ? std::max(1, atoi(e)) : 6; }();
     const int ny = a.Cout / BN;
     const long ntiles = (long)ceil_div(n_img, NI) * ny;
-    int run = 1;                                  // the longest run that does not add a round of tiles (256 CUs, one block each) and leaves >= 4 rounds of blocks
+    int run = 1;                                  // the longest run (at most 6 tiles) that does not add a round of tiles (256 CUs, one block each) and leaves >= 4 rounds of blocks
     {
         long best = -1;
-        for (int r = 1; r <= run_max; ++r) {
+        for (int r = 1; r <= 6; ++r) {
             const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
             if (r > 1 && rounds < 4) break;
             const long cost = rounds * r;
@@ -326,7 +314,7 @@ static bool launch_sp_patch(const ConvArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // v6 for the STRIDE-2 3x3 convs (ReID layerN.0.conv1: 64 -> 128 on 64 x 32, 128 -> 256 on 32 x 16, 256 -> 512 on 16 x 8 maps), which the
 // im2col kernels run L2-bound (see the note above): the PATCH form on the SPACE-TO-DEPTH view of the input, every input byte fetched once.
-// Measured against v4 on 15 360 crops, each layer alone (tools/ab_s2d.sh): layer2.0 1 748 against 1 918 us (663 TFLOP/s; its HBM floor -- 4 GB in,
+// Measured against v4 on 15 360 crops, each layer alone (tools/conv_bench.py): layer2.0 1 748 against 1 918 us (663 TFLOP/s; its HBM floor -- 4 GB in,
 // 2 GB out -- is ~1.0 ms: a tile is only 18 K-steps and its 128 KB epilogue is not overlapped), layer3.0 1 169 against 1 215 us, layer4.0 slower.
 //
 // Row 2i + di - 1 of the input is row a = i - 1 (di = 0) or a = i (di = 1, 2) of the parity plane pi = 1, 0, 1: with z[a][b][(pi, pj)][c] =
@@ -345,7 +333,6 @@ static bool launch_sp_patch(const ConvArgs& a, hipStream_t s) {
 // for the patch's.  Everything else as conv3x3_sp_patch_kernel.
 template <int NPASS> struct S2dSched;          // passes issued in body b for target t: 0 = c1 (plane 1,0), 1 = c2 (0,1), 2 = c3 (0,0), 3 = c0 of the NEXT period
 template <> struct S2dSched<5> { static constexpr int n[9][4] = {{1,1,0,0},{1,1,0,0},{0,2,0,0},{0,0,2,0},{0,0,3,0},{0,0,0,3},{0,0,0,2},{2,0,0,0},{1,1,0,0}}; };
-template <> struct S2dSched<4> { static constexpr int n[9][4] = {{1,1,0,0},{1,1,0,0},{0,1,0,0},{0,1,1,0},{0,0,2,0},{0,0,1,2},{0,0,0,2},{1,0,0,0},{1,0,0,0}}; };
 template <> struct S2dSched<3> { static constexpr int n[9][4] = {{1,0,0,0},{0,1,0,0},{0,1,0,0},{0,1,1,0},{0,0,2,0},{0,0,0,2},{0,0,0,1},{1,0,0,0},{1,0,0,0}}; };
 // (bodies 7 and 8 fetch c1 / c2 of the NEXT period; the counts per target sum to NPASS over the cyclic window that ends two bodies before
 //  the chunk's first fragment read: c1 [7, 8, 0, 1], c2 [8, 0 .. 3], c3 [3 .. 5], next c0 [5, 6])
@@ -619,13 +606,12 @@ static bool launch_s2_patch(const ConvArgs& a, hipStream_t s) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    static const int run_max = [] { const char* e = getenv("AICAM_PPP_RUN"); return e ? std::max(1, atoi(e)) : 6; }();
     const int ny = a.Cout / BN;
     const long ntiles = (long)ceil_div(n_img, NI) * ny;
     int run = 1;
     {
         long best = -1;
-        for (int r = 1; r <= run_max; ++r) {
+        for (int r = 1; r <= 6; ++r) {
             const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
             if (r > 1 && rounds < 4) break;
             const long cost = rounds * r;
@@ -639,32 +625,27 @@ static bool launch_s2_patch(const ConvArgs& a, hipStream_t s) {
 }
 
 // The stride-2 shapes (a property of the layer, not of the batch: such a layer is walked in k_order 3 by EVERY kernel): 3x3 / 2 / 1 convs whose
-// OUTPUT is one of the patch kernels' maps -- 1: Cout 128 on 32 x 16, 2: Cout % 256 on 16 x 8, 3: on 8 x 4 -- with Cin a multiple of 64.
+// OUTPUT is one of the patch kernels' maps -- 1: Cout 128 on 32 x 16, 2: Cout % 256 on 16 x 8 -- with Cin a multiple of 64.
 int conv_s2_patch_shape(const ConvArgs& a) {
-    static const bool on = getenv("AICAM_NO_S2D") == nullptr && getenv("AICAM_NO_SP") == nullptr;
-    if (!on || a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin % 64 || a.Kp != 9 * a.Cin || a.x2 || a.xs || a.w_tail) return 0;
+    if (a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin % 64 || a.Kp != 9 * a.Cin || a.x2 || a.xs || a.w_tail) return 0;
     if (a.H != 2 * a.Ho || a.W != 2 * a.Wo) return 0;
     if (a.Cout == 128 && a.Ho == 32 && a.Wo == 16) return 1;
     if (a.Cout % 256 == 0 && a.Ho == 16 && a.Wo == 8) return 2;
     // (8 x 4 output maps, ReID layer4.0.conv1: built and measured -- 1 135 against v4's 1 008 us per 15 360 crops; the map is small enough for the
-    //  im2col gather to stay in the L2.  Not taken: AICAM_S2D_ALL=1 takes it.)
-    static const bool all = getenv("AICAM_S2D_ALL") != nullptr;
-    if (all && a.Cout % 256 == 0 && a.Ho == 8 && a.Wo == 4) return 3;
+    //  im2col gather to stay in the L2.  Not kept.)
     return 0;
 }
 bool conv_try_s2_patch(const ConvArgs& a, hipStream_t s) {           // fp16, a batch large enough for one-block-per-CU tiles (the caller's check)
     const int shape = conv_s2_patch_shape(a);
     if (shape == 1) return launch_s2_patch<4, 2, 32, 16>(a, s);
     if (shape == 2) return launch_s2_patch<2, 4, 16, 8>(a, s);
-    if (shape == 3) return launch_s2_patch<2, 4, 8, 4>(a, s);
     return false;
 }
 
 // shape: conv_pp_patch_shape()'s (2 = Cout 128 on 32 x 16 maps, 3 / 4 = Cout % 256 on 16 x 8 / 8 x 4 maps); the caller has checked that the
-// batch is large enough for one-block-per-CU tiles.  AICAM_NO_SP=1: v5 everywhere (A/B).
+// batch is large enough for one-block-per-CU tiles.
 bool conv_try_sp_patch(const ConvArgs& a, int shape, hipStream_t s) {
-    static const bool on = getenv("AICAM_NO_SP") == nullptr;
-    if (!on || a.x2 || a.Cin % 128) return false;
+    if (a.x2 || a.Cin % 128) return false;
     if (shape == 2) return launch_sp_patch<8, 4, 4, 2, 32, 16>(a, s);
     if (shape == 3) return launch_sp_patch<8, 4, 2, 4, 16, 8>(a, s);
     if (shape == 4) return launch_sp_patch<8, 4, 2, 4, 8, 4>(a, s);

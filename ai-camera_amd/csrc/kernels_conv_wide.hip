@@ -235,10 +235,9 @@ static KTab ktab_for(const ConvArgs& a) {
     return r;
 }
 
-// The layers this kernel takes; `blocks`: the grid v2 would launch for the same tile.  AICAM_WIDE_BLOCKS: the largest grid (0: off)
+// The layers this kernel takes; `blocks`: the grid v2 would launch for the same tile (at most 256)
 static bool conv_wide_ok(const ConvArgs& a, long blocks, bool tail) {
-    static const int max_blocks = [] { const char* e = getenv("AICAM_WIDE_BLOCKS"); return e ? atoi(e) : 256; }();
-    if (blocks > max_blocks) return false;
+    if (blocks > 256) return false;
     if (a.xs || a.n_dev || (a.w_tail != nullptr) != tail) return false;
     if (a.k_order < 0 || a.k_order > 3) return false;
     if ((a.k_order == 2) != (a.bias_init != nullptr) || (a.k_order == 2 && (a.KH != 3 || a.x2 || tail))) return false;      // order 2 comes with the bias in front
@@ -271,7 +270,7 @@ static bool try_wide(const ConvArgs& a, hipStream_t s) {
     constexpr int STAGE = (BM + BNP) * 64;
     dim3 grid(ceil_div(a.M, BM), ceil_div(a.Cout, BN));
     if (!conv_wide_ok(a, (long)grid.x * grid.y, TAIL)) return false;
-    // Ring shape (tools/ab_wide.sh, ReID layer4 at 28 crops, 60.7 us on v2): G = 4 with 3 or 5 groups in the ring 32.3 / 32.8 us, G = 2 with 10
+    // Ring shape (tools/conv_bench.py, ReID layer4 at 28 crops, 60.7 us on v2): G = 4 with 3 or 5 groups in the ring 32.3 / 32.8 us, G = 2 with 10
     // groups 34.3 us -- the depth does not matter.  At most 96 .. 120 KB of LDS, so that a block of another stream's kernel still fits beside it.
     constexpr int G = STAGE <= 8 * 1024 ? 4 : 2;
     if constexpr (!TAIL && (BN == 64 || BN == 128) && WN == 2) {          // (the tiles the ReID trunk's second-source layers take at these sizes)

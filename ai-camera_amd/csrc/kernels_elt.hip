@@ -233,8 +233,7 @@ static inline int vecn(int dtype) { return dtype == AIC_F16 ? 8 : 4; }
 
 void launch_sppf_pool(int dtype, const EltArgs& a, hipStream_t s) {
     const size_t lds = (size_t)4 * a.h * a.w * 16;
-    static const bool direct = getenv("AICAM_SPPF_DIRECT") != nullptr;
-    if (!direct && lds <= 64 * 1024 && a.n > 0) {      // in-place safe: a block reads its whole (image, chunk) map before it writes
+    if (lds <= 64 * 1024 && a.n > 0) {      // in-place safe: a block reads its whole (image, chunk) map before it writes
         const int blocks = a.n * (a.c / vecn(dtype));
         if (dtype == AIC_F16) hipLaunchKernelGGL(sppf_pool_sep_kernel<half_t>, dim3(blocks), dim3(256), lds, s, a);
         else hipLaunchKernelGGL(sppf_pool_sep_kernel<float>, dim3(blocks), dim3(256), lds, s, a);

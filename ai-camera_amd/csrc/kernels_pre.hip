@@ -371,8 +371,7 @@ void launch_letterbox_u8(const uint8_t* frame, const LetterboxGeom& g, const int
 void launch_crop_resize(const uint8_t* frames, int h, int w, const float* boxes, const int* frame_of, int n,
                         const int* n_dev, int out_h, int out_w, int mode, int dtype, void* out, int* valid, hipStream_t s, bool slack) {
     if (n <= 0) return;
-    static const bool no_wide = getenv("AICAM_CROP_BYTES") != nullptr;
-    const int wide = slack && !no_wide;
+    const int wide = slack;
     AIC_REQUIRE(out_w <= 240, AIC_ERR_CAPACITY, "crop width above 240 is not supported");
     dim3 grid(ceil_div(out_h, CROP_ROWS), n);
     if (dtype == AIC_F16)

@@ -271,68 +271,8 @@ __global__ __launch_bounds__(256) void cosine_min_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused per-frame kernels of the tracker (one stream, three launches per frame).
-//
-// trk_assoc_kernel: block t = one live track. Wave 0 runs the Kalman predict in place
-// (kalman_filter.py:85-120), then all threads walk the detections: squared Mahalanobis distance
-// (kalman_filter.py:206-249), 1-IoU (matching.py:13-106) and the INFTY_COST initialisation of the
-// appearance row (matching.py:173).
+// Fused per-frame kernels of the tracker (one stream).
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-__global__ __launch_bounds__(128) void trk_assoc_kernel(float* mean, float* cov, const int* __restrict__ slots, int do_predict,
-                                                        const float* __restrict__ det_tlwh, const float* __restrict__ det_xyah,
-                                                        int n, float* app, float* d2, float* iouc) {
-    const int t = blockIdx.x;
-    const int slot = slots[t];
-    float* P = cov + (size_t)slot * 64;
-    float* m = mean + (size_t)slot * 8;
-    if (do_predict && threadIdx.x < 64) {
-        const int lane = threadIdx.x, i = lane >> 3, j = lane & 7;
-        const float h = m[3];
-        float t1 = P[i * 8 + j];
-        if (j < 4) t1 = t1 + P[i * 8 + j + 4];
-        float t2 = t1;
-        if (i < 4) {
-            float u = P[(i + 4) * 8 + j];
-            if (j < 4) u = u + P[(i + 4) * 8 + j + 4];
-            t2 = t1 + u;
-        }
-        if (i == j) t2 = t2 + q_diag(i, h);
-        float mi = 0.f;
-        if (j == 0) { mi = m[i]; if (i < 4) mi = mi + m[i + 4]; }
-        P[i * 8 + j] = t2;
-        if (j == 0) m[i] = mi;
-    }
-    __syncthreads();   // the block's own global writes are visible to its other waves after the barrier
-    float S[4][4], L[4][4];
-    innovation_cov(P, m[3], S);
-    const bool ok = cholesky<4>(S, L);
-    float bw = 0.f, bh = m[3];
-    if (bh > 0.f) bw = m[2] * bh; else bh = fmaxf(0.f, bh);
-    const float bx = m[0] - bw / 2.0f, by = m[1] - bh / 2.0f;
-    const float brx = bx + bw, bry = by + bh;
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const float* z = det_xyah + (size_t)j * 4;
-        float d[4], y[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) d[a] = z[a] - m[a];
-        fwd_solve<4>(L, d, y);
-        float acc = y[0] * y[0];
-        acc = acc + y[1] * y[1];
-        acc = acc + y[2] * y[2];
-        acc = acc + y[3] * y[3];
-        const size_t o = (size_t)t * n + j;
-        d2[o] = ok ? acc : __builtin_inff();
-        const float* c = det_tlwh + (size_t)j * 4;
-        const float crx = c[0] + c[2], cry = c[1] + c[3];
-        const float iw = fmaxf(0.f, fminf(brx, crx) - fmaxf(bx, c[0]));
-        const float ih = fmaxf(0.f, fminf(bry, cry) - fmaxf(by, c[1]));
-        const float inter = iw * ih;
-        const float uni = bw * bh + c[2] * c[3] - inter;
-        iouc[o] = 1.0f - inter / fmaxf(uni, 1e-7f);
-        app[o] = 1e5f;
-    }
-}
 
 // cosine_min on the matrix cores: cost[t][n] = min_g max(0, 1 - <gal_n[t][g], det_n[n]>) with both
 // operands ALREADY normalised (gallery rows at append time, detections once per launch group).
@@ -422,7 +362,8 @@ struct TrkCommit {   // per-track commit of the previous frame, folded into the 
 };
 
 // trk_assoc_all_kernel: ONE launch per frame for everything the host association needs about track t (one 1024-thread
-// block per track): the lazy Kalman predict + squared Mahalanobis + IoU rows of trk_assoc_kernel (waves 0..1) and the
+// block per track): the lazy Kalman predict in place (kalman_filter.py:85-120), the squared Mahalanobis (kalman_filter.py:206-249) and
+// 1-IoU (matching.py:13-106) rows (waves 0..1) and the
 // appearance row of cosine_min_mfma_kernel -- wave pair w>>1 takes the 16-row gallery slices, each wave half of K, and the per-slice minima
 // meet in LDS instead of atomicMin, so the three rows are plain stores and may go STRAIGHT to pinned host memory: no
 // init pass, no second launch, no device-to-host blit on the per-frame chain.  Same products; the dot product is summed as
@@ -619,7 +560,7 @@ __global__ __launch_bounds__(1024) void trk_assoc_all_kernel(float* mean, float*
         }
         app[(size_t)t * n + j] = v;
     }
-    // ---- gating distance + IoU rows (trk_assoc_kernel, threads 0..127)
+    // ---- gating distance + IoU rows (threads 0..127)
     if (threadIdx.x < 128) {
         float S[4][4], L[4][4];
         innovation_cov(P, m[3], S);
@@ -806,12 +747,6 @@ void launch_gallery_append(float* gal, int gmax, int dim, const int* slot, const
     KCHECK();
 }
 
-void launch_trk_assoc(float* mean, float* cov, const int* slots, int t, int do_predict, const float* det_tlwh,
-                      const float* det_xyah, int n, float* app, float* d2, float* iouc, hipStream_t s) {
-    if (t <= 0) return;
-    hipLaunchKernelGGL(trk_assoc_kernel, dim3(t), dim3(128), 0, s, mean, cov, slots, do_predict, det_tlwh, det_xyah, n, app, d2, iouc);
-    KCHECK();
-}
 void launch_cosine_min_mfma(const float* gal_n, const int* slots, const int* glen, int t, int gmax, int dim, const float* det_n,
                             const unsigned char* has_feat, int n, float* cost, hipStream_t s) {
     if (t <= 0 || n <= 0 || gmax <= 0) return;
@@ -832,8 +767,8 @@ void launch_trk_step(float* mean, float* cov, const int* slots, const int* glen,
                      hipStream_t s) {
     if (t <= 0 || (n <= 0 && c_kind == nullptr)) return;
     const TrkCommit cm{c_kind, c_det, c_kout, c_appos, c_apdet, c_xyah, c_feat, c_feat_n, c_out_tlwh, c_gal_raw, c_gal_w};
-    static const int ks = [] { const char* e = getenv("AICAM_TRK_KS"); return e ? atoi(e) : 1; }();   // 2: K split over wave pairs (1024-thread blocks wait longer for a CU: 88 vs 83 us chain)
-    hipLaunchKernelGGL(trk_assoc_all_kernel, dim3(t), dim3(ks == 2 ? 1024 : 512), ((size_t)8 * std::max(n, 0) + 8 * 64 * 8) * sizeof(float), s, mean, cov, slots, glen, do_predict,
+    // (a K split over wave pairs -- 1024-thread blocks -- waited longer for a CU: 88 against 83 us of chain)
+    hipLaunchKernelGGL(trk_assoc_all_kernel, dim3(t), dim3(512), ((size_t)8 * std::max(n, 0) + 8 * 64 * 8) * sizeof(float), s, mean, cov, slots, glen, do_predict,
                        det_tlwh, det_xyah, gal_n, gmax, dim, det_n, has_feat, n, app, d2, iouc, cm);
     KCHECK();
 }

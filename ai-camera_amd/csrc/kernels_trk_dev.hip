@@ -1307,10 +1307,9 @@ void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const floa
     // each, not one block per four tasks of the worst case (every slot of the table alive).  Every block of this launch has to find
     // a CU behind the one-block-per-CU conv kernels before the epoch kernel may start; with 512 blocks (225 of them with work at 30
     // tracks) the tracker chain was what the pipeline waited for in every run of the bench (9 831 frames/s, six runs), with 96 in none
-    // (9 969, five runs), with 32 the launch itself gets too long (9 708).  AICAM_TRK_PREP_GRID=n: exactly n blocks.
-    static const int grid_env = [] { const char* e = getenv("AICAM_TRK_PREP_GRID"); return e ? std::max(1, atoi(e)) : 0; }();
+    // (9 969, five runs), with 32 the launch itself gets too long (9 708).
     const long likely = ((long)dn_pad / std::max(k, 1) + dn_pad / 16) * (dn_pad / 32);
-    const int grid = grid_env ? grid_env : (int)std::min<long>(std::min<long>(512, (tasks + 3) / 4), std::max<long>(64, likely / 9));
+    const int grid = (int)std::min<long>(std::min<long>(512, (tasks + 3) / 4), std::max<long>(64, likely / 9));
     hipLaunchKernelGGL(trk_epoch_prep_kernel, dim3(grid), dim3(256), 0, s, hdr, trk, gal_n, gmax, dim, featn, dn, dn_pad, k, sm, gram);
     KCHECK();
 }
@@ -1357,15 +1356,13 @@ void launch_trk_epoch(DevTrkHdr* hdr, DevTrack* trk, int* free_slots, float* mea
     a.hdr = hdr, a.trk = trk, a.free_slots = free_slots, a.mean = mean, a.cov = cov, a.gal_raw = gal_raw, a.gal_n = gal_n;
     a.prm = prm, a.dets = dets, a.f0 = f0, a.k = k, a.d_begin = d_begin, a.dn_pad = dn_pad, a.nmax = std::max(nmax, 1), a.has_sm = has_sm;
     a.scr = scr, a.out = out, a.lds_bytes = epoch_lds_bytes();
-    static const bool commit_inline = getenv("AICAM_TRK_COMMIT_INLINE") != nullptr;       // A/B: the epoch kernel copies its appended rows itself
-    a.commit_ext = (!commit_inline && dets.feat != nullptr && dets.feat_n != nullptr && scr.appends != nullptr && prm.dim % 4 == 0) ? 1 : 0;
+    a.commit_ext = (dets.feat != nullptr && dets.feat_n != nullptr && scr.appends != nullptr && prm.dim % 4 == 0) ? 1 : 0;
     a.prof = g_phase.d;
     g_phase.launches += 1, g_phase.frames += k;
     hipLaunchKernelGGL(trk_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
     KCHECK();
     if (a.commit_ext) {
-        static const int cgrid = [] { const char* e = getenv("AICAM_TRK_COMMIT_GRID"); return e ? std::max(1, atoi(e)) : 256; }();
-        hipLaunchKernelGGL(gallery_commit_kernel, dim3(cgrid), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n);
+        hipLaunchKernelGGL(gallery_commit_kernel, dim3(256), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n);
         KCHECK();
     }
 }

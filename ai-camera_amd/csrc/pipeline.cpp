@@ -92,7 +92,7 @@ struct Pipeline {
     // group's epochs have run, so with two contexts the next detector is issued ~20 ms later): 10 755 against 10 960 frames/s with planted
     // boxes, 9 561 against 9 950 with the trained detector's own (tools/own_trained.py, same box) -- slower both ways; 2 stays.
     static constexpr int NCK = 3;
-    int nck = [] { const char* e = getenv("AICAM_IN_FLIGHT"); return e ? std::min(NCK, std::max(2, atoi(e))) : 2; }();
+    int nck = 2;
     Chunk ck[NCK];
     int dim;
     std::vector<float> last_emb;
@@ -175,8 +175,8 @@ struct Pipeline {
     hipEvent_t prev_end = nullptr;   // measured: no gain on MI355X
     const uint8_t* host_frames = nullptr;   // run_from_host: frames of the current call in (pinned) host memory
     hipStream_t s_copy = nullptr;
-    static constexpr int NCOPY = 8;   // H2D copies in flight: a group's frames cross PCIe up to COPY_AHEAD groups before its launch group is issued
-    int copy_ahead = [] { const char* e = getenv("AICAM_COPY_AHEAD"); return e ? std::min(std::max(atoi(e), 1), NCOPY - 2) : 2; }();
+    static constexpr int NCOPY = 8;   // H2D copies in flight: a group's frames cross PCIe up to copy_ahead groups before its launch group is issued
+    static constexpr int copy_ahead = 2;
     hipEvent_t ev_copy[NCOPY] = {};
     std::vector<int> plan_off, plan_len;   // launch groups of the running call (ring slot offset, frames)
     int plan_slot = 0, copies_issued = 0;
@@ -340,7 +340,7 @@ struct Pipeline {
         // consumer thread, that mode's critical thread), so the stream-ordered filter only saves a round trip where the association stays
         // on the device too.  The choice reads state the consumer wrote before it released this context: the same frames always take the
         // same path.  dev_filter 2: always on the device.
-        if (!prm.inject && reid && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16 && getenv("AICAM_NO_FUSE_CROP") == nullptr) {
+        if (!prm.inject && reid && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16) {
             c.ln->reid->in_pix4 = c.ln->reid->input_pix4_ok();
             c.filt_dev = c.ln->reid->in_pix4;
         }
@@ -416,11 +416,10 @@ struct Pipeline {
             // since round 4: a device-filtered group k and a host-filtered group k + 1 can be in flight together)
             std::lock_guard<std::mutex> lk(reid_mu);
             c.ln->reid->in_pix4 = c.ln->reid->input_pix4_ok();
-            static const bool fuse_crop = getenv("AICAM_NO_FUSE_CROP") == nullptr;
             const int round = c.ln->reid->fast_items();
             for (int c0 = 0; c0 < nc; c0 += round) {   // more crops than the ReID arena holds (or than its fast kernels address): several launch groups, nothing dropped
                 const int k = std::min(round, nc - c0);
-                if (fuse_crop && c.ln->reid->in_pix4) {
+                if (c.ln->reid->in_pix4) {
                     // crop + resize + normalise inside the ReID stem kernel: the crop tensor (1 GB per 15 360 crops) never exists
                     c.ln->reid->crop_src = CropSrc{f0, prm.frame_h, prm.frame_w, c.d_boxes.p + (size_t)c0 * 4, c.d_frame_of.p + c0, c.d_valid.p + c0};
                 } else {

@@ -40,8 +40,7 @@ Device& device(int id) {
         {   // the tracker chain is latency-critical: its small launches should win CU slots as soon as they free up
             int lo = 0, hi = 0;
             HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            const bool prio = getenv("AICAM_NO_TRK_PRIO") == nullptr;
-            HIP_CHECK(hipStreamCreateWithPriority(&d->s_trk, hipStreamNonBlocking, prio ? hi : lo));
+            HIP_CHECK(hipStreamCreateWithPriority(&d->s_trk, hipStreamNonBlocking, hi));
         }
         HIP_CHECK(hipStreamCreateWithFlags(&d->s_det, hipStreamNonBlocking));
         HIP_CHECK(hipStreamCreateWithFlags(&d->s_reid, hipStreamNonBlocking));

@@ -215,49 +215,32 @@ void Tracker::update(const float* det_tlwh, const float* conf, const int32_t* cl
     }
     if (T > 0 && n > 0) {
         h_stage.ensure(stage_bytes + 16);
-        d_stage.ensure(stage_bytes + 16);
         int* hs = reinterpret_cast<int*>(h_stage.p);
         for (int i = 0; i < T; ++i) { hs[i] = tracks[i].slot; hs[T + i] = tracks[i].glen; }
         std::memcpy(h_stage.p + off_tlwh, det_tlwh, (size_t)n * 16);
         std::memcpy(h_stage.p + off_xyah, xyah.data(), (size_t)n * 16);
         std::memcpy(h_stage.p + off_has, hf.data(), n);
         // The per-frame parameter block (a few hundred bytes) is read by the kernels straight from pinned host memory:
-        // one PCIe read per wave instead of a blit launch on the critical chain (AICAM_TRK_COPY=1 restores the copy).
-        static const bool zero_copy = getenv("AICAM_TRK_COPY") == nullptr;
+        // one PCIe read per wave instead of a blit launch on the critical chain.
         const char* pbase = h_stage.p;
-        if (!zero_copy) {
-            HIP_CHECK(hipMemcpyAsync(d_stage.p, h_stage.p, stage_bytes, hipMemcpyHostToDevice, s));
-            pbase = d_stage.p;
-        }
         const int* d_slots = reinterpret_cast<const int*>(pbase + off_slots);
         const int* d_glen = reinterpret_cast<const int*>(pbase + off_glen);
         const float* d_tl = reinterpret_cast<const float*>(pbase + off_tlwh);
         const float* d_xy = reinterpret_cast<const float*>(pbase + off_xyah);
         const unsigned char* d_has = reinterpret_cast<const unsigned char*>(pbase + off_has);
         const size_t tn = (size_t)T * n;
-        d_cost.ensure(3 * tn);
         h_cost.ensure(3 * tn);
-        static const bool fused = getenv("AICAM_TRK_SPLIT") == nullptr;   // one launch per frame; AICAM_TRK_SPLIT=1: the two-kernel form
         {
             Prof pr(*dev, PROF_TRK, s, any_feat ? 2.0 * T * gmax * (double)n * dim : 0.0,
                     any_feat ? ((double)T * gmax + n) * dim * 4 : 0.0);
-            if (have_rows) {
-                // nothing to launch
-            } else if (fused) {
+            if (!have_rows) {
                 // gating + IoU + appearance rows of every track in ONE launch, written straight into pinned host memory
-                float* out = zero_copy ? h_cost.p : d_cost.p;
+                float* out = h_cost.p;
                 launch_trk_assoc_all(d_mean.p, d_cov.p, d_slots, d_glen, T, pending_predict ? 1 : 0, d_tl, d_xy,
                                      (any_feat && dim > 0) ? d_gal_n.p : nullptr, gmax, dim, d_featn, d_has, n, out, out + tn, out + 2 * tn, s);
                 pending_predict = false;
-            } else {
-                launch_trk_assoc(d_mean.p, d_cov.p, d_slots, T, pending_predict ? 1 : 0, d_tl, d_xy, n, d_cost.p, d_cost.p + tn,
-                                 d_cost.p + 2 * tn, s);
-                pending_predict = false;
-                if (any_feat && dim > 0)
-                    launch_cosine_min_mfma(d_gal_n.p, d_slots, d_glen, T, gmax, dim, d_featn, d_has, n, d_cost.p, s);
             }
         }
-        if (!(fused && zero_copy) && !have_rows) HIP_CHECK(hipMemcpyAsync(h_cost.p, d_cost.p, 3 * tn * 4, hipMemcpyDeviceToHost, s));
         if (g_trk_times.on) tt1 = TrkTimes::now();
         HIP_CHECK(hipStreamSynchronize(s));
         if (g_trk_times.on) tt2 = TrkTimes::now();
@@ -336,20 +319,16 @@ void Tracker::update(const float* det_tlwh, const float* conf, const int32_t* cl
     if (g_trk_times.on) tt3 = TrkTimes::now();
     // ---- device: commit
     const int A = (int)ap_slot.size();
-    static const bool step_ok = getenv("AICAM_TRK_NOSTEP") == nullptr;
     const int tl_buf = out_parity;             // the pinned box buffer this frame's outputs will be resolved from
-    const bool stepped = nx != nullptr && defer_outputs && step_ok && getenv("AICAM_TRK_SPLIT") == nullptr && getenv("AICAM_TRK_COPY") == nullptr;
+    const bool stepped = nx != nullptr && defer_outputs;
     if (stepped) {                              // pipelined form: the commit rides in front of the next frame's association (below, after the prune)
-        d_tlwh.ensure((size_t)std::max(M, 1) * 4);
         h_tlwh2[out_parity].ensure((size_t)std::max(M, 1) * 4);
     } else if (M + U + A > 0) {
         const size_t words = (size_t)2 * M + 2 * U + 3 * A;
         const size_t xy_off = ((words * 4 + 15) / 16) * 16;
         const size_t bytes = xy_off + (size_t)n * 16;
         PinBuf<char>& hst = defer_outputs ? h_stage2 : h_stage;
-        DevBuf<char>& dst = defer_outputs ? d_stage2 : d_stage;
         hst.ensure(bytes);
-        dst.ensure(bytes);
         int* hs = reinterpret_cast<int*>(hst.p);
         int* p = hs;
         std::copy(upd_slot.begin(), upd_slot.end(), p); p += M;
@@ -360,23 +339,15 @@ void Tracker::update(const float* det_tlwh, const float* conf, const int32_t* cl
         std::copy(ap_pos.begin(), ap_pos.end(), p); p += A;
         std::copy(ap_det.begin(), ap_det.end(), p); p += A;
         std::memcpy(hst.p + xy_off, xyah.data(), (size_t)n * 16);
-        static const bool zero_copy2 = getenv("AICAM_TRK_COPY") == nullptr;
-        const char* pbase2 = hst.p;
-        if (!zero_copy2) {
-            HIP_CHECK(hipMemcpyAsync(dst.p, hst.p, bytes, hipMemcpyHostToDevice, s));
-            pbase2 = dst.p;
-        }
-        const int* d = reinterpret_cast<const int*>(pbase2);
-        const float* d_xy = reinterpret_cast<const float*>(pbase2 + xy_off);
-        d_tlwh.ensure((size_t)std::max(M, 1) * 4);
+        const int* d = reinterpret_cast<const int*>(hst.p);
+        const float* d_xy = reinterpret_cast<const float*>(hst.p + xy_off);
         PinBuf<float>& htl = defer_outputs ? h_tlwh2[out_parity] : h_tlwh;
         htl.ensure((size_t)std::max(M, 1) * 4);
         {
             Prof pr(*dev, PROF_TRK, s, 0, (double)(M + U) * 72 * 4 * 2 + (double)A * dim * 8);
-            launch_trk_commit(d_mean.p, d_cov.p, d, M, U, A, d_xy, zero_copy2 ? htl.p : d_tlwh.p, d_gal_raw.p, d_gal_n.p, gmax, dim,
+            launch_trk_commit(d_mean.p, d_cov.p, d, M, U, A, d_xy, htl.p, d_gal_raw.p, d_gal_n.p, gmax, dim,
                               d_featp, d_featn, s);   // the boxes go straight to pinned host memory
         }
-        if (M && !zero_copy2) HIP_CHECK(hipMemcpyAsync(htl.p, d_tlwh.p, (size_t)M * 16, hipMemcpyDeviceToHost, s));
         if (!defer_outputs) HIP_CHECK(hipStreamSynchronize(s));
     }
 
@@ -550,9 +521,7 @@ void Tracker::run_epochs(const EpochDets& dets, const int* h_n, const int* h_d0,
             d_gram.ensure((size_t)dn_pad * dn_pad);
             scr.sm = d_sm.p, scr.gram = d_gram.p;
             Prof pr(*dev, PROF_TRK, s, 2.0 * ((double)cap * gmax + dn) * dn * dim, 0);
-            static const int rep = [] { const char* e = getenv("AICAM_TRK_PREP_REPEAT"); return e ? std::max(1, atoi(e)) : 1; }();   // measurement: the prep launch's share of the interference
-            for (int r = 0; r < rep; ++r)
-                launch_trk_epoch_prep(tbl_hdr(), tbl_trk(), d_gal_n.p, gmax, dim, cap, dets.feat_n + (size_t)d_begin * dim, dn, dn_pad, k, d_sm.p, d_gram.p, s);
+            launch_trk_epoch_prep(tbl_hdr(), tbl_trk(), d_gal_n.p, gmax, dim, cap, dets.feat_n + (size_t)d_begin * dim, dn, dn_pad, k, d_sm.p, d_gram.p, s);
         }
         EpochOut o = out;
         const bool last = f + k >= frames;

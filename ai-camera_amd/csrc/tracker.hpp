@@ -34,17 +34,15 @@ struct Tracker {
     int next_id = 1;
     // staging
     PinBuf<char> h_stage;
-    DevBuf<char> d_stage;
     PinBuf<int> h_slots;
     DevBuf<int> d_slots;
     PinBuf<float> h_cost;
-    DevBuf<float> d_cost, d_detn, d_feat, d_tlwh;
+    DevBuf<float> d_detn, d_feat;
     PinBuf<float> h_tlwh;
     // Deferred outputs (the HBM-resident pipeline): update() does not wait for the commit kernel; the boxes of frame f
     // are read back behind the cost-matrix sync of frame f+1 (same in-order stream), or by finish_outputs().
     bool defer_outputs = false;
-    PinBuf<char> h_stage2;                 // phase-2 staging: may still be the source of a copy when the next frame starts
-    DevBuf<char> d_stage2;
+    PinBuf<char> h_stage2;                 // phase-2 staging: may still be read by the commit kernel when the next frame starts
     PinBuf<float> h_tlwh2[2];
     struct OutMeta { int k, id, cls; float conf; };
     struct { bool active = false; int buf = 0; std::vector<OutMeta> meta; } pend;

@@ -225,3 +225,35 @@ def test_no_conv_kernel_spills():
     assert not spilled, spilled
     others = {k: r["scratch"] for k, r in tab.items() if k not in hot and r["scratch"] > (512 if re.search(r"trk_epoch_kernel|trk_cascade_test", k) else 64)}
     assert not others, others
+
+
+def test_switches_match_design_table():
+    """The environment switches the library reads are exactly the ones DESIGN.md §11 lists, and every switch a test or tool names is one
+    the library reads: a reference-path test whose switch no longer exists would compare a path with itself and still pass."""
+    name = re.compile(r"\bAICAM_[A-Z0-9][A-Z0-9_]*")
+    src = os.path.join(ROOT, "ai-camera_amd")
+    read = set()
+    for f in sorted(os.listdir(os.path.join(src, "csrc"))):
+        if f.endswith((".hip", ".cpp", ".hpp")):
+            text = open(os.path.join(src, "csrc", f)).read()
+            read |= set(re.findall(r'getenv\("(' + name.pattern[2:] + r')"\)', text))
+            read |= set(re.findall(r"#\s*ifn?def\s+(" + name.pattern[2:] + ")", text))
+            read |= set(re.findall(r"defined\s*\(\s*(" + name.pattern[2:] + ")", text))
+    for dirpath, _, files in os.walk(src):
+        for f in files:
+            if f.endswith(".py"):
+                text = open(os.path.join(dirpath, f)).read()
+                read |= set(re.findall(r"""os\.(?:environ\.get\(|environ\[|getenv\()\s*["'](""" + name.pattern[2:] + ")", text))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = design[design.index("\n## 11."):design.index("\n## 12.")]
+    listed = set(name.findall("\n".join(l for l in table.splitlines() if l.startswith("|"))))
+    assert read == listed, (sorted(read - listed), sorted(listed - read))
+    named = {}
+    for d in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, d)):
+            for f in files:
+                if f.endswith((".py", ".sh")):
+                    for n in name.findall(open(os.path.join(dirpath, f)).read()):
+                        named.setdefault(n, os.path.relpath(os.path.join(dirpath, f), ROOT))
+    stale = {n: f for n, f in named.items() if n not in read}
+    assert not stale, stale

@@ -1,5 +1,5 @@
 """Does the fp16 ReID engine give the same bits for a crop whatever the batch it is in?  (kernel variants are chosen by batch size)
-    python tools/inv_check.py        [AICAM_NO_SIDE=1 / AICAM_NO_TAIL=1 to rule a fusion in or out]"""
+    python tools/inv_check.py        [AICAM_NO_TAIL=1 to rule the 1x1 tails in or out]"""
 import importlib, os, sys, numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 he = importlib.import_module("ai-camera_amd.hip_engine")
