@@ -134,4 +134,8 @@ static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 #define KCHECK() HIP_CHECK(hipGetLastError())
 
+// Raises kernel kfn's dynamic-LDS limit to `bytes`: once per (kernel, current device), from any thread.
+void set_lds_limit(const void* kfn, size_t bytes);
+template <class K> inline void set_lds_limit(K* kfn, size_t bytes) { set_lds_limit(reinterpret_cast<const void*>(kfn), bytes); }
+
 }  // namespace aic

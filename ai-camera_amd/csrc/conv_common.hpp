@@ -1,6 +1,6 @@
 // conv_common.hpp -- device helpers shared by the convolution translation units (kernels_conv*.hip): MFMA fragment
-// types, the LDS swizzle, the channel permutation and the epilogues, LDS-DMA typedefs and counted waits; plus the host
-// entry points by which launch_conv_igemm() (kernels_conv.hip) reaches the kernels that live in the other units.
+// types, the LDS swizzle, the channel permutation and the epilogues, LDS-DMA typedefs and counted waits; plus the
+// launchers by which launch_conv_igemm() (kernels_conv.hip) reaches the kernels that live in the other units.
 #pragma once
 #include "kernels.hpp"
 
@@ -9,12 +9,6 @@
 #include <utility>
 
 namespace aic {
-
-// CUs the persistent (one-block-per-CU) conv kernels size their grids for: all of them, minus the one the association epoch
-// kernel occupies for ~1 ms at a time while the tracker runs on the device (a 256th persistent block would otherwise sit in
-// the queue until that CU or another block's whole share of the images is done).
-int conv_cu_budget();
-void set_conv_cu_budget(int cus);
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -705,23 +699,17 @@ __device__ __forceinline__ int lane_here() {
 }
 
 
-// ---- host entry points of the other conv units; each returns false when the layer is not one of its shapes
-bool conv_try_pp_patch(int dtype, const ConvArgs& a, hipStream_t s);   // kernels_conv_pp.hip: v5 ping-pong patch (3x3/s1, Cout 128 / 256k)
-int conv_s2_patch_shape(const ConvArgs& a);                             // kernels_conv_sp.hip: != 0 for the 3x3 / stride-2 layers the space-to-depth patch kernel takes (k_order 3)
-bool conv_try_s2_patch(const ConvArgs& a, hipStream_t s);
-bool conv_try_sp_patch(const ConvArgs& a, int shape, hipStream_t s);    // kernels_conv_sp.hip: v6 software-pipelined patch (fp16; the shapes of v5 without a second source)
-// kernels_conv_wide.hip: the 4-wave LDS-DMA implicit GEMM with one wait + barrier per GROUP of K-steps, for launches of a few tiles (fp16)
-template <int MT, int NT, int WM, int WN> bool conv_try_wide(const ConvArgs& a, hipStream_t s);
-template <int MT, int NT> bool conv_try_wide_tail(const ConvArgs& a, hipStream_t s);      // 4 x 1 waves, the lead of a (conv, 1x1) pair (ConvArgs::w_tail)
-int conv_pp_patch_shape(int dtype, const ConvArgs& a);                 // != 0 (the tile shape, pp_patch_shape) when conv_try_pp_patch would take this layer at a large enough batch
-bool conv_try_pp(int dtype, const ConvArgs& a, hipStream_t s);         // kernels_conv_pp.hip: v4 ping-pong im2col (long K, Cout 128 / 256k)
-bool conv_try_patch(int dtype, const ConvArgs& a, hipStream_t s);      // kernels_conv_direct.hip: 4-wave patch kernel (Cout 64 / 32)
-bool conv_try_patch_tail(const ConvArgs& a, hipStream_t s);            // same kernel, Cout 64, with a.w_tail's 1x1 in its epilogue (fp16)
-bool conv_try_pm_patch(const ConvArgs& a, hipStream_t s);              // the same form without a tail: 64 -> 64 on 40-row maps, in 40 x 8 strips
-bool conv_try_pm_patch_tail(const ConvArgs& a, hipStream_t s);         // kernels_conv_direct.hip: 3x3 / 1, 80 -> 80 or 64 -> 64 channels with a.w_tail's 1x1 in its epilogue, pixel-major patch (fp16)
-bool conv_try_c16(const ConvArgs& a, hipStream_t s);                   // kernels_conv_direct.hip: 16 input channels, fp16
-bool conv_try_1x1_stream(const ConvArgs& a, hipStream_t s);             // kernels_conv_direct.hip: 1x1, <= 128 -> 64 channels, no LDS (fp16, large batch)
-bool conv_try_c32s2_tail(const ConvArgs& a, hipStream_t s);            // kernels_conv_direct.hip: 3x3 / 2, 32 -> 64 channels with a.w_tail's 1x1 in its epilogue (fp16, large batch)
-bool conv_try_c64_resident(const ConvArgs& a, hipStream_t s);          // kernels_conv_direct.hip: persistent Cin = Cout = 64, fp16
+// ---- the launchers of the other conv units: each launches the instantiation a plan of its form names (plan_conv, conv_plan.hpp)
+void launch_conv_wide(const ConvArgs& a, const ConvPlan& p, hipStream_t s);          // kernels_conv_wide.hip
+void launch_conv_pp(const ConvArgs& a, const ConvPlan& p, hipStream_t s);            // kernels_conv_pp.hip
+void launch_conv_pp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_sp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s);      // kernels_conv_sp.hip
+void launch_conv_s2_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s);         // kernels_conv_direct.hip
+void launch_conv_pm_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_c16(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_c32s2_tail(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_1x1_stream(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
+void launch_conv_c64_resident(const ConvArgs& a, const ConvPlan& p, hipStream_t s);
 
 }  // namespace aic

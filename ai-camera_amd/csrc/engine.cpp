@@ -636,14 +636,16 @@ void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
                 ops[oi + 2].v[0] == OP_CONV && ops[oi + 3].v[0] == OP_CONV && !ops[oi + 1].fuse && !ops[oi + 2].fuse && !ops[oi + 3].fuse) {
                 const double fl0 = fl, by0 = by;
                 const ConvArgs b1 = conv_args(oi + 1), b2 = conv_args(oi + 2), b3 = conv_args(oi + 3);
-                if (conv_try_c2f16(a, b1, b2, b3, s)) {
+                if (plan_c2f16(a, b1, b2, b3)) {
+                    launch_c2f16(a, b1, b2, b3, s);
                     if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
                     oi += 3;
                     continue;
                 }
                 fl = fl0, by = by0;
             }
-            if (pair && conv_try_c64_block(a, a2, s)) {
+            if (const int ipb = pair ? plan_c64_block(a, a2, conv_cu_budget()) : 0) {
+                launch_c64_block(a, a2, ipb, s);
                 if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
                 ++oi;
                 continue;

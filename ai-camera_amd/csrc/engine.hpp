@@ -64,7 +64,7 @@ struct Model {
     unsigned cls_reduced = 0, box_decoded = 0;
     bool input_pix4_ok() const;
     // The largest launch (<= max_items) every activation tensor of which stays below 2^31 elements: the patch / block / space-to-depth conv
-    // kernels address with 32-bit offsets and hand a larger tensor to the general kernels (conv_try_c64_block & co. check M * cs < 2^31).
+    // kernels address with 32-bit offsets and hand a larger tensor to the general kernels (plan_c64_block & co. check M * cs < 2^31).
     // A caller that is free to choose its launch size (the pipeline's bounded ReID round) stays at or below this: 16 384 crops of the
     // ReID engine put layer1's 64 x 32 x 64-channel tensors at exactly 2^31 and cost 3.8 ms per launch group on the slower kernels.
     int fast_items() const {

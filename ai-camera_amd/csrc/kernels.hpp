@@ -1,89 +1,17 @@
 // kernels.hpp -- host-callable launchers of the gfx950 kernels (defined in the .hip files).
 #pragma once
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace aic {
 
 typedef _Float16 half_t;
 
 // ------------------------------------------------------------------ conv / graph ops (kernels_conv.hip)
-struct ConvArgs {
-    const void* x;      // NHWC input, element type T
-    const void* w;      // packed weights [CoutPad][Kp], element type T, K = (kh, kw, cin)
-    const float* bias;  // [CoutPad]
-    void* y;            // NHWC output (T, or float when out_f32)
-    const void* res;    // residual, same layout family as y (type T)
-    int x_cs, x_coff, H, W, Cin;       // pixel stride (elements), channel offset, spatial dims, cin (multiple of 16B/sizeof(T))
-    int y_cs, y_coff, Ho, Wo, Cout;
-    int r_cs, r_coff, res_mode, act;
-    int KH, KW, stride, pad;
-    int Kp;             // K padded to a multiple of the K-step
-    int M;              // N * Ho * Wo
-    int out_f32;
-    int cout_pad;       // rows in w / bias (multiple of 128)
-    unsigned tap_rows;  // bit kh*KW set for kh < KH (replication pattern of the tap-validity mask)
-    const void* zero;   // 64 bytes of zeros in HBM: LDS-DMA source for padded / out-of-range chunks
-    int xcd_map;        // 1: blocks take tiles through xcd_tile() (set by launch_conv_igemm)
-    const float* bias_init;   // non-NULL (k_order 2 only): the accumulators START from this bias and `bias` points at zeros -- the
-                              // weights-resident kernels add their products onto the bias, (bias + sum) and (sum + bias) round differently
-    const int* n_dev;   // optional DEVICE-side item count (images / crops of this launch): M then is only an upper bound the grid was sized
-                        // for, and tiles past n_dev[0] * Ho * Wo leave at once (ReID behind the on-device detection filter, where the
-                        // host does not know the count when it launches).  NULL: M is exact
-    int k_order;        // order in which the K-steps (tap row kh, tap column kw, channel chunk cc) are accumulated:
-                        //   0 = (kh, kw, cc)  tap-major, the memory order of the packed weights (default);
-                        //   1 = (cc, kh, kw)  the order of the ping-pong patch kernel (conv3x3_pp_patch_kernel);
-                        //   2 = (kw, cc, kh)  the order of the weights-resident 64-channel kernels (conv3x3_c64_resident / _block).
-                        // Set by launch_conv_igemm from the layer SHAPE: a layer one of those kernels can take is accumulated in that
-                        // kernel's order by EVERY kernel its batch size may select, so embeddings do not depend on the batch
-    // ---- optional SECOND SOURCE: a 1x1 conv of another tensor accumulated into the same outputs (ResNet's downsample branch folded into
-    // the block's last conv: relu(conv3x3(t) + b + conv1x1/s(x) + b') is ONE GEMM over K = [window of t | channels of x]).  The packed
-    // weight rows hold the window's K columns, then Cin2 more; `bias` is the sum of both.  Only layers walked chunk-major (k_order 1)
-    // by the LDS-DMA implicit-GEMM kernels take it; x2's K-steps come after the window's.  x2 == NULL: none.
-    const void* x2;       // NHWC, element type T; output pixel (oh, ow) reads x2 pixel (oh * s2, ow * s2)
-    int x2_cs, x2_coff, H2, W2, s2, Cin2;
-    // ---- optional SPLIT SOURCE of a 1x1 / stride 1 conv: its first Cs input channels are not in x but in another tensor of half the
-    // resolution, read at (ih >> 1, iw >> 1) -- a 2x nearest-neighbour upsample that was only ever the first slice of this conv's
-    // concatenated input (YOLOv8's neck: up(P5) | P4 -> C2f.cv1).  The upsample launch, its write and three quarters of this conv's read
-    // of those channels go away; same values, same K order: bit-identical.  x / x_coff address channel 0 of the concat buffer as
-    // before (channels Cs .. Cin-1 are read from it).  xs == NULL: none.
-    const void* xs;
-    int xs_cs, xs_coff, Hs, Ws, Cs;
-    // ---- optional 1x1 "tail" conv run in this conv's epilogue (fp16 only; conv_tail_supported()).  This conv's own output
-    // (SiLU(acc + bias) rounded to fp16, exactly what it would have stored) never leaves the registers: it is the B operand of
-    // the tail's MFMAs.  y / y_cs / y_coff of THIS conv are then unused.  w_tail == NULL: no tail.
-    const void* w_tail;   // packed weights of the 1x1 [t_cout_pad][t_kp], K = this conv's Cout
-    const float* b_tail;  // [t_cout_pad]
-    void* y_tail;         // NHWC output of the tail (fp16, or float when t_out_f32)
-    int t_cout, t_kp, t_y_cs, t_y_coff, t_out_f32, t_act;
-    // ---- optional CLASS REDUCTION of the tail (the detect head's class branch, whose logits only ever feed an arg-max): instead of
-    // storing t_cout fp32 logits per pixel (320 bytes per anchor written here, read back by decode_kernel) the tail stores their
-    // maximum and the FIRST channel that reaches it (np.argmax's rule, as decode_kernel) -- the very fp32 values it would have stored,
-    // compared in registers.  Pixel m of the tail's map goes to t_max / t_arg[(m / t_hw) * t_na + t_a0 + m % t_hw]
-    // (image-major anchor order of DetArgs).  t_max == NULL: none (y_tail is then written as usual).
-    float* t_max; int* t_arg;
-    int t_hw, t_a0, t_na;
-    // ---- optional BOX DECODE of the tail (the detect head's box branch: 4 sides x 16 DFL bins per pixel): instead of 64 fp32 logits
-    // per pixel (256 bytes per anchor written, read back by decode_kernel) the tail stores the decoded xyxy box -- decode_kernel's own
-    // arithmetic on the same fp32 values in the same order (max, then exp / running sums bin 0 .. 15, one division per side), so the
-    // boxes are the bits decode_kernel would have produced.  Same anchor indexing as t_max; t_w / t_stride: the level's map width and
-    // stride.  t_box == NULL: none.
-    float* t_box; int t_w, t_stride;
-};
-// true when launch_conv_igemm can run `lead` with `tail` (a 1x1 / stride 1 / pad 0 conv reading exactly lead's output) in its epilogue:
-// fp16, lead = SiLU without residual with Cout 64 or 80 (a wave then owns every channel of its pixels), tail.Cout <= lead.Cout
-bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail);
-// true when launch_conv_igemm takes this 1x1 conv with the first cs channels of its input read from a half-resolution tensor (ConvArgs::xs)
-bool conv_xs_supported(int dtype, const ConvArgs& a, int cs);
-// true when launch_conv_igemm takes a conv of this shape (x2 fields ignored) with a second source (ConvArgs::x2) of cin2 channels
-bool conv_x2_supported(int dtype, const ConvArgs& a, int cin2);
-// dtype: AIC_F16 or AIC_F32 (type of x / w / res and, unless out_f32, y)
 void launch_conv_igemm(int dtype, const ConvArgs& a, hipStream_t s);
-// a whole 64-channel BasicBlock (c1: conv3x3+ReLU, c2: conv3x3 + block input, ReLU) in one fp16 kernel with the intermediate in
-// LDS (kernels_conv_block.hip); false = pattern / geometry not supported, nothing launched
-bool conv_try_c64_block(const ConvArgs& c1, const ConvArgs& c2, hipStream_t s);
-// a whole C2f block with 16-channel halves (cv1 1x1 32->32, m.cv1 / m.cv2 3x3 16->16 with shortcut, cv2 1x1 48->32) in one fp16 kernel,
-// concat buffer and intermediate in LDS (kernels_conv_c2f.hip); false = pattern / geometry not supported, nothing launched
-bool conv_try_c2f16(const ConvArgs& cv1, const ConvArgs& m_cv1, const ConvArgs& m_cv2, const ConvArgs& cv2, hipStream_t s);
+// the fused blocks, launched where plan_c64_block / plan_c2f16 (conv_plan.hpp) accept them (kernels_conv_block.hip, kernels_conv_c2f.hip)
+void launch_c64_block(const ConvArgs& c1, const ConvArgs& c2, int ipb, hipStream_t s);
+void launch_c2f16(const ConvArgs& cv1, const ConvArgs& m_cv1, const ConvArgs& m_cv2, const ConvArgs& cv2, hipStream_t s);
 
 // letterbox + conv 3x3/2 (3->16) + SiLU fused (fp16 YOLOv8 stem); false = geometry not supported, nothing launched
 struct LetterboxGeom;

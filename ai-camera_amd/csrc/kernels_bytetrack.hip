@@ -366,11 +366,7 @@ static int bt_lds_bytes() { return 159 * 1024; }
 
 void launch_bytetrack_epoch(const BtTable& tbl, const BtParams& prm, const EpochDets& dets, int f0, int k, float* ext,
                             const EpochOut& out, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bytetrack_epoch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bt_lds_bytes()));
-        attr = true;
-    }
+    set_lds_limit(bytetrack_epoch_kernel, bt_lds_bytes());
     BtArgs a{tbl, prm, dets, f0, k, ext, out, bt_lds_bytes()};
     hipLaunchKernelGGL(bytetrack_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), bt_lds_bytes(), s, a);
     KCHECK();

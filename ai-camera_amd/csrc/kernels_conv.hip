@@ -18,11 +18,6 @@
 
 namespace aic {
 
-static int g_conv_cus = 256;
-int conv_cu_budget() { return g_conv_cus; }
-void set_conv_cu_budget(int cus) { g_conv_cus = std::max(1, cus); }
-
-
 // ------------------------------------------------------------------------------------------------
 // v2: the tiling and MFMA mapping above; the operand tiles travel HBM/L2 -> LDS by LDS-DMA
 // (global_load_lds_dwordx4, 1 KiB per wave-instruction, no VGPR staging and no ds_write pass) into an
@@ -363,161 +358,57 @@ static void launch_dma(const ConvArgs& a, hipStream_t s) {
     dim3 grid(ceil_div(a.M, BM), ceil_div(a.Cout, BN));
     const size_t lds = (size_t)NSTAGE * (BM + BNP) * 64;
     auto kfn = conv_igemm_dma_kernel<T, MT, NT, WM, WN, NSTAGE, TAIL>;
-    static bool attr = false;
-    if (!attr && lds > 64 * 1024) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    if (lds > 64 * 1024) set_lds_limit(kfn, lds);
     hipLaunchKernelGGL(kfn, grid, dim3(64 * WM * WN), lds, s, a);
     KCHECK();
 }
+// (Measured in round 5 and removed for the small-tile launches: kernels_conv_sp.hip's lean K-step -- bit-identical, per-frame plugin loop
+//  1 070 -> 1 030 us of conv per frame but 16- / 64-frame groups 7 100 -> 6 320 / 10 300 -> 9 900 frames/s; inline-asm MFMAs with early loop
+//  exits also made the ReID layers non-deterministic -- and an 8-stage ring, 1 101 against 1 075 us: their K loop does not wait for memory.)
 
-template <typename T, int MT, int NT, int WM, int WN>
-static void launch_variant(const ConvArgs& a, hipStream_t s) {
-    // (A lean K-step for these small-tile launches -- kernels_conv_sp.hip's: per-lane row pointers + one scalar offset per step, next step's
-    //  fragments read under this step's MFMAs, immediates for ring stage and fragment set; bit-identical to this kernel, 31 net tests green --
-    //  was built and measured in round 5: the per-frame plugin loop's conv time 1 070 -> 1 030 us per frame (4 or 8 ring stages alike), but
-    //  16- / 64-frame launch groups 7 100 -> 6 320 and 10 300 -> 9 900 frames/s and the headline -0.4 %.  Removed.  Found on the way: with
-    //  inline-asm MFMAs and early loop exits the allocator copies accumulators between bodies -- VALU reads of matrix-pipe results the
-    //  compiler does not know are such -- and the ReID layers came out non-deterministic; in-place asm MFMAs are safe only where the
-    //  accumulators provably stay put, as in kernels_conv_sp.hip.)
-    if constexpr (sizeof(T) == 2 && WM * WN == 4) {
-        // launches of a few tiles (the per-frame plugin loop): one synchronisation per group of K-steps, bit-identical (kernels_conv_wide.hip)
-        if (conv_try_wide<MT, NT, WM, WN>(a, s)) return;
-    }
-    // (A deeper ring for the small launches -- 8 stages where a 64 x 64 tile's K loop runs 0.41 us per step -- was measured in round 5 on the
-    //  per-frame plugin loop: 1 101 against 1 075 us of conv time per frame.  Their K loop is not waiting for memory: it is ~90 instructions
-    //  per step for four MFMAs -- the chunk-major walks rebuild every row pointer every step.)
-    launch_dma<T, MT, NT, WM, WN, 4>(a, s);
-}
-
-template <typename T>
-static void launch_conv_t(const ConvArgs& a_in, hipStream_t s) {
-    ConvArgs a = a_in;
-    if (a.k_order == 2) {                      // the order AND the bias placement of the weights-resident kernels (Cout = 64: one 256-byte zero page covers the epilogue's reads)
-        a.bias_init = a.bias;
-        a.bias = reinterpret_cast<const float*>(a.zero);
-    }
-    const int c = a.Cout;
-    constexpr int DT = sizeof(T) == 2 ? AIC_F16 : AIC_F32;
-    const long blocks128 = (long)ceil_div(a.M, 128);
-    if constexpr (sizeof(T) == 4) {
-        // fp32 engines (the parity mode) run ONE kernel family since round 5: the LDS-DMA implicit GEMM on tiles of at most 8 MFMA tiles per wave,
-        // whose three-level summation carries a mid-level accumulator set (conv_common.hpp).  The patch,
-        // ping-pong and 8-wave forms are fp16 only.  (--dtype fp32 throughput: 1 167 frames/s with the two-level kernels of rounds 2-4.)
-        if (c % 128 == 0 || c > 160) launch_variant<T, 2, 4, 2, 2>(a, s);               // 64 px x 128 ch
-        else if (c % 80 == 0) launch_variant<T, 1, 5, 4, 1>(a, s);                      // 64 px x 80 ch
-        else if (c % 64 == 0) launch_variant<T, 2, 4, 4, 1>(a, s);                      // 128 px x 64 ch
-        else if (c % 48 == 0) launch_variant<T, 2, 3, 4, 1>(a, s);                      // 128 px x 48 ch
-        else if (c % 32 == 0 || c > 16) launch_variant<T, 4, 2, 4, 1>(a, s);            // 256 px x 32 ch
-        else launch_variant<T, 4, 1, 4, 1>(a, s);                                       // 256 px x 16 ch
-        return;
-    } else {
-    if (conv_try_pp_patch(DT, a, s)) return;
-    if (!a.x2 && DT == AIC_F16 && conv_try_pm_patch(a, s)) return;
-    if (!a.x2 && conv_try_patch(DT, a, s)) return;        // (a second source: the ping-pong patch kernel above or the LDS-DMA implicit GEMMs below)
-    if (c % 128 == 0 || c > 160) {
-        if (conv_try_pp(DT, a, s)) return;   // one-block-per-CU ping-pong kernels (kernels_conv_pp.hip)
-        if (c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= 200) launch_dma<T, 8, 4, 2, 4, 4>(a, s);   // 8 waves: 256 px x 256 ch (+12% on ReID layer3/4 over 256x128, profiles/)
-        else if ((blocks128 / 2) * ceil_div(c, 128) >= 384) launch_dma<T, 4, 4, 4, 2, 3>(a, s);   // 8 waves: 256 px x 128 ch
-        else if (blocks128 * ceil_div(c, 128) >= 128) launch_variant<T, 4, 4, 2, 2>(a, s);   // 128 px x 128 ch
-        else if ((long)ceil_div(a.M, 64) * ceil_div(c, 64) > 256 && conv_try_wide<4, 4, 2, 2>(a, s)) return;   // too many 64 x 64 tiles for the wide-step kernel, few enough 128 x 128 ones
-        else launch_variant<T, 2, 2, 2, 2>(a, s);                                       // 64 px x 64 ch (small maps)
-    } else if (c == 144) {
-        // the merged first convs of a YOLOv8 detect level (64 box + 80 class channels, Model::Model; fp16 only): one 144-wide tile,
-        // the map is read once.  4 waves, one per SIMD: 36 accumulator tiles per wave on the 256-pixel tile need the whole register file
-        if (ceil_div(a.M, 256) >= 512) launch_dma<T, 4, 9, 4, 1, 4>(a, s);          // 256 px x 144 ch
-        else if (!conv_try_wide<2, 9, 4, 1>(a, s)) launch_dma<T, 2, 9, 4, 1, 4>(a, s);   // 128 px x 144 ch (a few tiles: kernels_conv_wide.hip)
-    } else if (c % 80 == 0) {
-        // YOLOv8's class branches (Cout = nc = 80).  512 px x 80 ch on 8 waves once there are tiles for every CU:
-        // 428 -> 499 TFLOP/s on cls0.1 (80 -> 80, 3x3 at 80 x 80), +7..16 % on the others (tools/conv_bench.py)
-        if (ceil_div(a.M, 512) >= 256) launch_dma<T, 4, 5, 8, 1, 3>(a, s);
-        else launch_variant<T, 2, 5, 4, 1>(a, s);                                       // 128 px x 80 ch
-    } else if (c % 64 == 0) {
-        if (blocks128 >= 512) launch_variant<T, 4, 4, 4, 1>(a, s);                      // 256 px x 64 ch
-        else if (blocks128 * ceil_div(c, 64) > 256 && conv_try_wide<4, 4, 4, 1>(a, s)) return;   // (as above: 256 px tiles where the 128 px grid is too large for the wide-step kernel)
-        else launch_variant<T, 2, 4, 4, 1>(a, s);                                       // 128 px x 64 ch
-    } else if (c % 48 == 0) {
-        launch_variant<T, 2, 3, 4, 1>(a, s);                                            // 128 px x 48 ch
-    } else if (c % 32 == 0 || c > 16) {
-        launch_variant<T, 4, 2, 4, 1>(a, s);                                            // 256 px x 32 ch
-    } else {
-        launch_variant<T, 4, 1, 4, 1>(a, s);                                            // 256 px x 16 ch
-    }
-    }
-}
-
-// Lead conv of a (conv, 1x1) pair with the 1x1 in its epilogue.  Only the kernels whose waves own all channels of their pixels:
-// the 3x3 patch kernel where it applies (Cout 64), else the LDS-DMA implicit GEMM with NT = Cout / 16 and WN = 1 -- the same
-// choices the conv gets on its own.
-bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail) {
-    static const bool off = getenv("AICAM_NO_TAIL") != nullptr;
-    if (off || dtype != AIC_F16) return false;
-    if ((lead.Cout != 64 && lead.Cout != 80) || lead.act != 1 || lead.res_mode != 0 || lead.out_f32) return false;
-    if (lead.xs || lead.x2) return false;                          // split / second sources are walked by the plain kernels only
-    if (tail.KH != 1 || tail.KW != 1 || tail.stride != 1 || tail.pad != 0 || tail.res_mode != 0) return false;
-    if (tail.x != lead.y || tail.x_cs != lead.y_cs || tail.x_coff != lead.y_coff || tail.M != lead.M || tail.Cin != lead.Cout) return false;
-    if (tail.Cout > lead.Cout || tail.Kp != 32 * ((lead.Cout + 31) / 32) || tail.cout_pad < lead.Cout) return false;
-    if (lead.cout_pad < lead.Cout || (tail.y_cs | tail.y_coff) % 8) return false;
-    return true;
-}
-
-// A split source is walked by the memory-order fast path of conv_igemm_dma_kernel only: a 1x1 / 1 / 0 conv without tail whose Cout
-// keeps it away from the ping-pong kernels (K of these layers is short anyway) and from the direct kernels.
-bool conv_xs_supported(int dtype, const ConvArgs& a, int cs) {
-    const int bke = dtype == AIC_F16 ? 32 : 16;
-    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.w_tail || a.x2 || a.Cin % bke || cs <= 0 || cs % bke || cs >= a.Cin) return false;
-    if (a.H % 2 || a.W % 2) return false;
-    return a.Kp < 16 * bke;                                       // (conv_try_pp takes K >= 16 steps: it has no split-source walk)
-}
-
-// A second source rides on the chunk-major walk of conv_igemm_dma_kernel / conv_igemm_pp_kernel: the layer must be one that every
-// batch size sends there in that order -- a ping-pong-patch SHAPE (k_order 1) whose Cout takes the 128-multiple branch of launch_conv_t.
-bool conv_x2_supported(int dtype, const ConvArgs& a, int cin2) {
-    const int bke = dtype == AIC_F16 ? 32 : 16;
-    const int shape = conv_pp_patch_shape(dtype, a);             // 2: 512 x 128 tile, 3 / 4: 256 x 256 on 16 x 8 / 8 x 4 maps
-    if (shape < 2 || a.Cout % 128 || a.w_tail || a.out_f32 || cin2 <= 0 || cin2 % bke) return false;
-    return cin2 / bke < a.Cin / bke;                             // its chunk e rides behind the window's chunk e + 1
-}
-
-static void launch_conv_tail(const ConvArgs& a, hipStream_t s) {
-    if (a.Cout == 64) {
-        if (conv_try_c32s2_tail(a, s)) return;
-        if (conv_try_pm_patch_tail(a, s)) return;
-        if (conv_try_patch_tail(a, s)) return;
-        if ((long)ceil_div(a.M, 128) >= 512) launch_dma<half_t, 4, 4, 4, 1, 4, true>(a, s);   // 256 px x 64 ch
-        else if (!conv_try_wide_tail<2, 4>(a, s)) launch_dma<half_t, 2, 4, 4, 1, 4, true>(a, s);   // 128 px x 64 ch (a few tiles: kernels_conv_wide.hip)
-    } else {                                                                                  // 80
-        if (conv_try_pm_patch_tail(a, s)) return;
-        if (ceil_div(a.M, 512) >= 256) launch_dma<half_t, 4, 5, 8, 1, 3, true>(a, s);          // 512 px x 80 ch
-        else if (!conv_try_wide_tail<2, 5>(a, s)) launch_dma<half_t, 2, 5, 4, 1, 4, true>(a, s);   // 128 px x 80 ch
-    }
+// The LDS-DMA tiles plan_conv hands out (conv_plan.cpp): fp32 engines run the 4-wave tiles only, the 8-wave and 144-channel ones and the
+// tail forms are fp16.
+static void launch_conv_dma(int dtype, const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define DMA(T, MT, NT, WM, WN, NS, TAIL)                                                                                        \
+    if (sizeof(T) == (dtype == AIC_F16 ? 2u : 4u) && p.mt == MT && p.nt == NT && p.wm == WM && p.wn == WN && p.nstage == NS && \
+        p.tail == TAIL)                                                                                                        \
+        return launch_dma<T, MT, NT, WM, WN, NS, TAIL>(a, s);
+    DMA(float, 2, 4, 2, 2, 4, false) DMA(float, 1, 5, 4, 1, 4, false) DMA(float, 2, 4, 4, 1, 4, false)
+    DMA(float, 2, 3, 4, 1, 4, false) DMA(float, 4, 2, 4, 1, 4, false) DMA(float, 4, 1, 4, 1, 4, false)
+    DMA(half_t, 8, 4, 2, 4, 4, false) DMA(half_t, 4, 4, 4, 2, 3, false) DMA(half_t, 4, 4, 2, 2, 4, false) DMA(half_t, 2, 2, 2, 2, 4, false)
+    DMA(half_t, 4, 9, 4, 1, 4, false) DMA(half_t, 2, 9, 4, 1, 4, false) DMA(half_t, 4, 5, 8, 1, 3, false) DMA(half_t, 2, 5, 4, 1, 4, false)
+    DMA(half_t, 4, 4, 4, 1, 4, false) DMA(half_t, 2, 4, 4, 1, 4, false) DMA(half_t, 2, 3, 4, 1, 4, false) DMA(half_t, 4, 2, 4, 1, 4, false)
+    DMA(half_t, 4, 1, 4, 1, 4, false)
+    DMA(half_t, 4, 4, 4, 1, 4, true) DMA(half_t, 2, 4, 4, 1, 4, true) DMA(half_t, 4, 5, 8, 1, 3, true) DMA(half_t, 2, 5, 4, 1, 4, true)
+#undef DMA
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no LDS-DMA instantiation for this tile");
 }
 
 void launch_conv_igemm(int dtype, const ConvArgs& a0, hipStream_t s) {
     if (a0.M <= 0) return;
     ConvArgs a = a0;
     a.xcd_map = 1;
-    // the 64-channel weights-resident kernels (fp16): any 3x3 / 1 / 1 layer with Cin = Cout = 64 whose map they tile
-    // (ReLU, with or without the BasicBlock's residual: the only forms those kernels have)
-    const bool c64 = dtype == AIC_F16 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 64 && a.Cout == 64 && a.Kp == 576 &&
-                     a.act == 2 && a.res_mode <= 1 && !a.out_f32 && !a.w_tail &&
-                     a.Ho == a.H && a.Wo == a.W && ((a.W % 32 == 0 && a.H % 8 == 0) || (a.W == 32 && a.H % 4 == 0));
-    a.k_order = conv_pp_patch_shape(dtype, a) ? 1 : (c64 ? 2 : (conv_s2_patch_shape(a) ? 3 : 0));      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
-    if (a.x2) AIC_REQUIRE(a.k_order == 1 && a.Cout % 128 == 0 && !a.w_tail, AIC_ERR_INVALID, "conv with a second source: unsupported shape (check conv_x2_supported)");
-    if (a.xs) AIC_REQUIRE(a.k_order == 0 && a.KH == 1 && a.KW == 1 && !a.w_tail && a.Kp < 16 * (dtype == AIC_F16 ? 32 : 16), AIC_ERR_INVALID,
-                          "conv with a split source: unsupported shape (check conv_xs_supported)");
-    if (a.w_tail) {
-        AIC_REQUIRE(dtype == AIC_F16 && (a.Cout == 64 || a.Cout == 80) && a.act == 1 && a.res_mode == 0, AIC_ERR_INVALID,
-                    "conv with a 1x1 tail: unsupported lead (check conv_tail_supported before setting w_tail)");
-        launch_conv_tail(a, s);
-        return;
+    a.k_order = conv_k_order(dtype, a);      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
+    const ConvPlan p = plan_conv(dtype, a, conv_cu_budget());
+    if (a.k_order == 2 && p.form != ConvForm::C64Resident) {
+        // the order AND the bias placement of the weights-resident kernels (Cout = 64: one 256-byte zero page covers the epilogue's reads)
+        a.bias_init = a.bias;
+        a.bias = reinterpret_cast<const float*>(a.zero);
     }
-    if (dtype == AIC_F16 && conv_try_c16(a, s)) return;
-    if (dtype == AIC_F16 && conv_try_1x1_stream(a, s)) return;
-    if (dtype == AIC_F16 && conv_try_c64_resident(a, s)) return;
-    if (dtype == AIC_F16) launch_conv_t<half_t>(a, s);
-    else launch_conv_t<float>(a, s);
+    switch (p.form) {
+        case ConvForm::Dma: launch_conv_dma(dtype, a, p, s); break;
+        case ConvForm::Wide: launch_conv_wide(a, p, s); break;
+        case ConvForm::Pp: launch_conv_pp(a, p, s); break;
+        case ConvForm::PpPatch: launch_conv_pp_patch(a, p, s); break;
+        case ConvForm::SpPatch: launch_conv_sp_patch(a, p, s); break;
+        case ConvForm::S2Patch: launch_conv_s2_patch(a, p, s); break;
+        case ConvForm::Patch: launch_conv_patch(a, p, s); break;
+        case ConvForm::PmPatch: launch_conv_pm_patch(a, p, s); break;
+        case ConvForm::C16: launch_conv_c16(a, p, s); break;
+        case ConvForm::C32s2Tail: launch_conv_c32s2_tail(a, p, s); break;
+        case ConvForm::Stream1x1: launch_conv_1x1_stream(a, p, s); break;
+        case ConvForm::C64Resident: launch_conv_c64_resident(a, p, s); break;
+    }
 }
 
 

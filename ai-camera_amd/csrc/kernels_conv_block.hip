@@ -266,46 +266,18 @@ __global__ __launch_bounds__(512) void conv3x3_c64_block_kernel(const BlockArgs 
     wait_vmcnt<0>();
 }
 
-bool conv_try_c64_block(const ConvArgs& c1, const ConvArgs& c2, hipStream_t s) {
-    static const bool on = [] { const char* e = getenv("AICAM_C64_BLOCK"); return !e || atoi(e) != 0; }();
-    auto conv64 = [](const ConvArgs& a) {
-        return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 64 && a.Cout == 64 && !a.out_f32 && a.Kp == 576 && a.act == 2 &&
-               a.Ho == a.H && a.Wo == a.W && (a.x_cs | a.x_coff | a.y_cs | a.y_coff) % 8 == 0;
-    };
-    if (!on || !conv64(c1) || !conv64(c2) || c1.res_mode != 0 || c2.res_mode != 1) return false;
-    if (c1.W != 32 || c1.H % 4 || c1.H != c2.H || c2.W != 32 || c1.M != c2.M || c1.M < 1500000) return false;
-    if (c2.x != c1.y || c2.x_cs != c1.y_cs || c2.x_coff != c1.y_coff) return false;            // conv2 reads what conv1 writes
-    if (c2.res != c1.x || c2.r_cs != c1.x_cs || c2.r_coff != c1.x_coff) return false;        // and adds the block input
-    if ((long)c1.M * c1.x_cs >= (1l << 31) || (long)c2.M * c2.y_cs >= (1l << 31)) return false;
+// a BasicBlock plan_c64_block (conv_plan.cpp) accepts, `ipb` images per block
+void launch_c64_block(const ConvArgs& c1, const ConvArgs& c2, int ipb, hipStream_t s) {
     BlockArgs a{};
     a.x = c1.x, a.y = c2.y, a.w1 = c1.w, a.b1 = c1.bias, a.w2 = c2.w, a.b2 = c2.bias, a.zero = c1.zero;
     a.x_cs = c1.x_cs, a.x_coff = c1.x_coff, a.y_cs = c2.y_cs, a.y_coff = c2.y_coff, a.H = c1.H;
     a.n_img = c1.M / (c1.H * c1.W);
     a.n_dev = c1.n_dev;
-    // images per block: shorter-lived blocks than one persistent block per CU (each pays 3 steps of pipeline fill and a weight
-    // reload; in exchange the CU takes other streams' waiting blocks in between).  16 images per block (960 blocks for a 15 360-crop group): same box, interleaved, round 3: 9 490 / 9 482 frames/s with one
-    // persistent block per CU (0), 9 553 / 9 624 with 16 -- the NMS blocks of the side stream hold whole CUs for ~2 ms at the start of
-    // the ReID trunk, and a persistent block that starts late finishes late; shorter-lived blocks just flow around them.
-    // Round 5: 960 blocks are 3.75 rounds of 256 CUs -- the last round runs three quarters full.  12 .. 16 images per block, whichever
-    // wastes least of the last round (15 360 crops: 12 -> 1 280 blocks = 5 rounds; the layer alone 2 065 -> 2 000 us per conv, same box).
-    // (the CUs the blocks are dealt over: the budget leaves ONE out for the tracker's epoch block while it runs, which does not make 1 280
-    //  blocks six rounds -- counted against the whole chip)
-    const int cus = (conv_cu_budget() + 7) / 8 * 8;
-    long best = -1;
-    for (int ipb = 12; ipb <= 16; ++ipb) {
-        const long blocks = (a.n_img + ipb - 1) / ipb, rounds = (blocks + cus - 1) / cus;
-        const long waste = (rounds * cus - blocks) * 1000 / (rounds * cus);           // idle share of the CUs' block slots, per mille
-        if (best < 0 || waste < best) best = waste, a.ipb = ipb;
-    }
+    a.ipb = ipb;
     constexpr size_t lds = (size_t)(20 + 16) * 34 * 128 + 1024 + 512;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(conv3x3_c64_block_kernel, lds);
     hipLaunchKernelGGL(conv3x3_c64_block_kernel, dim3((a.n_img + a.ipb - 1) / a.ipb), dim3(512), lds, s, a);
     KCHECK();
-    return true;
 }
 
 }  // namespace aic

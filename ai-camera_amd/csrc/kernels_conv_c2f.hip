@@ -209,30 +209,10 @@ __global__ __launch_bounds__(256) void c2f16_fused_kernel(const C2fArgs a, int t
     }
 }
 
-// cv1 -> m.cv1 -> m.cv2 (+ shortcut) -> cv2 of a C2f with 16-channel halves, when the four convs are wired as engine_file.py's c2f()
-// wires them; false = pattern / geometry not supported, nothing launched.
-bool conv_try_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, const ConvArgs& c2, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_C2F") != nullptr;
-    if (off) return false;
-    auto one = [](const ConvArgs& c, int cin, int cout, int kp) {
-        return c.KH == 1 && c.KW == 1 && c.stride == 1 && c.pad == 0 && c.Cin == cin && c.Cout == cout && c.Kp == kp && c.act == 1 &&
-               c.res_mode == 0 && !c.out_f32;
-    };
-    auto three = [](const ConvArgs& c) {
-        return c.KH == 3 && c.KW == 3 && c.stride == 1 && c.pad == 1 && c.Cin == 16 && c.Cout == 16 && c.Kp == 160 && c.act == 1 && !c.out_f32;
-    };
-    if (!one(c1, 32, 32, 32) || !one(c2, 48, 32, 64) || !three(m1) || !three(m2) || m1.res_mode != 0 || m2.res_mode != 2) return false;
+// cv1 -> m.cv1 -> m.cv2 (+ shortcut) -> cv2 of a C2f with 16-channel halves, wired as plan_c2f16 (conv_plan.cpp) checks
+void launch_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, const ConvArgs& c2, hipStream_t s) {
+    static_assert(TH == 8 && TW == 32, "plan_c2f16 checks the map against 8 x 32 tiles");
     const int H = c1.H, W = c1.W;
-    for (const ConvArgs* c : {&c1, &m1, &m2, &c2})
-        if (c->H != H || c->W != W || c->Ho != H || c->Wo != W || c->M != c1.M) return false;
-    if (H % TH || W % TW) return false;
-    // wiring: cv1 writes cat[0:32]; m.cv1 reads cat[16:32] -> tmp; m.cv2 reads tmp, adds cat[16:32], writes cat[32:48]; cv2 reads cat[0:48]
-    const void* cat = c1.y;
-    if (c1.y_coff != 0 || m1.x != cat || m1.x_coff != 16 || m1.x_cs != c1.y_cs || m2.x != m1.y || m2.x_coff != m1.y_coff || m2.x_cs != m1.y_cs ||
-        m2.y != cat || m2.y_coff != 32 || m2.res != cat || m2.r_coff != 16 || m2.r_cs != c1.y_cs || c2.x != cat || c2.x_coff != 0 ||
-        c2.x_cs != c1.y_cs || c1.y_cs < 48)
-        return false;
-    if ((c1.x_cs | c1.x_coff | c2.y_cs | c2.y_coff) % 8) return false;
     C2fArgs a{};
     a.x = reinterpret_cast<const half_t*>(c1.x), a.y = reinterpret_cast<half_t*>(c2.y);
     a.w1 = reinterpret_cast<const half_t*>(c1.w), a.w2 = reinterpret_cast<const half_t*>(m1.w);
@@ -240,15 +220,10 @@ bool conv_try_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, 
     a.b1 = c1.bias, a.b2 = m1.bias, a.b3 = m2.bias, a.b4 = c2.bias;
     a.x_cs = c1.x_cs, a.x_coff = c1.x_coff, a.y_cs = c2.y_cs, a.y_coff = c2.y_coff, a.H = H, a.W = W;
     a.n_img = c1.M / (H * W), a.xcd_map = 1;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f16_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr = true;
-    }
+    set_lds_limit(c2f16_fused_kernel, LDS_BYTES);
     const int tiles_x = W / TW, tiles_y = H / TH;
     hipLaunchKernelGGL(c2f16_fused_kernel, dim3(a.n_img * tiles_x * tiles_y), dim3(256), (size_t)LDS_BYTES, s, a, tiles_x, tiles_y);
     KCHECK();
-    return true;
 }
 
 }  // namespace aic

@@ -128,17 +128,12 @@ static void launch_c16(const ConvArgs& a, hipStream_t s) {
     KCHECK();
 }
 
-static bool try_c16(const ConvArgs& a, hipStream_t s) {
-    if (a.KH != 3 || a.KW != 3 || a.pad != 1 || a.Cin != 16 || a.act != 1 || a.out_f32 || (a.res_mode != 0 && a.res_mode != 2)) return false;
-    if (a.Wo % 32 || a.Ho % 8 || a.Kp != 160 || (a.x_cs | a.x_coff | a.y_cs | a.y_coff | a.r_cs | a.r_coff) % 8) return false;
-    if (a.stride == 1 && (a.Ho != a.H || a.Wo != a.W)) return false;
-    if (a.stride == 2 && (a.Ho != (a.H + 1) / 2 || a.Wo != (a.W + 1) / 2)) return false;
+void launch_conv_c16(const ConvArgs& a, const ConvPlan&, hipStream_t s) {
     if (a.Cout == 16 && a.stride == 1) launch_c16<16, 1>(a, s);
     else if (a.Cout == 32 && a.stride == 2) launch_c16<32, 2>(a, s);
     else if (a.Cout == 16 && a.stride == 2) launch_c16<16, 2>(a, s);
     else if (a.Cout == 32 && a.stride == 1) launch_c16<32, 1>(a, s);
-    else return false;
-    return true;
+    else AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no 16-channel instantiation for this layer");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -248,26 +243,12 @@ template <int NW>
 static void launch_c32s2_tail(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = (size_t)(8 * NW + 1) * 2 * 18 * 64;
     const int tiles_x = a.Wo / 16, tiles_y = a.Ho / (4 * NW), n_img = a.M / (a.Ho * a.Wo);
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c32s2_tail_kernel<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(conv3x3_c32s2_tail_kernel<NW>, lds);
     hipLaunchKernelGGL(conv3x3_c32s2_tail_kernel<NW>, dim3((unsigned)(n_img * tiles_x * tiles_y)), dim3(64 * NW), lds, s, a, tiles_x, tiles_y);
     KCHECK();
 }
 
-static bool try_c32s2_tail(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_C32S2") != nullptr;
-    if (off || !a.w_tail || a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin != 32 || a.Cout != 64 || a.Kp != 288) return false;
-    if (a.act != 1 || a.res_mode != 0 || a.out_f32 || a.k_order != 0 || a.xs || a.x2 || a.n_dev || a.t_max || a.t_box) return false;
-    if (a.t_cout > 64 || a.t_cout % 8 || a.t_kp != 64 || a.cout_pad < 64) return false;
-    if (a.Ho % 16 || a.Wo % 16 || a.Ho != (a.H + 1) / 2 || a.Wo != (a.W + 1) / 2 || (a.x_cs | a.x_coff | a.t_y_cs | a.t_y_coff) % 8) return false;
-    const long blocks = (long)(a.M / (a.Ho * a.Wo)) * (a.Wo / 16) * (a.Ho / 16);
-    if (blocks < 512 || (long)a.M * std::max(a.t_y_cs, 1) >= (1l << 31)) return false;     // a few tiles: the wide-step kernel (one block per CU there)
-    launch_c32s2_tail<2>(a, s);
-    return true;
-}
+void launch_conv_c32s2_tail(const ConvArgs& a, const ConvPlan&, hipStream_t s) { launch_c32s2_tail<2>(a, s); }
 
 // ------------------------------------------------------------------------------------------------
 // Streaming 1x1 conv for 64 output channels and at most 128 input channels, fp16 (YOLOv8n's `4.c2f.cv2` and `15.c2f.cv2` at large batch:
@@ -335,15 +316,11 @@ static void launch_1x1_stream(const ConvArgs& a, hipStream_t s) {
     KCHECK();
 }
 
-static bool try_1x1_stream(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_1X1_STREAM") != nullptr;
-    if (off || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.Cout != 64 || a.Cin % 32 || a.Cin > 128 || a.Cin < 64 || a.Kp != a.Cin) return false;
-    if (a.res_mode != 0 || a.out_f32 || a.k_order != 0 || a.xs || a.x2 || a.w_tail || a.n_dev || a.bias_init || a.cout_pad < 64) return false;
-    if (a.M < 150000 || (a.x_cs | a.x_coff | a.y_cs | a.y_coff) % 8 || (long)a.M * std::max(a.x_cs, a.y_cs) >= (1l << 31)) return false;
+void launch_conv_1x1_stream(const ConvArgs& a, const ConvPlan&, hipStream_t s) {
     if (a.Cin == 128) launch_1x1_stream<4>(a, s);
     else if (a.Cin == 96) launch_1x1_stream<3>(a, s);
-    else launch_1x1_stream<2>(a, s);
-    return true;
+    else if (a.Cin == 64) launch_1x1_stream<2>(a, s);
+    else AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no streaming 1x1 instantiation for this layer");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -579,30 +556,18 @@ __global__ __launch_bounds__(512) void conv3x3_c64_resident_kernel(const ConvArg
     wait_vmcnt<0>();
 }
 
-static bool try_c64_resident(const ConvArgs& a, hipStream_t s) {
-    // with or without the residual: 612 -> 774 TFLOP/s against the 4-wave patch kernel
-    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin != 64 || a.Cout != 64 || a.out_f32 || a.Kp != 576) return false;
-    if (a.W % 32 || a.H % 8 || a.Ho != a.H || a.Wo != a.W || a.M < 1500000 || (long)a.M * a.x_cs >= (1l << 31) ||
-        (long)a.M * a.y_cs >= (1l << 31) || (a.res_mode != 0 && (long)a.M * a.r_cs >= (1l << 31))) return false;
-    if ((a.x_cs | a.x_coff | a.y_cs | a.y_coff | a.r_cs | a.r_coff) % 8) return false;
+void launch_conv_c64_resident(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     const int tiles_x = a.W / 32, tiles_y = a.H / 8, n_img = a.M / (a.H * a.W), n_tiles = n_img * tiles_x * tiles_y;
     constexpr size_t lds = (size_t)3 * 8 * 384 * 16 + 256;
     auto launch = [&](auto kfn) {
-        static bool attr = false;
-        if (!attr) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr = true;
-        }
-        const int nblk = conv_cu_budget();
-        hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, n_tiles, tiles_x, tiles_y, nblk);
+        set_lds_limit(kfn, lds);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)p.blocks), dim3(512), lds, s, a, n_tiles, tiles_x, tiles_y, (int)p.blocks);
         KCHECK();
     };
     if (a.act == 2 && a.res_mode == 0) launch(conv3x3_c64_resident_kernel<2, 0>);
     else if (a.act == 2 && a.res_mode == 1) launch(conv3x3_c64_resident_kernel<2, 1>);
-    else return false;
-    return true;
+    else AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no weights-resident instantiation for this layer");
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // v3 for 3x3 / stride 1 / pad 1: the im2col gather of v2 fetches every input chunk 9 times (once per
@@ -780,62 +745,34 @@ __global__ __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu((N
 }
 
 template <typename T, int MT, int NT, int WM, int WN, int TH, int TW, int NSTAGE, int LGCPP, bool TAIL = false, int KORD = 0>
-static bool launch_patch(const ConvArgs& a, hipStream_t s) {
-    constexpr int CH = 16 / (int)sizeof(T), NTHR = 64 * WM * WN, RP = NTHR / 4;
+static void launch_patch(const ConvArgs& a, hipStream_t s) {
+    constexpr int NTHR = 64 * WM * WN, RP = NTHR / 4;
     constexpr int BN = WN * NT * 16, BNP = (BN + RP - 1) / RP * RP;
     constexpr int CPP = 1 << LGCPP, PAL = CPP >= 8 ? CPP : 8, PWP = (TW + 2 + PAL - 1) / PAL * PAL;
     constexpr int TOTAL = (TH + 2) * PWP * CPP;
     constexpr size_t lds = (size_t)(TOTAL + NTHR - 1) / NTHR * NTHR * 16 + (size_t)NSTAGE * BNP * 64;
     static_assert(lds <= 160 * 1024, "patch does not fit the LDS");
-    if (a.Cin != CPP * CH) return false;
     const int tiles_x = ceil_div(a.Wo, TW), tiles_y = ceil_div(a.Ho, TH);
     const int n_img = a.M / (a.Ho * a.Wo);
     auto kfn = conv3x3_patch_kernel<T, MT, NT, WM, WN, TH, TW, NSTAGE, LGCPP, TAIL, KORD>;
-    static bool attr = false;
-    if (lds > 64 * 1024 && !attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    if (lds > 64 * 1024) set_lds_limit(kfn, lds);
     dim3 grid(n_img * tiles_x * tiles_y, ceil_div(a.Cout, BN));
     hipLaunchKernelGGL(kfn, grid, dim3(NTHR), lds, s, a, tiles_x, tiles_y);
     KCHECK();
-    return true;
 }
 
-// 3x3/s1/p1 with Cin a multiple of the K-step: tile shape by output width.
-template <typename T>
-static bool try_patch(const ConvArgs& a, hipStream_t s) {
-    // Measured on MI355X (profiles/): the patch form wins where Cout is small and M is large (ReID layer1);
-    // for Cout >= 128 the 8-wave im2col tile is faster, and small maps are launch-bound either way.
-    static const bool c32 = getenv("AICAM_NO_PATCH_C32") == nullptr;   // Cin = Cout = 32 (YOLOv8n P3 bottlenecks): 244 -> 460 TFLOP/s
-    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8) return false;
-    if (a.M < 200000) return false;
-    if (a.k_order == 1) return false;                                       // (cc, kh, kw): only the implicit-GEMM kernels walk K that way
-    const bool wide = a.Wo % 32 == 0 || (a.Wo % 16 != 0 && a.Wo >= 32);   // 8 x 32 tiles unless 16 x 16 tiles cover the map exactly
-    if (a.k_order == 2) {                                                   // fp16, Cin = Cout = 64, W % 32 == 0 (launch_conv_igemm): the resident kernels' order
-        if constexpr (sizeof(T) == 2) return a.Cout == 64 && wide && launch_patch<T, 4, 4, 4, 1, 8, 32, 3, 3, false, 2>(a, s);
-        return false;
-    }
-    if (a.Cout == 64) {
-        constexpr int LG64 = sizeof(T) == 2 ? 3 : 4;    // Cin = 64: 8 chunks (fp16) / 16 chunks (fp32) per pixel
-        if (wide) return launch_patch<T, 4, 4, 4, 1, 8, 32, 3, LG64>(a, s);
-        return launch_patch<T, 4, 4, 4, 1, 16, 16, 3, LG64>(a, s);
-    }
-    if (a.Cout == 80) {                                 // YOLOv8n's 22.cls0.0 (64 -> 80 at 80 x 80; round 5): 461 TFLOP/s on the 512 x 80 implicit-GEMM tile
-        static const bool c80 = getenv("AICAM_NO_PATCH_C80") == nullptr;
-        if constexpr (sizeof(T) == 2) {
-            if (!c80) return false;
-            if (wide) return launch_patch<T, 4, 5, 4, 1, 8, 32, 3, 3>(a, s);
-            return launch_patch<T, 4, 5, 4, 1, 16, 16, 3, 3>(a, s);
-        }
-        return false;
-    }
-    if (a.Cout == 32 && c32) {
-        constexpr int LG32 = sizeof(T) == 2 ? 2 : 3;    // Cin = 32
-        if (wide) return launch_patch<T, 4, 2, 4, 1, 8, 32, 3, LG32>(a, s);
-        return launch_patch<T, 4, 2, 4, 1, 16, 16, 3, LG32>(a, s);
-    }
-    return false;
+// 3x3 / 1 / 1 with Cin = 64 (Cout 64 / 80, 16 K-steps per tap pair) or 32 (Cout 32), fp16: 8 x 32 or 16 x 16 tiles (conv_plan.cpp's patch())
+void launch_conv_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define PATCH(NT, TH, TW, CPP, LG, TAIL, KORD)                                                                                         \
+    if (p.nt == NT && p.th == TH && p.tw == TW && p.cpp == CPP && p.tail == TAIL && p.kord == KORD)                                    \
+        return launch_patch<half_t, 4, NT, 4, 1, TH, TW, 3, LG, TAIL, KORD>(a, s);
+    AIC_REQUIRE(p.mt == 4 && p.wm == 4 && p.wn == 1 && p.nstage == 3, AIC_ERR_INVALID, "conv plan: no patch instantiation for this tile");
+    PATCH(4, 8, 32, 8, 3, false, 2)
+    PATCH(4, 8, 32, 8, 3, false, 0) PATCH(4, 16, 16, 8, 3, false, 0) PATCH(5, 8, 32, 8, 3, false, 0) PATCH(5, 16, 16, 8, 3, false, 0)
+    PATCH(2, 8, 32, 4, 2, false, 0) PATCH(2, 16, 16, 4, 2, false, 0)
+    PATCH(4, 8, 32, 8, 3, true, 0) PATCH(4, 16, 16, 8, 3, true, 0)
+#undef PATCH
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no patch instantiation for this tile");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -968,77 +905,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT >= 9 ? 1
 }
 
 template <int CPP, int PITCH, int NT, bool TAIL, int TH = 16, int TW = 16, int MT = 4>
-static bool launch_pm_patch(const ConvArgs& a, hipStream_t s) {
+static void launch_pm_patch(const ConvArgs& a, hipStream_t s) {
     constexpr int BNP = (NT * 16 + 63) / 64 * 64;
     constexpr size_t lds = (size_t)(((TH + 2) * (TW + 2) * PITCH + 255) / 256 * 256) * 16 + (size_t)3 * BNP * 64;
     static_assert((NT >= 9 ? 1 : 2) * lds <= 160 * 1024, "two blocks per CU (the 144-channel form: one, its patch alone is 112 KB)");
     auto kfn = conv3x3_pm_patch_kernel<CPP, PITCH, NT, TAIL, TH, TW, MT>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(kfn, lds);
     const int tiles_x = ceil_div(a.Wo, TW), tiles_y = ceil_div(a.Ho, TH), n_img = a.M / (a.Ho * a.Wo);
     hipLaunchKernelGGL(kfn, dim3(n_img * tiles_x * tiles_y), dim3(256), lds, s, a, tiles_x, tiles_y);
     KCHECK();
-    return true;
 }
 
-// shapes every form shares: 3x3 / 1 / 1 on whole maps, fp16, memory K order, launches of 50 000 pixels and more (below: a few tiles, the
-// wide-step kernel or v2)
-static bool pm_patch_shape(const ConvArgs& a) {
-    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.k_order != 0 || a.xs || a.x2 || a.n_dev || a.out_f32 || a.bias_init) return false;
-    return a.Ho == a.H && a.Wo == a.W && a.M >= 50000 && (a.x_cs | a.x_coff | a.y_cs | a.y_coff | a.r_cs | a.r_coff) % 8 == 0;
+// conv_plan.cpp's pm_patch().  (32 -> 32 on 80 x 80 maps -- YOLOv8n's P3 bottlenecks -- as launch_pm_patch<4, 5, 2, false> on 16 x 16 tiles:
+// built, bit-identical, measured 843 against 830 us for the four layers of 4.c2f: they wait on 64-byte slices of the concat buffer.  Not kept.)
+void launch_conv_pm_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define PM(CPP, PITCH, NT, TAIL, TH, TW, MT) \
+    if (p.cpp == CPP && p.pitch == PITCH && p.nt == NT && p.tail == TAIL && p.th == TH && p.tw == TW && p.mt == MT) \
+        return launch_pm_patch<CPP, PITCH, NT, TAIL, TH, TW, MT>(a, s);
+    PM(10, 10, 5, true, 16, 16, 4) PM(8, 9, 4, true, 40, 8, 5) PM(8, 9, 4, true, 16, 16, 4)
+    PM(8, 9, 4, false, 40, 8, 5) PM(16, 17, 9, false, 40, 8, 5)
+#undef PM
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no pixel-major patch instantiation for this tile");
 }
-// 16 x 16 tiles cover the map with at most half as many pixels again hanging over the edge (40 x 40: 1.44; 20 x 20 would be 2.56)
-static bool pm_cover16(const ConvArgs& a) {
-    const long cover = (long)ceil_div(a.Wo, 16) * 16 * ceil_div(a.Ho, 16) * 16;
-    return 2 * cover <= 3 * (long)a.Wo * a.Ho;
-}
-
-// lead + 1x1 tail: 80 -> 80 (the class branches), 64 -> 64 (the box branches)
-bool conv_try_pm_patch_tail(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_PATCH_C80") != nullptr;
-    if (off || !a.w_tail || !pm_patch_shape(a) || a.res_mode != 0 || a.act != 1) return false;
-    if (a.Cin == 80 && a.Cout == 80 && a.Kp == 736 && a.cout_pad >= 128 && pm_cover16(a)) return launch_pm_patch<10, 10, 5, true>(a, s);
-    if (a.Cin == 64 && a.Cout == 64 && a.Kp == 576 && a.cout_pad >= 64) {
-        if (a.Ho == 40 && a.Wo % 8 == 0) return launch_pm_patch<8, 9, 4, true, 40, 8, 5>(a, s);
-        if (pm_cover16(a)) return launch_pm_patch<8, 9, 4, true>(a, s);
-    }
-    return false;
-}
-// without a tail: 64 -> 64 on 40-row maps in 40 x 8 strips (YOLOv8n's P4 bottlenecks: eight layers on conv3x3_patch_kernel's 8 x 32 tiles,
-// which cover 1.6 maps).  On maps its 16 x 16 tiles cover exactly this form is no faster than that kernel (measured: 22.box0.0 348 against 354 us).
-bool conv_try_pm_patch(const ConvArgs& a, hipStream_t s) {
-    static const bool off = getenv("AICAM_NO_PATCH_C80") != nullptr;
-    if (off || a.w_tail || !pm_patch_shape(a) || a.act != 1 || (a.res_mode != 0 && a.res_mode != 2)) return false;
-    if (a.Cin == 64 && a.Cout == 64 && a.Kp == 576 && a.cout_pad >= 64 && a.Ho == 40 && a.Wo % 8 == 0) return launch_pm_patch<8, 9, 4, false, 40, 8, 5>(a, s);
-    // (32 -> 32 on 80 x 80 maps -- YOLOv8n's P3 bottlenecks, which conv3x3_patch_kernel's 8 x 32 tiles cover 1.2 times -- as
-    //  launch_pm_patch<4, 5, 2, false> on 16 x 16 tiles that cover the map exactly: built, bit-identical, measured 843 against 830 us for the
-    //  four layers of 4.c2f.  They do not wait for their tiles: they read and write 64-byte slices of a 256-byte-pitch concat buffer.  Not kept.)
-    // 128 -> 144 on 40-row maps: the merged first convs of YOLOv8n's 40 x 40 detect level (22.box1.0 + 22.cls1.0), which the implicit GEMM runs on a
-    // 256 x 144 tile with 36 accumulator tiles per wave, one wave per SIMD.  Sixteen chunks per pixel at a pitch of 17 (272 bytes: the 16 lanes of a
-    // fragment read sit four banks apart), nine channel tiles (the odd last one keeps the identity map), one block per CU.
-    if (a.res_mode == 0 && a.Cin == 128 && a.Cout == 144 && a.Kp == 1152 && a.cout_pad >= 144 && a.Ho == 40 && a.Wo % 8 == 0)
-        return launch_pm_patch<16, 17, 9, false, 40, 8, 5>(a, s);
-    return false;
-}
-
-// the Cout = 64 patch kernel with a 1x1 tail (same eligibility as try_patch)
-bool conv_try_patch_tail(const ConvArgs& a, hipStream_t s) {
-    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Wo < 16 || a.Ho < 8 || a.M < 200000 || a.Cout != 64 || a.k_order != 0) return false;
-    const bool wide = a.Wo % 32 == 0 || (a.Wo % 16 != 0 && a.Wo >= 32);
-    if (wide) return launch_patch<half_t, 4, 4, 4, 1, 8, 32, 3, 3, true>(a, s);
-    return launch_patch<half_t, 4, 4, 4, 1, 16, 16, 3, 3, true>(a, s);
-}
-
-bool conv_try_patch(int dtype, const ConvArgs& a, hipStream_t s) {
-    return dtype == AIC_F16 ? try_patch<half_t>(a, s) : false;          // (fp32 engines: the LDS-DMA implicit GEMM only, kernels_conv.hip)
-}
-bool conv_try_c16(const ConvArgs& a, hipStream_t s) { return try_c16(a, s); }
-bool conv_try_c32s2_tail(const ConvArgs& a, hipStream_t s) { return try_c32s2_tail(a, s); }
-bool conv_try_1x1_stream(const ConvArgs& a, hipStream_t s) { return try_1x1_stream(a, s); }
-bool conv_try_c64_resident(const ConvArgs& a, hipStream_t s) { return try_c64_resident(a, s); }
 
 // ------------------------------------------------------------------------------------------------
 // Fused ReID stem: conv 3x3/1 (3 -> 64) + bias + ReLU + max-pool 3x3/2 (pad 1) in one kernel, fp16.
@@ -1384,21 +1272,13 @@ void launch_reid_stem_pool(const void* x, const void* w, const float* bias, void
     AIC_REQUIRE(in_stride == 8 || (in_stride == 4 && reid_stem2_usable(H, W)), AIC_ERR_INVALID, "NHWC4 input needs the second stem form");
     const size_t lds2 = (size_t)(H + 2) * 66 * 8;
     if (reid_stem2_usable(H, W)) {
-        static bool attr2 = false;
-        if (!attr2) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(reid_stem_pool2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // + 8 KB of static tap tables
-            attr2 = true;
-        }
+        set_lds_limit(reid_stem_pool2_kernel, 150 * 1024);          // + 8 KB of static tap tables
         hipLaunchKernelGGL(reid_stem_pool2_kernel, dim3(n), dim3(512), lds2, s, a);
         KCHECK();
         return;
     }
     const size_t lds = ((11 * 66 * 8 + 15) / 16) * 16 + (size_t)9 * 64 * 128;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(reid_stem_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(reid_stem_pool_kernel, lds);
     hipLaunchKernelGGL(reid_stem_pool_kernel, dim3(n * (H / 2 / 4)), dim3(256), lds, s, a);
     KCHECK();
 }

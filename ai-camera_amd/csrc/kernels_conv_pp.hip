@@ -276,11 +276,7 @@ static void launch_pp(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = (size_t)NSTAGE * (BM + BNP) * 64;
     static_assert(lds <= 160 * 1024, "ring does not fit the LDS");
     auto kfn = conv_igemm_pp_kernel<T, MT, NT, WM, WN, NSTAGE>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(kfn, lds);
     static const bool times = getenv("AICAM_PP_TIMES") != nullptr;
     if (times) {
         const int on = 1;
@@ -619,37 +615,13 @@ __global__ __launch_bounds__(512) void conv3x3_pp_patch_kernel(const ConvArgs a,
 }
 
 template <typename T, int MT, int NT, int WM, int WN, int TH, int TW, int NSTAGE, bool X2 = false>
-static bool launch_pp_patch(const ConvArgs& a, hipStream_t s) {
+static void launch_pp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16, BNP = (BN + 127) / 128 * 128;
     constexpr int NI = BM / (TH * TW), NPIX = NI * ppp_ipix_pad(TH, TW), NPASS = (NPIX + 127) / 128;
     constexpr size_t lds = (size_t)2 * 4 * NPASS * 128 * 16 + 8192 + (size_t)NSTAGE * BNP * 64 + (X2 ? BM * 64 : 0);
     static_assert(lds <= 160 * 1024, "does not fit the LDS");
-    if (a.H % TH || a.W % TW || a.Ho != a.H || a.Wo != a.W) return false;
-    if (a.M >= (1 << 23) || a.x_cs >= (1 << 23) || (long)a.M * a.x_cs >= (1l << 31)) return false;      // issue_patch's 24-bit address arithmetic
-    if (X2 && ((long)(a.M / (a.Ho * a.Wo)) * a.H2 >= (1 << 23) || (long)a.W2 * a.x2_cs >= (1 << 23) ||
-               (long)(a.M / (a.Ho * a.Wo)) * a.H2 * a.W2 * a.x2_cs >= (1l << 31))) return false;                // issue_e's
-    const int tiles_x = a.W / TW, tiles_y = a.H / TH;
-    const int n_img = a.M / (a.Ho * a.Wo);
     auto kfn = conv3x3_pp_patch_kernel<T, MT, NT, WM, WN, TH, TW, NSTAGE, X2>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    // tiles per block: at most 6.  Same box, 15 360 crops: layer2 conv1 1 993 (one tile per block, the kernel before) ->
-    // 1 975 / 1 945 / 1 912 us at runs of 1 / 4 / 6; with a residual 2 257 -> 2 256 (its 9 us epilogue is what is left); layer3 / 4 -2 % / 0
-    const int ny = ceil_div(a.Cout, BN);
-    const long ntiles = (long)ceil_div(n_img, NI) * tiles_x * tiles_y * ny;
-    int run = 1;                                  // (second source: one tile per block)  the longest run that does not add a round of tiles (256 CUs, one block each) and leaves >= 4 rounds of blocks
-    {
-        long best = -1;
-        for (int r = 1; r <= (X2 ? 1 : 6); ++r) {
-            const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
-            if (r > 1 && rounds < 4) break;
-            const long cost = rounds * r;                 // tile times until the last block ends
-            if (best < 0 || cost <= best) best = cost, run = r;
-        }
-    }
+    set_lds_limit(kfn, lds);
     static const bool times = getenv("AICAM_PP_TIMES") != nullptr;
     if (times) {
         const int on = 1;
@@ -659,88 +631,29 @@ static bool launch_pp_patch(const ConvArgs& a, hipStream_t s) {
     // on the 512 x 128 tile (AICAM_PP_TIMES, one tile per block): 2 us off the epilogue (9.2 -> 7.2 us), 2.5 us onto the K loop (27.6 -> 30.3 us)
     // -- the pass is a load from HBM in the in-order vmcnt queue, and the next segment's counted wait stands behind it where it used to stand
     // behind a zero-page hit; layer2 / 3 / 4 conv2 alone: 2 432 / 2 021 / 1 894 us without, 2 452 / 2 019 / 1 889 with.  Not kept.)
-    const int nblk = (int)ceil_div(ntiles, (long)run);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, tiles_x, tiles_y, ny, run);
-    if (times) { KCHECK(); pp_times_report(s, nblk); }
+    hipLaunchKernelGGL(kfn, dim3((unsigned)p.blocks), dim3(512), lds, s, a, a.W / TW, a.H / TH, ceil_div(a.Cout, BN), p.run);
+    if (times) { KCHECK(); pp_times_report(s, (int)p.blocks); }
     KCHECK();
-    return true;
 }
 
-// 3x3/s1/p1 layers whose map tiles exactly: pick the tile by map shape and Cout (ReID layer2..4 shapes and their multiples).  (A Cout 64 tile
-// was slower than the 4-wave patch kernel -- 16 MFMAs per segment -- and a deeper weight ring gained nothing.)
-// The layer SHAPES this kernel takes (a property of the graph, not of the batch): 2 = Cout 128, 3 = Cout % 256 on 16 x 8 tiles, 4 = on
-// 8 x 4 tiles; 0 = not one of them.  Such a layer is walked chunk-major by EVERY conv kernel (ConvArgs::k_order = 1).
-template <typename T>
-static int pp_patch_shape(const ConvArgs& a) {
-    constexpr int BKE = 64 / (int)sizeof(T);
-    if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin % (2 * BKE) || a.Ho != a.H || a.Wo != a.W) return 0;
-    const int c = a.Cout;
-    if (c == 128) return (a.H % 32 == 0 && a.W % 16 == 0) ? 2 : 0;
-    if (c % 256 == 0) return (a.H % 16 == 0 && a.W % 8 == 0) ? 3 : ((a.H % 8 == 0 && a.W % 4 == 0) ? 4 : 0);
-    return 0;
+// v4: 256 px x 256 ch or 512 px x 128 ch (fp16; plan_conv's pp())
+void launch_conv_pp(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    AIC_REQUIRE(p.mt == 8 && p.nt == 4 && p.nstage == 4 && p.wm * p.wn == 8, AIC_ERR_INVALID, "conv plan: no ping-pong instantiation for this tile");
+    if (p.wm == 2) launch_pp<half_t, 8, 4, 2, 4, 4>(a, s);
+    else launch_pp<half_t, 8, 4, 4, 2, 4>(a, s);
 }
 
-template <typename T>
-static bool try_pp_patch(const ConvArgs& a, hipStream_t s) {
-    static const int pp_min = [] { const char* e = getenv("AICAM_PP_MIN"); return e ? atoi(e) : 200; }();
-    const int shape = pp_patch_shape<T>(a);
-    if (!shape) return false;
-    if ((long)a.M * a.x_cs >= (1l << 31)) return false;                       // 32-bit element offsets inside the kernel
-    const int c = a.Cout;
-    if (a.x2) {                                     // a second source (conv_x2_supported: shapes 2, 3 and 4)
-        if (shape == 2 && a.M / 512 >= pp_min) return launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 4, true>(a, s);
-        if (shape == 3 && (long)(a.M / 256) * (c / 256) >= pp_min) return launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 4, true>(a, s);
-        if (shape == 4 && (long)(a.M / 256) * (c / 256) >= pp_min) return launch_pp_patch<T, 8, 4, 2, 4, 8, 4, 4, true>(a, s);
-        return false;
-    }
-    if constexpr (sizeof(T) == 2) {                 // fp16: the software-pipelined form of the same tiles (kernels_conv_sp.hip; same K order, same bits)
-        if ((shape == 2 && a.M / 512 >= pp_min) || (shape >= 3 && (long)(a.M / 256) * (c / 256) >= pp_min))
-            if (conv_try_sp_patch(a, shape, s)) return true;
-    }
-    if (shape == 2 && a.M / 512 >= pp_min) return launch_pp_patch<T, 8, 4, 4, 2, 32, 16, 4>(a, s);
-    if (shape >= 3 && (long)(a.M / 256) * (c / 256) >= pp_min) {
-        if (shape == 3) return launch_pp_patch<T, 8, 4, 2, 4, 16, 8, 4>(a, s);
-        return launch_pp_patch<T, 8, 4, 2, 4, 8, 4, 4>(a, s);
-    }
-    return false;
-}
-
-
-bool conv_try_pp_patch(int dtype, const ConvArgs& a, hipStream_t s) {
-    return dtype == AIC_F16 ? try_pp_patch<half_t>(a, s) : false;       // (fp32 engines: the LDS-DMA implicit GEMM only, kernels_conv.hip)
-}
-
-int conv_pp_patch_shape(int dtype, const ConvArgs& a) {
-    return dtype == AIC_F16 ? pp_patch_shape<half_t>(a) : pp_patch_shape<float>(a);
-}
-
-// Ping-pong kernels (one block per CU) where the K loop is long enough to amortise the tile's prologue/epilogue:
-// measured on MI355X (tools/conv_bench.py, profiles/): +17..19% on ReID layer3/4, +14% on layer2, a loss at K < 512.
-template <typename T>
-static bool try_pp(const ConvArgs& a, hipStream_t s) {
-    static const int pp_min = [] { const char* e = getenv("AICAM_PP_MIN"); return e ? atoi(e) : 200; }();
-    // 18 K-steps: ReID layer2.0.conv1 (3x3 / 2, 64 -> 128, K = 576) takes the 512 x 128 ping-pong tile: 1 058 -> 948 us per 7 680 crops
-    // against the 8-wave 256 x 128 LDS-DMA tile (tools/conv_bench.py 64 32 64 128 3 7680 1 0 2); below that the short loop loses
-    constexpr int BKE_ = 64 / (int)sizeof(T);
-    const int c = a.Cout;
-    if (a.Cin % BKE_ != 0 || !(a.Kp >= 16 * BKE_ || pp_min == 0)) return false;
-    if constexpr (sizeof(T) == 2) {                 // stride-2 3x3 layers of the patch kernels' maps: the space-to-depth patch form (kernels_conv_sp.hip)
-        if (a.k_order == 3 && ((c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= pp_min) || (c == 128 && ceil_div(a.M, 512) >= pp_min)))
-            if (conv_try_s2_patch(a, s)) return true;
-    }
-    if (c % 256 == 0 && (long)ceil_div(a.M, 256) * (c / 256) >= pp_min) {                                  // 256 px x 256 ch
-        launch_pp<T, 8, 4, 2, 4, 4>(a, s);
-        return true;
-    }
-    if (c == 128 && (a.Kp >= 18 * BKE_ || pp_min == 0) && ceil_div(a.M, 512) >= pp_min) {              // 512 px x 128 ch
-        launch_pp<T, 8, 4, 4, 2, 4>(a, s);
-        return true;
-    }
-    return false;
-}
-
-bool conv_try_pp(int dtype, const ConvArgs& a, hipStream_t s) {
-    return dtype == AIC_F16 ? try_pp<half_t>(a, s) : false;
+// v5 on the three pp_patch shapes (conv_plan.cpp: 2 = Cout 128 on 32 x 16 tiles, 3 / 4 = Cout % 256 on 16 x 8 / 8 x 4 tiles), with or
+// without a second source (fp16).  (A Cout 64 tile was slower than the 4-wave patch kernel -- 16 MFMAs per segment -- and a deeper weight
+// ring gained nothing.)
+void launch_conv_pp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define PPP(WM, WN, TH, TW, X2)                                                                                     \
+    if (p.mt == 8 && p.nt == 4 && p.nstage == 4 && p.wm == WM && p.wn == WN && p.th == TH && p.tw == TW && p.x2 == X2) \
+        return launch_pp_patch<half_t, 8, 4, WM, WN, TH, TW, 4, X2>(a, p, s);
+    PPP(4, 2, 32, 16, false) PPP(2, 4, 16, 8, false) PPP(2, 4, 8, 4, false)
+    PPP(4, 2, 32, 16, true) PPP(2, 4, 16, 8, true) PPP(2, 4, 8, 4, true)
+#undef PPP
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no ping-pong patch instantiation for this tile");
 }
 
 }  // namespace aic

@@ -271,36 +271,15 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
 }
 
 template <int MT, int NT, int WM, int WN, int TH, int TW>
-static bool launch_sp_patch(const ConvArgs& a, hipStream_t s) {
+static void launch_sp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
     constexpr int NI = BM / (TH * TW), NPIX = NI * ppp_ipix_pad(TH, TW), NPASS = (NPIX + 127) / 128;
     constexpr size_t lds = (size_t)2 * 4 * NPASS * 128 * 16 + 8192 + (size_t)4 * BN * 64;
     static_assert(lds <= 160 * 1024, "does not fit the LDS");
-    if (a.H != TH || a.W != TW || a.Ho != a.H || a.Wo != a.W || a.Cout % BN) return false;            // whole-image tiles, whole channel tiles
-    if ((long)a.M * a.x_cs * 2 >= (1l << 32) || (long)a.Cout * a.Kp * 2 >= (1l << 32)) return false;   // 32-bit byte strides inside the kernel
-    const int n_img = a.M / (a.Ho * a.Wo);
     auto kfn = conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    const int ny = a.Cout / BN;
-    const long ntiles = (long)ceil_div(n_img, NI) * ny;
-    int run = 1;                                  // the longest run (at most 6 tiles) that does not add a round of tiles (256 CUs, one block each) and leaves >= 4 rounds of blocks
-    {
-        long best = -1;
-        for (int r = 1; r <= 6; ++r) {
-            const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
-            if (r > 1 && rounds < 4) break;
-            const long cost = rounds * r;
-            if (best < 0 || cost <= best) best = cost, run = r;
-        }
-    }
-    const int nblk = (int)ceil_div(ntiles, (long)run);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, ny, run);
+    set_lds_limit(kfn, lds);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)p.blocks), dim3(512), lds, s, a, a.Cout / BN, p.run);
     KCHECK();
-    return true;
 }
 
 // (The same schedule with the pixel operand as an im2col tile -- for the STRIDE-2 3x3 convs of ReID layerN.0.conv1 -- was built too
@@ -592,64 +571,31 @@ __global__ __launch_bounds__(512) void conv3x3s2_sp_patch_kernel(const ConvArgs 
 }
 
 template <int WM, int WN, int TH, int TW>
-static bool launch_s2_patch(const ConvArgs& a, hipStream_t s) {
+static void launch_s2_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     constexpr int BM = WM * 128, BN = WN * 64;
     constexpr int NI = BM / (TH * TW), NPIX = NI * ppp_ipix_pad(TH, TW), NPASS = (NPIX + 127) / 128;
     constexpr size_t lds = (size_t)3 * 4 * NPASS * 128 * 16 + (size_t)4 * BN * 64;
     static_assert(lds <= 160 * 1024, "does not fit the LDS");
-    if (a.Ho != TH || a.Wo != TW || a.H != 2 * TH || a.W != 2 * TW || a.Cout % BN || a.Cin % 64) return false;
-    if ((long)a.M * 4 * a.x_cs * 2 >= (1l << 32) || (long)a.Cout * a.Kp * 2 >= (1l << 32)) return false;   // 32-bit byte strides inside the kernel
-    const int n_img = a.M / (a.Ho * a.Wo);
     auto kfn = conv3x3s2_sp_patch_kernel<WM, WN, TH, TW>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    const int ny = a.Cout / BN;
-    const long ntiles = (long)ceil_div(n_img, NI) * ny;
-    int run = 1;
-    {
-        long best = -1;
-        for (int r = 1; r <= 6; ++r) {
-            const long blocks = (ntiles + r - 1) / r, rounds = (blocks + 255) / 256;
-            if (r > 1 && rounds < 4) break;
-            const long cost = rounds * r;
-            if (best < 0 || cost <= best) best = cost, run = r;
-        }
-    }
-    const int nblk = (int)ceil_div(ntiles, (long)run);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(512), lds, s, a, ny, run);
+    set_lds_limit(kfn, lds);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)p.blocks), dim3(512), lds, s, a, a.Cout / BN, p.run);
     KCHECK();
-    return true;
 }
 
-// The stride-2 shapes (a property of the layer, not of the batch: such a layer is walked in k_order 3 by EVERY kernel): 3x3 / 2 / 1 convs whose
-// OUTPUT is one of the patch kernels' maps -- 1: Cout 128 on 32 x 16, 2: Cout % 256 on 16 x 8 -- with Cin a multiple of 64.
-int conv_s2_patch_shape(const ConvArgs& a) {
-    if (a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.Cin % 64 || a.Kp != 9 * a.Cin || a.x2 || a.xs || a.w_tail) return 0;
-    if (a.H != 2 * a.Ho || a.W != 2 * a.Wo) return 0;
-    if (a.Cout == 128 && a.Ho == 32 && a.Wo == 16) return 1;
-    if (a.Cout % 256 == 0 && a.Ho == 16 && a.Wo == 8) return 2;
-    // (8 x 4 output maps, ReID layer4.0.conv1: built and measured -- 1 135 against v4's 1 008 us per 15 360 crops; the map is small enough for the
-    //  im2col gather to stay in the L2.  Not kept.)
-    return 0;
-}
-bool conv_try_s2_patch(const ConvArgs& a, hipStream_t s) {           // fp16, a batch large enough for one-block-per-CU tiles (the caller's check)
-    const int shape = conv_s2_patch_shape(a);
-    if (shape == 1) return launch_s2_patch<4, 2, 32, 16>(a, s);
-    if (shape == 2) return launch_s2_patch<2, 4, 16, 8>(a, s);
-    return false;
+// the two stride-2 shapes (conv_plan.cpp: Cout 128 on 32 x 16 output maps, Cout % 256 on 16 x 8), fp16
+void launch_conv_s2_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    if (p.wm == 4 && p.wn == 2 && p.th == 32 && p.tw == 16) return launch_s2_patch<4, 2, 32, 16>(a, p, s);
+    if (p.wm == 2 && p.wn == 4 && p.th == 16 && p.tw == 8) return launch_s2_patch<2, 4, 16, 8>(a, p, s);
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no stride-2 patch instantiation for this tile");
 }
 
-// shape: conv_pp_patch_shape()'s (2 = Cout 128 on 32 x 16 maps, 3 / 4 = Cout % 256 on 16 x 8 / 8 x 4 maps); the caller has checked that the
-// batch is large enough for one-block-per-CU tiles.
-bool conv_try_sp_patch(const ConvArgs& a, int shape, hipStream_t s) {
-    if (a.x2 || a.Cin % 128) return false;
-    if (shape == 2) return launch_sp_patch<8, 4, 4, 2, 32, 16>(a, s);
-    if (shape == 3) return launch_sp_patch<8, 4, 2, 4, 16, 8>(a, s);
-    if (shape == 4) return launch_sp_patch<8, 4, 2, 4, 8, 4>(a, s);
-    return false;
+// the shapes of v5 without a second source (conv_plan.cpp: 2 = Cout 128 on 32 x 16 maps, 3 / 4 = Cout % 256 on 16 x 8 / 8 x 4 maps), fp16
+void launch_conv_sp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    const bool t84 = p.mt == 8 && p.nt == 4;
+    if (t84 && p.wm == 4 && p.wn == 2 && p.th == 32 && p.tw == 16) return launch_sp_patch<8, 4, 4, 2, 32, 16>(a, p, s);
+    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 16 && p.tw == 8) return launch_sp_patch<8, 4, 2, 4, 16, 8>(a, p, s);
+    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 8 && p.tw == 4) return launch_sp_patch<8, 4, 2, 4, 8, 4>(a, p, s);
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no software-pipelined patch instantiation for this tile");
 }
 
 }  // namespace aic

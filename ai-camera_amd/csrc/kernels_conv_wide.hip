@@ -194,14 +194,16 @@ __global__ __launch_bounds__(256) void conv_wide_kernel(const ConvArgs a, const 
 
 // ---- the K walk of a layer shape as a table (v2's walks, kernels_conv.hip: k_order 0 = tap outer / chunk inner, 2 = tap column / chunk / tap row, 1 = chunk outer / taps in
 // order with the second source's chunk e behind tap (0, 0) of chunk e + 1, 3 = chunk outer / taps plane by plane).  One per distinct
-// (KH, W, x_cs, Cin, k_order, Cin2), built at first use, kept for the life of the process (a few KB each).
+// (device, KH, W, x_cs, Cin, k_order, Cin2), built at first use, kept for the life of the process (a few KB each).
 struct KTab { const uint4* dev; int nsteps; };
 
 static KTab ktab_for(const ConvArgs& a) {
     static std::mutex mu;
-    static std::map<std::array<int, 6>, KTab> cache;
+    static std::map<std::array<int, 7>, KTab> cache;
     const int cin2 = a.x2 ? a.Cin2 : 0;
-    const std::array<int, 6> key{a.KH, a.W, a.x_cs, a.Cin, a.k_order, cin2};
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const std::array<int, 7> key{dev, a.KH, a.W, a.x_cs, a.Cin, a.k_order, cin2};
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
@@ -211,7 +213,7 @@ static KTab ktab_for(const ConvArgs& a) {
     int ti = 0, cc = 0;
     bool xs = false;
     for (int k = 0; k < nsteps; ++k) {
-        if (a.k_order == 2) {                   // (kw, chunk, kh): the weights-resident kernels' order (3x3 only, conv_wide_ok)
+        if (a.k_order == 2) {                   // (kw, chunk, kh): the weights-resident kernels' order (3x3 only: conv_plan.cpp's wide())
             const int kw2 = k / (3 * csteps), c2 = (k / 3) % csteps, kh2 = k % 3, tap2 = kh2 * 3 + kw2;
             t.push_back(uint4{(unsigned)(((kh2 * a.W + kw2) * a.x_cs + c2 * 32) * 2), (unsigned)((tap2 * a.Cin + c2 * 32) * 2), 1u << tap2, 0u});
             continue;
@@ -235,66 +237,33 @@ static KTab ktab_for(const ConvArgs& a) {
     return r;
 }
 
-// The layers this kernel takes; `blocks`: the grid v2 would launch for the same tile (at most 256)
-static bool conv_wide_ok(const ConvArgs& a, long blocks, bool tail) {
-    if (blocks > 256) return false;
-    if (a.xs || a.n_dev || (a.w_tail != nullptr) != tail) return false;
-    if (a.k_order < 0 || a.k_order > 3) return false;
-    if ((a.k_order == 2) != (a.bias_init != nullptr) || (a.k_order == 2 && (a.KH != 3 || a.x2 || tail))) return false;      // order 2 comes with the bias in front
-    if (a.x2 && (a.k_order != 1 || tail || a.Cin2 <= 0 || a.Cin2 % 32 || a.Cin2 / 32 >= a.Cin / 32)) return false;
-    if (a.KH != a.KW || (a.KH != 1 && a.KH != 3) || a.pad != a.KH / 2 || a.Cin % 32 || a.Kp != a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0)) return false;
-    if (a.KH == 3 && a.tap_rows != 0x49u) return false;
-    if ((long)(2 * a.W + 2) * a.x_cs * 2 + a.Cin * 2 >= (1l << 31) || (long)a.Kp * 2 >= (1l << 31)) return false;      // the table's 32-bit byte offsets
-    if (a.Kp / 32 < 8) return false;                             // a K loop of a few steps has nothing to group
-    return true;
-}
-
 template <int MT, int NT, int WM, int WN, int G, int NG, bool TAIL, bool X2>
-static void launch_wide(const ConvArgs& a, dim3 grid, hipStream_t s) {
+static void launch_wide(const ConvArgs& a, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16, BNP = (BN + 63) / 64 * 64;
     constexpr size_t lds = (size_t)NG * G * (BM + BNP) * 64;
     auto kfn = conv_wide_kernel<MT, NT, WM, WN, G, NG, TAIL, X2>;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
+    set_lds_limit(kfn, lds);
     const KTab t = ktab_for(a);
-    hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, a, t.dev, t.nsteps);
+    hipLaunchKernelGGL(kfn, dim3(ceil_div(a.M, BM), ceil_div(a.Cout, BN)), dim3(256), lds, s, a, t.dev, t.nsteps);
     KCHECK();
 }
 
-template <int MT, int NT, int WM, int WN, bool TAIL>
-static bool try_wide(const ConvArgs& a, hipStream_t s) {
-    constexpr int BM = WM * MT * 16, BN = WN * NT * 16, BNP = (BN + 63) / 64 * 64;
-    constexpr int STAGE = (BM + BNP) * 64;
-    dim3 grid(ceil_div(a.M, BM), ceil_div(a.Cout, BN));
-    if (!conv_wide_ok(a, (long)grid.x * grid.y, TAIL)) return false;
-    // Ring shape (tools/conv_bench.py, ReID layer4 at 28 crops, 60.7 us on v2): G = 4 with 3 or 5 groups in the ring 32.3 / 32.8 us, G = 2 with 10
-    // groups 34.3 us -- the depth does not matter.  At most 96 .. 120 KB of LDS, so that a block of another stream's kernel still fits beside it.
-    constexpr int G = STAGE <= 8 * 1024 ? 4 : 2;
-    if constexpr (!TAIL && (BN == 64 || BN == 128) && WN == 2) {          // (the tiles the ReID trunk's second-source layers take at these sizes)
-        if (a.x2) { launch_wide<MT, NT, WM, WN, G, 3, false, true>(a, grid, s); return true; }
+// The tiles plan_conv hands to this kernel (conv_plan.cpp: the 4-wave tiles of fp16 layers, the 144-channel tile, the tail forms and the
+// second-source forms of the two tiles the ReID trunk's second-source layers take at these sizes).  G: K-steps per group, from the stage size.
+void launch_conv_wide(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define WIDE(MT, NT, WM, WN, TAIL, X2)                                                                                           \
+    if (p.mt == MT && p.nt == NT && p.wm == WM && p.wn == WN && p.tail == TAIL && p.x2 == X2 && p.nstage == 3) {                \
+        constexpr int G = (WM * MT * 16 + (WN * NT * 16 + 63) / 64 * 64) * 64 <= 8 * 1024 ? 4 : 2;                             \
+        AIC_REQUIRE(p.g == G, AIC_ERR_INVALID, "conv plan: wide-step group size");                                              \
+        return launch_wide<MT, NT, WM, WN, G, 3, TAIL, X2>(a, s);                                                               \
     }
-    if (a.x2) return false;
-    launch_wide<MT, NT, WM, WN, G, 3, TAIL, false>(a, grid, s);
-    return true;
+    WIDE(4, 4, 2, 2, false, false) WIDE(2, 2, 2, 2, false, false) WIDE(2, 5, 4, 1, false, false) WIDE(4, 4, 4, 1, false, false)
+    WIDE(2, 4, 4, 1, false, false) WIDE(2, 3, 4, 1, false, false) WIDE(4, 2, 4, 1, false, false) WIDE(4, 1, 4, 1, false, false)
+    WIDE(2, 9, 4, 1, false, false)                                       // the merged first convs of a detect level (144 channels)
+    WIDE(4, 4, 2, 2, false, true) WIDE(2, 2, 2, 2, false, true)         // second source
+    WIDE(2, 4, 4, 1, true, false) WIDE(2, 5, 4, 1, true, false)         // 128 px x 64 / 80 ch + 1x1 tail
+#undef WIDE
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no wide-step instantiation for this tile");
 }
-
-template <int MT, int NT, int WM, int WN> bool conv_try_wide(const ConvArgs& a, hipStream_t s) { return try_wide<MT, NT, WM, WN, false>(a, s); }
-template <int MT, int NT> bool conv_try_wide_tail(const ConvArgs& a, hipStream_t s) { return try_wide<MT, NT, 4, 1, true>(a, s); }
-
-// the 4-wave tiles launch_variant() hands out to fp16 layers (kernels_conv.hip)
-template bool conv_try_wide<4, 4, 2, 2>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<2, 2, 2, 2>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<2, 5, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<4, 4, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<2, 4, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<2, 3, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<4, 2, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<4, 1, 4, 1>(const ConvArgs&, hipStream_t);
-template bool conv_try_wide<2, 9, 4, 1>(const ConvArgs&, hipStream_t);      // the merged first convs of a detect level (144 channels)
-template bool conv_try_wide_tail<2, 4>(const ConvArgs&, hipStream_t);       // 128 px x 64 ch + 1x1 tail
-template bool conv_try_wide_tail<2, 5>(const ConvArgs&, hipStream_t);       // 128 px x 80 ch + 1x1 tail
 
 }  // namespace aic

@@ -309,12 +309,7 @@ void launch_select_sort_nms(const DetArgs& a, hipStream_t s) {
     while (P < a.n_anchors) P <<= 1;
     const size_t lds = (size_t)P * 8 + (size_t)a.max_det * (16 + 4) + NMS_THREADS * 4 + 16;
     AIC_REQUIRE(lds <= 160 * 1024 - 64, AIC_ERR_CAPACITY, "too many anchors / max_det for the NMS LDS budget");
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(select_sort_nms_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-        attr_set = true;
-    }
+    set_lds_limit(select_sort_nms_kernel, 160 * 1024 - 64);
     static const int dbg = [] { const char* e = getenv("AICAM_NMS_DBG"); return e ? atoi(e) : 0; }();
     hipLaunchKernelGGL(select_sort_nms_kernel, dim3(a.batch), dim3(NMS_THREADS), lds, s, a, P, dbg);
     KCHECK();

@@ -1315,12 +1315,8 @@ void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const floa
 }
 
 static void epoch_attr() {
-    static bool done = false;
-    if (!done) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trk_epoch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, epoch_lds_bytes()));
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trk_cascade_test_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, epoch_lds_bytes()));
-        done = true;
-    }
+    set_lds_limit(trk_epoch_kernel, epoch_lds_bytes());
+    set_lds_limit(trk_cascade_test_kernel, epoch_lds_bytes());
 }
 
 // AICAM_TRK_PHASES=1: per-phase shader-clock totals of the epoch kernel, printed at process exit

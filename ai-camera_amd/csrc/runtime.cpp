@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include <cstdlib>
+#include <set>
 
 namespace aic {
 
@@ -119,6 +120,17 @@ void Device::prof_reset() {
     for (int c = 0; c < AIC_PROF_CLASSES; ++c) ms[c] = 0, ms_union[c] = 0, launches[c] = 0, flops[c] = 0, bytes[c] = 0;
     if (!prof_ref && hipEventCreate(&prof_ref) != hipSuccess) prof_ref = nullptr;
     if (prof_ref) { (void)hipEventRecord(prof_ref, s_main); (void)hipEventSynchronize(prof_ref); }
+}
+
+void set_lds_limit(const void* kfn, size_t bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count({kfn, dev})) return;
+    HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done.insert({kfn, dev});
 }
 
 }  // namespace aic
