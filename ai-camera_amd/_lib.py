@@ -42,6 +42,12 @@ class ByteTrackParams(C.Structure):
                 ("fuse_score", C.c_int32), ("max_tracks", C.c_int32), ("first_track_id", C.c_int32)]
 
 
+class OCSortParams(C.Structure):
+    _fields_ = [("det_thresh", C.c_double), ("iou_threshold", C.c_double), ("inertia", C.c_double), ("max_age", C.c_int32),
+                ("min_hits", C.c_int32), ("delta_t", C.c_int32), ("use_byte", C.c_int32), ("max_tracks", C.c_int32),
+                ("first_track_id", C.c_int32)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -141,6 +147,13 @@ _SIGS = {
     "aic_bytetrack_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aic_bytetrack_counters": (_I, [_P, _P, _P, _P]),
     "aic_pipeline_create_bytetrack": (_I, [_P, _P, _P, _P]),
+    "aic_ocsort_create": (_I, [_I, _P, _P]),
+    "aic_ocsort_destroy": (_I, [_P]),
+    "aic_ocsort_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_ocsort_update_batch": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "aic_ocsort_export": (_I, [_P, _I] + [_P] * 14),
+    "aic_ocsort_counters": (_I, [_P] * 8),
+    "aic_pipeline_create_ocsort": (_I, [_P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

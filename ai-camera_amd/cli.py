@@ -48,9 +48,9 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--yolo_engine", type=str, default=str(config.YOLO_ENGINE_PATH))
     p.add_argument("--reid_engine", type=str, default=str(config.REID_ENGINE_PATH))
     p.add_argument("--conf_thresh", type=float, default=None,
-                   help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1)")
-    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack"),
-                   help="bytetrack: no ReID model, ByteTrack's association on the device")
+                   help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1, with ocsort its det_thresh 0.6)")
+    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort"),
+                   help="bytetrack / ocsort: no ReID model, the tracker's association on the device")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
@@ -146,7 +146,7 @@ class FrameWriter:
 
 
 class _FrameFree:
-    """The loop's tracker call with ByteTrack: update(boxes, scores, class_ids, frame) -- the frame is not needed (no ReID)."""
+    """The loop's tracker call with ByteTrack / OC-SORT: update(boxes, scores, class_ids, frame) -- the frame is not needed (no ReID)."""
 
     def __init__(self, tracker):
         self.tracker = tracker
@@ -163,8 +163,9 @@ def main(argv=None):
     print("Initializing YOLOv8 Detector...")
     name, frames, size = frame_source(args.input, args.webcam_id, cv2)
     bytetrack = args.tracker == "bytetrack"
-    if args.conf_thresh is None:             # ByteTrack's bands need the detector's low band (low_thresh = 0.1)
-        args.conf_thresh = 0.1 if bytetrack else config.YOLO_CONF_THRESHOLD
+    ocsort = args.tracker == "ocsort"
+    if args.conf_thresh is None:             # ByteTrack's bands need the detector's low band (low_thresh = 0.1); OC-SORT takes s > det_thresh
+        args.conf_thresh = 0.1 if bytetrack else 0.6 if ocsort else config.YOLO_CONF_THRESHOLD
     pipe = detector = tracker = None
     try:
         if args.batch > 1:
@@ -173,7 +174,7 @@ def main(argv=None):
             # clipped (the per-frame path and the reference, deepsort_tracker.py:126-141, emit every confirmed track)
             from .hip_engine import HipEngine
             dev_id = config.resolve_device(args.device)
-            reid = None if bytetrack else HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
+            reid = None if bytetrack or ocsort else HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
             pipe = TrackingPipeline(args.yolo_engine, reid, (size[1], size[0]), batch=args.batch, ring_frames=args.batch,
                                     max_persons=512, max_tracks=512, device=dev_id, dtype=args.dtype, conf_thresh=args.conf_thresh,
                                     tracker=args.tracker)
@@ -189,6 +190,14 @@ def main(argv=None):
             tracker = _FrameFree(BYTETracker(device=args.device))
         except Exception as e:
             print(f"Error initializing ByteTrack Tracker: {e}")
+            return 1
+    elif pipe is None and ocsort:
+        print("Initializing OC-SORT Tracker...")
+        try:
+            from .ocsort import OCSort
+            tracker = _FrameFree(OCSort(device=args.device))
+        except Exception as e:
+            print(f"Error initializing OC-SORT Tracker: {e}")
             return 1
     elif pipe is None:
         print("Initializing DeepSORT Tracker...")
@@ -241,7 +250,7 @@ def main(argv=None):
             frame_idx += 1
             display_fps = frame_idx / total if total > 0 else 0.0
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
-                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
+                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
                 if args.show_display and cv2 is not None:
                     cv2.imshow("AICamera Tracking", vis)
                     if cv2.waitKey(1) & 0xFF == ord("q"):

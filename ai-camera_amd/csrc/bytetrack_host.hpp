@@ -3,12 +3,13 @@
 #pragma once
 #include "bytetrack.hpp"
 #include "common.hpp"
+#include "epoch_tracker.hpp"
 
 namespace aic {
 
 BtParams bytetrack_params(const aic_bytetrack_params& p, int* first_id);
 
-struct ByteTracker {
+struct ByteTracker : EpochTracker {
     Device* dev;
     BtParams prm;
     DevBuf<char> d_tbl;
@@ -18,13 +19,12 @@ struct ByteTracker {
     DevBuf<char> d_api;
     int epoch_frames = 0;           // frames per epoch launch (0 = TRK_KMAX)
     bool lsap_fast = true;          // unique optima read off the costs (false: every problem through the LSAP)
-    bool failed = false;            // a capacity error stops the tracker: its table is no longer a frame boundary
-    std::string fail_msg;
 
     ByteTracker(Device& d, const BtParams& p, int first_id);
     // frames [0, frames) of `dets` as epochs on stream s; the header copy lands in h_hdr behind them (check_epochs() after the caller's sync)
-    void run_epochs(const EpochDets& dets, int frames, const EpochOut& out, hipStream_t s);
-    void check_epochs();
+    const char* name() const override { return "ByteTrack"; }
+    void run_epochs(const EpochDets& dets, int frames, const EpochOut& out, hipStream_t s) override;
+    void check_epochs() override;
     void update_batch(int k, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, int cap_rows,
                       int32_t* n_out, int32_t* out6, float* out_conf);
     void counters(int64_t* n_fast, int64_t* n_lsap, int32_t* max_side);

@@ -1,0 +1,22 @@
+// epoch_tracker.hpp -- a detector-only tracker of one video stream as the pipeline's stage B sees it (pipeline.cpp): the group's frames go
+// through its epoch launches on the tracker stream, the error check follows the caller's sync.  ByteTracker (bytetrack_host.hpp) and
+// OcSortTracker (ocsort_host.hpp) are the two.
+#pragma once
+#include <string>
+
+#include "common.hpp"
+#include "trk_dev.hpp"
+
+namespace aic {
+
+struct EpochTracker {
+    bool failed = false;            // a capacity error stops the tracker: its table is no longer a frame boundary
+    std::string fail_msg;
+    virtual ~EpochTracker() = default;
+    virtual const char* name() const = 0;
+    // frames [0, frames) of `dets` as epochs on stream s; the header copy lands behind them (check_epochs() after the caller's sync)
+    virtual void run_epochs(const EpochDets& dets, int frames, const EpochOut& out, hipStream_t s) = 0;
+    virtual void check_epochs() = 0;
+};
+
+}  // namespace aic

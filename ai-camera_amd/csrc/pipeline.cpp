@@ -15,6 +15,7 @@
 #include "engine.hpp"
 #include "tracker.hpp"
 #include "bytetrack_host.hpp"
+#include "ocsort_host.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -182,9 +183,11 @@ struct Pipeline {
     int plan_slot = 0, copies_issued = 0;
     int host_slot0 = 0;
 
-    // ByteTrack (aic_pipeline_create_bytetrack): no ReID model (reid == nullptr); crop, ReID and the embedding copies are not issued and
-    // the association is the ByteTrack epoch kernel on the tracker stream.  The DeepSORT tracker object below then exists but is never run.
-    std::unique_ptr<ByteTracker> bt;
+    // A detector-only tracker (aic_pipeline_create_bytetrack / _ocsort): no ReID model (reid == nullptr); crop, ReID and the embedding copies
+    // are not issued and the association is the tracker's epoch kernel on the tracker stream (epoch_tracker.hpp).  The DeepSORT tracker
+    // object below then exists but is never run.
+    std::unique_ptr<EpochTracker> bt;
+    std::string bt_name() const { return bt->name(); }
 
     static aic_tracker_params tracker_params(const aic_pipeline_params& p, bool bytetrack) {
         if (!bytetrack) return p.tracker;
@@ -194,10 +197,12 @@ struct Pipeline {
         return t;
     }
 
-    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1)
-        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp != nullptr))), trk(trk_handle->t) {
-        AIC_REQUIRE(y->kind == KIND_YOLO && (btp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
-                    btp ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine" : "pipeline needs a YOLO and a ReID engine");
+    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr)
+        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp))), trk(trk_handle->t) {
+        AIC_REQUIRE(y->kind == KIND_YOLO && (btp || ocp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
+                    btp   ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
+                    : ocp ? "an OC-SORT pipeline takes a YOLO engine and no ReID engine"
+                          : "pipeline needs a YOLO and a ReID engine");
         AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
@@ -205,6 +210,7 @@ struct Pipeline {
         AIC_REQUIRE(p.max_det > 0 && p.max_det <= y->max_det_cap, AIC_ERR_CAPACITY, "max_det out of range");
         dev->use();
         if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
+        else if (ocp) bt.reset(new OcSortTracker(*dev, *ocp, bt_first_id));
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
@@ -253,7 +259,7 @@ struct Pipeline {
         fd.n = 0;
         fd.tlwh.clear(), fd.xyxy.clear(), fd.conf.clear(), fd.cls.clear();
         for (int i = 0; i < n; ++i) {
-            if ((!bt && !(conf[i] >= prm.min_confidence)) || !tracked_class(cls[i])) continue;   // ByteTrack: its bands filter the scores
+            if ((!bt && !(conf[i] >= prm.min_confidence)) || !tracked_class(cls[i])) continue;   // detector-only trackers: their bands filter the scores
             const float* b = boxes_xyxy + (size_t)i * 4;
             fd.tlwh.insert(fd.tlwh.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});   // deepsort_tracker.py:185-186
             fd.xyxy.insert(fd.xyxy.end(), b, b + 4);                                    // crops use the xyxy box (:148)
@@ -295,7 +301,7 @@ struct Pipeline {
         dev->use();
         const int yi = std::min(yolo->max_items, std::max(dual_max, 1));
         yolo2.reset(new Model(*dev, yolo->blob_copy->data(), yolo->blob_copy->size(), yolo->dtype, yi));
-        if (reid) {                                               // (ByteTrack: no ReID model, no second copy of it)
+        if (reid) {                                               // (detector-only: no ReID model, no second copy of it)
             const int ri = std::min(reid->max_items, std::max(yi * prm.max_persons, 64));
             reid2.reset(new Model(*dev, reid->blob_copy->data(), reid->blob_copy->size(), reid->dtype, ri));
         }
@@ -384,7 +390,7 @@ struct Pipeline {
         }
         int n_max = 0;
         for (int f = 0; f < frames; ++f) n_max = std::max(n_max, c.dets[f].n);
-        const bool dev_mode = bt || use_device(n_max, c.tracks_after);   // ByteTrack: always the epoch kernel's detection arrays
+        const bool dev_mode = bt || use_device(n_max, c.tracks_after);   // detector-only: always the epoch kernel's detection arrays
         c.dev_mode = dev_mode;
         if (dev_mode) {   // what the epoch kernels read: frame_n[frames] | frame_d0[frames] | tlwh[nc,4] | conf[nc] | cls[nc]
             c.m_n = 0, c.m_d0 = (size_t)frames * 4, c.m_tlwh = (((size_t)frames * 8 + 15) / 16) * 16;
@@ -408,7 +414,7 @@ struct Pipeline {
         // crop + ReID on their own stream: in inject mode they do not depend on the detector, and their CU-filling
         // launches backfill the CUs that YOLO's thin layers (50-400 blocks per launch) leave idle
         hipStream_t sr = split_streams && reid ? c.ln->s_reid : s;
-        if (nc && reid) {                                          // (ByteTrack: no crops, no ReID, no embeddings)
+        if (nc && reid) {                                          // (detector-only: no crops, no ReID, no embeddings)
             HIP_CHECK(hipMemcpyAsync(c.d_boxes.p, c.h_boxes.p, (size_t)nc * 16, hipMemcpyHostToDevice, sr));
             HIP_CHECK(hipMemcpyAsync(c.d_frame_of.p, c.h_frame_of.p, (size_t)nc * 4, hipMemcpyHostToDevice, sr));
             // the engine's host-side launch state (in_pix4, crop_src, n_items_dev) is shared with the consumer thread, which may be running
@@ -712,9 +718,9 @@ struct Pipeline {
         n_frames_done += c.frames;
     }
 
-    // Stage B of a ByteTrack pipeline: the group's frames through the ByteTrack epochs on the tracker stream (no embeddings, no read-back
-    // of them); the host picks up the group's output rows at the end.
-    void stage_b_bytetrack(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
+    // Stage B of a detector-only pipeline: the group's frames through the tracker's epochs on the tracker stream (no embeddings, no
+    // read-back of them); the host picks up the group's output rows at the end.
+    void stage_b_epochs(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
                            float* det_boxes, float* det_scores, int32_t* det_labels) {
         const double t0 = now();
         n_assoc_dev += c.frames;
@@ -726,7 +732,7 @@ struct Pipeline {
         HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's detection arrays are in HBM
         const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
         for (int f = 0; f < c.frames; ++f)
-            AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "ByteTrack: more than 512 detections in one frame");
+            AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, bt_name() + ": more than 512 detections in one frame");
         EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
                        reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
                        reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), nullptr, nullptr, nullptr};
@@ -864,7 +870,7 @@ struct Pipeline {
                 final_group = k == nchunks - 1;
                 if (ck[k % nck].filt_dev) prepare_b(ck[k % nck]);
                 ck[k % nck].prev_dev_mode = ck[k % nck].dev_mode;
-                if (bt) stage_b_bytetrack(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
+                if (bt) stage_b_epochs(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
                 else if (ck[k % nck].dev_mode) {
                     trk.dev_assoc = true;
                     stage_b_device(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
@@ -899,7 +905,8 @@ using namespace aic;
 
 struct aic_pipeline {
     Pipeline p;
-    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1) : p(y, r, q, b, first_id) {}
+    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr)
+        : p(y, r, q, b, first_id, o) {}
 };
 
 extern "C" {
@@ -917,6 +924,15 @@ int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p,
         int first = 1;
         const BtParams b = bytetrack_params(*bp, &first);
         *out = new aic_pipeline(&yolo->m, nullptr, *p, &b, first);
+    });
+}
+
+int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, const aic_ocsort_params* op, aic_pipeline** out) {
+    return guarded([&] {
+        AIC_REQUIRE(yolo && p && op && out, AIC_ERR_INVALID, "NULL argument");
+        int first = 1;
+        const OcParams o = ocsort_params(*op, &first);
+        *out = new aic_pipeline(&yolo->m, nullptr, *p, nullptr, first, &o);
     });
 }
 
@@ -1023,7 +1039,7 @@ int aic_host_unregister(void* ptr) {
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out) {
     return guarded([&] {
         AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline has no DeepSORT tracker");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline has no DeepSORT tracker");
         *out = p->p.trk_handle.get();   // owned by the pipeline: do not destroy
     });
 }
@@ -1042,7 +1058,7 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
 int aic_pipeline_exchange_enable(aic_pipeline* p, float* shard0_dev, float* shard1_dev, int t_max, int every_groups) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "the gallery exchange needs DeepSORT's appearance galleries (this pipeline runs ByteTrack)");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "the gallery exchange needs DeepSORT's appearance galleries (this pipeline runs " + p->p.bt_name() + ")");
         Pipeline& q = p->p;
         q.dev->use();
         std::lock_guard<std::mutex> lk(q.x_mu);
@@ -1134,7 +1150,7 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
         }
         else if (k == "split_streams") p->p.split_streams = value != 0;
         else if (p->p.bt && (k == "device_assoc" || k == "device_assoc_limit" || k == "device_filter"))
-            AIC_REQUIRE(false, AIC_ERR_INVALID, "option " + k + " applies to DeepSORT pipelines only (this one runs ByteTrack)");
+            AIC_REQUIRE(false, AIC_ERR_INVALID, "option " + k + " applies to DeepSORT pipelines only (this one runs " + p->p.bt_name() + ")");
         else if (k == "device_assoc") {
             AIC_REQUIRE(value >= 0 && value <= 2, AIC_ERR_INVALID, "device_assoc: 0 host, 1 auto, 2 always on the device");
             p->p.dev_assoc = value;
@@ -1203,7 +1219,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
                                   int32_t* n_rows, int32_t* n_frames, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n_rows && n_frames && dim, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline computes no embeddings");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
         Pipeline& q = p->p;
         *dim = q.dim, *n_rows = 0, *n_frames = 0;
         if (q.last_chunk < 0) return;
@@ -1224,7 +1240,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
 int aic_pipeline_last_embeddings(aic_pipeline* p, float* emb, int cap_rows, int32_t* n, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n && dim, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a ByteTrack pipeline computes no embeddings");
+        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
         *n = p->p.last_emb_n, *dim = p->p.dim;
         AIC_REQUIRE(p->p.last_emb_n <= cap_rows, AIC_ERR_CAPACITY, "embedding capacity too small");
         if (emb) std::copy(p->p.last_emb.begin(), p->p.last_emb.end(), emb);

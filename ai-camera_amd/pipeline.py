@@ -22,9 +22,12 @@ class TrackingPipeline:
                  n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", **bytetrack_params):
         """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
         not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
-        conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band."""
-        if tracker not in ("deepsort", "bytetrack"):
-            raise ValueError(f"tracker must be 'deepsort' or 'bytetrack', not {tracker!r}")
+        conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
+        tracker="ocsort": the same pipeline with OC-SORT (aic_pipeline_create_ocsort); the extra arguments are OCSort's (det_thresh,
+        min_hits, iou_threshold, delta_t, inertia, use_byte; max_age is the named argument), and conf_thresh defaults to det_thresh,
+        or to 0.1 with use_byte."""
+        if tracker not in ("deepsort", "bytetrack", "ocsort"):
+            raise ValueError(f"tracker must be 'deepsort', 'bytetrack' or 'ocsort', not {tracker!r}")
         if tracker == "deepsort" and bytetrack_params:
             raise TypeError(f"unexpected arguments for a DeepSORT pipeline: {sorted(bytetrack_params)}")
         self.tracker_kind = tracker
@@ -48,6 +51,22 @@ class TrackingPipeline:
             self._h = C.c_void_p()
             L.call("aic_pipeline_create_bytetrack", self.yolo._h, C.byref(self.params), C.byref(self.bytetrack_params),
                    C.byref(self._h))
+            self.tracker_core = None
+            return
+        if tracker == "ocsort":
+            from .ocsort import ocsort_params as _ocp
+            self.reid = None
+            # max_age is a named argument here: left at the DeepSORT default it means OC-SORT's own default (30)
+            oc_age = 30 if max_age == config.DEEPSORT_MAX_AGE else max_age
+            self.ocsort_params = _ocp(max_tracks=max_tracks, max_age=oc_age, **bytetrack_params)
+            if conf_thresh is None:
+                conf_thresh = 0.1 if self.ocsort_params.use_byte else self.ocsort_params.det_thresh
+            tp = L.TrackerParams(0.2, 0.7, 1, 1, 1, 1, 0, 1)          # ignored by aic_pipeline_create_ocsort
+            self.params = L.PipelineParams(self.frame_h, self.frame_w, self.batch, self.ring_frames, self.max_persons,
+                                           float(conf_thresh), float(iou_thresh), self.max_det, 0.0,
+                                           int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
+            self._h = C.c_void_p()
+            L.call("aic_pipeline_create_ocsort", self.yolo._h, C.byref(self.params), C.byref(self.ocsort_params), C.byref(self._h))
             self.tracker_core = None
             return
         if conf_thresh is None:

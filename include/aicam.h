@@ -52,6 +52,7 @@ typedef struct aic_model aic_model;       /* one engine file resident on one GPU
 typedef struct aic_tracker aic_tracker;   /* DeepSORT core state of one video stream      */
 typedef struct aic_pipeline aic_pipeline; /* detector + ReID + tracker over resident frames */
 typedef struct aic_bytetrack aic_bytetrack; /* ByteTrack state of one video stream          */
+typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream            */
 
 /* ------------------------------------------------------------------ library / device */
 const char* aic_last_error(void);
@@ -292,6 +293,46 @@ int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* 
                          int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* n_tracks,
                          int32_t* n_tracked);
 
+/* ------------------------------------------------------------------ OC-SORT
+ * OCSort.update() of the OC-SORT authors (ocsort.py, association.py, kalmanfilter.py) on the device, k frames per launch
+ * (csrc/kernels_ocsort.hip; specification: tests/ocsort_oracle.py, deviations: DESIGN.md "OC-SORT").  No appearance model: SORT's 7-state
+ * filter on [x, y, s, r], the velocity-direction term (OCM), the last-observation stage (OCR) and the virtual-trajectory replay (ORU).
+ * Defaults are upstream's; every threshold is rounded to fp32 once. */
+typedef struct aic_ocsort_params {
+    double det_thresh;      /* 0.6: a detection takes part with s > det_thresh                            */
+    double iou_threshold;   /* 0.3: a pair needs IoU >= this                                               */
+    double inertia;         /* 0.2: weight of the velocity-direction term (OCM); 0 switches it off          */
+    int32_t max_age;        /* 30: a track is removed at time_since_update > max_age                       */
+    int32_t min_hits;       /* 3: output needs hit_streak >= min_hits (or frame <= min_hits)               */
+    int32_t delta_t;        /* 3 (1..8): the observation the velocity direction is taken from               */
+    int32_t use_byte;       /* 0; 1: a BYTE stage on the band 0.1 < s < det_thresh                          */
+    int32_t max_tracks;     /* live tracks (0 -> 512, at most 512)                                         */
+    int32_t first_track_id; /* 1: ids are counted per tracker                                              */
+} aic_ocsort_params;
+
+/* AIC_ERR_INVALID for a threshold outside (0, 1], inertia outside [0, 1], delta_t outside 1..8, max_tracks over 512, use_byte with
+ * det_thresh <= 0.1, ... (checked before the device). */
+int aic_ocsort_create(int device, const aic_ocsort_params* p, aic_ocsort** out);
+int aic_ocsort_destroy(aic_ocsort* t);
+/* "lsap_fast" = 0: stage 1 never takes upstream's read-off, every problem goes through the wave LSAP (default 1; the two are specified
+ * separately, tests/ocsort_oracle.py change 10); "epoch_frames" = 1..16: frames per epoch launch (0 = default 16), same results. */
+int aic_ocsort_option(aic_ocsort* t, const char* key, int value);
+/* k consecutive frames, each one OCSort.update(): arrays and outputs as aic_bytetrack_update_batch; the rows are the tracks' last
+ * observations, in upstream's order (the track list reversed).  AIC_ERR_CAPACITY when a frame has more than 512 detections or the live
+ * tracks outgrow max_tracks; nothing is dropped, and the tracker refuses further updates after such an error. */
+int aic_ocsort_update_batch(aic_ocsort* t, int k, const int32_t* counts, const float* boxes_xyxy, const float* conf,
+                            const int32_t* cls, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf);
+/* Live tracks in list order: counters of KalmanBoxTracker, frozen = the filter is frozen (the next observation replays the virtual
+ * trajectory), has_obs, score, last_observation[n,4] (xyxy, -1 before the first), velocity[n,2] (dy, dx), mean[n,7], cov[n,7,7].  Only the
+ * first `cap` are stored; any pointer may be NULL.  After an update failed the tracker has no consistent state: AIC_ERR_INVALID. */
+int aic_ocsort_export(aic_ocsort* t, int cap, int32_t* track_id, int32_t* age, int32_t* hits, int32_t* hit_streak,
+                      int32_t* time_since_update, int32_t* cls, int32_t* frozen, int32_t* has_obs, float* score,
+                      float* last_observation, float* velocity, float* mean, float* cov, int32_t* n_tracks);
+/* Since creation: stage-1 problems settled by the read-off / problems solved by the wave LSAP, the largest side the LSAP met, ORU replays
+ * and their longest gap, pairs made by the OCR stage and by the BYTE stage. */
+int aic_ocsort_counters(aic_ocsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_oru, int32_t* max_gap,
+                        int64_t* n_ocr, int64_t* n_byte);
+
 /* ------------------------------------------------------------------ end-to-end pipeline
  * The loop body of src/aicamera_tracker.py:169-207 (detect + track, the reference's own FPS
  * span) over frames that are already resident in HBM, batched: detection and ReID of
@@ -322,6 +363,10 @@ int aic_pipeline_create(aic_model* yolo, aic_model* reid, const aic_pipeline_par
  * "device_assoc", "device_assoc_limit", "device_filter" fail with AIC_ERR_INVALID on such a pipeline. */
 int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p, const aic_bytetrack_params* bp,
                                   aic_pipeline** out);
+/* The same detector-only pipeline with OC-SORT as its tracker.  Rejections as on a ByteTrack pipeline; conf_thresh should be at most
+ * det_thresh (0.1 with use_byte). */
+int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, const aic_ocsort_params* op,
+                               aic_pipeline** out);
 int aic_pipeline_destroy(aic_pipeline* p);
 /* Copy `count` u8 BGR frames into ring slots [slot, slot+count). */
 int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames_bgr, int count);

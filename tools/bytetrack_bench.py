@@ -1,9 +1,9 @@
-"""ByteTrack pipeline on the bench's headline workload, next to DeepSORT in the same process.
+"""ByteTrack and OC-SORT pipelines on the bench's headline workload, next to DeepSORT in the same process.
 
 1280x720, 30 planted persons (inject = 1), YOLOv8n on the trained weights, fp16, 512-frame launch groups (bench.py's clip: 256
-frames forward then backward).  Prints ONE JSON line: frames/s of the ByteTrack pipeline from HBM-resident frames and from host
-memory, the tracker stream's time per launch group and per 16-frame epoch (HIP events on the tracker kernels), the DeepSORT
-pipeline's frames/s measured the same way, and MOTA / IDF1 of both trackers against the planted identities on one scene whose scores
+frames forward then backward).  Prints ONE JSON line: frames/s of the ByteTrack and the OC-SORT pipeline (both detector-only) from
+HBM-resident frames and from host memory, the tracker stream's time per launch group and per 16-frame epoch (HIP events on the tracker kernels), the DeepSORT
+pipeline's frames/s measured the same way, and MOTA / IDF1 / ID switches of the three trackers against the planted identities on one scene whose scores
 are widened to (0.05, 0.95) so that ByteTrack's low band is used.  Reports numbers; gates on nothing.
 
     python tools/bytetrack_bench.py [--steps 2] [--warmup 1]
@@ -74,6 +74,9 @@ def main():
     bt = TP(ypath, None, (H, W), batch=512, ring_frames=2 * R, max_persons=32, device=dev, dtype="fp16", inject=True, tracker="bytetrack")
     res_bt = rates(bt)
     bt.close()
+    oc = TP(ypath, None, (H, W), batch=512, ring_frames=2 * R, max_persons=32, device=dev, dtype="fp16", inject=True, tracker="ocsort")
+    res_oc = rates(oc)
+    oc.close()
     ds = TP(ypath, rpath, (H, W), batch=512, ring_frames=2 * R, max_persons=32, device=dev, dtype="fp16", inject=True)
     ds.option("split_streams", 1)                                      # as bench.py's headline
     res_ds = rates(ds)
@@ -86,9 +89,11 @@ def main():
     frames = ms.render_batch(0, n)
     gt = mm.scene_ground_truth(ms, n)
     metrics = {}
-    for name in ("bytetrack", "deepsort"):
-        kw = dict(tracker="bytetrack") if name == "bytetrack" else {}
-        p = TP(ypath, None if name == "bytetrack" else rpath, (H, W), batch=32, ring_frames=n, max_persons=64, device=dev,
+    # ocsort: upstream's defaults (only scores above det_thresh = 0.6 take part, which on this scene is 2 detections in 5);
+    # ocsort_byte: use_byte = 1, the band 0.1 < s < 0.6 keeps tracks alive as it does for ByteTrack
+    for name in ("bytetrack", "ocsort", "ocsort_byte", "deepsort"):
+        kw = dict(tracker=name.split("_")[0], **(dict(use_byte=True) if name == "ocsort_byte" else {})) if name != "deepsort" else {}
+        p = TP(ypath, None if name != "deepsort" else rpath, (H, W), batch=32, ring_frames=n, max_persons=64, device=dev,
                dtype="fp16", inject=True, **kw)
         p.upload(0, frames)
         p.inject(0, [ms.detections(f)[:3] for f in range(n)])
@@ -97,7 +102,7 @@ def main():
         metrics[name] = dict(mota=round(m["mota"], 4), idf1=round(m["idf1"], 4), idsw=m["idsw"])
         p.close()
     print(json.dumps(dict(workload="1280x720, 30 planted persons, YOLOv8n (trained) fp16, 512-frame groups, inject=1",
-                          bytetrack=res_bt, deepsort=res_ds, metrics=metrics, steps=args.steps)))
+                          bytetrack=res_bt, ocsort=res_oc, deepsort=res_ds, metrics=metrics, steps=args.steps)))
 
 
 if __name__ == "__main__":
