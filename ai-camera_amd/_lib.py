@@ -48,6 +48,13 @@ class OCSortParams(C.Structure):
                 ("first_track_id", C.c_int32)]
 
 
+class BoTSORTParams(C.Structure):
+    _fields_ = [("track_high_thresh", C.c_double), ("track_low_thresh", C.c_double), ("new_track_thresh", C.c_double),
+                ("match_thresh", C.c_double), ("proximity_thresh", C.c_double), ("appearance_thresh", C.c_double),
+                ("feat_alpha", C.c_double), ("track_buffer", C.c_int32), ("frame_rate", C.c_int32), ("fuse_score", C.c_int32),
+                ("with_reid", C.c_int32), ("feature_dim", C.c_int32), ("max_tracks", C.c_int32), ("first_track_id", C.c_int32)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -154,6 +161,13 @@ _SIGS = {
     "aic_ocsort_export": (_I, [_P, _I] + [_P] * 14),
     "aic_ocsort_counters": (_I, [_P] * 8),
     "aic_pipeline_create_ocsort": (_I, [_P, _P, _P, _P]),
+    "aic_botsort_create": (_I, [_I, _P, _P]),
+    "aic_botsort_destroy": (_I, [_P]),
+    "aic_botsort_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_botsort_update_batch": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "aic_botsort_export": (_I, [_P, _I] + [_P] * 13),
+    "aic_botsort_counters": (_I, [_P] * 7),
+    "aic_pipeline_create_botsort": (_I, [_P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -48,9 +48,9 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--yolo_engine", type=str, default=str(config.YOLO_ENGINE_PATH))
     p.add_argument("--reid_engine", type=str, default=str(config.REID_ENGINE_PATH))
     p.add_argument("--conf_thresh", type=float, default=None,
-                   help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1, with ocsort its det_thresh 0.6)")
-    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort"),
-                   help="bytetrack / ocsort: no ReID model, the tracker's association on the device")
+                   help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1, with ocsort its det_thresh 0.6, with botsort its track_low_thresh 0.1)")
+    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort", "botsort"),
+                   help="bytetrack / ocsort: no ReID model, the tracker's association on the device; botsort: IoU + ReID fusion on the device")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
@@ -155,6 +155,31 @@ class _FrameFree:
         return self.tracker.update(boxes, scores, class_ids)
 
 
+class _BotSortFrame:
+    """The loop's tracker call with BoT-SORT: the boxes of tracked classes above the low band are embedded from the frame (ReIDModel, as
+    DeepSORT.update does) and handed to BoTSORT with their validity."""
+
+    def __init__(self, reid_engine, device, dtype):
+        from .botsort import BoTSORT
+        from .reid_model import ReIDModel
+        self.reid_model = ReIDModel(engine_path=reid_engine, input_shape=config.REID_INPUT_SHAPE, device=device, dtype=dtype)
+        self.tracker = BoTSORT(device=device, feature_dim=self.reid_model.feature_dim)
+        self.low = np.float32(self.tracker.params.track_low_thresh)
+
+    def update(self, boxes, scores, class_ids, frame):
+        b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+        s = np.asarray(scores, dtype=np.float32).reshape(-1)
+        k = np.asarray(class_ids).reshape(-1).astype(np.int64)
+        names = np.array([config.class_name(int(c)) in config.CLASSES_TO_TRACK for c in k], dtype=bool)
+        keep = np.nonzero((s > self.low) & names)[0]
+        if not len(keep):
+            return self.tracker.update(np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+        feats, valid = self.reid_model.embed_boxes(frame, b[keep])
+        rows, conf = self.tracker.update_batch_arrays([(b[keep], s[keep], k[keep].astype(np.int32), feats, None,
+                                                        np.asarray(valid).astype(np.int32))])[0]
+        return self.tracker._tuples(rows, conf)
+
+
 def main(argv=None):
     args = parse_arguments(argv)
     cv2 = probe_cv2()
@@ -164,8 +189,9 @@ def main(argv=None):
     name, frames, size = frame_source(args.input, args.webcam_id, cv2)
     bytetrack = args.tracker == "bytetrack"
     ocsort = args.tracker == "ocsort"
+    botsort = args.tracker == "botsort"
     if args.conf_thresh is None:             # ByteTrack's bands need the detector's low band (low_thresh = 0.1); OC-SORT takes s > det_thresh
-        args.conf_thresh = 0.1 if bytetrack else 0.6 if ocsort else config.YOLO_CONF_THRESHOLD
+        args.conf_thresh = 0.1 if bytetrack or botsort else 0.6 if ocsort else config.YOLO_CONF_THRESHOLD
     pipe = detector = tracker = None
     try:
         if args.batch > 1:
@@ -190,6 +216,13 @@ def main(argv=None):
             tracker = _FrameFree(BYTETracker(device=args.device))
         except Exception as e:
             print(f"Error initializing ByteTrack Tracker: {e}")
+            return 1
+    elif pipe is None and botsort:
+        print("Initializing BoT-SORT Tracker...")
+        try:
+            tracker = _BotSortFrame(args.reid_engine, args.device, args.dtype)
+        except Exception as e:
+            print(f"Error initializing BoT-SORT Tracker: {e}")
             return 1
     elif pipe is None and ocsort:
         print("Initializing OC-SORT Tracker...")
@@ -250,7 +283,7 @@ def main(argv=None):
             frame_idx += 1
             display_fps = frame_idx / total if total > 0 else 0.0
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
-                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
+                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
                 if args.show_display and cv2 is not None:
                     cv2.imshow("AICamera Tracking", vis)
                     if cv2.waitKey(1) & 0xFF == ord("q"):

@@ -1,0 +1,69 @@
+// botsort.hpp -- BoT-SORT with ReID on the device (BoTSORT.update of tracker/bot_sort.py, restated in tests/botsort_oracle.py): the
+// structures shared by kernels_botsort.hip (the one-block epoch kernel) and botsort.cpp (tracker object, pipeline hook).
+//
+// The track table lives in HBM between launches, indexed by SLOT:
+//   BsHdr | BtTrack[cap] | tracked list[cap] | lost list[cap] | mean[cap][8] | cov[cap][64] | has_feat[cap]     and   smooth[cap][dim]
+// An epoch launch (ONE block of 512 threads) loads the scalars, the lists and the means into LDS, walks k <= TRK_KMAX frames with no host
+// round trip (covariances and smoothed features stay in HBM) and writes them back.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "bytetrack.hpp"
+
+namespace aic {
+
+struct BsHdr {
+    int32_t n_tracked, n_lost, next_id, frame_id;
+    int32_t err;                    // 0 ok; 1 track slots exhausted; 3 an assignment problem beyond the LSAPs (extended side > 512)
+    int32_t err_frame;
+    int32_t max_side;               // largest extended side since creation
+    int32_t pad;
+    int64_t n_fast, n_lsap;         // assignment problems settled by the unique-optimum check / by the LSAP, since creation
+    int64_t n_app;                  // matched pairs (stages 1 and 3) whose winning term was the appearance distance (d_emb < d_iou)
+    int64_t cyc_cost, cyc_all;      // shader-clock cycles since creation: the appearance pass of the fused cost (dot products) / the whole kernel
+};
+constexpr size_t BS_HDR_BYTES = 128;
+static_assert(sizeof(BsHdr) <= BS_HDR_BYTES, "header area");
+
+struct BsParams {                   // every threshold rounded to fp32 once
+    float high, low, new_thresh, match_thresh, second_thresh, unconf_thresh, dup_dist, proximity, appearance, alpha, one_minus_alpha;
+    int32_t max_lost, fuse, reid, cap, dim, no_fast;
+};
+
+struct BsTable {                    // device pointers
+    BsHdr* hdr;
+    BtTrack* trk;                   // the per-slot scalars are ByteTrack's (bytetrack.hpp)
+    int32_t* tl;
+    int32_t* ll;
+    float* mean;
+    float* cov;
+    int32_t* hasf;
+    float* feat;                    // [cap, dim] smoothed unit features, its own allocation
+};
+
+static inline size_t bs_table_bytes(int cap) {
+    return BS_HDR_BYTES + (size_t)cap * (sizeof(BtTrack) + 8 + 4 * 8 + 4 * 64 + 4);
+}
+static inline BsTable bs_table(char* base, int cap, float* feat) {
+    BsTable t;
+    t.hdr = reinterpret_cast<BsHdr*>(base);
+    t.trk = reinterpret_cast<BtTrack*>(base + BS_HDR_BYTES);
+    t.tl = reinterpret_cast<int32_t*>(base + BS_HDR_BYTES + (size_t)cap * sizeof(BtTrack));
+    t.ll = t.tl + cap;
+    t.mean = reinterpret_cast<float*>(t.ll + cap);
+    t.cov = t.mean + (size_t)cap * 8;
+    t.hasf = reinterpret_cast<int32_t*>(t.cov + (size_t)cap * 64);
+    t.feat = feat;
+    return t;
+}
+
+// one launch: frames [f0, f0 + k) of the group.  dets.feat_n (unit rows; NULL = no features) and dets.valid are read for the high band only;
+// warps = [frames, 6] camera motion (r00 r01 t0 r10 r11 t1) or NULL; ext = [TRK_DEV_NMAX^2] HBM scratch for extended matrices beyond the LDS
+void launch_botsort_epoch(const BsTable& tbl, const BsParams& prm, const EpochDets& dets, const float* warps, int f0, int k, float* ext,
+                          const EpochOut& out, hipStream_t s);
+// out[r] = in[r] / |in[r]| in the order of kf8wh_math.hpp (one wavefront per row)
+void launch_botsort_normalize(const float* in, float* out, int rows, int dim, hipStream_t s);
+
+}  // namespace aic

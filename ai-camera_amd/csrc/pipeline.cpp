@@ -16,6 +16,7 @@
 #include "tracker.hpp"
 #include "bytetrack_host.hpp"
 #include "ocsort_host.hpp"
+#include "botsort_host.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -186,8 +187,12 @@ struct Pipeline {
     // A detector-only tracker (aic_pipeline_create_bytetrack / _ocsort): no ReID model (reid == nullptr); crop, ReID and the embedding copies
     // are not issued and the association is the tracker's epoch kernel on the tracker stream (epoch_tracker.hpp).  The DeepSORT tracker
     // object below then exists but is never run.
+    // BoT-SORT (aic_pipeline_create_botsort) is an epoch tracker WITH a ReID model: stage A crops and embeds as for DeepSORT (host detection
+    // filter), the embeddings stay in HBM and reach the epoch kernel through EpochDets.valid / feat / feat_n.
     std::unique_ptr<EpochTracker> bt;
     std::string bt_name() const { return bt->name(); }
+    bool bs = false;                // the epoch tracker is BoT-SORT
+    float bs_low = 0.f;             // its track_low_thresh: inject = 0 hands over the detections with score > bs_low
 
     static aic_tracker_params tracker_params(const aic_pipeline_params& p, bool bytetrack) {
         if (!bytetrack) return p.tracker;
@@ -197,12 +202,14 @@ struct Pipeline {
         return t;
     }
 
-    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr)
-        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp))), trk(trk_handle->t) {
+    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr,
+             const BsParams* bsp = nullptr)
+        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp || bsp))), trk(trk_handle->t) {
         AIC_REQUIRE(y->kind == KIND_YOLO && (btp || ocp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
                     btp   ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
                     : ocp ? "an OC-SORT pipeline takes a YOLO engine and no ReID engine"
                           : "pipeline needs a YOLO and a ReID engine");
+        AIC_REQUIRE(!bsp || bsp->dim == r->out_dim, AIC_ERR_INVALID, "feature_dim of the BoT-SORT parameters differs from the ReID engine's output");
         AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
@@ -211,6 +218,7 @@ struct Pipeline {
         dev->use();
         if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
         else if (ocp) bt.reset(new OcSortTracker(*dev, *ocp, bt_first_id));
+        else if (bsp) { bt.reset(new BotSortTracker(*dev, *bsp, bt_first_id)); bs = true; bs_low = bsp->low; }
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
@@ -260,6 +268,7 @@ struct Pipeline {
         fd.tlwh.clear(), fd.xyxy.clear(), fd.conf.clear(), fd.cls.clear();
         for (int i = 0; i < n; ++i) {
             if ((!bt && !(conf[i] >= prm.min_confidence)) || !tracked_class(cls[i])) continue;   // detector-only trackers: their bands filter the scores
+            if (bs && !prm.inject && !(conf[i] > bs_low)) continue;   // BoT-SORT: nothing at or below its low band is used, so nothing there is embedded
             const float* b = boxes_xyxy + (size_t)i * 4;
             fd.tlwh.insert(fd.tlwh.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});   // deepsort_tracker.py:185-186
             fd.xyxy.insert(fd.xyxy.end(), b, b + 4);                                    // crops use the xyxy box (:148)
@@ -346,7 +355,7 @@ struct Pipeline {
         // consumer thread, that mode's critical thread), so the stream-ordered filter only saves a round trip where the association stays
         // on the device too.  The choice reads state the consumer wrote before it released this context: the same frames always take the
         // same path.  dev_filter 2: always on the device.
-        if (!prm.inject && reid && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16) {
+        if (!prm.inject && reid && !bt && dev_filter && (dev_filter == 2 || c.prev_dev_mode) && c.ln->reid->dtype == AIC_F16) {
             c.ln->reid->in_pix4 = c.ln->reid->input_pix4_ok();
             c.filt_dev = c.ln->reid->in_pix4;
         }
@@ -439,7 +448,8 @@ struct Pipeline {
             }
             {   // matching.py:126-130 for every detection of the launch group at once
                 Prof pr(*dev, PROF_TRK, sr, 0, (double)nc * dim * 8);
-                launch_normalize_rows(c.d_emb.p, c.d_emb_n.p, nc, dim, sr);
+                if (bs) launch_botsort_normalize(c.d_emb.p, c.d_emb_n.p, nc, dim, sr);   // the summation order tests/botsort_oracle.py states
+                else launch_normalize_rows(c.d_emb.p, c.d_emb_n.p, nc, dim, sr);
             }
             HIP_CHECK(hipMemcpyAsync(c.h_valid.p, c.d_valid.p, (size_t)nc * 4, hipMemcpyDeviceToHost, sr));
         }
@@ -736,6 +746,7 @@ struct Pipeline {
         EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
                        reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
                        reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), nullptr, nullptr, nullptr};
+        if (reid && c.n_crops) dets.valid = c.d_valid.p, dets.feat = c.d_emb.p, dets.feat_n = c.d_emb_n.p;   // BoT-SORT: the group's embeddings, in HBM
         EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
                      mp, nullptr, nullptr, 0};
         bt->run_epochs(dets, c.frames, out, s);
@@ -762,6 +773,12 @@ struct Pipeline {
             if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
             if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
             if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
+        }
+        if (reid && final_group) {                               // aic_pipeline_last_embeddings, as after a DeepSORT group
+            const FrameDets& fl = c.dets[c.frames - 1];
+            last_emb_n = fl.n;
+            last_emb.resize((size_t)fl.n * dim);
+            if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
         }
         last_chunk = (int)(&c - &ck[0]);
         t_track += now() - t2;
@@ -905,8 +922,9 @@ using namespace aic;
 
 struct aic_pipeline {
     Pipeline p;
-    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr)
-        : p(y, r, q, b, first_id, o) {}
+    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr,
+                 const BsParams* bs = nullptr)
+        : p(y, r, q, b, first_id, o, bs) {}
 };
 
 extern "C" {
@@ -933,6 +951,15 @@ int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, co
         int first = 1;
         const OcParams o = ocsort_params(*op, &first);
         *out = new aic_pipeline(&yolo->m, nullptr, *p, nullptr, first, &o);
+    });
+}
+
+int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp, aic_pipeline** out) {
+    return guarded([&] {
+        AIC_REQUIRE(yolo && reid && p && bp && out, AIC_ERR_INVALID, "NULL argument");
+        int first = 1;
+        const BsParams b = botsort_params(*bp, &first);
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b);
     });
 }
 
@@ -1219,7 +1246,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
                                   int32_t* n_rows, int32_t* n_frames, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n_rows && n_frames && dim, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
+        AIC_REQUIRE(!p->p.bt || p->p.reid, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
         Pipeline& q = p->p;
         *dim = q.dim, *n_rows = 0, *n_frames = 0;
         if (q.last_chunk < 0) return;
@@ -1240,7 +1267,7 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
 int aic_pipeline_last_embeddings(aic_pipeline* p, float* emb, int cap_rows, int32_t* n, int32_t* dim) {
     return guarded([&] {
         AIC_REQUIRE(p && n && dim, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
+        AIC_REQUIRE(!p->p.bt || p->p.reid, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline computes no embeddings");
         *n = p->p.last_emb_n, *dim = p->p.dim;
         AIC_REQUIRE(p->p.last_emb_n <= cap_rows, AIC_ERR_CAPACITY, "embedding capacity too small");
         if (emb) std::copy(p->p.last_emb.begin(), p->p.last_emb.end(), emb);

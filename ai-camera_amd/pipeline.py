@@ -25,9 +25,13 @@ class TrackingPipeline:
         conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
         tracker="ocsort": the same pipeline with OC-SORT (aic_pipeline_create_ocsort); the extra arguments are OCSort's (det_thresh,
         min_hits, iou_threshold, delta_t, inertia, use_byte; max_age is the named argument), and conf_thresh defaults to det_thresh,
-        or to 0.1 with use_byte."""
-        if tracker not in ("deepsort", "bytetrack", "ocsort"):
-            raise ValueError(f"tracker must be 'deepsort', 'bytetrack' or 'ocsort', not {tracker!r}")
+        or to 0.1 with use_byte.
+        tracker="botsort": BoT-SORT WITH the ReID engine (aic_pipeline_create_botsort): crop + ReID as for DeepSORT, the embeddings stay
+        in HBM and feed the epoch kernel; the extra arguments are BoTSORT's (track_high_thresh, track_low_thresh, new_track_thresh,
+        match_thresh, proximity_thresh, appearance_thresh, track_buffer, frame_rate, fuse_score, with_reid, feat_alpha), and conf_thresh
+        defaults to track_low_thresh."""
+        if tracker not in ("deepsort", "bytetrack", "ocsort", "botsort"):
+            raise ValueError(f"tracker must be 'deepsort', 'bytetrack', 'ocsort' or 'botsort', not {tracker!r}")
         if tracker == "deepsort" and bytetrack_params:
             raise TypeError(f"unexpected arguments for a DeepSORT pipeline: {sorted(bytetrack_params)}")
         self.tracker_kind = tracker
@@ -67,6 +71,22 @@ class TrackingPipeline:
                                            int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
             self._h = C.c_void_p()
             L.call("aic_pipeline_create_ocsort", self.yolo._h, C.byref(self.params), C.byref(self.ocsort_params), C.byref(self._h))
+            self.tracker_core = None
+            return
+        if tracker == "botsort":
+            from .botsort import botsort_params as _bsp
+            self.reid = reid_engine if isinstance(reid_engine, HipEngine) else HipEngine(
+                reid_engine, device=device, dtype=dtype, max_items=self.batch * self.max_persons, warm_up=False)
+            self.botsort_params = _bsp(max_tracks=max_tracks, feature_dim=int(self.reid.out_dim), **bytetrack_params)
+            if conf_thresh is None:
+                conf_thresh = self.botsort_params.track_low_thresh
+            tp = L.TrackerParams(0.2, 0.7, 1, 1, 1, 1, 0, 1)          # ignored by aic_pipeline_create_botsort
+            self.params = L.PipelineParams(self.frame_h, self.frame_w, self.batch, self.ring_frames, self.max_persons,
+                                           float(conf_thresh), float(iou_thresh), self.max_det, 0.0,
+                                           int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
+            self._h = C.c_void_p()
+            L.call("aic_pipeline_create_botsort", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self.botsort_params),
+                   C.byref(self._h))
             self.tracker_core = None
             return
         if conf_thresh is None:

@@ -52,6 +52,7 @@ typedef struct aic_model aic_model;       /* one engine file resident on one GPU
 typedef struct aic_tracker aic_tracker;   /* DeepSORT core state of one video stream      */
 typedef struct aic_pipeline aic_pipeline; /* detector + ReID + tracker over resident frames */
 typedef struct aic_bytetrack aic_bytetrack; /* ByteTrack state of one video stream          */
+typedef struct aic_botsort aic_botsort;     /* BoT-SORT state of one video stream           */
 typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream            */
 
 /* ------------------------------------------------------------------ library / device */
@@ -333,6 +334,52 @@ int aic_ocsort_export(aic_ocsort* t, int cap, int32_t* track_id, int32_t* age, i
 int aic_ocsort_counters(aic_ocsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_oru, int32_t* max_gap,
                         int64_t* n_ocr, int64_t* n_byte);
 
+/* ------------------------------------------------------------------ BoT-SORT
+ * BoTSORT.update() with ReID of the BoT-SORT authors (tracker/bot_sort.py, matching.py, kalman_filter.py) on the device, k frames per
+ * launch (csrc/kernels_botsort.hip; specification: tests/botsort_oracle.py, deviations: DESIGN.md section 18): ByteTrack's bands and life
+ * cycle, a Kalman filter on [cx, cy, w, h], one exponentially smoothed appearance vector per track, and a first association on
+ * min(IoU distance, gated cosine distance / 2).  Camera motion is an input (a 2x3 affine per frame), never estimated here.
+ * Defaults are upstream's; every threshold is rounded to fp32 once. */
+typedef struct aic_botsort_params {
+    double track_high_thresh; /* 0.6: high band s > track_high_thresh (only these detections carry a feature)     */
+    double track_low_thresh;  /* 0.1: low band track_low_thresh < s < track_high_thresh                             */
+    double new_track_thresh;  /* 0.7: a new track needs s >= this                                                   */
+    double match_thresh;      /* 0.8: first association                                                             */
+    double proximity_thresh;  /* 0.5: appearance is ignored for a pair with IoU distance above this (before fusion) */
+    double appearance_thresh; /* 0.25: appearance is ignored for a pair with cosine distance / 2 above this          */
+    double feat_alpha;        /* 0.9: smooth <- alpha smooth + (1 - alpha) feature, renormalised                     */
+    int32_t track_buffer;     /* 30                                                                                 */
+    int32_t frame_rate;       /* 30: max_time_lost = int(frame_rate / 30 * track_buffer)                            */
+    int32_t fuse_score;       /* 1: IoU distance fused with the detection score                                      */
+    int32_t with_reid;        /* 1; 0: features are ignored, the cost is the IoU distance                            */
+    int32_t feature_dim;      /* 0 -> 512; a multiple of 4, at most 4096                                            */
+    int32_t max_tracks;       /* live tracks (0 -> 512, at most 512)                                                */
+    int32_t first_track_id;   /* 1: ids are counted per tracker                                                     */
+} aic_botsort_params;
+
+/* AIC_ERR_INVALID for a threshold outside (0, 1], track_low_thresh >= track_high_thresh, feat_alpha outside [0, 1), feature_dim not a
+ * multiple of 4, max_tracks over 512, ... (checked before the device). */
+int aic_botsort_create(int device, const aic_botsort_params* p, aic_botsort** out);
+int aic_botsort_destroy(aic_botsort* t);
+/* "lsap_fast" and "epoch_frames" as aic_bytetrack_option.  Same results either way. */
+int aic_botsort_option(aic_botsort* t, const char* key, int value);
+/* k consecutive frames, each one BoTSORT.update(): arrays and outputs as aic_bytetrack_update_batch, plus feat[sum, feature_dim] raw
+ * embeddings (normalised on the device; NULL = no features, the call then runs as with_reid = 0), valid[sum] (0 = the row has no
+ * feature; NULL = all have one) and warps[k, 6] (per frame r00 r01 t0 r10 r11 t1; NULL = no camera motion).  The output rows are ALL
+ * tracks of the tracked list, as upstream.  Errors as aic_bytetrack_update_batch. */
+int aic_botsort_update_batch(aic_botsort* t, int k, const int32_t* counts, const float* boxes_xyxy, const float* conf,
+                             const int32_t* cls, const float* feat, const int32_t* valid, const float* warps, int cap_rows,
+                             int32_t* n_out, int32_t* out6, float* out_conf);
+/* Live tracks as aic_bytetrack_export (mean = [cx, cy, w, h, v...]) plus has_feat[n] and smooth_feat[n, feature_dim] (zeros without). */
+int aic_botsort_export(aic_botsort* t, int cap, int32_t* track_id, int32_t* state, int32_t* is_activated, int32_t* start_frame,
+                       int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* has_feat, float* smooth_feat,
+                       int32_t* n_tracks, int32_t* n_tracked);
+/* As aic_bytetrack_counters, plus the matched pairs (first association and unconfirmed tracks) whose winning term was the appearance
+ * distance (d_emb < d_iou), and two shader-clock totals since creation: the appearance pass of the fused cost (the dot products) and
+ * the whole epoch kernel.  The counts are 64-bit on the device as well. */
+int aic_botsort_counters(aic_botsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_appearance,
+                         int64_t* cost_cycles, int64_t* kernel_cycles);
+
 /* ------------------------------------------------------------------ end-to-end pipeline
  * The loop body of src/aicamera_tracker.py:169-207 (detect + track, the reference's own FPS
  * span) over frames that are already resident in HBM, batched: detection and ReID of
@@ -367,6 +414,14 @@ int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p,
  * det_thresh (0.1 with use_byte). */
 int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, const aic_ocsort_params* op,
                                aic_pipeline** out);
+/* BoT-SORT as the pipeline's tracker, WITH the ReID engine: stage A as for DeepSORT with the host detection filter (crop + ReID for every
+ * detection handed to the tracker; the embeddings stay in HBM and reach the epoch kernel directly), stage B as on a ByteTrack pipeline.
+ * inject = 0 hands over the detections of a tracked class with score > track_low_thresh (min_confidence and p->tracker are ignored, so
+ * conf_thresh should be at most track_low_thresh).  No camera-motion warp.  bp->feature_dim must be the ReID engine's output size.
+ * aic_pipeline_last_embeddings / _group_embeddings work; aic_pipeline_tracker, the gallery exchange and the options "device_assoc",
+ * "device_assoc_limit", "device_filter" fail with AIC_ERR_INVALID. */
+int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp,
+                                aic_pipeline** out);
 int aic_pipeline_destroy(aic_pipeline* p);
 /* Copy `count` u8 BGR frames into ring slots [slot, slot+count). */
 int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames_bgr, int count);
