@@ -317,6 +317,11 @@ ConvPlan plan_conv(int dtype, const ConvArgs& a, int cu_budget) {
     return variant(4, 1, 4, 1);                                                                          // 256 px x 16 ch
 }
 
+ConvPlan plan_conv_launch(int dtype, ConvArgs& a, int cu_budget) {
+    a.k_order = conv_k_order(dtype, a);      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
+    return plan_conv(dtype, a, cu_budget);
+}
+
 // ---- the predicates the engine asks at load time
 
 bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail) {

@@ -113,6 +113,9 @@ int conv_k_order(int dtype, const ConvArgs& a);
 // The plan for `a` as launch_conv_igemm passes it (k_order set): the first rule of the tree that takes the layer.
 ConvPlan plan_conv(int dtype, const ConvArgs& a, int cu_budget);
 
+// What launch_conv_igemm does before it launches: sets a.k_order from the shape, then plans with it.
+ConvPlan plan_conv_launch(int dtype, ConvArgs& a, int cu_budget);
+
 // true when launch_conv_igemm can run `lead` with `tail` (a 1x1 / stride 1 / pad 0 conv reading exactly lead's output) in its epilogue:
 // fp16, lead = SiLU without residual with Cout 64 or 80 (a wave then owns every channel of its pixels), tail.Cout <= lead.Cout
 bool conv_tail_supported(int dtype, const ConvArgs& lead, const ConvArgs& tail);

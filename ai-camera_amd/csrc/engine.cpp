@@ -559,6 +559,113 @@ void Model::run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hip
     run(n, s);
 }
 
+// What run_range launches at conv op `oi` (engine.hpp, ConvStep).  No launch, no change to the model: aic_model_conv_plan asks the same
+// question for a test.
+Model::ConvStep Model::conv_step(size_t oi, size_t op1, int n) const {
+    ConvStep st;
+    const OpDesc& o = ops[oi];
+    double fl = 0, by = 0;
+    auto conv_args = [&](size_t k) {
+        const int* u = ops[k].v;
+        const BufDesc& xb = bufs[u[1]];
+        const BufDesc& yb = bufs[u[4]];
+        const ConvWeights& w = weights[u[15]];
+        ConvArgs a{};
+        a.x = xb.p, a.w = w.w.p, a.bias = w.bias.p, a.y = yb.p;
+        a.x_cs = xb.c, a.x_coff = u[2], a.H = xb.h, a.W = xb.w, a.Cin = w.cin_eff;
+        a.y_cs = yb.c, a.y_coff = u[5], a.Ho = yb.h, a.Wo = yb.w, a.Cout = w.cout;
+        a.res = nullptr, a.r_cs = 0, a.r_coff = 0, a.res_mode = u[14], a.act = u[11];
+        if (u[14]) { a.res = bufs[u[12]].p, a.r_cs = bufs[u[12]].c, a.r_coff = u[13]; }
+        a.KH = w.kh, a.KW = w.kw, a.stride = u[9], a.pad = u[10];
+        if (ops[k].xs_buf >= 0) {               // folded 2x upsample: the first channels come from the half-resolution tensor
+            const BufDesc& bs = bufs[ops[k].xs_buf];
+            a.xs = bs.p, a.xs_cs = bs.c, a.xs_coff = ops[k].xs_coff, a.Hs = bs.h, a.Ws = bs.w, a.Cs = ops[k].xs_c;
+        }
+        if (u[16]) {                            // folded 1x1 second source
+            const BufDesc& b2 = bufs[u[16] - 1];
+            a.x2 = b2.p, a.x2_cs = b2.c, a.x2_coff = u[17], a.H2 = b2.h, a.W2 = b2.w, a.s2 = u[19], a.Cin2 = u[18];
+            fl += 2.0 * n * yb.h * yb.w * (double)w.cout * u[18];
+            by += ((double)n * yb.h * yb.w * u[18] + (double)w.cout * u[18]) * (dtype == AIC_F16 ? 2 : 4);
+        }
+        a.Kp = w.Kp, a.M = n * yb.h * yb.w, a.out_f32 = yb.f32, a.cout_pad = w.cout_pad, a.zero = d_zero.p;
+        a.tap_rows = 0;
+        a.n_dev = n_items_dev;
+        for (int kh = 0; kh < w.kh; ++kh) a.tap_rows |= 1u << (kh * w.kw);
+        AIC_REQUIRE(w.kh * w.kw <= 25, AIC_ERR_FORMAT, "kernel window larger than 5x5");
+        fl += 2.0 * a.M * (double)w.cout * w.cin * w.kh * w.kw;
+        by += ((double)n * xb.h * xb.w * w.cin + (double)a.M * w.cout) * (dtype == AIC_F16 ? 2 : 4) +
+              (double)w.cout * w.cin * w.kh * w.kw * (dtype == AIC_F16 ? 2 : 4);
+        return a;
+    };
+    auto done = [&](int kind, int n_ops) { st.kind = kind, st.n_ops = n_ops, st.fl = fl, st.by = by; return st; };
+    const ConvArgs a = st.a[0] = conv_args(oi);
+    // a 64-channel BasicBlock (this conv and the next, which adds this one's input) runs as ONE kernel where it applies;
+    // FLOPs and algorithmic bytes are accounted as for the two convs
+    bool pair = false;
+    ConvArgs a2{};
+    if (dtype == AIC_F16 && oi + 1 < op1 && ops[oi + 1].v[0] == OP_CONV && ops[oi + 1].fuse == 0 && a.Cin == 64 && a.Cout == 64 &&
+        a.res_mode == 0 && ops[oi + 1].v[14] == 1) {
+        const double fl0 = fl, by0 = by;
+        a2 = conv_args(oi + 1);
+        pair = a2.res == a.x && a2.x == a.y;
+        if (!pair) fl = fl0, by = by0;
+    }
+    // a C2f block with 16-channel halves (YOLOv8n's 160 x 160 stage: cv1, m.cv1, m.cv2 + shortcut, cv2) runs as ONE kernel where
+    // it applies; FLOPs and algorithmic bytes are accounted as for the four convs
+    if (!pair && dtype == AIC_F16 && oi + 3 < op1 && a.KH == 1 && a.Cin == 32 && a.Cout == 32 && ops[oi + 1].v[0] == OP_CONV &&
+        ops[oi + 2].v[0] == OP_CONV && ops[oi + 3].v[0] == OP_CONV && !ops[oi + 1].fuse && !ops[oi + 2].fuse && !ops[oi + 3].fuse) {
+        const double fl0 = fl, by0 = by;
+        const ConvArgs b1 = conv_args(oi + 1), b2 = conv_args(oi + 2), b3 = conv_args(oi + 3);
+        if (plan_c2f16(a, b1, b2, b3)) {
+            st.a[1] = b1, st.a[2] = b2, st.a[3] = b3;
+            return done(ConvStep::C2f16, 4);
+        }
+        fl = fl0, by = by0;
+    }
+    if (const int ipb = pair ? plan_c64_block(a, a2, conv_cu_budget()) : 0) {
+        st.a[1] = a2, st.ipb = ipb;
+        return done(ConvStep::C64Block, 2);
+    }
+    if (pair) { fl = 0, by = 0; (void)conv_args(oi); }          // not fused after all: account this conv alone
+    // a conv whose only consumer is the 1x1 conv after it (marked at load time) takes that conv into its epilogue where the
+    // kernels can; FLOPs and algorithmic bytes are accounted as for the two convs
+    if (o.fuse == 3 && oi + 1 < op1) {
+        const double fl0 = fl, by0 = by;
+        const ConvArgs t = conv_args(oi + 1);
+        if (conv_tail_supported(dtype, a, t)) {
+            ConvArgs at = a;
+            at.w_tail = t.w, at.b_tail = t.bias, at.y_tail = t.y, at.t_cout = t.Cout, at.t_kp = t.Kp;
+            at.t_y_cs = t.y_cs, at.t_y_coff = t.y_coff, at.t_out_f32 = t.out_f32, at.t_act = t.act;
+            static const bool cls_reduce_on = getenv("AICAM_NO_CLS_REDUCE") == nullptr;
+            static const bool box_decode_on = getenv("AICAM_NO_BOX_DECODE") == nullptr;
+            if (reduce_cls && kind == KIND_YOLO && t.out_f32 && t.act == 0 && t.y_coff == 0 && t.y_cs == t.Cout) {
+                // a detect level's class / box branch: its logits only feed decode's arg-max / DFL expectation
+                const bool is_cls = cls_reduce_on && t.Cout == meta[0], is_box = box_decode_on && meta[1] == 16 && t.Cout == 64 && a.Cout == 64 && !is_cls;   // tail_1x1 decodes in place only in its NT == 4 form (lead Cout 64; YOLOv8x leads with 80)
+                int a0 = 0;
+                for (size_t l = 0; l < outs.size() && (is_cls || is_box); ++l) {
+                    const int* ov = outs[l].v;
+                    const BufDesc& ob = bufs[ov[is_cls ? 1 : 0]];
+                    if (ob.p == t.y && ov[3] * ov[4] == t.Ho * t.Wo) {
+                        at.t_hw = ov[3] * ov[4], at.t_a0 = a0, at.t_na = n_anchors;
+                        if (is_cls) {
+                            at.t_max = d_maxlogit.p, at.t_arg = d_labels.p;
+                            st.cls_bits |= 1u << l;
+                        } else {
+                            at.t_box = d_boxes.p, at.t_w = ov[4], at.t_stride = ov[2];
+                            st.box_bits |= 1u << l;
+                        }
+                    }
+                    a0 += ov[3] * ov[4];
+                }
+            }
+            st.a[0] = at;
+            return done(ConvStep::Tail, 2);
+        }
+        fl = fl0, by = by0;
+    }
+    return done(ConvStep::Single, 1);
+}
+
 void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
     // HIP-event timing of the conv kernel brackets RUNS of consecutive conv launches (one event pair per
     // run, not per launch: two event records per launch cost 13 % of end-to-end throughput); the summed
@@ -584,113 +691,16 @@ void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
             continue;
         }
         if (v[0] == OP_CONV) {
-            double fl = 0, by = 0;
-            auto conv_args = [&](size_t k) {
-                const int* u = ops[k].v;
-                const BufDesc& xb = bufs[u[1]];
-                const BufDesc& yb = bufs[u[4]];
-                const ConvWeights& w = weights[u[15]];
-                ConvArgs a{};
-                a.x = xb.p, a.w = w.w.p, a.bias = w.bias.p, a.y = yb.p;
-                a.x_cs = xb.c, a.x_coff = u[2], a.H = xb.h, a.W = xb.w, a.Cin = w.cin_eff;
-                a.y_cs = yb.c, a.y_coff = u[5], a.Ho = yb.h, a.Wo = yb.w, a.Cout = w.cout;
-                a.res = nullptr, a.r_cs = 0, a.r_coff = 0, a.res_mode = u[14], a.act = u[11];
-                if (u[14]) { a.res = bufs[u[12]].p, a.r_cs = bufs[u[12]].c, a.r_coff = u[13]; }
-                a.KH = w.kh, a.KW = w.kw, a.stride = u[9], a.pad = u[10];
-                if (ops[k].xs_buf >= 0) {               // folded 2x upsample: the first channels come from the half-resolution tensor
-                    const BufDesc& bs = bufs[ops[k].xs_buf];
-                    a.xs = bs.p, a.xs_cs = bs.c, a.xs_coff = ops[k].xs_coff, a.Hs = bs.h, a.Ws = bs.w, a.Cs = ops[k].xs_c;
-                }
-                if (u[16]) {                            // folded 1x1 second source
-                    const BufDesc& b2 = bufs[u[16] - 1];
-                    a.x2 = b2.p, a.x2_cs = b2.c, a.x2_coff = u[17], a.H2 = b2.h, a.W2 = b2.w, a.s2 = u[19], a.Cin2 = u[18];
-                    fl += 2.0 * n * yb.h * yb.w * (double)w.cout * u[18];
-                    by += ((double)n * yb.h * yb.w * u[18] + (double)w.cout * u[18]) * (dtype == AIC_F16 ? 2 : 4);
-                }
-                a.Kp = w.Kp, a.M = n * yb.h * yb.w, a.out_f32 = yb.f32, a.cout_pad = w.cout_pad, a.zero = d_zero.p;
-                a.tap_rows = 0;
-                a.n_dev = n_items_dev;
-                for (int kh = 0; kh < w.kh; ++kh) a.tap_rows |= 1u << (kh * w.kw);
-                AIC_REQUIRE(w.kh * w.kw <= 25, AIC_ERR_FORMAT, "kernel window larger than 5x5");
-                fl += 2.0 * a.M * (double)w.cout * w.cin * w.kh * w.kw;
-                by += ((double)n * xb.h * xb.w * w.cin + (double)a.M * w.cout) * (dtype == AIC_F16 ? 2 : 4) +
-                      (double)w.cout * w.cin * w.kh * w.kw * (dtype == AIC_F16 ? 2 : 4);
-                return a;
-            };
-            const ConvArgs a = conv_args(oi);
-            // a 64-channel BasicBlock (this conv and the next, which adds this one's input) runs as ONE kernel where it applies;
-            // FLOPs and algorithmic bytes are accounted as for the two convs
-            bool pair = false;
-            ConvArgs a2{};
-            if (dtype == AIC_F16 && oi + 1 < op1 && ops[oi + 1].v[0] == OP_CONV && ops[oi + 1].fuse == 0 && a.Cin == 64 && a.Cout == 64 &&
-                a.res_mode == 0 && ops[oi + 1].v[14] == 1) {
-                const double fl0 = fl, by0 = by;
-                a2 = conv_args(oi + 1);
-                pair = a2.res == a.x && a2.x == a.y;
-                if (!pair) fl = fl0, by = by0;
-            }
             if (prof_conv && !span_open) { dev->prof_begin(PROF_CONV, s, 0, 0); span_open = true; }
-            // a C2f block with 16-channel halves (YOLOv8n's 160 x 160 stage: cv1, m.cv1, m.cv2 + shortcut, cv2) runs as ONE kernel where
-            // it applies; FLOPs and algorithmic bytes are accounted as for the four convs
-            if (!pair && dtype == AIC_F16 && oi + 3 < op1 && a.KH == 1 && a.Cin == 32 && a.Cout == 32 && ops[oi + 1].v[0] == OP_CONV &&
-                ops[oi + 2].v[0] == OP_CONV && ops[oi + 3].v[0] == OP_CONV && !ops[oi + 1].fuse && !ops[oi + 2].fuse && !ops[oi + 3].fuse) {
-                const double fl0 = fl, by0 = by;
-                const ConvArgs b1 = conv_args(oi + 1), b2 = conv_args(oi + 2), b3 = conv_args(oi + 3);
-                if (plan_c2f16(a, b1, b2, b3)) {
-                    launch_c2f16(a, b1, b2, b3, s);
-                    if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
-                    oi += 3;
-                    continue;
-                }
-                fl = fl0, by = by0;
+            const ConvStep st = conv_step(oi, op1, n);
+            if (prof_conv) dev->prof_account(PROF_CONV, st.fl, st.by);
+            switch (st.kind) {
+                case ConvStep::C2f16: launch_c2f16(st.a[0], st.a[1], st.a[2], st.a[3], s); break;
+                case ConvStep::C64Block: launch_c64_block(st.a[0], st.a[1], st.ipb, s); break;
+                case ConvStep::Tail: cls_reduced |= st.cls_bits, box_decoded |= st.box_bits; [[fallthrough]];
+                default: launch_conv_igemm(dtype, st.a[0], s);
             }
-            if (const int ipb = pair ? plan_c64_block(a, a2, conv_cu_budget()) : 0) {
-                launch_c64_block(a, a2, ipb, s);
-                if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
-                ++oi;
-                continue;
-            }
-            if (pair) { fl = 0, by = 0; (void)conv_args(oi); }          // not fused after all: account this conv alone
-            // a conv whose only consumer is the 1x1 conv after it (marked at load time) takes that conv into its epilogue where the
-            // kernels can; FLOPs and algorithmic bytes are accounted as for the two convs
-            if (o.fuse == 3 && oi + 1 < op1) {
-                const double fl0 = fl, by0 = by;
-                const ConvArgs t = conv_args(oi + 1);
-                if (conv_tail_supported(dtype, a, t)) {
-                    ConvArgs at = a;
-                    at.w_tail = t.w, at.b_tail = t.bias, at.y_tail = t.y, at.t_cout = t.Cout, at.t_kp = t.Kp;
-                    at.t_y_cs = t.y_cs, at.t_y_coff = t.y_coff, at.t_out_f32 = t.out_f32, at.t_act = t.act;
-                    static const bool cls_reduce_on = getenv("AICAM_NO_CLS_REDUCE") == nullptr;
-                    static const bool box_decode_on = getenv("AICAM_NO_BOX_DECODE") == nullptr;
-                    if (reduce_cls && kind == KIND_YOLO && t.out_f32 && t.act == 0 && t.y_coff == 0 && t.y_cs == t.Cout) {
-                        // a detect level's class / box branch: its logits only feed decode's arg-max / DFL expectation
-                        const bool is_cls = cls_reduce_on && t.Cout == meta[0], is_box = box_decode_on && meta[1] == 16 && t.Cout == 64 && a.Cout == 64 && !is_cls;   // tail_1x1 decodes in place only in its NT == 4 form (lead Cout 64; YOLOv8x leads with 80)
-                        int a0 = 0;
-                        for (size_t l = 0; l < outs.size() && (is_cls || is_box); ++l) {
-                            const int* ov = outs[l].v;
-                            const BufDesc& ob = bufs[ov[is_cls ? 1 : 0]];
-                            if (ob.p == t.y && ov[3] * ov[4] == t.Ho * t.Wo) {
-                                at.t_hw = ov[3] * ov[4], at.t_a0 = a0, at.t_na = n_anchors;
-                                if (is_cls) {
-                                    at.t_max = d_maxlogit.p, at.t_arg = d_labels.p;
-                                    cls_reduced |= 1u << l;
-                                } else {
-                                    at.t_box = d_boxes.p, at.t_w = ov[4], at.t_stride = ov[2];
-                                    box_decoded |= 1u << l;
-                                }
-                            }
-                            a0 += ov[3] * ov[4];
-                        }
-                    }
-                    if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
-                    launch_conv_igemm(dtype, at, s);
-                    ++oi;
-                    continue;
-                }
-                fl = fl0, by = by0;
-            }
-            if (prof_conv) dev->prof_account(PROF_CONV, fl, by);
-            launch_conv_igemm(dtype, a, s);
+            oi += st.n_ops - 1;
         } else {
             EltArgs a{};
             a.src = sb.p, a.dst = db.p, a.n = n, a.h = sb.h, a.w = sb.w, a.c = v[3];
@@ -841,6 +851,36 @@ int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes) {
         m->m.dev->use();
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out, m->m.bufs[buf].p, bytes, hipMemcpyDeviceToHost));
+    });
+}
+
+int aic_model_conv_plan(aic_model* mm, int op, int n, int32_t* out) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && out && op >= 0 && op < (int)mm->m.ops.size() && n > 0 && n <= mm->m.max_items, AIC_ERR_INVALID, "bad argument");
+        const Model& m = mm->m;
+        std::fill(out, out + 24, 0);
+        for (size_t oi = 0; oi < m.ops.size(); ++oi) {          // the walk of run_range
+            const OpDesc& o = m.ops[oi];
+            const bool launches = o.v[0] == OP_CONV && o.fuse != 2 && o.fuse != 1;
+            if (!launches) {
+                if ((int)oi == op) { out[0] = -1; return; }
+                continue;
+            }
+            const Model::ConvStep st = m.conv_step(oi, m.ops.size(), n);
+            if (op >= (int)(oi + st.n_ops)) { oi += st.n_ops - 1; continue; }
+            out[1] = (int)oi, out[2] = st.n_ops, out[3] = st.ipb;
+            if ((int)oi != op) { out[0] = -2; return; }
+            out[0] = st.kind;
+            if (st.kind == Model::ConvStep::Single || st.kind == Model::ConvStep::Tail) {
+                ConvArgs a = st.a[0];
+                const ConvPlan p = plan_conv_launch(m.dtype, a, conv_cu_budget());
+                const long v[] = {(long)p.form, p.mt, p.nt, p.wm, p.wn, p.nstage, p.th, p.tw, p.cpp, p.pitch, p.kord, p.g, p.tail, p.x2, p.run, p.blocks};
+                out[4] = a.k_order;
+                for (int i = 0; i < 16; ++i) out[5 + i] = (int32_t)v[i];
+                out[21] = a.xs != nullptr, out[22] = a.y_coff, out[23] = a.x_coff;
+            }
+            return;
+        }
     });
 }
 

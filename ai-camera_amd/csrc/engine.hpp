@@ -80,6 +80,18 @@ struct Model {
     // u8 BGR frames -> letterbox -> the whole graph; fp16 YOLO engines fuse the letterbox into the stem conv
     void run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hipStream_t s);
     void run_range(size_t op0, size_t op1, int n, hipStream_t s);
+    // What run_range launches at conv op `oi` (live, not a fused stem) of a launch of n items whose range ends at op1: the conv alone,
+    // the conv with the next 1x1 as its tail (a[0] carries the tail), the 64-channel BasicBlock pair or the four convs of a C2f block
+    // in one kernel -- with the ConvArgs of the n_ops ops it covers, in list order, and the profiler's FLOPs / algorithmic bytes.
+    struct ConvStep {
+        enum { Single = 0, Tail = 1, C64Block = 2, C2f16 = 3 };
+        int kind = Single, n_ops = 1;
+        int ipb = 0;                              // C64Block: images per block
+        unsigned cls_bits = 0, box_bits = 0;      // Tail: the detect levels whose class reduction / box decode this launch does
+        ConvArgs a[4];
+        double fl = 0, by = 0;
+    };
+    ConvStep conv_step(size_t oi, size_t op1, int n) const;
     // Launches of a FEW frames (the per-frame plugin loop: one 640 x 640 image is 6 - 150 workgroups per layer on 256 CUs, ~10 us per dependent
     // launch): the detect branches of every level but the last leave the main stream -- level l's ops (those from which only output l is
     // reachable) run on a side stream from the moment their feature map exists, beside the rest of the neck, and the main stream joins them

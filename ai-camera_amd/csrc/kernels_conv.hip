@@ -388,8 +388,7 @@ void launch_conv_igemm(int dtype, const ConvArgs& a0, hipStream_t s) {
     if (a0.M <= 0) return;
     ConvArgs a = a0;
     a.xcd_map = 1;
-    a.k_order = conv_k_order(dtype, a);      // 3: the stride-2 patch kernel's order (kernels_conv_sp.hip)
-    const ConvPlan p = plan_conv(dtype, a, conv_cu_budget());
+    const ConvPlan p = plan_conv_launch(dtype, a, conv_cu_budget());
     if (a.k_order == 2 && p.form != ConvForm::C64Resident) {
         // the order AND the bias placement of the weights-resident kernels (Cout = 64: one 256-byte zero page covers the epilogue's reads)
         a.bias_init = a.bias;

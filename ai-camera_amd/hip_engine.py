@@ -128,6 +128,30 @@ class HipEngine:
             L.call("aic_reid_infer", self._h, L.ptr(x), n, L.HOST, L.ptr(out), L.HOST)
         return out
 
+    def read_buffer_np(self, buf, n):
+        """Activation buffer `buf` of the engine file's buffer table after the last run, items 0 .. n-1: an [n, h, w, c] NHWC array at
+        the buffer's element type (float32 for an fp32 buffer or engine, else float16) and full channel width."""
+        with open(self.engine_path, "rb") as f:
+            head = np.frombuffer(f.read(68), "<i4")
+            tab = np.frombuffer(f.read(16 * int(head[5])), "<i4").reshape(-1, 4)
+        h, w, c, f32 = (int(v) for v in tab[buf])
+        out = np.empty((int(n), h, w, c), np.float32 if f32 or self.dtype == L.F32 else np.float16)
+        L.call("aic_model_read_buffer", self._h, int(buf), L.ptr(out), out.nbytes)
+        return out
+
+    def conv_plan(self, op, n):
+        """What a launch of n items runs at op `op` of the engine file's op list (aic_model_conv_plan, include/aicam.h)."""
+        out = np.zeros(24, np.int32)
+        L.call("aic_model_conv_plan", self._h, int(op), int(n), L.ptr(out))
+        names = ["form", "mt", "nt", "wm", "wn", "nstage", "th", "tw", "cpp", "pitch", "kord", "g", "tail", "x2", "run", "blocks"]
+        forms = ["Dma", "Wide", "Pp", "PpPatch", "SpPatch", "S2Patch", "Patch", "PmPatch", "C16", "C32s2Tail", "Stream1x1", "C64Resident"]
+        r = {"kind": {-2: "covered", -1: "none", 0: "conv", 1: "conv+tail", 2: "c64_block", 3: "c2f16"}[int(out[0])],
+             "first_op": int(out[1]), "n_ops": int(out[2]), "ipb": int(out[3])}
+        if out[0] in (0, 1):
+            r.update({k: int(v) for k, v in zip(names, out[5:21])})
+            r.update(form=forms[r["form"]], k_order=int(out[4]), xs=int(out[21]), y_coff=int(out[22]), x_coff=int(out[23]))
+        return r
+
     def detect_np(self, frames_bgr, conf=None, iou=None, max_det=None):
         f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
         if f.ndim == 3:

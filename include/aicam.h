@@ -73,6 +73,13 @@ int aic_model_load_mem(const void* blob, size_t nbytes, int device, int dtype, i
  * items of the last run first) -- what a TensorRT user gets by marking a layer as an output (src/trt_utils/trt_engine.py:62-120 lists
  * only the marked I/O tensors). */
 int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes);
+/* Read-only: what a launch of n items runs at op `op` of the engine's op list, decided by the code the launch itself goes through.
+ * out[24]: [0] -1 = no conv launch of its own (not a conv, or absorbed at load time), -2 = runs inside the launch that starts at op
+ * out[1], 0 = one conv, 1 = conv with the next 1x1 in its epilogue, 2 = 64-channel BasicBlock pair in one kernel, 3 = C2f block in one
+ * kernel; [1] first op of the launch, [2] ops it covers, [3] images per block (kind 2); kinds 0 / 1: [4] K order, [5..20] the planner's
+ * form, mt, nt, wm, wn, nstage, th, tw, cpp, pitch, kord, g, tail, x2, run, blocks; [21] split source, [22] / [23] destination /
+ * source channel offset. */
+int aic_model_conv_plan(aic_model* m, int op, int n, int32_t* out);
 int aic_model_destroy(aic_model* m);
 /* kind, input H/W, classes (YOLO) or feature dim (ReID), anchors per image, conv FLOPs per item */
 int aic_model_info(const aic_model* m, int* kind, int* in_h, int* in_w, int* out_dim,
