@@ -80,6 +80,8 @@ _SIGS = {
     "aic_yolo_infer": (_I, [_P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "aic_yolo_head": (_I, [_P, _P, _I, _I, _P, _P]),
     "aic_yolo_decode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "aic_yolo_postprocess": (_I, [_P, _P, _P, _I, _F, _F, _I, _I, _F, _F, _F, _I, _I] + [_P] * 9),
+    "aic_det_filter": (_I, [_I, _P, _P, _P, _P, _I, _I, _F, _P, _I] + [_P] * 9),
     "aic_reid_infer": (_I, [_P, _P, _I, _I, _P, _I]),
     "aic_letterbox": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "aic_letterbox_image": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -87,7 +87,13 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
         b.h = btab[i * 4], b.w = btab[i * 4 + 1], b.c = btab[i * 4 + 2], b.f32 = btab[i * 4 + 3];
         AIC_REQUIRE(b.h > 0 && b.w > 0 && b.c > 0, AIC_ERR_FORMAT, "bad buffer shape");
         b.esize = b.f32 ? 4 : esz;
-        AIC_REQUIRE(b.c % (16 / b.esize) == 0, AIC_ERR_FORMAT, "buffer channel count must be a multiple of 16 bytes");
+        // whole 16-byte vectors per pixel: every conv reads its input, and the fast epilogues store, in such vectors.  The one exception is
+        // a YOLO level's fp32 class tensor: nothing reads it but decode_kernel (scalar arg-max when nc % 4 != 0) and the copies of
+        // aic_yolo_head, and a conv whose Cout is no multiple of 4 stores it through the scalar epilogue (epilogue_generic)
+        bool cls_out = false;
+        for (int o = 0; o < nout && kind == KIND_YOLO; ++o) cls_out = cls_out || outtab[(size_t)o * 8 + 1] == i;
+        AIC_REQUIRE(b.c % (16 / b.esize) == 0 || (cls_out && b.f32 && b.c == meta[0]), AIC_ERR_FORMAT,
+                    "buffer channel count must be a multiple of 16 bytes");
         b.per_item = (size_t)b.h * b.w * b.c * b.esize;
         storage[i].alloc(b.per_item * max_items + 256);
         HIP_CHECK(hipMemsetAsync(storage[i].p, 0, storage[i].n, d.s_main));
@@ -979,6 +985,98 @@ int aic_yolo_decode(aic_model* mm, const float* images, int batch, int mem, floa
         copy_out(boxes, m.d_boxes.p, ba * 16, AIC_HOST, s);
         copy_out(max_logit, m.d_maxlogit.p, ba * 4, AIC_HOST, s);
         copy_out(labels, m.d_labels.p, ba * 4, AIC_HOST, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int aic_yolo_postprocess(aic_model* mm, const float* dfl, const float* cls, int batch, float conf, float iou, int max_det, int use_geom,
+                         float pad_w, float pad_h, float ratio, int orig_w, int orig_h, float* boxes, float* max_logit, int32_t* labels,
+                         int32_t* n_cand, int32_t* num_dets, float* out_boxes, float* out_boxes_orig, float* out_scores, int32_t* out_labels) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && dfl && cls && boxes && max_logit && labels && n_cand && num_dets && out_boxes && out_scores && out_labels,
+                    AIC_ERR_INVALID, "NULL argument");
+        Model& m = mm->m;
+        AIC_REQUIRE(m.kind == KIND_YOLO, AIC_ERR_INVALID, "not a YOLO engine");
+        AIC_REQUIRE(batch > 0, AIC_ERR_INVALID, "batch must be positive");
+        AIC_REQUIRE(batch <= m.max_items, AIC_ERR_CAPACITY, "batch exceeds the engine's max_items");
+        AIC_REQUIRE(iou >= 0.f && iou <= 1.f, AIC_ERR_INVALID, "iou_thresh must be in [0,1]");
+        AIC_REQUIRE(!use_geom || (out_boxes_orig && ratio > 0.f && orig_w > 0 && orig_h > 0), AIC_ERR_INVALID, "bad letterbox geometry");
+        m.dev->use();
+        hipStream_t s = m.dev->s_main;
+        LetterboxGeom g{};
+        g.pad_w = pad_w, g.pad_h = pad_h, g.ratio = ratio, g.src_w = orig_w, g.src_h = orig_h;
+        // decode_kernel does everything itself for this call: no detect-branch tail has run on these logits
+        const unsigned keep_cls = m.cls_reduced, keep_box = m.box_decoded;
+        m.cls_reduced = m.box_decoded = 0;
+        DetArgs a;
+        try {
+            a = m.det_args(batch, conf, iou, max_det, use_geom ? &g : nullptr);       // (refuses max_det / conf out of range)
+        } catch (...) {
+            m.cls_reduced = keep_cls, m.box_decoded = keep_box;
+            throw;
+        }
+        m.cls_reduced = keep_cls, m.box_decoded = keep_box;
+        // the inverse of aic_yolo_head's copies: level-major host logits -> the model's own per-level head buffers
+        const int nc = m.meta[0], nb = 4 * m.meta[1];
+        int a0 = 0;
+        for (auto& o : m.outs) {
+            const int hw = o.v[3] * o.v[4];
+            const BufDesc& bb = m.bufs[o.v[0]];
+            const BufDesc& cb = m.bufs[o.v[1]];
+            AIC_REQUIRE(bb.p && cb.p && bb.esize == 4 && cb.esize == 4, AIC_ERR_FORMAT, "head buffers are not fp32");
+            for (int b = 0; b < batch; ++b) {
+                HIP_CHECK(hipMemcpyAsync(reinterpret_cast<float*>(bb.p) + (size_t)b * hw * nb, dfl + ((size_t)b * m.n_anchors + a0) * nb,
+                                         (size_t)hw * nb * 4, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(reinterpret_cast<float*>(cb.p) + (size_t)b * hw * nc, cls + ((size_t)b * m.n_anchors + a0) * nc,
+                                         (size_t)hw * nc * 4, hipMemcpyHostToDevice, s));
+            }
+            a0 += hw;
+        }
+        // in/out: what the caller put into the output arrays is on the device before the kernels run
+        const size_t ba = (size_t)batch * m.n_anchors, bm = (size_t)batch * max_det;
+        const struct { void* host; void* dev; size_t bytes; } io[] = {
+            {boxes, a.boxes, ba * 16}, {max_logit, a.max_logit, ba * 4}, {labels, a.labels, ba * 4}, {n_cand, a.n_cand, (size_t)batch * 4},
+            {num_dets, a.num_dets, (size_t)batch * 4}, {out_boxes, a.out_boxes, bm * 16}, {out_boxes_orig, a.out_boxes_orig, bm * 16},
+            {out_scores, a.out_scores, bm * 4}, {out_labels, a.out_labels, bm * 4}};
+        for (const auto& e : io)
+            if (e.host && e.dev) HIP_CHECK(hipMemcpyAsync(e.dev, e.host, e.bytes, hipMemcpyHostToDevice, s));
+        launch_decode(a, s);
+        launch_select_sort_nms(a, s);
+        for (const auto& e : io)
+            if (e.host && e.dev) HIP_CHECK(hipMemcpyAsync(e.host, e.dev, e.bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int aic_det_filter(int device_id, const int32_t* num_dets, const float* boxes, const float* scores, const int32_t* labels, int batch,
+                   int max_det, float min_conf, const uint64_t* mask, int cap, int32_t* rank, int32_t* frame_n, int32_t* frame_d0,
+                   int32_t* total, float* xyxy, float* tlwh, float* conf, int32_t* cls, int32_t* frame_of) {
+    return guarded([&] {
+        AIC_REQUIRE(num_dets && boxes && scores && labels && mask && rank && frame_n && frame_d0 && total && xyxy && tlwh && conf && cls &&
+                    frame_of, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(batch > 0 && max_det > 0 && cap > 0, AIC_ERR_INVALID, "batch, max_det and cap must be positive");
+        AIC_REQUIRE((size_t)batch * max_det <= ((size_t)1 << 28), AIC_ERR_CAPACITY, "batch * max_det too large");
+        Device& d = device(device_id);
+        hipStream_t s = d.s_main;
+        const size_t bm = (size_t)batch * max_det;
+        DevBuf<int> d_nd(batch), d_lab(bm), d_rank(bm), d_fn(batch), d_fd0(batch), d_total(2), d_cls(cap), d_fof(cap);
+        DevBuf<float> d_box(bm * 4), d_sc(bm), d_xyxy((size_t)cap * 4), d_tlwh((size_t)cap * 4), d_conf(cap);
+        const struct { void* host; void* dev; size_t bytes; bool out; } io[] = {
+            {const_cast<int32_t*>(num_dets), d_nd.p, (size_t)batch * 4, false}, {const_cast<float*>(boxes), d_box.p, bm * 16, false},
+            {const_cast<float*>(scores), d_sc.p, bm * 4, false}, {const_cast<int32_t*>(labels), d_lab.p, bm * 4, false},
+            {rank, d_rank.p, bm * 4, true}, {frame_n, d_fn.p, (size_t)batch * 4, true}, {frame_d0, d_fd0.p, (size_t)batch * 4, true},
+            {total, d_total.p, 8, true}, {xyxy, d_xyxy.p, (size_t)cap * 16, true}, {tlwh, d_tlwh.p, (size_t)cap * 16, true},
+            {conf, d_conf.p, (size_t)cap * 4, true}, {cls, d_cls.p, (size_t)cap * 4, true}, {frame_of, d_fof.p, (size_t)cap * 4, true}};
+        for (const auto& e : io) HIP_CHECK(hipMemcpyAsync(e.dev, e.host, e.bytes, hipMemcpyHostToDevice, s));
+        DetFilterArgs fa{};
+        fa.num_dets = d_nd.p, fa.boxes = d_box.p, fa.scores = d_sc.p, fa.labels = d_lab.p;
+        fa.batch = batch, fa.max_det = max_det, fa.min_conf = min_conf;
+        fa.mask[0] = mask[0], fa.mask[1] = mask[1];
+        fa.cap = cap, fa.rank = d_rank.p, fa.frame_n = d_fn.p, fa.frame_d0 = d_fd0.p, fa.total = d_total.p;
+        fa.xyxy = d_xyxy.p, fa.tlwh = d_tlwh.p, fa.conf = d_conf.p, fa.cls = d_cls.p, fa.frame_of = d_fof.p;
+        launch_det_filter(fa, s);
+        for (const auto& e : io)
+            if (e.out) HIP_CHECK(hipMemcpyAsync(e.host, e.dev, e.bytes, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
     });
 }

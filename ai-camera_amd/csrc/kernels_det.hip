@@ -95,7 +95,8 @@ __global__ void decode_kernel(const DetArgs a) {
 }
 
 __device__ __forceinline__ unsigned int ordered_bits(float f) {
-    const unsigned int u = __float_as_uint(f);
+    unsigned int u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;                        // -0.0 == +0.0: the two zeros tie and the anchor index decides (nets_oracle.nms)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone map float -> uint
 }
 

@@ -120,6 +120,51 @@ class HipEngine:
         L.call("aic_yolo_decode", self._h, L.ptr(x), b, L.HOST, L.ptr(boxes), L.ptr(ml), L.ptr(lab))
         return boxes, ml, lab
 
+    def yolo_postprocess_np(self, dfl_logits, cls_logits, conf=None, iou=None, max_det=None, geom=None, sentinel=None):
+        """decode + select + sort + NMS (+ un-letterbox) on head logits the caller supplies (aic_yolo_postprocess, include/aicam.h):
+        no conv runs.  geom: None or (pad_w, pad_h, ratio, orig_w, orig_h).  sentinel: None, or (float value, int value) every output
+        array is prefilled with -- an element that still holds it was not written.  Returns a dict of the nine output arrays."""
+        dfl, cls = L.as_f32(dfl_logits), L.as_f32(cls_logits)
+        with open(self.engine_path, "rb") as fh:
+            reg_max = int(np.frombuffer(fh.read(68), "<i4")[10])          # meta[1] of the engine file's header
+        b, a = cls.shape[0], self.n_anchors
+        if dfl.shape != (b, a, 4 * reg_max) or cls.shape != (b, a, self.out_dim):
+            raise ValueError(f"head logits {dfl.shape} / {cls.shape} do not fit an engine of {a} anchors, reg_max {reg_max}, {self.out_dim} classes")
+        md = int(max_det or self.max_det)
+        fs, is_ = sentinel if sentinel is not None else (0.0, 0)
+        f = lambda *s: np.full(s, fs, np.float32)            # noqa: E731
+        i = lambda *s: np.full(s, is_, np.int32)             # noqa: E731
+        m = max(md, 1)
+        r = dict(boxes=f(b, a, 4), max_logit=f(b, a), labels=i(b, a), n_cand=i(b), num_dets=i(b), out_boxes=f(b, m, 4),
+                 out_boxes_orig=f(b, m, 4), out_scores=f(b, m), out_labels=i(b, m))
+        g = geom if geom is not None else (0.0, 0.0, 1.0, 0, 0)
+        L.call("aic_yolo_postprocess", self._h, L.ptr(dfl), L.ptr(cls), b, float(conf if conf is not None else self.conf_thresh),
+               float(iou if iou is not None else self.iou_thresh), md, int(geom is not None), float(g[0]), float(g[1]), float(g[2]),
+               int(g[3]), int(g[4]), *(L.ptr(r[k]) for k in ("boxes", "max_logit", "labels", "n_cand", "num_dets", "out_boxes",
+                                                              "out_boxes_orig", "out_scores", "out_labels")))
+        return r
+
+    @staticmethod
+    def det_filter_np(num_dets, boxes, scores, labels, min_conf, mask, cap, device=0, sentinel=None):
+        """The pipeline's on-device detection filter on host arrays (aic_det_filter, include/aicam.h).  boxes [B, max_det, 4], scores /
+        labels [B, max_det], mask: two 64-bit words, bit c = class c is tracked.  sentinel as in yolo_postprocess_np.  Returns a dict
+        of rank, frame_n, frame_d0, total and the compact xyxy, tlwh, conf, cls, frame_of."""
+        nd = np.ascontiguousarray(num_dets, np.int32)
+        bx, sc, lb = L.as_f32(boxes), L.as_f32(scores), np.ascontiguousarray(labels, np.int32)
+        b, md = sc.shape
+        if nd.shape != (b,) or bx.shape != (b, md, 4) or lb.shape != (b, md):
+            raise ValueError(f"det_filter_np: shapes {nd.shape} {bx.shape} {sc.shape} {lb.shape} do not agree")
+        cap = int(cap)
+        fs, is_ = sentinel if sentinel is not None else (0.0, 0)
+        c = max(cap, 1)
+        r = dict(rank=np.full((b, md), is_, np.int32), frame_n=np.full(b, is_, np.int32), frame_d0=np.full(b, is_, np.int32),
+                 total=np.full(2, is_, np.int32), xyxy=np.full((c, 4), fs, np.float32), tlwh=np.full((c, 4), fs, np.float32),
+                 conf=np.full(c, fs, np.float32), cls=np.full(c, is_, np.int32), frame_of=np.full(c, is_, np.int32))
+        mk = np.array([int(mask[0]) & (2 ** 64 - 1), int(mask[1]) & (2 ** 64 - 1)], np.uint64)
+        L.call("aic_det_filter", int(device), L.ptr(nd), L.ptr(bx), L.ptr(sc), L.ptr(lb), b, md, float(min_conf), L.ptr(mk), cap,
+               *(L.ptr(r[k]) for k in ("rank", "frame_n", "frame_d0", "total", "xyxy", "tlwh", "conf", "cls", "frame_of")))
+        return r
+
     def reid_infer_np(self, crops_nchw):
         x = L.as_f32(crops_nchw)
         n = x.shape[0]

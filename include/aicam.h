@@ -101,6 +101,27 @@ int aic_yolo_head(aic_model* m, const float* images_nchw, int batch, int mem, fl
 int aic_yolo_decode(aic_model* m, const float* images_nchw, int batch, int mem, float* boxes,
                     float* max_logit, int32_t* labels);
 
+/* Tests / diagnostics: the post-processing of aic_yolo_infer / aic_detect alone, on head logits the caller supplies (the layout
+ * aic_yolo_head returns: dfl_logits[B,A,4*reg_max], cls_logits[B,A,nc], host).  No conv runs: the logits are copied into the engine's
+ * own head buffers and the production decode and select + sort + NMS launches run on them with the production arguments; the decode
+ * kernel does the whole decode (no detect-branch tail has seen these logits).  use_geom != 0: the kept boxes are also un-letterboxed
+ * (image_processing.py:141-183) with pad_w, pad_h, ratio into an orig_w x orig_h frame.  Every output is IN/OUT host memory: its
+ * contents are uploaded before the kernels run, so a caller that prefills a sentinel sees which elements the kernels wrote.
+ * boxes[B,A,4], max_logit[B,A], labels[B,A], n_cand[B], num_dets[B], out_boxes[B,max_det,4], out_boxes_orig[B,max_det,4] (may be
+ * NULL when use_geom == 0, and is left alone then), out_scores[B,max_det], out_labels[B,max_det]. */
+int aic_yolo_postprocess(aic_model* m, const float* dfl_logits, const float* cls_logits, int batch, float conf_thresh,
+                         float iou_thresh, int max_det, int use_geom, float pad_w, float pad_h, float ratio, int orig_w,
+                         int orig_h, float* boxes, float* max_logit, int32_t* labels, int32_t* n_cand, int32_t* num_dets,
+                         float* out_boxes, float* out_boxes_orig, float* out_scores, int32_t* out_labels);
+/* Tests / diagnostics: the pipeline's on-device detection filter (deepsort_tracker.py:88-101: conf >= min_conf and a tracked class,
+ * in order) on host arrays.  Inputs num_dets[B], boxes[B,max_det,4], scores[B,max_det], labels[B,max_det]; mask[2]: bit c = class c
+ * is tracked.  IN/OUT (uploaded first, as above): rank[B,max_det], frame_n[B], frame_d0[B], total[2] (rows present <= cap, rows the
+ * filter passed), and the compact xyxy[cap,4], tlwh[cap,4], conf[cap], cls[cap], frame_of[cap]. */
+int aic_det_filter(int device, const int32_t* num_dets, const float* boxes, const float* scores, const int32_t* labels,
+                   int batch, int max_det, float min_conf, const uint64_t* mask, int cap, int32_t* rank, int32_t* frame_n,
+                   int32_t* frame_d0, int32_t* total, float* xyxy, float* tlwh, float* conf, int32_t* cls,
+                   int32_t* frame_of);
+
 /* TRTEngine.infer for the ReID engine (src/tracker/reid_model.py:111-126): crops fp32 NCHW,
  * ImageNet-normalised -> embeddings[N, feature_dim] fp32. */
 int aic_reid_infer(aic_model* m, const float* crops_nchw, int n, int mem, float* embeddings,

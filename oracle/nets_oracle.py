@@ -109,31 +109,44 @@ class EngineOracle:
             cls.append(bufs[cls_b].permute(0, 2, 3, 1).flatten(1, 2))
         return torch.cat(dfl, 1), torch.cat(cls, 1)
 
+    def levels(self):
+        """[(stride, h, w)] of the detect levels, in anchor order."""
+        return [(s, h, w) for _, _, s, h, w, *_ in self.outputs]
+
     def anchors(self):
-        pts, strides = [], []
-        for _, _, s, h, w, *_ in self.outputs:
-            ys, xs = np.meshgrid(np.arange(h, dtype=np.float32) + 0.5, np.arange(w, dtype=np.float32) + 0.5,
-                                 indexing="ij")
-            pts.append(np.stack([xs.ravel(), ys.ravel()], 1))
-            strides.append(np.full(h * w, s, np.float32))
-        return np.concatenate(pts), np.concatenate(strides)
+        return level_anchors(self.levels())
 
     def decode(self, dfl_logits, cls_logits, ft=np.float32):
         """numpy fp32 (ft=np.float64: the double-precision anchor): boxes [N,A,4] xyxy (letterbox px), max logit [N,A], label [N,A]."""
-        nc, reg_max = self.meta[0], self.meta[1]
-        d = np.asarray(dfl_logits, ft)
-        n, a, _ = d.shape
-        d = d.reshape(n, a, 4, reg_max)
-        e = np.exp(d - d.max(-1, keepdims=True)).astype(ft)
-        p = e / e.sum(-1, keepdims=True, dtype=ft)
-        dist = (p * np.arange(reg_max, dtype=ft)).sum(-1, dtype=ft)      # l t r b
-        pts, st = self.anchors()
-        x1 = (pts[:, 0] - dist[..., 0]) * st
-        y1 = (pts[:, 1] - dist[..., 1]) * st
-        x2 = (pts[:, 0] + dist[..., 2]) * st
-        y2 = (pts[:, 1] + dist[..., 3]) * st
-        c = np.asarray(cls_logits, ft)
-        return np.stack([x1, y1, x2, y2], -1).astype(ft), c.max(-1), c.argmax(-1).astype(np.int32)
+        return decode_head(self.levels(), self.meta[1], dfl_logits, cls_logits, ft)
+
+
+def level_anchors(levels):
+    """levels: [(stride, h, w)].  -> (anchor centres [A,2] in cells (i + 0.5), strides [A]); anchors level-major, row-major."""
+    pts, strides = [], []
+    for s, h, w in levels:
+        ys, xs = np.meshgrid(np.arange(h, dtype=np.float32) + 0.5, np.arange(w, dtype=np.float32) + 0.5,
+                             indexing="ij")
+        pts.append(np.stack([xs.ravel(), ys.ravel()], 1))
+        strides.append(np.full(h * w, s, np.float32))
+    return np.concatenate(pts), np.concatenate(strides)
+
+
+def decode_head(levels, reg_max, dfl_logits, cls_logits, ft=np.float32):
+    """EngineOracle.decode on a level table: no engine file needed."""
+    d = np.asarray(dfl_logits, ft)
+    n, a, _ = d.shape
+    d = d.reshape(n, a, 4, reg_max)
+    e = np.exp(d - d.max(-1, keepdims=True)).astype(ft)
+    p = e / e.sum(-1, keepdims=True, dtype=ft)
+    dist = (p * np.arange(reg_max, dtype=ft)).sum(-1, dtype=ft)      # l t r b
+    pts, st = level_anchors(levels)
+    x1 = (pts[:, 0] - dist[..., 0]) * st
+    y1 = (pts[:, 1] - dist[..., 1]) * st
+    x2 = (pts[:, 0] + dist[..., 2]) * st
+    y2 = (pts[:, 1] + dist[..., 3]) * st
+    c = np.asarray(cls_logits, ft)
+    return np.stack([x1, y1, x2, y2], -1).astype(ft), c.max(-1), c.argmax(-1).astype(np.int32)
 
 
 def logit_threshold(conf: float) -> np.float32:
