@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "gmc", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
@@ -26,4 +26,6 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.ocsort").OCSort
     if name == "BoTSORT":
         return _importlib.import_module(f"{__name__}.botsort").BoTSORT
+    if name == "CameraMotion":
+        return _importlib.import_module(f"{__name__}.gmc").CameraMotion
     raise AttributeError(name)

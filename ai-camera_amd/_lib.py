@@ -55,6 +55,10 @@ class BoTSORTParams(C.Structure):
                 ("with_reid", C.c_int32), ("feature_dim", C.c_int32), ("max_tracks", C.c_int32), ("first_track_id", C.c_int32)]
 
 
+class GmcParams(C.Structure):
+    _fields_ = [("downscale", C.c_int32), ("min_inliers", C.c_int32)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -171,6 +175,11 @@ _SIGS = {
     "aic_botsort_export": (_I, [_P, _I] + [_P] * 13),
     "aic_botsort_counters": (_I, [_P] * 7),
     "aic_pipeline_create_botsort": (_I, [_P, _P, _P, _P, _P]),
+    "aic_gmc_create": (_I, [_I, _I, _I, _P, _P]),
+    "aic_gmc_destroy": (_I, [_P]),
+    "aic_gmc_reset": (_I, [_P]),
+    "aic_gmc_estimate_batch": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "aic_pipeline_group_warps": (_I, [_P, _P, _I, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

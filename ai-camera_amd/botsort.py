@@ -3,7 +3,8 @@
 ByteTrack's score bands and life cycle, a Kalman filter on [cx, cy, w, h], one exponentially smoothed appearance vector per track and
 a first association on min(IoU distance, gated cosine distance / 2).  The recurrence runs in csrc/kernels_botsort.hip (k frames per
 launch, the track table and the smoothed features resident in HBM); its specification is tests/botsort_oracle.py, the deliberate
-changes from upstream are listed there and in DESIGN.md section 18.  Camera motion is an input (`warp`), never estimated here.
+changes from upstream are listed there and in DESIGN.md section 18.  Camera motion is an input (`warp`); gmc.CameraMotion estimates
+it on the device, and a BoT-SORT pipeline does so itself with gmc=2 or 4.
 """
 from __future__ import annotations
 

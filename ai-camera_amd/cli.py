@@ -51,10 +51,15 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1, with ocsort its det_thresh 0.6, with botsort its track_low_thresh 0.1)")
     p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort", "botsort"),
                    help="bytetrack / ocsort: no ReID model, the tracker's association on the device; botsort: IoU + ReID fusion on the device")
+    p.add_argument("--gmc", type=int, default=0, choices=(0, 2, 4),
+                   help="botsort only: estimate the camera motion on the device at this downscale and warp the predicted tracks (0 = off)")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.gmc and args.tracker != "botsort":
+        p.error("--gmc needs --tracker botsort")
+    return args
 
 
 def frame_source(spec, webcam_id=0, cv2=None):
@@ -159,12 +164,16 @@ class _BotSortFrame:
     """The loop's tracker call with BoT-SORT: the boxes of tracked classes above the low band are embedded from the frame (ReIDModel, as
     DeepSORT.update does) and handed to BoTSORT with their validity."""
 
-    def __init__(self, reid_engine, device, dtype):
+    def __init__(self, reid_engine, device, dtype, gmc=0, frame_hw=None):
         from .botsort import BoTSORT
         from .reid_model import ReIDModel
         self.reid_model = ReIDModel(engine_path=reid_engine, input_shape=config.REID_INPUT_SHAPE, device=device, dtype=dtype)
         self.tracker = BoTSORT(device=device, feature_dim=self.reid_model.feature_dim)
         self.low = np.float32(self.tracker.params.track_low_thresh)
+        self.gmc = None
+        if gmc:
+            from .gmc import CameraMotion
+            self.gmc = CameraMotion(frame_hw[0], frame_hw[1], downscale=gmc, device=device)
 
     def update(self, boxes, scores, class_ids, frame):
         b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
@@ -172,10 +181,14 @@ class _BotSortFrame:
         k = np.asarray(class_ids).reshape(-1).astype(np.int64)
         names = np.array([config.class_name(int(c)) in config.CLASSES_TO_TRACK for c in k], dtype=bool)
         keep = np.nonzero((s > self.low) & names)[0]
+        warp = None
+        if self.gmc is not None:                 # the boxes as the tracker holds them (tlwh): x2 = x + w in fp32, as the pipeline's masks
+            m = b[keep]
+            warp = self.gmc.apply(frame, np.stack([m[:, 0], m[:, 1], m[:, 0] + (m[:, 2] - m[:, 0]), m[:, 1] + (m[:, 3] - m[:, 1])], 1))
         if not len(keep):
-            return self.tracker.update(np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32))
+            return self.tracker.update(np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32), warp=warp)
         feats, valid = self.reid_model.embed_boxes(frame, b[keep])
-        rows, conf = self.tracker.update_batch_arrays([(b[keep], s[keep], k[keep].astype(np.int32), feats, None,
+        rows, conf = self.tracker.update_batch_arrays([(b[keep], s[keep], k[keep].astype(np.int32), feats, warp,
                                                         np.asarray(valid).astype(np.int32))])[0]
         return self.tracker._tuples(rows, conf)
 
@@ -203,7 +216,7 @@ def main(argv=None):
             reid = None if bytetrack or ocsort else HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
             pipe = TrackingPipeline(args.yolo_engine, reid, (size[1], size[0]), batch=args.batch, ring_frames=args.batch,
                                     max_persons=512, max_tracks=512, device=dev_id, dtype=args.dtype, conf_thresh=args.conf_thresh,
-                                    tracker=args.tracker)
+                                    tracker=args.tracker, gmc=args.gmc)
         else:
             detector = YOLODetector(engine_path=args.yolo_engine, conf_threshold=args.conf_thresh, device=args.device, dtype=args.dtype)
     except Exception as e:   # aicamera_tracker.py:94-97
@@ -220,7 +233,7 @@ def main(argv=None):
     elif pipe is None and botsort:
         print("Initializing BoT-SORT Tracker...")
         try:
-            tracker = _BotSortFrame(args.reid_engine, args.device, args.dtype)
+            tracker = _BotSortFrame(args.reid_engine, args.device, args.dtype, gmc=args.gmc, frame_hw=(size[1], size[0]))
         except Exception as e:
             print(f"Error initializing BoT-SORT Tracker: {e}")
             return 1

@@ -17,6 +17,7 @@
 #include "bytetrack_host.hpp"
 #include "ocsort_host.hpp"
 #include "botsort_host.hpp"
+#include "gmc.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -67,6 +68,7 @@ struct Chunk {
     DevBuf<int> d_rank, d_fn, d_fd0, d_total, d_fcls;
     DevBuf<float> d_ftlwh, d_fconf;
     PinBuf<int> h_fn, h_fd0, h_total;
+    DevBuf<uint8_t> d_gray;          // option "gmc": the gray levels of the group's frames (stage A), read by stage B
     std::vector<FrameDets> dets;
     hipEvent_t done = nullptr, ev_yolo = nullptr, ev_det = nullptr, ev_reid = nullptr, ev_extra = nullptr;
     hipEvent_t t_begin = nullptr, t_end = nullptr, t_yolo = nullptr;   // AICAM_PIPE_TIMES: GPU timeline of the group on the main stream
@@ -193,6 +195,8 @@ struct Pipeline {
     std::string bt_name() const { return bt->name(); }
     bool bs = false;                // the epoch tracker is BoT-SORT
     float bs_low = 0.f;             // its track_low_thresh: inject = 0 hands over the detections with score > bs_low
+    // aic_pipeline_option("gmc"): camera motion per frame, estimated on the device and handed to the BoT-SORT epochs; NULL = off
+    std::unique_ptr<CameraMotionEstimator> gmc;
 
     static aic_tracker_params tracker_params(const aic_pipeline_params& p, bool bytetrack) {
         if (!bytetrack) return p.tracker;
@@ -338,6 +342,10 @@ struct Pipeline {
         if (pipe_times) HIP_CHECK(hipEventRecord(c.t_begin, s));
         c.ln->yolo->reduce_cls = true;           // the pipeline only ever decodes: the class tails store max logit + label themselves
         c.ln->yolo->run_frames(f0, frames, geom, s);
+        if (gmc) {                               // the group's gray levels, while its ring slots are this group's (this context is idle)
+            c.d_gray.ensure((size_t)frames * gmc->g.level);
+            launch_gmc_gray(f0, frames, gmc->g, c.d_gray.p, s);
+        }
         // decode + NMS + read-back on the side stream: a few latency-bound blocks that overlap the
         // (CU-filling) ReID launch group instead of serialising the main stream
         hipStream_t sd = c.ln->s_det;
@@ -749,6 +757,10 @@ struct Pipeline {
         if (reid && c.n_crops) dets.valid = c.d_valid.p, dets.feat = c.d_emb.p, dets.feat_n = c.d_emb_n.p;   // BoT-SORT: the group's embeddings, in HBM
         EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
                      mp, nullptr, nullptr, 0};
+        if (gmc) {                               // block matching under the detections handed to the tracker, fit, warps -> the epochs
+            gmc->match_fit(c.d_gray.p, c.frames, dets.frame_n, dets.frame_d0, dets.tlwh, true, s);
+            static_cast<BotSortTracker*>(bt.get())->warps = gmc->d_warps.p;
+        }
         bt->run_epochs(dets, c.frames, out, s);
         HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
         const double t1 = now();
@@ -1206,6 +1218,29 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
             AIC_REQUIRE(value >= 0 && value <= p->p.prm.batch, AIC_ERR_INVALID, "group_frames must be in 0..batch");
             p->p.group_frames = value;
         }
+        else if (k == "epoch_frames") {              // frames per BoT-SORT epoch launch, as aic_botsort_option (same results either way)
+            AIC_REQUIRE(p->p.bs, AIC_ERR_INVALID, "option epoch_frames applies to BoT-SORT pipelines only");
+            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
+            static_cast<BotSortTracker*>(p->p.bt.get())->epoch_frames = value;
+        }
+        else if (k == "gmc") {
+            AIC_REQUIRE(p->p.bs, AIC_ERR_INVALID, "option gmc applies to BoT-SORT pipelines only");
+            AIC_REQUIRE(value == 0 || value == 2 || value == 4, AIC_ERR_INVALID, "gmc: 0 off, 2 or 4 = downscale of the camera-motion estimate");
+            Pipeline& q = p->p;
+            if (value == 0 ? q.gmc != nullptr : (!q.gmc || q.gmc->g.s != value)) {
+                const GmcGeom g = gmc_geom(q.prm.frame_h, q.prm.frame_w, value ? value : 4);
+                AIC_REQUIRE(value == 0 || (g.nb >= 1 && g.nb <= GMC_MAX_BLOCKS), AIC_ERR_INVALID,
+                            "gmc: the frame holds no block, or more than 2048, at this downscale");
+                q.dev->use();
+                HIP_CHECK(hipDeviceSynchronize());
+                static_cast<BotSortTracker*>(q.bt.get())->warps = nullptr;   // (it pointed into the estimator that goes away)
+                q.gmc.reset();
+                if (value) {
+                    q.gmc.reset(new CameraMotionEstimator(*q.dev, q.prm.frame_h, q.prm.frame_w, value, 8));
+                    q.gmc->ensure(q.prm.batch);      // sized once for the largest launch group: stage B never reallocates
+                }
+            }
+        }
         else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown pipeline option: " + k);
     });
 }
@@ -1260,6 +1295,20 @@ int aic_pipeline_group_embeddings(aic_pipeline* p, float* emb, int cap_rows, int
             AIC_REQUIRE(c.n_crops <= cap_rows, AIC_ERR_CAPACITY, "embedding capacity too small");
             q.dev->use();
             HIP_CHECK(hipMemcpy(emb, c.d_emb.p, (size_t)c.n_crops * q.dim * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int aic_pipeline_group_warps(aic_pipeline* p, float* warps, int cap_frames, int32_t* n_frames) {
+    return guarded([&] {
+        AIC_REQUIRE(p && n_frames && cap_frames >= 0, AIC_ERR_INVALID, "bad argument");
+        Pipeline& q = p->p;
+        AIC_REQUIRE(q.gmc, AIC_ERR_INVALID, "the pipeline estimates no camera motion (option gmc)");
+        *n_frames = q.gmc->last_frames;
+        const int n = std::min(q.gmc->last_frames, cap_frames);
+        if (warps && n) {
+            q.dev->use();
+            HIP_CHECK(hipMemcpy(warps, q.gmc->d_warps.p, (size_t)n * 24, hipMemcpyDeviceToHost));
         }
     });
 }

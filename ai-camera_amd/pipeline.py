@@ -19,7 +19,7 @@ class TrackingPipeline:
                  max_det=config.YOLO_MAX_DET, min_confidence=config.DEEPSORT_MIN_CONFIDENCE, inject=False,
                  max_cosine_distance=config.DEEPSORT_MAX_DIST, nn_budget=config.DEEPSORT_NN_BUDGET,
                  max_iou_distance=config.DEEPSORT_MAX_IOU_DISTANCE, max_age=config.DEEPSORT_MAX_AGE,
-                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", **bytetrack_params):
+                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, **bytetrack_params):
         """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
         not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
         conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
@@ -29,7 +29,10 @@ class TrackingPipeline:
         tracker="botsort": BoT-SORT WITH the ReID engine (aic_pipeline_create_botsort): crop + ReID as for DeepSORT, the embeddings stay
         in HBM and feed the epoch kernel; the extra arguments are BoTSORT's (track_high_thresh, track_low_thresh, new_track_thresh,
         match_thresh, proximity_thresh, appearance_thresh, track_buffer, frame_rate, fuse_score, with_reid, feat_alpha), and conf_thresh
-        defaults to track_low_thresh."""
+        defaults to track_low_thresh.  gmc=2 or 4 (BoT-SORT only): the camera motion of every frame is estimated on the device at that
+        downscale (aic_pipeline_option "gmc", gmc.py) and warps the predicted tracks; group_warps() reads the last group's."""
+        if gmc and tracker != "botsort":
+            raise ValueError("gmc needs tracker='botsort'")
         if tracker not in ("deepsort", "bytetrack", "ocsort", "botsort"):
             raise ValueError(f"tracker must be 'deepsort', 'bytetrack', 'ocsort' or 'botsort', not {tracker!r}")
         if tracker == "deepsort" and bytetrack_params:
@@ -88,6 +91,8 @@ class TrackingPipeline:
             L.call("aic_pipeline_create_botsort", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self.botsort_params),
                    C.byref(self._h))
             self.tracker_core = None
+            if gmc:
+                self.option("gmc", int(gmc))
             return
         if conf_thresh is None:
             conf_thresh = config.YOLO_CONF_THRESHOLD
@@ -121,6 +126,14 @@ class TrackingPipeline:
             self.close()
         except Exception:
             pass
+
+    def group_warps(self):
+        """float32 [frames, 2, 3]: the camera-motion warps of the most recently finished launch group (gmc pipelines)."""
+        n = C.c_int32()
+        L.call("aic_pipeline_group_warps", self._h, None, 0, C.byref(n))
+        w = np.zeros((n.value, 2, 3), np.float32)
+        L.call("aic_pipeline_group_warps", self._h, L.ptr(w), n.value, C.byref(n))
+        return w
 
     def upload(self, slot, frames_bgr):
         f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)

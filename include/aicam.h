@@ -53,6 +53,7 @@ typedef struct aic_tracker aic_tracker;   /* DeepSORT core state of one video st
 typedef struct aic_pipeline aic_pipeline; /* detector + ReID + tracker over resident frames */
 typedef struct aic_bytetrack aic_bytetrack; /* ByteTrack state of one video stream          */
 typedef struct aic_botsort aic_botsort;     /* BoT-SORT state of one video stream           */
+typedef struct aic_gmc aic_gmc;             /* camera-motion estimator of one video stream  */
 typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream            */
 
 /* ------------------------------------------------------------------ library / device */
@@ -366,7 +367,8 @@ int aic_ocsort_counters(aic_ocsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t
  * BoTSORT.update() with ReID of the BoT-SORT authors (tracker/bot_sort.py, matching.py, kalman_filter.py) on the device, k frames per
  * launch (csrc/kernels_botsort.hip; specification: tests/botsort_oracle.py, deviations: DESIGN.md section 18): ByteTrack's bands and life
  * cycle, a Kalman filter on [cx, cy, w, h], one exponentially smoothed appearance vector per track, and a first association on
- * min(IoU distance, gated cosine distance / 2).  Camera motion is an input (a 2x3 affine per frame), never estimated here.
+ * min(IoU distance, gated cosine distance / 2).  Camera motion is an input (a 2x3 affine per frame): aic_gmc_estimate_batch below
+ * estimates it on the device, and a BoT-SORT pipeline does so itself with the option "gmc".
  * Defaults are upstream's; every threshold is rounded to fp32 once. */
 typedef struct aic_botsort_params {
     double track_high_thresh; /* 0.6: high band s > track_high_thresh (only these detections carry a feature)     */
@@ -408,6 +410,31 @@ int aic_botsort_export(aic_botsort* t, int cap, int32_t* track_id, int32_t* stat
 int aic_botsort_counters(aic_botsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_appearance,
                          int64_t* cost_cycles, int64_t* kernel_cycles);
 
+/* ------------------------------------------------------------------ camera motion
+ * The 2x3 affine of the camera motion between consecutive frames (previous-frame pixel coordinates -> current-frame ones, the `warps` of
+ * aic_botsort_update_batch), estimated on the device (csrc/kernels_gmc.hip; specification: tests/gmc_oracle.py):
+ * a gray pyramid level, integer block matching (16 x 16 blocks, +-8 gray pixels, SAD) with an integer sub-pixel step, and a robust
+ * least-squares similarity from exact integer sums.  Deterministic: equal inputs give equal bits.  Working range per frame: a
+ * translation below 8 * downscale pixels, about 1.4 degrees of rotation or 2.5 % of zoom; beyond it the identity is returned. */
+typedef struct aic_gmc_params {
+    int32_t downscale;   /* 2 or 4 (0 -> 4): frame pixels per gray pixel and side */
+    int32_t min_inliers; /* 0 -> 8: fewer agreeing blocks give the identity       */
+} aic_gmc_params;
+
+/* AIC_ERR_INVALID for a downscale other than 0, 2, 4, a negative min_inliers, a frame smaller than one block plus its search margin
+ * (32 * downscale pixels a side) or one with more than 2048 blocks (checked before the device). */
+int aic_gmc_create(int device, int height, int width, const aic_gmc_params* p, aic_gmc** out);
+int aic_gmc_destroy(aic_gmc* g);
+/* Forget the previous frame: the next frame is a stream's first. */
+int aic_gmc_reset(aic_gmc* g);
+/* k consecutive u8 BGR frames [k, height, width, 3] in host or device memory (mem: AIC_HOST / AIC_DEVICE).  Frame f takes frame f - 1
+ * of the call as its predecessor, frame 0 the last frame of the call before.  counts[k] and boxes_xyxy[sum, 4] (host memory; both may be
+ * NULL) are the detection boxes of each frame: blocks under them are left out.  warps_out[k, 6] (r00 r01 t0 r10 r11 t1) and
+ * stats_out[k, 4] (ok, blocks, blocks that entered the fit, inliers of the last fit) are host memory; either may be NULL.  A stream's
+ * first frame, and a frame whose motion could not be estimated, get the identity and ok = 0. */
+int aic_gmc_estimate_batch(aic_gmc* g, const uint8_t* frames_bgr, int k, int mem, const int32_t* counts, const float* boxes_xyxy,
+                           float* warps_out, int32_t* stats_out);
+
 /* ------------------------------------------------------------------ end-to-end pipeline
  * The loop body of src/aicamera_tracker.py:169-207 (detect + track, the reference's own FPS
  * span) over frames that are already resident in HBM, batched: detection and ReID of
@@ -445,7 +472,8 @@ int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, co
 /* BoT-SORT as the pipeline's tracker, WITH the ReID engine: stage A as for DeepSORT with the host detection filter (crop + ReID for every
  * detection handed to the tracker; the embeddings stay in HBM and reach the epoch kernel directly), stage B as on a ByteTrack pipeline.
  * inject = 0 hands over the detections of a tracked class with score > track_low_thresh (min_confidence and p->tracker are ignored, so
- * conf_thresh should be at most track_low_thresh).  No camera-motion warp.  bp->feature_dim must be the ReID engine's output size.
+ * conf_thresh should be at most track_low_thresh).  No camera-motion warp unless the option "gmc" is set (below).  bp->feature_dim must
+ * be the ReID engine's output size.
  * aic_pipeline_last_embeddings / _group_embeddings work; aic_pipeline_tracker, the gallery exchange and the options "device_assoc",
  * "device_assoc_limit", "device_filter" fail with AIC_ERR_INVALID. */
 int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp,
@@ -535,8 +563,17 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
  * "dual_lane_frames" (default 128): launch groups of at most that many frames alternate between TWO instances of each engine (the second
  * one built on first use: own activation arena, detector workspace and streams), so that the groups of the two chunk contexts run
  * side by side -- a small group is a chain of ~60 short dependent kernels that leaves most of the chip idle; 0 = one lane.
- * Same results in every mode. */
+ * Same results in every mode.
+ * "epoch_frames" (a BoT-SORT pipeline only; AIC_ERR_INVALID on any other): frames per epoch launch of the tracker, 0..16 as
+ * aic_botsort_option (0 = 16).  Same results either way.
+ * "gmc" (a BoT-SORT pipeline only; AIC_ERR_INVALID on any other): 0 (default) = no camera-motion warp, 2 or 4 = the camera motion of
+ * every frame is estimated on the device at that downscale (as aic_gmc_estimate_batch, the boxes being the detections handed to the
+ * tracker) and warps the predicted tracks.  The gray levels are computed in the group's launch group, matching and fit run on the
+ * tracker stream before the group's epochs; the stream's first frame gets the identity.  With 0 nothing of it is launched or allocated. */
 int aic_pipeline_option(aic_pipeline* p, const char* key, int value);
+/* The warps [n_frames, 6] (as aic_gmc_estimate_batch) of the most recently finished launch group of a pipeline with "gmc" set;
+ * AIC_ERR_INVALID without it.  warps may be NULL; *n_frames is the group's frame count, at most cap_frames rows are written. */
+int aic_pipeline_group_warps(aic_pipeline* p, float* warps, int cap_frames, int32_t* n_frames);
 /* launch groups issued on the second lane since the pipeline was created */
 int aic_pipeline_lane_groups(aic_pipeline* p, int64_t* lane1_groups);
 /* Launch groups whose crop count outgrew the buffers sized from max_persons (handled, not dropped), and frames

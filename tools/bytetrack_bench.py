@@ -5,7 +5,7 @@ frames forward then backward).  Prints ONE JSON line: frames/s of the ByteTrack 
 HBM-resident frames and from host memory, the tracker stream's time per launch group and per 16-frame epoch (HIP events on the tracker kernels), the DeepSORT
 pipeline's frames/s measured the same way, and MOTA / IDF1 / ID switches of the three trackers against the planted identities on one scene whose scores
 are widened to (0.05, 0.95) so that ByteTrack's low band is used.  BoT-SORT appears twice: its pipeline (with the ReID engine, as
-DeepSORT's) in the same columns, and the tracker object alone (BoTSORT.update_batch_arrays, 512 frames per call,
+DeepSORT's) in the same columns -- then with the camera-motion option gmc = 4, then with gmc = 0 again, back to back -- and the tracker object alone (BoTSORT.update_batch_arrays, 512 frames per call,
 synthetic.identity_features as the appearance input) with the shader-clock share of its appearance pass.  Its quality figures are given
 with identity_features on the occlusion scene, and with the real ReID net on that scene and on the headline clip.  Reports numbers;
 gates on nothing.
@@ -84,6 +84,10 @@ def main():
     bs = TP(ypath, rpath, (H, W), batch=512, ring_frames=2 * R, max_persons=32, device=dev, dtype="fp16", inject=True, tracker="botsort")
     bs.option("split_streams", 1)
     res_bsp = rates(bs)
+    bs.option("gmc", 4)                                                # the same pipeline, camera motion estimated per frame
+    res_bsp_gmc = rates(bs)
+    bs.option("gmc", 0)
+    res_bsp_again = rates(bs)                                          # ... and off again: the spread of the gmc = 0 figure in this process
     # quality on the headline clip's first pass with the real ReID net
     bs2 = TP(ypath, rpath, (H, W), batch=512, ring_frames=2 * R, max_persons=32, device=dev, dtype="fp16", inject=True, tracker="botsort")
     bs2.upload(0, host)
@@ -148,7 +152,7 @@ def main():
         metrics[name] = dict(mota=round(m["mota"], 4), idf1=round(m["idf1"], 4), idsw=m["idsw"])
         trk.close()
     print(json.dumps(dict(workload="1280x720, 30 planted persons, YOLOv8n (trained) fp16, 512-frame groups, inject=1",
-                          bytetrack=res_bt, ocsort=res_oc, botsort_pipeline=res_bsp, botsort=res_bs, deepsort=res_ds, headline_metrics=headline, metrics=metrics, steps=args.steps)))
+                          bytetrack=res_bt, ocsort=res_oc, botsort_pipeline=res_bsp, botsort_pipeline_gmc4=res_bsp_gmc, botsort_pipeline_gmc0_again=res_bsp_again, botsort=res_bs, deepsort=res_ds, headline_metrics=headline, metrics=metrics, steps=args.steps)))
 
 
 if __name__ == "__main__":
