@@ -24,6 +24,10 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.bytetrack").BYTETracker
     if name == "OCSort":
         return _importlib.import_module(f"{__name__}.ocsort").OCSort
+    if name == "BYTETrackerBank":
+        return _importlib.import_module(f"{__name__}.bytetrack").BYTETrackerBank
+    if name == "OCSortBank":
+        return _importlib.import_module(f"{__name__}.ocsort").OCSortBank
     if name == "BoTSORT":
         return _importlib.import_module(f"{__name__}.botsort").BoTSORT
     if name == "CameraMotion":

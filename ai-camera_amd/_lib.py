@@ -175,6 +175,21 @@ _SIGS = {
     "aic_botsort_export": (_I, [_P, _I] + [_P] * 13),
     "aic_botsort_counters": (_I, [_P] * 7),
     "aic_pipeline_create_botsort": (_I, [_P, _P, _P, _P, _P]),
+    "aic_bytetrack_bank_create": (_I, [_I, _P, _I, _P]),
+    "aic_bytetrack_bank_destroy": (_I, [_P]),
+    "aic_bytetrack_bank_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_bytetrack_bank_update": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "aic_bytetrack_bank_reset": (_I, [_P, _I]),
+    "aic_bytetrack_bank_export": (_I, [_P, _I, _I] + [_P] * 11),
+    "aic_bytetrack_bank_counters": (_I, [_P, _I, _P, _P, _P]),
+    "aic_ocsort_bank_create": (_I, [_I, _P, _I, _P]),
+    "aic_ocsort_bank_destroy": (_I, [_P]),
+    "aic_ocsort_bank_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_ocsort_bank_update": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "aic_ocsort_bank_reset": (_I, [_P, _I]),
+    "aic_ocsort_bank_export": (_I, [_P, _I, _I] + [_P] * 14),
+    "aic_ocsort_bank_counters": (_I, [_P, _I] + [_P] * 7),
+    "aic_pipeline_reset_stream": (_I, [_P, _I]),
     "aic_gmc_create": (_I, [_I, _I, _I, _P, _P]),
     "aic_gmc_destroy": (_I, [_P]),
     "aic_gmc_reset": (_I, [_P]),

@@ -111,3 +111,112 @@ class BYTETracker:
                C.byref(n), C.byref(nt))
         out["n_tracked"] = nt.value
         return out
+
+
+class TrackerBank:
+    """What BYTETrackerBank and OCSortBank share: `streams` independent streams on one device, one kernel block per stream and
+    launch.  Every stream computes exactly what the single class fed the same frames computes; a stream that meets a capacity
+    error stops alone (`failed`), the others go on, and reset(stream) starts it afresh."""
+    _abi = None                                                  # "aic_bytetrack_bank" / "aic_ocsort_bank"
+
+    def _create(self, streams, device):
+        self.streams = int(streams)
+        self.failed = {}                                         # stream -> message
+        self._h = C.c_void_p()
+        L.call(self._abi + "_create", config.resolve_device(device), C.byref(self.params), self.streams, C.byref(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(L.load(), self._abi + "_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def option(self, key, value):
+        """"lsap_fast" (0/1), "epoch_frames" (0..16), for the whole bank: same results either way."""
+        L.call(self._abi + "_option", self._h, key.encode(), int(value))
+
+    def reset(self, stream):
+        """The stream as after creation (no tracks, ids from first_track_id again), a stop cleared: a camera reconnecting."""
+        L.call(self._abi + "_reset", self._h, int(stream))
+        self.failed.pop(int(stream), None)
+
+    def update_arrays(self, per_stream_frames, cap_rows=None):
+        """per_stream_frames: `streams` lists of (boxes_xyxy [n,4], scores [n], class_ids [n]), any length each.  Returns `streams`
+        lists of (rows [m,6] int32, conf [m] fp32) per frame, None in place of a stopped stream's list."""
+        if len(per_stream_frames) != self.streams:
+            raise ValueError(f"{len(per_stream_frames)} frame lists for a bank of {self.streams} streams")
+        flat = [fr for frames in per_stream_frames for fr in frames]
+        fps = np.array([len(frames) for frames in per_stream_frames], dtype=np.int32)
+        k = len(flat)
+        boxes = [np.asarray(b, dtype=np.float32).reshape(-1, 4) for b, _, _ in flat]
+        scores = [np.asarray(s, dtype=np.float32).reshape(-1) for _, s, _ in flat]
+        cids = [np.asarray(c).reshape(-1).astype(np.int32) for _, _, c in flat]
+        for b, s, c in zip(boxes, scores, cids):
+            if not (len(b) == len(s) == len(c)):
+                raise ValueError("boxes, scores and class ids differ in length")
+        counts = np.array([len(b) for b in boxes], dtype=np.int32)
+        cap = int(cap_rows if cap_rows is not None else self.max_tracks or 512)
+        some = bool(counts.sum())
+        xyxy = np.ascontiguousarray(np.concatenate(boxes) if some else np.zeros((0, 4), np.float32))
+        conf = np.ascontiguousarray(np.concatenate(scores) if some else np.zeros(0, np.float32))
+        cls = np.ascontiguousarray(np.concatenate(cids) if some else np.zeros(0, np.int32))
+        n_out = np.zeros(max(k, 1), np.int32)
+        out6 = np.zeros((max(k, 1), cap, 6), np.int32)
+        oconf = np.zeros((max(k, 1), cap), np.float32)
+        status = np.zeros(self.streams, np.int32)
+        L.call(self._abi + "_update", self._h, L.ptr(fps), L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), cap, L.ptr(n_out),
+               L.ptr(out6), L.ptr(oconf), L.ptr(status))
+        res, f = [], 0
+        for s in range(self.streams):
+            if status[s] and s not in self.failed:
+                self.failed[s] = f"stream {s} stopped with libaicam error {int(status[s])} (reset({s}) starts it afresh)"
+            rows = []
+            for _ in range(int(fps[s])):
+                m = min(int(n_out[f]), cap)
+                rows.append((out6[f, :m].copy(), oconf[f, :m].copy()))
+                f += 1
+            res.append(None if status[s] else rows)
+        return res
+
+    def update(self, per_stream_detections):
+        """One tick: `streams` entries (boxes_xyxy, scores, class_ids), None = no frame from that camera this tick.  Returns
+        `streams` lists of (x1, y1, x2, y2, track_id, class_name, conf) tuples ([] without a frame), None for a stopped stream."""
+        got = self.update_arrays([[] if d is None else [d] for d in per_stream_detections])
+        return [None if g is None else (BYTETracker._tuples(*g[0]) if g else []) for g in got]
+
+
+class BYTETrackerBank(TrackerBank):
+    """BYTETrackerBank(streams, **BYTETracker's arguments): the ByteTrack state of `streams` cameras on one device."""
+    _abi = "aic_bytetrack_bank"
+
+    def __init__(self, streams, track_thresh=0.5, track_buffer=30, match_thresh=0.8, mot20=False, frame_rate=30, low_thresh=0.1, device=0,
+                 max_tracks=512, first_track_id=1):
+        self.params = bytetrack_params(track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh, max_tracks,
+                                       first_track_id)
+        self.max_tracks = max_tracks
+        self._create(streams, device)
+
+    def counters(self, stream):
+        """BYTETracker.counters() of one stream."""
+        nf, nl, ms = C.c_int64(), C.c_int64(), C.c_int32()
+        L.call("aic_bytetrack_bank_counters", self._h, int(stream), C.byref(nf), C.byref(nl), C.byref(ms))
+        return dict(n_fast=nf.value, n_lsap=nl.value, max_side=ms.value)
+
+    def export(self, stream):
+        """BYTETracker.export() of one stream; raises for a stopped stream."""
+        n, nt = C.c_int32(), C.c_int32()
+        L.call("aic_bytetrack_bank_export", self._h, int(stream), 0, *([None] * 9), C.byref(n), C.byref(nt))
+        m = n.value
+        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
+                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
+                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32))
+        L.call("aic_bytetrack_bank_export", self._h, int(stream), m,
+               *(L.ptr(out[k]) for k in ("track_id", "state", "is_activated", "start_frame", "end_frame", "cls", "score", "mean", "cov")),
+               C.byref(n), C.byref(nt))
+        out["n_tracked"] = nt.value
+        return out

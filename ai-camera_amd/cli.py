@@ -40,6 +40,9 @@ def probe_cv2():
 def parse_arguments(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="AICamera: Real-time Object Detection & Tracking (MI355X engine)")
     p.add_argument("--input", type=str, default=None, help="video file (cv2), synthetic:WxH:persons:frames[:seed], frames.npy or raw:WxH:path")
+    p.add_argument("--inputs", type=str, default=None,
+                   help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort only: one pipeline with one tracker "
+                        "stream per source; the shortest source ends the run, one output per stream (suffix _s<k>)")
     p.add_argument("--webcam_id", type=int, default=0, help="webcam used when no --input is given (cv2)")
     p.add_argument("--output_dir", type=str, default="outputs")
     p.add_argument("--output_filename", type=str, default=None)
@@ -59,6 +62,11 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.gmc and args.tracker != "botsort":
         p.error("--gmc needs --tracker botsort")
+    if args.inputs is not None:
+        if args.input is not None:
+            p.error("--inputs and --input are mutually exclusive")
+        if args.tracker not in ("bytetrack", "ocsort"):
+            p.error("--inputs needs --tracker bytetrack or ocsort")
     return args
 
 
@@ -193,11 +201,68 @@ class _BotSortFrame:
         return self.tracker._tuples(rows, conf)
 
 
+def main_streams(args, cv2):
+    """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S)), their frames interleaved tick by tick."""
+    from .pipeline import TrackingPipeline
+    sources = [frame_source(spec, args.webcam_id, cv2) for spec in args.inputs.split(",") if spec]
+    S = len(sources)
+    size = sources[0][2]
+    if any(src[2][:2] != size[:2] for src in sources):
+        print("Error: --inputs sources must have one frame size: " + ", ".join(f"{src[2][0]}x{src[2][1]}" for src in sources))
+        return 1
+    if args.conf_thresh is None:
+        args.conf_thresh = 0.1 if args.tracker == "bytetrack" else 0.6
+    batch = max(1, args.batch // S) * S          # whole ticks per launch group
+    dev = config.resolve_device(args.device)
+    try:
+        pipe = TrackingPipeline(args.yolo_engine, None, (size[1], size[0]), batch=batch, ring_frames=batch, max_persons=512, max_tracks=512,
+                                device=dev, dtype=args.dtype, conf_thresh=args.conf_thresh,
+                                tracker=args.tracker, streams=S)
+    except Exception as e:
+        print(f"Error initializing YOLO Detector: {e}")
+        return 1
+    label = "AICamera: YOLOv8 + " + ("ByteTrack" if args.tracker == "bytetrack" else "OC-SORT")
+    outs, writers = [None] * S, [None] * S
+    if not args.no_save:
+        out_dir = Path(args.output_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        stamp = time.strftime('%Y%m%d-%H%M%S')
+        for k, (name, _, _) in enumerate(sources):
+            stem = out_dir / f"{name}_tracked_{stamp}_s{k}"
+            outs[k] = open(str(stem) + ".jsonl", "w")
+            writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None)
+    ticks = (f for tick in zip(*(src[1] for src in sources)) for f in tick)       # the shortest source ends the run
+    n, t0 = 0, time.time()
+    try:
+        for frame, tracks in pipe.stream(ticks):
+            k, idx = n % S, n // S
+            n += 1
+            if writers[k] is not None:
+                writers[k].write(visualization.draw_frame(frame.copy(), tracks, [label, f"Input: {sources[k][0]} (stream {k})"], dev))
+            if outs[k]:
+                outs[k].write(json.dumps({"frame": idx, "tracks": tracks}) + "\n")
+    except KeyboardInterrupt:
+        print("Processing interrupted by user.")
+    finally:
+        for f in outs + writers:
+            if f is not None:
+                f.close()
+        pipe.close()
+    total = time.time() - t0
+    print("\n--- Processing Summary ---")
+    print(f"Streams: {S}; ticks processed: {n // S}; frames: {n}")
+    print(f"Total time: {total:.2f} seconds; average FPS over all streams: {n / total if total > 0 else 0:.2f}")
+    print("AICamera finished.")
+    return 0
+
+
 def main(argv=None):
     args = parse_arguments(argv)
     cv2 = probe_cv2()
     if cv2 is None:
         print("OpenCV (cv2) is not importable: video files / webcams / --show_display are unavailable; codec-free sources and raw outputs are used.")
+    if args.inputs is not None:
+        return main_streams(args, cv2)
     print("Initializing YOLOv8 Detector...")
     name, frames, size = frame_source(args.input, args.webcam_id, cv2)
     bytetrack = args.tracker == "bytetrack"

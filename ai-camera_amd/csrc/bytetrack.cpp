@@ -1,4 +1,4 @@
-// bytetrack.cpp -- the ByteTrack tracker object (device table, epoch planning, launch, error check, read-back) and its C ABI.
+// bytetrack.cpp -- the ByteTrack tracker object (a bank of streams, epoch_bank.hpp: its kernel launch, error texts, export) and its C ABI.
 // There is no host implementation of the algorithm: the recurrence runs in kernels_bytetrack.hip or the call raises.
 #include "bytetrack_host.hpp"
 
@@ -29,122 +29,42 @@ BtParams bytetrack_params(const aic_bytetrack_params& p, int* first_id) {
     return b;
 }
 
-ByteTracker::ByteTracker(Device& d, const BtParams& p, int first_id) : dev(&d), prm(p) {
-    dev->use();
-    const size_t bytes = bt_table_bytes(prm.cap);
-    d_tbl.alloc(bytes);
-    tbl = bt_table(d_tbl.p, prm.cap);
-    HIP_CHECK(hipMemsetAsync(d_tbl.p, 0, bytes, dev->s_trk));
-    BtHdr h{};
-    h.next_id = first_id;
-    HIP_CHECK(hipMemcpyAsync(tbl.hdr, &h, sizeof(h), hipMemcpyHostToDevice, dev->s_trk));
-    d_ext.alloc((size_t)TRK_DEV_NMAX * TRK_DEV_NMAX);
-    h_hdr.alloc(sizeof(BtHdr));
-    HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+ByteTracker::ByteTracker(Device& d, const BtParams& p, int first_id, int streams)
+    : EpochBank(d, p, first_id, streams, bt_table_bytes(p.cap), (size_t)TRK_DEV_NMAX * TRK_DEV_NMAX) {}
+
+void ByteTracker::launch(const BtParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
+                         const EpochOut& out, hipStream_t s) {
+    launch_bytetrack_epoch(d_tbl.p, stride, n_streams, p, dets, f0, k, stream_f0, stream_k, frame_stride, d_ext.p, out, s);
 }
 
-void ByteTracker::run_epochs(const EpochDets& dets, int frames, const EpochOut& out, hipStream_t s) {
-    AIC_REQUIRE(!failed, AIC_ERR_INVALID, "ByteTrack tracker stopped by an earlier error: " + fail_msg);
-    const int kmax = epoch_frames > 0 ? epoch_frames : TRK_KMAX;
-    BtParams p = prm;
-    p.no_fast = lsap_fast ? 0 : 1;
-    for (int f = 0; f < frames;) {
-        const int k = std::min(kmax, frames - f);
-        {
-            Prof pr(*dev, PROF_TRK, s, 0, 0);
-            launch_bytetrack_epoch(tbl, p, dets, f, k, d_ext.p, out, s);
-        }
-        f += k;
-    }
-    HIP_CHECK(hipMemcpyAsync(h_hdr.p, tbl.hdr, sizeof(BtHdr), hipMemcpyDeviceToHost, s));
-}
-
-void ByteTracker::check_epochs() {
-    const BtHdr* h = reinterpret_cast<const BtHdr*>(h_hdr.p);
-    if (h->err == 0) return;
-    failed = true;
-    const std::string at = " (frame " + std::to_string(h->err_frame) + " of the call)";
-    if (h->err == 1) fail_msg = "track capacity exhausted (raise max_tracks)" + at;
-    else if (h->err == 3) fail_msg = "an assignment problem beyond the epoch kernel's capacity (tracks + detections > 512, or > 512 detections in a frame)" + at;
-    else fail_msg = "the assignment problem has no finite solution" + at;
-    AIC_REQUIRE(false, AIC_ERR_CAPACITY, "ByteTrack: " + fail_msg);
+std::string ByteTracker::err_text(int err) const {
+    if (err == 1) return "track capacity exhausted (raise max_tracks)";
+    if (err == 3) return "an assignment problem beyond the epoch kernel's capacity (tracks + detections > 512, or > 512 detections in a frame)";
+    return "the assignment problem has no finite solution";
 }
 
 void ByteTracker::update_batch(int k, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, int cap_rows,
                                int32_t* n_out, int32_t* out6, float* out_conf) {
-    dev->use();
     AIC_REQUIRE(k >= 0 && cap_rows >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
     AIC_REQUIRE(!failed, AIC_ERR_INVALID, "ByteTrack tracker stopped by an earlier error: " + fail_msg);
-    if (k == 0) return;
-    long total = 0;
-    for (int f = 0; f < k; ++f) {
-        AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative detection count");
-        AIC_REQUIRE(counts[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "ByteTrack: more than 512 detections in one frame");
-        total += counts[f];
-    }
-    hipStream_t s = dev->s_trk;
-    const int n = (int)total;
-    // staging (host == device layout): frame_n[k] | frame_d0[k] | tlwh[n*4] | conf[n] | cls[n] || n_tracks[k] | rows[k*cap*6] | conf[k*cap]
-    const size_t o_d0 = (size_t)k * 4, o_tlwh = (((size_t)k * 8 + 15) / 16) * 16, o_conf = o_tlwh + (size_t)n * 16, o_cls = o_conf + (size_t)n * 4;
-    const size_t o_out = ((o_cls + (size_t)n * 4 + 15) / 16) * 16;
-    const size_t o_rows = o_out + (((size_t)k * 4 + 15) / 16) * 16, o_oconf = o_rows + (size_t)k * cap_rows * 24;
-    const size_t bytes = o_oconf + (size_t)k * cap_rows * 4;
-    HIP_CHECK(hipStreamSynchronize(s));
-    h_api.ensure(bytes);
-    d_api.ensure(bytes);
-    int* hn = reinterpret_cast<int*>(h_api.p);
-    int* hd = reinterpret_cast<int*>(h_api.p + o_d0);
-    int d0 = 0;
-    for (int f = 0; f < k; ++f) { hn[f] = counts[f]; hd[f] = d0; d0 += counts[f]; }
-    float* ht = reinterpret_cast<float*>(h_api.p + o_tlwh);
-    for (int j = 0; j < n; ++j) {                                 // tlbr -> tlwh (byte_tracker.py: STrack.tlbr_to_tlwh), fp32
-        const float* b = xyxy + (size_t)j * 4;
-        ht[j * 4 + 0] = b[0], ht[j * 4 + 1] = b[1], ht[j * 4 + 2] = b[2] - b[0], ht[j * 4 + 3] = b[3] - b[1];
-    }
-    if (n) {
-        std::memcpy(h_api.p + o_conf, conf, (size_t)n * 4);
-        std::memcpy(h_api.p + o_cls, cls, (size_t)n * 4);
-    }
-    HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
-    EpochDets dets{reinterpret_cast<const int*>(d_api.p), reinterpret_cast<const int*>(d_api.p + o_d0),
-                   reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
-                   reinterpret_cast<const int*>(d_api.p + o_cls), nullptr, nullptr, nullptr};
-    EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows), reinterpret_cast<float*>(d_api.p + o_oconf),
-                 cap_rows, nullptr, nullptr, 0};
-    run_epochs(dets, k, out, s);
-    HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    check_epochs();
-    const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
-    const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
-    const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
-    for (int f = 0; f < k; ++f) {
-        const int kk = std::min(on[f], cap_rows);
-        if (n_out) n_out[f] = on[f];                              // the true count: rows beyond cap_rows are not stored
-        if (out6) std::copy(rows + (size_t)f * cap_rows * 6, rows + ((size_t)f * cap_rows + kk) * 6, out6 + (size_t)f * cap_rows * 6);
-        if (out_conf) std::copy(oc + (size_t)f * cap_rows, oc + (size_t)f * cap_rows + kk, out_conf + (size_t)f * cap_rows);
-    }
+    const int32_t fps = k;
+    update(&fps, counts, xyxy, conf, cls, cap_rows, n_out, out6, out_conf, nullptr);
 }
 
-void ByteTracker::counters(int64_t* n_fast, int64_t* n_lsap, int32_t* max_side) {
-    dev->use();
-    HIP_CHECK(hipStreamSynchronize(dev->s_trk));
-    BtHdr h{};
-    HIP_CHECK(hipMemcpy(&h, tbl.hdr, sizeof(h), hipMemcpyDeviceToHost));
+void ByteTracker::counters(int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side) {
+    const std::vector<char> hb = fetch_table(stream, sizeof(BtHdr));
+    const BtHdr& h = *reinterpret_cast<const BtHdr*>(hb.data());
     if (n_fast) *n_fast = h.n_fast;
     if (n_lsap) *n_lsap = h.n_lsap;
     if (max_side) *max_side = h.max_side;
 }
 
-int ByteTracker::export_state(int cap_rows, int32_t* id, int32_t* state, int32_t* act, int32_t* start, int32_t* end, int32_t* cls,
+int ByteTracker::export_state(int stream, int cap_rows, int32_t* id, int32_t* state, int32_t* act, int32_t* start, int32_t* end, int32_t* cls,
                               float* score, float* mean, float* cov, int32_t* n_tracked) {
-    dev->use();
+    AIC_REQUIRE(stream >= 0 && stream < n_streams, AIC_ERR_INVALID, "stream outside the bank");
     // after an error the covariances hold the failing epoch's values and the rest the epoch before: there is no state to report
-    AIC_REQUIRE(!failed, AIC_ERR_INVALID, "ByteTrack tracker stopped by an earlier error (no consistent state to export): " + fail_msg);
-    hipStream_t s = dev->s_trk;
-    HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<char> h(bt_table_bytes(prm.cap));
-    HIP_CHECK(hipMemcpy(h.data(), d_tbl.p, h.size(), hipMemcpyDeviceToHost));
+    AIC_REQUIRE(!stop_code[stream], AIC_ERR_INVALID, "ByteTrack tracker stopped by an earlier error (no consistent state to export): " + stop_msg[stream]);
+    std::vector<char> h = fetch_table(stream, tbl_bytes);
     const BtTable t = bt_table(h.data(), prm.cap);
     const int ntl = t.hdr->n_tracked, nll = t.hdr->n_lost, n = ntl + nll;
     if (n_tracked) *n_tracked = ntl;
@@ -198,10 +118,7 @@ int aic_bytetrack_option(aic_bytetrack* t, const char* key, int value) {
 int aic_bytetrack_update_batch(aic_bytetrack* t, int k, const int32_t* counts, const float* boxes_xyxy, const float* conf, const int32_t* cls,
                                int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf) {
     return guarded([&] {
-        AIC_REQUIRE(t && (k == 0 || counts), AIC_ERR_INVALID, "NULL argument");
-        long total = 0;
-        for (int f = 0; f < k; ++f) total += counts[f];
-        AIC_REQUIRE(total == 0 || (boxes_xyxy && conf && cls), AIC_ERR_INVALID, "NULL detection arrays");
+        AIC_REQUIRE(t && (k <= 0 || counts), AIC_ERR_INVALID, "NULL argument");
         t->t.update_batch(k, counts, boxes_xyxy, conf, cls, cap_rows, n_out, out6, out_conf);
     });
 }
@@ -210,7 +127,7 @@ int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* 
                          int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* n_tracks, int32_t* n_tracked) {
     return guarded([&] {
         AIC_REQUIRE(t && cap >= 0, AIC_ERR_INVALID, "bad argument");
-        const int n = t->t.export_state(cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, n_tracked);
+        const int n = t->t.export_state(0, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, n_tracked);
         if (n_tracks) *n_tracks = n;
     });
 }
@@ -218,7 +135,70 @@ int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* 
 int aic_bytetrack_counters(aic_bytetrack* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side) {
     return guarded([&] {
         AIC_REQUIRE(t, AIC_ERR_INVALID, "NULL tracker");
-        t->t.counters(n_fast, n_lsap, max_side);
+        t->t.counters(0, n_fast, n_lsap, max_side);
+    });
+}
+
+// ---- banks
+int aic_bytetrack_bank_create(int device_id, const aic_bytetrack_params* p, int streams, aic_bytetrack_bank** out) {
+    return guarded([&] {
+        AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
+        int first = 1;
+        const BtParams b = bytetrack_params(*p, &first);
+        AIC_REQUIRE(streams >= 1 && streams <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+        *out = new aic_bytetrack_bank(device(device_id), b, first, streams);
+    });
+}
+
+int aic_bytetrack_bank_destroy(aic_bytetrack_bank* b) {
+    return guarded([&] { delete b; });
+}
+
+int aic_bytetrack_bank_option(aic_bytetrack_bank* b, const char* key, int value) {
+    return guarded([&] {
+        AIC_REQUIRE(b && key, AIC_ERR_INVALID, "NULL argument");
+        const std::string k(key);
+        if (k == "lsap_fast") b->t.lsap_fast = value != 0;
+        else if (k == "epoch_frames") {
+            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
+            b->t.epoch_frames = value;
+        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown ByteTrack option: " + k);
+    });
+}
+
+int aic_bytetrack_bank_update(aic_bytetrack_bank* b, const int32_t* frames_per_stream, const int32_t* counts, const float* boxes_xyxy,
+                              const float* conf, const int32_t* cls, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf,
+                              int32_t* status) {
+    return guarded([&] {
+        AIC_REQUIRE(b && frames_per_stream, AIC_ERR_INVALID, "NULL argument");
+        bool any = false;
+        for (int s = 0; s < b->t.n_streams; ++s) any |= frames_per_stream[s] > 0;
+        AIC_REQUIRE(!any || counts, AIC_ERR_INVALID, "NULL argument");
+        b->t.update(frames_per_stream, counts, boxes_xyxy, conf, cls, cap_rows, n_out, out6, out_conf, status);
+    });
+}
+
+int aic_bytetrack_bank_reset(aic_bytetrack_bank* b, int stream) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL bank");
+        b->t.reset_stream(stream);
+    });
+}
+
+int aic_bytetrack_bank_export(aic_bytetrack_bank* b, int stream, int cap, int32_t* track_id, int32_t* state, int32_t* is_activated,
+                              int32_t* start_frame, int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov,
+                              int32_t* n_tracks, int32_t* n_tracked) {
+    return guarded([&] {
+        AIC_REQUIRE(b && cap >= 0, AIC_ERR_INVALID, "bad argument");
+        const int n = b->t.export_state(stream, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, n_tracked);
+        if (n_tracks) *n_tracks = n;
+    });
+}
+
+int aic_bytetrack_bank_counters(aic_bytetrack_bank* b, int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL bank");
+        b->t.counters(stream, n_fast, n_lsap, max_side);
     });
 }
 

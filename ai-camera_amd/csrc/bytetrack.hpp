@@ -1,9 +1,10 @@
 // bytetrack.hpp -- ByteTrack on the device (BYTETracker.update of yolox/tracker/byte_tracker.py, restated in tests/bytetrack_oracle.py):
-// the structures shared by kernels_bytetrack.hip (the one-block epoch kernel) and bytetrack.cpp (tracker object, pipeline hook).
+// the structures shared by kernels_bytetrack.hip (the epoch kernel, one block per stream) and bytetrack.cpp (tracker object, pipeline hook).
 //
 // The track table lives in HBM between launches, indexed by SLOT (a slot is a track's place in the mean / cov arrays):
 //   BtHdr | BtTrack[cap] | tracked list[cap] | lost list[cap] (slots, list order) | mean[cap][8] | cov[cap][64]
-// An epoch launch (ONE block of 512 threads) loads the scalars, the lists and the means into LDS, walks k <= TRK_KMAX frames with no host
+// A bank holds the tables of its streams `table_stride` bytes apart in one allocation.  An epoch launch (ONE block of 512 threads per
+// stream) loads the scalars, the lists and the means into LDS, walks k <= TRK_KMAX frames with no host
 // round trip (covariances stay in HBM) and writes them back.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,7 +51,7 @@ struct BtTable {                    // device pointers into one allocation
 static inline size_t bt_table_bytes(int cap) {
     return 64 + (size_t)cap * (sizeof(BtTrack) + 8 + 4 * 8 + 4 * 64);
 }
-static inline BtTable bt_table(char* base, int cap) {
+__host__ __device__ static inline BtTable bt_table(char* base, int cap) {
     BtTable t;
     t.hdr = reinterpret_cast<BtHdr*>(base);
     t.trk = reinterpret_cast<BtTrack*>(base + 64);
@@ -61,8 +62,10 @@ static inline BtTable bt_table(char* base, int cap) {
     return t;
 }
 
-// one launch: frames [f0, f0 + k) of the group; ext = [TRK_DEV_NMAX * TRK_DEV_NMAX] HBM scratch for extended matrices that do not fit the LDS
-void launch_bytetrack_epoch(const BtTable& tbl, const BtParams& prm, const EpochDets& dets, int f0, int k, float* ext,
-                            const EpochOut& out, hipStream_t s);
+// one launch, one block per stream of the bank: local frames [f0, f0 + k) of every stream, cut at stream_k[s]; local frame i of stream s
+// is row stream_f0[s] + i * frame_stride of `dets` / `out` (stream_f0 = stream_k = NULL, streams = 1: row = local frame).
+// ext = [streams][TRK_DEV_NMAX * TRK_DEV_NMAX] HBM scratch for extended matrices that do not fit the LDS
+void launch_bytetrack_epoch(char* bank, size_t table_stride, int streams, const BtParams& prm, const EpochDets& dets, int f0, int k,
+                            const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s);
 
 }  // namespace aic

@@ -1,0 +1,234 @@
+// epoch_bank.hpp -- a bank of detector-only tracker streams on one device: what ByteTracker and OcSortTracker share.  One allocation holds
+// the streams' tables `stride` bytes apart, every epoch launch runs one block per stream (kernels_bytetrack.hip / kernels_ocsort.hip), and a
+// stream that meets a capacity error stops alone.  The single trackers of the C ABI and the pipeline's default are banks of one.
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "epoch_tracker.hpp"
+
+namespace aic {
+
+constexpr int BANK_STREAMS_MAX = 256;
+
+// Hdr: the table header (next_id, err, err_frame; at the start of every table).  Prm: the kernel's parameters (no_fast).
+template <class Hdr, class Prm>
+struct EpochBank : EpochTracker {
+    Device* dev;
+    Prm prm;
+    int first_id;
+    int n_streams = 0;
+    size_t tbl_bytes, stride, ext_floats;   // one table; distance of two tables; HBM scratch of one stream
+    DevBuf<char> d_tbl;
+    DevBuf<float> d_ext;
+    PinBuf<char> h_api, h_hdr;
+    DevBuf<char> d_api;
+    PinBuf<int> h_plan;             // the pipeline's tick-major plan: stream_f0[S] | stream_k[S]
+    DevBuf<int> d_plan;
+    int epoch_frames = 0;           // frames per epoch launch (0 = TRK_KMAX)
+    bool lsap_fast = true;
+    bool used = false;              // frames have gone through the bank
+    std::vector<int> stop_code;     // per stream: 0, or the error code that stopped it
+    std::vector<std::string> stop_msg;
+
+    EpochBank(Device& d, const Prm& p, int first, int streams, size_t table_bytes, size_t ext_per_stream)
+        : dev(&d), prm(p), first_id(first), tbl_bytes(table_bytes), stride((table_bytes + 255) / 256 * 256), ext_floats(ext_per_stream) {
+        resize(streams);
+    }
+
+    virtual void launch(const Prm& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
+                        const EpochOut& out, hipStream_t s) = 0;
+    virtual std::string err_text(int err) const = 0;
+
+    int streams() const override { return n_streams; }
+    char* table(int s) const { return d_tbl.p + (size_t)s * stride; }
+    const Hdr& host_hdr(int s) const { return *reinterpret_cast<const Hdr*>(h_hdr.p + (size_t)s * sizeof(Hdr)); }
+
+    void resize(int streams) {
+        dev->use();
+        HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+        n_streams = streams;
+        d_tbl.alloc(stride * streams);
+        d_ext.alloc(ext_floats * streams);
+        h_hdr.alloc(sizeof(Hdr) * streams);
+        h_plan.alloc(2 * (size_t)streams);
+        d_plan.alloc(2 * (size_t)streams);
+        stop_code.assign(streams, 0);
+        stop_msg.assign(streams, std::string());
+        failed = false, fail_msg.clear();
+        for (int s = 0; s < streams; ++s) clear_table(s);
+        HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+    }
+    void clear_table(int s) {
+        HIP_CHECK(hipMemsetAsync(table(s), 0, tbl_bytes, dev->s_trk));
+        Hdr h{};
+        h.next_id = first_id;
+        HIP_CHECK(hipMemcpyAsync(table(s), &h, sizeof(h), hipMemcpyHostToDevice, dev->s_trk));   // pageable source: copied before the call returns
+    }
+    void set_streams(int streams) override {
+        AIC_REQUIRE(streams >= 1 && streams <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+        AIC_REQUIRE(!used, AIC_ERR_INVALID, "streams is set before the first frames go through the tracker");
+        if (streams != n_streams) resize(streams);
+    }
+    // the stream's table as after create (ids from first_track_id again), a stop cleared: a camera reconnecting
+    void reset_stream(int s) override {
+        AIC_REQUIRE(s >= 0 && s < n_streams, AIC_ERR_INVALID, "stream outside the bank");
+        dev->use();
+        HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+        clear_table(s);
+        HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+        stop_code[s] = 0, stop_msg[s].clear();
+        failed = false, fail_msg.clear();
+        for (int q = n_streams - 1; q >= 0; --q)
+            if (stop_code[q]) failed = true, fail_msg = stop_msg[q];
+    }
+
+    // local frames [0, kmax_s) of every stream as epochs of one block per stream on stream s; the headers' copy lands in h_hdr behind them
+    void run_bank(const EpochDets& dets, int kmax_s, const int* stream_f0, const int* stream_k, int frame_stride, const EpochOut& out,
+                  hipStream_t s) {
+        used = true;
+        const int kmax = epoch_frames > 0 ? epoch_frames : TRK_KMAX;
+        Prm p = prm;
+        p.no_fast = lsap_fast ? 0 : 1;
+        for (int f = 0; f < kmax_s;) {
+            const int k = std::min(kmax, kmax_s - f);
+            {
+                Prof pr(*dev, PROF_TRK, s, 0, 0);
+                launch(p, dets, f, k, stream_f0, stream_k, frame_stride, out, s);
+            }
+            f += k;
+        }
+        if (n_streams == 1) HIP_CHECK(hipMemcpyAsync(h_hdr.p, d_tbl.p, sizeof(Hdr), hipMemcpyDeviceToHost, s));
+        else HIP_CHECK(hipMemcpy2DAsync(h_hdr.p, sizeof(Hdr), d_tbl.p, stride, sizeof(Hdr), n_streams, hipMemcpyDeviceToHost, s));
+    }
+
+    // The pipeline's hook: the group's frames, tick-major over the streams.  A stopped stream refuses the group.
+    void run_epochs(const EpochDets& dets, int frames, const EpochOut& out, hipStream_t s) override {
+        AIC_REQUIRE(!failed, AIC_ERR_INVALID, std::string(name()) + " tracker stopped by an earlier error: " + fail_msg);
+        if (n_streams == 1) return run_bank(dets, frames, nullptr, nullptr, 1, out, s);
+        AIC_REQUIRE(frames % n_streams == 0, AIC_ERR_INVALID, "a launch group must hold whole ticks of every stream");
+        for (int q = 0; q < n_streams; ++q) h_plan.p[q] = q, h_plan.p[n_streams + q] = frames / n_streams;
+        HIP_CHECK(hipMemcpyAsync(d_plan.p, h_plan.p, 2 * (size_t)n_streams * 4, hipMemcpyHostToDevice, s));   // the caller syncs s before the next group
+        run_bank(dets, frames / n_streams, d_plan.p, d_plan.p + n_streams, n_streams, out, s);
+    }
+
+    // after the caller's sync: the streams that stopped in the launches behind it.  Returns the lowest one, or -1.
+    int collect() {
+        int first = -1;
+        for (int q = 0; q < n_streams; ++q) {
+            const Hdr& h = host_hdr(q);
+            if (stop_code[q] || h.err == 0) continue;
+            stop_code[q] = AIC_ERR_CAPACITY;
+            stop_msg[q] = (n_streams > 1 ? "stream " + std::to_string(q) + ": " : std::string()) + err_text(h.err) + " (frame " +
+                          std::to_string(h.err_frame) + " of the call)";
+            if (first < 0) first = q;
+        }
+        for (int q = n_streams - 1; q >= 0; --q)
+            if (stop_code[q]) failed = true, fail_msg = stop_msg[q];
+        return first;
+    }
+    void check_epochs() override {
+        const int q = collect();
+        AIC_REQUIRE(q < 0, AIC_ERR_CAPACITY, std::string(name()) + ": " + stop_msg[q]);
+    }
+
+    // frames_per_stream[S] frames of every stream, stream-major (F in all): one staging upload, ceil(max k / epoch_frames) launches of S
+    // blocks, one read-back, one sync.  status (may be NULL): per stream 0 or the code that stopped it; with status NULL a stopped stream
+    // raises after the other streams' rows have been delivered.
+    void update(const int32_t* frames_per_stream, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, int cap_rows,
+                int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status) {
+        dev->use();
+        AIC_REQUIRE(cap_rows >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
+        const int S = n_streams;
+        long F = 0;
+        int kmax_s = 0;
+        for (int q = 0; q < S; ++q) {
+            AIC_REQUIRE(frames_per_stream[q] >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
+            F += frames_per_stream[q];
+            kmax_s = std::max(kmax_s, (int)frames_per_stream[q]);
+        }
+        AIC_REQUIRE(F <= (1 << 24), AIC_ERR_INVALID, "too many frames in one call");
+        long total = 0;
+        for (long f = 0; f < F; ++f) {
+            AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative detection count");
+            AIC_REQUIRE(counts[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, std::string(name()) + ": more than 512 detections in one frame");
+            total += counts[f];
+        }
+        AIC_REQUIRE(total == 0 || (xyxy && conf && cls), AIC_ERR_INVALID, "NULL detection arrays");
+        if (status) std::copy(stop_code.begin(), stop_code.end(), status);
+        const std::vector<int> before = stop_code;
+        int bad = -1;
+        if (F > 0) {
+            hipStream_t s = dev->s_trk;
+            const size_t k = (size_t)F, n = (size_t)total;
+            auto up = [](size_t x) { return (x + 15) / 16 * 16; };
+            // staging (host == device layout): stream_f0[S] | stream_k[S] | frame_n[F] | frame_d0[F] | tlwh[n*4] | conf[n] | cls[n]
+            //                                  || n_tracks[F] | rows[F*cap*6] | conf[F*cap]
+            const size_t o_n = up((size_t)S * 8), o_d0 = o_n + k * 4, o_tlwh = up(o_d0 + k * 4), o_conf = o_tlwh + n * 16, o_cls = o_conf + n * 4;
+            const size_t o_out = up(o_cls + n * 4);
+            const size_t o_rows = o_out + up(k * 4), o_oconf = o_rows + k * cap_rows * 24;
+            const size_t bytes = o_oconf + k * cap_rows * 4;
+            HIP_CHECK(hipStreamSynchronize(s));
+            h_api.ensure(bytes);
+            d_api.ensure(bytes);
+            int* hp = reinterpret_cast<int*>(h_api.p);
+            for (int q = 0, f = 0; q < S; ++q) { hp[q] = f; hp[S + q] = frames_per_stream[q]; f += frames_per_stream[q]; }
+            int* hn = reinterpret_cast<int*>(h_api.p + o_n);
+            int* hd = reinterpret_cast<int*>(h_api.p + o_d0);
+            int d0 = 0;
+            for (size_t f = 0; f < k; ++f) { hn[f] = counts[f]; hd[f] = d0; d0 += counts[f]; }
+            float* ht = reinterpret_cast<float*>(h_api.p + o_tlwh);
+            for (size_t j = 0; j < n; ++j) {                      // xyxy -> tlwh, fp32: the detection format of every tracker here
+                const float* b = xyxy + j * 4;
+                ht[j * 4 + 0] = b[0], ht[j * 4 + 1] = b[1], ht[j * 4 + 2] = b[2] - b[0], ht[j * 4 + 3] = b[3] - b[1];
+            }
+            if (n) {
+                std::memcpy(h_api.p + o_conf, conf, n * 4);
+                std::memcpy(h_api.p + o_cls, cls, n * 4);
+            }
+            HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
+            EpochDets dets{reinterpret_cast<const int*>(d_api.p + o_n), reinterpret_cast<const int*>(d_api.p + o_d0),
+                           reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
+                           reinterpret_cast<const int*>(d_api.p + o_cls), nullptr, nullptr, nullptr};
+            EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows),
+                         reinterpret_cast<float*>(d_api.p + o_oconf), cap_rows, nullptr, nullptr, 0};
+            const int* dp = reinterpret_cast<const int*>(d_api.p);
+            if (S == 1) run_bank(dets, kmax_s, nullptr, nullptr, 1, out, s);
+            else run_bank(dets, kmax_s, dp, dp + S, 1, out, s);
+            HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            collect();
+            const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
+            const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
+            const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
+            for (int q = 0, f = 0; q < S; ++q) {
+                // a stream stopped before the call delivers nothing; one that stopped in it, the frames before the failing one
+                const int good = before[q] ? 0 : stop_code[q] ? host_hdr(q).err_frame : frames_per_stream[q];
+                for (int i = 0; i < frames_per_stream[q]; ++i, ++f) {
+                    const int m = i < good ? on[f] : 0;
+                    const int kk = std::min(m, cap_rows);
+                    if (n_out) n_out[f] = m;                      // the true count: rows beyond cap_rows are not stored
+                    if (out6) std::copy(rows + (size_t)f * cap_rows * 6, rows + ((size_t)f * cap_rows + kk) * 6, out6 + (size_t)f * cap_rows * 6);
+                    if (out_conf) std::copy(oc + (size_t)f * cap_rows, oc + (size_t)f * cap_rows + kk, out_conf + (size_t)f * cap_rows);
+                }
+                if (bad < 0 && stop_code[q] && frames_per_stream[q] > 0) bad = q;
+            }
+        }
+        if (status) std::copy(stop_code.begin(), stop_code.end(), status);
+        else AIC_REQUIRE(bad < 0, stop_code[bad], std::string(name()) + ": " + stop_msg[bad]);
+    }
+
+    // the stream's table on the host (export, counters)
+    std::vector<char> fetch_table(int s, size_t bytes) {
+        AIC_REQUIRE(s >= 0 && s < n_streams, AIC_ERR_INVALID, "stream outside the bank");
+        dev->use();
+        HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+        std::vector<char> h(bytes);
+        HIP_CHECK(hipMemcpy(h.data(), table(s), bytes, hipMemcpyDeviceToHost));
+        return h;
+    }
+};
+
+}  // namespace aic

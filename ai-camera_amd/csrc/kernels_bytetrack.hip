@@ -5,7 +5,9 @@
 // per-tracker ids, SciPy's tie rules on lap's extended matrix).  The Kalman arithmetic is trk_math.hpp's, the LSAPs, the DPP
 // reductions and the ordered compaction are trk_wave.hpp's (shared with the DeepSORT epoch kernel).
 //
-// ONE block of 512 threads walks the frames of one stream: thread i <-> list position i / detection i / slot i.  Per frame:
+// ONE block of 512 threads walks the frames of one stream: thread i <-> list position i / detection i / slot i.  A launch holds one
+// block per stream of a bank (blockIdx.x = stream: its own table, its own slice of the HBM scratch, its own rows of the group); a
+// single tracker is the bank of one.  Per frame:
 //   bands (high: s > track_thresh, second: low < s < track_thresh) -> pool = activated tracked ++ lost, Kalman predict (mean[7] = 0
 //   first for lost tracks; unconfirmed tracks are not predicted) -> stage 1 (pool x high, fused IoU, match_thresh) -> stage 2 (pool's
 //   unmatched Tracked x second band, IoU, 0.5) -> stage 3 (unconfirmed x high left over, fused, 0.7) -> new tracks -> lost timeout ->
@@ -21,11 +23,15 @@
 namespace aic {
 
 struct BtArgs {
-    BtTable tbl;
+    char* bank;                     // stream s: bt_table(bank + s * table_stride, cap)
+    size_t table_stride;
     BtParams prm;
     EpochDets dets;
-    int f0, k;
-    float* ext;                     // [TRK_DEV_NMAX^2] extended matrices that do not fit the LDS arena
+    int f0, k;                      // local frames [f0, f0 + k) of every stream, cut at stream_k[s]
+    const int* stream_f0;           // [streams] local frame i of stream s = row stream_f0[s] + i * frame_stride of dets / out;
+    const int* stream_k;            // [streams] frames of stream s in the call.  Both NULL: one stream, row = local frame
+    int frame_stride;
+    float* ext;                     // [streams][TRK_DEV_NMAX^2] extended matrices that do not fit the LDS arena
     EpochOut out;
     int lds_bytes;
 };
@@ -92,7 +98,7 @@ __device__ __forceinline__ float iou_dist(const float b[4], const float* c) {
 // linear_assignment(cost, thresh) of matching.py for rows (slots) x cols (detections), block-wide.
 // Out: L.mrow[r] = column of row r or -1, L.mcol[c] = row of column c or -1.  *err = 3 when the extended side exceeds the LSAPs.
 // Ls: the same carve in LDS, what the (noinline) LSAPs get a reference to -- a reference to the kernel's own copy would put it in scratch.
-__device__ void bt_assign(const BtLds& L, const BtLds& Ls, const BtArgs& a, const int* rows, int nr, const int* cols, int nc, bool fuse, float th, int* err) {
+__device__ void bt_assign(const BtLds& L, const BtLds& Ls, const BtArgs& a, float* hbm, const int* rows, int nr, const int* cols, int nc, bool fuse, float th, int* err) {
     const int tid = threadIdx.x;
     for (int r = tid; r < nr; r += BT) L.mrow[r] = -1;
     for (int c = tid; c < nc; c += BT) L.mcol[c] = -1;
@@ -101,7 +107,7 @@ __device__ void bt_assign(const BtLds& L, const BtLds& Ls, const BtArgs& a, cons
     const int S = nr + nc;
     if (S > TRK_DEV_NMAX) { if (tid == 0) *err = 3; __syncthreads(); return; }
     if (tid == 0) L.wcnt[NW + 4] = max(L.wcnt[NW + 4], S);
-    float* ext = S * S <= L.arena_floats ? L.arena : a.ext;
+    float* ext = S * S <= L.arena_floats ? L.arena : hbm;
     const float half = th * 0.5f;
     for (int e = tid; e < S * S; e += BT) {
         const int r = e / S, c = e - r * S;
@@ -170,24 +176,31 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void bytetrack_epoch_kernel(BtArgs a)
     const BtParams& P = a.prm;
     const int cap = P.cap;
     int* err = L.wcnt + NW + 3;
-    if (a.tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
+    // ---- this block's stream: frame range, table, HBM scratch
+    const int sid = blockIdx.x;
+    const int row0 = a.stream_f0 ? a.stream_f0[sid] : 0;
+    const int kend = a.stream_k ? min(a.f0 + a.k, a.stream_k[sid]) : a.f0 + a.k;
+    if (a.f0 >= kend) return;                                     // nothing for this stream in this epoch: its table is not touched
+    const BtTable tbl = bt_table(a.bank + (size_t)sid * a.table_stride, cap);
+    float* hbm = a.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_NMAX;
+    if (tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
 
     // ---- load the table
-    int ntl = a.tbl.hdr->n_tracked, nll = a.tbl.hdr->n_lost, next_id = a.tbl.hdr->next_id, frame = a.tbl.hdr->frame_id;
+    int ntl = tbl.hdr->n_tracked, nll = tbl.hdr->n_lost, next_id = tbl.hdr->next_id, frame = tbl.hdr->frame_id;
     if (tid < cap) {
-        const BtTrack t = a.tbl.trk[tid];
+        const BtTrack t = tbl.trk[tid];
         L.id[tid] = t.id, L.state[tid] = t.state, L.act[tid] = t.act, L.start[tid] = t.start, L.end[tid] = t.end, L.cls[tid] = t.cls;
         L.score[tid] = t.score;
     }
-    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = a.tbl.mean[e];
-    if (tid < ntl) L.tl[tid] = a.tbl.tl[tid];
-    if (tid < nll) L.ll[tid] = a.tbl.ll[tid];
-    if (tid == 0) { *err = 0; L.wcnt[NW + 1] = 0; L.wcnt[NW + 2] = 0; L.wcnt[NW + 4] = a.tbl.hdr->max_side; }
+    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = tbl.mean[e];
+    if (tid < ntl) L.tl[tid] = tbl.tl[tid];
+    if (tid < nll) L.ll[tid] = tbl.ll[tid];
+    if (tid == 0) { *err = 0; L.wcnt[NW + 1] = 0; L.wcnt[NW + 2] = 0; L.wcnt[NW + 4] = tbl.hdr->max_side; }
     __syncthreads();
-    float* cov = a.tbl.cov;
-    int fi = 0;
-    for (; fi < a.k; ++fi) {
-        const int f = a.f0 + fi;
+    float* cov = tbl.cov;
+    int fi = a.f0;
+    for (; fi < kend; ++fi) {
+        const int f = row0 + fi * a.frame_stride;
         ++frame;
         const int n = a.dets.frame_n[f], d0 = a.dets.frame_d0[f];
         if (n > TRK_DEV_NMAX) { if (tid == 0) *err = 3; break; }
@@ -220,7 +233,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void bytetrack_epoch_kernel(BtArgs a)
         __syncthreads();
 
         // ---- stage 1: pool x high band
-        bt_assign(L, s_lds, a, L.pool, np, L.hi, nh, P.fuse != 0, P.match_thresh, err);
+        bt_assign(L, s_lds, a, hbm, L.pool, np, L.hi, nh, P.fuse != 0, P.match_thresh, err);
         if (*err) break;
         for (int r = wv; r < np; r += NW) {
             const int c = L.mrow[r];
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void bytetrack_epoch_kernel(BtArgs a)
         __syncthreads();
 
         // ---- stage 2: the pool's unmatched Tracked tracks x second band, IoU distance, no fusion
-        bt_assign(L, s_lds, a, L.rows, nr2, L.lo, nlo, false, P.second_thresh, err);
+        bt_assign(L, s_lds, a, hbm, L.rows, nr2, L.lo, nlo, false, P.second_thresh, err);
         if (*err) break;
         for (int r = wv; r < nr2; r += NW) {
             const int c = L.mrow[r];
@@ -256,7 +269,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void bytetrack_epoch_kernel(BtArgs a)
 
         // ---- stage 3: unconfirmed x the high band left over, fused, 0.7
         const int nh3 = block_compact(tid < nh && !L.hm[tid], tid < nh ? L.hi[tid] : 0, L.cols, L.wcnt);
-        bt_assign(L, s_lds, a, L.unc, nun, L.cols, nh3, P.fuse != 0, P.unconf_thresh, err);
+        bt_assign(L, s_lds, a, hbm, L.unc, nun, L.cols, nh3, P.fuse != 0, P.unconf_thresh, err);
         if (*err) break;
         for (int r = wv; r < nun; r += NW) {
             const int c = L.mrow[r];
@@ -348,27 +361,27 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void bytetrack_epoch_kernel(BtArgs a)
             BtTrack t;
             t.id = L.id[tid], t.state = L.state[tid], t.act = L.act[tid], t.start = L.start[tid], t.end = L.end[tid], t.cls = L.cls[tid];
             t.score = L.score[tid], t.pad = 0;
-            a.tbl.trk[tid] = t;
+            tbl.trk[tid] = t;
         }
-        for (int i = tid; i < cap * 8; i += BT) a.tbl.mean[i] = L.mean[i];
-        if (tid < ntl) a.tbl.tl[tid] = L.tl[tid];
-        if (tid < nll) a.tbl.ll[tid] = L.ll[tid];
+        for (int i = tid; i < cap * 8; i += BT) tbl.mean[i] = L.mean[i];
+        if (tid < ntl) tbl.tl[tid] = L.tl[tid];
+        if (tid < nll) tbl.ll[tid] = L.ll[tid];
     }
     if (tid == 0) {
-        BtHdr* h = a.tbl.hdr;
+        BtHdr* h = tbl.hdr;
         if (e == 0) h->n_tracked = ntl, h->n_lost = nll, h->next_id = next_id, h->frame_id = frame;
-        else h->err = e, h->err_frame = a.f0 + fi;
+        else h->err = e, h->err_frame = fi;
         h->n_fast += L.wcnt[NW + 1], h->n_lsap += L.wcnt[NW + 2], h->max_side = L.wcnt[NW + 4];
     }
 }
 
 static int bt_lds_bytes() { return 159 * 1024; }
 
-void launch_bytetrack_epoch(const BtTable& tbl, const BtParams& prm, const EpochDets& dets, int f0, int k, float* ext,
-                            const EpochOut& out, hipStream_t s) {
+void launch_bytetrack_epoch(char* bank, size_t table_stride, int streams, const BtParams& prm, const EpochDets& dets, int f0, int k,
+                            const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s) {
     set_lds_limit(bytetrack_epoch_kernel, bt_lds_bytes());
-    BtArgs a{tbl, prm, dets, f0, k, ext, out, bt_lds_bytes()};
-    hipLaunchKernelGGL(bytetrack_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), bt_lds_bytes(), s, a);
+    BtArgs a{bank, table_stride, prm, dets, f0, k, stream_f0, stream_k, frame_stride, ext, out, bt_lds_bytes()};
+    hipLaunchKernelGGL(bytetrack_epoch_kernel, dim3(streams), dim3(TRK_DEV_TMAX), bt_lds_bytes(), s, a);
     KCHECK();
 }
 

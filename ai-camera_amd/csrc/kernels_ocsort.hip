@@ -23,11 +23,15 @@
 namespace aic {
 
 struct OcArgs {
-    OcTable tbl;
+    char* bank;                     // stream s: oc_table(bank + s * table_stride, cap)
+    size_t table_stride;
     OcParams prm;
     EpochDets dets;
-    int f0, k;
-    float* ext;                     // [TRK_DEV_NMAX * TRK_DEV_TMAX] cost matrices that do not fit the LDS arena
+    int f0, k;                      // local frames [f0, f0 + k) of every stream, cut at stream_k[s]
+    const int* stream_f0;           // [streams] local frame i of stream s = row stream_f0[s] + i * frame_stride of dets / out;
+    const int* stream_k;            // [streams] frames of stream s in the call.  Both NULL: one stream, row = local frame
+    int frame_stride;
+    float* ext;                     // [streams][TRK_DEV_NMAX * TRK_DEV_TMAX] cost matrices that do not fit the LDS arena
     EpochOut out;
     int lds_bytes;
 };
@@ -85,7 +89,7 @@ __device__ __forceinline__ OcLds oc_carve(char* base, int total_bytes) {
 //   OC_BYTE:   cost -IoU(det, prediction);   OC_OCR: cost -IoU(det, last observation); both solved only if some IoU exceeds the threshold.
 // A pair stands if its IoU is not below the threshold.  Out: L.mrow[r] = column index or -1.  Returns through *err (2: no finite solution).
 // Ls: the same carve in LDS, what the (noinline) LSAPs get a reference to -- a reference to the kernel's own copy would put it in scratch.
-__device__ void oc_assign(const OcLds& L, const OcLds& Ls, const OcArgs& a, const int* rows, int nr, const int* cols, int nc, int mode, int* err) {
+__device__ void oc_assign(const OcLds& L, const OcLds& Ls, const OcArgs& a, float* hbm, const int* rows, int nr, const int* cols, int nc, int mode, int* err) {
     const int tid = threadIdx.x;
     const float th = a.prm.iou_thresh;
     int* rcnt = L.pred; int* rarg = L.colof; int* ccnt = L.rowof;  // free until the LSAP starts
@@ -94,7 +98,7 @@ __device__ void oc_assign(const OcLds& L, const OcLds& Ls, const OcArgs& a, cons
     if (tid == 0) L.wcnt[NW + W_ANY] = 0;
     __syncthreads();
     if (nr == 0 || nc == 0) return;
-    float* cm = nr * nc <= L.arena_floats ? L.arena : a.ext;
+    float* cm = nr * nc <= L.arena_floats ? L.arena : hbm;
     const float* tbox = mode == OC_OCR ? L.last : L.pbox;
     for (int e = tid; e < nr * nc; e += BT) {
         const int r = e / nc, c = e - r * nc;
@@ -164,28 +168,35 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
     const OcParams& P = a.prm;
     const int cap = P.cap, DT = P.delta_t;
     int* err = L.wcnt + NW + W_ERR;
-    if (a.tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
+    // ---- this block's stream: frame range, table, HBM scratch
+    const int sid = blockIdx.x;
+    const int row0 = a.stream_f0 ? a.stream_f0[sid] : 0;
+    const int kend = a.stream_k ? min(a.f0 + a.k, a.stream_k[sid]) : a.f0 + a.k;
+    if (a.f0 >= kend) return;                                     // nothing for this stream in this epoch: its table is not touched
+    const OcTable tbl = oc_table(a.bank + (size_t)sid * a.table_stride, cap);
+    float* hbm = a.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_TMAX;
+    if (tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
 
     // ---- load the table
-    int nt = a.tbl.hdr->n_tracks, next_id = a.tbl.hdr->next_id, frame = a.tbl.hdr->frame;
+    int nt = tbl.hdr->n_tracks, next_id = tbl.hdr->next_id, frame = tbl.hdr->frame;
     if (tid < cap) {
-        const OcTrack t = a.tbl.trk[tid];
+        const OcTrack t = tbl.trk[tid];
         L.id[tid] = t.id, L.age[tid] = t.age, L.hits[tid] = t.hits, L.streak[tid] = t.streak, L.tsu[tid] = t.tsu, L.cls[tid] = t.cls;
         L.kst[tid] = t.kstate, L.hobs[tid] = t.has_obs, L.hvel[tid] = t.has_vel, L.score[tid] = t.score;
 #pragma unroll
         for (int q = 0; q < 4; ++q) L.last[tid * 4 + q] = t.last[q];
         L.vel[tid * 2] = t.vel[0], L.vel[tid * 2 + 1] = t.vel[1];
     }
-    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = a.tbl.mean[e];
-    if (tid < nt) L.tl[tid] = a.tbl.tl[tid];
+    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = tbl.mean[e];
+    if (tid < nt) L.tl[tid] = tbl.tl[tid];
     if (tid < W_N) L.wcnt[NW + tid] = 0;
     __syncthreads();
-    if (tid == 0) L.wcnt[NW + W_SIDE] = a.tbl.hdr->max_side, L.wcnt[NW + W_GAP] = a.tbl.hdr->max_gap;
+    if (tid == 0) L.wcnt[NW + W_SIDE] = tbl.hdr->max_side, L.wcnt[NW + W_GAP] = tbl.hdr->max_gap;
     __syncthreads();
-    float* cov = a.tbl.cov;
-    int fi = 0;
-    for (; fi < a.k; ++fi) {
-        const int f = a.f0 + fi;
+    float* cov = tbl.cov;
+    int fi = a.f0;
+    for (; fi < kend; ++fi) {
+        const int f = row0 + fi * a.frame_stride;
         ++frame;
         const int n = a.dets.frame_n[f], d0 = a.dets.frame_d0[f];
         if (n > TRK_DEV_NMAX) { if (tid == 0) *err = 3; break; }
@@ -234,9 +245,9 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
                     const int key = age - dt;
                     if (key < 1) continue;
                     const int o = sl * OC_DTMAX + key % DT;
-                    if (a.tbl.ring_age[o] == key) {
+                    if (tbl.ring_age[o] == key) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) q4[q] = a.tbl.ring_box[(size_t)o * 4 + q];
+                        for (int q = 0; q < 4; ++q) q4[q] = tbl.ring_box[(size_t)o * 4 + q];
                         break;
                     }
                 }
@@ -252,7 +263,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
         __syncthreads();
 
         // ---- stage 1: high band x every track
-        oc_assign(L, s_lds, a, L.hi, nh, L.ut, nt, OC_STAGE1, err);
+        oc_assign(L, s_lds, a, hbm, L.hi, nh, L.ut, nt, OC_STAGE1, err);
         if (*err) break;
         if (tid < nh && L.mrow[tid] >= 0) { L.tdet[L.mrow[tid]] = L.hi[tid]; L.dfree[L.hi[tid]] = 0; }
         __syncthreads();
@@ -260,7 +271,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
         // ---- BYTE stage: low band x unmatched tracks, IoU with the prediction
         if (nlo > 0) {
             const int nut = block_compact(tid < nt && L.tdet[tid] < 0, tid, L.ut, L.wcnt);
-            oc_assign(L, s_lds, a, L.lo, nlo, L.ut, nut, OC_BYTE, err);
+            oc_assign(L, s_lds, a, hbm, L.lo, nlo, L.ut, nut, OC_BYTE, err);
             if (*err) break;
             if (tid < nlo && nut > 0 && L.mrow[tid] >= 0) { L.tdet[L.ut[L.mrow[tid]]] = L.lo[tid]; atomicAdd(&L.wcnt[NW + W_BYTE], 1); }
             __syncthreads();
@@ -270,7 +281,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
             const int hj = tid < nh ? L.hi[tid] : 0;
             const int nud = block_compact(tid < nh && L.dfree[hj], hj, L.ud, L.wcnt);
             const int nut = block_compact(tid < nt && L.tdet[tid] < 0, tid, L.ut, L.wcnt);
-            oc_assign(L, s_lds, a, L.ud, nud, L.ut, nut, OC_OCR, err);
+            oc_assign(L, s_lds, a, hbm, L.ud, nud, L.ut, nut, OC_OCR, err);
             if (*err) break;
             if (tid < nud && nut > 0 && L.mrow[tid] >= 0) {
                 L.tdet[L.ut[L.mrow[tid]]] = L.ud[tid];
@@ -285,8 +296,8 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
             const int sl = L.tl[r], d = L.tdet[r], ks = L.kst[sl];
             if (d < 0) {
                 if (ks == KF7_OBSERVED) {                         // freeze: the filter as predicted into the first missed frame
-                    a.tbl.fcov[(size_t)sl * 64 + lane] = cov[(size_t)sl * 64 + lane];
-                    if (lj == 0) a.tbl.fmean[sl * 8 + li] = L.mean[sl * 8 + li];
+                    tbl.fcov[(size_t)sl * 64 + lane] = cov[(size_t)sl * 64 + lane];
+                    if (lj == 0) tbl.fmean[sl * 8 + li] = L.mean[sl * 8 + li];
                 }
                 continue;
             }
@@ -297,7 +308,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
             if (ks == KF7_FROZEN) {
                 // ORU (unfreeze): back to the frozen filter, `gap` virtual observations on the straight line, in (x, y, w, h), from the last
                 // observation to the new one; update, then predict except after the last.  gap <= max_age + 1.
-                p = a.tbl.fcov[(size_t)sl * 64 + lane], m = a.tbl.fmean[sl * 8 + li];
+                p = tbl.fcov[(size_t)sl * 64 + lane], m = tbl.fmean[sl * 8 + li];
                 const int gap = min(L.tsu[sl], P.max_age + 1);
                 float z1[4];
                 bbox_to_z(L.last + sl * 4, z1);
@@ -341,9 +352,9 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
                 }
                 L.kst[sl] = KF7_OBSERVED;
                 const int age = L.age[sl], o = sl * OC_DTMAX + age % DT;
-                a.tbl.ring_age[o] = age;
+                tbl.ring_age[o] = age;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { L.last[sl * 4 + q] = nb[q]; a.tbl.ring_box[(size_t)o * 4 + q] = nb[q]; }
+                for (int q = 0; q < 4; ++q) { L.last[sl * 4 + q] = nb[q]; tbl.ring_box[(size_t)o * 4 + q] = nb[q]; }
                 L.hobs[sl] = 1, L.tsu[sl] = 0, L.hits[sl] += 1, L.streak[sl] += 1;
                 L.score[sl] = L.dconf[d], L.cls[sl] = L.dcls[d];
             }
@@ -366,7 +377,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) { L.last[sl * 4 + q] = -1.f; L.mean[sl * 8 + q] = z[q]; L.mean[sl * 8 + 4 + q] = 0.f; }
             L.vel[sl * 2] = 0.f, L.vel[sl * 2 + 1] = 0.f;
-            for (int q = 0; q < OC_DTMAX; ++q) a.tbl.ring_age[sl * OC_DTMAX + q] = -1;
+            for (int q = 0; q < OC_DTMAX; ++q) tbl.ring_age[sl * OC_DTMAX + q] = -1;
             L.tl[nt + tid] = sl;
         }
         for (int e = tid; e < nnew * 64; e += BT) {
@@ -409,15 +420,15 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) t.last[q] = L.last[tid * 4 + q];
             t.vel[0] = L.vel[tid * 2], t.vel[1] = L.vel[tid * 2 + 1];
-            a.tbl.trk[tid] = t;
+            tbl.trk[tid] = t;
         }
-        for (int i = tid; i < cap * 8; i += BT) a.tbl.mean[i] = L.mean[i];
-        if (tid < nt) a.tbl.tl[tid] = L.tl[tid];
+        for (int i = tid; i < cap * 8; i += BT) tbl.mean[i] = L.mean[i];
+        if (tid < nt) tbl.tl[tid] = L.tl[tid];
     }
     if (tid == 0) {
-        OcHdr* h = a.tbl.hdr;
+        OcHdr* h = tbl.hdr;
         if (e == 0) h->n_tracks = nt, h->next_id = next_id, h->frame = frame;
-        else h->err = e, h->err_frame = a.f0 + fi;
+        else h->err = e, h->err_frame = fi;
         h->n_fast += L.wcnt[NW + W_FAST], h->n_lsap += L.wcnt[NW + W_LSAP], h->max_side = L.wcnt[NW + W_SIDE];
         h->n_oru += L.wcnt[NW + W_ORU], h->max_gap = L.wcnt[NW + W_GAP], h->n_ocr += L.wcnt[NW + W_OCR], h->n_byte += L.wcnt[NW + W_BYTE];
     }
@@ -425,11 +436,11 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
 
 static int oc_lds_bytes() { return 159 * 1024; }
 
-void launch_ocsort_epoch(const OcTable& tbl, const OcParams& prm, const EpochDets& dets, int f0, int k, float* ext, const EpochOut& out,
-                         hipStream_t s) {
+void launch_ocsort_epoch(char* bank, size_t table_stride, int streams, const OcParams& prm, const EpochDets& dets, int f0, int k,
+                         const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s) {
     set_lds_limit(ocsort_epoch_kernel, oc_lds_bytes());
-    OcArgs a{tbl, prm, dets, f0, k, ext, out, oc_lds_bytes()};
-    hipLaunchKernelGGL(ocsort_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), oc_lds_bytes(), s, a);
+    OcArgs a{bank, table_stride, prm, dets, f0, k, stream_f0, stream_k, frame_stride, ext, out, oc_lds_bytes()};
+    hipLaunchKernelGGL(ocsort_epoch_kernel, dim3(streams), dim3(TRK_DEV_TMAX), oc_lds_bytes(), s, a);
     KCHECK();
 }
 

@@ -1,10 +1,11 @@
 // ocsort.hpp -- OC-SORT on the device (OCSort.update of the OC-SORT authors, restated in tests/ocsort_oracle.py): the structures shared
-// by kernels_ocsort.hip (the one-block epoch kernel) and ocsort.cpp (tracker object, pipeline hook).
+// by kernels_ocsort.hip (the epoch kernel, one block per stream) and ocsort.cpp (tracker object, pipeline hook).
 //
 // The track table lives in HBM between launches, indexed by SLOT:
 //   OcHdr | OcTrack[cap] | track list[cap] (slots, list order) | mean[cap][8] | cov[cap][64] | frozen mean[cap][8] | frozen cov[cap][64]
 //   | ring age[cap][OC_DTMAX] | ring box[cap][OC_DTMAX][4]
-// (7-state filter stored with a pitch of 8: lane (i, j) of a wavefront <-> P[i][j]).  An epoch launch (ONE block of 512 threads) loads the
+// (7-state filter stored with a pitch of 8: lane (i, j) of a wavefront <-> P[i][j]).  A bank holds the tables of its streams
+// `table_stride` bytes apart in one allocation.  An epoch launch (ONE block of 512 threads per stream) loads the
 // scalars, the list and the means into LDS, walks k <= TRK_KMAX frames with no host round trip and writes them back.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,7 +56,7 @@ struct OcTable {                    // device pointers into one allocation
 static inline size_t oc_table_bytes(int cap) {
     return 64 + (size_t)cap * (sizeof(OcTrack) + 4 + 2 * (4 * 8 + 4 * 64) + OC_DTMAX * 4 + OC_DTMAX * 16);
 }
-static inline OcTable oc_table(char* base, int cap) {
+__host__ __device__ static inline OcTable oc_table(char* base, int cap) {
     OcTable t;
     t.hdr = reinterpret_cast<OcHdr*>(base);
     t.trk = reinterpret_cast<OcTrack*>(base + 64);
@@ -69,8 +70,9 @@ static inline OcTable oc_table(char* base, int cap) {
     return t;
 }
 
-// one launch: frames [f0, f0 + k) of the group; ext = [TRK_DEV_NMAX * TRK_DEV_TMAX] HBM scratch for cost matrices that do not fit the LDS
-void launch_ocsort_epoch(const OcTable& tbl, const OcParams& prm, const EpochDets& dets, int f0, int k, float* ext, const EpochOut& out,
-                         hipStream_t s);
+// one launch, one block per stream of the bank: frame ranges and rows as launch_bytetrack_epoch (bytetrack.hpp);
+// ext = [streams][TRK_DEV_NMAX * TRK_DEV_TMAX] HBM scratch for cost matrices that do not fit the LDS
+void launch_ocsort_epoch(char* bank, size_t table_stride, int streams, const OcParams& prm, const EpochDets& dets, int f0, int k,
+                         const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s);
 
 }  // namespace aic

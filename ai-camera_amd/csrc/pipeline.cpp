@@ -167,6 +167,8 @@ struct Pipeline {
     std::mutex x_mu;
     std::condition_variable x_cv;
     int group_frames = 0;            // frames per launch group (aic_pipeline_option("group_frames")); 0 = prm.batch
+    int trk_cus = 2;                 // CUs at most that persistent conv grids leave to the epoch blocks of a bank of streams: min(streams, trk_cus)
+                                     // (aic_pipeline_option("tracker_cus"); measured: DESIGN.md section 22)
     struct GroupTime { int frames; double submit, done; };
     std::vector<GroupTime> group_times;   // per launch group of the last call: stage A start -> track tuples on the host
     std::vector<double> submit_t;
@@ -803,17 +805,21 @@ struct Pipeline {
              float* det_scores, int32_t* det_labels, int passes = 1) {
         AIC_REQUIRE(slot >= 0 && count >= 0 && slot + count <= prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
         AIC_REQUIRE(passes >= 1, AIC_ERR_INVALID, "passes must be >= 1");
+        const int S = bt ? bt->streams() : 1;    // > 1: ring and run ranges are tick-major over S streams
+        AIC_REQUIRE(slot % S == 0 && count % S == 0, AIC_ERR_INVALID, "slot and count must be multiples of the pipeline's streams");
         dev->use();
         if (count <= 0) return;
-        // the association epoch kernel holds one CU while the next group's convs run: persistent conv grids leave it free
-        set_conv_cu_budget(bt || (dev_assoc && trk.dev_capable()) ? dev->n_cu - 1 : dev->n_cu);
+        // the association epoch kernel holds one CU (a bank: one per stream, trk_cus at most) while the next group's convs run:
+        // persistent conv grids leave them free
+        set_conv_cu_budget(bt || (dev_assoc && trk.dev_capable()) ? dev->n_cu - std::max(1, std::min(S, trk_cus)) : dev->n_cu);
         tracks_seen = trk.on_device ? tracks_seen.load() : (int)trk.tracks.size();
         for (auto& c : ck) c.tracks_after = tracks_seen;
         // Launch groups: full batches, then the last batch tapered (1/2, 1/4, ... down to 16 frames): stage B of the
         // final group cannot overlap any GPU work, so a short final group shortens the un-overlapped tail of the call.
         std::vector<int> goff, glen;
         {
-            const int gf = group_frames > 0 ? std::min(group_frames, prm.batch) : prm.batch;
+            auto ticks = [S](int g) { return S > 1 ? std::max(S, g / S * S) : g; };   // a launch group holds whole ticks of every stream
+            const int gf = ticks(group_frames > 0 ? std::min(group_frames, prm.batch) : prm.batch);
             for (int pass = 0; pass < passes; ++pass) {
                 const bool last = pass == passes - 1;
                 int done = 0;
@@ -822,11 +828,14 @@ struct Pipeline {
                 // therefore opens with a ramp of small groups (gf/16, gf/8, ... gf/2): compute starts after the first 32 frames' copy and
                 // every later copy runs under the group before it.  aic_pipeline_option("head_ramp", 0): off.
                 if (pass == 0 && host_frames && head_ramp && gf >= 64)
-                    for (int g = std::max(16, gf / 16); g < gf && count - done > g + gf; g *= 2) { goff.push_back(done); glen.push_back(g); done += g; }
+                    for (int g0 = std::max(16, gf / 16); g0 < gf && count - done > ticks(g0) + gf; g0 *= 2) {
+                        const int g = ticks(g0);
+                        goff.push_back(done); glen.push_back(g); done += g;
+                    }
                 while (count - done > gf) { goff.push_back(done); glen.push_back(gf); done += gf; }
                 int rem = count - done;
                 while (taper && last && rem > 16) {
-                    const int g = std::max(16, rem / 2);
+                    const int g = ticks(std::max(16, rem / 2));
                     if (rem - g < 8) break;
                     goff.push_back(done); glen.push_back(g); done += g; rem -= g;
                 }
@@ -1179,6 +1188,14 @@ int aic_pipeline_exchange_done(aic_pipeline* p, int64_t seq) {
     });
 }
 
+int aic_pipeline_reset_stream(aic_pipeline* p, int stream) {
+    return guarded([&] {
+        AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
+        AIC_REQUIRE(p->p.bt && !p->p.bs, AIC_ERR_INVALID, "reset_stream applies to ByteTrack and OC-SORT pipelines only");
+        p->p.bt->reset_stream(stream);
+    });
+}
+
 int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
     return guarded([&] {
         AIC_REQUIRE(p && key, AIC_ERR_INVALID, "NULL argument");
@@ -1213,6 +1230,16 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
         else if (k == "in_flight") {
             AIC_REQUIRE(value >= 2 && value <= Pipeline::NCK, AIC_ERR_INVALID, "in_flight: 2 or 3 launch groups");
             p->p.nck = value;
+        }
+        else if (k == "streams") {
+            AIC_REQUIRE(p->p.bt && !p->p.bs, AIC_ERR_INVALID, "option streams applies to ByteTrack and OC-SORT pipelines only");
+            AIC_REQUIRE(value >= 1 && value <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+            AIC_REQUIRE(p->p.prm.batch % value == 0, AIC_ERR_INVALID, "batch must be a multiple of streams");
+            p->p.bt->set_streams(value);
+        }
+        else if (k == "tracker_cus") {               // measurements: the CU reserve of a bank's epoch blocks
+            AIC_REQUIRE(value >= 1 && value <= 64, AIC_ERR_INVALID, "tracker_cus must be in 1..64");
+            p->p.trk_cus = value;
         }
         else if (k == "group_frames") {
             AIC_REQUIRE(value >= 0 && value <= p->p.prm.batch, AIC_ERR_INVALID, "group_frames must be in 0..batch");

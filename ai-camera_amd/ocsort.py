@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from . import config
+from .bytetrack import TrackerBank
 
 
 def ocsort_params(det_thresh=0.6, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3, inertia=0.2, use_byte=False,
@@ -114,4 +115,36 @@ class OCSort:
         out.update(score=np.zeros(m, np.float32), last_observation=np.zeros((m, 4), np.float32), velocity=np.zeros((m, 2), np.float32),
                    mean=np.zeros((m, 7), np.float32), cov=np.zeros((m, 7, 7), np.float32))
         L.call("aic_ocsort_export", self._h, m, *(L.ptr(out[k]) for k in self.KEYS), C.byref(n))
+        return out
+
+
+class OCSortBank(TrackerBank):
+    """OCSortBank(streams, **OCSort's arguments): the OC-SORT state of `streams` cameras on one device (bytetrack.TrackerBank)."""
+    _abi = "aic_ocsort_bank"
+
+    def __init__(self, streams, det_thresh=0.6, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3, inertia=0.2, use_byte=False, device=0,
+                 max_tracks=512, first_track_id=1):
+        self.params = ocsort_params(det_thresh, max_age, min_hits, iou_threshold, delta_t, inertia, use_byte, max_tracks,
+                                    first_track_id)
+        self.max_tracks = max_tracks
+        self._create(streams, device)
+
+    def counters(self, stream):
+        """OCSort.counters() of one stream."""
+        nf, nl, no, nr, nb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        ms, mg = C.c_int32(), C.c_int32()
+        L.call("aic_ocsort_bank_counters", self._h, int(stream), C.byref(nf), C.byref(nl), C.byref(ms), C.byref(no), C.byref(mg),
+               C.byref(nr), C.byref(nb))
+        return dict(n_fast=nf.value, n_lsap=nl.value, max_side=ms.value, n_oru=no.value, max_gap=mg.value, n_ocr=nr.value,
+                    n_byte=nb.value)
+
+    def export(self, stream):
+        """OCSort.export() of one stream; raises for a stopped stream."""
+        n = C.c_int32()
+        L.call("aic_ocsort_bank_export", self._h, int(stream), 0, *([None] * 13), C.byref(n))
+        m = n.value
+        out = {k: np.zeros(m, np.int32) for k in OCSort.KEYS[:8]}
+        out.update(score=np.zeros(m, np.float32), last_observation=np.zeros((m, 4), np.float32), velocity=np.zeros((m, 2), np.float32),
+                   mean=np.zeros((m, 7), np.float32), cov=np.zeros((m, 7, 7), np.float32))
+        L.call("aic_ocsort_bank_export", self._h, int(stream), m, *(L.ptr(out[k]) for k in OCSort.KEYS), C.byref(n))
         return out

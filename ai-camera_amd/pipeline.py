@@ -19,7 +19,7 @@ class TrackingPipeline:
                  max_det=config.YOLO_MAX_DET, min_confidence=config.DEEPSORT_MIN_CONFIDENCE, inject=False,
                  max_cosine_distance=config.DEEPSORT_MAX_DIST, nn_budget=config.DEEPSORT_NN_BUDGET,
                  max_iou_distance=config.DEEPSORT_MAX_IOU_DISTANCE, max_age=config.DEEPSORT_MAX_AGE,
-                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, **bytetrack_params):
+                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, streams=1, **bytetrack_params):
         """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
         not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
         conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
@@ -30,7 +30,12 @@ class TrackingPipeline:
         in HBM and feed the epoch kernel; the extra arguments are BoTSORT's (track_high_thresh, track_low_thresh, new_track_thresh,
         match_thresh, proximity_thresh, appearance_thresh, track_buffer, frame_rate, fuse_score, with_reid, feat_alpha), and conf_thresh
         defaults to track_low_thresh.  gmc=2 or 4 (BoT-SORT only): the camera motion of every frame is estimated on the device at that
-        downscale (aic_pipeline_option "gmc", gmc.py) and warps the predicted tracks; group_warps() reads the last group's."""
+        downscale (aic_pipeline_option "gmc", gmc.py) and warps the predicted tracks; group_warps() reads the last group's.
+        streams=S (ByteTrack / OC-SORT only): one pipeline for S cameras.  The ring and every run range are tick-major, slot t * S + s
+        being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams."""
+        self.streams = int(streams)
+        if self.streams != 1 and tracker not in ("bytetrack", "ocsort"):
+            raise ValueError("streams needs tracker='bytetrack' or 'ocsort'")
         if gmc and tracker != "botsort":
             raise ValueError("gmc needs tracker='botsort'")
         if tracker not in ("deepsort", "bytetrack", "ocsort", "botsort"):
@@ -59,6 +64,8 @@ class TrackingPipeline:
             L.call("aic_pipeline_create_bytetrack", self.yolo._h, C.byref(self.params), C.byref(self.bytetrack_params),
                    C.byref(self._h))
             self.tracker_core = None
+            if self.streams != 1:
+                self.option("streams", self.streams)
             return
         if tracker == "ocsort":
             from .ocsort import ocsort_params as _ocp
@@ -75,6 +82,8 @@ class TrackingPipeline:
             self._h = C.c_void_p()
             L.call("aic_pipeline_create_ocsort", self.yolo._h, C.byref(self.params), C.byref(self.ocsort_params), C.byref(self._h))
             self.tracker_core = None
+            if self.streams != 1:
+                self.option("streams", self.streams)
             return
         if tracker == "botsort":
             from .botsort import botsort_params as _bsp
@@ -109,6 +118,10 @@ class TrackingPipeline:
         L.call("aic_pipeline_tracker", self._h, C.byref(th))
         self.tracker_core = TrackerCore._from_handle(th, tp)
         self.tracker_core._dim = self.reid.out_dim
+
+    def reset_stream(self, s):
+        """streams=S pipelines, between run calls: stream s as after creation (a camera reconnecting)."""
+        L.call("aic_pipeline_reset_stream", self._h, int(s))
 
     def close(self):
         for b in getattr(self, "_staging", []):

@@ -55,6 +55,8 @@ typedef struct aic_bytetrack aic_bytetrack; /* ByteTrack state of one video stre
 typedef struct aic_botsort aic_botsort;     /* BoT-SORT state of one video stream           */
 typedef struct aic_gmc aic_gmc;             /* camera-motion estimator of one video stream  */
 typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream            */
+typedef struct aic_bytetrack_bank aic_bytetrack_bank; /* ByteTrack state of 1..256 streams    */
+typedef struct aic_ocsort_bank aic_ocsort_bank;       /* OC-SORT state of 1..256 streams      */
 
 /* ------------------------------------------------------------------ library / device */
 const char* aic_last_error(void);
@@ -323,6 +325,31 @@ int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* 
                          int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* n_tracks,
                          int32_t* n_tracked);
 
+/* A bank: `streams` (1..256) independent ByteTrack streams on one device, e.g. the cameras of one installation.  Every epoch launch runs
+ * one kernel block per stream, so a tick of all cameras costs one staging upload, one launch and one sync instead of `streams` of each.
+ * Parameters and first_track_id apply to every stream (ids are counted per stream); each stream computes exactly what an aic_bytetrack
+ * fed the same frames computes.  AIC_ERR_INVALID for streams outside 1..256 and as aic_bytetrack_create (checked before the device). */
+int aic_bytetrack_bank_create(int device, const aic_bytetrack_params* p, int streams, aic_bytetrack_bank** out);
+int aic_bytetrack_bank_destroy(aic_bytetrack_bank* b);
+/* "lsap_fast", "epoch_frames" as aic_bytetrack_option, for the whole bank. */
+int aic_bytetrack_bank_option(aic_bytetrack_bank* b, const char* key, int value);
+/* frames_per_stream[streams] consecutive frames of every stream (0 and more than 16 are fine), F in all, stream-major: stream 0's frames,
+ * then stream 1's, ...  counts[F], the detection arrays and the per-frame outputs n_out[F], out6[F,cap_rows,6], out_conf[F,cap_rows] are as
+ * aic_bytetrack_update_batch.  A negative count or more than 512 detections in a frame rejects the whole call before anything is launched.
+ * A stream that meets a capacity error is stopped alone: its frames from the failing one on (and every frame handed to it later) get
+ * n_out = 0, the other streams' frames are processed.  status[streams] non-NULL: the call returns AIC_OK and status holds 0 or the error
+ * code per stream; status NULL: the call returns the code of the lowest failing stream that was handed frames (the message names it). */
+int aic_bytetrack_bank_update(aic_bytetrack_bank* b, const int32_t* frames_per_stream, const int32_t* counts, const float* boxes_xyxy,
+                              const float* conf, const int32_t* cls, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf,
+                              int32_t* status);
+/* The stream as after create (no tracks, ids from first_track_id again), a stop cleared: a camera reconnecting. */
+int aic_bytetrack_bank_reset(aic_bytetrack_bank* b, int stream);
+/* As aic_bytetrack_export / aic_bytetrack_counters for one stream; export fails with AIC_ERR_INVALID for a stopped stream only. */
+int aic_bytetrack_bank_export(aic_bytetrack_bank* b, int stream, int cap, int32_t* track_id, int32_t* state, int32_t* is_activated,
+                              int32_t* start_frame, int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov,
+                              int32_t* n_tracks, int32_t* n_tracked);
+int aic_bytetrack_bank_counters(aic_bytetrack_bank* b, int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side);
+
 /* ------------------------------------------------------------------ OC-SORT
  * OCSort.update() of the OC-SORT authors (ocsort.py, association.py, kalmanfilter.py) on the device, k frames per launch
  * (csrc/kernels_ocsort.hip; specification: tests/ocsort_oracle.py, deviations: DESIGN.md "OC-SORT").  No appearance model: SORT's 7-state
@@ -362,6 +389,20 @@ int aic_ocsort_export(aic_ocsort* t, int cap, int32_t* track_id, int32_t* age, i
  * and their longest gap, pairs made by the OCR stage and by the BYTE stage. */
 int aic_ocsort_counters(aic_ocsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_oru, int32_t* max_gap,
                         int64_t* n_ocr, int64_t* n_byte);
+
+/* A bank of `streams` (1..256) OC-SORT streams: every call as its aic_bytetrack_bank_* counterpart, per-stream arrays as aic_ocsort_*. */
+int aic_ocsort_bank_create(int device, const aic_ocsort_params* p, int streams, aic_ocsort_bank** out);
+int aic_ocsort_bank_destroy(aic_ocsort_bank* b);
+int aic_ocsort_bank_option(aic_ocsort_bank* b, const char* key, int value);
+int aic_ocsort_bank_update(aic_ocsort_bank* b, const int32_t* frames_per_stream, const int32_t* counts, const float* boxes_xyxy,
+                           const float* conf, const int32_t* cls, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf,
+                           int32_t* status);
+int aic_ocsort_bank_reset(aic_ocsort_bank* b, int stream);
+int aic_ocsort_bank_export(aic_ocsort_bank* b, int stream, int cap, int32_t* track_id, int32_t* age, int32_t* hits, int32_t* hit_streak,
+                           int32_t* time_since_update, int32_t* cls, int32_t* frozen, int32_t* has_obs, float* score,
+                           float* last_observation, float* velocity, float* mean, float* cov, int32_t* n_tracks);
+int aic_ocsort_bank_counters(aic_ocsort_bank* b, int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_oru,
+                             int32_t* max_gap, int64_t* n_ocr, int64_t* n_byte);
 
 /* ------------------------------------------------------------------ BoT-SORT
  * BoTSORT.update() with ReID of the BoT-SORT authors (tracker/bot_sort.py, matching.py, kalman_filter.py) on the device, k frames per
@@ -569,8 +610,13 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
  * "gmc" (a BoT-SORT pipeline only; AIC_ERR_INVALID on any other): 0 (default) = no camera-motion warp, 2 or 4 = the camera motion of
  * every frame is estimated on the device at that downscale (as aic_gmc_estimate_batch, the boxes being the detections handed to the
  * tracker) and warps the predicted tracks.  The gray levels are computed in the group's launch group, matching and fit run on the
- * tracker stream before the group's epochs; the stream's first frame gets the identity.  With 0 nothing of it is launched or allocated. */
+ * tracker stream before the group's epochs; the stream's first frame gets the identity.  With 0 nothing of it is launched or allocated.
+ * "streams" (ByteTrack and OC-SORT pipelines only; 1..256, default 1; set before the first run): the ring and every run range are
+ * tick-major over that many camera streams, slot t * streams + s being tick t of stream s, and the tracker is a bank (one kernel block
+ * per stream).  `batch` must be a multiple of it, as must slot and count of every run call; launch groups round to whole ticks. */
 int aic_pipeline_option(aic_pipeline* p, const char* key, int value);
+/* A pipeline with "streams": stream s as after create (aic_bytetrack_bank_reset), between run calls. */
+int aic_pipeline_reset_stream(aic_pipeline* p, int stream);
 /* The warps [n_frames, 6] (as aic_gmc_estimate_batch) of the most recently finished launch group of a pipeline with "gmc" set;
  * AIC_ERR_INVALID without it.  warps may be NULL; *n_frames is the group's frame count, at most cap_frames rows are written. */
 int aic_pipeline_group_warps(aic_pipeline* p, float* warps, int cap_frames, int32_t* n_frames);
