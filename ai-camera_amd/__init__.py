@@ -30,6 +30,10 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.ocsort").OCSortBank
     if name == "BoTSORT":
         return _importlib.import_module(f"{__name__}.botsort").BoTSORT
+    if name == "BoTSORTBank":
+        return _importlib.import_module(f"{__name__}.botsort").BoTSORTBank
+    if name == "CameraMotionBank":
+        return _importlib.import_module(f"{__name__}.gmc").CameraMotionBank
     if name == "CameraMotion":
         return _importlib.import_module(f"{__name__}.gmc").CameraMotion
     raise AttributeError(name)

@@ -195,6 +195,18 @@ _SIGS = {
     "aic_gmc_reset": (_I, [_P]),
     "aic_gmc_estimate_batch": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "aic_pipeline_group_warps": (_I, [_P, _P, _I, _P]),
+    "aic_botsort_bank_create": (_I, [_I, _P, _I, _P]),
+    "aic_botsort_bank_destroy": (_I, [_P]),
+    "aic_botsort_bank_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_botsort_bank_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "aic_botsort_bank_reset": (_I, [_P, _I]),
+    "aic_botsort_bank_export": (_I, [_P, _I, _I] + [_P] * 13),
+    "aic_botsort_bank_counters": (_I, [_P, _I] + [_P] * 6),
+    "aic_gmc_bank_create": (_I, [_I, _I, _I, _P, _I, _P]),
+    "aic_gmc_bank_destroy": (_I, [_P]),
+    "aic_gmc_bank_reset": (_I, [_P, _I]),
+    "aic_gmc_bank_estimate": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "aic_pipeline_create_botsort_bank": (_I, [_P, _P, _P, _P, _I, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

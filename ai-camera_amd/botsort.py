@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from . import config
+from .bytetrack import TrackerBank
 
 
 def botsort_params(track_high_thresh=0.6, track_low_thresh=0.1, new_track_thresh=0.7, match_thresh=0.8, proximity_thresh=0.5,
@@ -26,6 +27,39 @@ def botsort_params(track_high_thresh=0.6, track_low_thresh=0.1, new_track_thresh
                            feat_alpha=float(feat_alpha), track_buffer=int(track_buffer), frame_rate=int(frame_rate),
                            fuse_score=1 if fuse_score else 0, with_reid=1 if with_reid else 0, feature_dim=int(feature_dim),
                            max_tracks=int(max_tracks), first_track_id=int(first_track_id))
+
+
+def _pack_frames(frames, feature_dim):
+    """The frame tuples of BoTSORT.update_batch_arrays as the C ABI's flat arrays: counts, xyxy, conf, cls, feat, valid, warps."""
+    frames = [tuple(f) + (None,) * (6 - len(f)) for f in frames]
+    boxes = [np.asarray(f[0], dtype=np.float32).reshape(-1, 4) for f in frames]
+    scores = [np.asarray(f[1], dtype=np.float32).reshape(-1) for f in frames]
+    cids = [np.asarray(f[2]).reshape(-1).astype(np.int32) for f in frames]
+    counts = np.array([len(b) for b in boxes], dtype=np.int32)
+    for b, s, c in zip(boxes, scores, cids):
+        if not (len(b) == len(s) == len(c)):
+            raise ValueError("boxes, scores and class ids differ in length")
+    total = int(counts.sum())
+    with_feat = [f[3] is not None for f in frames]
+    if any(with_feat) and not all(w or n == 0 for w, n in zip(with_feat, counts)):
+        raise ValueError("features must be given for every frame of a call or for none")
+    feat = None
+    if any(with_feat) and total:
+        fs = [np.asarray(f[3], dtype=np.float32).reshape(n, feature_dim) for f, n in zip(frames, counts) if n]
+        feat = np.ascontiguousarray(np.concatenate(fs))
+    valid = None
+    if any(f[5] is not None for f in frames):
+        valid = np.ascontiguousarray(np.concatenate([np.ones(n, np.int32) if f[5] is None else
+                                                     np.asarray(f[5]).reshape(n).astype(np.int32) for f, n in zip(frames, counts)]))
+    warps = None
+    if any(f[4] is not None for f in frames):
+        eye = np.array([[1, 0, 0], [0, 1, 0]], np.float32)
+        warps = np.ascontiguousarray(np.stack([eye if f[4] is None else np.asarray(f[4], dtype=np.float32).reshape(2, 3)
+                                               for f in frames]))
+    xyxy = np.ascontiguousarray(np.concatenate(boxes) if total else np.zeros((0, 4), np.float32))
+    conf = np.ascontiguousarray(np.concatenate(scores) if total else np.zeros(0, np.float32))
+    cls = np.ascontiguousarray(np.concatenate(cids) if total else np.zeros(0, np.int32))
+    return counts, xyxy, conf, cls, feat, valid, warps
 
 
 class BoTSORT:
@@ -63,35 +97,8 @@ class BoTSORT:
         k = len(frames)
         if k == 0:
             return []
-        frames = [tuple(f) + (None,) * (6 - len(f)) for f in frames]
-        boxes = [np.asarray(f[0], dtype=np.float32).reshape(-1, 4) for f in frames]
-        scores = [np.asarray(f[1], dtype=np.float32).reshape(-1) for f in frames]
-        cids = [np.asarray(f[2]).reshape(-1).astype(np.int32) for f in frames]
-        counts = np.array([len(b) for b in boxes], dtype=np.int32)
-        for b, s, c in zip(boxes, scores, cids):
-            if not (len(b) == len(s) == len(c)):
-                raise ValueError("boxes, scores and class ids differ in length")
-        total = int(counts.sum())
-        with_feat = [f[3] is not None for f in frames]
-        if any(with_feat) and not all(w or n == 0 for w, n in zip(with_feat, counts)):
-            raise ValueError("features must be given for every frame of a call or for none")
-        feat = None
-        if any(with_feat) and total:
-            fs = [np.asarray(f[3], dtype=np.float32).reshape(n, self.feature_dim) for f, n in zip(frames, counts) if n]
-            feat = np.ascontiguousarray(np.concatenate(fs))
-        valid = None
-        if any(f[5] is not None for f in frames):
-            valid = np.ascontiguousarray(np.concatenate([np.ones(n, np.int32) if f[5] is None else
-                                                         np.asarray(f[5]).reshape(n).astype(np.int32) for f, n in zip(frames, counts)]))
-        warps = None
-        if any(f[4] is not None for f in frames):
-            eye = np.array([[1, 0, 0], [0, 1, 0]], np.float32)
-            warps = np.ascontiguousarray(np.stack([eye if f[4] is None else np.asarray(f[4], dtype=np.float32).reshape(2, 3)
-                                                   for f in frames]))
+        counts, xyxy, conf, cls, feat, valid, warps = _pack_frames(frames, self.feature_dim)
         cap = int(cap_rows if cap_rows is not None else self.max_tracks or 512)
-        xyxy = np.ascontiguousarray(np.concatenate(boxes) if total else np.zeros((0, 4), np.float32))
-        conf = np.ascontiguousarray(np.concatenate(scores) if total else np.zeros(0, np.float32))
-        cls = np.ascontiguousarray(np.concatenate(cids) if total else np.zeros(0, np.int32))
         n_out = np.zeros(k, np.int32)
         out6 = np.zeros((k, cap, 6), np.int32)
         oconf = np.zeros((k, cap), np.float32)
@@ -132,5 +139,63 @@ class BoTSORT:
                    score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32),
                    has_feat=np.zeros(m, np.int32), smooth_feat=np.zeros((m, self.feature_dim), np.float32))
         L.call("aic_botsort_export", self._h, m, *(L.ptr(v) for v in out.values()), C.byref(n), C.byref(nt))
+        out["n_tracked"] = nt.value
+        return out
+
+
+class BoTSORTBank(TrackerBank):
+    """BoTSORTBank(streams, device=0, **BoTSORT's parameters): the BoT-SORT state of `streams` cameras on one device, one kernel block
+    per stream and launch.  Every stream has its own table, smoothed features and ids and computes exactly what a BoTSORT fed the same
+    frames computes; a stream that meets a capacity error stops alone, and reset(stream) starts it afresh."""
+    _abi = "aic_botsort_bank"
+
+    def __init__(self, streams, device=0, **params):
+        self.params = botsort_params(**params)
+        self.max_tracks = self.params.max_tracks
+        self.feature_dim = self.params.feature_dim or 512
+        self._create(streams, device)
+
+    def update_arrays(self, per_stream_frames, cap_rows=None):
+        """per_stream_frames: `streams` lists of BoTSORT.update_batch_arrays' frame tuples, any length each; features are all-or-nothing
+        over the call.  Returns `streams` lists of (rows [m,6] int32, conf [m] fp32) per frame, None in place of a stopped stream's."""
+        if len(per_stream_frames) != self.streams:
+            raise ValueError(f"{len(per_stream_frames)} frame lists for a bank of {self.streams} streams")
+        flat = [fr for frames in per_stream_frames for fr in frames]
+        fps = np.array([len(frames) for frames in per_stream_frames], dtype=np.int32)
+        k = len(flat)
+        counts, xyxy, conf, cls, feat, valid, warps = _pack_frames(flat, self.feature_dim)
+        cap = int(cap_rows if cap_rows is not None else self.max_tracks or 512)
+        n_out = np.zeros(max(k, 1), np.int32)
+        out6 = np.zeros((max(k, 1), cap, 6), np.int32)
+        oconf = np.zeros((max(k, 1), cap), np.float32)
+        status = np.zeros(self.streams, np.int32)
+        L.call("aic_botsort_bank_update", self._h, L.ptr(fps), L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), L.ptr(feat),
+               L.ptr(valid), L.ptr(warps), cap, L.ptr(n_out), L.ptr(out6), L.ptr(oconf), L.ptr(status))
+        return self._unpack(fps, n_out, out6, oconf, status, cap)
+
+    def update(self, per_stream_detections):
+        """One tick: `streams` entries (boxes_xyxy, scores, class_ids[, features[, warp]]), None = no frame from that camera this
+        tick.  Returns `streams` lists of (x1, y1, x2, y2, track_id, class_name, conf) tuples, None for a stopped stream."""
+        got = self.update_arrays([[] if d is None else [d] for d in per_stream_detections])
+        return [None if g is None else (BoTSORT._tuples(*g[0]) if g else []) for g in got]
+
+    def counters(self, stream):
+        """BoTSORT.counters() of one stream."""
+        nf, nl, ms, na, cc, ck = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.call("aic_botsort_bank_counters", self._h, int(stream), C.byref(nf), C.byref(nl), C.byref(ms), C.byref(na), C.byref(cc),
+               C.byref(ck))
+        return dict(n_fast=nf.value, n_lsap=nl.value, max_side=ms.value, n_appearance=na.value, cost_cycles=cc.value,
+                    kernel_cycles=ck.value)
+
+    def export(self, stream):
+        """BoTSORT.export() of one stream; raises for a stopped stream."""
+        n, nt = C.c_int32(), C.c_int32()
+        L.call("aic_botsort_bank_export", self._h, int(stream), 0, *([None] * 11), C.byref(n), C.byref(nt))
+        m = n.value
+        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
+                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
+                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32),
+                   has_feat=np.zeros(m, np.int32), smooth_feat=np.zeros((m, self.feature_dim), np.float32))
+        L.call("aic_botsort_bank_export", self._h, int(stream), m, *(L.ptr(v) for v in out.values()), C.byref(n), C.byref(nt))
         out["n_tracked"] = nt.value
         return out

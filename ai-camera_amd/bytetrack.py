@@ -114,7 +114,7 @@ class BYTETracker:
 
 
 class TrackerBank:
-    """What BYTETrackerBank and OCSortBank share: `streams` independent streams on one device, one kernel block per stream and
+    """What BYTETrackerBank, OCSortBank and BoTSORTBank share: `streams` independent streams on one device, one kernel block per stream and
     launch.  Every stream computes exactly what the single class fed the same frames computes; a stream that meets a capacity
     error stops alone (`failed`), the others go on, and reset(stream) starts it afresh."""
     _abi = None                                                  # "aic_bytetrack_bank" / "aic_ocsort_bank"
@@ -171,6 +171,10 @@ class TrackerBank:
         status = np.zeros(self.streams, np.int32)
         L.call(self._abi + "_update", self._h, L.ptr(fps), L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), cap, L.ptr(n_out),
                L.ptr(out6), L.ptr(oconf), L.ptr(status))
+        return self._unpack(fps, n_out, out6, oconf, status, cap)
+
+    def _unpack(self, fps, n_out, out6, oconf, status, cap):
+        """The flat outputs of a bank update as `streams` lists of (rows, conf) per frame; a stopped stream is noted and gets None."""
         res, f = [], 0
         for s in range(self.streams):
             if status[s] and s not in self.failed:

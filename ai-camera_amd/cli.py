@@ -41,7 +41,7 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="AICamera: Real-time Object Detection & Tracking (MI355X engine)")
     p.add_argument("--input", type=str, default=None, help="video file (cv2), synthetic:WxH:persons:frames[:seed], frames.npy or raw:WxH:path")
     p.add_argument("--inputs", type=str, default=None,
-                   help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort only: one pipeline with one tracker "
+                   help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort|botsort only: one pipeline with one tracker "
                         "stream per source; the shortest source ends the run, one output per stream (suffix _s<k>)")
     p.add_argument("--webcam_id", type=int, default=0, help="webcam used when no --input is given (cv2)")
     p.add_argument("--output_dir", type=str, default="outputs")
@@ -65,8 +65,8 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     if args.inputs is not None:
         if args.input is not None:
             p.error("--inputs and --input are mutually exclusive")
-        if args.tracker not in ("bytetrack", "ocsort"):
-            p.error("--inputs needs --tracker bytetrack or ocsort")
+        if args.tracker not in ("bytetrack", "ocsort", "botsort"):
+            p.error("--inputs needs --tracker bytetrack, ocsort or botsort")
     return args
 
 
@@ -202,7 +202,8 @@ class _BotSortFrame:
 
 
 def main_streams(args, cv2):
-    """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S)), their frames interleaved tick by tick."""
+    """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank for
+    --tracker botsort), their frames interleaved tick by tick."""
     from .pipeline import TrackingPipeline
     sources = [frame_source(spec, args.webcam_id, cv2) for spec in args.inputs.split(",") if spec]
     S = len(sources)
@@ -211,17 +212,24 @@ def main_streams(args, cv2):
         print("Error: --inputs sources must have one frame size: " + ", ".join(f"{src[2][0]}x{src[2][1]}" for src in sources))
         return 1
     if args.conf_thresh is None:
-        args.conf_thresh = 0.1 if args.tracker == "bytetrack" else 0.6
+        args.conf_thresh = 0.1 if args.tracker in ("bytetrack", "botsort") else 0.6
     batch = max(1, args.batch // S) * S          # whole ticks per launch group
     dev = config.resolve_device(args.device)
     try:
-        pipe = TrackingPipeline(args.yolo_engine, None, (size[1], size[0]), batch=batch, ring_frames=batch, max_persons=512, max_tracks=512,
-                                device=dev, dtype=args.dtype, conf_thresh=args.conf_thresh,
-                                tracker=args.tracker, streams=S)
+        if args.tracker == "botsort":
+            from .hip_engine import HipEngine
+            reid = HipEngine(args.reid_engine, device=dev, dtype=args.dtype, max_items=batch * 64, warm_up=False)   # as the single-source path
+            pipe = TrackingPipeline.botsort_bank(args.yolo_engine, reid, (size[1], size[0]), cameras=S, gmc=args.gmc, batch=batch,
+                                                 ring_frames=batch, max_persons=512, max_tracks=512, device=dev, dtype=args.dtype,
+                                                 conf_thresh=args.conf_thresh)
+        else:
+            pipe = TrackingPipeline(args.yolo_engine, None, (size[1], size[0]), batch=batch, ring_frames=batch, max_persons=512,
+                                    max_tracks=512, device=dev, dtype=args.dtype, conf_thresh=args.conf_thresh,
+                                    tracker=args.tracker, streams=S)
     except Exception as e:
         print(f"Error initializing YOLO Detector: {e}")
         return 1
-    label = "AICamera: YOLOv8 + " + ("ByteTrack" if args.tracker == "bytetrack" else "OC-SORT")
+    label = "AICamera: YOLOv8 + " + {"bytetrack": "ByteTrack", "ocsort": "OC-SORT", "botsort": "BoT-SORT"}[args.tracker]
     outs, writers = [None] * S, [None] * S
     if not args.no_save:
         out_dir = Path(args.output_dir)

@@ -1,9 +1,10 @@
 // botsort.hpp -- BoT-SORT with ReID on the device (BoTSORT.update of tracker/bot_sort.py, restated in tests/botsort_oracle.py): the
-// structures shared by kernels_botsort.hip (the one-block epoch kernel) and botsort.cpp (tracker object, pipeline hook).
+// structures shared by kernels_botsort.hip (the epoch kernel: one block per stream) and botsort.cpp (tracker object, a bank of streams).
 //
 // The track table lives in HBM between launches, indexed by SLOT:
 //   BsHdr | BtTrack[cap] | tracked list[cap] | lost list[cap] | mean[cap][8] | cov[cap][64] | has_feat[cap]     and   smooth[cap][dim]
-// An epoch launch (ONE block of 512 threads) loads the scalars, the lists and the means into LDS, walks k <= TRK_KMAX frames with no host
+// A bank holds the tables of its streams `table_stride` bytes apart and their smoothed features `smooth_stride` floats apart.
+// An epoch launch (ONE block of 512 threads per stream) loads the scalars, the lists and the means into LDS, walks k <= TRK_KMAX frames with no host
 // round trip (covariances and smoothed features stay in HBM) and writes them back.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,7 +47,7 @@ struct BsTable {                    // device pointers
 static inline size_t bs_table_bytes(int cap) {
     return BS_HDR_BYTES + (size_t)cap * (sizeof(BtTrack) + 8 + 4 * 8 + 4 * 64 + 4);
 }
-static inline BsTable bs_table(char* base, int cap, float* feat) {
+__host__ __device__ static inline BsTable bs_table(char* base, int cap, float* feat) {
     BsTable t;
     t.hdr = reinterpret_cast<BsHdr*>(base);
     t.trk = reinterpret_cast<BtTrack*>(base + BS_HDR_BYTES);
@@ -59,10 +60,13 @@ static inline BsTable bs_table(char* base, int cap, float* feat) {
     return t;
 }
 
-// one launch: frames [f0, f0 + k) of the group.  dets.feat_n (unit rows; NULL = no features) and dets.valid are read for the high band only;
-// warps = [frames, 6] camera motion (r00 r01 t0 r10 r11 t1) or NULL; ext = [TRK_DEV_NMAX^2] HBM scratch for extended matrices beyond the LDS
-void launch_botsort_epoch(const BsTable& tbl, const BsParams& prm, const EpochDets& dets, const float* warps, int f0, int k, float* ext,
-                          const EpochOut& out, hipStream_t s);
+// one launch, one block per stream: local frames [f0, f0 + k) of every stream, cut at stream_k[s]; local frame i of stream s is row
+// stream_f0[s] + i * frame_stride of dets, out and warps (stream_f0 == stream_k == NULL with one stream: row = local frame).
+// dets.feat_n (unit rows; NULL = no features) and dets.valid are read for the high band only, by detection row; warps = [rows, 6] camera
+// motion (r00 r01 t0 r10 r11 t1) or NULL; ext = [streams][TRK_DEV_NMAX^2] HBM scratch for extended matrices beyond the LDS
+void launch_botsort_epoch(char* bank, size_t table_stride, float* smooth, size_t smooth_stride, int streams, const BsParams& prm,
+                          const EpochDets& dets, const float* warps, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
+                          float* ext, const EpochOut& out, hipStream_t s);
 // out[r] = in[r] / |in[r]| in the order of kf8wh_math.hpp (one wavefront per row)
 void launch_botsort_normalize(const float* in, float* out, int rows, int dim, hipStream_t s);
 

@@ -1,6 +1,8 @@
-// epoch_bank.hpp -- a bank of detector-only tracker streams on one device: what ByteTracker and OcSortTracker share.  One allocation holds
-// the streams' tables `stride` bytes apart, every epoch launch runs one block per stream (kernels_bytetrack.hip / kernels_ocsort.hip), and a
-// stream that meets a capacity error stops alone.  The single trackers of the C ABI and the pipeline's default are banks of one.
+// epoch_bank.hpp -- a bank of epoch-tracker streams on one device: what ByteTracker, OcSortTracker and BotSortTracker share.  One allocation
+// holds the streams' tables `stride` bytes apart, every epoch launch runs one block per stream (kernels_bytetrack.hip / kernels_ocsort.hip /
+// kernels_botsort.hip), and a stream that meets a capacity error stops alone.  The single trackers of the C ABI and the pipeline's default
+// are banks of one.  BoT-SORT stages features, validity and camera motion on top (BankExtra); the detector-only trackers pass none and
+// their staging layout and launches are what they were without it.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -12,6 +14,14 @@
 namespace aic {
 
 constexpr int BANK_STREAMS_MAX = 256;
+
+// What update() stages on top of the detections for a tracker that sees appearance (host pointers, any may be NULL)
+struct BankExtra {
+    const float* feat;              // [rows, dim] raw embeddings of every detection row of the call
+    const int32_t* valid;           // [rows]
+    const float* warps6;            // [F, 6] camera motion per frame
+    int dim;
+};
 
 // Hdr: the table header (next_id, err, err_frame; at the start of every table).  Prm: the kernel's parameters (no_fast).
 template <class Hdr, class Prm>
@@ -41,6 +51,9 @@ struct EpochBank : EpochTracker {
     virtual void launch(const Prm& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
                         const EpochOut& out, hipStream_t s) = 0;
     virtual std::string err_text(int err) const = 0;
+    // update() with a BankExtra: the extras are on their way to the device (stream s), before the epochs.  dets.valid / dets.feat are set
+    // where given; d_warps is NULL without camera motion, d_feat_n [rows, dim] is free device memory for the normalised features.
+    virtual void extra_staged(EpochDets&, const float* /*d_warps*/, float* /*d_feat_n*/, int /*rows*/, hipStream_t) {}
 
     int streams() const override { return n_streams; }
     char* table(int s) const { return d_tbl.p + (size_t)s * stride; }
@@ -138,7 +151,7 @@ struct EpochBank : EpochTracker {
     // blocks, one read-back, one sync.  status (may be NULL): per stream 0 or the code that stopped it; with status NULL a stopped stream
     // raises after the other streams' rows have been delivered.
     void update(const int32_t* frames_per_stream, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, int cap_rows,
-                int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status) {
+                int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status, const BankExtra* x = nullptr) {
         dev->use();
         AIC_REQUIRE(cap_rows >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
         const int S = n_streams;
@@ -166,13 +179,21 @@ struct EpochBank : EpochTracker {
             auto up = [](size_t x) { return (x + 15) / 16 * 16; };
             // staging (host == device layout): stream_f0[S] | stream_k[S] | frame_n[F] | frame_d0[F] | tlwh[n*4] | conf[n] | cls[n]
             //                                  || n_tracks[F] | rows[F*cap*6] | conf[F*cap]
+            // with a BankExtra, between cls and ||: valid[n] | warps[F*6] | feat[n*dim], and, device only, feat_n[n*dim] behind the outputs
             const size_t o_n = up((size_t)S * 8), o_d0 = o_n + k * 4, o_tlwh = up(o_d0 + k * 4), o_conf = o_tlwh + n * 16, o_cls = o_conf + n * 4;
-            const size_t o_out = up(o_cls + n * 4);
+            size_t in_end = o_cls + n * 4, o_valid = 0, o_warp = 0, o_feat = 0, feat_bytes = 0;
+            if (x) {
+                if (x->valid) o_valid = in_end, in_end += n * 4;
+                if (x->warps6) o_warp = up(in_end), in_end = o_warp + k * 24;
+                if (x->feat && n) o_feat = up(in_end), feat_bytes = n * (size_t)x->dim * 4, in_end = o_feat + feat_bytes;
+            }
+            const size_t o_out = up(in_end);
             const size_t o_rows = o_out + up(k * 4), o_oconf = o_rows + k * cap_rows * 24;
             const size_t bytes = o_oconf + k * cap_rows * 4;
+            const size_t o_featn = up(bytes);
             HIP_CHECK(hipStreamSynchronize(s));
             h_api.ensure(bytes);
-            d_api.ensure(bytes);
+            d_api.ensure(x ? o_featn + feat_bytes : bytes);
             int* hp = reinterpret_cast<int*>(h_api.p);
             for (int q = 0, f = 0; q < S; ++q) { hp[q] = f; hp[S + q] = frames_per_stream[q]; f += frames_per_stream[q]; }
             int* hn = reinterpret_cast<int*>(h_api.p + o_n);
@@ -187,13 +208,22 @@ struct EpochBank : EpochTracker {
             if (n) {
                 std::memcpy(h_api.p + o_conf, conf, n * 4);
                 std::memcpy(h_api.p + o_cls, cls, n * 4);
+                if (o_valid) std::memcpy(h_api.p + o_valid, x->valid, n * 4);
+                if (o_feat) std::memcpy(h_api.p + o_feat, x->feat, feat_bytes);
             }
+            if (o_warp) std::memcpy(h_api.p + o_warp, x->warps6, k * 24);
             HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
             EpochDets dets{reinterpret_cast<const int*>(d_api.p + o_n), reinterpret_cast<const int*>(d_api.p + o_d0),
                            reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
                            reinterpret_cast<const int*>(d_api.p + o_cls), nullptr, nullptr, nullptr};
             EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows),
                          reinterpret_cast<float*>(d_api.p + o_oconf), cap_rows, nullptr, nullptr, 0};
+            if (x) {
+                if (o_valid) dets.valid = reinterpret_cast<const int*>(d_api.p + o_valid);
+                if (o_feat) dets.feat = reinterpret_cast<const float*>(d_api.p + o_feat);
+                extra_staged(dets, o_warp ? reinterpret_cast<const float*>(d_api.p + o_warp) : nullptr,
+                             reinterpret_cast<float*>(d_api.p + o_featn), (int)n, s);
+            }
             const int* dp = reinterpret_cast<const int*>(d_api.p);
             if (S == 1) run_bank(dets, kmax_s, nullptr, nullptr, 1, out, s);
             else run_bank(dets, kmax_s, dp, dp + S, 1, out, s);

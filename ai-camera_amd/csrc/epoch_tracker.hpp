@@ -1,6 +1,7 @@
-// epoch_tracker.hpp -- a detector-only tracker as the pipeline's stage B sees it (pipeline.cpp): the group's frames go through its epoch
-// launches on the tracker stream, the error check follows the caller's sync.  ByteTracker (bytetrack_host.hpp) and OcSortTracker
-// (ocsort_host.hpp) are banks of streams (epoch_bank.hpp: one kernel block per stream), BotSortTracker is one stream.
+// epoch_tracker.hpp -- an epoch tracker as the pipeline's stage B sees it (pipeline.cpp): the group's frames go through its epoch
+// launches on the tracker stream, the error check follows the caller's sync.  ByteTracker (bytetrack_host.hpp), OcSortTracker
+// (ocsort_host.hpp) and BotSortTracker (botsort_host.hpp) are banks of streams (epoch_bank.hpp: one kernel block per stream); a
+// BoT-SORT pipeline fixes its stream count at creation (aic_pipeline_create_botsort_bank), the other two take the option "streams".
 #pragma once
 #include <string>
 

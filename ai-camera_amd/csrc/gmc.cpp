@@ -7,9 +7,21 @@
 
 namespace aic {
 
-CameraMotionEstimator::CameraMotionEstimator(Device& d, int h, int w, int s, int min_inl) : dev(&d), g(gmc_geom(h, w, s)), min_inliers(min_inl) {
+CameraMotionEstimator::CameraMotionEstimator(Device& d, int h, int w, int s, int min_inl, int n_streams)
+    : dev(&d), g(gmc_geom(h, w, s)), min_inliers(min_inl), streams(n_streams), have(n_streams, 0) {
     dev->use();
-    d_prev.alloc(g.level);
+    d_prev.alloc(g.level * streams);
+    d_have.alloc(streams);
+    HIP_CHECK(hipMemsetAsync(d_have.p, 0, streams, dev->s_trk));
+    HIP_CHECK(hipStreamSynchronize(dev->s_trk));
+}
+
+void CameraMotionEstimator::reset(int stream) {
+    AIC_REQUIRE(stream >= 0 && stream < streams, AIC_ERR_INVALID, "stream outside the bank");
+    dev->use();
+    have[stream] = 0;
+    HIP_CHECK(hipMemsetAsync(d_have.p + stream, 0, 1, dev->s_trk));
+    HIP_CHECK(hipStreamSynchronize(dev->s_trk));
 }
 
 void CameraMotionEstimator::ensure(int k) {
@@ -22,11 +34,15 @@ void CameraMotionEstimator::ensure(int k) {
 
 void CameraMotionEstimator::match_fit(const uint8_t* levels, int k, const int32_t* frame_n, const int32_t* frame_d0, const float* boxes,
                                       bool tlwh, hipStream_t s) {
+    AIC_REQUIRE(k > 0 && k % streams == 0, AIC_ERR_INVALID, "camera motion takes whole ticks of every stream");
     ensure(k);
-    launch_gmc_match(levels, have_prev ? d_prev.p : nullptr, k, g, frame_n, frame_d0, boxes, tlwh, d_disp.p, s);
+    launch_gmc_match(levels, d_prev.p, d_have.p, streams, k, g, frame_n, frame_d0, boxes, tlwh, d_disp.p, s);
     launch_gmc_fit(d_disp.p, k, g, min_inliers, d_warps.p, d_stats.p, s);
-    HIP_CHECK(hipMemcpyAsync(d_prev.p, levels + (size_t)(k - 1) * g.level, g.level, hipMemcpyDeviceToDevice, s));
-    have_prev = true;
+    HIP_CHECK(hipMemcpyAsync(d_prev.p, levels + (size_t)(k - streams) * g.level, g.level * streams, hipMemcpyDeviceToDevice, s));
+    if (std::find(have.begin(), have.end(), 0) != have.end()) {   // a first tick only: every stream has a carried level from here on
+        HIP_CHECK(hipMemsetAsync(d_have.p, 1, streams, s));
+        std::fill(have.begin(), have.end(), 1);
+    }
     last_frames = k;
 }
 
@@ -69,16 +85,32 @@ using namespace aic;
 
 extern "C" {
 
+// Parameter checks of aic_gmc_create / aic_gmc_bank_create: nothing is touched before they pass.  Returns the downscale.
+static int gmc_checked(int height, int width, const aic_gmc_params* p) {
+    AIC_REQUIRE(p->downscale == 0 || p->downscale == 2 || p->downscale == 4, AIC_ERR_INVALID, "downscale must be 2 or 4 (0 = 4)");
+    AIC_REQUIRE(p->min_inliers >= 0, AIC_ERR_INVALID, "min_inliers must be >= 0 (0 = 8)");
+    AIC_REQUIRE(height > 0 && width > 0 && height <= 16384 && width <= 16384, AIC_ERR_INVALID, "bad frame size");
+    const int s = p->downscale ? p->downscale : 4;
+    const GmcGeom g = gmc_geom(height, width, s);
+    AIC_REQUIRE(g.nb >= 1, AIC_ERR_INVALID, "frame smaller than one block plus its search margin (32 * downscale pixels a side)");
+    AIC_REQUIRE(g.nb <= GMC_MAX_BLOCKS, AIC_ERR_INVALID, "more than 2048 blocks per frame: use downscale 4");
+    return s;
+}
+
+static void gmc_estimate_checked(CameraMotionEstimator& e, const uint8_t* frames_bgr, int k, int mem, const int32_t* counts,
+                                 const float* boxes_xyxy, float* warps_out, int32_t* stats_out) {
+    AIC_REQUIRE(k >= 0 && (k == 0 || frames_bgr), AIC_ERR_INVALID, "NULL argument / negative frame count");
+    AIC_REQUIRE(mem == AIC_HOST || mem == AIC_DEVICE, AIC_ERR_INVALID, "mem must be AIC_HOST or AIC_DEVICE");
+    AIC_REQUIRE(!boxes_xyxy || counts, AIC_ERR_INVALID, "boxes without counts");
+    if (counts && boxes_xyxy)
+        for (int f = 0; f < k; ++f) AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative box count");
+    e.estimate_batch(frames_bgr, k, mem, counts, boxes_xyxy, warps_out, stats_out);
+}
+
 int aic_gmc_create(int device_id, int height, int width, const aic_gmc_params* p, aic_gmc** out) {
     return guarded([&] {
         AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(p->downscale == 0 || p->downscale == 2 || p->downscale == 4, AIC_ERR_INVALID, "downscale must be 2 or 4 (0 = 4)");
-        AIC_REQUIRE(p->min_inliers >= 0, AIC_ERR_INVALID, "min_inliers must be >= 0 (0 = 8)");
-        AIC_REQUIRE(height > 0 && width > 0 && height <= 16384 && width <= 16384, AIC_ERR_INVALID, "bad frame size");
-        const int s = p->downscale ? p->downscale : 4;
-        const GmcGeom g = gmc_geom(height, width, s);
-        AIC_REQUIRE(g.nb >= 1, AIC_ERR_INVALID, "frame smaller than one block plus its search margin (32 * downscale pixels a side)");
-        AIC_REQUIRE(g.nb <= GMC_MAX_BLOCKS, AIC_ERR_INVALID, "more than 2048 blocks per frame: use downscale 4");
+        const int s = gmc_checked(height, width, p);
         *out = new aic_gmc(device(device_id), height, width, s, p->min_inliers ? p->min_inliers : 8);
     });
 }
@@ -93,19 +125,48 @@ int aic_gmc_destroy(aic_gmc* g) {
 int aic_gmc_reset(aic_gmc* g) {
     return guarded([&] {
         AIC_REQUIRE(g, AIC_ERR_INVALID, "NULL estimator");
-        g->e.reset();
+        g->e.reset(0);
     });
 }
 
 int aic_gmc_estimate_batch(aic_gmc* g, const uint8_t* frames_bgr, int k, int mem, const int32_t* counts, const float* boxes_xyxy,
                            float* warps_out, int32_t* stats_out) {
     return guarded([&] {
-        AIC_REQUIRE(g && k >= 0 && (k == 0 || frames_bgr), AIC_ERR_INVALID, "NULL argument / negative frame count");
-        AIC_REQUIRE(mem == AIC_HOST || mem == AIC_DEVICE, AIC_ERR_INVALID, "mem must be AIC_HOST or AIC_DEVICE");
-        AIC_REQUIRE(!boxes_xyxy || counts, AIC_ERR_INVALID, "boxes without counts");
-        if (counts && boxes_xyxy)
-            for (int f = 0; f < k; ++f) AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative box count");
-        g->e.estimate_batch(frames_bgr, k, mem, counts, boxes_xyxy, warps_out, stats_out);
+        AIC_REQUIRE(g, AIC_ERR_INVALID, "NULL argument / negative frame count");
+        gmc_estimate_checked(g->e, frames_bgr, k, mem, counts, boxes_xyxy, warps_out, stats_out);
+    });
+}
+
+// ---- banks
+int aic_gmc_bank_create(int device_id, int height, int width, const aic_gmc_params* p, int streams, aic_gmc_bank** out) {
+    return guarded([&] {
+        AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
+        const int s = gmc_checked(height, width, p);
+        AIC_REQUIRE(streams >= 1 && streams <= 256, AIC_ERR_INVALID, "streams must be in 1..256");
+        *out = new aic_gmc_bank(device(device_id), height, width, s, p->min_inliers ? p->min_inliers : 8, streams);
+    });
+}
+
+int aic_gmc_bank_destroy(aic_gmc_bank* b) {
+    return guarded([&] {
+        if (b) { b->e.dev->use(); (void)hipStreamSynchronize(b->e.dev->s_trk); }
+        delete b;
+    });
+}
+
+int aic_gmc_bank_reset(aic_gmc_bank* b, int stream) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL estimator");
+        b->e.reset(stream);
+    });
+}
+
+int aic_gmc_bank_estimate(aic_gmc_bank* b, const uint8_t* frames_bgr, int ticks, int mem, const int32_t* counts, const float* boxes_xyxy,
+                          float* warps_out, int32_t* stats_out) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument / negative frame count");
+        AIC_REQUIRE(ticks >= 0 && ticks <= (1 << 24) / b->e.streams, AIC_ERR_INVALID, "NULL argument / negative frame count");
+        gmc_estimate_checked(b->e, frames_bgr, ticks * b->e.streams, mem, counts, boxes_xyxy, warps_out, stats_out);
     });
 }
 

@@ -4,7 +4,8 @@
 // tests/botsort_oracle.py, with the deliberate changes listed there.  The filter, the warp and the ordered feature sums are
 // kf8wh_math.hpp's; the LSAPs and the ordered compaction are trk_wave.hpp's (shared with the DeepSORT and ByteTrack epoch kernels).
 //
-// ONE block of 512 threads walks the frames of one stream: thread i <-> list position i / detection i / slot i.  Per frame:
+// ONE block of 512 threads walks the frames of one stream (a bank: one block per stream, each on its own table, smoothed features and
+// HBM scratch): thread i <-> list position i / detection i / slot i.  Per frame:
 //   bands -> pool = activated tracked ++ lost, Kalman predict (vw = vh = 0 first for tracks that are not Tracked) -> camera-motion warp of
 //   pool and unconfirmed -> stage 1 (pool x high, min(fused IoU distance, gated appearance distance), match_thresh) -> stage 2 (pool's
 //   unmatched Tracked x low band, IoU, 0.5) -> stage 3 (unconfirmed x high left over, the fused cost, 0.7) -> new tracks -> lost timeout ->
@@ -20,12 +21,18 @@
 namespace aic {
 
 struct BsArgs {
-    BsTable tbl;
+    char* bank;                     // stream s: bs_table(bank + s * table_stride, cap, smooth + s * smooth_stride)
+    size_t table_stride;
+    float* smooth;                  // [streams][cap][dim] smoothed unit features
+    size_t smooth_stride;           // floats between two streams' features
     BsParams prm;
     EpochDets dets;
-    const float* warps;
-    int f0, k;
-    float* ext;                     // [TRK_DEV_NMAX^2] extended matrices that do not fit the LDS arena
+    const float* warps;             // [rows, 6], indexed like dets.frame_n / out
+    int f0, k;                      // local frames [f0, f0 + k) of every stream, cut at stream_k[s]
+    const int* stream_f0;           // [streams] local frame i of stream s = row stream_f0[s] + i * frame_stride of dets / out / warps;
+    const int* stream_k;            // [streams] frames of stream s in the call.  Both NULL: one stream, row = local frame
+    int frame_stride;
+    float* ext;                     // [streams][TRK_DEV_NMAX^2] extended matrices that do not fit the LDS arena
     EpochOut out;
     int lds_bytes;
 };
@@ -113,8 +120,9 @@ __device__ __forceinline__ void count_appearance(const BsLds& L, const float* ex
 // linear_assignment(cost, thresh) of matching.py for rows (slots) x cols (detections), block-wide; reid: cost = min(d_iou, gated d_emb).
 // Out: L.mrow[r] = column of row r or -1, L.mcol[c] = row of column c or -1.  *err = 3 when the extended side exceeds the LSAPs.
 // Ls: the same carve in LDS, what the (noinline) LSAPs get a reference to -- a reference to the kernel's own copy would put it in scratch.
-__device__ void bs_assign(const BsLds& L, const BsLds& Ls, const BsArgs& a, const int* rows, int nr, const int* cols, int nc, int d0, bool fuse,
-                          bool reid, float th, int* err, long long* cyc) {
+// smooth / hbm: the block's own smoothed features and HBM scratch.
+__device__ void bs_assign(const BsLds& L, const BsLds& Ls, const BsArgs& a, const float* smooth, float* hbm, const int* rows, int nr,
+                          const int* cols, int nc, int d0, bool fuse, bool reid, float th, int* err, long long* cyc) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int r = tid; r < nr; r += BT) L.mrow[r] = -1;
     for (int c = tid; c < nc; c += BT) L.mcol[c] = -1;
@@ -123,7 +131,7 @@ __device__ void bs_assign(const BsLds& L, const BsLds& Ls, const BsArgs& a, cons
     const int S = nr + nc;
     if (S > TRK_DEV_NMAX) { if (tid == 0) *err = 3; __syncthreads(); return; }
     if (tid == 0) L.wcnt[NW + 4] = max(L.wcnt[NW + 4], S);
-    float* ext = S * S <= L.arena_floats ? L.arena : a.ext;
+    float* ext = S * S <= L.arena_floats ? L.arena : hbm;
     const float half = th * 0.5f;
     for (int e = tid; e < S * S; e += BT) {
         const int r = e / S, c = e - r * S;
@@ -163,7 +171,7 @@ __device__ void bs_assign(const BsLds& L, const BsLds& Ls, const BsArgs& a, cons
                 const int bit = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
                 const int q2 = base + bit, r2 = q2 / nc, c2 = q2 - r2 * nc;
-                const float d = wave_dot(a.tbl.feat + (size_t)rows[r2] * dim, a.dets.feat_n + (size_t)(d0 + cols[c2]) * dim, dim, lane);
+                const float d = wave_dot(smooth + (size_t)rows[r2] * dim, a.dets.feat_n + (size_t)(d0 + cols[c2]) * dim, dim, lane);
                 if (lane == bit) mine = d;
             }
             if (need) {
@@ -221,15 +229,16 @@ __device__ void bs_assign(const BsLds& L, const BsLds& Ls, const BsArgs& a, cons
 }
 
 // Kalman update and feature update of the matched rows: one wavefront per row
-__device__ __forceinline__ void bs_commit(const BsLds& L, const BsArgs& a, const int* rows, int nr, const int* cols, int d0, bool feats) {
+__device__ __forceinline__ void bs_commit(const BsLds& L, const BsArgs& a, const BsTable& tbl, const int* rows, int nr, const int* cols, int d0,
+                                          bool feats) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int r = wv; r < nr; r += NW) {
         const int c = L.mrow[r];
         if (c < 0) continue;
         const int sl = rows[r], j = cols[c];
-        kf_slot(L, a.tbl.cov, sl, lane, [&](float& p, float& m) { kf8_update_wave(p, m, L.xywh + j * 4, lane); });
+        kf_slot(L, tbl.cov, sl, lane, [&](float& p, float& m) { kf8_update_wave(p, m, L.xywh + j * 4, lane); });
         if (feats && L.dhas[j])
-            feat_update_wave(a.tbl.feat + (size_t)sl * a.prm.dim, a.dets.feat_n + (size_t)(d0 + j) * a.prm.dim, a.prm.dim, !L.hasf[sl],
+            feat_update_wave(tbl.feat + (size_t)sl * a.prm.dim, a.dets.feat_n + (size_t)(d0 + j) * a.prm.dim, a.prm.dim, !L.hasf[sl],
                              a.prm.alpha, a.prm.one_minus_alpha, lane);
     }
     __threadfence_block();
@@ -252,25 +261,32 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
     const int cap = P.cap, dim = P.dim;
     const bool reid = P.reid && a.dets.feat_n != nullptr;
     int* err = L.wcnt + NW + 3;
-    if (a.tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
+    // ---- this block's stream: frame range, table, smoothed features, HBM scratch
+    const int sid = blockIdx.x;
+    const int row0 = a.stream_f0 ? a.stream_f0[sid] : 0;
+    const int kend = a.stream_k ? min(a.f0 + a.k, a.stream_k[sid]) : a.f0 + a.k;
+    if (a.f0 >= kend) return;                                     // nothing for this stream in this epoch: its table is not touched
+    const BsTable tbl = bs_table(a.bank + (size_t)sid * a.table_stride, cap, a.smooth + (size_t)sid * a.smooth_stride);
+    float* hbm = a.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_NMAX;
+    if (tbl.hdr->err) return;                                     // an earlier epoch of the call failed: the table is not a frame boundary
 
     // ---- load the table
-    int ntl = a.tbl.hdr->n_tracked, nll = a.tbl.hdr->n_lost, next_id = a.tbl.hdr->next_id, frame = a.tbl.hdr->frame_id;
+    int ntl = tbl.hdr->n_tracked, nll = tbl.hdr->n_lost, next_id = tbl.hdr->next_id, frame = tbl.hdr->frame_id;
     if (tid < cap) {
-        const BtTrack t = a.tbl.trk[tid];
+        const BtTrack t = tbl.trk[tid];
         L.id[tid] = t.id, L.state[tid] = t.state, L.act[tid] = t.act, L.start[tid] = t.start, L.end[tid] = t.end, L.cls[tid] = t.cls;
         L.score[tid] = t.score;
-        L.hasf[tid] = a.tbl.hasf[tid];
+        L.hasf[tid] = tbl.hasf[tid];
     }
-    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = a.tbl.mean[e];
-    if (tid < ntl) L.tl[tid] = a.tbl.tl[tid];
-    if (tid < nll) L.ll[tid] = a.tbl.ll[tid];
-    if (tid == 0) { s_cyc = 0; *err = 0; L.wcnt[NW + 1] = 0; L.wcnt[NW + 2] = 0; L.wcnt[NW + 4] = a.tbl.hdr->max_side; L.wcnt[NW + 5] = 0; }
+    for (int e = tid; e < cap * 8; e += BT) L.mean[e] = tbl.mean[e];
+    if (tid < ntl) L.tl[tid] = tbl.tl[tid];
+    if (tid < nll) L.ll[tid] = tbl.ll[tid];
+    if (tid == 0) { s_cyc = 0; *err = 0; L.wcnt[NW + 1] = 0; L.wcnt[NW + 2] = 0; L.wcnt[NW + 4] = tbl.hdr->max_side; L.wcnt[NW + 5] = 0; }
     __syncthreads();
-    float* cov = a.tbl.cov;
-    int fi = 0;
-    for (; fi < a.k; ++fi) {
-        const int f = a.f0 + fi;
+    float* cov = tbl.cov;
+    int fi = a.f0;
+    for (; fi < kend; ++fi) {
+        const int f = row0 + fi * a.frame_stride;
         ++frame;
         const int n = a.dets.frame_n[f], d0 = a.dets.frame_d0[f];
         if (n > TRK_DEV_NMAX) { if (tid == 0) *err = 3; break; }
@@ -307,9 +323,9 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
         __syncthreads();
 
         // ---- stage 1: pool x high band
-        bs_assign(L, s_lds, a, L.pool, np, L.hi, nh, d0, P.fuse != 0, reid, P.match_thresh, err, &s_cyc);
+        bs_assign(L, s_lds, a, tbl.feat, hbm, L.pool, np, L.hi, nh, d0, P.fuse != 0, reid, P.match_thresh, err, &s_cyc);
         if (*err) break;
-        bs_commit(L, a, L.pool, np, L.hi, d0, reid);
+        bs_commit(L, a, tbl, L.pool, np, L.hi, d0, reid);
         const int nr2 = block_compact(tid < np && L.mrow[tid] < 0 && L.state[L.pool[tid]] == BT_TRACKED, tid < np ? L.pool[tid] : 0, L.rows, L.wcnt);
         if (tid < nh) L.hm[tid] = L.mcol[tid] >= 0;
         if (tid < np && L.mrow[tid] >= 0) {                       // update (Tracked) / re_activate (Lost -> refound)
@@ -319,9 +335,9 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
         __syncthreads();
 
         // ---- stage 2: the pool's unmatched Tracked tracks x low band, IoU distance, no fusion, no features
-        bs_assign(L, s_lds, a, L.rows, nr2, L.lo, nlo, d0, false, false, P.second_thresh, err, &s_cyc);
+        bs_assign(L, s_lds, a, tbl.feat, hbm, L.rows, nr2, L.lo, nlo, d0, false, false, P.second_thresh, err, &s_cyc);
         if (*err) break;
-        bs_commit(L, a, L.rows, nr2, L.lo, d0, false);
+        bs_commit(L, a, tbl, L.rows, nr2, L.lo, d0, false);
         if (tid < nr2) {
             const int sl = L.rows[tid], c = L.mrow[tid];
             if (c >= 0) {
@@ -333,9 +349,9 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
 
         // ---- stage 3: unconfirmed x the high band left over, the fused cost, 0.7
         const int nh3 = block_compact(tid < nh && !L.hm[tid], tid < nh ? L.hi[tid] : 0, L.cols, L.wcnt);
-        bs_assign(L, s_lds, a, L.unc, nun, L.cols, nh3, d0, P.fuse != 0, reid, P.unconf_thresh, err, &s_cyc);
+        bs_assign(L, s_lds, a, tbl.feat, hbm, L.unc, nun, L.cols, nh3, d0, P.fuse != 0, reid, P.unconf_thresh, err, &s_cyc);
         if (*err) break;
-        bs_commit(L, a, L.unc, nun, L.cols, d0, reid);
+        bs_commit(L, a, tbl, L.unc, nun, L.cols, d0, reid);
         if (tid < nun) {
             const int sl = L.unc[tid], c = L.mrow[tid];
             if (c >= 0) {
@@ -375,7 +391,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
         for (int r = wv; r < nnew; r += NW) {
             const int sl = L.fre[r], j = L.newd[r];
             kf_slot(L, cov, sl, lane, [&](float& p, float& m) { kf8_initiate_wave(p, m, L.xywh + j * 4, lane); });
-            if (L.dhas[j]) feat_update_wave(a.tbl.feat + (size_t)sl * dim, a.dets.feat_n + (size_t)(d0 + j) * dim, dim, true, 0.f, 0.f, lane);
+            if (L.dhas[j]) feat_update_wave(tbl.feat + (size_t)sl * dim, a.dets.feat_n + (size_t)(d0 + j) * dim, dim, true, 0.f, 0.f, lane);
         }
         next_id += nnew;
         __threadfence_block();
@@ -422,17 +438,17 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
             BtTrack t;
             t.id = L.id[tid], t.state = L.state[tid], t.act = L.act[tid], t.start = L.start[tid], t.end = L.end[tid], t.cls = L.cls[tid];
             t.score = L.score[tid], t.pad = 0;
-            a.tbl.trk[tid] = t;
-            a.tbl.hasf[tid] = L.hasf[tid];
+            tbl.trk[tid] = t;
+            tbl.hasf[tid] = L.hasf[tid];
         }
-        for (int i = tid; i < cap * 8; i += BT) a.tbl.mean[i] = L.mean[i];
-        if (tid < ntl) a.tbl.tl[tid] = L.tl[tid];
-        if (tid < nll) a.tbl.ll[tid] = L.ll[tid];
+        for (int i = tid; i < cap * 8; i += BT) tbl.mean[i] = L.mean[i];
+        if (tid < ntl) tbl.tl[tid] = L.tl[tid];
+        if (tid < nll) tbl.ll[tid] = L.ll[tid];
     }
     if (tid == 0) {
-        BsHdr* h = a.tbl.hdr;
+        BsHdr* h = tbl.hdr;
         if (e == 0) h->n_tracked = ntl, h->n_lost = nll, h->next_id = next_id, h->frame_id = frame;
-        else h->err = e, h->err_frame = a.f0 + fi;
+        else h->err = e, h->err_frame = fi;
         h->n_fast += L.wcnt[NW + 1], h->n_lsap += L.wcnt[NW + 2], h->max_side = L.wcnt[NW + 4], h->n_app += L.wcnt[NW + 5];
         h->cyc_cost += s_cyc, h->cyc_all += clock64() - t_all;
     }
@@ -453,11 +469,13 @@ __global__ __launch_bounds__(256) void botsort_normalize_kernel(const float* in,
 
 static int bs_lds_bytes() { return 159 * 1024; }
 
-void launch_botsort_epoch(const BsTable& tbl, const BsParams& prm, const EpochDets& dets, const float* warps, int f0, int k, float* ext,
-                          const EpochOut& out, hipStream_t s) {
+void launch_botsort_epoch(char* bank, size_t table_stride, float* smooth, size_t smooth_stride, int streams, const BsParams& prm,
+                          const EpochDets& dets, const float* warps, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
+                          float* ext, const EpochOut& out, hipStream_t s) {
     set_lds_limit(botsort_epoch_kernel, bs_lds_bytes());
-    BsArgs a{tbl, prm, dets, warps, f0, k, ext, out, bs_lds_bytes()};
-    hipLaunchKernelGGL(botsort_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), bs_lds_bytes(), s, a);
+    BsArgs a{bank, table_stride, smooth, smooth_stride, prm, dets, warps, f0, k, stream_f0, stream_k, frame_stride, ext, out, bs_lds_bytes()};
+    // one block per stream; 512 threads (__launch_bounds__) and 159 KB of dynamic LDS keep it at one block per CU
+    hipLaunchKernelGGL(botsort_epoch_kernel, dim3(streams), dim3(TRK_DEV_TMAX), bs_lds_bytes(), s, a);
     KCHECK();
 }
 

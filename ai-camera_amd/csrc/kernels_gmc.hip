@@ -84,11 +84,12 @@ __device__ __forceinline__ int gmc_step(int m, int z, int p) {
     return d > 0 ? q : -q;
 }
 
-// One wavefront per (block, frame).  LDS: the previous level's 17 x 17 pixels at the block (16 x 16 + the texture's right / lower
+// One wavefront per (block, frame).  The frames are tick-major over `streams` streams: the predecessor of row f is row f - streams, and
+// for the first tick level f of the carried bank `prev_bank`, where have[f] says that stream f has one.  LDS: the previous level's 17 x 17 pixels at the block (16 x 16 + the texture's right / lower
 // neighbours; rows of 20 bytes), the current level's 32 x 32 window (rows of 32 bytes) and the 289 SADs.  A lane takes the candidates
 // lane, lane + 64, ...: 16 rows of four packed byte SADs, the window dwords byte-aligned to dx.
-__global__ __launch_bounds__(64) void gmc_match_kernel(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ prev0, int gw, int nbx,
-                                                       int nb, int s, size_t level, const int32_t* __restrict__ frame_n,
+__global__ __launch_bounds__(64) void gmc_match_kernel(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ prev_bank,
+                                                       const uint8_t* __restrict__ have, int streams, int gw, int nbx, int nb, int s, size_t level, const int32_t* __restrict__ frame_n,
                                                        const int32_t* __restrict__ frame_d0, const float* __restrict__ boxes, int tlwh,
                                                        int32_t* __restrict__ disp) {
     constexpr int NC = (2 * GMC_R + 1) * (2 * GMC_R + 1);
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(64) void gmc_match_kernel(const uint8_t* __restrict
     const int lane = threadIdx.x, b = blockIdx.x, f = blockIdx.y;
     int32_t* out = disp + ((size_t)f * nb + b) * 2;
     const uint8_t* cur = gray + (size_t)f * level;
-    const uint8_t* prev = f > 0 ? cur - level : prev0;
+    const uint8_t* prev = f >= streams ? cur - (size_t)streams * level : have[f] ? prev_bank + (size_t)f * level : nullptr;
     const int bj = b / nbx, bi = b - bj * nbx;
     const int x0 = GMC_R + GMC_B * bi, y0 = GMC_R + GMC_B * bj;
     bool skip = prev == nullptr;
@@ -175,11 +176,11 @@ __global__ __launch_bounds__(64) void gmc_match_kernel(const uint8_t* __restrict
     }
 }
 
-void launch_gmc_match(const uint8_t* gray, const uint8_t* prev0, int k, const GmcGeom& g, const int32_t* frame_n, const int32_t* frame_d0,
-                      const float* boxes, bool tlwh, int32_t* disp, hipStream_t s) {
+void launch_gmc_match(const uint8_t* gray, const uint8_t* prev_bank, const uint8_t* have, int streams, int k, const GmcGeom& g,
+                      const int32_t* frame_n, const int32_t* frame_d0, const float* boxes, bool tlwh, int32_t* disp, hipStream_t s) {
     if (k <= 0 || g.nb <= 0) return;
-    hipLaunchKernelGGL(gmc_match_kernel, dim3(g.nb, k), dim3(64), 0, s, gray, prev0, g.gw, g.nbx, g.nb, g.s, g.level, frame_n, frame_d0,
-                       boxes, tlwh ? 1 : 0, disp);
+    hipLaunchKernelGGL(gmc_match_kernel, dim3(g.nb, k), dim3(64), 0, s, gray, prev_bank, have, streams, g.gw, g.nbx, g.nb, g.s, g.level, frame_n,
+                       frame_d0, boxes, tlwh ? 1 : 0, disp);
     KCHECK();
 }
 

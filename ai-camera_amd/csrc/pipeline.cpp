@@ -196,6 +196,7 @@ struct Pipeline {
     std::unique_ptr<EpochTracker> bt;
     std::string bt_name() const { return bt->name(); }
     bool bs = false;                // the epoch tracker is BoT-SORT
+    bool bs_bank = false;           // ... created as a bank of cameras (aic_pipeline_create_botsort_bank): the count is fixed, reset_stream works
     float bs_low = 0.f;             // its track_low_thresh: inject = 0 hands over the detections with score > bs_low
     // aic_pipeline_option("gmc"): camera motion per frame, estimated on the device and handed to the BoT-SORT epochs; NULL = off
     std::unique_ptr<CameraMotionEstimator> gmc;
@@ -209,7 +210,7 @@ struct Pipeline {
     }
 
     Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr,
-             const BsParams* bsp = nullptr)
+             const BsParams* bsp = nullptr, int bs_streams = 0)
         : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp || bsp))), trk(trk_handle->t) {
         AIC_REQUIRE(y->kind == KIND_YOLO && (btp || ocp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
                     btp   ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
@@ -219,12 +220,14 @@ struct Pipeline {
         AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
+        AIC_REQUIRE(!bs_streams || (p.batch % bs_streams == 0 && p.ring_frames % bs_streams == 0), AIC_ERR_INVALID,
+                    "batch and ring_frames must be multiples of streams");
         AIC_REQUIRE(p.batch <= y->max_items, AIC_ERR_CAPACITY, "batch exceeds the YOLO engine's max_items");
         AIC_REQUIRE(p.max_det > 0 && p.max_det <= y->max_det_cap, AIC_ERR_CAPACITY, "max_det out of range");
         dev->use();
         if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
         else if (ocp) bt.reset(new OcSortTracker(*dev, *ocp, bt_first_id));
-        else if (bsp) { bt.reset(new BotSortTracker(*dev, *bsp, bt_first_id)); bs = true; bs_low = bsp->low; }
+        else if (bsp) { bt.reset(new BotSortTracker(*dev, *bsp, bt_first_id, std::max(1, bs_streams))); bs = true; bs_low = bsp->low; bs_bank = bs_streams > 0; }
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
@@ -944,8 +947,8 @@ using namespace aic;
 struct aic_pipeline {
     Pipeline p;
     aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr,
-                 const BsParams* bs = nullptr)
-        : p(y, r, q, b, first_id, o, bs) {}
+                 const BsParams* bs = nullptr, int bs_streams = 0)
+        : p(y, r, q, b, first_id, o, bs, bs_streams) {}
 };
 
 extern "C" {
@@ -981,6 +984,17 @@ int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipe
         int first = 1;
         const BsParams b = botsort_params(*bp, &first);
         *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b);
+    });
+}
+
+int aic_pipeline_create_botsort_bank(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp, int streams,
+                                     aic_pipeline** out) {
+    return guarded([&] {
+        AIC_REQUIRE(yolo && reid && p && bp && out, AIC_ERR_INVALID, "NULL argument");
+        int first = 1;
+        const BsParams b = botsort_params(*bp, &first);
+        AIC_REQUIRE(streams >= 1 && streams <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b, streams);
     });
 }
 
@@ -1191,8 +1205,10 @@ int aic_pipeline_exchange_done(aic_pipeline* p, int64_t seq) {
 int aic_pipeline_reset_stream(aic_pipeline* p, int stream) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
-        AIC_REQUIRE(p->p.bt && !p->p.bs, AIC_ERR_INVALID, "reset_stream applies to ByteTrack and OC-SORT pipelines only");
+        AIC_REQUIRE(p->p.bt && (!p->p.bs || p->p.bs_bank), AIC_ERR_INVALID,
+                    "reset_stream applies to ByteTrack and OC-SORT pipelines and to BoT-SORT banks (aic_pipeline_create_botsort_bank) only");
         p->p.bt->reset_stream(stream);
+        if (p->p.gmc) p->p.gmc->reset(stream);       // the camera's next frame is its first
     });
 }
 
@@ -1263,7 +1279,7 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
                 static_cast<BotSortTracker*>(q.bt.get())->warps = nullptr;   // (it pointed into the estimator that goes away)
                 q.gmc.reset();
                 if (value) {
-                    q.gmc.reset(new CameraMotionEstimator(*q.dev, q.prm.frame_h, q.prm.frame_w, value, 8));
+                    q.gmc.reset(new CameraMotionEstimator(*q.dev, q.prm.frame_h, q.prm.frame_w, value, 8, q.bt->streams()));
                     q.gmc->ensure(q.prm.batch);      // sized once for the largest launch group: stage B never reallocates
                 }
             }

@@ -19,7 +19,7 @@ class TrackingPipeline:
                  max_det=config.YOLO_MAX_DET, min_confidence=config.DEEPSORT_MIN_CONFIDENCE, inject=False,
                  max_cosine_distance=config.DEEPSORT_MAX_DIST, nn_budget=config.DEEPSORT_NN_BUDGET,
                  max_iou_distance=config.DEEPSORT_MAX_IOU_DISTANCE, max_age=config.DEEPSORT_MAX_AGE,
-                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, streams=1, **bytetrack_params):
+                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, streams=1, _cameras=0, **bytetrack_params):
         """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
         not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
         conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
@@ -32,9 +32,12 @@ class TrackingPipeline:
         defaults to track_low_thresh.  gmc=2 or 4 (BoT-SORT only): the camera motion of every frame is estimated on the device at that
         downscale (aic_pipeline_option "gmc", gmc.py) and warps the predicted tracks; group_warps() reads the last group's.
         streams=S (ByteTrack / OC-SORT only): one pipeline for S cameras.  The ring and every run range are tick-major, slot t * S + s
-        being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams."""
-        self.streams = int(streams)
-        if self.streams != 1 and tracker not in ("bytetrack", "ocsort"):
+        being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams.
+        BoT-SORT for S cameras: TrackingPipeline.botsort_bank(...), which passes the camera count as _cameras."""
+        self.streams = int(_cameras) or int(streams)
+        if _cameras and tracker != "botsort":
+            raise ValueError("a camera count needs tracker='botsort' (TrackingPipeline.botsort_bank)")
+        if int(streams) != 1 and tracker not in ("bytetrack", "ocsort"):
             raise ValueError("streams needs tracker='bytetrack' or 'ocsort'")
         if gmc and tracker != "botsort":
             raise ValueError("gmc needs tracker='botsort'")
@@ -97,8 +100,12 @@ class TrackingPipeline:
                                            float(conf_thresh), float(iou_thresh), self.max_det, 0.0,
                                            int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
             self._h = C.c_void_p()
-            L.call("aic_pipeline_create_botsort", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self.botsort_params),
-                   C.byref(self._h))
+            if _cameras:
+                L.call("aic_pipeline_create_botsort_bank", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self.botsort_params),
+                       int(_cameras), C.byref(self._h))
+            else:
+                L.call("aic_pipeline_create_botsort", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self.botsort_params),
+                       C.byref(self._h))
             self.tracker_core = None
             if gmc:
                 self.option("gmc", int(gmc))
@@ -119,8 +126,24 @@ class TrackingPipeline:
         self.tracker_core = TrackerCore._from_handle(th, tp)
         self.tracker_core._dim = self.reid.out_dim
 
+    @classmethod
+    def botsort_bank(cls, yolo_engine, reid_engine, frame_hw, cameras, gmc=0, **kw):
+        """A BoT-SORT pipeline for `cameras` cameras (aic_pipeline_create_botsort_bank): the tracker is a bank of that many streams, fixed
+        here because the smoothed features and the camera-motion estimator (gmc=2 or 4: a bank as well) are sized by it.  The other
+        arguments are those of tracker="botsort"; the ring and every run range are tick-major as with streams=S, batch and
+        ring_frames are multiples of `cameras`, reset_stream(s) works and `.streams` is the camera count."""
+        cameras = int(cameras)
+        if not 1 <= cameras <= 256:
+            raise ValueError("cameras must be in 1..256")
+        if "tracker" in kw or "streams" in kw:
+            raise TypeError("botsort_bank fixes tracker and streams itself")
+        batch = int(kw.get("batch", 8))
+        if batch % cameras or int(kw.get("ring_frames") or 4 * batch) % cameras:
+            raise ValueError("batch and ring_frames must be multiples of cameras")
+        return cls(yolo_engine, reid_engine, frame_hw, tracker="botsort", gmc=gmc, _cameras=cameras, **kw)
+
     def reset_stream(self, s):
-        """streams=S pipelines, between run calls: stream s as after creation (a camera reconnecting)."""
+        """streams=S and botsort_bank pipelines, between run calls: stream s as after creation (a camera reconnecting)."""
         L.call("aic_pipeline_reset_stream", self._h, int(s))
 
     def close(self):

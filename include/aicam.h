@@ -57,6 +57,8 @@ typedef struct aic_gmc aic_gmc;             /* camera-motion estimator of one vi
 typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream            */
 typedef struct aic_bytetrack_bank aic_bytetrack_bank; /* ByteTrack state of 1..256 streams    */
 typedef struct aic_ocsort_bank aic_ocsort_bank;       /* OC-SORT state of 1..256 streams      */
+typedef struct aic_botsort_bank aic_botsort_bank;     /* BoT-SORT state of 1..256 streams     */
+typedef struct aic_gmc_bank aic_gmc_bank;             /* camera-motion estimator of 1..256 streams */
 
 /* ------------------------------------------------------------------ library / device */
 const char* aic_last_error(void);
@@ -451,6 +453,27 @@ int aic_botsort_export(aic_botsort* t, int cap, int32_t* track_id, int32_t* stat
 int aic_botsort_counters(aic_botsort* t, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_appearance,
                          int64_t* cost_cycles, int64_t* kernel_cycles);
 
+/* A bank of `streams` (1..256) BoT-SORT streams: every call as its aic_bytetrack_bank_* counterpart.  Each stream has its own table,
+ * smoothed features (max_tracks * feature_dim floats, allocated for `streams`) and ids, and computes exactly what an aic_botsort fed the
+ * same frames computes.  AIC_ERR_INVALID for streams outside 1..256 and as aic_botsort_create (checked before the device). */
+int aic_botsort_bank_create(int device, const aic_botsort_params* p, int streams, aic_botsort_bank** out);
+int aic_botsort_bank_destroy(aic_botsort_bank* b);
+int aic_botsort_bank_option(aic_botsort_bank* b, const char* key, int value);
+/* As aic_bytetrack_bank_update (frames_per_stream[streams], F frames in all, stream-major; status[streams] and the per-stream failure
+ * contract), plus, as aic_botsort_update_batch: feat[sum, feature_dim] for all rows of the call or NULL, valid[sum] or NULL, and
+ * warps[F, 6] (one row per frame of the call, in the frames' order) or NULL.  The features are normalised once over all rows. */
+int aic_botsort_bank_update(aic_botsort_bank* b, const int32_t* frames_per_stream, const int32_t* counts, const float* boxes_xyxy,
+                            const float* conf, const int32_t* cls, const float* feat, const int32_t* valid, const float* warps,
+                            int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status);
+/* The stream as after create: no tracks, no smoothed features, ids from first_track_id again, a stop cleared. */
+int aic_botsort_bank_reset(aic_botsort_bank* b, int stream);
+/* As aic_botsort_export / aic_botsort_counters for one stream; export fails with AIC_ERR_INVALID for a stopped stream only. */
+int aic_botsort_bank_export(aic_botsort_bank* b, int stream, int cap, int32_t* track_id, int32_t* state, int32_t* is_activated,
+                            int32_t* start_frame, int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov,
+                            int32_t* has_feat, float* smooth_feat, int32_t* n_tracks, int32_t* n_tracked);
+int aic_botsort_bank_counters(aic_botsort_bank* b, int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side,
+                              int64_t* n_appearance, int64_t* cost_cycles, int64_t* kernel_cycles);
+
 /* ------------------------------------------------------------------ camera motion
  * The 2x3 affine of the camera motion between consecutive frames (previous-frame pixel coordinates -> current-frame ones, the `warps` of
  * aic_botsort_update_batch), estimated on the device (csrc/kernels_gmc.hip; specification: tests/gmc_oracle.py):
@@ -475,6 +498,17 @@ int aic_gmc_reset(aic_gmc* g);
  * first frame, and a frame whose motion could not be estimated, get the identity and ok = 0. */
 int aic_gmc_estimate_batch(aic_gmc* g, const uint8_t* frames_bgr, int k, int mem, const int32_t* counts, const float* boxes_xyxy,
                            float* warps_out, int32_t* stats_out);
+
+/* A bank: the estimator of `streams` (1..256) cameras of one frame size whose frames come tick-major (frame t * streams + s = tick t of
+ * camera s); aic_gmc is the bank of one.  AIC_ERR_INVALID as aic_gmc_create and for streams outside 1..256 (checked before the device). */
+int aic_gmc_bank_create(int device, int height, int width, const aic_gmc_params* p, int streams, aic_gmc_bank** out);
+int aic_gmc_bank_destroy(aic_gmc_bank* b);
+/* Forget camera `stream`'s previous frame: its next frame is its first (identity, every block skipped). */
+int aic_gmc_bank_reset(aic_gmc_bank* b, int stream);
+/* `ticks` ticks of every camera: ticks * streams frames, counts, warps_out and stats_out rows, tick-major, otherwise as
+ * aic_gmc_estimate_batch.  A frame's predecessor is the same camera's frame of the tick before (of the call before for tick 0). */
+int aic_gmc_bank_estimate(aic_gmc_bank* b, const uint8_t* frames_bgr, int ticks, int mem, const int32_t* counts, const float* boxes_xyxy,
+                          float* warps_out, int32_t* stats_out);
 
 /* ------------------------------------------------------------------ end-to-end pipeline
  * The loop body of src/aicamera_tracker.py:169-207 (detect + track, the reference's own FPS
@@ -519,6 +553,13 @@ int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, co
  * "device_assoc_limit", "device_filter" fail with AIC_ERR_INVALID. */
 int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp,
                                 aic_pipeline** out);
+/* A BoT-SORT pipeline for `streams` (1..256) cameras, fixed at creation (the smoothed features and the camera-motion estimator are sized
+ * by it): the tracker is a BoT-SORT bank as above, ids per camera from bp->first_track_id, the ring and every run range are tick-major as with
+ * the option "streams", and `batch` and `ring_frames` must be multiples of `streams`.  With the option "gmc" the estimator is a bank of
+ * `streams` and aic_pipeline_group_warps returns the group's rows in slot order.  aic_pipeline_reset_stream works; the option "streams"
+ * does not (AIC_ERR_INVALID, as on aic_pipeline_create_botsort). */
+int aic_pipeline_create_botsort_bank(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp,
+                                     int streams, aic_pipeline** out);
 int aic_pipeline_destroy(aic_pipeline* p);
 /* Copy `count` u8 BGR frames into ring slots [slot, slot+count). */
 int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames_bgr, int count);
@@ -615,7 +656,9 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
  * tick-major over that many camera streams, slot t * streams + s being tick t of stream s, and the tracker is a bank (one kernel block
  * per stream).  `batch` must be a multiple of it, as must slot and count of every run call; launch groups round to whole ticks. */
 int aic_pipeline_option(aic_pipeline* p, const char* key, int value);
-/* A pipeline with "streams": stream s as after create (aic_bytetrack_bank_reset), between run calls. */
+/* A pipeline with "streams", or one from aic_pipeline_create_botsort_bank: stream s as after create (aic_bytetrack_bank_reset), between
+ * run calls; with "gmc" the camera's carried gray level is forgotten as well.  AIC_ERR_INVALID on DeepSORT and aic_pipeline_create_botsort
+ * pipelines. */
 int aic_pipeline_reset_stream(aic_pipeline* p, int stream);
 /* The warps [n_frames, 6] (as aic_gmc_estimate_batch) of the most recently finished launch group of a pipeline with "gmc" set;
  * AIC_ERR_INVALID without it.  warps may be NULL; *n_frames is the group's frame count, at most cap_frames rows are written. */

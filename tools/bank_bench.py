@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
-"""Tracker banks against loops over single trackers, and the conv CU reserve of a multi-stream pipeline (run by hand; DESIGN.md §22).
+"""Tracker banks against loops over single trackers, and the conv CU reserve of a multi-stream pipeline (run by hand; DESIGN.md §22, §23).
 
-    python tools/bank_bench.py tracker  [--kinds bytetrack,ocsort] [--streams 1,8,32,128,256] [--ticks 256]
+    python tools/bank_bench.py tracker  [--kinds bytetrack,ocsort,botsort] [--streams 1,8,32,128,256] [--ticks 256]
     python tools/bank_bench.py pipeline [--streams 1,8,32] [--reserve 1,2,4,8,16] [--ring 512] [--batch 256]
+    python tools/bank_bench.py botsort  [--streams 1,8,32,128,256] [--ticks 256]           # shorthand: tracker --kinds botsort
+    python tools/bank_bench.py botsort-pipeline [--streams 1,8,32] [--ring 512] [--batch 256] [--steps 5] [--gmc 0]
 
 tracker:  S synthetic 30-person streams for `ticks` ticks, fed one tick per call and 16 ticks per call, to a bank of S streams
           (one launch of S blocks per epoch) and to S single trackers in a loop (S launches and syncs per epoch: what a caller had
           before the banks).  Prints frames/s and ms per tick.
 pipeline: the ByteTrack pipeline on the trained detector's own detections, ring resident in HBM, `streams` tick-major streams, the
           epoch blocks' CU reserve ("tracker_cus") swept.  Prints frames/s.
+botsort (a kind of `tracker`): every detection carries a 512-float feature (synthetic.identity_features, feature_dim 512), so a call
+          uploads 2 KB per detection on top.
+botsort-pipeline: the BoT-SORT bank pipeline (TrackingPipeline.botsort_bank) on the trained detector's own detections with the seeded
+          ReID engine, ring resident in HBM, against S single BoT-SORT pipelines, each created, warmed, run `steps` times on one
+          camera's ring / S frames and closed before the next (the time of step i is the sum of the S pipelines' i-th runs).
 Every configuration is a child process of its own under `timeout`, and the first one that fails ends the run.
 """
 from __future__ import annotations
@@ -35,11 +42,24 @@ def stream_frames(seed, ticks):
     return [tuple(np.ascontiguousarray(a) for a in sc.detections(f)[:3]) for f in range(ticks)]
 
 
+def stream_frames_with_features(seed, ticks):
+    import numpy as np
+    syn = pkg("synthetic")
+    sc = syn.Scene(seed=seed, n_targets=30, conf_range=(0.3, 0.95), jitter=1.5, shuffle=True)
+    out = []
+    for f in range(ticks):
+        b, c, k, ident = sc.detections(f)
+        out.append((np.ascontiguousarray(b), np.ascontiguousarray(c), np.ascontiguousarray(k), syn.identity_features(ident, f, dim=512, seed=seed)))
+    return out
+
+
 def step_tracker(kind, S, ticks):
-    base = [stream_frames(seed, ticks) for seed in range(min(S, 8))]       # 8 distinct scenes, reused round-robin
+    make = stream_frames_with_features if kind == "botsort" else stream_frames
+    base = [make(seed, ticks) for seed in range(min(S, 8))]                # 8 distinct scenes, reused round-robin
     dets = [base[s % len(base)] for s in range(S)]
-    mod = pkg("bytetrack" if kind == "bytetrack" else "ocsort")
-    Bank, One = (mod.BYTETrackerBank, mod.BYTETracker) if kind == "bytetrack" else (mod.OCSortBank, mod.OCSort)
+    mod = pkg(kind)
+    Bank, One = {"bytetrack": lambda: (mod.BYTETrackerBank, mod.BYTETracker), "ocsort": lambda: (mod.OCSortBank, mod.OCSort),
+                 "botsort": lambda: (mod.BoTSORTBank, mod.BoTSORT)}[kind]()
     out = dict(kind=kind, streams=S, ticks=ticks)
     for per_call in (1, 16):
         bk = Bank(S)
@@ -85,9 +105,45 @@ def step_pipeline(S, reserve, ring, batch, steps):
                           fps_min=ring / max(times), fps_max=ring / min(times))), flush=True)
 
 
+def step_botsort_pipeline(S, ring, batch, steps, gmc):
+    """frames/s over all cameras: one botsort_bank pipeline of S cameras against S single pipelines one after another (ring / S frames each)."""
+    import numpy as np
+    ypath = pkg("engine_file").ensure_trained_detector(ROOT)
+    _, rpath = pkg("engine_file").ensure_seeded_engines(ROOT)
+    TP = pkg("pipeline").TrackingPipeline
+    uniq = pkg("synthetic").Scene(seed=0, n_targets=30).render_batch(0, 64)
+    kw = dict(max_persons=64, dtype="fp16")
+
+    def timed(pipe, n):
+        pipe.run_raw(0, n)                                                  # warm-up
+        ts = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            pipe.run_raw(0, n)
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    bank = TP.botsort_bank(ypath, rpath, (720, 1280), cameras=S, gmc=gmc, batch=batch, ring_frames=ring, **kw)
+    for i in range(0, ring, 64):                                            # every camera walks the same 64-frame clip
+        bank.upload(i, uniq[[((i + j) // S) % 64 for j in range(min(64, ring - i))]])
+    tb = timed(bank, ring)
+    bank.close()
+    n1 = ring // S
+    t1 = [0.0] * steps
+    for _ in range(S):                                                      # S cameras one after another, a pipeline each
+        one = TP(ypath, rpath, (720, 1280), batch=min(batch, n1), ring_frames=n1, tracker="botsort", gmc=gmc, **kw)
+        one.upload(0, uniq[[j % 64 for j in range(n1)]])
+        t1 = [a + b for a, b in zip(t1, timed(one, n1))]
+        one.close()
+    print(json.dumps(dict(streams=S, ring=ring, batch=batch, gmc=gmc, bank_fps_median=ring / float(np.median(tb)), bank_fps_min=ring / max(tb),
+                          bank_fps_max=ring / min(tb), singles_fps_median=ring / float(np.median(t1)), singles_fps_min=ring / max(t1),
+                          singles_fps_max=ring / min(t1))), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("mode", choices=("tracker", "pipeline", "step-tracker", "step-pipeline"))
+    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline"))
+    p.add_argument("--gmc", type=int, default=0)
     p.add_argument("--kinds", default="bytetrack,ocsort")
     p.add_argument("--streams", default=None)
     p.add_argument("--ticks", type=int, default=256)
@@ -101,8 +157,15 @@ def main():
         return step_tracker(a.kinds, int(a.streams), a.ticks)
     if a.mode == "step-pipeline":
         return step_pipeline(int(a.streams), int(a.reserve), a.ring, a.batch, a.steps)
+    if a.mode == "step-botsort-pipeline":
+        return step_botsort_pipeline(int(a.streams), a.ring, a.batch, a.steps, a.gmc)
     me = [sys.executable, os.path.abspath(__file__)]
-    if a.mode == "tracker":
+    if a.mode == "botsort":
+        a.mode, a.kinds = "tracker", "botsort"
+    if a.mode == "botsort-pipeline":
+        jobs = [me + ["step-botsort-pipeline", "--streams", s, "--ring", str(a.ring), "--batch", str(a.batch), "--steps", str(a.steps),
+                      "--gmc", str(a.gmc)] for s in (a.streams or "1,8,32").split(",")]
+    elif a.mode == "tracker":
         jobs = [me + ["step-tracker", "--kinds", k, "--streams", s, "--ticks", str(a.ticks)]
                 for k in a.kinds.split(",") for s in (a.streams or "1,8,32,128,256").split(",")]
     else:
