@@ -292,6 +292,9 @@ __global__ __launch_bounds__(256) void cosine_min_mfma_kernel(const float* __res
     // are never read (the min below and the atomics are guarded), and the loads stay branch-free
     const float* grow = gal_n + ((size_t)slots[t] * gmax + min(g0 + r, len - 1)) * dim;
     unsigned int* out = reinterpret_cast<unsigned int*>(cost) + (size_t)t * n;
+    // rows start at row * dim floats: 16-byte aligned only when dim % 4 == 0.  Otherwise (block-uniform) the element-guarded loop
+    // walks all of K, k in the same order
+    const bool vec = (dim & 3) == 0;
     for (int d0 = 0; d0 < n; d0 += 32) {
         const int da = d0 + r, db = d0 + 16 + r;
         const float* pa = det_n + (size_t)min(da, n - 1) * dim;
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(256) void cosine_min_mfma_kernel(const float* __res
         const bool oka = da < n, okb = db < n;
         floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         int k0 = 0;
-        for (; k0 + 64 <= dim; k0 += 64) {          // 12 independent 16-byte loads in flight per lane
+        for (; vec && k0 + 64 <= dim; k0 += 64) {   // 12 independent 16-byte loads in flight per lane
             floatx4 a[4], b0[4], b1[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -473,6 +476,7 @@ __global__ __launch_bounds__(1024) void trk_assoc_all_kernel(float* mean, float*
         for (int j = lane; j < n; j += 64) red[sl * n + j] = 3.0e38f;
     const int kmid = two ? (dim / 2) / 64 * 64 : dim;   // K split on a 64-element boundary (the tail stays in the upper half)
     const int k_lo = ks ? kmid : 0, k_hi = ks ? dim : kmid;
+    const bool vec = (dim & 3) == 0;                    // 16-byte row loads need dim % 4 == 0; else the element-guarded loop walks all of K
     for (int gb = 0; gb < len; gb += 128) {             // block-uniform trip counts: the barriers below are safe
         const int g0 = gb + sl * 16;
         const bool live = g0 < len;
@@ -484,7 +488,7 @@ __global__ __launch_bounds__(1024) void trk_assoc_all_kernel(float* mean, float*
                 const float* pa = det_n + (size_t)min(da, n - 1) * dim;
                 const float* pb = det_n + (size_t)min(db, n - 1) * dim;
                 int k0 = k_lo;
-                for (; k0 + 64 <= k_hi; k0 += 64) {
+                for (; vec && k0 + 64 <= k_hi; k0 += 64) {
                     floatx4 a[4], b0[4], b1[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
