@@ -207,6 +207,14 @@ _SIGS = {
     "aic_gmc_bank_reset": (_I, [_P, _I]),
     "aic_gmc_bank_estimate": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "aic_pipeline_create_botsort_bank": (_I, [_P, _P, _P, _P, _I, _P]),
+    "aic_deepsort_bank_create": (_I, [_I, _P, _I, _P]),
+    "aic_deepsort_bank_destroy": (_I, [_P]),
+    "aic_deepsort_bank_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_deepsort_bank_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "aic_deepsort_bank_reset": (_I, [_P, _I]),
+    "aic_deepsort_bank_export": (_I, [_P, _I, _I] + [_P] * 11),
+    "aic_deepsort_bank_export_gallery": (_I, [_P, _I, _I, _P, _I]),
+    "aic_deepsort_bank_counters": (_I, [_P, _I, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

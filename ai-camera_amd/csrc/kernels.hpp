@@ -141,6 +141,11 @@ void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const floa
 void launch_trk_epoch(DevTrkHdr* hdr, DevTrack* trk, int* free_slots, float* mean, float* cov, float* gal_raw, float* gal_n,
                       const TrkDevParams& prm, const EpochDets& dets, int f0, int k, int d_begin, int dn_pad, int nmax, int has_sm,
                       const EpochScratch& scr, const EpochOut& out, hipStream_t s);
+struct EpochBankArgs;
+void launch_trk_epoch_prep_bank(const EpochBankArgs& bk, int streams, const float* gal_n, int gmax, int dim, int cap, const float* featn,
+                                int dn_pad_max, int f0, int k, float* sm, float* gram, hipStream_t s);
+void launch_trk_epoch_bank(const EpochBankArgs& bk, int streams, float* mean, float* cov, float* gal_raw, float* gal_n, const TrkDevParams& prm,
+                           const EpochDets& dets, int f0, int k, int nmax_call, const EpochScratch& scr, const EpochOut& out, hipStream_t s);
 void launch_gallery_shard(const DevTrkHdr* hdr, const DevTrack* trk, const float* gal_n, int gmax, int dim, float* out, int t_max, hipStream_t s);
 // configs[4] annotation pass: gathered [world, t_max, 2 + dim] -> per row (all ranks) track id or -1, nearest valid row of another rank or -1, its cosine distance
 void launch_gallery_nearest(const float* gathered, int world, int t_max, int dim, int* ids, int* near_row, float* near_dist, hipStream_t s);

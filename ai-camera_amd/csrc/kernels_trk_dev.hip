@@ -83,13 +83,27 @@ __device__ __forceinline__ float cos_dist(float dot) {       // matching.py:136-
 // bit-identical to cos_tile's.  The suffix minima are then taken group by group, newest rows first.
 constexpr int SMG = 7;
 
+// A bank (bk.stream_k != NULL): blockIdx.y = stream; its table, galleries, SM / GRAM slices and dn / dn_pad come from the stream's plan, and
+// epoch-local row i of the stream is row rmap[i] of featn (the single tracker: featn starts at the epoch's first row, rows in one run).
 __global__ __launch_bounds__(256) void trk_epoch_prep_kernel(const DevTrkHdr* __restrict__ hdr, const DevTrack* __restrict__ trk,
                                                              const float* __restrict__ gal_n, int gmax, int dim,
                                                              const float* __restrict__ featn, int dn, int dn_pad, int k,
-                                                             float* __restrict__ sm, float* __restrict__ gram) {
+                                                             float* __restrict__ sm, float* __restrict__ gram, int f0, EpochBankArgs bk) {
     __shared__ float tiles[4][16][36];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     float (*tile)[36] = tiles[wv];
+    const int* rmap = nullptr;
+    if (bk.stream_k) {
+        const size_t sid = blockIdx.y;
+        const EpochStreamPlan pl = bk.plan[sid];
+        hdr = reinterpret_cast<const DevTrkHdr*>(bk.tbl + sid * bk.tbl_stride);
+        if (!pl.has_sm || bk.stream_k[sid] <= f0 || hdr->err) return;      // what the epoch kernel's block of this stream will not read
+        trk = reinterpret_cast<const DevTrack*>(hdr + 1);
+        gal_n += sid * bk.gal_stride, sm += sid * bk.sm_stride, gram += sid * bk.gram_stride;
+        dn = pl.dn, dn_pad = pl.dn_pad;
+        rmap = bk.row_map + pl.map0;
+    }
+    auto frow = [&](int i) -> const float* { return featn + (size_t)(rmap ? rmap[i] : i) * dim; };
     const int T0 = hdr->n_tracks;
     const int nchunk = dn_pad / 32;
     const int n_sm = T0 * nchunk, n_all = n_sm + (dn_pad / 16) * nchunk;
@@ -98,13 +112,13 @@ __global__ __launch_bounds__(256) void trk_epoch_prep_kernel(const DevTrkHdr* __
         const int tk = is_sm ? task : task - n_sm;
         const int rowi = tk / nchunk, c = tk - rowi * nchunk;     // track (SM) or 16-row detection group (GRAM)
         const int d_base = c * 32;
-        const float* pa = featn + (size_t)min(d_base + r, dn - 1) * dim;
-        const float* pb = featn + (size_t)min(d_base + 16 + r, dn - 1) * dim;
+        const float* pa = frow(min(d_base + r, dn - 1));
+        const float* pb = frow(min(d_base + 16 + r, dn - 1));
         if (!is_sm) {
             const int a0 = rowi * 16;
             if (a0 >= d_base + 32) continue;                      // rows all later than the columns: never read (an appended row only meets LATER frames)
             floatx4 acc0, acc1;
-            cos_tile(featn + (size_t)min(a0 + r, dn - 1) * dim, pa, pb, dim, q, acc0, acc1);
+            cos_tile(frow(min(a0 + r, dn - 1)), pa, pb, dim, q, acc0, acc1);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float* o = gram + (size_t)(a0 + 4 * q + e) * dn_pad + d_base;
@@ -273,6 +287,8 @@ struct EpochArgs {
     int lds_bytes;
     int commit_ext;                        // 1: the appended gallery rows are copied by gallery_commit_kernel after this launch (the list + its count stay in scr.appends)
     long long* prof;                       // AICAM_TRK_PHASES: shader-clock cycles per phase, accumulated by thread 0 (NULL: off)
+    int cost_plane;                        // floats between the three full matrices in scr.cost
+    EpochBankArgs bank;                    // bank.stream_k != NULL: block s = stream s; the fields above that are per stream are resolved at the kernel's top
 };
 
 namespace {
@@ -587,9 +603,47 @@ __device__ __forceinline__ int ring_push(int& glen, int& ghead, int gmax) {
 
 #define PHASE(i) do { if (a.prof && threadIdx.x == 0) { const long long _t = clock64(); atomicAdd((unsigned long long*)&a.prof[i], (unsigned long long)(_t - t_ph)); t_ph = _t; } } while (0)
 
-__global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
+// a block-uniform value the compiler cannot see as one (loaded from memory the kernel also writes): back into scalar registers
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <class T> __device__ __forceinline__ T* uni(T* p) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
+}
+
+// BANK = false is the single tracker's kernel as it always was (its arguments stay kernel arguments); BANK = true resolves the block's stream.
+template <bool BANK>
+__global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_err;
+    // ---- this block's stream.  The single tracker: the launch's arguments as they are.  A bank: table, Kalman state, galleries, scratch
+    //      slices and the epoch's facts of stream blockIdx.x; local frame i of the stream is row row0 + i * fstride of dets / out.
+    EpochArgs a_bank;
+    if constexpr (BANK) a_bank = a_in;
+    EpochArgs& a = BANK ? a_bank : a_in;
+    int row0 = 0, fstride = 1;
+    const int* rmap = nullptr;             // bank: epoch-local row -> detection row (the single tracker's rows are one run from d_begin)
+    const int* fe0 = nullptr;              // bank: first epoch-local row of a frame, by the frame's row of dets
+    if constexpr (BANK) {
+        const EpochBankArgs& b = a_in.bank;
+        const size_t sid = blockIdx.x;
+        a.hdr = uni(reinterpret_cast<DevTrkHdr*>(b.tbl + sid * b.tbl_stride));
+        const int left = uni(b.stream_k[sid] - a.f0);
+        if (left <= 0 || uni(a.hdr->err)) {     // no frames left in this epoch, or stopped by an earlier one: the table is not touched
+            if (threadIdx.x == 0) (a_in.scr.appends + sid * TRK_APPENDS_INTS)[3 * TRK_DEV_DNMAX] = 0;     // (nothing for gallery_commit_kernel)
+            return;
+        }
+        a.k = min(a.k, left);
+        a.trk = reinterpret_cast<DevTrack*>(a.hdr + 1);
+        a.free_slots = reinterpret_cast<int*>(a.trk + a.prm.cap);
+        a.mean = uni(a_in.mean + sid * b.mean_stride), a.cov = uni(a_in.cov + sid * b.cov_stride);
+        a.scr.sm = uni(a_in.scr.sm + sid * b.sm_stride), a.scr.gram = uni(a_in.scr.gram + sid * b.gram_stride);
+        a.scr.cost = uni(a_in.scr.cost + sid * b.cost_stride), a.scr.sub = uni(a_in.scr.sub + sid * b.sub_stride);
+        const EpochStreamPlan pl = b.plan[sid];
+        a.d_begin = 0, a.dn_pad = uni(pl.dn_pad), a.nmax = uni(pl.nmax), a.has_sm = uni(pl.has_sm);
+        fe0 = b.frame_e0;
+        row0 = uni(b.stream_f0[sid]), fstride = b.frame_stride;
+    }
     long long t_ph = a.prof ? clock64() : 0;
     const Lds L = lds_carve(smem, a.prm.cap, a.nmax, a.lds_bytes, a.k);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -619,7 +673,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
 
     // the detections of a frame are requested one frame ahead (four global loads per detection, a round trip to L2 / HBM under the conv
     // kernels' traffic: they used to open every frame) and wait in registers
-    int pn = a.dets.frame_n[a.f0], pd0 = a.dets.frame_d0[a.f0];
+    int pn = a.dets.frame_n[row0 + a.f0 * fstride], pd0 = a.dets.frame_d0[row0 + a.f0 * fstride];
     floatx4 pb = {0.f, 0.f, 0.f, 0.f};
     float pconf = 0.f;
     int pcls = 0, phas = 0;
@@ -634,12 +688,13 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
     fetch_dets(pn, pd0);
     int fi = 0, err_frame = -1;
     for (; fi < a.k; ++fi) {
-        const int f = a.f0 + fi;
+        const int fl = a.f0 + fi;                                // local frame of the stream (what err_frame reports)
+        const int f = row0 + fl * fstride;                       // its row of dets / out
         const int n = pn, d0 = pd0;
-        const int erow0 = d0 - a.d_begin;                        // first epoch row of this frame
+        const int erow0 = BANK ? uni(fe0[f]) : d0 - a.d_begin;   // first epoch row of this frame
         if (n > a.nmax || n > TRK_DEV_NMAX || erow0 + n > a.dn_pad) {     // (block-uniform: every thread read the same counts -- no barrier needed,
             if (tid == 0) s_err = 3;                                      //  and the one that stood here waited for the previous frame's output stores)
-            err_frame = f;
+            err_frame = fl;
             break;
         }
         // ---- detections of the frame -> LDS (detection.py:36-47 for xyah); Kalman predict of every track (tracker_core.py:44-49)
@@ -657,7 +712,7 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
             L.und[tid] = tid;
         }
         if (fi + 1 < a.k) {                                       // the next frame's detections: in flight until the next iteration
-            pn = a.dets.frame_n[f + 1], pd0 = a.dets.frame_d0[f + 1];
+            pn = a.dets.frame_n[f + fstride], pd0 = a.dets.frame_d0[f + fstride];
             fetch_dets(pn, pd0);
         }
         if (tid == 0 && a.out.dbg_match && a.out.dbg_stride) a.out.dbg_match[(size_t)f * a.out.dbg_stride] = 0;
@@ -679,8 +734,8 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
         // the three full matrices in HBM scratch.
         const bool cost_lds = !a.out.dbg_tn && T > 0 && n > 0 && tn + 24 * T <= L.arena_floats;
         float* c_app = cost_lds ? L.arena : a.scr.cost;            // lean: the gated matrix (appearance first, the gate applied in place)
-        float* c_maha = cost_lds ? nullptr : a.scr.cost + (size_t)TRK_DEV_TMAX * TRK_DEV_NMAX;
-        float* c_iou = cost_lds ? nullptr : a.scr.cost + 2 * (size_t)TRK_DEV_TMAX * TRK_DEV_NMAX;
+        float* c_maha = cost_lds ? nullptr : a.scr.cost + (size_t)a.cost_plane;
+        float* c_iou = cost_lds ? nullptr : a.scr.cost + 2 * (size_t)a.cost_plane;
         const FrameCosts fc{cost_lds ? nullptr : c_app, c_maha, c_iou, cost_lds ? L.arena + tn : L.arena, cost_lds ? L.arena_floats - tn : L.arena_floats,
                             cost_lds ? c_app : nullptr, a.mean};
         // Gate data of a track (innovation covariance, its Cholesky factor, the predicted box) are the same for all its pairs: ONE THREAD per
@@ -847,14 +902,14 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
             }
         }
         __syncthreads();
-        if (s_err) { err_frame = f; break; }
+        if (s_err) { err_frame = fl; break; }
         PHASE(4);
 
         // ---- lifecycle (tracker_core.py:63-81): unmatched detections in ascending order become new tracks
         const int U = block_compact(tid < n && L.mtrk[tid] < 0, tid, L.cols, L.wcnt);
         if (nfree < U || T + U > BT) { if (tid == 0) s_err = 1; }
         __syncthreads();
-        if (s_err) { err_frame = f; break; }
+        if (s_err) { err_frame = fl; break; }
         if (tid < T) {
             const int det = L.mdet[tid];
             if (det >= 0) {                                        // Track.update, track.py:82-104
@@ -1042,6 +1097,16 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
     //      ring is at ghead + glen - 1: entry q of track t goes to ghead + glen - napp + q.  Dead tracks' rows are not written.
     //      16-byte copies, four rows per wave in flight (dim % 4 == 0 on this path)
     __syncthreads();
+    if constexpr (BANK) {                  // what only the epoch's tail reads is resolved here, not carried through the frames in registers
+        const EpochBankArgs& b = a_in.bank;
+        const size_t sid = blockIdx.x;
+        a.hdr = uni(reinterpret_cast<DevTrkHdr*>(b.tbl + sid * b.tbl_stride));
+        a.trk = reinterpret_cast<DevTrack*>(a.hdr + 1);
+        a.free_slots = reinterpret_cast<int*>(a.trk + a.prm.cap);
+        a.gal_raw = uni(a_in.gal_raw + sid * b.gal_stride), a.gal_n = uni(a_in.gal_n + sid * b.gal_stride);
+        a.scr.appends = uni(a_in.scr.appends + sid * TRK_APPENDS_INTS);
+        rmap = uni(b.row_map + b.plan[sid].map0);
+    }
     {
         const int myn = tid < T ? L.napp[tid] : 0;
         int incl = myn;                                          // inclusive scan over the wave, wave totals through wcnt
@@ -1065,7 +1130,8 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a) {
             if (pos >= gmax) pos -= gmax;
             for (int q = 0; q < myn; ++q) {
                 int* e = a.scr.appends + (size_t)(off + q) * 3;
-                e[0] = slot, e[1] = pos, e[2] = L.newrow[tid * KS + q];
+                const int er = L.newrow[tid * KS + q];
+                e[0] = slot, e[1] = pos, e[2] = rmap ? rmap[er] : er;       // bank: the detection row itself (d_begin = 0)
                 if (++pos == gmax) pos = 0;
             }
         }
@@ -1279,8 +1345,12 @@ void launch_gallery_shard(const DevTrkHdr* hdr, const DevTrack* trk, const float
 // ------------------------------------------------------------------------------------------------ gallery commit
 // The rows an epoch appended to the galleries (list left by trk_epoch_kernel: slot, ring position, epoch row; length behind the list),
 // raw + unit, one row per block and pass.
+// A bank (gal_stride > 0 with more than one grid row): blockIdx.y = stream, whose list holds detection rows themselves (d_begin = 0).
 __global__ __launch_bounds__(256) void gallery_commit_kernel(const int* __restrict__ appends, const float* __restrict__ feat, const float* __restrict__ feat_n,
-                                                             int d_begin, int dim, int gmax, float* __restrict__ gal_raw, float* __restrict__ gal_n) {
+                                                             int d_begin, int dim, int gmax, float* __restrict__ gal_raw, float* __restrict__ gal_n,
+                                                             size_t gal_stride) {
+    appends += (size_t)blockIdx.y * TRK_APPENDS_INTS;
+    gal_raw += blockIdx.y * gal_stride, gal_n += blockIdx.y * gal_stride;
     const int na = min(appends[3 * TRK_DEV_DNMAX], TRK_DEV_DNMAX), d4 = dim >> 2;
     const floatx4* fr = reinterpret_cast<const floatx4*>(feat + (size_t)d_begin * dim);
     const floatx4* fn = reinterpret_cast<const floatx4*>(feat_n + (size_t)d_begin * dim);
@@ -1310,12 +1380,28 @@ void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const floa
     // (9 969, five runs), with 32 the launch itself gets too long (9 708).
     const long likely = ((long)dn_pad / std::max(k, 1) + dn_pad / 16) * (dn_pad / 32);
     const int grid = (int)std::min<long>(std::min<long>(512, (tasks + 3) / 4), std::max<long>(64, likely / 9));
-    hipLaunchKernelGGL(trk_epoch_prep_kernel, dim3(grid), dim3(256), 0, s, hdr, trk, gal_n, gmax, dim, featn, dn, dn_pad, k, sm, gram);
+    hipLaunchKernelGGL(trk_epoch_prep_kernel, dim3(grid), dim3(256), 0, s, hdr, trk, gal_n, gmax, dim, featn, dn, dn_pad, k, sm, gram, 0, EpochBankArgs{});
+    KCHECK();
+}
+
+// The bank form: `dn_pad_max` is the largest dn_pad of a stream's plan in this epoch (the grid is sized for it; a block whose stream has
+// fewer tasks leaves its task loop at once).
+void launch_trk_epoch_prep_bank(const EpochBankArgs& bk, int streams, const float* gal_n, int gmax, int dim, int cap, const float* featn,
+                                int dn_pad_max, int f0, int k, float* sm, float* gram, hipStream_t s) {
+    if (dn_pad_max <= 0 || streams <= 0) return;
+    const long tasks = ((long)cap + dn_pad_max / 16) * (dn_pad_max / 32);
+    const long likely = ((long)dn_pad_max / std::max(k, 1) + dn_pad_max / 16) * (dn_pad_max / 32);
+    // one stream: the single tracker's grid.  S streams share the 256 CUs: at least 8 blocks each, about 1024 in all
+    const long per = std::min<long>(std::min<long>(512, (tasks + 3) / 4), std::max<long>(64, likely / 9));
+    const int grid = (int)std::max<long>(std::min<long>(per, std::max<long>(8, 1024 / streams)), 1);
+    hipLaunchKernelGGL(trk_epoch_prep_kernel, dim3(grid, streams), dim3(256), 0, s, (const DevTrkHdr*)nullptr, (const DevTrack*)nullptr, gal_n, gmax,
+                       dim, featn, 0, 0, k, sm, gram, f0, bk);
     KCHECK();
 }
 
 static void epoch_attr() {
-    set_lds_limit(trk_epoch_kernel, epoch_lds_bytes());
+    set_lds_limit(trk_epoch_kernel<false>, epoch_lds_bytes());
+    set_lds_limit(trk_epoch_kernel<true>, epoch_lds_bytes());
     set_lds_limit(trk_cascade_test_kernel, epoch_lds_bytes());
 }
 
@@ -1354,11 +1440,40 @@ void launch_trk_epoch(DevTrkHdr* hdr, DevTrack* trk, int* free_slots, float* mea
     a.scr = scr, a.out = out, a.lds_bytes = epoch_lds_bytes();
     a.commit_ext = (dets.feat != nullptr && dets.feat_n != nullptr && scr.appends != nullptr && prm.dim % 4 == 0) ? 1 : 0;
     a.prof = g_phase.d;
+    a.cost_plane = TRK_DEV_TMAX * TRK_DEV_NMAX;
+    a.bank = EpochBankArgs{};
     g_phase.launches += 1, g_phase.frames += k;
-    hipLaunchKernelGGL(trk_epoch_kernel, dim3(1), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
+    hipLaunchKernelGGL(trk_epoch_kernel<false>, dim3(1), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
     KCHECK();
     if (a.commit_ext) {
-        hipLaunchKernelGGL(gallery_commit_kernel, dim3(256), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n);
+        hipLaunchKernelGGL(gallery_commit_kernel, dim3(256), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n,
+                           (size_t)0);
+        KCHECK();
+    }
+}
+
+// The bank form: local frames [f0, f0 + k) of every stream, one block per stream; mean / cov / gal_raw / gal_n / scr are stream 0's, the
+// others' lie the strides of `bk` behind.  nmax_call: most detections in a frame of the call (the pitch scr.cost / scr.sub were sized for).
+void launch_trk_epoch_bank(const EpochBankArgs& bk, int streams, float* mean, float* cov, float* gal_raw, float* gal_n, const TrkDevParams& prm,
+                           const EpochDets& dets, int f0, int k, int nmax_call, const EpochScratch& scr, const EpochOut& out, hipStream_t s) {
+    AIC_REQUIRE(prm.cap <= TRK_DEV_TMAX && nmax_call <= TRK_DEV_NMAX && k >= 1 && k <= TRK_KMAX && streams >= 1, AIC_ERR_CAPACITY,
+                "device association: shape beyond the epoch kernel");
+    AIC_REQUIRE(bk.stream_k && bk.stream_f0 && bk.plan && bk.row_map && scr.appends && prm.dim % 4 == 0, AIC_ERR_INVALID, "device association: incomplete bank launch");
+    epoch_attr();
+    EpochArgs a{};
+    a.mean = mean, a.cov = cov, a.gal_raw = gal_raw, a.gal_n = gal_n;
+    a.prm = prm, a.dets = dets, a.f0 = f0, a.k = k, a.nmax = 1;
+    a.scr = scr, a.out = out, a.lds_bytes = epoch_lds_bytes();
+    a.commit_ext = 1;
+    a.prof = g_phase.d;
+    a.cost_plane = prm.cap * std::max(nmax_call, 1);
+    a.bank = bk;
+    g_phase.launches += 1, g_phase.frames += k;
+    hipLaunchKernelGGL(trk_epoch_kernel<true>, dim3(streams), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
+    KCHECK();
+    if (dets.feat != nullptr && dets.feat_n != nullptr) {
+        hipLaunchKernelGGL(gallery_commit_kernel, dim3(std::max(8, 256 / streams), streams), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, 0, prm.dim,
+                           prm.gmax, gal_raw, gal_n, bk.gal_stride);
         KCHECK();
     }
 }

@@ -11,6 +11,7 @@
 //                           rows, matching cascade + rectangular LSAP (SciPy tie rules), lifecycle, Kalman update / initiate,
 //                           gallery bookkeeping, output rows.
 // The track table (what Tracker::tracks holds on the host path) lives in HBM between launches.
+// A bank of S streams (deepsort_bank.hpp) runs the same three kernels with one epoch-kernel block per stream: EpochBankArgs below.
 #pragma once
 #include <cstdint>
 
@@ -72,6 +73,31 @@ struct EpochScratch {
     float* cost;                    // 3 x [TRK_DEV_TMAX * TRK_DEV_NMAX] full matrices of the current frame (app, maha, iou)
     float* sub;                     // LSAP sub-matrix when it does not fit the LDS arena
     int32_t* appends;               // [TRK_DEV_DNMAX, 3] (slot, ring position, epoch row) gallery rows written at the end of the epoch; [3 * TRK_DEV_DNMAX] = their number
+};
+
+constexpr int TRK_APPENDS_INTS = 3 * TRK_DEV_DNMAX + 4;   // one appends list with its length behind it
+
+// ---- the bank form (deepsort_bank.cpp): S streams per launch, block s of trk_epoch_kernel = stream s, the stream as the second grid
+// dimension of trk_epoch_prep_kernel and gallery_commit_kernel.  What is launch-wide for the single tracker is per stream here:
+struct EpochStreamPlan {            // one stream's share of one epoch launch; device memory, uploaded with the call's staging
+    int32_t dn, dn_pad;             // detection rows of the stream's frames in the epoch; padded to 32 (pitch of the stream's SM / GRAM)
+    int32_t nmax;                   // most detections in one of those frames (>= 1)
+    int32_t has_sm;                 // the stream's SM / GRAM are built for this epoch (it has rows, and the call has features)
+    int32_t map0;                   // row_map + map0: the stream's map from epoch-local row to detection row, dn entries
+    int32_t pad[3];
+};
+
+struct EpochBankArgs {              // stream_k == NULL: the single tracker, nothing below is read
+    char* tbl;                      // DevTrkHdr | DevTrack[cap] | free[cap] per stream, tbl_stride bytes apart
+    size_t tbl_stride;
+    size_t mean_stride, cov_stride, gal_stride;          // floats between two streams' mean / cov / gal_raw and gal_n
+    size_t sm_stride, gram_stride, cost_stride, sub_stride;   // floats between two streams' slices of EpochScratch (appends: TRK_APPENDS_INTS)
+    const int32_t* stream_f0;       // [S] local frame i of stream s = row stream_f0[s] + i * frame_stride of EpochDets / EpochOut
+    const int32_t* stream_k;        // [S] frames of stream s in the call
+    int32_t frame_stride;
+    const EpochStreamPlan* plan;    // [S] of this epoch
+    const int32_t* row_map;
+    const int32_t* frame_e0;        // [frames] first epoch-local row of the frame in its stream's epoch, by the frame's row of EpochDets
 };
 
 }  // namespace aic

@@ -58,6 +58,7 @@ typedef struct aic_ocsort aic_ocsort;     /* OC-SORT state of one video stream  
 typedef struct aic_bytetrack_bank aic_bytetrack_bank; /* ByteTrack state of 1..256 streams    */
 typedef struct aic_ocsort_bank aic_ocsort_bank;       /* OC-SORT state of 1..256 streams      */
 typedef struct aic_botsort_bank aic_botsort_bank;     /* BoT-SORT state of 1..256 streams     */
+typedef struct aic_deepsort_bank aic_deepsort_bank;   /* DeepSORT state of 1..256 streams     */
 typedef struct aic_gmc_bank aic_gmc_bank;             /* camera-motion estimator of 1..256 streams */
 
 /* ------------------------------------------------------------------ library / device */
@@ -287,6 +288,38 @@ int aic_tracker_assoc_counters(aic_tracker* t, int64_t* n_unique, int64_t* n_lsa
 int aic_tracker_last_matches(aic_tracker* t, int32_t* track_id, int32_t* det, int cap, int32_t* n);
 int aic_tracker_last_costs(aic_tracker* t, float* app, float* maha, float* iou, int cap, int32_t* t_n,
                            int32_t* d_n);
+
+/* A bank of `streams` (1..256) DeepSORT streams on one device: every epoch launch of the device association runs one kernel block per
+ * stream (csrc/deepsort_bank.hpp, csrc/kernels_trk_dev.hip).  Each stream has its own track table, Kalman state, galleries and ids
+ * (from first_track_id) and computes exactly what an aic_tracker with "device_assoc" fed the same frames computes.  Device association
+ * only: AIC_ERR_INVALID (checked before the device) for streams outside 1..256, nn_budget <= 0, max_tracks > 512 (0 = 512) or a
+ * feature_dim that is no multiple of 4 in 0..1024 (0 = 512).  Resident memory per stream: 2 * max_tracks * nn_budget * feature_dim * 4
+ * bytes of galleries (210 MB at 512 x 100 x 512) + 340 * max_tracks bytes; an allocation that does not fit fails the create. */
+int aic_deepsort_bank_create(int device, const aic_tracker_params* p, int streams, aic_deepsort_bank** out);
+int aic_deepsort_bank_destroy(aic_deepsort_bank* b);
+/* "epoch_frames" (0..16, 0 = 16), "lsap_fast" (0/1), "wave_cascade" (0/1), for the whole bank: same results either way. */
+int aic_deepsort_bank_option(aic_deepsort_bank* b, const char* key, int value);
+/* frames_per_stream[streams] consecutive frames of every stream (0 = none this call), F frames in all, stream-major: counts[F] and the
+ * rows of all frames concatenated as aic_tracker_update_batch takes them (det_tlwh[sum,4], conf[sum], class id[sum], feat[sum,
+ * feature_dim] raw host embeddings for all rows of the call or NULL, valid[sum]: 0 = the row has no feature, NULL = all have one).  One
+ * staging upload, ceil(max frames / k) launches of `streams` blocks, one read-back, one sync.  n_out[F] (true counts), out6[F,cap_rows,6],
+ * out_conf[F,cap_rows] as aic_tracker_update_batch.  A frame with more than 512 detections rejects the whole call before anything is
+ * staged (AIC_ERR_CAPACITY).  A stream that exhausts max_tracks stops alone: status[streams] (may be NULL) gets 0 or the code that
+ * stopped the stream, the frames before the failing one are delivered, the other streams complete, and later calls deliver nothing
+ * for it until aic_deepsort_bank_reset.  With status NULL the call returns the first stopped stream's code after delivering the rest. */
+int aic_deepsort_bank_update(aic_deepsort_bank* b, const int32_t* frames_per_stream, const int32_t* counts, const float* det_tlwh,
+                             const float* conf, const int32_t* cls, const float* feat, const int32_t* valid, int cap_rows,
+                             int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status);
+/* The stream as after create: no tracks, empty galleries, ids from first_track_id again, a stop cleared. */
+int aic_deepsort_bank_reset(aic_deepsort_bank* b, int stream);
+/* The arrays of aic_tracker_export for one stream (the first `cap` tracks; *n_tracks = the true count) and of
+ * aic_tracker_export_gallery; AIC_ERR_INVALID for a stopped stream. */
+int aic_deepsort_bank_export(aic_deepsort_bank* b, int stream, int cap, int32_t* track_id, int32_t* state, int32_t* hits,
+                             int32_t* age, int32_t* time_since_update, int32_t* cls, float* conf, int32_t* gallery_len,
+                             float* mean, float* cov, int32_t* n_tracks);
+int aic_deepsort_bank_export_gallery(aic_deepsort_bank* b, int stream, int index, float* out, int cap_rows);
+/* As aic_tracker_assoc_counters for one stream, since create or the stream's last reset. */
+int aic_deepsort_bank_counters(aic_deepsort_bank* b, int stream, int64_t* n_unique, int64_t* n_lsap);
 
 /* ------------------------------------------------------------------ ByteTrack
  * BYTETracker.update() of the ByteTrack authors (yolox/tracker/byte_tracker.py, matching.py) on the device, k frames per launch

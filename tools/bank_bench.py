@@ -5,6 +5,7 @@
     python tools/bank_bench.py pipeline [--streams 1,8,32] [--reserve 1,2,4,8,16] [--ring 512] [--batch 256]
     python tools/bank_bench.py botsort  [--streams 1,8,32,128,256] [--ticks 256]           # shorthand: tracker --kinds botsort
     python tools/bank_bench.py botsort-pipeline [--streams 1,8,32] [--ring 512] [--batch 256] [--steps 5] [--gmc 0]
+    python tools/bank_bench.py deepsort [--streams 1,8,32] [--ticks 256]                   # shorthand: tracker --kinds deepsort
 
 tracker:  S synthetic 30-person streams for `ticks` ticks, fed one tick per call and 16 ticks per call, to a bank of S streams
           (one launch of S blocks per epoch) and to S single trackers in a loop (S launches and syncs per epoch: what a caller had
@@ -13,6 +14,8 @@ pipeline: the ByteTrack pipeline on the trained detector's own detections, ring 
           epoch blocks' CU reserve ("tracker_cus") swept.  Prints frames/s.
 botsort (a kind of `tracker`): every detection carries a 512-float feature (synthetic.identity_features, feature_dim 512), so a call
           uploads 2 KB per detection on top.
+deepsort (a kind of `tracker`): the DeepSORT bank against S single device trackers (TrackerCore.update_batch) in a loop; features as for
+          botsort, max_tracks 64 and nn_budget 100 so that 32 streams stay near 1 GB of galleries.
 botsort-pipeline: the BoT-SORT bank pipeline (TrackingPipeline.botsort_bank) on the trained detector's own detections with the seeded
           ReID engine, ring resident in HBM, against S single BoT-SORT pipelines, each created, warmed, run `steps` times on one
           camera's ring / S frames and closed before the next (the time of step i is the sum of the S pipelines' i-th runs).
@@ -53,12 +56,42 @@ def stream_frames_with_features(seed, ticks):
     return out
 
 
+def deepsort_classes():
+    """(bank, single) with the interface step_tracker drives, over DeepSORTBank and TrackerCore.update_batch; detections go in as tlwh."""
+    import numpy as np
+    Bank, TC = pkg("deepsort_bank").DeepSORTBank, pkg("core.tracker_core").TrackerCore
+
+    def tlwh(frames):
+        out = []
+        for b, c, k, f in frames:
+            t = b.copy()
+            t[:, 2:] -= t[:, :2]
+            out.append((t, c, k, f))
+        return out
+
+    class B(Bank):
+        def __init__(self, S):
+            super().__init__(S, max_tracks=64, nn_budget=100)
+
+        def update_arrays(self, per_stream):
+            return super().update_arrays([tlwh(fr) for fr in per_stream])
+
+    class One(TC):
+        def __init__(self):
+            super().__init__(max_tracks=64, nn_budget=100)
+
+        def update_batch_arrays(self, frames):
+            return self.update_batch(tlwh(frames), cap_rows=64)
+
+    return B, One
+
+
 def step_tracker(kind, S, ticks):
-    make = stream_frames_with_features if kind == "botsort" else stream_frames
+    make = stream_frames_with_features if kind in ("botsort", "deepsort") else stream_frames
     base = [make(seed, ticks) for seed in range(min(S, 8))]                # 8 distinct scenes, reused round-robin
     dets = [base[s % len(base)] for s in range(S)]
-    mod = pkg(kind)
-    Bank, One = {"bytetrack": lambda: (mod.BYTETrackerBank, mod.BYTETracker), "ocsort": lambda: (mod.OCSortBank, mod.OCSort),
+    mod = None if kind == "deepsort" else pkg(kind)
+    Bank, One = {"deepsort": deepsort_classes, "bytetrack": lambda: (mod.BYTETrackerBank, mod.BYTETracker), "ocsort": lambda: (mod.OCSortBank, mod.OCSort),
                  "botsort": lambda: (mod.BoTSORTBank, mod.BoTSORT)}[kind]()
     out = dict(kind=kind, streams=S, ticks=ticks)
     for per_call in (1, 16):
@@ -142,7 +175,7 @@ def step_botsort_pipeline(S, ring, batch, steps, gmc):
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline"))
+    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "deepsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline"))
     p.add_argument("--gmc", type=int, default=0)
     p.add_argument("--kinds", default="bytetrack,ocsort")
     p.add_argument("--streams", default=None)
@@ -160,8 +193,8 @@ def main():
     if a.mode == "step-botsort-pipeline":
         return step_botsort_pipeline(int(a.streams), a.ring, a.batch, a.steps, a.gmc)
     me = [sys.executable, os.path.abspath(__file__)]
-    if a.mode == "botsort":
-        a.mode, a.kinds = "tracker", "botsort"
+    if a.mode in ("botsort", "deepsort"):
+        a.mode, a.kinds, a.streams = "tracker", a.mode, a.streams or ("1,8,32" if a.mode == "deepsort" else None)
     if a.mode == "botsort-pipeline":
         jobs = [me + ["step-botsort-pipeline", "--streams", s, "--ring", str(a.ring), "--batch", str(a.batch), "--steps", str(a.steps),
                       "--gmc", str(a.gmc)] for s in (a.streams or "1,8,32").split(",")]
