@@ -215,6 +215,19 @@ _SIGS = {
     "aic_deepsort_bank_export": (_I, [_P, _I, _I] + [_P] * 11),
     "aic_deepsort_bank_export_gallery": (_I, [_P, _I, _I, _P, _I]),
     "aic_deepsort_bank_counters": (_I, [_P, _I, _P, _P]),
+    "aic_gid_forget_rank": (_I, [_P, _I]),
+    "aic_xcam_create": (_I, [_I, _I, _I, _I, _D, _P]),
+    "aic_xcam_destroy": (_I, [_P]),
+    "aic_xcam_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_xcam_link_deepsort_bank": (_I, [_P, _P, _P]),
+    "aic_xcam_link_botsort_bank": (_I, [_P, _P, _P]),
+    "aic_xcam_link_shards": (_I, [_P, _P, _P, _I, _P]),
+    "aic_xcam_tables": (_I, [_P, _P, _P, _P]),
+    "aic_xcam_shards": (_I, [_P, _P]),
+    "aic_xcam_global_ids": (_I, [_P, _I, _P, _I, _P]),
+    "aic_xcam_size": (_I, [_P, _P, _P, _P]),
+    "aic_xcam_forget_stream": (_I, [_P, _I]),
+    "aic_pipeline_link_cameras": (_I, [_P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

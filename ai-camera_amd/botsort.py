@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib as L
 from . import config
 from .bytetrack import TrackerBank
+from .xcam import CameraLinks
 
 
 def botsort_params(track_high_thresh=0.6, track_low_thresh=0.1, new_track_thresh=0.7, match_thresh=0.8, proximity_thresh=0.5,
@@ -143,10 +144,12 @@ class BoTSORT:
         return out
 
 
-class BoTSORTBank(TrackerBank):
+class BoTSORTBank(CameraLinks, TrackerBank):
     """BoTSORTBank(streams, device=0, **BoTSORT's parameters): the BoT-SORT state of `streams` cameras on one device, one kernel block
     per stream and launch.  Every stream has its own table, smoothed features and ids and computes exactly what a BoTSORT fed the same
-    frames computes; a stream that meets a capacity error stops alone, and reset(stream) starts it afresh."""
+    frames computes; a stream that meets a capacity error stops alone, and reset(stream) starts it afresh.  link_cameras() links the
+    identities of the cameras' activated tracks by their smoothed features on the device (xcam.py; cosine distance within
+    config.DEEPSORT_MAX_DIST unless a CrossCamera with another threshold is handed over); global_ids(stream, track_ids) reads them."""
     _abi = "aic_botsort_bank"
 
     def __init__(self, streams, device=0, **params):

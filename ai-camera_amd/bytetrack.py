@@ -122,6 +122,7 @@ class TrackerBank:
     def _create(self, streams, device):
         self.streams = int(streams)
         self.failed = {}                                         # stream -> message
+        self._device = device
         self._h = C.c_void_p()
         L.call(self._abi + "_create", config.resolve_device(device), C.byref(self.params), self.streams, C.byref(self._h))
 

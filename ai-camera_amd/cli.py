@@ -56,12 +56,17 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help="bytetrack / ocsort: no ReID model, the tracker's association on the device; botsort: IoU + ReID fusion on the device")
     p.add_argument("--gmc", type=int, default=0, choices=(0, 2, 4),
                    help="botsort only: estimate the camera motion on the device at this downscale and warp the predicted tracks (0 = off)")
+    p.add_argument("--link_cameras", action="store_true",
+                   help="--inputs with --tracker botsort only: link the cameras' identities on the device after every run call; every JSON line "
+                        "gains \"global_ids\" parallel to \"tracks\" (-1 = not linked yet) and the overlay label shows the global id")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
     args = p.parse_args(argv)
     if args.gmc and args.tracker != "botsort":
         p.error("--gmc needs --tracker botsort")
+    if args.link_cameras and (args.inputs is None or args.tracker != "botsort"):
+        p.error("--link_cameras needs --inputs a,b,c --tracker botsort")
     if args.inputs is not None:
         if args.input is not None:
             p.error("--inputs and --input are mutually exclusive")
@@ -239,16 +244,22 @@ def main_streams(args, cv2):
             stem = out_dir / f"{name}_tracked_{stamp}_s{k}"
             outs[k] = open(str(stem) + ".jsonl", "w")
             writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None)
+    pipe.link_after_run = bool(args.link_cameras)
     ticks = (f for tick in zip(*(src[1] for src in sources)) for f in tick)       # the shortest source ends the run
     n, t0 = 0, time.time()
     try:
         for frame, tracks in pipe.stream(ticks):
             k, idx = n % S, n // S
             n += 1
+            gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if writers[k] is not None:
-                writers[k].write(visualization.draw_frame(frame.copy(), tracks, [label, f"Input: {sources[k][0]} (stream {k})"], dev))
+                shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
+                writers[k].write(visualization.draw_frame(frame.copy(), shown, [label, f"Input: {sources[k][0]} (stream {k})"], dev))
             if outs[k]:
-                outs[k].write(json.dumps({"frame": idx, "tracks": tracks}) + "\n")
+                line = {"frame": idx, "tracks": tracks}
+                if gids is not None:
+                    line["global_ids"] = gids
+                outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
     finally:

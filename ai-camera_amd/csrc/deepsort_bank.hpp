@@ -3,7 +3,8 @@
 // of trk_epoch_prep_kernel and gallery_commit_kernel).  A stream computes exactly what an aic_tracker with "device_assoc" fed the same
 // frames computes -- it is that tracker's code in its arithmetic order -- and a stream that exhausts max_tracks stops alone.
 //
-// Device association only: nn_budget > 0, max_tracks <= 512, feature_dim % 4 == 0; there is no host fallback and no gallery exchange.
+// Device association only: nn_budget > 0, max_tracks <= 512, feature_dim % 4 == 0; there is no host fallback and no gallery exchange
+// between ranks (the cameras of one bank are linked by xcam.hpp).
 //
 // Memory per stream, resident:  table   32 + 52 * max_tracks bytes
 //                               Kalman  (8 + 64) * 4 * max_tracks bytes

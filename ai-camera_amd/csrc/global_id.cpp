@@ -19,33 +19,42 @@
 #include <vector>
 
 #include "assoc_host.hpp"
+#include "global_id.hpp"
 
 namespace aic {
 
-struct GidTable {
-    int world;
-    std::map<uint64_t, uint64_t> first;     // (rank << 32 | track id) -> global id given at its first sighting
-    std::map<uint64_t, uint64_t> parent;    // global id -> smaller global id it was merged into
-    long links = 0, updates = 0;
-    static uint64_t key(int rank, int id) { return ((uint64_t)(uint32_t)rank << 32) | (uint32_t)id; }
-    uint64_t find(uint64_t g) {
-        uint64_t r = g;
-        for (auto it = parent.find(r); it != parent.end(); it = parent.find(r)) r = it->second;
-        while (g != r) {                      // path compression
-            auto it = parent.find(g);
-            const uint64_t nx = it->second;
-            it->second = r;
-            g = nx;
-        }
-        return r;
+void GidTable::forget_rank(int rank) {
+    AIC_REQUIRE(rank >= 0 && rank < world, AIC_ERR_INVALID, "rank outside the table's world");
+    const uint32_t g = generation(rank);
+    AIC_REQUIRE(g < kGenMax, AIC_ERR_CAPACITY, "rank forgotten too often (2^19 generations)");
+    gen[rank] = g + 1;
+}
+
+int GidTable::update(int world_, int t_max, const int32_t* track_id, const int32_t* near_row, const float* near_dist, double max_cosine_distance) {
+    AIC_REQUIRE(world_ == world, AIC_ERR_INVALID, "world size differs from the table's");
+    const int n = world * t_max;
+    const float thr = (float)max_cosine_distance;
+    for (int i = 0; i < n; ++i) {
+        if (track_id[i] < 0) continue;
+        const uint64_t k = key(i / t_max, track_id[i]);
+        first.emplace(k, k);                   // first sighting: its own (rank, track id)
     }
-    bool unite(uint64_t a, uint64_t b) {
-        a = find(a), b = find(b);
-        if (a == b) return false;
-        if (a < b) parent[b] = a; else parent[a] = b;
-        return true;
+    int n_new = 0;
+    for (int i = 0; i < n; ++i) {              // mutual nearest neighbours within the threshold, ascending row order
+        const int j = near_row[i];
+        if (track_id[i] < 0 || j <= i || j >= n || track_id[j] < 0) continue;
+        if (near_row[j] != i || !(near_dist[i] <= thr)) continue;
+        AIC_REQUIRE(i / t_max != j / t_max, AIC_ERR_INVALID, "nearest-neighbour table links two tracks of one camera");
+        if (unite(first[key(i / t_max, track_id[i])], first[key(j / t_max, track_id[j])])) ++n_new;
     }
-};
+    links += n_new, updates += 1;
+    return n_new;
+}
+
+int64_t GidTable::lookup(int rank, int track_id) {
+    auto it = first.find(key(rank, track_id));
+    return it == first.end() ? -1 : (int64_t)find(it->second);
+}
 
 }  // namespace aic
 
@@ -71,24 +80,7 @@ int aic_gid_update(aic_gid* g, int world, int t_max, const int32_t* track_id, co
                    double max_cosine_distance, int32_t* n_links) {
     return guarded([&] {
         AIC_REQUIRE(g && track_id && near_row && near_dist && t_max > 0, AIC_ERR_INVALID, "bad argument");
-        AIC_REQUIRE(world == g->t.world, AIC_ERR_INVALID, "world size differs from the table's");
-        GidTable& t = g->t;
-        const int n = world * t_max;
-        const float thr = (float)max_cosine_distance;
-        for (int i = 0; i < n; ++i) {
-            if (track_id[i] < 0) continue;
-            const uint64_t k = GidTable::key(i / t_max, track_id[i]);
-            t.first.emplace(k, k);             // first sighting: its own (rank, track id)
-        }
-        int links = 0;
-        for (int i = 0; i < n; ++i) {          // mutual nearest neighbours within the threshold, ascending row order
-            const int j = near_row[i];
-            if (track_id[i] < 0 || j <= i || j >= n || track_id[j] < 0) continue;
-            if (near_row[j] != i || !(near_dist[i] <= thr)) continue;
-            AIC_REQUIRE(i / t_max != j / t_max, AIC_ERR_INVALID, "nearest-neighbour table links two tracks of one camera");
-            if (t.unite(t.first[GidTable::key(i / t_max, track_id[i])], t.first[GidTable::key(j / t_max, track_id[j])])) ++links;
-        }
-        t.links += links, t.updates += 1;
+        const int links = g->t.update(world, t_max, track_id, near_row, near_dist, max_cosine_distance);
         if (n_links) *n_links = links;
     });
 }
@@ -96,8 +88,14 @@ int aic_gid_update(aic_gid* g, int world, int t_max, const int32_t* track_id, co
 int aic_gid_lookup(aic_gid* g, int rank, int track_id, int64_t* global_id) {
     return guarded([&] {
         AIC_REQUIRE(g && global_id, AIC_ERR_INVALID, "NULL argument");
-        auto it = g->t.first.find(GidTable::key(rank, track_id));
-        *global_id = it == g->t.first.end() ? -1 : (int64_t)g->t.find(it->second);
+        *global_id = g->t.lookup(rank, track_id);
+    });
+}
+
+int aic_gid_forget_rank(aic_gid* g, int rank) {
+    return guarded([&] {
+        AIC_REQUIRE(g, AIC_ERR_INVALID, "NULL argument");
+        g->t.forget_rank(rank);
     });
 }
 

@@ -149,6 +149,20 @@ void launch_trk_epoch_bank(const EpochBankArgs& bk, int streams, float* mean, fl
 void launch_gallery_shard(const DevTrkHdr* hdr, const DevTrack* trk, const float* gal_n, int gmax, int dim, float* out, int t_max, hipStream_t s);
 // configs[4] annotation pass: gathered [world, t_max, 2 + dim] -> per row (all ranks) track id or -1, nearest valid row of another rank or -1, its cosine distance
 void launch_gallery_nearest(const float* gathered, int world, int t_max, int dim, int* ids, int* near_row, float* near_dist, hipStream_t s);
+// cross-camera links inside a bank (kernels_xcam.hip, xcam.hpp): shards fp32 [streams, t_max, 2 + dim] in the layout of launch_gallery_shard,
+// n_valid[streams] = the valid prefix of every stream's slice, flags[streams] (bit 0: valid rows not a prefix; bit 1: a track id >= 2^24)
+constexpr int BANK_STREAMS_MAX_XCAM = 256;  // streams of one pass (= the nearest kernel's block: one thread per stream in its prefix sum)
+constexpr int XCAM_KC = 32;                 // K-chunk of the nearest kernel's LDS tiles
+constexpr int XCAM_SMALL_ROWS = 4096;       // streams * t_max below this: 32 x 32 tiles (2 x 2 per thread), else 64 x 64 (4 x 4 per thread)
+void launch_xcam_pack_deepsort(const char* tbl, size_t tbl_stride, const float* gal_n, size_t gal_stride, int gmax, int dim, int streams, int t_max,
+                               float* shards, int* n_valid, int* flags, hipStream_t s);
+void launch_xcam_pack_botsort(char* bank, size_t table_stride, float* smooth, size_t smooth_stride, int cap, int dim, int streams, int t_max,
+                              float* shards, int* n_valid, int* flags, hipStream_t s);
+void launch_xcam_count(const float* shards, int streams, int t_max, int dim, int* n_valid, int* flags, hipStream_t s);
+int xcam_tile_rows(int streams, int t_max, int tile);   // tile: 32 / 64 = that tile, anything else = by size
+// the table of launch_gallery_nearest over [streams, t_max] rows (dim % 4 == 0, streams <= 256); best = [streams * t_max] scratch keys
+void launch_xcam_nearest(const float* shards, const int* n_valid, int streams, int t_max, int dim, int tile, unsigned long long* best, int* ids,
+                         int* near_row, float* near_dist, hipStream_t s);
 void launch_trk_cascade_test(const TrkDevParams& prm, const EpochScratch& scr, int T, int n, const int* state, const int* tsu,
                              int* out_mdet, int* out_err, int stage1_only, hipStream_t s);
 

@@ -18,6 +18,7 @@
 #include "ocsort_host.hpp"
 #include "botsort_host.hpp"
 #include "gmc.hpp"
+#include "xcam.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -1209,6 +1210,16 @@ int aic_pipeline_reset_stream(aic_pipeline* p, int stream) {
                     "reset_stream applies to ByteTrack and OC-SORT pipelines and to BoT-SORT banks (aic_pipeline_create_botsort_bank) only");
         p->p.bt->reset_stream(stream);
         if (p->p.gmc) p->p.gmc->reset(stream);       // the camera's next frame is its first
+    });
+}
+
+int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links) {
+    return guarded([&] {
+        AIC_REQUIRE(p && x, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(p->p.bt && p->p.bs && p->p.bs_bank, AIC_ERR_INVALID,
+                    "link_cameras applies to BoT-SORT bank pipelines (aic_pipeline_create_botsort_bank) only");
+        const int l = x->x.link(*static_cast<BotSortTracker*>(p->p.bt.get()));   // on the tracker stream, behind the last run call's epochs
+        if (n_links) *n_links = l;
     });
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib as L
 from . import config
 from .bytetrack import TrackerBank
+from .xcam import CameraLinks
 
 
 def deepsort_bank_params(max_cosine_distance=0.2, nn_budget=100, max_iou_distance=0.7, max_age=70, n_init=3, max_tracks=512,
@@ -23,10 +24,14 @@ def deepsort_bank_params(max_cosine_distance=0.2, nn_budget=100, max_iou_distanc
                            int(n_init), int(max_tracks), int(feature_dim), int(first_track_id))
 
 
-class DeepSORTBank(TrackerBank):
+class DeepSORTBank(CameraLinks, TrackerBank):
     """DeepSORTBank(streams, device=0, **deepsort_bank_params): the DeepSORT state of `streams` cameras.  A stream that exhausts
-    max_tracks stops alone (`failed`), the others go on, and reset(stream) starts it afresh."""
+    max_tracks stops alone (`failed`), the others go on, and reset(stream) starts it afresh.  link_cameras() links the identities of
+    the cameras' confirmed tracks on the device (xcam.py) within max_cosine_distance; global_ids(stream, track_ids) reads them."""
     _abi = "aic_deepsort_bank"
+
+    def _link_threshold(self):
+        return self.params.max_cosine_distance
 
     def __init__(self, streams, device=0, **params):
         self.params = deepsort_bank_params(**params)

@@ -35,6 +35,7 @@ class TrackingPipeline:
         being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams.
         BoT-SORT for S cameras: TrackingPipeline.botsort_bank(...), which passes the camera count as _cameras."""
         self.streams = int(_cameras) or int(streams)
+        self.cameras, self._device, self.xcam, self.link_after_run = int(_cameras), device, None, False
         if _cameras and tracker != "botsort":
             raise ValueError("a camera count needs tracker='botsort' (TrackingPipeline.botsort_bank)")
         if int(streams) != 1 and tracker not in ("bytetrack", "ocsort"):
@@ -143,8 +144,30 @@ class TrackingPipeline:
         return cls(yolo_engine, reid_engine, frame_hw, tracker="botsort", gmc=gmc, _cameras=cameras, **kw)
 
     def reset_stream(self, s):
-        """streams=S and botsort_bank pipelines, between run calls: stream s as after creation (a camera reconnecting)."""
+        """streams=S and botsort_bank pipelines, between run calls: stream s as after creation (a camera reconnecting).  An attached
+        CrossCamera forgets the stream's identities with it."""
         L.call("aic_pipeline_reset_stream", self._h, int(s))
+        if self.xcam is not None:
+            self.xcam.forget_stream(s)
+
+    def link_cameras(self, xcam=None):
+        """botsort_bank pipelines, between run calls: one cross-camera pass over the bank's activated tracks (xcam.py).  The first call
+        creates and keeps a CrossCamera unless one is handed over; returns the identities merged by this call."""
+        if self.tracker_kind != "botsort" or not self.cameras:
+            raise ValueError("link_cameras needs a TrackingPipeline.botsort_bank pipeline")
+        from .xcam import CrossCamera
+        if xcam is not None:
+            self.xcam = xcam
+        if self.xcam is None:
+            p = self.botsort_params
+            self.xcam = CrossCamera(self.streams, p.max_tracks or 512, p.feature_dim or 512, device=self._device)
+        return self.xcam.link_pipeline(self)
+
+    def global_ids(self, stream, track_ids):
+        """int64 global ids of the stream's local track ids after link_cameras(); -1 = not seen in a pass yet."""
+        if self.xcam is None:
+            raise RuntimeError("link_cameras() has not run yet")
+        return self.xcam.global_ids(stream, track_ids)
 
     def close(self):
         for b in getattr(self, "_staging", []):
@@ -305,6 +328,8 @@ class TrackingPipeline:
                 break
             if n:
                 tracks = self.run_from_host(self._staging[b][:n])
+                if self.link_after_run:                  # the CLI's --link_cameras: identities follow every run call
+                    self.link_cameras()
                 for i in range(n):
                     yield self._staging[b][i], tracks[i]
             free.put(b)

@@ -658,6 +658,49 @@ int aic_gid_update(aic_gid* g, int world, int t_max, const int32_t* track_id, co
                    double max_cosine_distance, int32_t* n_links);
 int aic_gid_lookup(aic_gid* g, int rank, int track_id, int64_t* global_id);
 int aic_gid_size(aic_gid* g, int64_t* n_tracks, int64_t* n_identities, int64_t* n_links);
+/* The rank's local track ids start over (a camera reset): its (rank, track id) keys of now must not be met again.  Every rank carries a
+ * generation in the key's free upper bits (generation << 44 | rank << 32 | track id; rank takes 12 bits, generation 0 keys are the keys
+ * above): sightings from here on are filed under the next generation and lookup() resolves the current generation only (-1 until the
+ * recycled id is seen again).  Identities that other ranks adopted from the forgotten one keep their number.  The keys of earlier
+ * generations stay in the table (ids merged into them must still resolve), so aic_gid_size / aic_xcam_size count forgotten tracks too
+ * and the table grows by a camera's tracks with every reconnect, as it grows with every new track id on the rank path. */
+int aic_gid_forget_rank(aic_gid* g, int rank);
+
+/* ------------------------------------------------------------------ cross-camera identities inside one bank
+ * The same answer for the cameras of ONE process: is this track of stream 3 the one stream 11 sees?  An aic_xcam holds the global-id
+ * table above with world = streams and runs, per link call, one device pass on the tracker stream between the bank's update calls:
+ * every stream's shard (valid, track id, unit embedding; fp32 [streams, t_max, 2 + dim]; the valid rows of a stream are a prefix of its
+ * slice) is packed on the device, every live row's nearest row of another stream is found by a tiled all-pairs kernel whose cost follows
+ * the live rows (same arithmetic, same bits as aic_gallery_annotate), the tables are read back once and the policy is applied on the
+ * host.  The bank's own association never reads the result.
+ * create: streams 1..256, t_max 1..512 (rows per stream: the first t_max eligible tracks in list order), dim a multiple of 4 in 4..1024.
+ * link_deepsort_bank: rows = confirmed tracks with a gallery, the newest gallery entry's unit row.  link_botsort_bank: activated tracks
+ * of the tracked list that have a feature, the smoothed unit feature.  AIC_ERR_INVALID before the device is touched when the bank's
+ * stream count or feature dimension differs from the object's or when a stream is stopped by an error (reset it first);
+ * AIC_ERR_CAPACITY when a packed track id is >= 2^24 (ids travel as fp32).  *n_links = identities merged by this call.
+ * link_shards: the same pass on caller-made shards in host or device memory (mem: AIC_HOST / AIC_DEVICE; device memory 8-byte aligned).
+ * The valid prefix of every stream is counted from the valid column on the device, and shards whose valid rows are not a prefix are
+ * rejected with AIC_ERR_INVALID.  n_valid[streams] (host; may be NULL) is the caller's statement of those counts: a value outside
+ * 0..t_max, or one that differs from the valid column, is AIC_ERR_INVALID and nothing is linked (host memory: before the device is
+ * touched; device memory: after the pass's read-back, before the policy).
+ * tables: the last pass's arrays over all streams * t_max rows, as aic_gallery_annotate's (any may be NULL).  shards: its shard array.
+ * global_ids: -1 = never seen.  size: as aic_gid_size.  forget_stream: aic_gid_forget_rank for a camera that was reset.
+ * option "tile": 32 / 64 = rows per tile of the nearest kernel, 0 (default) = by size; same results either way. */
+typedef struct aic_xcam aic_xcam;
+int aic_xcam_create(int device, int streams, int t_max, int dim, double max_cosine_distance, aic_xcam** out);
+int aic_xcam_destroy(aic_xcam* x);
+int aic_xcam_option(aic_xcam* x, const char* key, int value);
+int aic_xcam_link_deepsort_bank(aic_xcam* x, aic_deepsort_bank* bank, int32_t* n_links);
+int aic_xcam_link_botsort_bank(aic_xcam* x, aic_botsort_bank* bank, int32_t* n_links);
+int aic_xcam_link_shards(aic_xcam* x, const float* shards, const int32_t* n_valid, int mem, int32_t* n_links);
+int aic_xcam_tables(aic_xcam* x, int32_t* track_id, int32_t* near_row, float* near_dist);
+int aic_xcam_shards(aic_xcam* x, float* out);
+int aic_xcam_global_ids(aic_xcam* x, int stream, const int32_t* track_ids, int n, int64_t* global_ids);
+int aic_xcam_size(aic_xcam* x, int64_t* n_tracks, int64_t* n_identities, int64_t* n_links);
+int aic_xcam_forget_stream(aic_xcam* x, int stream);
+/* The link pass for the BoT-SORT bank of a pipeline from aic_pipeline_create_botsort_bank, between run calls; AIC_ERR_INVALID on any
+ * other pipeline. */
+int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links);
 int aic_host_register(void* ptr, size_t bytes);   /* hipHostRegister: page-lock caller memory */
 int aic_host_unregister(void* ptr);
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out);

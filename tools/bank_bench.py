@@ -6,6 +6,7 @@
     python tools/bank_bench.py botsort  [--streams 1,8,32,128,256] [--ticks 256]           # shorthand: tracker --kinds botsort
     python tools/bank_bench.py botsort-pipeline [--streams 1,8,32] [--ring 512] [--batch 256] [--steps 5] [--gmc 0]
     python tools/bank_bench.py deepsort [--streams 1,8,32] [--ticks 256]                   # shorthand: tracker --kinds deepsort
+    python tools/bank_bench.py xcam     [--streams 8,32,256] [--valid 128,30] [--steps 7]  # cross-camera links of a bank
 
 tracker:  S synthetic 30-person streams for `ticks` ticks, fed one tick per call and 16 ticks per call, to a bank of S streams
           (one launch of S blocks per epoch) and to S single trackers in a loop (S launches and syncs per epoch: what a caller had
@@ -19,6 +20,10 @@ deepsort (a kind of `tracker`): the DeepSORT bank against S single device tracke
 botsort-pipeline: the BoT-SORT bank pipeline (TrackingPipeline.botsort_bank) on the trained detector's own detections with the seeded
           ReID engine, ring resident in HBM, against S single BoT-SORT pipelines, each created, warmed, run `steps` times on one
           camera's ring / S frames and closed before the next (the time of step i is the sum of the S pipelines' i-th runs).
+xcam:     xcam_nearest_kernel (aic_xcam_link_shards) against gallery_nearest_kernel (aic_gallery_annotate) on the same device-resident shards,
+          t_max 128, dim 512, `valid` of the 128 rows of every stream valid: kernel time from the library's HIP-event brackets (class
+          "tracker": memset + nearest + finalize on one side, the one kernel on the other), two warm-up passes, `steps` timed passes in
+          alternating order, outputs compared once per shape.  Then a whole link_cameras() call of a 32-camera DeepSORT bank, wall clock.
 Every configuration is a child process of its own under `timeout`, and the first one that fails ends the run.
 """
 from __future__ import annotations
@@ -173,9 +178,76 @@ def step_botsort_pipeline(S, ring, batch, steps, gmc):
                           singles_fps_max=ring / min(t1))), flush=True)
 
 
+def step_xcam(S, valid, steps, t_max=128, dim=512):
+    import ctypes as C
+    import numpy as np
+    import torch                                                            # before libaicam.so: one HIP runtime in the process
+    L = pkg("_lib")
+    rng = np.random.default_rng(S)
+    g = np.zeros((S, t_max, 2 + dim), np.float32)
+    e = rng.standard_normal((S, valid, dim)).astype(np.float32)
+    g[:, :valid, 0], g[:, :valid, 1], g[:, :valid, 2:] = 1.0, np.arange(1, valid + 1), e / np.linalg.norm(e, axis=2, keepdims=True)
+    gd = torch.from_numpy(g).cuda()
+    n = S * t_max
+    nv = np.full(S, valid, np.int32)
+    xc = pkg("xcam").CrossCamera(S, t_max, dim, 0.2)
+    old = (np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32))
+
+    def run_new():
+        xc.link_shards(gd, n_valid=nv)
+
+    def run_old():
+        L.call("aic_gallery_annotate", 0, None, C.c_void_p(gd.data_ptr()), S, 0, t_max, dim, 0.2, L.ptr(old[0]), L.ptr(old[1]), L.ptr(old[2]), None)
+
+    def timed(fn):
+        L.call("aic_prof_reset", 0)
+        fn()
+        return L.prof_read(0)["tracker"]["ms"]
+
+    L.call("aic_prof_enable", 0, 1 << 6)
+    for _ in range(2):
+        run_new(), run_old()
+    same = all(np.array_equal(a, b) for a, b in zip(xc.tables(), old))
+    t_new, t_old = [], []
+    for i in range(steps):                                                  # alternating order
+        for which in ((0, 1) if i % 2 == 0 else (1, 0)):
+            (t_new if which == 0 else t_old).append(timed(run_new if which == 0 else run_old))
+    L.call("aic_prof_enable", 0, 0)
+    live = S * valid
+    pairs = float(live) * live - float(S) * valid * valid                   # ordered pairs of different streams
+    cus, ghz = torch.cuda.get_device_properties(0).multi_processor_count, 2.4   # the device's CUs; its nominal clock (the sustained one is not read)
+    bound_ms = 1e3 * pairs * dim * 2 / (cus * 4 * 16 * 2 * ghz * 1e9)       # one multiply + one add per product, packed fp32 (2 per lane and clock)
+    stat = lambda t: dict(median=float(np.median(t)), min=min(t), max=max(t))   # noqa: E731
+    print(json.dumps(dict(streams=S, t_max=t_max, dim=dim, valid=valid, identical=bool(same), xcam_ms=stat(t_new),
+                          rank_kernel_ms=stat(t_old), valu_bound_ms=bound_ms, bound_cus=cus, bound_ghz=ghz)), flush=True)
+    xc.close()
+    return 0 if same else 1
+
+
+def step_xcam_link(S, steps):
+    """Wall clock of DeepSORTBank.link_cameras(): pack + nearest + read-back + sync + policy, 30 persons per camera, max_tracks 64, dim 512."""
+    import numpy as np
+    Bank, _ = deepsort_classes()
+    base = [stream_frames_with_features(seed, 6) for seed in range(min(S, 8))]
+    bk = Bank(S)
+    bk.update_arrays([base[s % len(base)] for s in range(S)])
+    links = bk.link_cameras()                                               # warm-up: allocations, module load
+    rows = int((bk.xcam.tables()[0] >= 0).sum())
+    ts = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        bk.link_cameras()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    print(json.dumps(dict(link_cameras_streams=S, t_max=bk.xcam.t_max, live_rows=rows, first_call_links=links, ms_median=float(np.median(ts)),
+                          ms_min=min(ts), ms_max=max(ts))), flush=True)
+    bk.xcam.close(), bk.close()
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "deepsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline"))
+    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "deepsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline", "xcam", "step-xcam",
+                                         "step-xcam-link"))
+    p.add_argument("--valid", default="128,30")
     p.add_argument("--gmc", type=int, default=0)
     p.add_argument("--kinds", default="bytetrack,ocsort")
     p.add_argument("--streams", default=None)
@@ -192,10 +264,17 @@ def main():
         return step_pipeline(int(a.streams), int(a.reserve), a.ring, a.batch, a.steps)
     if a.mode == "step-botsort-pipeline":
         return step_botsort_pipeline(int(a.streams), a.ring, a.batch, a.steps, a.gmc)
+    if a.mode == "step-xcam":
+        return step_xcam(int(a.streams), int(a.valid), a.steps)
+    if a.mode == "step-xcam-link":
+        return step_xcam_link(int(a.streams), a.steps)
     me = [sys.executable, os.path.abspath(__file__)]
     if a.mode in ("botsort", "deepsort"):
         a.mode, a.kinds, a.streams = "tracker", a.mode, a.streams or ("1,8,32" if a.mode == "deepsort" else None)
-    if a.mode == "botsort-pipeline":
+    if a.mode == "xcam":
+        jobs = [me + ["step-xcam", "--streams", s, "--valid", v, "--steps", str(a.steps)] for s in (a.streams or "8,32,256").split(",")
+                for v in a.valid.split(",")] + [me + ["step-xcam-link", "--streams", "32", "--steps", str(max(a.steps, 20))]]
+    elif a.mode == "botsort-pipeline":
         jobs = [me + ["step-botsort-pipeline", "--streams", s, "--ring", str(a.ring), "--batch", str(a.batch), "--steps", str(a.steps),
                       "--gmc", str(a.gmc)] for s in (a.streams or "1,8,32").split(",")]
     elif a.mode == "tracker":
