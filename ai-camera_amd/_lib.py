@@ -228,6 +228,8 @@ _SIGS = {
     "aic_xcam_size": (_I, [_P, _P, _P, _P]),
     "aic_xcam_forget_stream": (_I, [_P, _I]),
     "aic_pipeline_link_cameras": (_I, [_P, _P, _P]),
+    "aic_pipeline_create_deepsort_bank": (_I, [_P, _P, _P, _I, _P]),
+    "aic_pipeline_deepsort_bank": (_I, [_P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -41,7 +41,7 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="AICamera: Real-time Object Detection & Tracking (MI355X engine)")
     p.add_argument("--input", type=str, default=None, help="video file (cv2), synthetic:WxH:persons:frames[:seed], frames.npy or raw:WxH:path")
     p.add_argument("--inputs", type=str, default=None,
-                   help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort|botsort only: one pipeline with one tracker "
+                   help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort|botsort|deepsort_bank only: one pipeline with one tracker "
                         "stream per source; the shortest source ends the run, one output per stream (suffix _s<k>)")
     p.add_argument("--webcam_id", type=int, default=0, help="webcam used when no --input is given (cv2)")
     p.add_argument("--output_dir", type=str, default="outputs")
@@ -52,12 +52,13 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--reid_engine", type=str, default=str(config.REID_ENGINE_PATH))
     p.add_argument("--conf_thresh", type=float, default=None,
                    help=f"detector score floor (default {config.YOLO_CONF_THRESHOLD}; with --tracker bytetrack its low_thresh 0.1, with ocsort its det_thresh 0.6, with botsort its track_low_thresh 0.1)")
-    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort", "botsort"),
-                   help="bytetrack / ocsort: no ReID model, the tracker's association on the device; botsort: IoU + ReID fusion on the device")
+    p.add_argument("--tracker", type=str, default="deepsort", choices=("deepsort", "bytetrack", "ocsort", "botsort", "deepsort_bank"),
+                   help="bytetrack / ocsort: no ReID model, the tracker's association on the device; botsort: IoU + ReID fusion on the device; "
+                        "deepsort_bank (with --inputs): DeepSORT for every source, one bank on the device")
     p.add_argument("--gmc", type=int, default=0, choices=(0, 2, 4),
                    help="botsort only: estimate the camera motion on the device at this downscale and warp the predicted tracks (0 = off)")
     p.add_argument("--link_cameras", action="store_true",
-                   help="--inputs with --tracker botsort only: link the cameras' identities on the device after every run call; every JSON line "
+                   help="--inputs with --tracker botsort or deepsort_bank only: link the cameras' identities on the device after every run call; every JSON line "
                         "gains \"global_ids\" parallel to \"tracks\" (-1 = not linked yet) and the overlay label shows the global id")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
@@ -65,13 +66,15 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.gmc and args.tracker != "botsort":
         p.error("--gmc needs --tracker botsort")
-    if args.link_cameras and (args.inputs is None or args.tracker != "botsort"):
-        p.error("--link_cameras needs --inputs a,b,c --tracker botsort")
+    if args.link_cameras and (args.inputs is None or args.tracker not in ("botsort", "deepsort_bank")):
+        p.error("--link_cameras needs --inputs a,b,c --tracker botsort or deepsort_bank")
+    if args.tracker == "deepsort_bank" and args.inputs is None:
+        p.error("--tracker deepsort_bank needs --inputs a,b,c (one source: --tracker deepsort)")
     if args.inputs is not None:
         if args.input is not None:
             p.error("--inputs and --input are mutually exclusive")
-        if args.tracker not in ("bytetrack", "ocsort", "botsort"):
-            p.error("--inputs needs --tracker bytetrack, ocsort or botsort")
+        if args.tracker not in ("bytetrack", "ocsort", "botsort", "deepsort_bank"):
+            p.error("--inputs needs --tracker bytetrack, ocsort, botsort or deepsort_bank")
     return args
 
 
@@ -207,8 +210,8 @@ class _BotSortFrame:
 
 
 def main_streams(args, cv2):
-    """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank for
-    --tracker botsort), their frames interleaved tick by tick."""
+    """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank /
+    deepsort_bank for --tracker botsort / deepsort_bank), their frames interleaved tick by tick."""
     from .pipeline import TrackingPipeline
     sources = [frame_source(spec, args.webcam_id, cv2) for spec in args.inputs.split(",") if spec]
     S = len(sources)
@@ -217,7 +220,8 @@ def main_streams(args, cv2):
         print("Error: --inputs sources must have one frame size: " + ", ".join(f"{src[2][0]}x{src[2][1]}" for src in sources))
         return 1
     if args.conf_thresh is None:
-        args.conf_thresh = 0.1 if args.tracker in ("bytetrack", "botsort") else 0.6
+        args.conf_thresh = (0.1 if args.tracker in ("bytetrack", "botsort") else
+                            config.YOLO_CONF_THRESHOLD if args.tracker == "deepsort_bank" else 0.6)
     batch = max(1, args.batch // S) * S          # whole ticks per launch group
     dev = config.resolve_device(args.device)
     try:
@@ -227,6 +231,12 @@ def main_streams(args, cv2):
             pipe = TrackingPipeline.botsort_bank(args.yolo_engine, reid, (size[1], size[0]), cameras=S, gmc=args.gmc, batch=batch,
                                                  ring_frames=batch, max_persons=512, max_tracks=512, device=dev, dtype=args.dtype,
                                                  conf_thresh=args.conf_thresh)
+        elif args.tracker == "deepsort_bank":
+            from .hip_engine import HipEngine
+            reid = HipEngine(args.reid_engine, device=dev, dtype=args.dtype, max_items=batch * 64, warm_up=False)   # as the single-source path
+            pipe = TrackingPipeline.deepsort_bank(args.yolo_engine, reid, (size[1], size[0]), cameras=S, batch=batch, ring_frames=batch,
+                                                  max_persons=512, max_tracks=512, device=dev, dtype=args.dtype,
+                                                  conf_thresh=args.conf_thresh)
         else:
             pipe = TrackingPipeline(args.yolo_engine, None, (size[1], size[0]), batch=batch, ring_frames=batch, max_persons=512,
                                     max_tracks=512, device=dev, dtype=args.dtype, conf_thresh=args.conf_thresh,
@@ -234,7 +244,7 @@ def main_streams(args, cv2):
     except Exception as e:
         print(f"Error initializing YOLO Detector: {e}")
         return 1
-    label = "AICamera: YOLOv8 + " + {"bytetrack": "ByteTrack", "ocsort": "OC-SORT", "botsort": "BoT-SORT"}[args.tracker]
+    label = "AICamera: YOLOv8 + " + {"bytetrack": "ByteTrack", "ocsort": "OC-SORT", "botsort": "BoT-SORT", "deepsort_bank": "DeepSORT"}[args.tracker]
     outs, writers = [None] * S, [None] * S
     if not args.no_save:
         out_dir = Path(args.output_dir)

@@ -73,6 +73,143 @@ static std::string err_text(int err) {
     return "the assignment problem has no finite solution";
 }
 
+void DeepSortBank::plan_epochs(BankPlan& pl, const int32_t* counts, const int* d0, bool feats, const int32_t* valid) const {
+    const int S = n_streams, st = pl.frame_stride;
+    const int kmax = std::max(1, std::min(std::min(TRK_KMAX, epoch_frames > 0 ? epoch_frames : TRK_KMAX), gmax));
+    auto row_of = [&](int q, int i) { return pl.stream_f0[q] + i * st; };
+    for (int f = 0; f < pl.kmax_s;) {
+        int ke = std::min(kmax, pl.kmax_s - f);
+        for (int q = 0; q < S; ++q) {
+            int dn = 0, kk = 0;
+            while (kk < ke && f + kk < pl.stream_k[q] && dn + counts[row_of(q, f + kk)] <= TRK_DEV_DNMAX) dn += counts[row_of(q, f + kk)], ++kk;
+            if (f + kk < pl.stream_k[q]) ke = std::min(ke, kk);     // cut by the row budget, not by the stream's end
+        }
+        BankPlan::Epoch e{f, ke, 0};
+        for (int q = 0; q < S; ++q) {
+            EpochStreamPlan p{};
+            p.map0 = (int)pl.row_map.size();
+            p.nmax = 1;
+            bool any_valid = false;
+            for (int i = f; i < f + ke && i < pl.stream_k[q]; ++i) {
+                const int row = row_of(q, i), c = counts[row];
+                pl.e0[row] = p.dn;
+                p.dn += c, p.nmax = std::max(p.nmax, c);
+                for (int j = 0; j < c; ++j) {
+                    pl.row_map.push_back(d0[row] + j);
+                    any_valid |= !valid || valid[d0[row] + j] != 0;
+                }
+            }
+            p.dn_pad = std::max(32, (p.dn + 31) / 32 * 32);
+            p.has_sm = (feats && any_valid) ? 1 : 0;          // a stream without detections, or without features, runs without SM / GRAM
+            if (p.has_sm) e.dn_pad_max = std::max(e.dn_pad_max, p.dn_pad);
+            pl.plans.push_back(p);
+        }
+        pl.dn_pad_call = std::max(pl.dn_pad_call, e.dn_pad_max);
+        pl.epochs.push_back(e);
+        f += ke;
+    }
+}
+
+// scratch slices for what the call needs (not the kernels' maxima: SM alone is 71 MB per stream there)
+void DeepSortBank::size_scratch(const BankPlan& pl) {
+    const int S = n_streams;
+    sm_stride = std::max(sm_stride, (size_t)cap * (TRK_KMAX + 1) * pl.dn_pad_call);
+    gram_stride = std::max(gram_stride, (size_t)pl.dn_pad_call * pl.dn_pad_call);
+    cost_stride = std::max(cost_stride, (size_t)3 * cap * pl.nmax_call);
+    sub_stride = std::max(sub_stride, (size_t)cap * pl.nmax_call);
+    d_sm.ensure(sm_stride * S), d_gram.ensure(gram_stride * S), d_cost.ensure(cost_stride * S), d_sub.ensure(sub_stride * S);
+}
+
+void DeepSortBank::launch_epochs(const BankPlan& pl, const EpochStreamPlan* d_plan, const int* d_map, const int* d_e0, const int* d_f0,
+                                 const int* d_k, const EpochDets& dets, const EpochOut& out, hipStream_t s) {
+    const int S = n_streams;
+    EpochBankArgs bk{};
+    bk.tbl = d_tbl.p, bk.tbl_stride = tbl_stride;
+    bk.mean_stride = (size_t)cap * 8, bk.cov_stride = (size_t)cap * 64, bk.gal_stride = gal_stride;
+    bk.sm_stride = sm_stride, bk.gram_stride = gram_stride, bk.cost_stride = cost_stride, bk.sub_stride = sub_stride;
+    bk.stream_f0 = d_f0, bk.stream_k = d_k;
+    bk.frame_stride = pl.frame_stride;
+    bk.row_map = d_map;
+    bk.frame_e0 = d_e0;
+    TrkDevParams p = prm;
+    p.no_fast = lsap_fast ? 0 : 1, p.no_wave = wave_cascade ? 0 : 1;
+    const EpochScratch scr{d_sm.p, d_gram.p, d_cost.p, d_sub.p, d_appends.p};
+    for (size_t e = 0; e < pl.epochs.size(); ++e) {
+        const BankPlan::Epoch& ep = pl.epochs[e];
+        bk.plan = d_plan + e * S;
+        if (ep.dn_pad_max > 0) {
+            Prof pr(*dev, PROF_TRK, s, 0, 0);
+            launch_trk_epoch_prep_bank(bk, S, d_gal_n.p, gmax, dim, cap, dets.feat_n, ep.dn_pad_max, ep.f0, ep.k, d_sm.p, d_gram.p, s);
+        }
+        Prof pr(*dev, PROF_TRK, s, 0, 0);
+        launch_trk_epoch_bank(bk, S, d_mean.p, d_cov.p, d_gal_raw.p, d_gal_n.p, p, dets, ep.f0, ep.k, pl.nmax_call, scr, out, s);
+    }
+}
+
+void DeepSortBank::note_stops(const DevTrkHdr* hh) {
+    for (int q = 0; q < n_streams; ++q) {
+        if (stop_code[q] || hh[q].err == 0) continue;
+        stop_code[q] = hh[q].err == 2 ? AIC_ERR_RUNTIME : AIC_ERR_CAPACITY;
+        stop_msg[q] = "stream " + std::to_string(q) + ": " + err_text(hh[q].err) + " (frame " + std::to_string(hh[q].err_frame) + " of the call)";
+    }
+}
+
+void DeepSortBank::run_group(const EpochDets& dets, const int* h_n, const int* h_d0, int frames, const EpochOut& out, hipStream_t s) {
+    const int S = n_streams;
+    AIC_REQUIRE(frames > 0 && frames % S == 0, AIC_ERR_INVALID, "a launch group must hold whole ticks of every stream");
+    for (int q = 0; q < S; ++q)
+        AIC_REQUIRE(!stop_code[q], AIC_ERR_INVALID, "DeepSORT bank stream stopped by an earlier error (reset it first): " + stop_msg[q]);
+    BankPlan& pl = grp;
+    pl = BankPlan{};
+    pl.stream_f0.resize(S), pl.stream_k.assign(S, frames / S);
+    for (int q = 0; q < S; ++q) pl.stream_f0[q] = q;
+    pl.frame_stride = S, pl.kmax_s = frames / S;
+    size_t n = 0;
+    for (int f = 0; f < frames; ++f) {
+        AIC_REQUIRE(h_n[f] >= 0 && h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "DeepSORT bank: more than 512 detections in one frame");
+        pl.nmax_call = std::max(pl.nmax_call, h_n[f]);
+        n += (size_t)h_n[f];
+    }
+    pl.e0.resize(frames);
+    pl.row_map.reserve(n);
+    // the crop validity lives in HBM: a stream's SM / GRAM are built whenever it has rows (Tracker::run_epochs)
+    plan_epochs(pl, h_n, h_d0, dets.feat_n != nullptr, nullptr);
+    const size_t E = pl.epochs.size(), k = (size_t)frames;
+    auto up = [](size_t x) { return (x + 15) / 16 * 16; };
+    const size_t o_map = E * S * sizeof(EpochStreamPlan), o_e0 = o_map + n * 4, o_f0 = up(o_e0 + k * 4), o_k = o_f0 + (size_t)S * 4;
+    const size_t o_hdr = up(o_k + (size_t)S * 4), bytes = o_hdr + (size_t)S * sizeof(DevTrkHdr);
+    if (bytes > h_grp.n) {                                         // (the caller synced s behind the previous group)
+        HIP_CHECK(hipStreamSynchronize(s));
+        h_grp.alloc(bytes + bytes / 4), d_grp.alloc(bytes + bytes / 4);
+    }
+    size_scratch(pl);
+    std::memcpy(h_grp.p, pl.plans.data(), o_map);
+    if (n) std::memcpy(h_grp.p + o_map, pl.row_map.data(), n * 4);
+    std::memcpy(h_grp.p + o_e0, pl.e0.data(), k * 4);
+    std::memcpy(h_grp.p + o_f0, pl.stream_f0.data(), (size_t)S * 4);
+    std::memcpy(h_grp.p + o_k, pl.stream_k.data(), (size_t)S * 4);
+    HIP_CHECK(hipMemcpyAsync(d_grp.p, h_grp.p, o_hdr, hipMemcpyHostToDevice, s));
+    launch_epochs(pl, reinterpret_cast<const EpochStreamPlan*>(d_grp.p), reinterpret_cast<const int*>(d_grp.p + o_map),
+                  reinterpret_cast<const int*>(d_grp.p + o_e0), reinterpret_cast<const int*>(d_grp.p + o_f0),
+                  reinterpret_cast<const int*>(d_grp.p + o_k), dets, out, s);
+    HIP_CHECK(hipMemcpy2DAsync(d_grp.p + o_hdr, sizeof(DevTrkHdr), d_tbl.p, tbl_stride, sizeof(DevTrkHdr), S, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(h_grp.p + o_hdr, d_grp.p + o_hdr, (size_t)S * sizeof(DevTrkHdr), hipMemcpyDeviceToHost, s));
+    grp_hdr = o_hdr;
+}
+
+int DeepSortBank::check_group() {
+    const DevTrkHdr* hh = reinterpret_cast<const DevTrkHdr*>(h_grp.p + grp_hdr);
+    const std::vector<int> before = stop_code;
+    note_stops(hh);
+    int bad = -1;
+    grp_good.assign(n_streams, 0);
+    for (int q = 0; q < n_streams; ++q) {
+        grp_good[q] = before[q] ? 0 : stop_code[q] ? hh[q].err_frame : grp.stream_k[q];
+        if (bad < 0 && stop_code[q] && !before[q]) bad = q;
+    }
+    return bad;
+}
+
 void DeepSortBank::update(const int32_t* frames_per_stream, const int32_t* counts, const float* det_tlwh, const float* conf, const int32_t* cls,
                           const float* feat, const int32_t* valid, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf,
                           int32_t* status) {
@@ -105,50 +242,21 @@ void DeepSortBank::update(const int32_t* frames_per_stream, const int32_t* count
         const size_t k = (size_t)F, n = (size_t)total;
         const bool feats = feat != nullptr && n > 0;
 
-        // ---- the call's epochs.  k is common to the streams of a launch: the largest k <= min(epoch_frames or 16, gmax) for which every
-        //      stream's rows of the epoch stay within TRK_DEV_DNMAX (a frame holds <= 512 rows, so k >= 4 whatever the load).
-        std::vector<int> f0s(S), d0(k), e0(k);
-        for (int q = 0, f = 0; q < S; ++q) { f0s[q] = f; f += frames_per_stream[q]; }
+        // ---- the call's epochs (plan_epochs: shared with run_group)
+        BankPlan pl;
+        pl.stream_f0.resize(S), pl.stream_k.assign(frames_per_stream, frames_per_stream + S);
+        for (int q = 0, f = 0; q < S; ++q) { pl.stream_f0[q] = f; f += frames_per_stream[q]; }
+        pl.frame_stride = 1, pl.kmax_s = kmax_s, pl.nmax_call = nmax_call;
+        std::vector<int> d0(k);
         { int d = 0; for (size_t f = 0; f < k; ++f) { d0[f] = d; d += counts[f]; } }
-        const int kmax = std::max(1, std::min(std::min(TRK_KMAX, epoch_frames > 0 ? epoch_frames : TRK_KMAX), gmax));
-        struct Epoch { int f0, k, dn_pad_max; };
-        std::vector<Epoch> epochs;
-        std::vector<EpochStreamPlan> plans;                        // [epochs][S]
-        std::vector<int> row_map;
-        row_map.reserve(n);
-        int dn_pad_call = 0;
-        for (int f = 0; f < kmax_s;) {
-            int ke = std::min(kmax, kmax_s - f);
-            for (int q = 0; q < S; ++q) {
-                int dn = 0, kk = 0;
-                while (kk < ke && f + kk < frames_per_stream[q] && dn + counts[f0s[q] + f + kk] <= TRK_DEV_DNMAX) dn += counts[f0s[q] + f + kk], ++kk;
-                if (f + kk < frames_per_stream[q]) ke = std::min(ke, kk);     // cut by the row budget, not by the stream's end
-            }
-            Epoch e{f, ke, 0};
-            for (int q = 0; q < S; ++q) {
-                EpochStreamPlan pl{};
-                pl.map0 = (int)row_map.size();
-                pl.nmax = 1;
-                bool any_valid = false;
-                for (int i = f; i < f + ke && i < frames_per_stream[q]; ++i) {
-                    const int row = f0s[q] + i, c = counts[row];
-                    e0[row] = pl.dn;
-                    pl.dn += c, pl.nmax = std::max(pl.nmax, c);
-                    for (int j = 0; j < c; ++j) {
-                        row_map.push_back(d0[row] + j);
-                        any_valid |= !valid || valid[d0[row] + j] != 0;
-                    }
-                }
-                pl.dn_pad = std::max(32, (pl.dn + 31) / 32 * 32);
-                pl.has_sm = (feats && any_valid) ? 1 : 0;         // a stream without detections, or without features, runs without SM / GRAM
-                if (pl.has_sm) e.dn_pad_max = std::max(e.dn_pad_max, pl.dn_pad);
-                plans.push_back(pl);
-            }
-            dn_pad_call = std::max(dn_pad_call, e.dn_pad_max);
-            epochs.push_back(e);
-            f += ke;
-        }
-        const size_t E = epochs.size();
+        pl.e0.resize(k);
+        pl.row_map.reserve(n);
+        plan_epochs(pl, counts, d0.data(), feats, valid);
+        const std::vector<int>& f0s = pl.stream_f0;
+        const std::vector<int>& e0 = pl.e0;
+        const std::vector<int>& row_map = pl.row_map;
+        const std::vector<EpochStreamPlan>& plans = pl.plans;
+        const size_t E = pl.epochs.size();
 
         // ---- staging (host == device layout):
         //   plan[E*S] | row_map[n] | frame_e0[F] | stream_f0[S] | stream_k[S] | frame_n[F] | frame_d0[F] | tlwh[n*4] | conf[n] | cls[n] | valid[n] | feat[n*dim]
@@ -163,12 +271,7 @@ void DeepSortBank::update(const int32_t* frames_per_stream, const int32_t* count
         HIP_CHECK(hipStreamSynchronize(s));
         h_api.ensure(bytes);
         d_api.ensure(o_featn + feat_bytes);
-        // scratch slices for what this call needs (not the kernels' maxima: SM alone is 71 MB per stream there)
-        sm_stride = std::max(sm_stride, (size_t)cap * (TRK_KMAX + 1) * dn_pad_call);
-        gram_stride = std::max(gram_stride, (size_t)dn_pad_call * dn_pad_call);
-        cost_stride = std::max(cost_stride, (size_t)3 * cap * nmax_call);
-        sub_stride = std::max(sub_stride, (size_t)cap * nmax_call);
-        d_sm.ensure(sm_stride * S), d_gram.ensure(gram_stride * S), d_cost.ensure(cost_stride * S), d_sub.ensure(sub_stride * S);
+        size_scratch(pl);
 
         std::memcpy(h_api.p, plans.data(), o_map);
         if (n) std::memcpy(h_api.p + o_map, row_map.data(), n * 4);
@@ -198,36 +301,14 @@ void DeepSortBank::update(const int32_t* frames_per_stream, const int32_t* count
         }
         EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows), reinterpret_cast<float*>(d_api.p + o_oconf),
                      cap_rows, nullptr, nullptr, 0};
-        EpochBankArgs bk{};
-        bk.tbl = d_tbl.p, bk.tbl_stride = tbl_stride;
-        bk.mean_stride = (size_t)cap * 8, bk.cov_stride = (size_t)cap * 64, bk.gal_stride = gal_stride;
-        bk.sm_stride = sm_stride, bk.gram_stride = gram_stride, bk.cost_stride = cost_stride, bk.sub_stride = sub_stride;
-        bk.stream_f0 = reinterpret_cast<const int*>(d_api.p + o_f0), bk.stream_k = reinterpret_cast<const int*>(d_api.p + o_k);
-        bk.frame_stride = 1;
-        bk.row_map = reinterpret_cast<const int*>(d_api.p + o_map);
-        bk.frame_e0 = reinterpret_cast<const int*>(d_api.p + o_e0);
-        TrkDevParams p = prm;
-        p.no_fast = lsap_fast ? 0 : 1, p.no_wave = wave_cascade ? 0 : 1;
-        const EpochScratch scr{d_sm.p, d_gram.p, d_cost.p, d_sub.p, d_appends.p};
-        for (size_t e = 0; e < E; ++e) {
-            bk.plan = reinterpret_cast<const EpochStreamPlan*>(d_api.p) + e * S;
-            if (epochs[e].dn_pad_max > 0) {
-                Prof pr(*dev, PROF_TRK, s, 0, 0);
-                launch_trk_epoch_prep_bank(bk, S, d_gal_n.p, gmax, dim, cap, dets.feat_n, epochs[e].dn_pad_max, epochs[e].f0, epochs[e].k, d_sm.p,
-                                           d_gram.p, s);
-            }
-            Prof pr(*dev, PROF_TRK, s, 0, 0);
-            launch_trk_epoch_bank(bk, S, d_mean.p, d_cov.p, d_gal_raw.p, d_gal_n.p, p, dets, epochs[e].f0, epochs[e].k, nmax_call, scr, out, s);
-        }
+        launch_epochs(pl, reinterpret_cast<const EpochStreamPlan*>(d_api.p), reinterpret_cast<const int*>(d_api.p + o_map),
+                      reinterpret_cast<const int*>(d_api.p + o_e0), reinterpret_cast<const int*>(d_api.p + o_f0),
+                      reinterpret_cast<const int*>(d_api.p + o_k), dets, out, s);
         HIP_CHECK(hipMemcpy2DAsync(d_api.p + o_hdr, sizeof(DevTrkHdr), d_tbl.p, tbl_stride, sizeof(DevTrkHdr), S, hipMemcpyDeviceToDevice, s));
         HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         const DevTrkHdr* hh = reinterpret_cast<const DevTrkHdr*>(h_api.p + o_hdr);
-        for (int q = 0; q < S; ++q) {
-            if (stop_code[q] || hh[q].err == 0) continue;
-            stop_code[q] = hh[q].err == 2 ? AIC_ERR_RUNTIME : AIC_ERR_CAPACITY;
-            stop_msg[q] = "stream " + std::to_string(q) + ": " + err_text(hh[q].err) + " (frame " + std::to_string(hh[q].err_frame) + " of the call)";
-        }
+        note_stops(hh);
         const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
         const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
         const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);

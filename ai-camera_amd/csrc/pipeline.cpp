@@ -19,6 +19,7 @@
 #include "botsort_host.hpp"
 #include "gmc.hpp"
 #include "xcam.hpp"
+#include "deepsort_bank.hpp"
 #include "conv_common.hpp"
 
 #include <algorithm>
@@ -201,6 +202,9 @@ struct Pipeline {
     float bs_low = 0.f;             // its track_low_thresh: inject = 0 hands over the detections with score > bs_low
     // aic_pipeline_option("gmc"): camera motion per frame, estimated on the device and handed to the BoT-SORT epochs; NULL = off
     std::unique_ptr<CameraMotionEstimator> gmc;
+    // A DeepSORT bank (aic_pipeline_create_deepsort_bank): stage A as for the single DeepSORT pipeline (device filter included), stage B hands
+    // the group to DeepSortBank::run_group -- always the device association, one block per camera.  `trk` then exists but is never run.
+    std::unique_ptr<aic_deepsort_bank> dsb;
 
     static aic_tracker_params tracker_params(const aic_pipeline_params& p, bool bytetrack) {
         if (!bytetrack) return p.tracker;
@@ -211,8 +215,8 @@ struct Pipeline {
     }
 
     Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr,
-             const BsParams* bsp = nullptr, int bs_streams = 0)
-        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp || bsp))), trk(trk_handle->t) {
+             const BsParams* bsp = nullptr, int bs_streams = 0, const TrkDevParams* dsp = nullptr, int ds_streams = 0)
+        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp || bsp || dsp))), trk(trk_handle->t) {
         AIC_REQUIRE(y->kind == KIND_YOLO && (btp || ocp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
                     btp   ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
                     : ocp ? "an OC-SORT pipeline takes a YOLO engine and no ReID engine"
@@ -221,7 +225,8 @@ struct Pipeline {
         AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
-        AIC_REQUIRE(!bs_streams || (p.batch % bs_streams == 0 && p.ring_frames % bs_streams == 0), AIC_ERR_INVALID,
+        const int bank_streams = std::max(bs_streams, ds_streams);
+        AIC_REQUIRE(!bank_streams || (p.batch % bank_streams == 0 && p.ring_frames % bank_streams == 0), AIC_ERR_INVALID,
                     "batch and ring_frames must be multiples of streams");
         AIC_REQUIRE(p.batch <= y->max_items, AIC_ERR_CAPACITY, "batch exceeds the YOLO engine's max_items");
         AIC_REQUIRE(p.max_det > 0 && p.max_det <= y->max_det_cap, AIC_ERR_CAPACITY, "max_det out of range");
@@ -229,6 +234,7 @@ struct Pipeline {
         if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
         else if (ocp) bt.reset(new OcSortTracker(*dev, *ocp, bt_first_id));
         else if (bsp) { bt.reset(new BotSortTracker(*dev, *bsp, bt_first_id, std::max(1, bs_streams))); bs = true; bs_low = bsp->low; bs_bank = bs_streams > 0; }
+        else if (dsp) dsb.reset(new aic_deepsort_bank(*dev, *dsp, bt_first_id, ds_streams));
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
@@ -413,7 +419,7 @@ struct Pipeline {
         }
         int n_max = 0;
         for (int f = 0; f < frames; ++f) n_max = std::max(n_max, c.dets[f].n);
-        const bool dev_mode = bt || use_device(n_max, c.tracks_after);   // detector-only: always the epoch kernel's detection arrays
+        const bool dev_mode = bt || dsb || use_device(n_max, c.tracks_after);   // detector-only, DeepSORT bank: always the epoch kernel's detection arrays
         c.dev_mode = dev_mode;
         if (dev_mode) {   // what the epoch kernels read: frame_n[frames] | frame_d0[frames] | tlwh[nc,4] | conf[nc] | cls[nc]
             c.m_n = 0, c.m_d0 = (size_t)frames * 4, c.m_tlwh = (((size_t)frames * 8 + 15) / 16) * 16;
@@ -564,7 +570,7 @@ struct Pipeline {
             fd.n = c.h_fn.p[f], fd.crop0 = c.h_fd0.p[f];
             n_max = std::max(n_max, fd.n);
         }
-        c.dev_mode = use_device(n_max, c.tracks_after);
+        c.dev_mode = dsb || use_device(n_max, c.tracks_after);   // (a bank has no host chain: run_group refuses a frame beyond 512 rows)
         if (total > c.reid_rows) {             // a crowded group: every surviving detection is embedded (deepsort_tracker.py:104-113), in further rounds
             hipStream_t s = c.s_reid_used ? c.s_reid_used : c.ln->s_main;
             const uint8_t* f0 = ring.p + (size_t)c.first_slot * frame_bytes;
@@ -803,19 +809,83 @@ struct Pipeline {
         n_frames_done += c.frames;
     }
 
+    // Stage B of a DeepSORT bank pipeline: the group, tick-major over the cameras, through DeepSortBank::run_group on the tracker stream.
+    // Boxes and embeddings stay where stage A left them; the plan (a few ints per detection) is all that goes up.  A camera that stops
+    // in the group gets no rows from its failing frame on, the other cameras' rows are delivered, then the call raises.
+    void stage_b_bank(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets, float* det_boxes,
+                      float* det_scores, int32_t* det_labels) {
+        const double t0 = now();
+        DeepSortBank& b = dsb->t;
+        const int S = b.n_streams;
+        hipStream_t s = dev->s_trk;
+        const int mp = prm.max_persons;
+        const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
+        const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
+        EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
+                       reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
+                       reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
+        const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
+        const int* h_d0 = reinterpret_cast<const int*>(c.h_meta.p + c.m_d0);
+        if (c.filt_dev) {                                      // the arrays the device filter wrote; counts came back behind ev_det (prepare_b)
+            dets = EpochDets{c.d_fn.p, c.d_fd0.p, c.d_ftlwh.p, c.d_fconf.p, c.d_fcls.p, c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
+            h_n = c.h_fn.p, h_d0 = c.h_fd0.p;
+        }
+        if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
+        HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's embeddings, crop validity and detection arrays are in HBM
+        EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
+                     mp, nullptr, nullptr, 0};
+        b.run_group(dets, h_n, h_d0, c.frames, out, s);        // (a frame beyond 512 rows raises before anything is launched: no host chain here)
+        n_assoc_dev += c.frames;
+        HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
+        const double t1 = now();
+        t_track += t1 - t0;                                    // host time of the association: planning + launches
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipEventSynchronize(c.ev_det));              // the detector's outputs of the group are on the host (inject: `done` did not cover them)
+        const int bad = b.check_group();
+        const double t2 = now();
+        t_wait += t2 - t1;
+        const int* on = reinterpret_cast<const int*>(c.h_out.p);
+        const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
+        const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
+        const size_t md = prm.max_det;
+        for (int f = 0; f < c.frames; ++f) {
+            const int o = out_base + f;
+            const int m = f / S < b.grp_good[f % S] ? on[f] : 0;   // a stopped camera: nothing from its failing frame on
+            const int k = std::min(m, mp);
+            if (n_tracks) n_tracks[o] = m;                     // the true count: rows beyond max_persons are not stored
+            if (m > mp) n_rows_clipped += 1;
+            if (tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, tracks6 + (size_t)o * mp * 6);
+            if (track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, track_conf + (size_t)o * mp);
+            if (n_dets) n_dets[o] = c.h_numdets.p[f];
+            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
+            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
+            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
+        }
+        const FrameDets& fl = c.dets[c.frames - 1];
+        if (final_group) {
+            last_emb_n = fl.n;
+            last_emb.resize((size_t)fl.n * dim);
+            if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
+        }
+        last_chunk = (int)(&c - &ck[0]);
+        t_track += now() - t2;
+        n_frames_done += c.frames;
+        AIC_REQUIRE(bad < 0, b.stop_code[bad], "DeepSORT bank: " + b.stop_msg[bad]);
+    }
+
     // passes > 1: the same ring range is walked `passes` times back to back as ONE continuous stream (outputs of a
     // later pass overwrite the rows of the earlier one): only the very last group of the call has an un-overlapped tail.
     void run(int slot, int count, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets, float* det_boxes,
              float* det_scores, int32_t* det_labels, int passes = 1) {
         AIC_REQUIRE(slot >= 0 && count >= 0 && slot + count <= prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
         AIC_REQUIRE(passes >= 1, AIC_ERR_INVALID, "passes must be >= 1");
-        const int S = bt ? bt->streams() : 1;    // > 1: ring and run ranges are tick-major over S streams
+        const int S = bt ? bt->streams() : dsb ? dsb->t.n_streams : 1;    // > 1: ring and run ranges are tick-major over S streams
         AIC_REQUIRE(slot % S == 0 && count % S == 0, AIC_ERR_INVALID, "slot and count must be multiples of the pipeline's streams");
         dev->use();
         if (count <= 0) return;
         // the association epoch kernel holds one CU (a bank: one per stream, trk_cus at most) while the next group's convs run:
         // persistent conv grids leave them free
-        set_conv_cu_budget(bt || (dev_assoc && trk.dev_capable()) ? dev->n_cu - std::max(1, std::min(S, trk_cus)) : dev->n_cu);
+        set_conv_cu_budget(bt || dsb || (dev_assoc && trk.dev_capable()) ? dev->n_cu - std::max(1, std::min(S, trk_cus)) : dev->n_cu);
         tracks_seen = trk.on_device ? tracks_seen.load() : (int)trk.tracks.size();
         for (auto& c : ck) c.tracks_after = tracks_seen;
         // Launch groups: full batches, then the last batch tapered (1/2, 1/4, ... down to 16 frames): stage B of the
@@ -913,6 +983,7 @@ struct Pipeline {
                 if (ck[k % nck].filt_dev) prepare_b(ck[k % nck]);
                 ck[k % nck].prev_dev_mode = ck[k % nck].dev_mode;
                 if (bt) stage_b_epochs(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
+                else if (dsb) stage_b_bank(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
                 else if (ck[k % nck].dev_mode) {
                     trk.dev_assoc = true;
                     stage_b_device(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
@@ -948,8 +1019,8 @@ using namespace aic;
 struct aic_pipeline {
     Pipeline p;
     aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr,
-                 const BsParams* bs = nullptr, int bs_streams = 0)
-        : p(y, r, q, b, first_id, o, bs, bs_streams) {}
+                 const BsParams* bs = nullptr, int bs_streams = 0, const aic::TrkDevParams* ds = nullptr, int ds_streams = 0)
+        : p(y, r, q, b, first_id, o, bs, bs_streams, ds, ds_streams) {}
 };
 
 extern "C" {
@@ -996,6 +1067,28 @@ int aic_pipeline_create_botsort_bank(aic_model* yolo, aic_model* reid, const aic
         const BsParams b = botsort_params(*bp, &first);
         AIC_REQUIRE(streams >= 1 && streams <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
         *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b, streams);
+    });
+}
+
+int aic_pipeline_create_deepsort_bank(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, int streams, aic_pipeline** out) {
+    return guarded([&] {
+        AIC_REQUIRE(yolo && reid && p && out, AIC_ERR_INVALID, "NULL argument");
+        aic_tracker_params tp = p->tracker;
+        AIC_REQUIRE(reid->m.kind == KIND_REID, AIC_ERR_INVALID, "pipeline needs a YOLO and a ReID engine");
+        AIC_REQUIRE(tp.feature_dim == 0 || tp.feature_dim == reid->m.out_dim, AIC_ERR_INVALID,
+                    "feature_dim of the tracker parameters differs from the ReID engine's output");
+        tp.feature_dim = reid->m.out_dim;
+        int first = 1;
+        const TrkDevParams t = deepsort_bank_params(tp, streams, &first);   // the rejections of aic_deepsort_bank_create
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, nullptr, 0, &t, streams);
+    });
+}
+
+int aic_pipeline_deepsort_bank(aic_pipeline* p, aic_deepsort_bank** out) {
+    return guarded([&] {
+        AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(p->p.dsb, AIC_ERR_INVALID, "not a DeepSORT bank pipeline (aic_pipeline_create_deepsort_bank)");
+        *out = p->p.dsb.get();          // owned by the pipeline: do not destroy
     });
 }
 
@@ -1103,6 +1196,7 @@ int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out) {
     return guarded([&] {
         AIC_REQUIRE(p && out, AIC_ERR_INVALID, "NULL argument");
         AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "a " + p->p.bt_name() + " pipeline has no DeepSORT tracker");
+        AIC_REQUIRE(!p->p.dsb, AIC_ERR_INVALID, "a DeepSORT bank pipeline has no single tracker: its cameras' state is aic_pipeline_deepsort_bank's");
         *out = p->p.trk_handle.get();   // owned by the pipeline: do not destroy
     });
 }
@@ -1122,6 +1216,7 @@ int aic_pipeline_exchange_enable(aic_pipeline* p, float* shard0_dev, float* shar
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
         AIC_REQUIRE(!p->p.bt, AIC_ERR_INVALID, "the gallery exchange needs DeepSORT's appearance galleries (this pipeline runs " + p->p.bt_name() + ")");
+        AIC_REQUIRE(!p->p.dsb, AIC_ERR_INVALID, "the gallery exchange serves one camera per rank: a DeepSORT bank's cameras are linked by aic_pipeline_link_cameras");
         Pipeline& q = p->p;
         q.dev->use();
         std::lock_guard<std::mutex> lk(q.x_mu);
@@ -1206,8 +1301,10 @@ int aic_pipeline_exchange_done(aic_pipeline* p, int64_t seq) {
 int aic_pipeline_reset_stream(aic_pipeline* p, int stream) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
+        if (p->p.dsb) return p->p.dsb->t.reset_stream(stream);
         AIC_REQUIRE(p->p.bt && (!p->p.bs || p->p.bs_bank), AIC_ERR_INVALID,
-                    "reset_stream applies to ByteTrack and OC-SORT pipelines and to BoT-SORT banks (aic_pipeline_create_botsort_bank) only");
+                    "reset_stream applies to ByteTrack and OC-SORT pipelines and to BoT-SORT and DeepSORT banks (aic_pipeline_create_botsort_bank, "
+                    "aic_pipeline_create_deepsort_bank) only");
         p->p.bt->reset_stream(stream);
         if (p->p.gmc) p->p.gmc->reset(stream);       // the camera's next frame is its first
     });
@@ -1216,9 +1313,10 @@ int aic_pipeline_reset_stream(aic_pipeline* p, int stream) {
 int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links) {
     return guarded([&] {
         AIC_REQUIRE(p && x, AIC_ERR_INVALID, "NULL argument");
-        AIC_REQUIRE(p->p.bt && p->p.bs && p->p.bs_bank, AIC_ERR_INVALID,
-                    "link_cameras applies to BoT-SORT bank pipelines (aic_pipeline_create_botsort_bank) only");
-        const int l = x->x.link(*static_cast<BotSortTracker*>(p->p.bt.get()));   // on the tracker stream, behind the last run call's epochs
+        AIC_REQUIRE(p->p.dsb || (p->p.bt && p->p.bs && p->p.bs_bank), AIC_ERR_INVALID,
+                    "link_cameras applies to BoT-SORT and DeepSORT bank pipelines (aic_pipeline_create_botsort_bank, aic_pipeline_create_deepsort_bank) only");
+        // on the tracker stream, behind the last run call's epochs
+        const int l = p->p.dsb ? x->x.link(p->p.dsb->t) : x->x.link(*static_cast<BotSortTracker*>(p->p.bt.get()));
         if (n_links) *n_links = l;
     });
 }
@@ -1234,6 +1332,10 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
         else if (k == "split_streams") p->p.split_streams = value != 0;
         else if (p->p.bt && (k == "device_assoc" || k == "device_assoc_limit" || k == "device_filter"))
             AIC_REQUIRE(false, AIC_ERR_INVALID, "option " + k + " applies to DeepSORT pipelines only (this one runs " + p->p.bt_name() + ")");
+        else if (p->p.dsb && (k == "device_assoc" || k == "device_assoc_limit" || k == "streams" || k == "gmc"))
+            AIC_REQUIRE(false, AIC_ERR_INVALID, k == "streams" ? "option streams: the camera count of a DeepSORT bank pipeline is fixed at creation"
+                                                : k == "gmc"   ? "option gmc applies to BoT-SORT pipelines only"
+                                                               : "option " + k + ": a DeepSORT bank pipeline always associates on the device (it has no host chain)");
         else if (k == "device_assoc") {
             AIC_REQUIRE(value >= 0 && value <= 2, AIC_ERR_INVALID, "device_assoc: 0 host, 1 auto, 2 always on the device");
             p->p.dev_assoc = value;
@@ -1272,10 +1374,11 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
             AIC_REQUIRE(value >= 0 && value <= p->p.prm.batch, AIC_ERR_INVALID, "group_frames must be in 0..batch");
             p->p.group_frames = value;
         }
-        else if (k == "epoch_frames") {              // frames per BoT-SORT epoch launch, as aic_botsort_option (same results either way)
-            AIC_REQUIRE(p->p.bs, AIC_ERR_INVALID, "option epoch_frames applies to BoT-SORT pipelines only");
+        else if (k == "epoch_frames") {              // frames per epoch launch, as aic_botsort_option / aic_deepsort_bank_option (same results either way)
+            AIC_REQUIRE(p->p.bs || p->p.dsb, AIC_ERR_INVALID, "option epoch_frames applies to BoT-SORT and DeepSORT bank pipelines only");
             AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
-            static_cast<BotSortTracker*>(p->p.bt.get())->epoch_frames = value;
+            if (p->p.dsb) p->p.dsb->t.epoch_frames = value;
+            else static_cast<BotSortTracker*>(p->p.bt.get())->epoch_frames = value;
         }
         else if (k == "gmc") {
             AIC_REQUIRE(p->p.bs, AIC_ERR_INVALID, "option gmc applies to BoT-SORT pipelines only");

@@ -39,6 +39,21 @@ class DeepSORTBank(CameraLinks, TrackerBank):
         self.feature_dim = self.params.feature_dim or 512
         self._create(streams, device)
 
+    @classmethod
+    def _borrow(cls, handle, params, streams, device, feature_dim):
+        """The bank a TrackingPipeline.deepsort_bank pipeline owns (aic_pipeline_deepsort_bank): close() destroys nothing."""
+        b = cls.__new__(cls)
+        b.params, b._h, b._borrowed = params, handle, True
+        b.streams, b.failed, b._device = int(streams), {}, device
+        b.max_tracks, b.feature_dim = params.max_tracks or 512, int(feature_dim)
+        return b
+
+    def close(self):
+        if getattr(self, "_borrowed", False):
+            self._h = C.c_void_p()
+        else:
+            super().close()
+
     def option(self, key, value):
         """"lsap_fast" (0/1), "wave_cascade" (0/1), "epoch_frames" (0..16), for the whole bank: same results either way."""
         L.call(self._abi + "_option", self._h, key.encode(), int(value))

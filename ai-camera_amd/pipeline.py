@@ -33,11 +33,12 @@ class TrackingPipeline:
         downscale (aic_pipeline_option "gmc", gmc.py) and warps the predicted tracks; group_warps() reads the last group's.
         streams=S (ByteTrack / OC-SORT only): one pipeline for S cameras.  The ring and every run range are tick-major, slot t * S + s
         being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams.
-        BoT-SORT for S cameras: TrackingPipeline.botsort_bank(...), which passes the camera count as _cameras."""
+        BoT-SORT or DeepSORT for S cameras: TrackingPipeline.botsort_bank(...) / TrackingPipeline.deepsort_bank(...), which pass the
+        camera count as _cameras."""
         self.streams = int(_cameras) or int(streams)
-        self.cameras, self._device, self.xcam, self.link_after_run = int(_cameras), device, None, False
-        if _cameras and tracker != "botsort":
-            raise ValueError("a camera count needs tracker='botsort' (TrackingPipeline.botsort_bank)")
+        self.cameras, self._device, self.xcam, self.link_after_run, self._bank = int(_cameras), device, None, False, None
+        if _cameras and tracker not in ("botsort", "deepsort"):
+            raise ValueError("a camera count needs TrackingPipeline.botsort_bank or TrackingPipeline.deepsort_bank")
         if int(streams) != 1 and tracker not in ("bytetrack", "ocsort"):
             raise ValueError("streams needs tracker='bytetrack' or 'ocsort'")
         if gmc and tracker != "botsort":
@@ -121,6 +122,10 @@ class TrackingPipeline:
                                        float(conf_thresh), float(iou_thresh), self.max_det, float(min_confidence),
                                        int(bool(inject)), (C.c_uint64 * 2)(lo, hi), tp)
         self._h = C.c_void_p()
+        if _cameras:                                             # a DeepSORT bank: the cameras' state is .bank's, there is no single tracker
+            L.call("aic_pipeline_create_deepsort_bank", self.yolo._h, self.reid._h, C.byref(self.params), int(_cameras), C.byref(self._h))
+            self.tracker_params, self.tracker_core = tp, None
+            return
         L.call("aic_pipeline_create", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self._h))
         th = C.c_void_p()
         L.call("aic_pipeline_tracker", self._h, C.byref(th))
@@ -143,21 +148,55 @@ class TrackingPipeline:
             raise ValueError("batch and ring_frames must be multiples of cameras")
         return cls(yolo_engine, reid_engine, frame_hw, tracker="botsort", gmc=gmc, _cameras=cameras, **kw)
 
+    @classmethod
+    def deepsort_bank(cls, yolo_engine, reid_engine, frame_hw, cameras, **kw):
+        """A DeepSORT pipeline for `cameras` cameras (aic_pipeline_create_deepsort_bank): the tracker is a DeepSORT bank of that many
+        streams (deepsort_bank.py: device association only, nn_budget > 0, max_tracks <= 512), fed from HBM -- boxes and embeddings are
+        never copied for it.  The other arguments are those of a DeepSORT pipeline; the ring and every run range are tick-major as with
+        streams=S, batch and ring_frames are multiples of `cameras`, reset_stream(s), link_cameras() and global_ids() work, `.bank`
+        exports the cameras' tracks and galleries and `.streams` is the camera count.  A camera that exhausts max_tracks fails the run
+        call (AicError, ERR_CAPACITY) and every later one until reset_stream(camera)."""
+        cameras = int(cameras)
+        if not 1 <= cameras <= 256:
+            raise ValueError("cameras must be in 1..256")
+        if "tracker" in kw or "streams" in kw:
+            raise TypeError("deepsort_bank fixes tracker and streams itself")
+        batch = int(kw.get("batch", 8))
+        if batch % cameras or int(kw.get("ring_frames") or 4 * batch) % cameras:
+            raise ValueError("batch and ring_frames must be multiples of cameras")
+        return cls(yolo_engine, reid_engine, frame_hw, tracker="deepsort", _cameras=cameras, **kw)
+
+    @property
+    def bank(self):
+        """deepsort_bank pipelines: the pipeline's DeepSORTBank (borrowed: export, export_gallery, counters, option), between run calls."""
+        if self.tracker_kind != "deepsort" or not self.cameras:
+            raise ValueError("bank needs a TrackingPipeline.deepsort_bank pipeline")
+        if self._bank is None:
+            from .deepsort_bank import DeepSORTBank
+            h = C.c_void_p()
+            L.call("aic_pipeline_deepsort_bank", self._h, C.byref(h))
+            self._bank = DeepSORTBank._borrow(h, self.tracker_params, self.streams, self._device, int(self.reid.out_dim))
+        return self._bank
+
     def reset_stream(self, s):
-        """streams=S and botsort_bank pipelines, between run calls: stream s as after creation (a camera reconnecting).  An attached
+        """streams=S, botsort_bank and deepsort_bank pipelines, between run calls: stream s as after creation (a camera reconnecting).  An attached
         CrossCamera forgets the stream's identities with it."""
         L.call("aic_pipeline_reset_stream", self._h, int(s))
         if self.xcam is not None:
             self.xcam.forget_stream(s)
 
     def link_cameras(self, xcam=None):
-        """botsort_bank pipelines, between run calls: one cross-camera pass over the bank's activated tracks (xcam.py).  The first call
-        creates and keeps a CrossCamera unless one is handed over; returns the identities merged by this call."""
-        if self.tracker_kind != "botsort" or not self.cameras:
-            raise ValueError("link_cameras needs a TrackingPipeline.botsort_bank pipeline")
+        """botsort_bank and deepsort_bank pipelines, between run calls: one cross-camera pass over the bank's activated / confirmed tracks
+        (xcam.py).  The first call creates and keeps a CrossCamera unless one is handed over (a DeepSORT bank links within its
+        max_cosine_distance); returns the identities merged by this call."""
+        if self.tracker_kind not in ("botsort", "deepsort") or not self.cameras:
+            raise ValueError("link_cameras needs a TrackingPipeline.botsort_bank or deepsort_bank pipeline")
         from .xcam import CrossCamera
         if xcam is not None:
             self.xcam = xcam
+        if self.xcam is None and self.tracker_kind == "deepsort":
+            p = self.tracker_params
+            self.xcam = CrossCamera(self.streams, p.max_tracks or 512, int(self.reid.out_dim), p.max_cosine_distance, device=self._device)
         if self.xcam is None:
             p = self.botsort_params
             self.xcam = CrossCamera(self.streams, p.max_tracks or 512, p.feature_dim or 512, device=self._device)
@@ -176,6 +215,9 @@ class TrackingPipeline:
             except Exception:
                 pass
         self._staging = []
+        if getattr(self, "_bank", None) is not None:
+            self._bank.close()                                   # borrowed: forgets the handle, destroys nothing
+            self._bank = None
         if getattr(self, "_h", None):
             L.call("aic_pipeline_destroy", self._h)
             self._h = C.c_void_p()

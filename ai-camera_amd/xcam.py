@@ -51,7 +51,7 @@ class CrossCamera:
         return self._link("aic_xcam_link_" + bank._abi[4:], bank._h)
 
     def link_pipeline(self, pipe):
-        """The pass for the BoT-SORT bank of a TrackingPipeline.botsort_bank pipeline, between run calls."""
+        """The pass for the bank of a TrackingPipeline.botsort_bank / deepsort_bank pipeline, between run calls."""
         n = C.c_int32()
         L.call("aic_pipeline_link_cameras", pipe._h, self._h, C.byref(n))
         return n.value

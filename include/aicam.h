@@ -593,6 +593,25 @@ int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipe
  * does not (AIC_ERR_INVALID, as on aic_pipeline_create_botsort). */
 int aic_pipeline_create_botsort_bank(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, const aic_botsort_params* bp,
                                      int streams, aic_pipeline** out);
+/* A DeepSORT pipeline for `streams` (1..256) cameras, fixed at creation: the tracker is a DeepSORT bank (aic_deepsort_bank_create) with
+ * p->tracker as its parameters -- its create-time rejections apply: nn_budget > 0, max_tracks <= 512 -- feature_dim being the ReID
+ * engine's output width (0, or that width), and every camera's ids starting at first_track_id.  The ring and every run range are
+ * tick-major as with the option "streams"; `batch` and `ring_frames` must be multiples of `streams`.  Stage A is the DeepSORT pipeline's
+ * (with inject = 0 the detection filter on the device and the device-sized ReID round, option "device_filter"); boxes and embeddings
+ * stay in HBM and the group's association runs in one epoch-kernel block per camera.  There is no host association chain: a frame with
+ * more than 512 detections fails the run call with AIC_ERR_CAPACITY before the group's association is launched.
+ * A camera that exhausts max_tracks stops alone: the run call delivers the group's rows -- none for that camera from its failing frame
+ * on, all of the other cameras', whose state is that after the group -- and returns AIC_ERR_CAPACITY at that launch group, naming the
+ * camera; frames of later groups of the call are not processed.  Further run calls fail with AIC_ERR_INVALID until
+ * aic_pipeline_reset_stream(p, camera).
+ * aic_pipeline_reset_stream, aic_pipeline_link_cameras, aic_pipeline_group_embeddings / _last_embeddings and the option "epoch_frames"
+ * work.  aic_pipeline_tracker, the gallery exchange and the options "device_assoc", "device_assoc_limit", "streams" and "gmc" fail with
+ * AIC_ERR_INVALID. */
+int aic_pipeline_create_deepsort_bank(aic_model* yolo, aic_model* reid, const aic_pipeline_params* p, int streams, aic_pipeline** out);
+/* The bank of a pipeline from aic_pipeline_create_deepsort_bank, owned by the pipeline (do not destroy): aic_deepsort_bank_export,
+ * _export_gallery, _counters and _option work on it between run calls -- the bank counterpart of aic_pipeline_tracker.
+ * AIC_ERR_INVALID on any other pipeline. */
+int aic_pipeline_deepsort_bank(aic_pipeline* p, aic_deepsort_bank** out);
 int aic_pipeline_destroy(aic_pipeline* p);
 /* Copy `count` u8 BGR frames into ring slots [slot, slot+count). */
 int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames_bgr, int count);
@@ -698,8 +717,8 @@ int aic_xcam_shards(aic_xcam* x, float* out);
 int aic_xcam_global_ids(aic_xcam* x, int stream, const int32_t* track_ids, int n, int64_t* global_ids);
 int aic_xcam_size(aic_xcam* x, int64_t* n_tracks, int64_t* n_identities, int64_t* n_links);
 int aic_xcam_forget_stream(aic_xcam* x, int stream);
-/* The link pass for the BoT-SORT bank of a pipeline from aic_pipeline_create_botsort_bank, between run calls; AIC_ERR_INVALID on any
- * other pipeline. */
+/* The link pass for the bank of a pipeline from aic_pipeline_create_botsort_bank or aic_pipeline_create_deepsort_bank, between run
+ * calls; AIC_ERR_INVALID on any other pipeline. */
 int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links);
 int aic_host_register(void* ptr, size_t bytes);   /* hipHostRegister: page-lock caller memory */
 int aic_host_unregister(void* ptr);
@@ -722,8 +741,8 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
  * one built on first use: own activation arena, detector workspace and streams), so that the groups of the two chunk contexts run
  * side by side -- a small group is a chain of ~60 short dependent kernels that leaves most of the chip idle; 0 = one lane.
  * Same results in every mode.
- * "epoch_frames" (a BoT-SORT pipeline only; AIC_ERR_INVALID on any other): frames per epoch launch of the tracker, 0..16 as
- * aic_botsort_option (0 = 16).  Same results either way.
+ * "epoch_frames" (BoT-SORT pipelines and DeepSORT bank pipelines only; AIC_ERR_INVALID on any other): frames per epoch launch of the
+ * tracker, 0..16 as aic_botsort_option / aic_deepsort_bank_option (0 = 16).  Same results either way.
  * "gmc" (a BoT-SORT pipeline only; AIC_ERR_INVALID on any other): 0 (default) = no camera-motion warp, 2 or 4 = the camera motion of
  * every frame is estimated on the device at that downscale (as aic_gmc_estimate_batch, the boxes being the detections handed to the
  * tracker) and warps the predicted tracks.  The gray levels are computed in the group's launch group, matching and fit run on the
@@ -732,9 +751,9 @@ int aic_pipeline_stats(aic_pipeline* p, double* issue_s, double* wait_s, double*
  * tick-major over that many camera streams, slot t * streams + s being tick t of stream s, and the tracker is a bank (one kernel block
  * per stream).  `batch` must be a multiple of it, as must slot and count of every run call; launch groups round to whole ticks. */
 int aic_pipeline_option(aic_pipeline* p, const char* key, int value);
-/* A pipeline with "streams", or one from aic_pipeline_create_botsort_bank: stream s as after create (aic_bytetrack_bank_reset), between
- * run calls; with "gmc" the camera's carried gray level is forgotten as well.  AIC_ERR_INVALID on DeepSORT and aic_pipeline_create_botsort
- * pipelines. */
+/* A pipeline with "streams", or one from aic_pipeline_create_botsort_bank or aic_pipeline_create_deepsort_bank: stream s as after create
+ * (aic_bytetrack_bank_reset), a stop cleared, between run calls; with "gmc" the camera's carried gray level is forgotten as well.
+ * AIC_ERR_INVALID on pipelines from aic_pipeline_create and aic_pipeline_create_botsort. */
 int aic_pipeline_reset_stream(aic_pipeline* p, int stream);
 /* The warps [n_frames, 6] (as aic_gmc_estimate_batch) of the most recently finished launch group of a pipeline with "gmc" set;
  * AIC_ERR_INVALID without it.  warps may be NULL; *n_frames is the group's frame count, at most cap_frames rows are written. */

@@ -6,6 +6,7 @@
     python tools/bank_bench.py botsort  [--streams 1,8,32,128,256] [--ticks 256]           # shorthand: tracker --kinds botsort
     python tools/bank_bench.py botsort-pipeline [--streams 1,8,32] [--ring 512] [--batch 256] [--steps 5] [--gmc 0]
     python tools/bank_bench.py deepsort [--streams 1,8,32] [--ticks 256]                   # shorthand: tracker --kinds deepsort
+    python tools/bank_bench.py deepsort-pipeline [--streams 1,8,32] [--ring 512] [--batch 256] [--steps 3]
     python tools/bank_bench.py xcam     [--streams 8,32,256] [--valid 128,30] [--steps 7]  # cross-camera links of a bank
 
 tracker:  S synthetic 30-person streams for `ticks` ticks, fed one tick per call and 16 ticks per call, to a bank of S streams
@@ -20,6 +21,8 @@ deepsort (a kind of `tracker`): the DeepSORT bank against S single device tracke
 botsort-pipeline: the BoT-SORT bank pipeline (TrackingPipeline.botsort_bank) on the trained detector's own detections with the seeded
           ReID engine, ring resident in HBM, against S single BoT-SORT pipelines, each created, warmed, run `steps` times on one
           camera's ring / S frames and closed before the next (the time of step i is the sum of the S pipelines' i-th runs).
+deepsort-pipeline: the DeepSORT bank pipeline (TrackingPipeline.deepsort_bank, max_tracks 64) in the shape of botsort-pipeline, against
+          S single DeepSORT pipelines one after another.
 xcam:     xcam_nearest_kernel (aic_xcam_link_shards) against gallery_nearest_kernel (aic_gallery_annotate) on the same device-resident shards,
           t_max 128, dim 512, `valid` of the 128 rows of every stream valid: kernel time from the library's HIP-event brackets (class
           "tracker": memset + nearest + finalize on one side, the one kernel on the other), two warm-up passes, `steps` timed passes in
@@ -178,6 +181,44 @@ def step_botsort_pipeline(S, ring, batch, steps, gmc):
                           singles_fps_max=ring / min(t1))), flush=True)
 
 
+def step_deepsort_pipeline(S, ring, batch, steps):
+    """frames/s over all cameras: one deepsort_bank pipeline of S cameras against S single DeepSORT pipelines one after another (ring / S
+    frames each); the detector's own detections, filtered and embedded on the device on both sides."""
+    import numpy as np
+    ypath = pkg("engine_file").ensure_trained_detector(ROOT)
+    _, rpath = pkg("engine_file").ensure_seeded_engines(ROOT)
+    TP = pkg("pipeline").TrackingPipeline
+    uniq = pkg("synthetic").Scene(seed=0, n_targets=30).render_batch(0, 64)
+    kw = dict(max_persons=64, max_tracks=64, dtype="fp16")
+
+    def timed(pipe, n):
+        pipe.run_raw(0, n)                                                  # warm-up
+        ts = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            pipe.run_raw(0, n)
+            ts.append(time.perf_counter() - t0)
+        return ts
+
+    bank = TP.deepsort_bank(ypath, rpath, (720, 1280), cameras=S, batch=batch, ring_frames=ring, **kw)
+    for i in range(0, ring, 64):                                            # every camera walks the same 64-frame clip
+        bank.upload(i, uniq[[((i + j) // S) % 64 for j in range(min(64, ring - i))]])
+    tb = timed(bank, ring)
+    c = bank.counters()
+    bank.close()
+    n1 = ring // S
+    t1 = [0.0] * steps
+    for _ in range(S):                                                      # S cameras one after another, a pipeline each
+        one = TP(ypath, rpath, (720, 1280), batch=min(batch, n1), ring_frames=n1, **kw)
+        one.upload(0, uniq[[j % 64 for j in range(n1)]])
+        t1 = [a + b for a, b in zip(t1, timed(one, n1))]
+        one.close()
+    print(json.dumps(dict(streams=S, ring=ring, batch=batch, bank_fps_median=ring / float(np.median(tb)), bank_fps_min=ring / max(tb),
+                          bank_fps_max=ring / min(tb), singles_fps_median=ring / float(np.median(t1)), singles_fps_min=ring / max(t1),
+                          singles_fps_max=ring / min(t1), bank_filter_device_groups=c["filter_device_groups"],
+                          bank_filter_host_groups=c["filter_host_groups"])), flush=True)
+
+
 def step_xcam(S, valid, steps, t_max=128, dim=512):
     import ctypes as C
     import numpy as np
@@ -245,7 +286,8 @@ def step_xcam_link(S, steps):
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "deepsort", "botsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline", "xcam", "step-xcam",
+    p.add_argument("mode", choices=("tracker", "pipeline", "botsort", "deepsort", "botsort-pipeline", "deepsort-pipeline", "step-tracker", "step-pipeline", "step-botsort-pipeline",
+                                         "step-deepsort-pipeline", "xcam", "step-xcam",
                                          "step-xcam-link"))
     p.add_argument("--valid", default="128,30")
     p.add_argument("--gmc", type=int, default=0)
@@ -264,6 +306,8 @@ def main():
         return step_pipeline(int(a.streams), int(a.reserve), a.ring, a.batch, a.steps)
     if a.mode == "step-botsort-pipeline":
         return step_botsort_pipeline(int(a.streams), a.ring, a.batch, a.steps, a.gmc)
+    if a.mode == "step-deepsort-pipeline":
+        return step_deepsort_pipeline(int(a.streams), a.ring, a.batch, a.steps)
     if a.mode == "step-xcam":
         return step_xcam(int(a.streams), int(a.valid), a.steps)
     if a.mode == "step-xcam-link":
@@ -277,6 +321,9 @@ def main():
     elif a.mode == "botsort-pipeline":
         jobs = [me + ["step-botsort-pipeline", "--streams", s, "--ring", str(a.ring), "--batch", str(a.batch), "--steps", str(a.steps),
                       "--gmc", str(a.gmc)] for s in (a.streams or "1,8,32").split(",")]
+    elif a.mode == "deepsort-pipeline":
+        jobs = [me + ["step-deepsort-pipeline", "--streams", s, "--ring", str(a.ring), "--batch", str(a.batch), "--steps", str(a.steps)]
+                for s in (a.streams or "1,8,32").split(",")]
     elif a.mode == "tracker":
         jobs = [me + ["step-tracker", "--kinds", k, "--streams", s, "--ticks", str(a.ticks)]
                 for k in a.kinds.split(",") for s in (a.streams or "1,8,32,128,256").split(",")]
