@@ -230,6 +230,13 @@ _SIGS = {
     "aic_pipeline_link_cameras": (_I, [_P, _P, _P]),
     "aic_pipeline_create_deepsort_bank": (_I, [_P, _P, _P, _I, _P]),
     "aic_pipeline_deepsort_bank": (_I, [_P, _P]),
+    "aic_zones_create": (_I, [_I, _I, _I, _I, _I, _P]),
+    "aic_zones_destroy": (_I, [_P]),
+    "aic_zones_set": (_I, [_P, _I, _I, _P, _P, _I, _P]),
+    "aic_zones_update": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "aic_zones_counters": (_I, [_P, _I, _P, _P, _P, _P]),
+    "aic_zones_reset": (_I, [_P, _I]),
+    "aic_zones_option": (_I, [_P, C.c_char_p, _I]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -60,6 +60,10 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--link_cameras", action="store_true",
                    help="--inputs with --tracker botsort or deepsort_bank only: link the cameras' identities on the device after every run call; every JSON line "
                         "gains \"global_ids\" parallel to \"tracks\" (-1 = not linked yet) and the overlay label shows the global id")
+    p.add_argument("--zones", type=str, default=None,
+                   help="JSON file {\"cameras\": [{\"zones\": [[[x, y], ...], ...], \"lines\": [[[x, y], [x, y]], ...]}, ...]} in integer pixels, one entry per "
+                        "source (a single entry serves every source): zone entries, dwell and line crossings are counted on the device and every "
+                        "JSON line gains \"zones\": {occupancy, zone_in, zone_out, line_pos, line_neg, events}")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
@@ -209,6 +213,46 @@ class _BotSortFrame:
         return self.tracker._tuples(rows, conf)
 
 
+class _ZoneLines:
+    """--zones: a ZoneCounter (zones.py) over the run's tracks and the "zones" object of every JSON line.  With a pipeline the counter is
+    attached to it (one update per run call) and the cumulative counts of a line are those after the frame's run call; frame by frame
+    (no pipeline) the tracker's tuples are handed over per frame."""
+
+    def __init__(self, path, streams, device, pipe=None):
+        from .zones import KINDS, ZoneCounter, load_zones_file
+        geometry = load_zones_file(path, streams)
+        self.kinds, self.streams, self.pipe = KINDS, streams, pipe
+        self.counter = ZoneCounter(streams=streams, device=device)
+        for s, (zs, ls) in enumerate(geometry):
+            self.counter.set_zones(s, zs, ls)
+        self._res, self._pos, self._counts = None, 0, None
+        if pipe is not None:
+            pipe.attach_zones(self.counter)
+
+    def line(self, tracks):
+        """The next frame's object, in the order the frames are yielded (tick-major over the streams)."""
+        if self.pipe is None:
+            res, s, f = self.counter.update_tuples([[tracks]]), 0, 0
+            self._counts = None
+        else:
+            res = self.pipe.zone_result
+            if res is not self._res:
+                self._res, self._pos, self._counts = res, 0, None
+            s, t = self._pos % self.streams, self._pos // self.streams
+            self._pos += 1
+            f = int(res.frames_per_stream[:s].sum()) + t
+        if self._counts is None:
+            self._counts = [self.counter.counters(k) for k in range(self.streams)]
+        out = {"occupancy": res.occupancy[f, :self.counter.n_zones[s]].tolist()}
+        out.update({k: v.tolist() for k, v in self._counts[s].items()})
+        out["events"] = [{"kind": self.kinds[int(e[0])], "index": int(e[1]), "id": int(e[2]), "cls": int(e[3]), "frame": int(e[4]), "value": int(e[5]),
+                          "anchor": [e[6] / 2, e[7] / 2]} for e in res.events[f, :min(int(res.n_events[f]), res.events.shape[1])]]
+        return out
+
+    def close(self):
+        self.counter.close()
+
+
 def main_streams(args, cv2):
     """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank /
     deepsort_bank for --tracker botsort / deepsort_bank), their frames interleaved tick by tick."""
@@ -255,6 +299,14 @@ def main_streams(args, cv2):
             outs[k] = open(str(stem) + ".jsonl", "w")
             writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None)
     pipe.link_after_run = bool(args.link_cameras)
+    zones = None
+    if args.zones:
+        try:
+            zones = _ZoneLines(args.zones, S, dev, pipe)
+        except Exception as e:
+            print(f"Error reading --zones {args.zones}: {e}")
+            pipe.close()
+            return 1
     ticks = (f for tick in zip(*(src[1] for src in sources)) for f in tick)       # the shortest source ends the run
     n, t0 = 0, time.time()
     try:
@@ -269,6 +321,8 @@ def main_streams(args, cv2):
                 line = {"frame": idx, "tracks": tracks}
                 if gids is not None:
                     line["global_ids"] = gids
+                if zones is not None:
+                    line["zones"] = zones.line(tracks)
                 outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
@@ -276,6 +330,8 @@ def main_streams(args, cv2):
         for f in outs + writers:
             if f is not None:
                 f.close()
+        if zones is not None:
+            zones.close()
         pipe.close()
     total = time.time() - t0
     print("\n--- Processing Summary ---")
@@ -358,6 +414,16 @@ def main(argv=None):
         print("--show_display ignored: no display backend (cv2) here.")
     frame_idx, total, display_fps = 0, 0.0, 0.0
     dev = config.resolve_device(args.device)
+    zones = None
+    if args.zones:
+        try:
+            zones = _ZoneLines(args.zones, 1, dev, pipe)
+        except Exception as e:
+            print(f"Error reading --zones {args.zones}: {e}")
+            for f in (out_f, writer, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     def per_frame():
         nonlocal total
@@ -399,7 +465,10 @@ def main(argv=None):
                 if writer is not None:
                     writer.write(vis)
             if out_f:
-                out_f.write(json.dumps({"frame": frame_idx - 1, "tracks": tracks}) + "\n")
+                line = {"frame": frame_idx - 1, "tracks": tracks}
+                if zones is not None:
+                    line["zones"] = zones.line(tracks)
+                out_f.write(json.dumps(line) + "\n")
             if frame_idx % 100 == 0:
                 print(f"Processed {frame_idx} frames. Current FPS: {display_fps:.2f}")
     except KeyboardInterrupt:
@@ -409,6 +478,8 @@ def main(argv=None):
             out_f.close()
         if writer is not None:
             writer.close()
+        if zones is not None:
+            zones.close()
         if pipe is not None:
             clipped = pipe.counters()["clipped_frames"]
             if clipped:

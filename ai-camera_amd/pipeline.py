@@ -208,6 +208,35 @@ class TrackingPipeline:
             raise RuntimeError("link_cameras() has not run yet")
         return self.xcam.global_ids(stream, track_ids)
 
+    _zones = zone_result = zone_events = zone_occupancy = None
+
+    def attach_zones(self, counter):
+        """A ZoneCounter (zones.py) of `.streams` streams: after every run* call the call's tracks -- all frames, all streams, ONE
+        counter.update -- go through it, and zone_events ([stream][frame] -> event rows), zone_occupancy ([stream] -> [frames, 32]),
+        zone_result (the flat ZoneResult) and zone_counters() describe that call.  The rows are the run call's host outputs (the
+        kernels read them from a staging upload, not from the tracker's HBM); the tracks returned are untouched.  None detaches."""
+        if counter is not None and counter.streams != self.streams:
+            raise ValueError(f"a counter of {counter.streams} streams for a pipeline of {self.streams}")
+        self._zones = counter
+        self.zone_result = self.zone_events = self.zone_occupancy = None
+
+    def zone_counters(self):
+        """[stream] -> dict(zone_in, zone_out, line_pos, line_neg) of the attached counter."""
+        if self._zones is None:
+            raise RuntimeError("attach_zones() has not run yet")
+        return [self._zones.counters(s) for s in range(self.streams)]
+
+    def _feed_zones(self, nt, rows, cap_events=256):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major (frame i is tick i // streams of stream i % streams)."""
+        z = self._zones
+        if z is None:
+            return
+        S, mp = self.streams, rows.shape[1]
+        res = z.update([[rows[i, :min(int(nt[i]), mp)] for i in range(s, len(nt), S)] for s in range(S)], cap_events=cap_events)
+        self.zone_result, self.zone_events = res, z.event_lists(res)
+        off = np.concatenate([[0], np.cumsum(res.frames_per_stream)])
+        self.zone_occupancy = [res.occupancy[off[s]:off[s + 1]] for s in range(S)]
+
     def close(self):
         for b in getattr(self, "_staging", []):
             try:
@@ -266,6 +295,7 @@ class TrackingPipeline:
         dl = np.zeros((count, md), np.int32) if want_dets else None
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                L.ptr(db), L.ptr(ds), L.ptr(dl))
+        self._feed_zones(nt, rows)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -285,12 +315,14 @@ class TrackingPipeline:
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                None, None, None)
+        self._feed_zones(nt[:count], rows[:count])
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
         """`passes` consecutive walks over the same ring range as ONE call (a looped clip streamed continuously)."""
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_passes", self._h, int(slot), int(count), int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
+        self._feed_zones(nt[:count], rows[:count])
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -307,6 +339,7 @@ class TrackingPipeline:
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host", self._h, L.ptr(f), int(slot), count, L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
+        self._feed_zones(nt[:count], rows[:count])
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -316,6 +349,7 @@ class TrackingPipeline:
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host_passes", self._h, L.ptr(f), int(slot), count, int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
+        self._feed_zones(nt[:count], rows[:count])
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

@@ -720,6 +720,34 @@ int aic_xcam_forget_stream(aic_xcam* x, int stream);
 /* The link pass for the bank of a pipeline from aic_pipeline_create_botsort_bank or aic_pipeline_create_deepsort_bank, between run
  * calls; AIC_ERR_INVALID on any other pipeline. */
 int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links);
+
+/* ---- zone entries, dwell and line crossings per camera (csrc/zones.hpp) -------------------------------------
+ * A tracker-agnostic stage over the rows every tracker delivers (x1 y1 x2 y2 id cls, int32).  `streams` (1..256) cameras, each with
+ * up to 32 zones (simple polygons of 3..32 integer-pixel vertices, either winding) and 32 directed lines A->B, and a table of
+ * max_tracks (1..512) slots; a track not seen for more than forget_after frames is forgotten.  anchor: 0 = the bottom centre of the
+ * box, 1 = its centre.  All arithmetic is exact (doubled coordinates in int64); tests/zones_oracle.py is the specification.
+ * Every argument error is AIC_ERR_INVALID before the device is touched: create, set, reset and option never touch it (the first
+ * update does).  Coordinates of zones and lines outside +-2^20 are rejected; a row with a box coordinate outside it is ignored.
+ * set: zone_nvert[n_zones], zone_xy = the zones' vertices one after another (x, y), line_xy[n_lines][4] = ax ay bx by; between
+ * updates; the stream's state and counters start over; AIC_ERR_INVALID for a stopped stream (reset it first).
+ * update: stream-major as the bank updates: frames_per_stream[streams], counts[F] rows per frame (F = the sum), rows6 [sum of
+ * counts, 6] in host or device memory (mem: AIC_HOST / AIC_DEVICE).  A frame of more than 512 rows rejects the call with
+ * AIC_ERR_CAPACITY before anything is staged.  Outputs (host): n_events[F] true counts, events[F, cap_events, 8] = kind (1 ENTER,
+ * 2 EXIT, 3 LOST, 4 CROSS), zone / line index, track id, cls, frame, value (dwell in frames, or +-1 = the side of A->B the track ends
+ * on), doubled anchor x, y; truncated at cap_events (0..65536), zero-filled; occupancy[F, 32].  A stream that needs more than
+ * max_tracks slots stops alone: that frame and its later ones deliver nothing, status[streams] (may be NULL) gets 0 or
+ * AIC_ERR_CAPACITY, the other streams finish, and later calls deliver nothing for it until aic_zones_reset.
+ * counters: cumulative int64 [32] each (any may be NULL); they never depend on cap_events.
+ * option "frames_per_launch": 0 (default) = a call's frames in one launch, k = at most k frames of a stream per launch; same results. */
+typedef struct aic_zones aic_zones;
+int aic_zones_create(int device, int streams, int max_tracks, int forget_after, int anchor, aic_zones** out);
+int aic_zones_destroy(aic_zones* z);
+int aic_zones_set(aic_zones* z, int stream, int n_zones, const int32_t* zone_nvert, const int32_t* zone_xy, int n_lines, const int32_t* line_xy);
+int aic_zones_update(aic_zones* z, const int32_t* frames_per_stream, const int32_t* counts, const int32_t* rows6, int mem, int cap_events,
+                     int32_t* n_events, int32_t* events, int32_t* occupancy, int32_t* status);
+int aic_zones_counters(aic_zones* z, int stream, int64_t* zone_in, int64_t* zone_out, int64_t* line_pos, int64_t* line_neg);
+int aic_zones_reset(aic_zones* z, int stream);
+int aic_zones_option(aic_zones* z, const char* key, int value);
 int aic_host_register(void* ptr, size_t bytes);   /* hipHostRegister: page-lock caller memory */
 int aic_host_unregister(void* ptr);
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out);
