@@ -33,7 +33,7 @@ __global__ void sppf_pool_kernel(const EltArgs a) {
     const T* src = reinterpret_cast<const T*>(a.src);
     T* dst = reinterpret_cast<T*>(a.dst);
     V m5, m9, m13;
-    const T lowest = (T)(-65504.0f);
+    const T lowest = (T)(-__builtin_huge_valf());       // -inf of the element type: an fp32 window may lie wholly below -65504
 #pragma unroll
     for (int e = 0; e < VN; ++e) m5[e] = m9[e] = m13[e] = lowest;
     for (int dy = -6; dy <= 6; ++dy) {
@@ -156,7 +156,7 @@ __global__ void maxpool3s2_kernel(const EltArgs a) {
     T* dst = reinterpret_cast<T*>(a.dst);
     V m;
 #pragma unroll
-    for (int e = 0; e < VN; ++e) m[e] = (T)(-65504.0f);
+    for (int e = 0; e < VN; ++e) m[e] = (T)(-__builtin_huge_valf());      // -inf of the element type (see sppf_pool_kernel)
     for (int dy = -1; dy <= 1; ++dy) {
         const int yy = 2 * y + dy;
         if (yy < 0 || yy >= a.h) continue;

@@ -227,13 +227,19 @@ def test_embed_boxes_fused_crop_equals_crop_kernel_plus_stem(gpu, engines, frame
     extra = np.array([[-20.5, -3.2, 40.9, 90.1], [1270.2, 700.7, 1300, 760], [100, 100, 100.9, 180], [50, 60, 178, 316],
                       [0, 0, 1280, 720], [640.99, 10.01, 641.99, 11.5], [300, 200, 290, 260], [5, 5, 69, 133]], np.float32)
     boxes = np.concatenate([sc.detections(3)[0], extra])
+    g = ef.read_engine(engines[1])
+    pool = next(o for o in g.ops if o[0] == ef.OP_MAXPOOL3S2)                # the fused stem's output: the pooled tensor
+    assert g.buffers[pool[4]][:3] == (64, 32, 64) and len(boxes) <= 64
     eng = HipEngine(engines[1], dtype="fp16", max_items=64, warm_up=False)
     emb, valid = eng.embed_boxes_np(frame, boxes)
+    pooled = eng.read_buffer_np(pool[4], len(boxes))
     crops, cvalid = ip.crops_from_boxes(frame, boxes)
     ref = eng.reid_infer_np(crops)
+    pooled_ref = eng.read_buffer_np(pool[4], len(boxes))
     eng.close()
     assert valid.tolist() == cvalid.tolist() and 0 < valid.sum() < len(boxes)
     ok = valid.astype(bool)
+    assert pooled[ok].any() and np.array_equal(pooled[ok], pooled_ref[ok])   # the stem's own tensor, not only what seven more stages leave of it
     assert np.array_equal(emb[ok], ref[ok])
 
 
