@@ -3,6 +3,7 @@
 // project's layers.  The launchers (kernels_conv*.hip) map a ConvPlan to its template instantiation and launch it.
 #pragma once
 #include "assoc_host.hpp"
+#include "row_band.hpp"
 
 namespace aic {
 
@@ -68,6 +69,12 @@ struct ConvArgs {
     // boxes are the bits decode_kernel would have produced.  Same anchor indexing as t_max; t_w / t_stride: the level's map width and
     // stride.  t_box == NULL: none.
     float* t_box; int t_w, t_stride;
+    // ---- optional ROW WINDOW (row_band.hpp): the launch computes output rows [win_y0, win_y0 + win_rows) only -- in whole tiles from a
+    // clamped origin (tile_window) or exactly, by kernel -- and leaves every other row of y as it is.  Bounds checks and zero padding
+    // stay those of the full map: the window's edge rows read their real neighbours.  Only the direct kernels of YOLOv8n's first stages
+    // take it (conv3x3_c16, conv3x3_c32s2_tail, conv3x3_patch, conv1x1_stream, and c2f16_fused through its cv2's arguments); plan_conv
+    // does not look at it.  win_rows == 0: the full map.
+    int win_y0, win_rows;
 };
 
 // CUs the persistent (one-block-per-CU) conv kernels size their grids for: all of them, minus the one the association epoch
@@ -106,6 +113,21 @@ struct ConvPlan {
     int run = 1;                          // PpPatch, SpPatch, S2Patch: tiles per block
     long blocks = 0;                      // PpPatch, SpPatch, S2Patch, C64Resident: grid size
 };
+
+// Row windows (ConvArgs::win_rows): the tile rows a form's launch walks its window in, and whether it stores exactly the window's rows
+// (`exact`) or whole tiles.  0: the form has no window and always computes the full map.  The launchers assert these against their
+// kernels' tiles; the window planner (Model::row_plan) asks here and nowhere else.
+constexpr int kWinTileC16 = 8, kWinTileC32s2Tail = 8, kWinTileC2f16 = 8;
+inline int conv_window_tile(const ConvPlan& p, bool& exact) {
+    exact = p.form == ConvForm::Patch || p.form == ConvForm::Stream1x1;
+    switch (p.form) {
+        case ConvForm::C16: return kWinTileC16;
+        case ConvForm::C32s2Tail: return kWinTileC32s2Tail;
+        case ConvForm::Patch: return p.th;          // conv3x3_patch_kernel drops the rows of its tiles outside the window
+        case ConvForm::Stream1x1: return 1;         // conv1x1_stream_kernel walks the window's pixels of every image
+        default: return 0;
+    }
+}
 
 // The K order of a layer (ConvArgs::k_order): a property of its SHAPE, never of the batch, so that every kernel any batch size may
 // select accumulates in the same order and embeddings do not depend on the batch.

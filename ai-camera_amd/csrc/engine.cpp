@@ -534,7 +534,114 @@ void Model::run(int n, hipStream_t s) {
     AIC_REQUIRE(n >= 0 && n <= max_items, AIC_ERR_CAPACITY, "batch exceeds the engine's max_items");
     if (n == 0) return;
     cls_reduced = box_decoded = 0;
+    rb_slots = 0;                                   // whoever filled input() wrote anything: no row of any map is known any more
+    std::fill(rb_ran.begin(), rb_ran.end(), 0);
     run_ops(0, n, s);
+}
+
+// ---- row bands (engine.hpp, row_band.hpp)
+std::vector<RowBand> Model::plan_bands(const LetterboxGeom& g) const {
+    std::vector<RbOp> ro(ops.size());
+    std::vector<int> bh(bufs.size());
+    for (size_t i = 0; i < bufs.size(); ++i) bh[i] = bufs[i].h;
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const OpDesc& o = ops[i];
+        const int* v = o.v;
+        RbOp& r = ro[i];
+        r.src = v[1], r.src_c0 = v[2], r.src_cn = v[0] == OP_CONV && v[3] == 3 ? 8 : v[3];
+        r.dst = v[4], r.dst_c0 = v[5], r.dst_cn = v[0] == OP_SPPF_POOL ? 3 * v[6] : v[6];      // (the SPPF pool writes its three copies side by side)
+        r.conv = dtype == AIC_F16 && v[0] == OP_CONV && (o.fuse == 0 || o.fuse == 3) && o.xs_buf < 0 && v[16] == 0 && v[7] == v[8] &&
+                 !bufs[v[1]].f32 && !bufs[v[4]].f32;
+        r.k = v[7], r.stride = v[9], r.pad = v[10];
+        if (v[0] == OP_CONV && v[14]) r.res = v[12], r.res_c0 = v[13];
+    }
+    const bool side_pad = g.left != 0 || g.unpad_w != g.out_w || g.out_h != in_h;
+    return plan_row_bands(ro, bh, g.top, g.unpad_h, side_pad);
+}
+
+const Model::RowPlan& Model::row_plan(const LetterboxGeom& g, int n) {
+    for (const RowPlan& p : row_plans)
+        if (p.top == g.top && p.unpad_h == g.unpad_h && p.n == n && p.cu == conv_cu_budget() && p.n_dev == (n_items_dev != nullptr)) return p;
+    RowPlan p;
+    p.top = g.top, p.unpad_h = g.unpad_h, p.n = n, p.cu = conv_cu_budget(), p.n_dev = n_items_dev != nullptr;
+    const size_t no = ops.size();
+    p.bands = plan_bands(g);
+    p.win.assign(no, RowWindow{}), p.n_ops.assign(no, 0), p.frac.assign(no, 1.f), p.covered.assign(no, 0), p.th.assign(no, 0), p.exact.assign(no, 0);
+    // the launches of run_range(1, end) behind the fused stem, as the window planner sees them
+    std::vector<RbStep> steps;
+    std::vector<size_t> first;
+    std::vector<std::vector<int>> step_sig;                           // per step: what it launches (kind, ops, the conv plan)
+    constexpr int all_ch = 1 << 30;
+    auto read_all = [&](int buf) { RbRead r; r.buf = buf, r.c0 = 0, r.cn = all_ch, r.all = true; return r; };
+    {
+        RbStep st;                                                    // the stem: reads the frames
+        st.op = 0, st.dst = ops[0].v[4], st.dst_c0 = ops[0].v[5], st.dst_cn = ops[0].v[6], st.Ho = bufs[ops[0].v[4]].h, st.th = 8;
+        steps.push_back(st), first.push_back(0), step_sig.push_back({0, 1});
+        p.n_ops[0] = 1;
+    }
+    for (size_t oi = 1; oi < no; ++oi) {
+        const OpDesc& o = ops[oi];
+        if (o.fuse == 2) continue;
+        RbStep st;
+        int n_ops = 1;
+        std::vector<int> sg{(int)oi, -1};
+        if (o.v[0] != OP_CONV || o.fuse == 1) {
+            st.op = (int)oi, st.dst = o.v[4], st.dst_c0 = o.v[5], st.dst_cn = o.v[0] == OP_SPPF_POOL ? 3 * o.v[6] : o.v[6], st.Ho = bufs[o.v[4]].h;
+            st.reads.push_back(read_all(o.v[1]));
+        } else {
+            const ConvStep cs = conv_step(oi, no, n);
+            n_ops = cs.n_ops;
+            sg = {(int)oi, cs.kind, cs.n_ops, cs.ipb};
+            const OpDesc& last = ops[oi + n_ops - 1];
+            st.op = (int)(oi + n_ops - 1), st.dst = last.v[4], st.dst_c0 = last.v[5], st.dst_cn = last.v[6], st.Ho = bufs[last.v[4]].h;
+            const ConvArgs& a = cs.a[0];
+            RbRead r;
+            r.buf = o.v[1], r.c0 = o.v[2], r.cn = a.Cin, r.stride = a.stride, r.halo_lo = a.pad, r.halo_hi = a.KH - 1 - a.pad;
+            if (cs.kind == ConvStep::C2f16) {
+                st.th = kWinTileC2f16, r.halo_lo = r.halo_hi = 2;     // cv1's input under the two 3x3 convs of the bottleneck
+            } else if (cs.kind == ConvStep::Single || cs.kind == ConvStep::Tail) {
+                ConvArgs b = a;
+                const ConvPlan cp = plan_conv_launch(dtype, b, conv_cu_budget());
+                st.th = conv_window_tile(cp, st.exact);
+                if (a.xs || a.x2 || a.n_dev || a.out_f32) st.th = 0;
+                for (int f : {(int)cp.form, cp.mt, cp.nt, cp.wm, cp.wn, cp.nstage, cp.th, cp.tw, cp.cpp, cp.pitch, cp.kord, cp.g, (int)cp.tail, (int)cp.x2, b.k_order}) sg.push_back(f);
+            }
+            if (st.th == 0) r.all = true;
+            st.reads.push_back(r);
+            for (int k = 0; k < n_ops; ++k) {                         // residuals and further sources from outside the launch
+                const OpDesc& q = ops[oi + k];
+                if (q.v[14] && cs.kind != ConvStep::C2f16) { RbRead rr; rr.buf = q.v[12], rr.c0 = q.v[13], rr.cn = q.v[6], rr.all = st.th == 0; st.reads.push_back(rr); }
+                if (q.v[16]) st.reads.push_back(read_all(q.v[16] - 1));
+                if (q.xs_buf >= 0) st.reads.push_back(read_all(q.xs_buf));
+            }
+        }
+        steps.push_back(st), first.push_back(oi), step_sig.push_back(sg);
+        p.n_ops[oi] = n_ops;
+        oi += n_ops - 1;
+    }
+    const std::vector<RowWindow> w = plan_row_windows(steps, p.bands);
+    size_t last_win = 0;
+    for (size_t k = 0; k < steps.size(); ++k)
+        if (w[k].rows) last_win = k;
+    // the rows a windowed run leaves alone were computed by the kernels of the run that put them there, from rows the kernels in front of
+    // them computed: the signature names every launch up to the last windowed one (kernels of one layer may round differently)
+    for (size_t k = 0; k <= last_win && k < steps.size(); ++k) {
+        p.sig.insert(p.sig.end(), step_sig[k].begin(), step_sig[k].end());
+        p.sig.push_back(w[k].y0), p.sig.push_back(w[k].rows);
+    }
+    for (size_t k = 0; k < steps.size(); ++k) {
+        if (w[k].rows == 0) continue;
+        const RbStep& st = steps[k];
+        const TileWindow t = tile_window(w[k].y0, w[k].rows, st.th, st.Ho);
+        p.win[first[k]] = w[k];
+        p.th[first[k]] = st.th, p.exact[first[k]] = st.exact;
+        p.frac[first[k]] = (float)(st.exact ? w[k].rows : t.tiles * st.th) / (float)st.Ho;
+        for (int j = 0; j < p.n_ops[first[k]]; ++j) p.covered[first[k] + j] = 1;
+        p.any = true;
+    }
+    if (row_plans.size() >= 8) row_plans.erase(row_plans.begin());
+    row_plans.push_back(std::move(p));
+    return row_plans.back();
 }
 
 void Model::run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hipStream_t s) {
@@ -543,18 +650,45 @@ void Model::run_frames(const uint8_t* frames, int n, const LetterboxGeom& g, hip
     const int* v = ops[0].v;
     const bool stem = kind == KIND_YOLO && dtype == AIC_F16 && ops[0].fuse == 0 && v[0] == OP_CONV && v[1] == 0 && v[2] == 0 &&
                       v[3] == 3 && v[6] == 16 && v[7] == 3 && v[8] == 3 && v[9] == 2 && v[10] == 1 && v[11] == 1 && v[14] == 0;
+    rb_ran.assign(ops.size(), 0), rb_ran_win.assign(ops.size(), RowWindow{});
     if (stem) {
         const ConvWeights& w = weights[v[15]];
         const BufDesc& db = bufs[v[4]];
+        // AICAM_NO_ROW_BAND=1: every launch computes its full map, as before the row bands (A/B runs, the reference of the bit-equality tests)
+        static const bool rb_on = getenv("AICAM_NO_ROW_BAND") == nullptr;
+        // (launches of a few frames may run their heads on side streams in pieces of the op list: no windows there)
+        const bool plain = !(side_ok && !side_heads.empty() && n <= side_max_items);
+        const RowPlan* rp = rb_on && plain && db.h % 8 == 0 ? &row_plan(g, n) : nullptr;
+        if (rp && !rp->any) rp = nullptr;
+        const bool windowed = rp && rb_slots >= n && rb_top == rp->top && rb_unpad == rp->unpad_h && rb_sig == rp->sig;
+        const int slots = rb_slots;
+        rb_slots = 0;                               // until this call is through: a failed launch leaves nothing known
+        const RowWindow w0 = windowed ? rp->win[0] : RowWindow{};
+        const double share = windowed ? rp->frac[0] : 1.0;
         bool ok;
         {
-            Prof pr(*dev, PROF_LETTERBOX, s, 2.0 * n * db.h * db.w * 16.0 * 27.0,
-                    (double)n * ((double)g.src_h * g.src_w * 3 + (double)db.h * db.w * 32.0));
-            ok = launch_yolo_stem_fused(frames, n, g, w.w.p, w.bias.p, w.Kp, db.p, db.c, v[5], db.h, db.w, s);
+            Prof pr(*dev, PROF_LETTERBOX, s, 2.0 * n * db.h * db.w * 16.0 * 27.0 * share,
+                    (double)n * ((double)g.src_h * g.src_w * 3 + (double)db.h * db.w * 32.0 * share));
+            ok = launch_yolo_stem_fused(frames, n, g, w.w.p, w.bias.p, w.Kp, db.p, db.c, v[5], db.h, db.w, s, w0.y0, w0.rows);
         }
         if (ok) {
             cls_reduced = box_decoded = 0;
-            run_ops(1, n, s);
+            rb_now = windowed ? rp : nullptr;
+            try {
+                run_ops(1, n, s);
+            } catch (...) {
+                rb_now = nullptr;
+                throw;
+            }
+            rb_now = nullptr;
+            if (windowed) {
+                rb_slots = slots;
+                rb_ran = rp->covered, rb_ran_win = rp->win;
+                for (size_t i = 0; i < ops.size(); ++i)           // (the query answers per op: a covered op has its launch's window)
+                    if (rp->covered[i] && rp->n_ops[i] == 0 && i > 0) rb_ran_win[i] = rb_ran_win[i - 1];
+            } else if (rp) {
+                rb_top = rp->top, rb_unpad = rp->unpad_h, rb_slots = n, rb_sig = rp->sig;
+            }
             return;
         }
     }
@@ -698,8 +832,21 @@ void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
         }
         if (v[0] == OP_CONV) {
             if (prof_conv && !span_open) { dev->prof_begin(PROF_CONV, s, 0, 0); span_open = true; }
-            const ConvStep st = conv_step(oi, op1, n);
-            if (prof_conv) dev->prof_account(PROF_CONV, st.fl, st.by);
+            ConvStep st = conv_step(oi, op1, n);
+            double share = 1.0;
+            if (rb_now && rb_now->win[oi].rows > 0) {                   // a row window (engine.hpp): planned for exactly this launch
+                AIC_REQUIRE(rb_now->n_ops[oi] == st.n_ops && rb_now->n == n, AIC_ERR_INVALID, "row window planned for another launch");
+                if (st.kind == ConvStep::Single || st.kind == ConvStep::Tail) {   // ... and for the kernel form launch_conv_igemm is about to select
+                    ConvArgs b = st.a[0];
+                    bool exact = false;
+                    const int th = conv_window_tile(plan_conv_launch(dtype, b, conv_cu_budget()), exact);
+                    AIC_REQUIRE(th > 0 && th == rb_now->th[oi] && exact == (rb_now->exact[oi] != 0), AIC_ERR_INVALID, "row window planned for another kernel form");
+                }
+                ConvArgs& wa = st.a[st.kind == ConvStep::C2f16 ? 3 : 0];
+                wa.win_y0 = rb_now->win[oi].y0, wa.win_rows = rb_now->win[oi].rows;
+                share = rb_now->frac[oi];
+            }
+            if (prof_conv) dev->prof_account(PROF_CONV, st.fl * share, st.by * share);   // what the launch executes, not the layer's
             switch (st.kind) {
                 case ConvStep::C2f16: launch_c2f16(st.a[0], st.a[1], st.a[2], st.a[3], s); break;
                 case ConvStep::C64Block: launch_c64_block(st.a[0], st.a[1], st.ipb, s); break;
@@ -887,6 +1034,21 @@ int aic_model_conv_plan(aic_model* mm, int op, int n, int32_t* out) {
             }
             return;
         }
+    });
+}
+
+int aic_model_row_band(aic_model* mm, int op, int src_h, int src_w, int32_t* out) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && out && op >= 0 && op < (int)mm->m.ops.size() && src_h > 0 && src_w > 0, AIC_ERR_INVALID, "bad argument");
+        const Model& m = mm->m;
+        const LetterboxGeom g = letterbox_geometry(src_h, src_w, m.in_h, m.in_w);
+        const RowBand b = m.plan_bands(g)[op];
+        const int h = m.bufs[m.ops[op].v[4]].h;
+        out[0] = b.full ? 1 : 0, out[1] = b.full ? 0 : b.lo, out[2] = b.full ? h - 1 : b.hi, out[3] = h;
+        const bool ran = op < (int)m.rb_ran.size() && m.rb_ran[op];
+        out[4] = ran ? 1 : 0;
+        out[5] = ran ? m.rb_ran_win[op].y0 : 0, out[6] = ran ? m.rb_ran_win[op].rows : 0;
+        out[7] = m.rb_slots;
     });
 }
 

@@ -104,6 +104,36 @@ struct Model {
     int side_max_items = 2;                     // aic_model_option-free: AICAM_SIDE_HEADS=0 turns the schedule off, =N moves the item bound
     void plan_side_heads();
     void run_ops(size_t op0, int n, hipStream_t s);     // ops [op0, end) of the whole batch: the side-head schedule where it applies, else run_range
+    // ---- row bands (row_band.hpp): run_frames on a geometry whose picture has flat borders above and below launches, for the ops in front
+    // of the network whose kernels take a row window (ConvArgs::win_rows), only the tile rows that can depend on the frame.  The rows around
+    // them are the same for every frame of that geometry: a full run leaves them in the activation buffers (one storage per buffer, never
+    // aliased) and the windowed runs behind it leave them alone.
+    struct RowPlan {
+        int top = 0, unpad_h = 0, n = 0;          // the geometry key (pictures as wide as the input only) and the launch size planned for
+        int cu = 0;                               // ... and what else the conv plans depend on: the CU budget of the persistent grids,
+        bool n_dev = false;                       // a device-side item count
+        std::vector<RowBand> bands;               // per op
+        std::vector<RowWindow> win;               // per op: the window of the launch that STARTS at this op (rows == 0: the full map)
+        std::vector<int> n_ops;                   // per op: ops that launch covers (0: no launch starts here)
+        std::vector<float> frac;                  // per op: the share of the map's rows that launch computes
+        std::vector<char> covered;                // per op: a windowed launch covers it
+        std::vector<int> th;                      // per op: the tile rows the window was planned on (conv_window_tile) ...
+        std::vector<char> exact;                  // ... and whether the kernel stores exact rows: run_range checks both against the form it launches
+        std::vector<int> sig;                     // the launches up to the last windowed one: kernels and windows
+        bool any = false;
+    };
+    std::vector<RowPlan> row_plans;               // the last few (geometry, launch size) pairs
+    std::vector<RowBand> plan_bands(const LetterboxGeom& g) const;
+    const RowPlan& row_plan(const LetterboxGeom& g, int n);
+    // The state: the constant rows of geometry (rb_top, rb_unpad) are in place in item slots [0, rb_slots), left there by the launches
+    // rb_sig.  A call with another geometry, other launches (another launch size may select other kernels: without a window form, or
+    // with another rounding) or more items runs full and records itself; run(), the unfused letterbox path and a failed launch leave
+    // rb_slots = 0.
+    int rb_top = -1, rb_unpad = -1, rb_slots = 0;
+    std::vector<int> rb_sig;
+    const RowPlan* rb_now = nullptr;              // set around run_ops() by run_frames: the windows in force
+    std::vector<char> rb_ran;                     // per op: the last run_frames ran it windowed
+    std::vector<RowWindow> rb_ran_win;            // per op: the window it had (the launch's)
     ~Model();
     // YOLO post-processing on the buffers left by run()
     DetArgs det_args(int batch, float conf, float iou, int max_det, const LetterboxGeom* g);

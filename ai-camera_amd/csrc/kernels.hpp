@@ -16,7 +16,7 @@ void launch_c2f16(const ConvArgs& cv1, const ConvArgs& m_cv1, const ConvArgs& m_
 // letterbox + conv 3x3/2 (3->16) + SiLU fused (fp16 YOLOv8 stem); false = geometry not supported, nothing launched
 struct LetterboxGeom;
 bool launch_yolo_stem_fused(const uint8_t* frames, int n, const LetterboxGeom& g, const void* w, const float* bias, int Kp, void* y,
-                            int y_cs, int y_coff, int Ho, int Wo, hipStream_t s);
+                            int y_cs, int y_coff, int Ho, int Wo, hipStream_t s, int win_y0 = 0, int win_rows = 0);   // win_*: ConvArgs::win_y0 / win_rows
 
 // conv 3x3/1 (3->64) + ReLU + max-pool 3x3/2 fused (fp16, W == 64, H % 8 == 0): ReID stem
 // in_stride: halves per input pixel, 8 (NHWC8) or 4 (NHWC4 = RGB0; only where reid_stem2_usable(H, W))

@@ -58,14 +58,14 @@ struct C2fArgs {
     int x_cs, x_coff, y_cs, y_coff, H, W, n_img, xcd_map;
 };
 
-__global__ __launch_bounds__(256) void c2f16_fused_kernel(const C2fArgs a, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(256) void c2f16_fused_kernel(const C2fArgs a, int tiles_x, int tiles_y, int oy_org) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, r = lane & 15, q = lane >> 4;
     int bx = xcd_tile((int)blockIdx.x, (int)gridDim.x, a.xcd_map);
     const int tx = bx % tiles_x; bx /= tiles_x;
     const int ty = bx % tiles_y;
     const int img = bx / tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int oy0 = oy_org + ty * TH, ox0 = tx * TW;          // (a row window, ConvArgs::win_rows of cv2: tiles_y tile rows from output row oy_org)
     const half_t* xg = a.x + (size_t)img * a.H * a.W * a.x_cs + a.x_coff;
 
     // ---- S1: input tile with halo 2 -> LDS (four 16-byte channel groups per pixel)
@@ -212,6 +212,7 @@ __global__ __launch_bounds__(256) void c2f16_fused_kernel(const C2fArgs a, int t
 // cv1 -> m.cv1 -> m.cv2 (+ shortcut) -> cv2 of a C2f with 16-channel halves, wired as plan_c2f16 (conv_plan.cpp) checks
 void launch_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, const ConvArgs& c2, hipStream_t s) {
     static_assert(TH == 8 && TW == 32, "plan_c2f16 checks the map against 8 x 32 tiles");
+    static_assert(TH == kWinTileC2f16, "the window planner's tile rows");
     const int H = c1.H, W = c1.W;
     C2fArgs a{};
     a.x = reinterpret_cast<const half_t*>(c1.x), a.y = reinterpret_cast<half_t*>(c2.y);
@@ -221,8 +222,9 @@ void launch_c2f16(const ConvArgs& c1, const ConvArgs& m1, const ConvArgs& m2, co
     a.x_cs = c1.x_cs, a.x_coff = c1.x_coff, a.y_cs = c2.y_cs, a.y_coff = c2.y_coff, a.H = H, a.W = W;
     a.n_img = c1.M / (H * W), a.xcd_map = 1;
     set_lds_limit(c2f16_fused_kernel, LDS_BYTES);
-    const int tiles_x = W / TW, tiles_y = H / TH;
-    hipLaunchKernelGGL(c2f16_fused_kernel, dim3(a.n_img * tiles_x * tiles_y), dim3(256), (size_t)LDS_BYTES, s, a, tiles_x, tiles_y);
+    const TileWindow win = tile_window(c2.win_y0, c2.win_rows, TH, H);          // the block's output is cv2's: its window is the launch's
+    const int tiles_x = W / TW, tiles_y = win.tiles;
+    hipLaunchKernelGGL(c2f16_fused_kernel, dim3(a.n_img * tiles_x * tiles_y), dim3(256), (size_t)LDS_BYTES, s, a, tiles_x, tiles_y, win.origin);
     KCHECK();
 }
 

@@ -15,7 +15,7 @@ namespace aic {
 // LDS entry (row, column parity p, channel half h, column c2) = 16 bytes; for stride 2 even and odd input columns
 // are kept apart so that 16 consecutive output pixels read 16 consecutive entries (conflict-free).
 template <int COUT, int S>
-__global__ __launch_bounds__(256) void conv3x3_c16_kernel(const ConvArgs a, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(256) void conv3x3_c16_kernel(const ConvArgs a, int tiles_x, int tiles_y, int oy_org) {
     constexpr int TH = 8, TW = 32, NCT = COUT / 16;
     constexpr int PR = (TH - 1) * S + 3, PC = (TW - 1) * S + 3;
     constexpr int NPAR = S, PCP = (PC + NPAR - 1) / NPAR;
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void conv3x3_c16_kernel(const ConvArgs a, int 
     const int tx = bx % tiles_x; bx /= tiles_x;
     const int ty = bx % tiles_y;
     const int img = bx / tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int oy0 = oy_org + ty * TH, ox0 = tx * TW;          // (a row window, ConvArgs::win_rows: tiles_y tile rows from output row oy_org)
     const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
     const half_t* xg = reinterpret_cast<const half_t*>(a.x) + (size_t)img * a.H * a.W * a.x_cs + a.x_coff;
 
@@ -123,8 +123,10 @@ template <int COUT, int S>
 static void launch_c16(const ConvArgs& a, hipStream_t s) {
     constexpr int PR = 7 * S + 3, PC = 31 * S + 3, PCP = (PC + S - 1) / S;
     constexpr size_t lds = (size_t)PR * S * 2 * PCP * 16;
-    const int tiles_x = a.Wo / 32, tiles_y = a.Ho / 8, n_img = a.M / (a.Ho * a.Wo);
-    hipLaunchKernelGGL((conv3x3_c16_kernel<COUT, S>), dim3(n_img * tiles_x * tiles_y), dim3(256), lds, s, a, tiles_x, tiles_y);
+    static_assert(kWinTileC16 == 8, "conv3x3_c16_kernel's tiles are 8 rows");
+    const TileWindow win = tile_window(a.win_y0, a.win_rows, kWinTileC16, a.Ho);
+    const int tiles_x = a.Wo / 32, tiles_y = win.tiles, n_img = a.M / (a.Ho * a.Wo);
+    hipLaunchKernelGGL((conv3x3_c16_kernel<COUT, S>), dim3(n_img * tiles_x * tiles_y), dim3(256), lds, s, a, tiles_x, tiles_y, win.origin);
     KCHECK();
 }
 
@@ -153,7 +155,7 @@ void launch_conv_c16(const ConvArgs& a, const ConvPlan&, hipStream_t s) {
 //  * NW waves per block (2: 8 x 16 outputs, a 17 x 33 patch, four blocks per CU; 4: 16 x 16 outputs, two blocks per CU): what a block
 //    spends its time on is latency -- the patch, the weights of each pass, the tail's weights -- and the CU hides it behind OTHER blocks.
 template <int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_c32s2_tail_kernel(const ConvArgs a, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_c32s2_tail_kernel(const ConvArgs a, int tiles_x, int tiles_y, int oy_org) {
     constexpr int TH = 4 * NW, TW = 16, PRH = 2 * TH + 1, PRW = 2 * TW + 1, PCP = 18, ROWB = 2 * PCP * 64;   // patch rows x columns; columns per parity (padded); bytes per patch row
     constexpr int NTHR = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int tx = bx % tiles_x; bx /= tiles_x;
     const int ty = bx % tiles_y;
     const int img = bx / tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int oy0 = oy_org + ty * TH, ox0 = tx * TW;          // (a row window, ConvArgs::win_rows: tiles_y tile rows from output row oy_org)
     const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;
     const half_t* xg = reinterpret_cast<const half_t*>(a.x) + (size_t)img * a.H * a.W * a.x_cs + a.x_coff;
     const half_t* wg = reinterpret_cast<const half_t*>(a.w);
@@ -242,13 +244,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 template <int NW>
 static void launch_c32s2_tail(const ConvArgs& a, hipStream_t s) {
     constexpr size_t lds = (size_t)(8 * NW + 1) * 2 * 18 * 64;
-    const int tiles_x = a.Wo / 16, tiles_y = a.Ho / (4 * NW), n_img = a.M / (a.Ho * a.Wo);
+    const TileWindow win = tile_window(a.win_y0, a.win_rows, 4 * NW, a.Ho);
+    const int tiles_x = a.Wo / 16, tiles_y = win.tiles, n_img = a.M / (a.Ho * a.Wo);
     set_lds_limit(conv3x3_c32s2_tail_kernel<NW>, lds);
-    hipLaunchKernelGGL(conv3x3_c32s2_tail_kernel<NW>, dim3((unsigned)(n_img * tiles_x * tiles_y)), dim3(64 * NW), lds, s, a, tiles_x, tiles_y);
+    hipLaunchKernelGGL(conv3x3_c32s2_tail_kernel<NW>, dim3((unsigned)(n_img * tiles_x * tiles_y)), dim3(64 * NW), lds, s, a, tiles_x, tiles_y, win.origin);
     KCHECK();
 }
 
-void launch_conv_c32s2_tail(const ConvArgs& a, const ConvPlan&, hipStream_t s) { launch_c32s2_tail<2>(a, s); }
+void launch_conv_c32s2_tail(const ConvArgs& a, const ConvPlan&, hipStream_t s) {
+    static_assert(kWinTileC32s2Tail == 4 * 2, "conv3x3_c32s2_tail_kernel<2>'s tiles are 8 rows");
+    launch_c32s2_tail<2>(a, s);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Streaming 1x1 conv for 64 output channels and at most 128 input channels, fp16 (YOLOv8n's `4.c2f.cv2` and `15.c2f.cv2` at large batch:
@@ -260,7 +266,7 @@ void launch_conv_c32s2_tail(const ConvArgs& a, const ConvPlan&, hipStream_t s) {
 //  registers; the 1 024 launched are 1.33 rounds): 4.c2f.cv2 347 / 335 us against 339, 15.c2f.cv2 290 / 267 against 252.  It is not
 //  bytes in flight that this kernel waits for.  Not kept.)
 template <int KS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv1x1_stream_kernel(const ConvArgs a, int n_tiles) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv1x1_stream_kernel(const ConvArgs a, int n_tiles, int tpi) {
     const int t = threadIdx.x, lane = t & 63, r = lane & 15, q = lane >> 4;
     const int wave = (int)blockIdx.x * 4 + (t >> 6), n_waves = (int)gridDim.x * 4;
     const half_t* wg = reinterpret_cast<const half_t*>(a.w);
@@ -276,8 +282,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
     const char* xb = reinterpret_cast<const char*>(a.x) + ((size_t)a.x_coff + 8 * (lane & 3)) * 2;
     const size_t pitch = (size_t)a.x_cs * 2;
     const int src_lane4 = (4 * r + q) * 4;
+    // A row window (ConvArgs::win_rows; tpi > 0): the walk covers tpi tiles per image, the pixels of rows [win_y0, win_y0 + win_rows)
+    // of each image's map; tile -> first pixel and the end of its run.  tpi == 0: the M pixels as one run.
+    const int hw = a.Ho * a.Wo, wpx0 = a.win_y0 * a.Wo, wpx = a.win_rows * a.Wo;
+    auto tile_m0 = [&](int tile, int& m_end) {
+        if (tpi == 0) { m_end = a.M; return tile * 16; }
+        const int img = tile / tpi, base = img * hw + wpx0;
+        m_end = base + wpx;
+        return base + (tile - img * tpi) * 16;
+    };
     auto fetch = [&](int tile, int4 (&xr)[KS]) {
-        const int m = min(tile * 16 + (lane >> 2), a.M - 1);   // (rows past the end: any pixel; nothing of them is stored)
+        int m_end;
+        const int m0 = tile_m0(tile, m_end);
+        const int m = min(m0 + (lane >> 2), m_end - 1);   // (rows past the end: any pixel; nothing of them is stored)
         const char* p = xb + (size_t)m * pitch;
 #pragma unroll
         for (int s = 0; s < KS; ++s) xr[s] = *reinterpret_cast<const int4*>(p + 64 * s);
@@ -300,8 +317,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[j][s], xf, acc[0][j], 0, 0, 0);
         }
-        const int m = tile * 16 + r;
-        const int mrow[1] = {m < a.M ? m : -1};
+        int m_end;
+        const int m = tile_m0(tile, m_end) + r;
+        const int mrow[1] = {m < m_end ? m : -1};
         epilogue_dispatch<half_t, 1, 4, true>(a, acc, mrow, 0, q);
 #pragma unroll
         for (int s = 0; s < KS; ++s) xr[s] = xn[s];
@@ -310,9 +328,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 
 template <int KS>
 static void launch_1x1_stream(const ConvArgs& a, hipStream_t s) {
-    const int n_tiles = (a.M + 15) / 16;
+    const bool win = a.win_rows > 0 && a.win_y0 >= 0 && a.win_y0 + a.win_rows <= a.Ho;
+    const int tpi = win ? (a.win_rows * a.Wo + 15) / 16 : 0;           // a row window: the tiles of every image's rows
+    const int n_tiles = win ? a.M / (a.Ho * a.Wo) * tpi : (a.M + 15) / 16;
     const int blocks = std::min((n_tiles + 3) / 4, 256 * 4);           // 3 - 4 waves per SIMD resident: every wave walks a strided run of tiles
-    hipLaunchKernelGGL(conv1x1_stream_kernel<KS>, dim3(blocks), dim3(256), 0, s, a, n_tiles);
+    hipLaunchKernelGGL(conv1x1_stream_kernel<KS>, dim3(blocks), dim3(256), 0, s, a, n_tiles, tpi);
     KCHECK();
 }
 
@@ -591,7 +611,7 @@ template <int CPP> __device__ __forceinline__ int patch_swz(int p) { return CPP 
 // KORD: 0 = K-steps in memory order (kh, kw, cc); 2 = (kw, cc, kh), the accumulation order of the weights-resident 64-channel
 // kernels (ConvArgs::k_order): the same layer then gives the same bits below and above their batch threshold.
 template <typename T, int MT, int NT, int WM, int WN, int TH, int TW, int NSTAGE, int LGCPP, bool TAIL = false, int KORD = 0>
-__global__ __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu((NT == 5 || TAIL) ? 2 : 1))) void conv3x3_patch_kernel(const ConvArgs a, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu((NT == 5 || TAIL) ? 2 : 1))) void conv3x3_patch_kernel(const ConvArgs a, int tiles_x, int tiles_y, int oy_org) {
     constexpr int CH = 16 / (int)sizeof(T);
     constexpr int BKE = 4 * CH;
     constexpr int NTHR = 64 * WM * WN;
@@ -618,7 +638,7 @@ __global__ __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu((N
     const int tx = bx % tiles_x; bx /= tiles_x;
     const int ty = bx % tiles_y;
     const int img = bx / tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int oy0 = oy_org + ty * TH, ox0 = tx * TW;          // (a row window, ConvArgs::win_rows: tiles_y tile rows from output row oy_org)
     const int n0 = tby * BN;
 
     const T* __restrict__ wg = reinterpret_cast<const T*>(a.w);
@@ -729,12 +749,15 @@ __global__ __launch_bounds__(64 * WM * WN) __attribute__((amdgpu_waves_per_eu((N
     }
     wait_vmcnt<0>();
 
+    // a row window is stored exactly: rows of its tiles outside [win_y0, win_y0 + win_rows) are dropped (a reader's input there may be
+    // another writer's output -- the bottleneck scratch of a C2f with two bottlenecks)
+    const int oy_lo = a.win_rows ? a.win_y0 : 0, oy_hi = a.win_rows ? min(a.win_y0 + a.win_rows, a.Ho) : a.Ho;
     int mrow[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int pt = (wm * MT + i) * 16 + r;
         const int oy = oy0 + pt / TW, ox = ox0 + pt % TW;
-        mrow[i] = (oy < a.Ho && ox < a.Wo) ? (img * a.Ho + oy) * a.Wo + ox : -1;
+        mrow[i] = (oy >= oy_lo && oy < oy_hi && ox < a.Wo) ? (img * a.Ho + oy) * a.Wo + ox : -1;
     }
     if constexpr (TAIL) {
         static_assert(sizeof(T) == 2 && WN == 1, "the tail needs fp16 and a wave that owns every channel of its pixels");
@@ -752,12 +775,13 @@ static void launch_patch(const ConvArgs& a, hipStream_t s) {
     constexpr int TOTAL = (TH + 2) * PWP * CPP;
     constexpr size_t lds = (size_t)(TOTAL + NTHR - 1) / NTHR * NTHR * 16 + (size_t)NSTAGE * BNP * 64;
     static_assert(lds <= 160 * 1024, "patch does not fit the LDS");
-    const int tiles_x = ceil_div(a.Wo, TW), tiles_y = ceil_div(a.Ho, TH);
+    const TileWindow win = tile_window(a.win_y0, a.win_rows, TH, a.Ho);
+    const int tiles_x = ceil_div(a.Wo, TW), tiles_y = win.tiles;
     const int n_img = a.M / (a.Ho * a.Wo);
     auto kfn = conv3x3_patch_kernel<T, MT, NT, WM, WN, TH, TW, NSTAGE, LGCPP, TAIL, KORD>;
     if (lds > 64 * 1024) set_lds_limit(kfn, lds);
     dim3 grid(n_img * tiles_x * tiles_y, ceil_div(a.Cout, BN));
-    hipLaunchKernelGGL(kfn, grid, dim3(NTHR), lds, s, a, tiles_x, tiles_y);
+    hipLaunchKernelGGL(kfn, grid, dim3(NTHR), lds, s, a, tiles_x, tiles_y, win.origin);
     KCHECK();
 }
 

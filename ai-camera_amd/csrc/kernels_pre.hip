@@ -137,7 +137,7 @@ typedef float floatx4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void yolo_stem_fused_kernel(const uint8_t* __restrict__ frames, LetterboxGeom g,
                                                               const half_t* __restrict__ w, const float* __restrict__ bias, int Kp,
                                                               half_t* __restrict__ y, int y_cs, int y_coff, int Ho, int Wo, int tiles_x,
-                                                              int tiles_y, unsigned frames_limit) {
+                                                              int tiles_y, int oy_org, unsigned frames_limit) {
     constexpr int TH = 8, TW = 32, PR = 2 * TH + 1, PC = 2 * TW + 1, PCP = (PC + 1) / 2;
     __shared__ uint2 patch[PR * 2 * PCP];      // entry (row, column parity, column / 2)
 
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void yolo_stem_fused_kernel(const uint8_t* __r
     const int tx = bx % tiles_x; bx /= tiles_x;
     const int ty = bx % tiles_y;
     const int img = bx / tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int oy0 = oy_org + ty * TH, ox0 = tx * TW;          // (a row window: tiles_y tile rows from output row oy_org; the full map: Ho / TH from 0)
     const int Y0 = 2 * oy0 - 1, X0 = 2 * ox0 - 1;
     const uint8_t* f = frames + (size_t)img * g.src_h * g.src_w * 3;
     const bool area2 = is_area2(g.src_w, g.src_h, g.unpad_w, g.unpad_h);
@@ -232,15 +232,16 @@ __global__ __launch_bounds__(256) void yolo_stem_fused_kernel(const uint8_t* __r
 }
 
 bool launch_yolo_stem_fused(const uint8_t* frames, int n, const LetterboxGeom& g, const void* w, const float* bias, int Kp, void* y,
-                            int y_cs, int y_coff, int Ho, int Wo, hipStream_t s) {
+                            int y_cs, int y_coff, int Ho, int Wo, hipStream_t s, int win_y0, int win_rows) {
     if (n <= 0) return true;
     if (Ho % 8 || Wo % 32 || Ho * 2 != g.out_h || Wo * 2 != g.out_w || (y_cs | y_coff) % 4) return false;
-    const int tiles_x = Wo / 32, tiles_y = Ho / 8;
+    const TileWindow tw = tile_window(win_y0, win_rows, 8, Ho);          // (no window: Ho / 8 tile rows from row 0)
+    const int tiles_x = Wo / 32, tiles_y = tw.tiles;
     // bytes from the 4-byte-aligned base to the end of the call's last frame, or 0 when they do not fit 32 bits (the kernel then reads bytes)
     const unsigned long long total = (unsigned long long)(reinterpret_cast<uintptr_t>(frames) & 3) + (unsigned long long)n * g.src_h * g.src_w * 3;
     const unsigned frames_limit = total < (1ull << 32) - 64 ? (unsigned)total : 0u;
     hipLaunchKernelGGL(yolo_stem_fused_kernel, dim3(n * tiles_x * tiles_y), dim3(256), 0, s, frames, g, reinterpret_cast<const half_t*>(w),
-                       bias, Kp, reinterpret_cast<half_t*>(y), y_cs, y_coff, Ho, Wo, tiles_x, tiles_y, frames_limit);
+                       bias, Kp, reinterpret_cast<half_t*>(y), y_cs, y_coff, Ho, Wo, tiles_x, tiles_y, tw.origin, frames_limit);
     KCHECK();
     return true;
 }

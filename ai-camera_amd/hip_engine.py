@@ -197,6 +197,14 @@ class HipEngine:
             r.update(form=forms[r["form"]], k_order=int(out[4]), xs=int(out[21]), y_coff=int(out[22]), x_coff=int(out[23]))
         return r
 
+    def row_band(self, op, src_h, src_w):
+        """The rows of op `op`'s output map that can depend on a src_h x src_w frame, and whether the last run on frames ran the op on a
+        row window (aic_model_row_band, include/aicam.h)."""
+        out = np.zeros(8, np.int32)
+        L.call("aic_model_row_band", self._h, int(op), int(src_h), int(src_w), L.ptr(out))
+        return {"full": bool(out[0]), "lo": int(out[1]), "hi": int(out[2]), "rows": int(out[3]), "windowed": bool(out[4]),
+                "win_y0": int(out[5]), "win_rows": int(out[6]), "slots": int(out[7])}
+
     def detect_np(self, frames_bgr, conf=None, iou=None, max_det=None):
         f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
         if f.ndim == 3:

@@ -86,6 +86,13 @@ int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes);
  * form, mt, nt, wm, wn, nstage, th, tw, cpp, pitch, kord, g, tail, x2, run, blocks; [21] split source, [22] / [23] destination /
  * source channel offset. */
 int aic_model_conv_plan(aic_model* m, int op, int n, int32_t* out);
+/* Read-only: the row band of op `op` of the engine's op list for frames of src_h x src_w -- the rows of its output map that can depend
+ * on the frame when the letterboxed picture has flat borders above and below it (csrc/row_band.hpp) -- and what the last run of the
+ * engine on frames (aic_detect, the pipeline) did with it.  out[8]: [0] 1 = every row (the op is not modelled, follows one that is
+ * not, or the geometry has borders left / right), [1] / [2] first / last row of the band, [3] rows of the map, [4] 1 = the last run on
+ * frames ran the launch that covers this op on a row window, [5] / [6] that window's first row and row count, [7] item slots whose
+ * constant rows are in place (0: the next run on frames computes the full maps). */
+int aic_model_row_band(aic_model* m, int op, int src_h, int src_w, int32_t* out);
 int aic_model_destroy(aic_model* m);
 /* kind, input H/W, classes (YOLO) or feature dim (ReID), anchors per image, conv FLOPs per item */
 int aic_model_info(const aic_model* m, int* kind, int* in_h, int* in_w, int* out_dim,

@@ -140,22 +140,32 @@ def main(d, frames=16, crops=480, top=30, fused_stem=1, fused_yolo_stem=1, fused
     gkey = [int(g[0].get("Grid_Size_X", g[0].get("Grid_Size", 0))) for g in glist]
     modal = collections.Counter(gkey).most_common(1)[0][0]
     dur = [[] for _ in range(per)]
+    grid_of = lambda r: int(r.get("Grid_Size_X", r.get("Grid_Size", 0)))
+    mgrid, fgrid = [0] * per, [0] * per
     for g, k in zip(glist, gkey):
+        for i, r in enumerate(g):
+            fgrid[i] = max(fgrid[i], grid_of(r))
         if k != modal:
             continue
         for i, r in enumerate(g):
             dur[i].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+            mgrid[i] = grid_of(r)
     groups = sum(1 for k in gkey if k == modal)
+    # Row windows: the steady-state (modal) groups launch fewer tile rows of the detector's first layers than the group that
+    # populated the borders' rows -- the largest grid a launch position ever had.  A layer's FLOPs are scaled by that ratio, so the
+    # rate column describes the rows that ran (the streaming 1x1's grid is capped: its share is not visible here and stays 1).
+    # AICAM_NO_ROW_BAND=1 traces have share 1 everywhere.
     out = []
-    for (name, ln, m, co, k), ts in zip(layers, dur):
+    for i, ((name, ln, m, co, k), ts) in enumerate(zip(layers, dur)):
         t = statistics.median(ts)
-        out.append((t, name, ln, m, co, k, 2.0 * m * co * k / t / 1e6))
+        share = min(1.0, mgrid[i] / fgrid[i]) if fgrid[i] else 1.0
+        out.append((t, name, ln, m, co, k, 2.0 * m * share * co * k / t / 1e6, share))
     total = sum(o[0] for o in out)
     print(f"\nconv launches per group {per}, groups {groups}, conv us per group {total:.0f} "
           f"(yolo {sum(o[0] for o in out if o[1] == 'yolo'):.0f}, reid {sum(o[0] for o in out if o[1] == 'reid'):.0f}); "
-          f"overall {sum(2.0 * o[3] * o[4] * o[5] for o in out) / total / 1e6:.0f} TFLOP/s")
-    for t, name, ln, m, co, k, tf in sorted(out, reverse=True)[:top]:
-        print(f"{t:8.1f} us {100 * t / total:5.1f}%  {name} {ln:18s} M={m:8d} N={co:4d} K={k:5d} {tf:7.1f} TF")
+          f"overall {sum(2.0 * o[3] * o[7] * o[4] * o[5] for o in out) / total / 1e6:.0f} TFLOP/s")
+    for t, name, ln, m, co, k, tf, share in sorted(out, reverse=True)[:top]:
+        print(f"{t:8.1f} us {100 * t / total:5.1f}%  {name} {ln:18s} M={m:8d} N={co:4d} K={k:5d} {tf:7.1f} TF" + (f"  rows launched {100 * share:.0f} %" if share < 1 else ""))
 
 
 if __name__ == "__main__":
