@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "zones", "gmc", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "zones", "render", "gmc", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
@@ -38,6 +38,8 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.xcam").CrossCamera
     if name == "ZoneCounter":
         return _importlib.import_module(f"{__name__}.zones").ZoneCounter
+    if name == "Renderer":
+        return _importlib.import_module(f"{__name__}.render").Renderer
     if name == "CameraMotionBank":
         return _importlib.import_module(f"{__name__}.gmc").CameraMotionBank
     if name == "CameraMotion":

@@ -238,6 +238,12 @@ _SIGS = {
     "aic_zones_counters": (_I, [_P, _I, _P, _P, _P, _P]),
     "aic_zones_reset": (_I, [_P, _I]),
     "aic_zones_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_render_create": (_I, [_I, _I, _P]),
+    "aic_render_destroy": (_I, [_P]),
+    "aic_render_option": (_I, [_P, C.c_char_p, C.c_int64]),
+    "aic_render_set_masks": (_I, [_P, _I, _I, _P, _P]),
+    "aic_render_rects": (_I, [_P, _P, _I, _P, _P]),
+    "aic_render_frames": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

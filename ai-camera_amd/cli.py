@@ -14,6 +14,9 @@ Outputs (the step AFTER the path, §8(f)-3): tracks + info panel are drawn on ev
 (ai-camera_amd/visualization.py).  Unless `--no_save`: an annotated video through cv2.VideoWriter when cv2 is there
 (aicamera_tracker.py:140-161), else annotated BGR24 frames appended to `<name>_tracked_<time>.bgr24` (+ `.json` with size / fps);
 the tracks always go to a `.jsonl` next to it.  `--show_display` needs cv2 (imshow); without it the flag is accepted and ignored.
+With `--inputs` the S frames of a tick and their tracks go through ONE `render.Renderer` call; `--redact
+{off,box,head}`, `--redact_style mosaic:16|...|fill`, `--masks FILE.json` and `--draw_zones` (with `--zones`) pixelate or fill the tracked
+objects, black out fixed regions and draw the zones, with `--input` as well; with none of them the written pixels are the overlay's.
 """
 from __future__ import annotations
 
@@ -64,6 +67,14 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help="JSON file {\"cameras\": [{\"zones\": [[[x, y], ...], ...], \"lines\": [[[x, y], [x, y]], ...]}, ...]} in integer pixels, one entry per "
                         "source (a single entry serves every source): zone entries, dwell and line crossings are counted on the device and every "
                         "JSON line gains \"zones\": {occupancy, zone_in, zone_out, line_pos, line_neg, events}")
+    p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
+                   help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
+    p.add_argument("--redact_style", type=str, default="mosaic:16",
+                   help="mosaic:4 | mosaic:8 | mosaic:16 | mosaic:32 (cells of that many pixels, anchored at the frame's origin) or fill (black)")
+    p.add_argument("--masks", type=str, default=None,
+                   help="JSON file {\"cameras\": [{\"masks\": [[[x, y], ...], ...]}, ...]} in integer pixels, one entry per source (a single "
+                        "entry serves every source): the polygons are blacked out on every saved frame")
+    p.add_argument("--draw_zones", action="store_true", help="draw the zones and lines of --zones on the saved frames")
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
@@ -74,6 +85,8 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--link_cameras needs --inputs a,b,c --tracker botsort or deepsort_bank")
     if args.tracker == "deepsort_bank" and args.inputs is None:
         p.error("--tracker deepsort_bank needs --inputs a,b,c (one source: --tracker deepsort)")
+    if args.draw_zones and not args.zones:
+        p.error("--draw_zones needs --zones FILE.json")
     if args.inputs is not None:
         if args.input is not None:
             p.error("--inputs and --input are mutually exclusive")
@@ -253,6 +266,46 @@ class _ZoneLines:
         self.counter.close()
 
 
+class _Output:
+    """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
+    render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
+    -1 (unknown) is always redacted."""
+
+    def __init__(self, args, cameras, device):
+        from .render import Renderer, load_masks_file, parse_style
+        self.asked = args.redact != "off" or bool(args.masks) or args.draw_zones
+        style, cell = parse_style(args.redact_style)
+        masks = load_masks_file(args.masks, cameras) if args.masks else None
+        geometry = None
+        if args.draw_zones:
+            from .zones import load_zones_file
+            geometry = load_zones_file(args.zones, cameras)
+        self.geometry, self.cameras, self.ids = geometry, cameras, {n: i for i, n in enumerate(config.CLASSES)}
+        self.renderer = Renderer(cameras=cameras, redact=args.redact, style=style, cell=cell, device=device)
+        try:
+            for c, polys in enumerate(masks or []):
+                self.renderer.set_masks(c, polys)
+        except Exception:
+            self.renderer.close()
+            raise
+
+    def draw(self, frames, tracks, shown, infos):
+        """frames: S arrays [H, W, 3] of cameras 0..S-1, or one uint8 array [S, H, W, 3] (drawn in place) -> uint8 [S, H, W, 3] annotated.  tracks: the trackers' tuples (redaction), shown: the
+        tuples as labelled, infos: the info panel's lines per frame."""
+        batch = frames if isinstance(frames, np.ndarray) else np.ascontiguousarray(np.stack(frames), dtype=np.uint8)
+        rows = [np.array([[t[0], t[1], t[2], t[3], 0, self.ids.get(t[5], -1)] for t in tr], np.int64).reshape(-1, 6) for tr in tracks]
+        prims = []
+        for c, (sh, info) in enumerate(zip(shown, infos)):
+            pl = visualization.PrimList()
+            if self.geometry is not None:
+                visualization.zone_prims(pl, *self.geometry[c])
+            prims.append(visualization.info_prims(visualization.track_prims(pl, sh), list(info)))
+        return self.renderer.render(batch, np.concatenate(rows).astype(np.int32), [len(r) for r in rows], prims)
+
+    def close(self):
+        self.renderer.close()
+
+
 def main_streams(args, cv2):
     """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank /
     deepsort_bank for --tracker botsort / deepsort_bank), their frames interleaved tick by tick."""
@@ -307,16 +360,36 @@ def main_streams(args, cv2):
             print(f"Error reading --zones {args.zones}: {e}")
             pipe.close()
             return 1
+    output = None
+    if not args.no_save:
+        try:
+            output = _Output(args, S, dev)
+        except Exception as e:
+            print(f"Error setting up the output stage (--redact_style / --masks / --draw_zones): {e}")
+            for f in outs + writers + [zones]:
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     ticks = (f for tick in zip(*(src[1] for src in sources)) for f in tick)       # the shortest source ends the run
     n, t0 = 0, time.time()
+    tick = []                                                                     # the tick's (tracks, labelled tracks) so far
+    batch = np.empty((S, size[1], size[0], 3), np.uint8) if output is not None else None      # its frames: copied as they arrive
     try:
         for frame, tracks in pipe.stream(ticks):
             k, idx = n % S, n // S
             n += 1
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
-            if writers[k] is not None:
+            if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
-                writers[k].write(visualization.draw_frame(frame.copy(), shown, [label, f"Input: {sources[k][0]} (stream {k})"], dev))
+                batch[k] = frame
+                tick.append((tracks, shown))
+                if len(tick) == S:                                                # the tick's S frames in ONE render call
+                    drawn = output.draw(batch, [t[0] for t in tick], [t[1] for t in tick],
+                                        [[label, f"Input: {sources[c][0]} (stream {c})"] for c in range(S)])
+                    for c in range(S):
+                        writers[c].write(drawn[c])
+                    tick = []
             if outs[k]:
                 line = {"frame": idx, "tracks": tracks}
                 if gids is not None:
@@ -332,6 +405,8 @@ def main_streams(args, cv2):
                 f.close()
         if zones is not None:
             zones.close()
+        if output is not None:
+            output.close()
         pipe.close()
     total = time.time() - t0
     print("\n--- Processing Summary ---")
@@ -425,6 +500,17 @@ def main(argv=None):
                     f.close()
             return 1
 
+    output = None
+    if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
+        try:
+            output = _Output(args, 1, dev)
+        except Exception as e:
+            print(f"Error setting up the output stage (--redact_style / --masks / --draw_zones): {e}")
+            for f in (out_f, writer, zones, pipe):
+                if f is not None:
+                    f.close()
+            return 1
+
     def per_frame():
         nonlocal total
         for frame in frames:
@@ -456,7 +542,8 @@ def main(argv=None):
             frame_idx += 1
             display_fps = frame_idx / total if total > 0 else 0.0
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
-                vis = visualization.draw_frame(frame.copy(), tracks, ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"], dev)
+                info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
+                vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info])[0]
                 if args.show_display and cv2 is not None:
                     cv2.imshow("AICamera Tracking", vis)
                     if cv2.waitKey(1) & 0xFF == ord("q"):
@@ -480,6 +567,8 @@ def main(argv=None):
             writer.close()
         if zones is not None:
             zones.close()
+        if output is not None:
+            output.close()
         if pipe is not None:
             clipped = pipe.counters()["clipped_frames"]
             if clipped:

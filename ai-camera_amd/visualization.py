@@ -37,6 +37,10 @@ class PrimList:
         self.prims.append((2, int(x0), int(y0), 0, 0, self._color(color), len(self.text), len(raw) | int(scale) << 16))
         self.text += raw
 
+    def segment(self, ax, ay, bx, by, t, color):
+        """Kind 3, the tiled renderer's only (render.py; aic_overlay rejects it): a segment A->B of thickness t in 1..8."""
+        self.prims.append((3, int(ax), int(ay), int(bx), int(by), self._color(color), int(t), 0))
+
     def arrays(self):
         return (np.asarray(self.prims, np.int32).reshape(-1, 8), np.frombuffer(bytes(self.text), np.uint8).copy())
 
@@ -107,6 +111,17 @@ def info_prims(pl, info_lines):
         (_, th), bl = text_size(s, SCALE_INFO)
         pl.put_text(start_x, y + bl + th // 2 - th, s, SCALE_INFO)       # baseline position of visualization.py:214 minus the glyph height
         y += line_h
+    return pl
+
+
+def zone_prims(pl, zones, lines, color=(0, 255, 255), t=2):
+    """The zones (closed polygon outlines) and lines of a camera's --zones geometry as kind-3 segments, for render.Renderer."""
+    for z in zones:
+        pts = [(int(x), int(y)) for x, y in z]
+        for (ax, ay), (bx, by) in zip(pts, pts[1:] + pts[:1]):
+            pl.segment(ax, ay, bx, by, t, color)
+    for (ax, ay), (bx, by) in lines:
+        pl.segment(ax, ay, bx, by, t, color)
     return pl
 
 

@@ -755,6 +755,42 @@ int aic_zones_update(aic_zones* z, const int32_t* frames_per_stream, const int32
 int aic_zones_counters(aic_zones* z, int stream, int64_t* zone_in, int64_t* zone_out, int64_t* line_pos, int64_t* line_neg);
 int aic_zones_reset(aic_zones* z, int stream);
 int aic_zones_option(aic_zones* z, const char* key, int value);
+
+/* ---- privacy redaction, static masks and annotation of a bank of frames in one launch (csrc/render.hpp) -------
+ * The output stage after the path: u8 BGR frames [n_frames, h, w, 3] of one size (h, w in 1..16384), the rows every tracker delivers
+ * (x1 y1 x2 y2 id cls), per-frame primitive lists and per-camera mask polygons.  tests/render_oracle.py is the specification; the
+ * device matches it bit for bit.  Per pixel, the first rule that applies, everything "original" read from the frame as handed in:
+ *   (a) the colour of the LAST primitive of the frame's list that covers it.  prims [n, 8] as aic_overlay (kinds 0, 1, 2), and kind 3 =
+ *       (3, ax, ay, bx, by, color, t, 0): a segment A->B of thickness t in 1..8.  dx = bx - ax, dy = by - ay; |dx| >= |dy| and dx != 0:
+ *       hit iff min(ax, bx) <= x <= max(ax, bx) and 2 |dx (y - ay) - dy (x - ax)| <= t |dx|; |dy| > |dx|: the same with the axes
+ *       exchanged; A == B draws nothing.  Text offsets index the call's one text buffer.  |coordinate| <= 2^20.
+ *   (b) mask_color inside a mask polygon of the frame's camera (even-odd rule with half-open edges on the integer pixel (x, y)).
+ *   (c) inside the union of the frame's redaction rectangles: fill_color (style 0), or (style 1, mosaic) the mean per channel of the
+ *       original pixels of cell (x / cell, y / cell), grid anchored at the frame's origin, (sum + n / 2) / n over the n pixels the cell
+ *       has inside the frame.
+ *   (d) unchanged.
+ * A row gives a rectangle: coordinates saturated to +-2^20, rows with x2 < x1 or y2 < y1 dropped; mode 1 (box) = (x1 - pad, y1 - pad,
+ * x2 + pad, y2 + pad) inclusive, mode 2 (head) = the same x range, y from y1 - pad to y1 + (((y2 - y1) * head_q8) >> 8); mode 0 = none.
+ * class_all 1 (default) redacts every row; after option "class_mask" (bit c = class c) only rows of those classes and rows whose cls
+ * is outside 0..63 (an unknown class fails safe).
+ * create, option, set_masks, rects and every argument error of frames never touch the device.
+ * option keys: "mode" 0..2, "style" 0 / 1, "cell" 4 / 8 / 16 / 32, "fill_color", "mask_color" (B | G << 8 | R << 16), "pad" 0..4096,
+ * "head_q8" 1..256, "class_mask", "class_all" 0 / 1, "chunk_frames" (0 = a call's frames in one device buffer, k = at most k frames per
+ * upload, launch and download; same results).
+ * set_masks: n_verts[n_polys] (n_polys in 0..32, 3..32 vertices each), xy = the vertices one after another (x, y).
+ * rects: host only; rects4 [<= n_rows, 4] = x0 y0 x1 y1 the rows give under the current options, *n_rects their number.
+ * frames: rows6 [sum of row_counts, 6] with row_counts[n_frames] (both may be NULL: no rows; at most 512 per frame, else
+ * AIC_ERR_CAPACITY), prims [sum of prim_counts, 8] with prim_counts[n_frames] (may be NULL; at most 1500 per frame), cameras[n_frames]
+ * (NULL: frame f is camera f % cameras).  Host frames (AIC_HOST) are uploaded, rendered and downloaded; device frames (AIC_DEVICE) are
+ * rendered in place.  One stream synchronise ends the call. */
+typedef struct aic_render aic_render;
+int aic_render_create(int device, int cameras, aic_render** out);
+int aic_render_destroy(aic_render* r);
+int aic_render_option(aic_render* r, const char* key, int64_t value);
+int aic_render_set_masks(aic_render* r, int camera, int n_polys, const int32_t* n_verts, const int32_t* xy);
+int aic_render_rects(aic_render* r, const int32_t* rows6, int n_rows, int32_t* rects4, int* n_rects);
+int aic_render_frames(aic_render* r, uint8_t* frames_bgr, int n_frames, int h, int w, int mem, const int32_t* rows6, const int32_t* row_counts,
+                      const int32_t* prims, const int32_t* prim_counts, const uint8_t* text, int text_bytes, const int32_t* cameras);
 int aic_host_register(void* ptr, size_t bytes);   /* hipHostRegister: page-lock caller memory */
 int aic_host_unregister(void* ptr);
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out);
