@@ -93,6 +93,8 @@ _SIGS = {
     "aic_crop_resize": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "aic_detect": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "aic_reid_embed": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "aic_crop_resize_ex": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "aic_reid_embed_bank": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "aic_kf_initiate": (_I, [_I, _P, _I, _P, _P]),
     "aic_kf_predict": (_I, [_I, _P, _P, _I]),
     "aic_kf_predict_dt": (_I, [_I, _P, _P, _I, _F]),

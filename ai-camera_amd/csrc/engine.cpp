@@ -1431,3 +1431,112 @@ int aic_reid_embed(aic_model* mm, const uint8_t* frame, int h, int w, int mem, c
 }
 
 }  // extern "C"
+
+namespace {
+
+// The staging of the two parity-test entries below: a bank of n_frames frames that starts byte_offset (0..3) bytes into a device buffer
+// filled with a non-zero byte, so that a tap taken from outside the bank shows as a wrong VALUE; with `slack` 16 of those bytes follow
+// the bank (what the aligned 12-byte loads of the wide crop path and of the fused stem are promised), without it the buffer ends with
+// the bank.  frame_of (may be NULL) is checked against the bank on the host: no kernel ever sees an index outside it.
+struct TestBank {
+    DevBuf<uint8_t> buf;
+    DevBuf<int> frame_of, n_live;
+    int n_live_host = 0;                 // the upload's source: lives as long as the bank
+    const uint8_t* frames = nullptr;
+};
+
+void stage_test_bank(TestBank& tb, const uint8_t* frames, int n_frames, int h, int w, int byte_offset, bool slack, const int32_t* frame_of,
+                     int n, int n_live, hipStream_t s) {
+    AIC_REQUIRE(frames && n_frames > 0 && h > 0 && w > 0 && byte_offset >= 0 && byte_offset <= 3, AIC_ERR_INVALID, "bad bank");
+    const size_t bytes = (size_t)n_frames * h * w * 3;
+    AIC_REQUIRE(bytes < ((size_t)1 << 31), AIC_ERR_INVALID, "bank too large");
+    if (frame_of)
+        for (int i = 0; i < n; ++i) AIC_REQUIRE(frame_of[i] >= 0 && frame_of[i] < n_frames, AIC_ERR_INVALID, "frame_of outside the bank");
+    tb.buf.alloc((size_t)byte_offset + bytes + (slack ? 16 : 0));
+    HIP_CHECK(hipMemsetAsync(tb.buf.p, 0xA5, tb.buf.n, s));
+    tb.frames = tb.buf.p + byte_offset;
+    HIP_CHECK(hipMemcpyAsync(tb.buf.p + byte_offset, frames, bytes, hipMemcpyHostToDevice, s));
+    if (frame_of) {
+        tb.frame_of.alloc(n);
+        HIP_CHECK(hipMemcpyAsync(tb.frame_of.p, frame_of, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    }
+    if (n_live >= 0) {
+        tb.n_live.alloc(1);
+        tb.n_live_host = n_live;
+        HIP_CHECK(hipMemcpyAsync(tb.n_live.p, &tb.n_live_host, 4, hipMemcpyHostToDevice, s));
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int aic_crop_resize_ex(int device_id, const uint8_t* frames, int n_frames, int h, int w, int byte_offset, const float* boxes,
+                       const int32_t* frame_of, int n, int n_live, int out_h, int out_w, int mode, int dtype, int slack, void* out,
+                       int32_t* valid) {
+    return guarded([&] {
+        AIC_REQUIRE(n >= 0 && out_h > 0 && out_w > 0 && mode >= 0 && mode <= 2 && (dtype == AIC_F32 || dtype == AIC_F16), AIC_ERR_INVALID, "bad argument");
+        AIC_REQUIRE(mode != 0 || dtype == AIC_F32, AIC_ERR_INVALID, "the NCHW layout is fp32");
+        if (n == 0) return;
+        AIC_REQUIRE(boxes && out && valid, AIC_ERR_INVALID, "NULL argument");
+        Device& d = device(device_id);
+        hipStream_t s = d.s_main;
+        TestBank tb;
+        stage_test_bank(tb, frames, n_frames, h, w, byte_offset, slack != 0, frame_of, n, n_live, s);
+        const size_t px = (size_t)n * out_h * out_w;
+        const size_t out_bytes = mode == 0 ? px * 3 * 4 : mode == 1 ? px * 8 * (dtype == AIC_F16 ? 2 : 4) : px * 4 * 2;
+        DevBuf<float> db((size_t)n * 4);
+        DevBuf<char> dout(out_bytes);
+        DevBuf<int> dv(n);
+        HIP_CHECK(hipMemcpyAsync(db.p, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(dout.p, 0xFF, out_bytes, s));           // an element no thread stores keeps this pattern
+        HIP_CHECK(hipMemsetAsync(dv.p, 0xFF, (size_t)n * 4, s));         // = -1
+        try {
+            launch_crop_resize(tb.frames, h, w, db.p, tb.frame_of.p, n, tb.n_live.p, out_h, out_w, mode, dtype, dout.p, dv.p, s, slack != 0);
+        } catch (...) {
+            (void)hipStreamSynchronize(s);                                // the staging copies read the caller's arrays
+            throw;
+        }
+        HIP_CHECK(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(valid, dv.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int aic_reid_embed_bank(aic_model* mm, const uint8_t* frames, int n_frames, int h, int w, int byte_offset, const float* boxes,
+                        const int32_t* frame_of, int n, int n_live, float* emb, int32_t* valid) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && n >= 0, AIC_ERR_INVALID, "bad argument");
+        if (n == 0) return;
+        AIC_REQUIRE(boxes && emb && valid, AIC_ERR_INVALID, "NULL argument");
+        Model& m = mm->m;
+        AIC_REQUIRE(m.kind == KIND_REID && m.dtype == AIC_F16 && m.input_pix4_ok() && reid_stem2_usable(m.in_h, m.in_w) && m.in_h <= 192,
+                    AIC_ERR_INVALID, "this engine does not take the fused crop");
+        AIC_REQUIRE(n <= m.max_items, AIC_ERR_INVALID, "more crops than the engine's max_items");
+        m.dev->use();
+        hipStream_t s = m.dev->s_main;
+        TestBank tb;
+        stage_test_bank(tb, frames, n_frames, h, w, byte_offset, true, frame_of, n, n_live, s);
+        m.d_crop_boxes.ensure((size_t)n * 4);
+        m.d_valid.ensure(n);
+        HIP_CHECK(hipMemcpyAsync(m.d_crop_boxes.p, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(m.d_valid.p, 0xFF, (size_t)n * 4, s));
+        // as the pipeline's device-filtered round sets it (pipeline.cpp, stage_a_device_filter)
+        m.in_pix4 = true;
+        m.crop_src = CropSrc{tb.frames, h, w, m.d_crop_boxes.p, tb.frame_of.p, m.d_valid.p};
+        m.n_items_dev = tb.n_live.p;
+        try {
+            m.run(n, s);
+        } catch (...) {
+            m.crop_src.frames = nullptr, m.n_items_dev = nullptr;
+            (void)hipStreamSynchronize(s);
+            throw;
+        }
+        m.crop_src.frames = nullptr, m.n_items_dev = nullptr;
+        copy_out(emb, m.embeddings(), (size_t)n * m.out_dim * 4, AIC_HOST, s);
+        HIP_CHECK(hipMemcpyAsync(valid, m.d_valid.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+}  // extern "C"

@@ -374,6 +374,7 @@ void launch_crop_resize(const uint8_t* frames, int h, int w, const float* boxes,
     if (n <= 0) return;
     const int wide = slack;
     AIC_REQUIRE(out_w <= 240, AIC_ERR_CAPACITY, "crop width above 240 is not supported");
+    AIC_REQUIRE(mode != 2 || dtype == AIC_F16, AIC_ERR_INVALID, "the NHWC4 crop layout is fp16 only");      // (the fp32 kernel has no store for it)
     dim3 grid(ceil_div(out_h, CROP_ROWS), n);
     if (dtype == AIC_F16)
         hipLaunchKernelGGL(crop_resize_kernel<half_t>, grid, dim3(256), 0, s, frames, h, w, boxes, frame_of, n, n_dev, out_h, out_w, mode, out, valid, wide);

@@ -226,6 +226,23 @@ class HipEngine:
             L.call("aic_reid_embed", self._h, L.ptr(f), f.shape[0], f.shape[1], L.HOST, L.ptr(b), n, L.ptr(emb), L.ptr(valid))
         return emb, valid
 
+    def embed_bank_np(self, frames_bgr, boxes_xyxy, frame_of=None, byte_offset=0, n_live=None):
+        """One run with the crops resampled inside the fused stem from a bank of frames [F, h, w, 3], set up as the pipeline's
+        device-filtered round (aic_reid_embed_bank, include/aicam.h; parity tests).  valid is prefilled with -1 and rows at and beyond
+        n_live are not computed.  -> (embeddings, valid); the stem's pooled tensor is left for read_buffer_np."""
+        f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+        if f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError("expected u8 frames [F, h, w, 3]")
+        b = L.as_f32(boxes_xyxy).reshape(-1, 4)
+        n = len(b)
+        fo = None if frame_of is None else np.ascontiguousarray(frame_of, np.int32)
+        if fo is not None and fo.shape != (n,):
+            raise ValueError("frame_of must hold one index per box")
+        emb, valid = np.zeros((n, self.out_dim), np.float32), np.full(n, -1, np.int32)
+        L.call("aic_reid_embed_bank", self._h, L.ptr(f), f.shape[0], f.shape[1], f.shape[2], int(byte_offset), L.ptr(b), L.ptr(fo), n,
+               -1 if n_live is None else int(n_live), L.ptr(emb), L.ptr(valid))
+        return emb, valid
+
     # ---- TRTEngine surface (torch tensors) -----------------------------------------------------
     def _warm_up(self, iterations=5):   # trt_engine.py:119-149
         start = time.time()

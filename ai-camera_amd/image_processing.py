@@ -99,6 +99,30 @@ def crops_from_boxes(frame_bgr, boxes_xyxy, target_shape=(128, 64), device=0):
     return out, valid
 
 
+def crop_resize_ex(frames_bgr, boxes_xyxy, frame_of=None, target_shape=(128, 64), mode=0, dtype="fp32", slack=False, byte_offset=0,
+                   n_live=None, device=0):
+    """The crop kernel in any of its forms on a bank of frames [F, h, w, 3] (aic_crop_resize_ex, include/aicam.h; parity tests).
+    mode 0: fp32 [N, 3, H, W]; mode 1: [N, H, W, 8] of dtype; mode 2: float16 [N, H, W, 4].  The output is prefilled with 0xFF bytes and
+    valid with -1.  -> (tensor, valid)."""
+    f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+    if f.ndim != 4 or f.shape[3] != 3:
+        raise ValueError("expected u8 frames [F, h, w, 3]")
+    b = L.as_f32(boxes_xyxy).reshape(-1, 4)
+    n = len(b)
+    fo = None if frame_of is None else np.ascontiguousarray(frame_of, np.int32)
+    if fo is not None and fo.shape != (n,):
+        raise ValueError("frame_of must hold one index per box")
+    oh, ow = int(target_shape[0]), int(target_shape[1])
+    f16 = str(dtype).lower() in ("fp16", "f16", "half")
+    shape = (n, 3, oh, ow) if mode == 0 else (n, oh, ow, 8) if mode == 1 else (n, oh, ow, 4)
+    out = np.empty(shape, np.float32 if mode == 0 or (mode == 1 and not f16) else np.float16)
+    out.view(np.uint8)[...] = 0xFF
+    valid = np.full(n, -1, np.int32)
+    L.call("aic_crop_resize_ex", device, L.ptr(f), f.shape[0], f.shape[1], f.shape[2], int(byte_offset), L.ptr(b), L.ptr(fo), n,
+           -1 if n_live is None else int(n_live), oh, ow, int(mode), L.F16 if f16 else L.F32, int(bool(slack)), L.ptr(out), L.ptr(valid))
+    return out, valid
+
+
 def scale_bboxes(bboxes_letterboxed, original_shape, letterbox_shape, ratio, padding):
     """image_processing.py:141-183.  Host-side convenience on <= max_det boxes; inside
     YOLODetector.detect the same arithmetic is fused into the NMS kernel's epilogue."""

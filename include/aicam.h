@@ -168,6 +168,23 @@ int aic_detect(aic_model* yolo, const uint8_t* frames_bgr, int batch, int h, int
 int aic_reid_embed(aic_model* reid, const uint8_t* frame_bgr, int h, int w, int mem,
                    const float* boxes_xyxy, int n, float* embeddings, int32_t* valid);
 
+/* Parity-test entry points of the crop resamplers (tests/test_gpu_crop_paths.py); no production path goes through them.
+ * Both stage a bank of frames [n_frames, h, w, 3] (host) byte_offset (0..3) bytes into a device buffer filled with a non-zero byte,
+ * frame_of[n] (may be NULL: frame 0; checked against the bank on the host) and, when n_live >= 0, a device-side crop count holding
+ * n_live (n_live < 0: none).
+ * aic_crop_resize_ex: the crop kernel in any of its layouts -- mode 0: fp32 [n, 3, out_h, out_w]; mode 1: [n, out_h, out_w, 8] of
+ * dtype; mode 2: fp16 [n, out_h, out_w, 4] (fp32 is refused with AIC_ERR_INVALID).  slack != 0: 16 readable bytes follow the bank and
+ * the kernel takes its aligned 12-byte loads.  out is prefilled with 0xFF bytes and valid with -1: what the kernel does not store shows. */
+int aic_crop_resize_ex(int device, const uint8_t* frames_bgr, int n_frames, int h, int w, int byte_offset, const float* boxes_xyxy,
+                       const int32_t* frame_of, int n, int n_live, int out_h, int out_w, int mode, int dtype, int slack, void* out,
+                       int32_t* valid);
+/* aic_reid_embed_bank: one run of an fp16 ReID engine whose fused stem resamples the crops itself, set up as the pipeline's
+ * device-filtered round sets it up (frames, boxes, frame_of, crop validity, device-side count).  AIC_ERR_INVALID for an engine that
+ * would not take the fused crop or n > max_items.  The stem's pooled tensor stays in the engine (aic_model_read_buffer); rows at and
+ * beyond n_live are not computed.  valid is prefilled with -1. */
+int aic_reid_embed_bank(aic_model* reid, const uint8_t* frames_bgr, int n_frames, int h, int w, int byte_offset,
+                        const float* boxes_xyxy, const int32_t* frame_of, int n, int n_live, float* embeddings, int32_t* valid);
+
 /* ------------------------------------------------------------------ Kalman filter (batched)
  * KalmanFilter.initiate/predict/project/update/gating_distance
  * (src/tracker/core/kalman_filter.py:55-83,85-120,122-151,153-204,206-249), n independent
