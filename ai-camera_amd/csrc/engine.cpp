@@ -779,14 +779,16 @@ Model::ConvStep Model::conv_step(size_t oi, size_t op1, int n) const {
             static const bool cls_reduce_on = getenv("AICAM_NO_CLS_REDUCE") == nullptr;
             static const bool box_decode_on = getenv("AICAM_NO_BOX_DECODE") == nullptr;
             if (reduce_cls && kind == KIND_YOLO && t.out_f32 && t.act == 0 && t.y_coff == 0 && t.y_cs == t.Cout) {
-                // a detect level's class / box branch: its logits only feed decode's arg-max / DFL expectation
-                const bool is_cls = cls_reduce_on && t.Cout == meta[0], is_box = box_decode_on && meta[1] == 16 && t.Cout == 64 && a.Cout == 64 && !is_cls;   // tail_1x1 decodes in place only in its NT == 4 form (lead Cout 64; YOLOv8x leads with 80)
+                // a detect level's class / box branch: its logits only feed decode's arg-max / DFL expectation.  Which of the two it is, is
+                // what it writes -- the level's class or box tensor -- not its width: with nc = 64 both 1x1s have 64 outputs
                 int a0 = 0;
-                for (size_t l = 0; l < outs.size() && (is_cls || is_box); ++l) {
+                for (size_t l = 0; l < outs.size(); ++l) {
                     const int* ov = outs[l].v;
-                    const BufDesc& ob = bufs[ov[is_cls ? 1 : 0]];
-                    if (ob.p == t.y && ov[3] * ov[4] == t.Ho * t.Wo) {
-                        at.t_hw = ov[3] * ov[4], at.t_a0 = a0, at.t_na = n_anchors;
+                    const int hw = ov[3] * ov[4];
+                    const bool is_cls = cls_reduce_on && bufs[ov[1]].p == t.y && t.Cout == meta[0];
+                    const bool is_box = box_decode_on && bufs[ov[0]].p == t.y && meta[1] == 16 && t.Cout == 64 && a.Cout == 64;   // tail_1x1 decodes in place only in its NT == 4 form (lead Cout 64; YOLOv8x leads with 80)
+                    if ((is_cls || is_box) && hw == t.Ho * t.Wo) {
+                        at.t_hw = hw, at.t_a0 = a0, at.t_na = n_anchors;
                         if (is_cls) {
                             at.t_max = d_maxlogit.p, at.t_arg = d_labels.p;
                             st.cls_bits |= 1u << l;
@@ -794,8 +796,9 @@ Model::ConvStep Model::conv_step(size_t oi, size_t op1, int n) const {
                             at.t_box = d_boxes.p, at.t_w = ov[4], at.t_stride = ov[2];
                             st.box_bits |= 1u << l;
                         }
+                        break;
                     }
-                    a0 += ov[3] * ov[4];
+                    a0 += hw;
                 }
             }
             st.a[0] = at;
