@@ -159,12 +159,7 @@ int aic_botsort_destroy(aic_botsort* t) {
 int aic_botsort_option(aic_botsort* t, const char* key, int value) {
     return guarded([&] {
         AIC_REQUIRE(t && key, AIC_ERR_INVALID, "NULL argument");
-        const std::string k(key);
-        if (k == "lsap_fast") t->t.lsap_fast = value != 0;
-        else if (k == "epoch_frames") {
-            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
-            t->t.epoch_frames = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown BoT-SORT option: " + k);
+        t->t.option(key, value);
     });
 }
 
@@ -217,12 +212,7 @@ int aic_botsort_bank_destroy(aic_botsort_bank* b) {
 int aic_botsort_bank_option(aic_botsort_bank* b, const char* key, int value) {
     return guarded([&] {
         AIC_REQUIRE(b && key, AIC_ERR_INVALID, "NULL argument");
-        const std::string k(key);
-        if (k == "lsap_fast") b->t.lsap_fast = value != 0;
-        else if (k == "epoch_frames") {
-            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
-            b->t.epoch_frames = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown BoT-SORT option: " + k);
+        b->t.option(key, value);
     });
 }
 
@@ -231,9 +221,7 @@ int aic_botsort_bank_update(aic_botsort_bank* b, const int32_t* frames_per_strea
                             int32_t* n_out, int32_t* out6, float* out_conf, int32_t* status) {
     return guarded([&] {
         AIC_REQUIRE(b && frames_per_stream, AIC_ERR_INVALID, "NULL argument");
-        bool any = false;
-        for (int s = 0; s < b->t.n_streams; ++s) any |= frames_per_stream[s] > 0;
-        AIC_REQUIRE(!any || counts, AIC_ERR_INVALID, "NULL argument");
+        b->t.require_counts(frames_per_stream, counts);
         b->t.update_bank(frames_per_stream, counts, boxes_xyxy, conf, cls, feat, valid, warps, cap_rows, n_out, out6, out_conf, status);
     });
 }

@@ -250,6 +250,21 @@ struct EpochBank : EpochTracker {
         else AIC_REQUIRE(bad < 0, stop_code[bad], std::string(name()) + ": " + stop_msg[bad]);
     }
 
+    // aic_<tracker>_option and aic_<tracker>_bank_option: the options every epoch tracker takes
+    void option(const std::string& k, int value) {
+        if (k == "lsap_fast") lsap_fast = value != 0;
+        else if (k == "epoch_frames") {
+            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
+            epoch_frames = value;
+        } else AIC_REQUIRE(false, AIC_ERR_INVALID, std::string("unknown ") + name() + " option: " + k);
+    }
+    // aic_<tracker>_bank_update: counts may be NULL only when no stream has frames
+    void require_counts(const int32_t* frames_per_stream, const int32_t* counts) const {
+        bool any = false;
+        for (int s = 0; s < n_streams; ++s) any |= frames_per_stream[s] > 0;
+        AIC_REQUIRE(!any || counts, AIC_ERR_INVALID, "NULL argument");
+    }
+
     // the stream's table on the host (export, counters)
     std::vector<char> fetch_table(int s, size_t bytes) {
         AIC_REQUIRE(s >= 0 && s < n_streams, AIC_ERR_INVALID, "stream outside the bank");

@@ -105,12 +105,7 @@ int aic_ocsort_destroy(aic_ocsort* t) {
 int aic_ocsort_option(aic_ocsort* t, const char* key, int value) {
     return guarded([&] {
         AIC_REQUIRE(t && key, AIC_ERR_INVALID, "NULL argument");
-        const std::string k(key);
-        if (k == "lsap_fast") t->t.lsap_fast = value != 0;
-        else if (k == "epoch_frames") {
-            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
-            t->t.epoch_frames = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown OC-SORT option: " + k);
+        t->t.option(key, value);
     });
 }
 
@@ -166,12 +161,7 @@ int aic_ocsort_bank_destroy(aic_ocsort_bank* b) {
 int aic_ocsort_bank_option(aic_ocsort_bank* b, const char* key, int value) {
     return guarded([&] {
         AIC_REQUIRE(b && key, AIC_ERR_INVALID, "NULL argument");
-        const std::string k(key);
-        if (k == "lsap_fast") b->t.lsap_fast = value != 0;
-        else if (k == "epoch_frames") {
-            AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
-            b->t.epoch_frames = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown OC-SORT option: " + k);
+        b->t.option(key, value);
     });
 }
 
@@ -180,9 +170,7 @@ int aic_ocsort_bank_update(aic_ocsort_bank* b, const int32_t* frames_per_stream,
                            int32_t* status) {
     return guarded([&] {
         AIC_REQUIRE(b && frames_per_stream, AIC_ERR_INVALID, "NULL argument");
-        bool any = false;
-        for (int s = 0; s < b->t.n_streams; ++s) any |= frames_per_stream[s] > 0;
-        AIC_REQUIRE(!any || counts, AIC_ERR_INVALID, "NULL argument");
+        b->t.require_counts(frames_per_stream, counts);
         b->t.update(frames_per_stream, counts, boxes_xyxy, conf, cls, cap_rows, n_out, out6, out_conf, status);
     });
 }

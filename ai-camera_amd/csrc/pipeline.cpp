@@ -76,6 +76,28 @@ struct Chunk {
     hipEvent_t t_begin = nullptr, t_end = nullptr, t_yolo = nullptr;   // AICAM_PIPE_TIMES: GPU timeline of the group on the main stream
 };
 
+// The caller's output arrays of a run call, row o = frame o of the call (any may be NULL): what the extern "C" entry points fill and
+// hand down to stage B.
+struct RunOut {
+    int32_t* n_tracks;
+    int32_t* tracks6;
+    float* track_conf;
+    int32_t* n_dets;
+    float* det_boxes;
+    float* det_scores;
+    int32_t* det_labels;
+};
+
+// The tracker a pipeline is created with (aic_pipeline_create*).  params: the kind's validated parameters -- BtParams, OcParams, BsParams,
+// TrkDevParams; DeepSORT takes its own from aic_pipeline_params.  streams: the cameras of a BoT-SORT or DeepSORT bank (0 = a single
+// BoT-SORT tracker; ByteTrack and OC-SORT take the option "streams").
+struct TrackerChoice {
+    enum Kind { DEEPSORT, BYTETRACK, OCSORT, BOTSORT, DEEPSORT_BANK } kind = DEEPSORT;
+    const void* params = nullptr;
+    int first_id = 1;
+    int streams = 0;
+};
+
 struct Pipeline {
     Device* dev;
     Model* yolo;
@@ -197,7 +219,7 @@ struct Pipeline {
     // filter), the embeddings stay in HBM and reach the epoch kernel through EpochDets.valid / feat / feat_n.
     std::unique_ptr<EpochTracker> bt;
     std::string bt_name() const { return bt->name(); }
-    bool bs = false;                // the epoch tracker is BoT-SORT
+    BotSortTracker* bs = nullptr;   // `bt` when the epoch tracker is BoT-SORT (not owned), else NULL
     bool bs_bank = false;           // ... created as a bank of cameras (aic_pipeline_create_botsort_bank): the count is fixed, reset_stream works
     float bs_low = 0.f;             // its track_low_thresh: inject = 0 hands over the detections with score > bs_low
     // aic_pipeline_option("gmc"): camera motion per frame, estimated on the device and handed to the BoT-SORT epochs; NULL = off
@@ -214,27 +236,32 @@ struct Pipeline {
         return t;
     }
 
-    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const BtParams* btp = nullptr, int bt_first_id = 1, const OcParams* ocp = nullptr,
-             const BsParams* bsp = nullptr, int bs_streams = 0, const TrkDevParams* dsp = nullptr, int ds_streams = 0)
-        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, btp || ocp || bsp || dsp))), trk(trk_handle->t) {
-        AIC_REQUIRE(y->kind == KIND_YOLO && (btp || ocp ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
-                    btp   ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
-                    : ocp ? "an OC-SORT pipeline takes a YOLO engine and no ReID engine"
-                          : "pipeline needs a YOLO and a ReID engine");
+    Pipeline(Model* y, Model* r, const aic_pipeline_params& p, const TrackerChoice& tc = TrackerChoice{})
+        : dev(y->dev), yolo(y), reid(r), prm(p), trk_handle(new aic_tracker(*y->dev, tracker_params(p, tc.kind != TrackerChoice::DEEPSORT))),
+          trk(trk_handle->t) {
+        const bool byte = tc.kind == TrackerChoice::BYTETRACK, oc = tc.kind == TrackerChoice::OCSORT;
+        const BsParams* bsp = tc.kind == TrackerChoice::BOTSORT ? static_cast<const BsParams*>(tc.params) : nullptr;
+        AIC_REQUIRE(y->kind == KIND_YOLO && (byte || oc ? r == nullptr : (r && r->kind == KIND_REID)), AIC_ERR_INVALID,
+                    byte ? "a ByteTrack pipeline takes a YOLO engine and no ReID engine"
+                    : oc ? "an OC-SORT pipeline takes a YOLO engine and no ReID engine"
+                         : "pipeline needs a YOLO and a ReID engine");
         AIC_REQUIRE(!bsp || bsp->dim == r->out_dim, AIC_ERR_INVALID, "feature_dim of the BoT-SORT parameters differs from the ReID engine's output");
         AIC_REQUIRE(!r || y->dev == r->dev, AIC_ERR_INVALID, "engines live on different devices");
         AIC_REQUIRE(p.frame_h > 0 && p.frame_w > 0 && p.batch > 0 && p.ring_frames >= p.batch && p.max_persons > 0,
                     AIC_ERR_INVALID, "bad pipeline geometry");
-        const int bank_streams = std::max(bs_streams, ds_streams);
-        AIC_REQUIRE(!bank_streams || (p.batch % bank_streams == 0 && p.ring_frames % bank_streams == 0), AIC_ERR_INVALID,
+        AIC_REQUIRE(!tc.streams || (p.batch % tc.streams == 0 && p.ring_frames % tc.streams == 0), AIC_ERR_INVALID,
                     "batch and ring_frames must be multiples of streams");
         AIC_REQUIRE(p.batch <= y->max_items, AIC_ERR_CAPACITY, "batch exceeds the YOLO engine's max_items");
         AIC_REQUIRE(p.max_det > 0 && p.max_det <= y->max_det_cap, AIC_ERR_CAPACITY, "max_det out of range");
         dev->use();
-        if (btp) bt.reset(new ByteTracker(*dev, *btp, bt_first_id));
-        else if (ocp) bt.reset(new OcSortTracker(*dev, *ocp, bt_first_id));
-        else if (bsp) { bt.reset(new BotSortTracker(*dev, *bsp, bt_first_id, std::max(1, bs_streams))); bs = true; bs_low = bsp->low; bs_bank = bs_streams > 0; }
-        else if (dsp) dsb.reset(new aic_deepsort_bank(*dev, *dsp, bt_first_id, ds_streams));
+        if (byte) bt.reset(new ByteTracker(*dev, *static_cast<const BtParams*>(tc.params), tc.first_id));
+        else if (oc) bt.reset(new OcSortTracker(*dev, *static_cast<const OcParams*>(tc.params), tc.first_id));
+        else if (bsp) {
+            bs = new BotSortTracker(*dev, *bsp, tc.first_id, std::max(1, tc.streams));
+            bt.reset(bs);
+            bs_low = bsp->low, bs_bank = tc.streams > 0;
+        } else if (tc.kind == TrackerChoice::DEEPSORT_BANK)
+            dsb.reset(new aic_deepsort_bank(*dev, *static_cast<const TrkDevParams*>(tc.params), tc.first_id, tc.streams));
         lane[0] = Lane{y, r, dev->s_main, dev->s_det, dev->s_reid};
         for (Chunk& c : ck) c.ln = &lane[0];
         geom = letterbox_geometry(p.frame_h, p.frame_w, y->in_h, y->in_w);
@@ -606,8 +633,24 @@ struct Pipeline {
         t_wait += now() - t0;
     }
 
-    void stage_b(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
-                 float* det_boxes, float* det_scores, int32_t* det_labels) {
+    // frame f's detector outputs (on the host behind ev_det) -> row o of the caller's arrays
+    void emit_dets(const Chunk& c, int f, int o, const RunOut& out) const {
+        const size_t md = prm.max_det;
+        if (out.n_dets) out.n_dets[o] = c.h_numdets.p[f];
+        if (out.det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, out.det_boxes + (size_t)o * md * 4);
+        if (out.det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, out.det_scores + (size_t)o * md);
+        if (out.det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, out.det_labels + (size_t)o * md);
+    }
+
+    // aic_pipeline_last_embeddings: the embeddings of the group's last frame (a blocking copy: the call's final group only, see final_group)
+    void read_last_emb(const Chunk& c) {
+        const FrameDets& fl = c.dets[c.frames - 1];
+        last_emb_n = fl.n;
+        last_emb.resize((size_t)fl.n * dim);
+        if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
+    }
+
+    void stage_b(Chunk& c, int out_base, const RunOut& out) {
         const double t0 = now();
         n_assoc_host += c.frames;
         HIP_CHECK(hipEventSynchronize(c.done));
@@ -626,15 +669,15 @@ struct Pipeline {
         trk.defer_outputs = true;
         auto emit = [&](int o) {               // the tracker's resolved outputs -> row o of the caller's arrays
             const std::vector<TrackOut>& outs = trk.resolved;
-            if (n_tracks) n_tracks[o] = (int32_t)outs.size();       // the true count: rows beyond max_persons are not stored
+            if (out.n_tracks) out.n_tracks[o] = (int32_t)outs.size();       // the true count: rows beyond max_persons are not stored
             if ((int)outs.size() > prm.max_persons) n_rows_clipped += 1;
             for (size_t k = 0; k < outs.size() && (int)k < prm.max_persons; ++k) {
                 const TrackOut& t = outs[k];
-                if (tracks6) {
-                    int32_t* r = tracks6 + ((size_t)o * prm.max_persons + k) * 6;
+                if (out.tracks6) {
+                    int32_t* r = out.tracks6 + ((size_t)o * prm.max_persons + k) * 6;
                     r[0] = t.x1, r[1] = t.y1, r[2] = t.x2, r[3] = t.y2, r[4] = t.id, r[5] = t.cls;
                 }
-                if (track_conf) track_conf[(size_t)o * prm.max_persons + k] = t.conf;
+                if (out.track_conf) out.track_conf[(size_t)o * prm.max_persons + k] = t.conf;
             }
         };
         std::vector<std::vector<uint8_t>> hasv(c.frames);
@@ -659,21 +702,11 @@ struct Pipeline {
                        have_next ? &nx : nullptr);
             const int o = out_base + f;
             if (f > 0) emit(o - 1);            // frame f-1's boxes came back behind frame f's cost-matrix sync
-            if (n_dets) n_dets[o] = c.h_numdets.p[f];
-            const size_t md = prm.max_det;
-            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
-            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
-            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
+            emit_dets(c, f, o, out);
             if (f == c.frames - 1) {
                 trk.finish_outputs();          // also fences the chunk's embedding buffers before the producer reuses them
                 emit(o);
-                if (final_group) {
-                    last_emb_n = fd.n;
-                    last_emb.resize((size_t)fd.n * dim);
-                    if (fd.n) {
-                        HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fd.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
-                    }
-                }
+                if (final_group) read_last_emb(c);
             }
         }
         trk.defer_outputs = false;             // direct users of the tracker handle get synchronous outputs
@@ -685,198 +718,93 @@ struct Pipeline {
         n_frames_done += c.frames;
     }
 
-    // Stage B with the association on the device: the frames of the group go through the tracker in epochs of k frames, two
-    // launches per epoch on the tracker stream and NO host round trip; the host picks up the group's output rows at the end.
-    void stage_b_device(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
-                        float* det_boxes, float* det_scores, int32_t* det_labels) {
+    // The group's detection arrays as the epoch kernels read them, and its per-frame counts and first rows on the host: what stage A
+    // packed into d_meta / h_meta, or the arrays the device filter wrote (their counts came back behind ev_det: prepare_b).
+    EpochDets group_dets(const Chunk& c, const int*& h_n, const int*& h_d0) const {
+        if (c.filt_dev) {
+            h_n = c.h_fn.p, h_d0 = c.h_fd0.p;
+            return EpochDets{c.d_fn.p, c.d_fd0.p, c.d_ftlwh.p, c.d_fconf.p, c.d_fcls.p, c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
+        }
+        h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n), h_d0 = reinterpret_cast<const int*>(c.h_meta.p + c.m_d0);
+        return EpochDets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
+                         reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
+                         reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
+    }
+
+    // Stage B with the association on the device: the frames of the group go through the pipeline's tracker in epochs of k frames on the
+    // tracker stream with NO host round trip; the host picks up the group's output rows at the end.  Boxes and embeddings stay where stage A
+    // left them.  The tracker shows at two points, the launch and the check behind the sync:
+    //   DeepSORT          trk.run_epochs, two launches per epoch; the live track count for the next groups' host / device choice.
+    //   an epoch tracker  (bt: ByteTrack, OC-SORT, BoT-SORT) no embeddings and no read-back of them without a ReID model.  A stream that
+    //                     stopped raises BEFORE any row of the group is copied out.
+    //   a DeepSORT bank   the group is tick-major over the cameras (DeepSortBank::run_group; the plan, a few ints per detection, is all
+    //                     that goes up).  A camera that stops in the group gets no rows from its failing frame on, the other cameras' rows
+    //                     are delivered, then the call raises.
+    void stage_b_device(Chunk& c, int out_base, const RunOut& out) {
         const double t0 = now();
-        n_assoc_dev += c.frames;
         hipStream_t s = dev->s_trk;
         const int mp = prm.max_persons;
         const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
         const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
         if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
-        trk.ensure_dim(dim);
+        if (!bt && !dsb) trk.ensure_dim(dim);
         HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's embeddings, crop validity and detection arrays are in HBM
-        EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
-                       reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
-                       reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
-        const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
-        const int* h_d0 = reinterpret_cast<const int*>(c.h_meta.p + c.m_d0);
-        if (c.filt_dev) {                                      // the arrays the device filter wrote; counts came back behind ev_det (prepare_b)
-            dets = EpochDets{c.d_fn.p, c.d_fd0.p, c.d_ftlwh.p, c.d_fconf.p, c.d_fcls.p, c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
-            h_n = c.h_fn.p, h_d0 = c.h_fd0.p;
-        }
-        EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
-                     mp, nullptr, nullptr, 0};
-        trk.run_epochs(dets, h_n, h_d0, c.frames, out, s);
+        const int *h_n, *h_d0;
+        EpochDets dets = group_dets(c, h_n, h_d0);
+        EpochOut eo{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
+                    mp, nullptr, nullptr, 0};
+        if (bt) {
+            for (int f = 0; f < c.frames; ++f)
+                AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, bt_name() + ": more than 512 detections in one frame");
+            if (!reid || !c.n_crops) dets.valid = nullptr, dets.feat = nullptr, dets.feat_n = nullptr;   // only BoT-SORT reads the group's embeddings
+            if (gmc) {                           // block matching under the detections handed to the tracker, fit, warps -> the epochs
+                gmc->match_fit(c.d_gray.p, c.frames, dets.frame_n, dets.frame_d0, dets.tlwh, true, s);
+                bs->warps = gmc->d_warps.p;
+            }
+            bt->run_epochs(dets, c.frames, eo, s);
+        } else if (dsb) dsb->t.run_group(dets, h_n, h_d0, c.frames, eo, s);   // (a frame beyond 512 rows raises before anything is launched: no host chain here)
+        else trk.run_epochs(dets, h_n, h_d0, c.frames, eo, s);
+        n_assoc_dev += c.frames;                               // the launches are queued: a refused group does not count
         HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
-        pack_shard_if_due(s);
+        pack_shard_if_due(s);                                  // (DeepSORT only: the exchange cannot be enabled on the other two)
         const double t1 = now();
         t_track += t1 - t0;                                    // host time of the association: planning + launches
         HIP_CHECK(hipStreamSynchronize(s));
         HIP_CHECK(hipEventSynchronize(c.ev_det));              // the detector's outputs of the group are on the host (inject: `done` did not cover them)
-        trk.check_epochs();
-        tracks_seen = reinterpret_cast<const DevTrkHdr*>(trk.h_tbl.p)->n_tracks;
-        c.tracks_after = tracks_seen;
+        int bad = -1;                                          // DeepSORT bank: the first camera that stopped in the group
+        if (bt) bt->check_epochs();
+        else if (dsb) bad = dsb->t.check_group();
+        else {
+            trk.check_epochs();
+            tracks_seen = reinterpret_cast<const DevTrkHdr*>(trk.h_tbl.p)->n_tracks;
+            c.tracks_after = tracks_seen;
+        }
         const double t2 = now();
         t_wait += t2 - t1;
         const int* on = reinterpret_cast<const int*>(c.h_out.p);
         const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
         const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
-        const size_t md = prm.max_det;
+        const int S = dsb ? dsb->t.n_streams : 1;
         for (int f = 0; f < c.frames; ++f) {
             const int o = out_base + f;
-            const int k = std::min(on[f], mp);
-            if (n_tracks) n_tracks[o] = on[f];                 // the true count: rows beyond max_persons are not stored
-            if (on[f] > mp) n_rows_clipped += 1;
-            if (tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, tracks6 + (size_t)o * mp * 6);
-            if (track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, track_conf + (size_t)o * mp);
-            if (n_dets) n_dets[o] = c.h_numdets.p[f];
-            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
-            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
-            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
-        }
-        const FrameDets& fl = c.dets[c.frames - 1];
-        if (final_group) {
-            last_emb_n = fl.n;
-            last_emb.resize((size_t)fl.n * dim);
-            if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
-        }
-        last_chunk = (int)(&c - &ck[0]);
-        t_track += now() - t2;
-        n_frames_done += c.frames;
-    }
-
-    // Stage B of a detector-only pipeline: the group's frames through the tracker's epochs on the tracker stream (no embeddings, no
-    // read-back of them); the host picks up the group's output rows at the end.
-    void stage_b_epochs(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets,
-                           float* det_boxes, float* det_scores, int32_t* det_labels) {
-        const double t0 = now();
-        n_assoc_dev += c.frames;
-        hipStream_t s = dev->s_trk;
-        const int mp = prm.max_persons;
-        const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
-        const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
-        if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
-        HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's detection arrays are in HBM
-        const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
-        for (int f = 0; f < c.frames; ++f)
-            AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, bt_name() + ": more than 512 detections in one frame");
-        EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
-                       reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
-                       reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), nullptr, nullptr, nullptr};
-        if (reid && c.n_crops) dets.valid = c.d_valid.p, dets.feat = c.d_emb.p, dets.feat_n = c.d_emb_n.p;   // BoT-SORT: the group's embeddings, in HBM
-        EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
-                     mp, nullptr, nullptr, 0};
-        if (gmc) {                               // block matching under the detections handed to the tracker, fit, warps -> the epochs
-            gmc->match_fit(c.d_gray.p, c.frames, dets.frame_n, dets.frame_d0, dets.tlwh, true, s);
-            static_cast<BotSortTracker*>(bt.get())->warps = gmc->d_warps.p;
-        }
-        bt->run_epochs(dets, c.frames, out, s);
-        HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
-        const double t1 = now();
-        t_track += t1 - t0;
-        HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(hipEventSynchronize(c.ev_det));              // the detector's outputs of the group are on the host
-        bt->check_epochs();
-        const double t2 = now();
-        t_wait += t2 - t1;
-        const int* on = reinterpret_cast<const int*>(c.h_out.p);
-        const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
-        const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
-        const size_t md = prm.max_det;
-        for (int f = 0; f < c.frames; ++f) {
-            const int o = out_base + f;
-            const int k = std::min(on[f], mp);
-            if (n_tracks) n_tracks[o] = on[f];
-            if (on[f] > mp) n_rows_clipped += 1;
-            if (tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, tracks6 + (size_t)o * mp * 6);
-            if (track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, track_conf + (size_t)o * mp);
-            if (n_dets) n_dets[o] = c.h_numdets.p[f];
-            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
-            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
-            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
-        }
-        if (reid && final_group) {                               // aic_pipeline_last_embeddings, as after a DeepSORT group
-            const FrameDets& fl = c.dets[c.frames - 1];
-            last_emb_n = fl.n;
-            last_emb.resize((size_t)fl.n * dim);
-            if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
-        }
-        last_chunk = (int)(&c - &ck[0]);
-        t_track += now() - t2;
-        n_frames_done += c.frames;
-    }
-
-    // Stage B of a DeepSORT bank pipeline: the group, tick-major over the cameras, through DeepSortBank::run_group on the tracker stream.
-    // Boxes and embeddings stay where stage A left them; the plan (a few ints per detection) is all that goes up.  A camera that stops
-    // in the group gets no rows from its failing frame on, the other cameras' rows are delivered, then the call raises.
-    void stage_b_bank(Chunk& c, int out_base, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets, float* det_boxes,
-                      float* det_scores, int32_t* det_labels) {
-        const double t0 = now();
-        DeepSortBank& b = dsb->t;
-        const int S = b.n_streams;
-        hipStream_t s = dev->s_trk;
-        const int mp = prm.max_persons;
-        const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
-        const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
-        EpochDets dets{reinterpret_cast<const int*>(c.d_meta.p + c.m_n), reinterpret_cast<const int*>(c.d_meta.p + c.m_d0),
-                       reinterpret_cast<const float*>(c.d_meta.p + c.m_tlwh), reinterpret_cast<const float*>(c.d_meta.p + c.m_conf),
-                       reinterpret_cast<const int*>(c.d_meta.p + c.m_cls), c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
-        const int* h_n = reinterpret_cast<const int*>(c.h_meta.p + c.m_n);
-        const int* h_d0 = reinterpret_cast<const int*>(c.h_meta.p + c.m_d0);
-        if (c.filt_dev) {                                      // the arrays the device filter wrote; counts came back behind ev_det (prepare_b)
-            dets = EpochDets{c.d_fn.p, c.d_fd0.p, c.d_ftlwh.p, c.d_fconf.p, c.d_fcls.p, c.d_valid.p, c.d_emb.p, c.d_emb_n.p};
-            h_n = c.h_fn.p, h_d0 = c.h_fd0.p;
-        }
-        if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
-        HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's embeddings, crop validity and detection arrays are in HBM
-        EpochOut out{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
-                     mp, nullptr, nullptr, 0};
-        b.run_group(dets, h_n, h_d0, c.frames, out, s);        // (a frame beyond 512 rows raises before anything is launched: no host chain here)
-        n_assoc_dev += c.frames;
-        HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, obytes, hipMemcpyDeviceToHost, s));
-        const double t1 = now();
-        t_track += t1 - t0;                                    // host time of the association: planning + launches
-        HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(hipEventSynchronize(c.ev_det));              // the detector's outputs of the group are on the host (inject: `done` did not cover them)
-        const int bad = b.check_group();
-        const double t2 = now();
-        t_wait += t2 - t1;
-        const int* on = reinterpret_cast<const int*>(c.h_out.p);
-        const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
-        const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
-        const size_t md = prm.max_det;
-        for (int f = 0; f < c.frames; ++f) {
-            const int o = out_base + f;
-            const int m = f / S < b.grp_good[f % S] ? on[f] : 0;   // a stopped camera: nothing from its failing frame on
+            const int m = dsb && f / S >= dsb->t.grp_good[f % S] ? 0 : on[f];   // a stopped camera: nothing from its failing frame on
             const int k = std::min(m, mp);
-            if (n_tracks) n_tracks[o] = m;                     // the true count: rows beyond max_persons are not stored
+            if (out.n_tracks) out.n_tracks[o] = m;             // the true count: rows beyond max_persons are not stored
             if (m > mp) n_rows_clipped += 1;
-            if (tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, tracks6 + (size_t)o * mp * 6);
-            if (track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, track_conf + (size_t)o * mp);
-            if (n_dets) n_dets[o] = c.h_numdets.p[f];
-            if (det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, det_boxes + (size_t)o * md * 4);
-            if (det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, det_scores + (size_t)o * md);
-            if (det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, det_labels + (size_t)o * md);
+            if (out.tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, out.tracks6 + (size_t)o * mp * 6);
+            if (out.track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, out.track_conf + (size_t)o * mp);
+            emit_dets(c, f, o, out);
         }
-        const FrameDets& fl = c.dets[c.frames - 1];
-        if (final_group) {
-            last_emb_n = fl.n;
-            last_emb.resize((size_t)fl.n * dim);
-            if (fl.n) HIP_CHECK(hipMemcpy(last_emb.data(), c.d_emb.p + (size_t)fl.crop0 * dim, last_emb.size() * 4, hipMemcpyDeviceToHost));
-        }
+        if (final_group && (!bt || reid)) read_last_emb(c);   // (a detector-only pipeline computes no embeddings)
         last_chunk = (int)(&c - &ck[0]);
         t_track += now() - t2;
         n_frames_done += c.frames;
-        AIC_REQUIRE(bad < 0, b.stop_code[bad], "DeepSORT bank: " + b.stop_msg[bad]);
+        AIC_REQUIRE(bad < 0, dsb->t.stop_code[bad], "DeepSORT bank: " + dsb->t.stop_msg[bad]);
     }
 
     // passes > 1: the same ring range is walked `passes` times back to back as ONE continuous stream (outputs of a
     // later pass overwrite the rows of the earlier one): only the very last group of the call has an un-overlapped tail.
-    void run(int slot, int count, int32_t* n_tracks, int32_t* tracks6, float* track_conf, int32_t* n_dets, float* det_boxes,
-             float* det_scores, int32_t* det_labels, int passes = 1) {
+    void run(int slot, int count, const RunOut& out, int passes = 1) {
         AIC_REQUIRE(slot >= 0 && count >= 0 && slot + count <= prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
         AIC_REQUIRE(passes >= 1, AIC_ERR_INVALID, "passes must be >= 1");
         const int S = bt ? bt->streams() : dsb ? dsb->t.n_streams : 1;    // > 1: ring and run ranges are tick-major over S streams
@@ -982,15 +910,9 @@ struct Pipeline {
                 final_group = k == nchunks - 1;
                 if (ck[k % nck].filt_dev) prepare_b(ck[k % nck]);
                 ck[k % nck].prev_dev_mode = ck[k % nck].dev_mode;
-                if (bt) stage_b_epochs(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
-                else if (dsb) stage_b_bank(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
-                else if (ck[k % nck].dev_mode) {
-                    trk.dev_assoc = true;
-                    stage_b_device(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
-                } else {
-                    trk.dev_assoc = false;
-                    stage_b(ck[k % nck], goff[k], n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
-                }
+                if (!bt && !dsb) trk.dev_assoc = ck[k % nck].dev_mode;
+                if (bt || dsb || ck[k % nck].dev_mode) stage_b_device(ck[k % nck], goff[k], out);   // (epoch trackers and banks have no host chain)
+                else stage_b(ck[k % nck], goff[k], out);
                 group_times.push_back(GroupTime{glen[k], submit_t[k], now()});
                 {
                     std::lock_guard<std::mutex> lk(mu);
@@ -1018,9 +940,7 @@ using namespace aic;
 
 struct aic_pipeline {
     Pipeline p;
-    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const BtParams* b = nullptr, int first_id = 1, const OcParams* o = nullptr,
-                 const BsParams* bs = nullptr, int bs_streams = 0, const aic::TrkDevParams* ds = nullptr, int ds_streams = 0)
-        : p(y, r, q, b, first_id, o, bs, bs_streams, ds, ds_streams) {}
+    aic_pipeline(Model* y, Model* r, const aic_pipeline_params& q, const TrackerChoice& tc = TrackerChoice{}) : p(y, r, q, tc) {}
 };
 
 extern "C" {
@@ -1037,7 +957,7 @@ int aic_pipeline_create_bytetrack(aic_model* yolo, const aic_pipeline_params* p,
         AIC_REQUIRE(yolo && p && bp && out, AIC_ERR_INVALID, "NULL argument");
         int first = 1;
         const BtParams b = bytetrack_params(*bp, &first);
-        *out = new aic_pipeline(&yolo->m, nullptr, *p, &b, first);
+        *out = new aic_pipeline(&yolo->m, nullptr, *p, TrackerChoice{TrackerChoice::BYTETRACK, &b, first, 0});
     });
 }
 
@@ -1046,7 +966,7 @@ int aic_pipeline_create_ocsort(aic_model* yolo, const aic_pipeline_params* p, co
         AIC_REQUIRE(yolo && p && op && out, AIC_ERR_INVALID, "NULL argument");
         int first = 1;
         const OcParams o = ocsort_params(*op, &first);
-        *out = new aic_pipeline(&yolo->m, nullptr, *p, nullptr, first, &o);
+        *out = new aic_pipeline(&yolo->m, nullptr, *p, TrackerChoice{TrackerChoice::OCSORT, &o, first, 0});
     });
 }
 
@@ -1055,7 +975,7 @@ int aic_pipeline_create_botsort(aic_model* yolo, aic_model* reid, const aic_pipe
         AIC_REQUIRE(yolo && reid && p && bp && out, AIC_ERR_INVALID, "NULL argument");
         int first = 1;
         const BsParams b = botsort_params(*bp, &first);
-        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b);
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, TrackerChoice{TrackerChoice::BOTSORT, &b, first, 0});
     });
 }
 
@@ -1066,7 +986,7 @@ int aic_pipeline_create_botsort_bank(aic_model* yolo, aic_model* reid, const aic
         int first = 1;
         const BsParams b = botsort_params(*bp, &first);
         AIC_REQUIRE(streams >= 1 && streams <= BANK_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
-        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, &b, streams);
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, TrackerChoice{TrackerChoice::BOTSORT, &b, first, streams});
     });
 }
 
@@ -1080,7 +1000,7 @@ int aic_pipeline_create_deepsort_bank(aic_model* yolo, aic_model* reid, const ai
         tp.feature_dim = reid->m.out_dim;
         int first = 1;
         const TrkDevParams t = deepsort_bank_params(tp, streams, &first);   // the rejections of aic_deepsort_bank_create
-        *out = new aic_pipeline(&yolo->m, &reid->m, *p, nullptr, first, nullptr, nullptr, 0, &t, streams);
+        *out = new aic_pipeline(&yolo->m, &reid->m, *p, TrackerChoice{TrackerChoice::DEEPSORT_BANK, &t, first, streams});
     });
 }
 
@@ -1130,7 +1050,7 @@ int aic_pipeline_run(aic_pipeline* p, int slot, int count, int32_t* n_tracks, in
                      int32_t* n_dets, float* det_boxes, float* det_scores, int32_t* det_labels) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL pipeline");
-        p->p.run(slot, count, n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels);
+        p->p.run(slot, count, RunOut{n_tracks, tracks6, track_conf, n_dets, det_boxes, det_scores, det_labels});
     });
 }
 
@@ -1138,7 +1058,7 @@ int aic_pipeline_run_passes(aic_pipeline* p, int slot, int count, int passes, in
                             int32_t* n_dets) {
     return guarded([&] {
         AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL handle");
-        p->p.run(slot, count, n_tracks, tracks6, track_conf, n_dets, nullptr, nullptr, nullptr, passes);
+        p->p.run(slot, count, RunOut{n_tracks, tracks6, track_conf, n_dets, nullptr, nullptr, nullptr}, passes);
     });
 }
 
@@ -1169,7 +1089,7 @@ int aic_pipeline_run_from_host_passes(aic_pipeline* p, const uint8_t* frames_bgr
         q.host_frames = frames_bgr;
         q.host_slot0 = slot;
         try {
-            q.run(slot, count, n_tracks, tracks6, track_conf, n_dets, nullptr, nullptr, nullptr, passes);
+            q.run(slot, count, RunOut{n_tracks, tracks6, track_conf, n_dets, nullptr, nullptr, nullptr}, passes);
         } catch (...) {
             q.host_frames = nullptr;
             throw;
@@ -1316,7 +1236,7 @@ int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links) {
         AIC_REQUIRE(p->p.dsb || (p->p.bt && p->p.bs && p->p.bs_bank), AIC_ERR_INVALID,
                     "link_cameras applies to BoT-SORT and DeepSORT bank pipelines (aic_pipeline_create_botsort_bank, aic_pipeline_create_deepsort_bank) only");
         // on the tracker stream, behind the last run call's epochs
-        const int l = p->p.dsb ? x->x.link(p->p.dsb->t) : x->x.link(*static_cast<BotSortTracker*>(p->p.bt.get()));
+        const int l = p->p.dsb ? x->x.link(p->p.dsb->t) : x->x.link(*p->p.bs);
         if (n_links) *n_links = l;
     });
 }
@@ -1378,7 +1298,7 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
             AIC_REQUIRE(p->p.bs || p->p.dsb, AIC_ERR_INVALID, "option epoch_frames applies to BoT-SORT and DeepSORT bank pipelines only");
             AIC_REQUIRE(value >= 0 && value <= TRK_KMAX, AIC_ERR_INVALID, "epoch_frames must be in 0..16 (0 = default)");
             if (p->p.dsb) p->p.dsb->t.epoch_frames = value;
-            else static_cast<BotSortTracker*>(p->p.bt.get())->epoch_frames = value;
+            else p->p.bs->epoch_frames = value;
         }
         else if (k == "gmc") {
             AIC_REQUIRE(p->p.bs, AIC_ERR_INVALID, "option gmc applies to BoT-SORT pipelines only");
@@ -1390,7 +1310,7 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
                             "gmc: the frame holds no block, or more than 2048, at this downscale");
                 q.dev->use();
                 HIP_CHECK(hipDeviceSynchronize());
-                static_cast<BotSortTracker*>(q.bt.get())->warps = nullptr;   // (it pointed into the estimator that goes away)
+                q.bs->warps = nullptr;   // (it pointed into the estimator that goes away)
                 q.gmc.reset();
                 if (value) {
                     q.gmc.reset(new CameraMotionEstimator(*q.dev, q.prm.frame_h, q.prm.frame_w, value, 8, q.bt->streams()));

@@ -295,6 +295,40 @@ def test_pipeline_streams_rejections():
     pipe.close()
 
 
+def test_pipeline_stream_that_exhausts_max_tracks_delivers_nothing_of_its_group():
+    """max_tracks 16, at most 5 planted boxes per camera; camera 1 gets 18 more boxes in tick 2: more rows than its table holds.  An epoch
+    tracker's check raises BEFORE any row of the launch group is copied out (the DeepSORT bank pipeline delivers the other cameras' rows and
+    then raises: test_a_camera_that_exhausts_max_tracks_stops_alone): the caller's track arrays are untouched, run calls are refused until
+    reset_stream(1)."""
+    L = pkg("_lib")
+    lib = L.load()
+    ypath, _ = pkg("engine_file").ensure_seeded_engines(ROOT)
+    planted = [[(b[:5], c[:5], k[:5]) for b, c, k in cam[:4]] for cam in _planted()]
+    gx, gy = np.meshgrid(np.arange(9) * 135.0 + 40.0, np.arange(2) * 300.0 + 60.0)
+    more = np.stack([gx.ravel(), gy.ravel(), gx.ravel() + 60.0, gy.ravel() + 140.0], 1).astype(np.float32)
+    b, c, k = planted[1][2]
+    planted[1][2] = (np.concatenate([b, more]), np.concatenate([c, np.full(18, 0.8, np.float32)]), np.concatenate([k, np.zeros(18, np.int32)]))
+    pipe = _pipe(ypath, "bytetrack", 12, 12, streams=3, max_tracks=16)
+    pipe.option("taper", 0)                                      # the call is one launch group
+    pipe.upload(0, np.zeros((12, 720, 1280, 3), np.uint8))
+    pipe.inject(0, [planted[i % 3][i // 3] for i in range(12)])  # tick-major: slot t * 3 + s
+    mp = pipe.max_persons
+    nt, r6, cf = np.full(12, -7, np.int32), np.full((12, mp, 6), -7, np.int32), np.full((12, mp), -7.0, np.float32)
+    args = (pipe._h, 0, 12, L.ptr(nt), L.ptr(r6), L.ptr(cf), None, None, None, None)
+    assert lib.aic_pipeline_run(*args) == L.ERR_CAPACITY
+    msg = lib.aic_last_error()
+    assert b"stream 1" in msg and b"max_tracks" in msg, msg
+    assert (nt == -7).all() and (r6 == -7).all() and (cf == -7.0).all()     # nothing of the group was delivered
+    assert lib.aic_pipeline_run(*args) == L.ERR_INVALID
+    assert (nt == -7).all() and (r6 == -7).all() and (cf == -7.0).all()
+    pipe.reset_stream(1)
+    planted[1][2] = (b, c, k)                                    # the camera reconnects to a scene its table holds
+    pipe.inject(0, [planted[i % 3][i // 3] for i in range(12)])
+    assert lib.aic_pipeline_run(*args) == L.OK
+    assert (nt >= 0).all()
+    pipe.close()
+
+
 def test_cli_inputs_writes_one_output_per_stream(tmp_path):
     ypath, _ = pkg("engine_file").ensure_seeded_engines(ROOT)
     cli = pkg("cli")
