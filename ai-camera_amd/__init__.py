@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "zones", "render", "gmc", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "zones", "render", "gmc", "frames", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):

@@ -17,6 +17,9 @@ OK, ERR_INVALID, ERR_NOT_FOUND, ERR_RUNTIME, ERR_NO_DEVICE, ERR_CAPACITY, ERR_FO
 HOST, DEVICE = 0, 1
 F32, F16 = 0, 1
 MODEL_YOLO, MODEL_REID = 1, 2
+PIX_BGR24, PIX_NV12, PIX_I420 = 0, 1, 2
+YUV_BT601, YUV_BT709 = 0, 1
+YUV_LIMITED, YUV_FULL = 0, 1
 PROF_CLASSES = ("conv_igemm", "conv_direct", "misc", "letterbox", "crop_resize", "decode_nms", "tracker")
 
 
@@ -246,6 +249,10 @@ _SIGS = {
     "aic_render_set_masks": (_I, [_P, _I, _I, _P, _P]),
     "aic_render_rects": (_I, [_P, _P, _I, _P, _P]),
     "aic_render_frames": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "aic_yuv_coeffs": (_I, [_I, _I, _P, _P, _P]),
+    "aic_frames_to_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
+    "aic_frames_from_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
+    "aic_pipeline_read_frames": (_I, [_P, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

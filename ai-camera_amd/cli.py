@@ -5,7 +5,9 @@ Frame sources (`--input`; the step BEFORE the path):
                                                         WHEN cv2 is importable (probed at start; it is not in this image)
     synthetic:WxH:persons:frames[:seed]                 the seeded scene of ai-camera_amd/synthetic.py
     path/to/frames.npy                                  uint8 [T,H,W,3] BGR (memory-mapped)
-    raw:WxH:path                                        headerless BGR24 frames (memory-mapped), e.g. `ffmpeg -pix_fmt bgr24 -f rawvideo`
+    raw:WxH:path                                        headerless BGR24 frames (memory-mapped), e.g. `ffmpeg -pix_fmt bgr24 -f rawvideo`;
+                                                        with `--pixel_format nv12|i420` (`--yuv_matrix`, `--yuv_range`) tightly packed 4:2:0
+                                                        frames, memory-mapped as [T, H*3/2, W] (`ffmpeg -pix_fmt nv12 -f rawvideo`)
 The loop body is the reference's (detect -> tracker update, timed the same way, aicamera_tracker.py:175,201-207).  `--batch N`
 (N > 1, not a reference flag) runs the same loop through the batched pipeline with double-buffered page-locked staging
 (TrackingPipeline.stream) instead of one synchronous call pair per frame.
@@ -17,6 +19,11 @@ the tracks always go to a `.jsonl` next to it.  `--show_display` needs cv2 (imsh
 With `--inputs` the S frames of a tick and their tracks go through ONE `render.Renderer` call; `--redact
 {off,box,head}`, `--redact_style mosaic:16|...|fill`, `--masks FILE.json` and `--draw_zones` (with `--zones`) pixelate or fill the tracked
 objects, black out fixed regions and draw the zones, with `--input` as well; with none of them the written pixels are the overlay's.
+
+Pixel formats: with `--batch N` (and `--inputs`) YUV frames cross PCIe as they are and the pipeline unpacks them
+into its BGR ring on the device; frames that are saved or shown come back through TrackingPipeline.read_frames.  With `--batch 1` each
+frame goes through frames.to_bgr before the plugin classes, whose signatures stay BGR.  `--output_pixel_format nv12` makes the headerless
+writer append NV12 frames (`.nv12`, converted by frames.from_bgr after rendering) -- what an encoder takes.
 """
 from __future__ import annotations
 
@@ -28,6 +35,7 @@ from pathlib import Path
 import numpy as np
 
 from . import config, synthetic, visualization
+from . import frames as pixfmt
 from .detector import YOLODetector
 from .deepsort_tracker import DeepSORT
 
@@ -78,7 +86,17 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--dtype", type=str, default="fp16", choices=("fp16", "fp32"))
     p.add_argument("--batch", type=int, default=1, help="> 1: batched pipeline with double-buffered pinned staging")
+    p.add_argument("--pixel_format", type=str, default="bgr24", choices=("bgr24", "nv12", "i420"),
+                   help="pixel format of raw:WxH:path sources; nv12 / i420: tightly packed 4:2:0 frames of W*H*3/2 bytes, unpacked on the device")
+    p.add_argument("--yuv_matrix", type=str, default="bt601", choices=("bt601", "bt709"), help="YUV matrix of --pixel_format / --output_pixel_format")
+    p.add_argument("--yuv_range", type=str, default="limited", choices=("limited", "full"), help="YUV range of --pixel_format / --output_pixel_format")
+    p.add_argument("--output_pixel_format", type=str, default="bgr24", choices=("bgr24", "nv12"),
+                   help="nv12: the annotated frames are appended as NV12 to a headerless <name>.nv12 file (+ .json) instead of BGR24")
     args = p.parse_args(argv)
+    if args.pixel_format != "bgr24":
+        specs = args.inputs.split(",") if args.inputs is not None else [args.input]
+        if not all(spec and spec.startswith("raw:") for spec in specs):
+            p.error("--pixel_format nv12 / i420 applies to raw:WxH:path sources only")
     if args.gmc and args.tracker != "botsort":
         p.error("--gmc needs --tracker botsort")
     if args.link_cameras and (args.inputs is None or args.tracker not in ("botsort", "deepsort_bank")):
@@ -95,8 +113,24 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     return args
 
 
-def frame_source(spec, webcam_id=0, cv2=None):
-    """-> (name, frame iterator, (width, height, fps) or None when unknown before the first frame)."""
+def raw_frames(path, w, h, pixel_format="bgr24"):
+    """The headerless file memory-mapped as uint8 [T, H, W, 3] (bgr24; a trailing partial frame is ignored) or [T, H*3/2, W] (nv12 / i420:
+    W and H even, and the file must hold a whole number of frames)."""
+    if pixel_format == "bgr24":
+        arr = np.memmap(path, np.uint8, "r")
+        n = arr.size // (h * w * 3)
+        return arr[:n * h * w * 3].reshape(n, h, w, 3)
+    if w <= 0 or h <= 0 or w % 2 or h % 2:
+        raise SystemExit(f"Error: {pixel_format} frames need an even width and height, not {w}x{h}")
+    fb, size = pixfmt.frame_bytes(pixel_format, h, w), Path(path).stat().st_size
+    if size == 0 or size % fb:
+        raise SystemExit(f"Error: {path} holds {size} bytes, not a whole number of {w}x{h} {pixel_format} frames of {fb} bytes")
+    return np.memmap(path, np.uint8, "r").reshape(size // fb, h * 3 // 2, w)
+
+
+def frame_source(spec, webcam_id=0, cv2=None, pixel_format="bgr24"):
+    """-> (name, frame iterator, (width, height, fps) or None when unknown before the first frame).  pixel_format: of raw: sources, whose
+    frames are then [H*3/2, W]."""
     if spec is not None and spec.startswith("synthetic:"):
         parts = spec.split(":")
         w, h = (int(v) for v in parts[1].lower().split("x"))
@@ -109,10 +143,8 @@ def frame_source(spec, webcam_id=0, cv2=None):
         w, h = (int(v) for v in size.lower().split("x"))
         if not Path(path).exists():
             raise SystemExit(f"Error: Input video file not found: {path}")
-        arr = np.memmap(path, np.uint8, "r")
-        n = arr.size // (h * w * 3)
-        arr = arr[:n * h * w * 3].reshape(n, h, w, 3)
-        return Path(path).stem, (np.ascontiguousarray(arr[i]) for i in range(n)), (w, h, float(config.DEFAULT_OUTPUT_FPS))
+        arr = raw_frames(path, w, h, pixel_format)
+        return Path(path).stem, (np.ascontiguousarray(arr[i]) for i in range(len(arr))), (w, h, float(config.DEFAULT_OUTPUT_FPS))
     if spec is not None and spec.endswith(".npy"):
         path = Path(spec)
         if not path.exists():
@@ -147,12 +179,14 @@ def frame_source(spec, webcam_id=0, cv2=None):
 
 
 class FrameWriter:
-    """Annotated frames: cv2.VideoWriter when cv2 is there (mp4v / XVID as aicamera_tracker.py:155-156), else headerless BGR24."""
+    """Annotated frames: cv2.VideoWriter when cv2 is there (mp4v / XVID as aicamera_tracker.py:155-156), else headerless BGR24.
+    pixel_format="nv12": always headerless, NV12 (frames.from_bgr with the given matrix / range), suffix .nv12."""
 
-    def __init__(self, path_stem: Path, size, cv2=None, filename=None):
+    def __init__(self, path_stem: Path, size, cv2=None, filename=None, pixel_format="bgr24", yuv_matrix="bt601", yuv_range="limited"):
         self.cv2, self.raw, self.vw, self.frames = cv2, None, None, 0
+        self.yuv = None if pixel_format == "bgr24" else (pixel_format, yuv_matrix, yuv_range)
         w, h, fps = size
-        if cv2 is not None:
+        if cv2 is not None and self.yuv is None:
             name = filename or path_stem.name + ".mp4"
             if not name.lower().endswith((".mp4", ".avi")):
                 name += ".mp4"
@@ -163,14 +197,18 @@ class FrameWriter:
                 print(f"Error: Could not open video writer for {self.path}. Video will not be saved.")
                 self.vw = None
         else:
-            self.path = path_stem.parent / ((filename or path_stem.name) + ".bgr24")
+            self.path = path_stem.parent / ((filename or path_stem.name) + "." + pixel_format)
             self.raw = open(self.path, "wb")
-            self.meta = dict(width=w, height=h, fps=fps, pixel_format="bgr24")
+            self.meta = dict(width=w, height=h, fps=fps, pixel_format=pixel_format)
+            if self.yuv is not None:
+                self.meta.update(yuv_matrix=yuv_matrix, yuv_range=yuv_range)
         print(f"Output video will be saved to: {self.path}")
 
     def write(self, frame):
         if self.vw is not None:
             self.vw.write(frame)
+        elif self.raw is not None and self.yuv is not None:
+            self.raw.write(pixfmt.from_bgr(frame, self.yuv[0], matrix=self.yuv[1], range=self.yuv[2]).tobytes())
         elif self.raw is not None:
             self.raw.write(np.ascontiguousarray(frame).tobytes())
         self.frames += 1
@@ -310,7 +348,9 @@ def main_streams(args, cv2):
     """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank /
     deepsort_bank for --tracker botsort / deepsort_bank), their frames interleaved tick by tick."""
     from .pipeline import TrackingPipeline
-    sources = [frame_source(spec, args.webcam_id, cv2) for spec in args.inputs.split(",") if spec]
+    sources = [frame_source(spec, args.webcam_id, cv2, args.pixel_format) for spec in args.inputs.split(",") if spec]
+    yuv_in = dict(pixel_format=args.pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
+    yuv_out = dict(pixel_format=args.output_pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
     S = len(sources)
     size = sources[0][2]
     if any(src[2][:2] != size[:2] for src in sources):
@@ -327,17 +367,17 @@ def main_streams(args, cv2):
             reid = HipEngine(args.reid_engine, device=dev, dtype=args.dtype, max_items=batch * 64, warm_up=False)   # as the single-source path
             pipe = TrackingPipeline.botsort_bank(args.yolo_engine, reid, (size[1], size[0]), cameras=S, gmc=args.gmc, batch=batch,
                                                  ring_frames=batch, max_persons=512, max_tracks=512, device=dev, dtype=args.dtype,
-                                                 conf_thresh=args.conf_thresh)
+                                                 conf_thresh=args.conf_thresh, **yuv_in)
         elif args.tracker == "deepsort_bank":
             from .hip_engine import HipEngine
             reid = HipEngine(args.reid_engine, device=dev, dtype=args.dtype, max_items=batch * 64, warm_up=False)   # as the single-source path
             pipe = TrackingPipeline.deepsort_bank(args.yolo_engine, reid, (size[1], size[0]), cameras=S, batch=batch, ring_frames=batch,
                                                   max_persons=512, max_tracks=512, device=dev, dtype=args.dtype,
-                                                  conf_thresh=args.conf_thresh)
+                                                  conf_thresh=args.conf_thresh, **yuv_in)
         else:
             pipe = TrackingPipeline(args.yolo_engine, None, (size[1], size[0]), batch=batch, ring_frames=batch, max_persons=512,
                                     max_tracks=512, device=dev, dtype=args.dtype, conf_thresh=args.conf_thresh,
-                                    tracker=args.tracker, streams=S)
+                                    tracker=args.tracker, streams=S, **yuv_in)
     except Exception as e:
         print(f"Error initializing YOLO Detector: {e}")
         return 1
@@ -350,7 +390,7 @@ def main_streams(args, cv2):
         for k, (name, _, _) in enumerate(sources):
             stem = out_dir / f"{name}_tracked_{stamp}_s{k}"
             outs[k] = open(str(stem) + ".jsonl", "w")
-            writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None)
+            writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None, **yuv_out)
     pipe.link_after_run = bool(args.link_cameras)
     zones = None
     if args.zones:
@@ -376,7 +416,7 @@ def main_streams(args, cv2):
     tick = []                                                                     # the tick's (tracks, labelled tracks) so far
     batch = np.empty((S, size[1], size[0], 3), np.uint8) if output is not None else None      # its frames: copied as they arrive
     try:
-        for frame, tracks in pipe.stream(ticks):
+        for frame, tracks in pipe.stream(ticks, read_back=output is not None):   # (YUV sources: the frames drawn on come back from the ring)
             k, idx = n % S, n // S
             n += 1
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
@@ -424,7 +464,10 @@ def main(argv=None):
     if args.inputs is not None:
         return main_streams(args, cv2)
     print("Initializing YOLOv8 Detector...")
-    name, frames, size = frame_source(args.input, args.webcam_id, cv2)
+    name, frames, size = frame_source(args.input, args.webcam_id, cv2, args.pixel_format)
+    yuv_in = dict(pixel_format=args.pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
+    if args.pixel_format != "bgr24" and args.batch <= 1:       # the plugin classes' signatures stay BGR: convert frame by frame
+        frames = (pixfmt.to_bgr(f, args.pixel_format, matrix=args.yuv_matrix, range=args.yuv_range)[0] for f in frames)
     bytetrack = args.tracker == "bytetrack"
     ocsort = args.tracker == "ocsort"
     botsort = args.tracker == "botsort"
@@ -441,7 +484,7 @@ def main(argv=None):
             reid = None if bytetrack or ocsort else HipEngine(args.reid_engine, device=dev_id, dtype=args.dtype, max_items=args.batch * 64, warm_up=False)   # arena for 64 crops per frame; busier groups take more ReID rounds
             pipe = TrackingPipeline(args.yolo_engine, reid, (size[1], size[0]), batch=args.batch, ring_frames=args.batch,
                                     max_persons=512, max_tracks=512, device=dev_id, dtype=args.dtype, conf_thresh=args.conf_thresh,
-                                    tracker=args.tracker, gmc=args.gmc)
+                                    tracker=args.tracker, gmc=args.gmc, **yuv_in)
         else:
             detector = YOLODetector(engine_path=args.yolo_engine, conf_threshold=args.conf_thresh, device=args.device, dtype=args.dtype)
     except Exception as e:   # aicamera_tracker.py:94-97
@@ -484,7 +527,7 @@ def main(argv=None):
         out_dir.mkdir(parents=True, exist_ok=True)
         stem = out_dir / f"{name}_tracked_{time.strftime('%Y%m%d-%H%M%S')}"
         out_f = open(str(stem) + ".jsonl", "w")
-        writer = FrameWriter(stem, size, cv2, args.output_filename)
+        writer = FrameWriter(stem, size, cv2, args.output_filename, args.output_pixel_format, args.yuv_matrix, args.yuv_range)
     if args.show_display and cv2 is None:
         print("--show_display ignored: no display backend (cv2) here.")
     frame_idx, total, display_fps = 0, 0.0, 0.0
@@ -531,7 +574,7 @@ def main(argv=None):
     def batched():
         nonlocal total
         t_prev = time.time()
-        for frame, tracks in pipe.stream(frames):
+        for frame, tracks in pipe.stream(frames, read_back=writer is not None or (args.show_display and cv2 is not None)):
             now = time.time()
             total += now - t_prev      # the staging thread reads ahead; per-frame time = the stream's pace
             yield frame, tracks

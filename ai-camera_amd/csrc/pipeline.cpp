@@ -21,6 +21,7 @@
 #include "xcam.hpp"
 #include "deepsort_bank.hpp"
 #include "conv_common.hpp"
+#include "yuv.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -208,6 +209,24 @@ struct Pipeline {
     static constexpr int NCOPY = 8;   // H2D copies in flight: a group's frames cross PCIe up to copy_ahead groups before its launch group is issued
     static constexpr int copy_ahead = 2;
     hipEvent_t ev_copy[NCOPY] = {};
+    // aic_pipeline_option("pixel_format" / "yuv_matrix" / "yuv_range"): host frames arrive as 4:2:0 YUV (h * w * 3 / 2 bytes, tight).  They are
+    // copied into yuv_ring (one slot per ring slot, allocated on first use) and unpacked into the BGR ring slot on the copy stream, directly
+    // behind their copy (yuv.hpp); the ring itself stays BGR and nothing after it changes.
+    int pix_format = AIC_PIX_BGR24, yuv_matrix = AIC_YUV_BT601, yuv_range = AIC_YUV_LIMITED;
+    DevBuf<uint8_t> yuv_ring;
+    size_t host_frame_bytes() const { return pix_format == AIC_PIX_BGR24 ? frame_bytes : frame_bytes / 2; }
+    // `count` host frames (in the pipeline's pixel format) into the ring slots from `slot` on, on stream st
+    void copy_frames_in(int slot, const uint8_t* host, int count, hipStream_t st) {
+        if (pix_format == AIC_PIX_BGR24) {
+            HIP_CHECK(hipMemcpyAsync(ring.p + (size_t)slot * frame_bytes, host, (size_t)count * frame_bytes, hipMemcpyHostToDevice, st));
+            return;
+        }
+        const YuvLayout L = yuv_layout(count, prm.frame_h, prm.frame_w, pix_format, 0, 0);
+        if (!yuv_ring.p) yuv_ring.alloc(L.frame_stride * prm.ring_frames);
+        uint8_t* staged = yuv_ring.p + (size_t)slot * L.frame_stride;
+        HIP_CHECK(hipMemcpyAsync(staged, host, (size_t)count * L.frame_stride, hipMemcpyHostToDevice, st));
+        launch_yuv_to_bgr(staged, count, L, yuv_coeffs(yuv_matrix, yuv_range), ring.p + (size_t)slot * frame_bytes, st);
+    }
     std::vector<int> plan_off, plan_len;   // launch groups of the running call (ring slot offset, frames)
     int plan_slot = 0, copies_issued = 0;
     int host_slot0 = 0;
@@ -339,8 +358,7 @@ struct Pipeline {
                     if (plan_off[i] < plan_off[j] + plan_len[j] && plan_off[j] < plan_off[i] + plan_len[i])
                         HIP_CHECK(hipStreamWaitEvent(s_copy, ck[i % nck].done, 0));
             const int slot = plan_slot + plan_off[j];
-            HIP_CHECK(hipMemcpyAsync(ring.p + (size_t)slot * frame_bytes, host_frames + (size_t)(slot - host_slot0) * frame_bytes,
-                                     (size_t)plan_len[j] * frame_bytes, hipMemcpyHostToDevice, s_copy));
+            copy_frames_in(slot, host_frames + (size_t)(slot - host_slot0) * host_frame_bytes(), plan_len[j], s_copy);
             HIP_CHECK(hipEventRecord(ev_copy[j % NCOPY], s_copy));
             copies_issued += 1;
         }
@@ -1025,7 +1043,24 @@ int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames, int co
         Pipeline& q = p->p;
         AIC_REQUIRE(slot >= 0 && slot + count <= q.prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
         q.dev->use();
-        HIP_CHECK(hipMemcpy(q.ring.p + (size_t)slot * q.frame_bytes, frames, (size_t)count * q.frame_bytes, hipMemcpyHostToDevice));
+        if (q.pix_format == AIC_PIX_BGR24) {
+            HIP_CHECK(hipMemcpy(q.ring.p + (size_t)slot * q.frame_bytes, frames, (size_t)count * q.frame_bytes, hipMemcpyHostToDevice));
+            return;
+        }
+        if (count == 0) return;
+        q.copy_frames_in(slot, frames, count, q.s_copy);
+        HIP_CHECK(hipStreamSynchronize(q.s_copy));
+    });
+}
+
+int aic_pipeline_read_frames(aic_pipeline* p, int slot, int count, uint8_t* out_bgr) {
+    return guarded([&] {
+        AIC_REQUIRE(p && out_bgr && count >= 0, AIC_ERR_INVALID, "bad argument");
+        Pipeline& q = p->p;
+        AIC_REQUIRE(slot >= 0 && slot + count <= q.prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
+        if (count == 0) return;
+        q.dev->use();
+        HIP_CHECK(hipMemcpy(out_bgr, q.ring.p + (size_t)slot * q.frame_bytes, (size_t)count * q.frame_bytes, hipMemcpyDeviceToHost));
     });
 }
 
@@ -1250,6 +1285,22 @@ int aic_pipeline_option(aic_pipeline* p, const char* key, int value) {
             if (!value) p->p.head_ramp = false;
         }
         else if (k == "split_streams") p->p.split_streams = value != 0;
+        else if (k == "pixel_format") {
+            AIC_REQUIRE(value == AIC_PIX_BGR24 || value == AIC_PIX_NV12 || value == AIC_PIX_I420, AIC_ERR_INVALID,
+                        "pixel_format: 0 BGR24, 1 NV12, 2 I420");
+            AIC_REQUIRE(value == AIC_PIX_BGR24 || (p->p.prm.frame_h % 2 == 0 && p->p.prm.frame_w % 2 == 0), AIC_ERR_INVALID,
+                        "pixel_format: 4:2:0 frames need an even frame_h and frame_w");
+            if (value != AIC_PIX_BGR24) yuv_layout(1, p->p.prm.frame_h, p->p.prm.frame_w, value, 0, 0);     // the size limits of the conversion
+            p->p.pix_format = value;
+        }
+        else if (k == "yuv_matrix") {
+            AIC_REQUIRE(value == AIC_YUV_BT601 || value == AIC_YUV_BT709, AIC_ERR_INVALID, "yuv_matrix: 0 BT.601, 1 BT.709");
+            p->p.yuv_matrix = value;
+        }
+        else if (k == "yuv_range") {
+            AIC_REQUIRE(value == AIC_YUV_LIMITED || value == AIC_YUV_FULL, AIC_ERR_INVALID, "yuv_range: 0 limited, 1 full");
+            p->p.yuv_range = value;
+        }
         else if (p->p.bt && (k == "device_assoc" || k == "device_assoc_limit" || k == "device_filter"))
             AIC_REQUIRE(false, AIC_ERR_INVALID, "option " + k + " applies to DeepSORT pipelines only (this one runs " + p->p.bt_name() + ")");
         else if (p->p.dsb && (k == "device_assoc" || k == "device_assoc_limit" || k == "streams" || k == "gmc"))

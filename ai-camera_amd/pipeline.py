@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib as L
 from . import config
+from . import frames
 from .core.tracker_core import TrackerCore
 from .hip_engine import HipEngine
 
@@ -19,7 +20,8 @@ class TrackingPipeline:
                  max_det=config.YOLO_MAX_DET, min_confidence=config.DEEPSORT_MIN_CONFIDENCE, inject=False,
                  max_cosine_distance=config.DEEPSORT_MAX_DIST, nn_budget=config.DEEPSORT_NN_BUDGET,
                  max_iou_distance=config.DEEPSORT_MAX_IOU_DISTANCE, max_age=config.DEEPSORT_MAX_AGE,
-                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, streams=1, _cameras=0, **bytetrack_params):
+                 n_init=config.DEEPSORT_N_INIT, max_tracks=512, tracker="deepsort", gmc=0, streams=1, _cameras=0,
+                 pixel_format="bgr24", yuv_matrix="bt601", yuv_range="limited", **bytetrack_params):
         """tracker="bytetrack": a detector-only pipeline with ByteTrack (aic_pipeline_create_bytetrack); reid_engine may be None and is
         not used, bytetrack_params are BYTETracker's (track_thresh, track_buffer, match_thresh, mot20, frame_rate, low_thresh), and
         conf_thresh defaults to low_thresh so that the detector hands over ByteTrack's low band.
@@ -34,7 +36,11 @@ class TrackingPipeline:
         streams=S (ByteTrack / OC-SORT only): one pipeline for S cameras.  The ring and every run range are tick-major, slot t * S + s
         being tick t of stream s; batch, slot and count are multiples of S, and the tracker is a bank of S streams.
         BoT-SORT or DeepSORT for S cameras: TrackingPipeline.botsort_bank(...) / TrackingPipeline.deepsort_bank(...), which pass the
-        camera count as _cameras."""
+        camera count as _cameras.
+        pixel_format="nv12" or "i420" (any tracker, the bank constructors included; yuv_matrix "bt601" / "bt709", yuv_range "limited" /
+        "full"): upload, run_raw_from_host*, run_from_host and stream take uint8 [n, H*3/2, W] frames instead of [n, H, W, 3]; they are
+        unpacked into the BGR ring on the copy stream (frames.py, set_pixel_format), read_frames returns ring slots as BGR."""
+        self._pix = (frames.format_code(pixel_format), frames.matrix_code(yuv_matrix), frames.range_code(yuv_range))
         self.streams = int(_cameras) or int(streams)
         self.cameras, self._device, self.xcam, self.link_after_run, self._bank = int(_cameras), device, None, False, None
         if _cameras and tracker not in ("botsort", "deepsort"):
@@ -71,6 +77,7 @@ class TrackingPipeline:
             self.tracker_core = None
             if self.streams != 1:
                 self.option("streams", self.streams)
+            self._apply_pixel_format()
             return
         if tracker == "ocsort":
             from .ocsort import ocsort_params as _ocp
@@ -89,6 +96,7 @@ class TrackingPipeline:
             self.tracker_core = None
             if self.streams != 1:
                 self.option("streams", self.streams)
+            self._apply_pixel_format()
             return
         if tracker == "botsort":
             from .botsort import botsort_params as _bsp
@@ -111,6 +119,7 @@ class TrackingPipeline:
             self.tracker_core = None
             if gmc:
                 self.option("gmc", int(gmc))
+            self._apply_pixel_format()
             return
         if conf_thresh is None:
             conf_thresh = config.YOLO_CONF_THRESHOLD
@@ -125,12 +134,41 @@ class TrackingPipeline:
         if _cameras:                                             # a DeepSORT bank: the cameras' state is .bank's, there is no single tracker
             L.call("aic_pipeline_create_deepsort_bank", self.yolo._h, self.reid._h, C.byref(self.params), int(_cameras), C.byref(self._h))
             self.tracker_params, self.tracker_core = tp, None
+            self._apply_pixel_format()
             return
         L.call("aic_pipeline_create", self.yolo._h, self.reid._h, C.byref(self.params), C.byref(self._h))
         th = C.c_void_p()
         L.call("aic_pipeline_tracker", self._h, C.byref(th))
         self.tracker_core = TrackerCore._from_handle(th, tp)
         self.tracker_core._dim = self.reid.out_dim
+        self._apply_pixel_format()
+
+    def _apply_pixel_format(self):
+        if self._pix != (L.PIX_BGR24, L.YUV_BT601, L.YUV_LIMITED):
+            self.set_pixel_format(*self._pix)
+
+    def set_pixel_format(self, pixel_format="bgr24", yuv_matrix="bt601", yuv_range="limited"):
+        """Between calls: the format of the host frames that upload / run*_from_host / stream take from now on."""
+        pix = (frames.format_code(pixel_format), frames.matrix_code(yuv_matrix), frames.range_code(yuv_range))
+        for key, v in zip(("pixel_format", "yuv_matrix", "yuv_range"), pix):
+            self.option(key, v)
+        self._pix = pix
+        if hasattr(self, "_staging"):                            # stream()'s pinned buffers have the old format's shape
+            for b in self._staging:
+                self.unpin(b)
+            del self._staging
+
+    @property
+    def host_frame_shape(self):
+        """Shape of one host frame in the pipeline's pixel format: (H, W, 3) BGR24, (H*3/2, W) NV12 / I420."""
+        return (self.frame_h, self.frame_w, 3) if self._pix[0] == L.PIX_BGR24 else (self.frame_h * 3 // 2, self.frame_w)
+
+    def read_frames(self, slot, count):
+        """Ring slots [slot, slot + count) as BGR uint8 [count, H, W, 3], between calls (what the frames that arrived as YUV were
+        unpacked to)."""
+        out = np.empty((int(count), self.frame_h, self.frame_w, 3), np.uint8)
+        L.call("aic_pipeline_read_frames", self._h, int(slot), int(count), L.ptr(out))
+        return out
 
     @classmethod
     def botsort_bank(cls, yolo_engine, reid_engine, frame_hw, cameras, gmc=0, **kw):
@@ -267,9 +305,9 @@ class TrackingPipeline:
 
     def upload(self, slot, frames_bgr):
         f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
-        if f.ndim == 3:
+        if f.ndim == len(self.host_frame_shape):
             f = f[None]
-        assert f.shape[1:] == (self.frame_h, self.frame_w, 3), f.shape
+        assert f.shape[1:] == self.host_frame_shape, f.shape
         L.call("aic_pipeline_upload", self._h, int(slot), L.ptr(f), len(f))
 
     def inject(self, slot, detections):
@@ -332,10 +370,10 @@ class TrackingPipeline:
         return dict(issue_s=a.value, wait_s=b.value, track_s=c.value, frames=n.value)
 
     def run_raw_from_host(self, frames_bgr, slot=0):
-        """PCIe-inclusive timed path: frames (uint8 [n,H,W,3], ideally pinned via pin()) stream host -> HBM per launch
-        group on a copy stream, overlapped with compute."""
+        """PCIe-inclusive timed path: frames (uint8 [n,H,W,3], or [n,H*3/2,W] with a YUV pixel_format; ideally pinned via pin()) stream
+        host -> HBM per launch group on a copy stream, overlapped with compute."""
         f = frames_bgr
-        assert f.dtype == np.uint8 and f.flags["C_CONTIGUOUS"] and f.shape[1:] == (self.frame_h, self.frame_w, 3)
+        assert f.dtype == np.uint8 and f.flags["C_CONTIGUOUS"] and f.shape[1:] == self.host_frame_shape
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host", self._h, L.ptr(f), int(slot), count, L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
@@ -345,7 +383,7 @@ class TrackingPipeline:
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
         """The host clip looped `passes` times as ONE continuous stream (bench.py's timed region)."""
         f = frames_bgr
-        assert f.dtype == np.uint8 and f.flags["C_CONTIGUOUS"] and f.shape[1:] == (self.frame_h, self.frame_w, 3)
+        assert f.dtype == np.uint8 and f.flags["C_CONTIGUOUS"] and f.shape[1:] == self.host_frame_shape
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host_passes", self._h, L.ptr(f), int(slot), count, int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
@@ -359,15 +397,18 @@ class TrackingPipeline:
         return [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                  for r, c in zip(rows[f, :min(nt[f], self.max_persons)], tconf[f, :min(nt[f], self.max_persons)])] for f in range(len(frames_bgr))]
 
-    def stream(self, frames_iter):
+    def stream(self, frames_iter, read_back=False):
         """Frame source -> (frame, tracks) per frame, in order, through DOUBLE-BUFFERED PAGE-LOCKED STAGING: two buffers of `batch`
         frames are pinned once (never per call); a reader thread fills one from the source (cap.read() of
         src/aicamera_tracker.py:170) while the GPU works on the other, whose frames cross PCIe on the copy stream under compute.
-        The yielded frame is a view of the staging buffer: use it before asking for the frame `batch` positions later."""
+        The yielded frame is a view of the staging buffer: use it before asking for the frame `batch` positions later.
+        With a YUV pixel_format the staging buffers and the source's frames are [H*3/2, W]; read_back=True then yields, instead of the
+        staged YUV frame, the BGR frame the ring holds for it (read_frames: one device-to-host copy per run call) -- what a consumer that
+        draws on the frames needs.  A BGR pipeline ignores read_back."""
         import queue
         import threading
         if not hasattr(self, "_staging"):
-            self._staging = [np.empty((self.batch, self.frame_h, self.frame_w, 3), np.uint8) for _ in range(2)]
+            self._staging = [np.empty((self.batch,) + self.host_frame_shape, np.uint8) for _ in range(2)]
             for b in self._staging:
                 self.pin(b)
         free, full = queue.Queue(), queue.Queue(maxsize=2)
@@ -387,8 +428,8 @@ class TrackingPipeline:
                         except StopIteration:
                             done = True
                             break
-                        if f.shape != (self.frame_h, self.frame_w, 3):
-                            raise ValueError(f"frame of shape {f.shape}, the pipeline was built for {(self.frame_h, self.frame_w, 3)}")
+                        if f.shape != self.host_frame_shape:
+                            raise ValueError(f"frame of shape {f.shape}, the pipeline was built for {self.host_frame_shape}")
                         self._staging[b][n] = f
                         n += 1
                     full.put((b, n))
@@ -406,8 +447,9 @@ class TrackingPipeline:
                 tracks = self.run_from_host(self._staging[b][:n])
                 if self.link_after_run:                  # the CLI's --link_cameras: identities follow every run call
                     self.link_cameras()
+                shown = self.read_frames(0, n) if read_back and self._pix[0] != L.PIX_BGR24 else self._staging[b]
                 for i in range(n):
-                    yield self._staging[b][i], tracks[i]
+                    yield shown[i], tracks[i]
             free.put(b)
         th.join()
         if err:

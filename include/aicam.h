@@ -808,6 +808,43 @@ int aic_render_set_masks(aic_render* r, int camera, int n_polys, const int32_t* 
 int aic_render_rects(aic_render* r, const int32_t* rows6, int n_rows, int32_t* rects4, int* n_rects);
 int aic_render_frames(aic_render* r, uint8_t* frames_bgr, int n_frames, int h, int w, int mem, const int32_t* rows6, const int32_t* row_counts,
                       const int32_t* prims, const int32_t* prim_counts, const uint8_t* text, int text_bytes, const int32_t* cameras);
+/* ---- 4:2:0 YUV frames in, NV12 out: pixel-format conversion of a bank of frames in one launch (csrc/yuv.hpp) -------
+ * Decoders, RTSP stacks and camera SDKs deliver NV12 (sometimes I420) on pitched surfaces and encoders want the same back; everything else
+ * in this library reads packed BGR24.  tests/yuv_oracle.py is the specification and the device equals it bit for bit in both directions:
+ * int32 arithmetic on coefficients scaled by 2^20 (the standards' exact fractions, rounded half away from zero -- not OpenCV's
+ * three-decimal constants, from which results may differ by one level), chroma replicated on decode (pixel (x, y) takes the chroma sample
+ * of block (x/2, y/2)) and taken from the sums over each 2x2 block on encode.
+ * Layout of one frame: AIC_PIX_NV12 = a Y plane of h rows of `pitch` bytes, then h/2 rows of `pitch` bytes holding U,V interleaved;
+ * AIC_PIX_I420 = the Y plane, then a U plane of h/2 rows of pitch/2 bytes, then a V plane of the same shape.  Frame f starts at
+ * f * frame_stride.  h and w even and in 2..16384; pitch >= w (even for I420), 0 = w; frame_stride >= pitch * h * 3 / 2, 0 = exactly that.
+ * The BGR side is always [n_frames, h, w, 3], tight.  matrix: AIC_YUV_BT601 / AIC_YUV_BT709; range: AIC_YUV_LIMITED (luma 16..235,
+ * chroma 16..240) / AIC_YUV_FULL.
+ * aic_yuv_coeffs (host only): the decode coefficients cy cvr cvg cug cub, the encode coefficients yr yg yb ur ug ub vr vg vb and the
+ * luma offset of a matrix / range pair.
+ * aic_frames_to_bgr / aic_frames_from_bgr: src and dst both in host memory (AIC_HOST: uploaded, converted, downloaded) or both in the
+ * device's HBM (AIC_DEVICE; any alignment -- 8-byte aligned bases with w, pitch and frame_stride multiples of 8 take the wide path, the
+ * same bytes either way).  from_bgr writes only the bytes inside w: pitch padding and the tail of a frame_stride keep their contents.
+ * Every argument error (odd or out-of-range h / w, pitch < w, an odd I420 pitch, a short frame_stride, format AIC_PIX_BGR24 or unknown,
+ * unknown matrix / range / mem, NULL) is AIC_ERR_INVALID before the device is touched; n_frames = 0 succeeds without touching it.
+ * One stream synchronise ends the call. */
+#define AIC_PIX_BGR24 0
+#define AIC_PIX_NV12 1
+#define AIC_PIX_I420 2
+#define AIC_YUV_BT601 0
+#define AIC_YUV_BT709 1
+#define AIC_YUV_LIMITED 0
+#define AIC_YUV_FULL 1
+int aic_yuv_coeffs(int matrix, int range, int32_t dec[5], int32_t enc[9], int32_t* y_offset);
+int aic_frames_to_bgr(int device, const uint8_t* src, int n_frames, int h, int w, int format, int64_t pitch, int64_t frame_stride, int matrix,
+                      int range, int mem, uint8_t* dst_bgr);
+int aic_frames_from_bgr(int device, const uint8_t* src_bgr, int n_frames, int h, int w, int format, int64_t pitch, int64_t frame_stride,
+                        int matrix, int range, int mem, uint8_t* dst);
+/* A pipeline fed 4:2:0 frames: aic_pipeline_option "pixel_format" (AIC_PIX_*; default AIC_PIX_BGR24), "yuv_matrix", "yuv_range", legal
+ * between calls (an odd frame_h or frame_w rejects a YUV format).  aic_pipeline_upload and aic_pipeline_run_from_host[_passes] then read
+ * host frames of h * w * 3 / 2 bytes, tightly packed; they land in a YUV staging ring (one slot per ring slot, allocated on first use) and
+ * are unpacked into the BGR ring slot on the copy stream, directly behind their copy.  The ring stays BGR: nothing after it changes.
+ * aic_pipeline_read_frames: ring slots [slot, slot + count) as BGR [count, frame_h, frame_w, 3] to the host, between calls. */
+int aic_pipeline_read_frames(aic_pipeline* p, int slot, int count, uint8_t* out_bgr);
 int aic_host_register(void* ptr, size_t bytes);   /* hipHostRegister: page-lock caller memory */
 int aic_host_unregister(void* ptr);
 int aic_pipeline_tracker(aic_pipeline* p, aic_tracker** out);
