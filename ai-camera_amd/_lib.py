@@ -82,6 +82,7 @@ _SIGS = {
     "aic_model_load_mem": (_I, [_P, C.c_size_t, _I, _I, _I, _P]),
     "aic_model_read_buffer": (_I, [_P, _I, _P, C.c_size_t]),
     "aic_model_conv_plan": (_I, [_P, _I, _I, _P]),
+    "aic_model_conv_plan_live": (_I, [_P, _I, _I, _P]),
     "aic_model_row_band": (_I, [_P, _I, _I, _I, _P]),
     "aic_model_destroy": (_I, [_P]),
     "aic_model_info": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
@@ -91,6 +92,7 @@ _SIGS = {
     "aic_yolo_postprocess": (_I, [_P, _P, _P, _I, _F, _F, _I, _I, _F, _F, _F, _I, _I] + [_P] * 9),
     "aic_det_filter": (_I, [_I, _P, _P, _P, _P, _I, _I, _F, _P, _I] + [_P] * 9),
     "aic_reid_infer": (_I, [_P, _P, _I, _I, _P, _I]),
+    "aic_reid_infer_live": (_I, [_P, _P, _I, _I, _I, _P, _I]),
     "aic_letterbox": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "aic_letterbox_image": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "aic_crop_resize": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _P, _P]),

@@ -1010,10 +1010,9 @@ int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes) {
     });
 }
 
-int aic_model_conv_plan(aic_model* mm, int op, int n, int32_t* out) {
-    return guarded([&] {
-        AIC_REQUIRE(mm && out && op >= 0 && op < (int)mm->m.ops.size() && n > 0 && n <= mm->m.max_items, AIC_ERR_INVALID, "bad argument");
-        const Model& m = mm->m;
+// aic_model_conv_plan / aic_model_conv_plan_live: the walk of run_range up to op `op`, every step asked of Model::conv_step
+static void conv_plan_query(const Model& m, int op, int n, int32_t* out) {
+    {
         std::fill(out, out + 24, 0);
         for (size_t oi = 0; oi < m.ops.size(); ++oi) {          // the walk of run_range
             const OpDesc& o = m.ops[oi];
@@ -1037,6 +1036,29 @@ int aic_model_conv_plan(aic_model* mm, int op, int n, int32_t* out) {
             }
             return;
         }
+    }
+}
+
+int aic_model_conv_plan(aic_model* mm, int op, int n, int32_t* out) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && out && op >= 0 && op < (int)mm->m.ops.size() && n > 0 && n <= mm->m.max_items, AIC_ERR_INVALID, "bad argument");
+        conv_plan_query(mm->m, op, n, out);
+    });
+}
+
+int aic_model_conv_plan_live(aic_model* mm, int op, int n, int32_t* out) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && out && op >= 0 && op < (int)mm->m.ops.size() && n > 0 && n <= mm->m.max_items, AIC_ERR_INVALID, "bad argument");
+        Model& m = mm->m;
+        const int* before = m.n_items_dev;
+        m.n_items_dev = reinterpret_cast<const int*>(m.d_zero.p);      // any device address: nothing is launched, nobody reads it
+        try {
+            conv_plan_query(m, op, n, out);
+        } catch (...) {
+            m.n_items_dev = before;
+            throw;
+        }
+        m.n_items_dev = before;
     });
 }
 
@@ -1264,6 +1286,34 @@ int aic_reid_infer(aic_model* mm, const float* crops, int n, int mem, float* emb
             m.run(k, s);
             copy_out(emb + (size_t)c0 * m.out_dim, m.embeddings(), (size_t)k * m.out_dim * 4, out_mem, s);
         }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int aic_reid_infer_live(aic_model* mm, const float* crops, int n, int n_live, int mem, float* emb, int out_mem) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && n >= 0 && n_live >= 0, AIC_ERR_INVALID, "bad argument");
+        if (n == 0) return;
+        AIC_REQUIRE(crops && emb, AIC_ERR_INVALID, "NULL argument");
+        Model& m = mm->m;
+        AIC_REQUIRE(m.kind == KIND_REID, AIC_ERR_INVALID, "not a ReID engine");
+        AIC_REQUIRE(n <= m.max_items, AIC_ERR_INVALID, "more crops than the engine's max_items");
+        m.dev->use();
+        hipStream_t s = m.dev->s_main;
+        DevBuf<int> d_live(1);
+        const int live_host = n_live;                                     // the upload's source: lives until the stream is through
+        HIP_CHECK(hipMemcpyAsync(d_live.p, &live_host, 4, hipMemcpyHostToDevice, s));
+        m.n_items_dev = d_live.p;                                         // as the pipeline's device-filtered round sets it (pipeline.cpp)
+        try {
+            load_input_nchw(m, crops, n, mem, s);
+            m.run(n, s);
+        } catch (...) {
+            m.n_items_dev = nullptr;
+            (void)hipStreamSynchronize(s);
+            throw;
+        }
+        m.n_items_dev = nullptr;
+        copy_out(emb, m.embeddings(), (size_t)std::min(n, n_live) * m.out_dim * 4, out_mem, s);
         HIP_CHECK(hipStreamSynchronize(s));
     });
 }

@@ -165,12 +165,16 @@ class HipEngine:
                *(L.ptr(r[k]) for k in ("rank", "frame_n", "frame_d0", "total", "xyxy", "tlwh", "conf", "cls", "frame_of")))
         return r
 
-    def reid_infer_np(self, crops_nchw):
+    def reid_infer_np(self, crops_nchw, n_live=None):
+        """n_live: run with a device-side count holding n_live in force (aic_reid_infer_live, include/aicam.h; tests): rows at and past
+        it are not computed and come back as zeros."""
         x = L.as_f32(crops_nchw)
         n = x.shape[0]
         out = np.zeros((n, self.out_dim), np.float32)
-        if n:
+        if n and n_live is None:
             L.call("aic_reid_infer", self._h, L.ptr(x), n, L.HOST, L.ptr(out), L.HOST)
+        elif n:
+            L.call("aic_reid_infer_live", self._h, L.ptr(x), n, int(n_live), L.HOST, L.ptr(out), L.HOST)
         return out
 
     def read_buffer_np(self, buf, n):
@@ -184,10 +188,11 @@ class HipEngine:
         L.call("aic_model_read_buffer", self._h, int(buf), L.ptr(out), out.nbytes)
         return out
 
-    def conv_plan(self, op, n):
-        """What a launch of n items runs at op `op` of the engine file's op list (aic_model_conv_plan, include/aicam.h)."""
+    def conv_plan(self, op, n, live=False):
+        """What a launch of n items runs at op `op` of the engine file's op list (aic_model_conv_plan, include/aicam.h); live: with a
+        device-side item count in force (aic_model_conv_plan_live)."""
         out = np.zeros(24, np.int32)
-        L.call("aic_model_conv_plan", self._h, int(op), int(n), L.ptr(out))
+        L.call("aic_model_conv_plan_live" if live else "aic_model_conv_plan", self._h, int(op), int(n), L.ptr(out))
         names = ["form", "mt", "nt", "wm", "wn", "nstage", "th", "tw", "cpp", "pitch", "kord", "g", "tail", "x2", "run", "blocks"]
         forms = ["Dma", "Wide", "Pp", "PpPatch", "SpPatch", "S2Patch", "Patch", "PmPatch", "C16", "C32s2Tail", "Stream1x1", "C64Resident"]
         r = {"kind": {-2: "covered", -1: "none", 0: "conv", 1: "conv+tail", 2: "c64_block", 3: "c2f16"}[int(out[0])],

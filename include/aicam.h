@@ -86,6 +86,9 @@ int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes);
  * form, mt, nt, wm, wn, nstage, th, tw, cpp, pitch, kord, g, tail, x2, run, blocks; [21] split source, [22] / [23] destination /
  * source channel offset. */
 int aic_model_conv_plan(aic_model* m, int op, int n, int32_t* out);
+/* Tests: the same answer with a device-side item count in force (the pipeline's device-filtered ReID rounds, aic_reid_infer_live):
+ * the planner refuses some forms then, so the layer may run another kernel than aic_model_conv_plan names.  Launches nothing. */
+int aic_model_conv_plan_live(aic_model* m, int op, int n, int32_t* out);
 /* Read-only: the row band of op `op` of the engine's op list for frames of src_h x src_w -- the rows of its output map that can depend
  * on the frame when the letterboxed picture has flat borders above and below it (csrc/row_band.hpp) -- and what the last run of the
  * engine on frames (aic_detect, the pipeline) did with it.  out[8]: [0] 1 = every row (the op is not modelled, follows one that is
@@ -184,6 +187,12 @@ int aic_crop_resize_ex(int device, const uint8_t* frames_bgr, int n_frames, int 
  * beyond n_live are not computed.  valid is prefilled with -1. */
 int aic_reid_embed_bank(aic_model* reid, const uint8_t* frames_bgr, int n_frames, int h, int w, int byte_offset,
                         const float* boxes_xyxy, const int32_t* frame_of, int n, int n_live, float* embeddings, int32_t* valid);
+/* Tests: aic_reid_infer for one group of n <= max_items crops with a device-side count holding n_live in force for the run, as the
+ * pipeline's device-filtered round sets it: every launch is sized for n, the kernels that read the count leave items at and past
+ * min(n_live, n) alone (n_live > n is allowed: the pipeline's count exceeds the bound in an overflow round).  Only the first
+ * min(n_live, n) embeddings are copied out; the rest of `embeddings` is left as the caller filled it.  AIC_ERR_INVALID for
+ * n > max_items or n_live < 0.  The activations stay in the engine (aic_model_read_buffer). */
+int aic_reid_infer_live(aic_model* m, const float* crops_nchw, int n, int n_live, int mem, float* embeddings, int out_mem);
 
 /* ------------------------------------------------------------------ Kalman filter (batched)
  * KalmanFilter.initiate/predict/project/update/gating_distance

@@ -5,7 +5,7 @@
 using namespace aic;
 
 // L: H, W, Cin, Ho, Wo, Cout, K (square window), stride, act, res_mode, n (images), tail Cout (0: none), Cin2 (0: none), Cs (0: none),
-// out_f32.  Laid out as the engine lays out a dense layer.  out: k_order, form, mt, nt, wm, wn, nstage, th, tw, cpp, pitch, kord, g, tail,
+// out_f32, n_dev (1: a device-side item count is in force, ConvArgs::n_dev).  Laid out as the engine lays out a dense layer.  out: k_order, form, mt, nt, wm, wn, nstage, th, tw, cpp, pitch, kord, g, tail,
 // x2, run, blocks, then conv_tail_supported, conv_x2_supported, conv_xs_supported.  Returns 0, or -1 when plan_conv refuses the layer.
 extern "C" int probe_plan(int dtype, const int* L, int cu_budget, long* out) {
     static const char page[256] = {0};
@@ -18,6 +18,7 @@ extern "C" int probe_plan(int dtype, const int* L, int cu_budget, long* out) {
     for (int kh = 0; kh < k; ++kh) a.tap_rows |= 1u << (kh * k);
     a.x = a.w = a.zero = page, a.y = (void*)page, a.bias = reinterpret_cast<const float*>(page);
     if (a.res_mode) a.res = page;
+    if (L[15]) a.n_dev = reinterpret_cast<const int*>(page);
     ConvArgs t{};
     if (L[11]) {
         t.x = a.y, t.x_cs = a.y_cs, t.M = a.M, t.Cin = a.Cout, t.Cout = L[11], t.KH = t.KW = 1, t.stride = 1, t.Kp = 32 * ((a.Cout + 31) / 32);
@@ -39,4 +40,16 @@ extern "C" int probe_plan(int dtype, const int* L, int cu_budget, long* out) {
         return -1;
     }
     return 0;
+}
+
+// The 64-channel BasicBlock pair on an H x 32 map at n images, as the engine lays it out: plan_c64_block's images per block (0: not fused).
+extern "C" int probe_c64_block(int H, int n, int cu_budget) {
+    static const char px[256] = {0}, pm[256] = {0}, py[256] = {0};
+    ConvArgs c1{}, c2{};
+    for (ConvArgs* c : {&c1, &c2}) {
+        c->H = c->Ho = H, c->W = c->Wo = 32, c->Cin = c->Cout = 64, c->KH = c->KW = 3, c->stride = 1, c->pad = 1, c->act = 2, c->Kp = 576;
+        c->M = n * H * 32, c->x_cs = c->y_cs = 64, c->cout_pad = 128;
+    }
+    c1.x = px, c1.y = (void*)pm, c2.x = pm, c2.y = (void*)py, c2.res = px, c2.r_cs = 64, c2.res_mode = 1;
+    return plan_c64_block(c1, c2, cu_budget);
 }

@@ -140,6 +140,21 @@ def _cases():
 
 CASES = _cases()
 
+# ---- under a device-side item count (EltArgs::n_dev): the ops that cut their index range by it (kernels_elt.hip: maxpool3s2, avgpool,
+# avgpool8, l2norm; the SPPF pool and the upsample belong to YOLO graphs and have none), the smallest cases of each in both element types
+LIVE = ("mp_13x7_c24", "mp_13x7_c24_slice", "ap_4x8_c64_n37", "ap_7x3_c20_n37", "ap_13x7_c16_slice_n37", "l2_c40_n5", "l2_c200_n37",
+        "l2_c200_slice_n5")
+LIVE_CASES = [c for c in CASES if c.id.rsplit("_", 1)[0] in LIVE]
+
+
+def live_counts(c: Case):
+    """0, 1, n - 1 and n + 3 (a count may exceed the bound); L2 normalise, four items per block: also a count that is no multiple of
+    four and not 1, so that a block's last wavefronts leave while its first ones work."""
+    ks = {0, 1, c.n - 1, c.n + 3}
+    if c.op == "l2norm":
+        ks.add(next(k for k in (6, 3) if k < c.n))
+    return tuple(sorted(ks))
+
 
 def expected_kernel(c: Case, B) -> str:
     """The launchers' own rules (csrc/kernels_elt.hip, csrc/kernels_conv_direct.hip), restated from the case's graph."""

@@ -91,10 +91,12 @@ def planner(tmp_path_factory):
     lib = ctypes.CDLL(so)
     lib.probe_plan.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_long)]
     lib.probe_plan.restype = ctypes.c_int
+    lib.probe_c64_block.argtypes = [ctypes.c_int] * 3
+    lib.probe_c64_block.restype = ctypes.c_int
 
-    def plan(dtype, layer, n, cu_budget=256):
+    def plan(dtype, layer, n, cu_budget=256, n_dev=False):
         H, W, Cin, Ho, Wo, Cout, K, stride, act, res, tail, cin2, cs = layer
-        L = (ctypes.c_int * 15)(H, W, Cin, Ho, Wo, Cout, K, stride, act, res, n, tail, cin2, cs, 0)
+        L = (ctypes.c_int * 16)(H, W, Cin, Ho, Wo, Cout, K, stride, act, res, n, tail, cin2, cs, 0, int(n_dev))
         out = (ctypes.c_long * 20)()
         rc = lib.probe_plan(dtype, L, cu_budget, out)
         r = {"k_order": out[0], "tail_ok": out[17], "x2_ok": out[18], "xs_ok": out[19]}
@@ -102,6 +104,7 @@ def planner(tmp_path_factory):
             r.update({f: out[1 + i] for i, f in enumerate(FIELDS)})
             r["form"] = FORMS[r["form"]]
         return r
+    plan.c64_block = lambda H, n, cu_budget=256: lib.probe_c64_block(H, n, cu_budget)
     return plan
 
 
@@ -205,3 +208,106 @@ def test_fp32_stays_on_the_implicit_gemm(planner):
             p = planner(F32, layer[:10] + (0, 0, 0), n)
             assert p["form"] in ("Dma", "Wide"), (name, n, summary(p))
             assert p["nstage"] == 4 and p["wm"] * p["wn"] == 4, (name, n, summary(p))
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/conv_ref.py
+import conv_ref as R  # noqa: E402
+
+
+def case_layers(c):
+    """The layers of a conv_ref case that its `expect` / `expect_live` describe, as probe tuples: [(name, layer)]."""
+    if c.pattern == "ds":
+        return [("c2", (c.Ho, c.Wo, 128, c.Ho, c.Wo, 128, 3, 1, R.RELU, 0, 0, 64, 0))]
+    if c.pattern == "xs":
+        return [("layer", (c.H, c.W, 96, c.H, c.W, 64, 1, 1, c.act, 0, 0, 0, 64))]
+    if c.pattern == "block64":
+        return [(nm, (c.H, c.W, 64, c.H, c.W, 64, 3, 1, R.RELU, rm, 0, 0, 0)) for nm, rm in (("c1", 0), ("c2", 1))]
+    return [("layer", (c.H, c.W, c.cin, c.Ho, c.Wo, c.cout, c.k, c.stride, c.act, c.res, c.tail, 0, 0))]
+
+
+def case_plans(planner, c, n_dev):
+    dt = F16 if c.dtype == "fp16" else F32
+    out = []
+    for name, layer in case_layers(c):
+        p = planner(dt, layer, c.n, n_dev=n_dev)
+        assert "form" in p, (c.id, name)
+        if layer[10]:
+            assert p["tail_ok"], (c.id, "the engine would not attach this tail")
+        if layer[11]:
+            assert p["x2_ok"], (c.id, "the engine would not fold this second source")
+        if layer[12]:
+            assert p["xs_ok"], (c.id, "the engine would not fold this split source")
+        out.append((name, p))
+    return out
+
+
+@pytest.mark.parametrize("n_dev", [False, True], ids=["host_count", "device_count"])
+def test_conv_ref_cases_plan_as_they_expect(planner, n_dev):
+    """Every case's hand-written plan -- `expect`, and `expect_live` under a device-side item count -- is what plan_conv_launch answers."""
+    for c in R.CASES:
+        want = c.expect_live if n_dev else c.expect
+        if want.get("kind") == "c64_block":
+            ipb = planner.c64_block(c.H, c.n)
+            assert 12 <= ipb <= 16 and (not n_dev or ipb == want["ipb"]), (c.id, ipb)
+            continue
+        for name, p in case_plans(planner, c, n_dev):
+            w = {k: v for k, v in want.items() if k in p}
+            assert {k: p[k] for k in w} == w, (c.id, name, want, summary(p), p["k_order"])
+
+
+def _live_fields(planner, c):
+    """expect_live's fields as the planner gives them now (the block kernel: its images per block)."""
+    if c.expect_live.get("kind") == "c64_block":
+        return dict(kind="c64_block", ipb=planner.c64_block(c.H, c.n))
+    return case_plans(planner, c, True)[-1][1]
+
+
+def test_counts_follow_the_construction_rules(planner):
+    """Every case's `counts` is what live_counts builds from the planner's CURRENT answer, and satisfies the rules it was built by, with the
+    unit (BM, NI, run, tiles per image, blocks, grid) recomputed here from that answer."""
+    cdiv = lambda a, b: -(-a // b)                                                      # noqa: E731
+    forms = set()
+    for c in R.CASES:
+        if not c.counts:
+            assert c.id not in R.LIVE
+            continue
+        p, n, ks = _live_fields(planner, c), c.n, set(c.counts)
+        form = p.get("form", p.get("kind"))
+        forms.add(form)
+        assert c.counts == R.live_counts(c, p), (c.id, c.counts, R.live_counts(c, p))
+        assert {0, 1, n - 1, n + 3} <= ks and all(0 <= k < n or k == n + 3 for k in ks), (c.id, c.counts)
+        px = c.Ho * c.Wo
+        if form in ("Dma", "Pp"):
+            bm = p["wm"] * p["mt"] * 16
+            edges = [k for k in range(1, n - 1) if k * px % bm == 0]
+            if edges:
+                assert any(k in ks and k - 1 in ks and k + 1 in ks for k in edges), (c.id, bm, px, c.counts)
+            assert any(k * px % bm for k in ks if 0 < k < n) or px % bm == 0, (c.id, "no count ends inside a tile")
+        elif form in ("PpPatch", "SpPatch", "S2Patch"):
+            ni = p["wm"] * (p["mt"] or 8) * 16 // (p["th"] * p["tw"])
+            cout = 128 if c.pattern == "ds" else c.cout
+            tpg = cdiv(cout, p["wn"] * 64) * ((c.Ho // p["th"]) * (c.Wo // p["tw"]) if form == "PpPatch" else 1)
+            assert p["blocks"] == cdiv(cdiv(n, ni) * tpg, p["run"]), (c.id, summary(p))          # the grid is the bound's
+            if ni > 1:
+                assert {ni - 1, ni, ni + 1} <= ks, (c.id, ni, c.counts)
+            if p["run"] > 1:
+                live = [cdiv(k, ni) * tpg for k in ks if 0 < k < n]
+                assert any(t % p["run"] for t in live) and any(t % p["run"] == 0 for t in live), (c.id, p["run"], c.counts)
+        elif form == "Patch":
+            tpi = cdiv(c.Wo, p["tw"]) * cdiv(c.Ho, p["th"])
+            live = [k * tpi for k in ks if 0 < k < n]
+            assert any(t < 8 for t in live) and any(t >= 8 and t % 8 == 0 for t in live), (c.id, tpi, c.counts)
+            want = {1, 7} if tpi % 2 else ({2, 6} if tpi % 4 else {4})          # an even tile count per image never leaves 1 or 7
+            assert any(t >= 8 and t % 8 in want for t in live), (c.id, tpi, c.counts)
+        elif form == "C64Resident":
+            tpi = (c.W // 32) * (c.H // 8)
+            assert any(0 < k * tpi < p["blocks"] for k in ks) and any(k * tpi > p["blocks"] for k in ks if k < n), (c.id, c.counts)
+        elif form == "c64_block":
+            g = cdiv(n, p["ipb"])
+            assert {1, g - 1, g, g + 1, 2 * g + 1} <= ks, (c.id, g, c.counts)
+            assert [cdiv(k, g) for k in (1, g, g + 1, 2 * g + 1)] == [1, 1, 2, 3]             # images per block the kernel works out
+        else:
+            assert form == "C16", (c.id, form)                                               # reads no count: live rows only
+    assert forms >= set(R.READS_COUNT), set(R.READS_COUNT) - forms
+    patch = [(cdiv(c.Wo, c.expect_live["tw"]) * cdiv(c.Ho, c.expect_live["th"]), c) for c in R.CASES if c.counts and c.expect_live.get("form") == "Patch"]
+    assert any(t % 2 and any(k * t >= 8 and (k * t) % 8 in (1, 7) for k in c.counts) for t, c in patch)

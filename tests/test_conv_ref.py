@@ -93,3 +93,57 @@ def test_tolerance_sits_between_honest_arithmetic_and_the_smallest_bugs(c):
         good = rows[-1]
         r = _ratio(bad[3], good[3], good[4])
         assert r > 1.0, f"{c.id}: the {mut} bug stays inside the tolerance ({r:.3f} x)"
+
+
+def _assert_live(res):
+    """The assertions of tests/test_gpu_conv_counts.py on check_live's figures, in its order; -> the name of the first that fails."""
+    if res["live"] and not res["dirty"] > 1.0:
+        return "dirty"
+    if not res["ratio"] <= 1.0:
+        return "live rows"
+    if not res["past"]:
+        return "past the count"
+    if res["host"] is False:
+        return "same kernel, same bits"
+    return None
+
+
+def test_count_checks_separate_honest_results_from_the_smallest_bugs():
+    """check_live on dma_2x5's shape (400 pixels per image on 128-pixel tiles), 12 images, count 9: the fp64 reference rounded to fp16 is
+    the device's output below the count, another draw's reference what the run found there.  Four planted bugs, each caught by the
+    assertion it belongs to; the unplanted array passes all of them."""
+    c = next(c for c in R.CASES if c.id == "dma_2x5")
+    n, k, B = 12, 9, R.build_graph(c)
+    assert k in c.counts and k * c.Ho * c.Wo % 128 and R.live_unit(c)["bm"] == 128
+
+    def outputs(salt):
+        base, _ = R.images(c, n, salt)
+        vals = R.host_inputs(c, B, base)
+        name, _, _, ref, tol = R.case_reference(c, B, lambda nm: vals[nm])[-1]
+        return ref, tol, ref.astype(np.float16)[np.arange(n) % len(ref)]
+    ref, tol, host = outputs(0)
+    _, _, dirty = outputs(1)
+    honest = np.concatenate([host[:k], dirty[k:]])
+    assert _assert_live(R.check_live(honest, dirty, ref, tol, k, host=host)) is None
+    for count in (0, 1, n - 1, n + 3):
+        good = np.concatenate([host[:count], dirty[count:]])
+        assert _assert_live(R.check_live(good, dirty, ref, tol, count, host=host)) is None, count
+    P, px = len(ref), c.Ho * c.Wo
+    bugs = {}
+    bugs["last live image left as it was"] = honest.copy()
+    bugs["last live image left as it was"][k - 1] = dirty[k - 1]
+    bugs["image k also written"] = honest.copy()
+    bugs["image k also written"][k] = host[k]
+    z = honest.copy().reshape(n * px, -1)
+    z[k * px // 128 * 128:k * px] = 0                                   # the live rows of the tile that straddles the count
+    bugs["straddling tile not stored"] = z.reshape(honest.shape)
+    bugs["image k - 1 from image k's input"] = honest.copy()
+    bugs["image k - 1 from image k's input"][k - 1] = host[k]
+    want = {"last live image left as it was": "live rows", "image k also written": "past the count",
+            "straddling tile not stored": "live rows", "image k - 1 from image k's input": "live rows"}
+    for name, got in bugs.items():
+        res = R.check_live(got, dirty, ref, tol, k, host=host)
+        assert _assert_live(res) == want[name], (name, res)
+    # the first bug shows only because the tensor was dirty: over a tensor that already held the right values it would pass
+    clean = R.check_live(honest, honest, ref, tol, k)
+    assert clean["ratio"] <= 1.0 and not clean["dirty"] > 1.0

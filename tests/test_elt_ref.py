@@ -125,3 +125,16 @@ def test_yolo_stem_reference(name):
             continue
         r = _ratio(E.yolo_stem_ref(frames, w, b, mut=mut)[0], ref, tol)
         assert r > 1.0, f"{name}: the {mut} bug stays inside the tolerance ({r:.3f} x)"
+
+
+def test_count_cases_cover_every_op_that_reads_a_count():
+    """The cases tests/test_gpu_elt_ops.py runs under a device-side count: every kernel that cuts its range by one, in both element
+    types, at 0, 1, n - 1 and n + 3; L2 normalise (four items per block) also at a count that is no multiple of four and not 1."""
+    assert len(E.LIVE_CASES) == 2 * len(E.LIVE) and {c.id.rsplit("_", 1)[0] for c in E.LIVE_CASES} == set(E.LIVE)
+    assert {c.kernel for c in E.LIVE_CASES} == {E.MP, E.AVG, E.AVG8, E.L2}
+    for c in E.LIVE_CASES:
+        assert c.kernel == E.expected_kernel(c, E.build_graph(c))
+        ks = E.live_counts(c)
+        assert {0, 1, c.n - 1, c.n + 3} <= set(ks) and c.n > 1
+        if c.op == "l2norm":
+            assert any(1 < k < c.n and k % 4 for k in ks), (c.id, ks)

@@ -86,6 +86,46 @@ def test_graph_op_against_reference(gpu, tmp_path, c):
         eng.close()
 
 
+@pytest.mark.parametrize("c", E.LIVE_CASES, ids=[c.id for c in E.LIVE_CASES])
+@_stop_on_device_error
+def test_graph_op_under_a_device_count(gpu, tmp_path, c):
+    """maxpool3s2, avgpool, avgpool8 and l2norm with a device-side item count in force (EltArgs::n_dev, aic_reid_infer_live): the launch
+    is sized for n, the kernel cuts its index range at the count.  Before every counted run the engine runs other images without a
+    count; the rows below the count are compared with the same references at the same bounds as above, computed from the op's input
+    as read back; the rows at and past it still hold, bit for bit, what the run before left there."""
+    HipEngine = pkg("hip_engine").HipEngine
+    B = E.build_graph(c)
+    path = str(tmp_path / f"{c.id}.aicw")
+    E.ef.write_engine(path, B.g)
+    x = E.images(c)
+    noise = np.ascontiguousarray(x[::-1] * np.float32(0.5) + np.float32(0.25))          # other images of the same range; a zero image is none
+    eng = HipEngine(path, dtype=c.dtype, max_items=c.n, warm_up=False)
+    try:
+        assert E.expected_kernel(c, B) == c.kernel
+        for k in E.live_counts(c):
+            live = min(k, c.n)
+            eng.reid_infer_np(noise)
+            dirty = eng.read_buffer_np(B.bufs["y"], c.n)
+            emb = eng.reid_infer_np(x, n_live=k)
+            cache = {}
+
+            def raw(name):
+                if name not in cache:
+                    cache[name] = eng.read_buffer_np(B.bufs[name], c.n)
+                return cache[name]
+            y = raw("y")
+            assert np.array_equal(R.bits(y[live:]), R.bits(dirty[live:])), f"{c.id} n_live={k}: rows at and past the count were written"
+            if live:
+                assert not np.array_equal(R.bits(y[:live]), R.bits(dirty[:live])), f"{c.id} n_live={k}: nothing was stored below the count"
+            rows = E.case_reference(c, B, lambda name: raw(name).astype(np.float64))
+            _compare(f"{c.id} n_live={k}", [(nm, buf, c0, ref[:live], tol[:live], exact) for nm, buf, c0, ref, tol, exact in rows],
+                     lambda name: raw(name)[:live])
+            if c.op == "l2norm":
+                assert np.array_equal(emb[:live], y.reshape(c.n, -1)[:live]) and not emb[live:].any()
+    finally:
+        eng.close()
+
+
 @pytest.fixture(scope="module")
 def yolo_small(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("elt") / "yolov8n_64x128.aicw")
