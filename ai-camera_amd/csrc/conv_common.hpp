@@ -3,6 +3,7 @@
 // launchers by which launch_conv_igemm() (kernels_conv.hip) reaches the kernels that live in the other units.
 #pragma once
 #include "kernels.hpp"
+#include "pad_skip_map.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -683,6 +684,20 @@ constexpr int ppp_ipix_pad(int th, int tw) {
     while (ipix % 16 != tw && ipix % 16 != 16 - tw) ++ipix;
     return ipix;
 }
+
+// Patch geometry and halo skipping of the software-pipelined patch kernel's 16-pixel MFMA tiles (MT tiles per wave, WM wave rows, NI
+// images per block):
+//   row pieces  a tile is whole rows or a piece of ONE row of 16 / TW images (pitch TW + 2); every tap of every tile is issued
+//   COL         a tile is ONE column of 16 / TH images (pad_skip_map.hpp: odd pitch); the tiles of column 0 read only the halo at the
+//               taps kw = 0, those of column TW - 1 at kw = 2 -- 2 / TW of the tiles x 1 / 3 of the taps issue no MFMA, read no fragment
+// A skipped (tile, tap) has an all-zero pixel fragment and finite weights: each of its MFMAs would add +-0 to an accumulator that
+// started at +0 and, under round-to-nearest, can never have become -0 -- C + 0 = C bit for bit.  The implicit-GEMM kernels and v5 still
+// execute those MFMAs, so the bit-equality across kernel families (tests/test_gpu_nets.py) checks exactly this.
+template <int TH, int TW, int NI, int WM, int MT, bool COL> struct PatchGeom {
+    static constexpr int PW = TW + 2, IPIXP = ppp_ipix_pad(TH, TW);
+    static constexpr bool skip(int, int) { return false; }
+};
+template <int TH, int TW, int NI, int WM, int MT> struct PatchGeom<TH, TW, NI, WM, MT, true> : ColTiles<TH, TW, NI, WM, MT> {};
 
 // X2 (ConvArgs::x2: a 1x1 / stride-s conv of a second tensor accumulated into the same outputs -- a ResNet downsample branch folded into
 // the block's last conv): the second source's channel chunk e (BM pixels x one K-step) sits in a buffer of its own behind the weight ring.

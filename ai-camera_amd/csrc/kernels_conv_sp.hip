@@ -34,11 +34,20 @@
 //            the buffer is in body tap 8.
 //   tiles    a block walks a run of tiles as in v5; a tile's LAST body reads whatever the next tile's buffers hold by then and the
 //            next tile's first fragments are read again behind the epilogue (the fragments would have to live across it).
+//
+// COL (the 16 x 8 and 8 x 4 maps of ReID layer3 / 4): in layers 3 / 4 the K loop is bound by the matrix pipe, and 12 % / 24 %
+// of a 3x3 / pad 1 conv's (pixel, tap) products on these maps read the zero halo.  A 16-pixel MFMA tile is ONE COLUMN of one or two images
+// (PatchGeom / ColTiles, pad_skip_map.hpp: odd patch pitch, so that a column's sixteen rows fall into sixteen bank slots), and the
+// (tile, tap) pairs whose pixels ALL read the halo -- column 0 at kw = 0, column TW - 1 at kw = 2: 1 / 12 and 1 / 6 of the MFMAs, the same
+// tiles in every wave -- issue neither their four MFMAs nor the read of their pixel fragment.  Bit-identical (see body()); LDS-DMA issues,
+// counted waits and barriers are those of every step; the patch takes one more pass per chunk (4 and 5 of at most 7).  Measured on
+// 15 360 crops, layer alone: 1 729 -> 1 566 us on 8 x 4 (512 -> 512), 1 873 -> 1 813 us on 16 x 8 (256 -> 256).
+// AICAM_NO_PAD_SKIP=1 launches the row-piece instantiations.
 #include "conv_common.hpp"
 
 namespace aic {
 
-template <int MT, int NT, int WM, int WN, int TH, int TW>
+template <int MT, int NT, int WM, int WN, int TH, int TW, bool COL = false>
 __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a, int ny, int run) {
     typedef half_t T;
     constexpr int NSTAGE = 4;
@@ -48,7 +57,8 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
     constexpr int B_PER = BN / RP;
     constexpr int LPS = B_PER + 1;
     constexpr int TPIX = TH * TW, NI = BM / TPIX;
-    constexpr int PW = TW + 2, PH = TH + 2, IPIX = PW * PH, IPIXP = ppp_ipix_pad(TH, TW), NPIX = NI * IPIXP;
+    typedef PatchGeom<TH, TW, NI, WM, MT, COL> GEO;
+    constexpr int PW = GEO::PW, PH = TH + 2, IPIX = PW * PH, IPIXP = GEO::IPIXP, NPIX = NI * IPIXP;
     constexpr int G = TW >= 16 ? 1 : 16 / TW;                          // images per 16-pixel MFMA tile
     constexpr int NPASS = (NPIX + 127) / 128, NPIXP = NPASS * 128;
     constexpr int PLANE = NPIXP * 16, PBUF = 4 * PLANE, WSTAGE = BN * 64;
@@ -160,7 +170,9 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
                                                         : (t / TH) * G * IPIXP + (t % TH) * PW; };
     auto patch_pix = [tile_pix](int m) constexpr { return G == 1 ? tile_pix(m / 16) : (TH % MT == 0 ? (m / 16) * PW : tile_pix(m / 16)); };
     int xa0;                                    // LDS byte address of (this lane's pixel of tile 0, tap (0, 0)) in patch buffer 0
-    if constexpr (G == 1) {
+    if constexpr (COL) {
+        xa0 = PATCH0 + q * PLANE + (GEO::wave_off(wm) + GEO::lane_off(r)) * 16;
+    } else if constexpr (G == 1) {
         const int ml = wm * MT * 16 + r;
         const int il = ml / TPIX, rem = ml - il * TPIX;
         const int ly = rem / TW, lx = rem - ly * TW;
@@ -181,7 +193,10 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
         for (int j = 0; j < NT; ++j) wf[S][j] = *reinterpret_cast<const half8*>(smem + woff2[j & 1] + st * WSTAGE + (j >> 1) * 2048);
     };
     auto read_x = [&](int i, int buf, int tap) {       // all three are constants after inlining: one ds_read_b128 with an immediate
-        xf[i] = *reinterpret_cast<const half8*>(smem + xa0 + buf * PBUF + ((tap / 3) * PW + tap % 3) * 16 + patch_pix(16 * i) * 16);
+        int toff;
+        if constexpr (COL) toff = GEO::tile_off(i);
+        else toff = patch_pix(16 * i);
+        xf[i] = *reinterpret_cast<const half8*>(smem + xa0 + buf * PBUF + ((tap / 3) * PW + tap % 3) * 16 + toff * 16);
     };
 
     // ---- prologue (first tile of the run): patch chunk 0, weights of steps 0 .. 2
@@ -206,10 +221,15 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
         if constexpr (tap == 0) set_patch(c);
         static_for<MT>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
+            // A (tile, tap) whose sixteen pixels all read the zero halo: its pixel fragment is all zeros and the weights are finite, so each of
+            // its MFMAs would add +-0 to an accumulator that started at +0 and, under round-to-nearest, can never have become -0: C + 0 = C bit
+            // for bit.  Neither the MFMAs nor the read of that fragment are issued; LDS-DMA, waits and barrier are those of every step.
+            if constexpr (!GEO::skip(i, tap)) {
 #pragma unroll
-            for (int j = 0; j < NT; ++j)
-                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[CUR][j]), "v"(xf[i]));
-            read_x(i, nbuf, ntap);
+                for (int j = 0; j < NT; ++j)
+                    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[CUR][j]), "v"(xf[i]));
+            }
+            if constexpr (!GEO::skip(i, ntap)) read_x(i, nbuf, ntap);
             if constexpr (i == 0) read_w(std::integral_constant<int, NXT>{}, (ST + 1) & 3);
             if constexpr (i == 1) issue_w((ST + 3) & 3, (tap + 3) % 9);
             if constexpr (i == 2) {
@@ -249,7 +269,9 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             int il, ly, lx;
-            if constexpr (G == 1) {
+            if constexpr (COL) {
+                il = GEO::img(wm, i, rr), ly = GEO::y(rr), lx = GEO::x(i);
+            } else if constexpr (G == 1) {
                 const int ml = (wm * MT + i) * 16 + rr;
                 il = ml / TPIX;
                 const int rem = ml - il * TPIX;
@@ -270,13 +292,13 @@ __global__ __launch_bounds__(512) void conv3x3_sp_patch_kernel(const ConvArgs a,
     }
 }
 
-template <int MT, int NT, int WM, int WN, int TH, int TW>
+template <int MT, int NT, int WM, int WN, int TH, int TW, bool COL = false>
 static void launch_sp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
-    constexpr int NI = BM / (TH * TW), NPIX = NI * ppp_ipix_pad(TH, TW), NPASS = (NPIX + 127) / 128;
+    constexpr int NI = BM / (TH * TW), NPIX = NI * PatchGeom<TH, TW, NI, WM, MT, COL>::IPIXP, NPASS = (NPIX + 127) / 128;
     constexpr size_t lds = (size_t)2 * 4 * NPASS * 128 * 16 + 8192 + (size_t)4 * BN * 64;
     static_assert(lds <= 160 * 1024, "does not fit the LDS");
-    auto kfn = conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW>;
+    auto kfn = conv3x3_sp_patch_kernel<MT, NT, WM, WN, TH, TW, COL>;
     set_lds_limit(kfn, lds);
     hipLaunchKernelGGL(kfn, dim3((unsigned)p.blocks), dim3(512), lds, s, a, a.Cout / BN, p.run);
     KCHECK();
@@ -592,9 +614,14 @@ void launch_conv_s2_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
 // the shapes of v5 without a second source (conv_plan.cpp: 2 = Cout 128 on 32 x 16 maps, 3 / 4 = Cout % 256 on 16 x 8 / 8 x 4 maps), fp16
 void launch_conv_sp_patch(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
     const bool t84 = p.mt == 8 && p.nt == 4;
+    // AICAM_NO_PAD_SKIP=1: row-piece tiles and every tap on the two narrow maps too, as before the column tiles (A/B runs, the reference
+    // of tests/test_gpu_pad_skip.py's bit-equality)
+    static const bool col = getenv("AICAM_NO_PAD_SKIP") == nullptr;
     if (t84 && p.wm == 4 && p.wn == 2 && p.th == 32 && p.tw == 16) return launch_sp_patch<8, 4, 4, 2, 32, 16>(a, p, s);
-    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 16 && p.tw == 8) return launch_sp_patch<8, 4, 2, 4, 16, 8>(a, p, s);
-    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 8 && p.tw == 4) return launch_sp_patch<8, 4, 2, 4, 8, 4>(a, p, s);
+    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 16 && p.tw == 8)
+        return col ? launch_sp_patch<8, 4, 2, 4, 16, 8, true>(a, p, s) : launch_sp_patch<8, 4, 2, 4, 16, 8>(a, p, s);
+    if (t84 && p.wm == 2 && p.wn == 4 && p.th == 8 && p.tw == 4)
+        return col ? launch_sp_patch<8, 4, 2, 4, 8, 4, true>(a, p, s) : launch_sp_patch<8, 4, 2, 4, 8, 4>(a, p, s);
     AIC_REQUIRE(false, AIC_ERR_INVALID, "conv plan: no software-pipelined patch instantiation for this tile");
 }
 
