@@ -255,6 +255,26 @@ _SIGS = {
     "aic_frames_to_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
     "aic_frames_from_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
     "aic_pipeline_read_frames": (_I, [_P, _I, _I, _P]),
+    "aic_archive_index_create": (_I, [C.c_int64, _P]),
+    "aic_archive_index_destroy": (_I, [_P]),
+    "aic_archive_index_assign": (_I, [_P, _P, _P, C.c_int64, _I, _P, _P]),
+    "aic_archive_index_find": (_I, [_P, C.c_int64, _P]),
+    "aic_archive_index_remove": (_I, [_P, C.c_int64, _P]),
+    "aic_archive_index_size": (_I, [_P, _P, _P]),
+    "aic_archive_create": (_I, [_I, C.c_int64, _I, _P]),
+    "aic_archive_destroy": (_I, [_P]),
+    "aic_archive_put": (_I, [_P, _P, _P, C.c_int64, _P, _I, _I]),
+    "aic_archive_remove": (_I, [_P, C.c_int64]),
+    "aic_archive_search": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "aic_archive_size": (_I, [_P, _P, _P]),
+    "aic_archive_export": (_I, [_P] * 8),
+    "aic_archive_import": (_I, [_P] * 7 + [C.c_int64]),
+    "aic_archive_clear": (_I, [_P]),
+    "aic_archive_block_rows": (_I, [_P, _I, _P]),
+    "aic_gid_find_key": (_I, [_P, C.c_int64, _P]),
+    "aic_gid_link_keys": (_I, [_P, C.c_int64, C.c_int64, _P]),
+    "aic_xcam_attach_archive": (_I, [_P, _P]),
+    "aic_xcam_returning": (_I, [_P, _P, _P, _P, _P, _I, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -71,6 +71,11 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--link_cameras", action="store_true",
                    help="--inputs with --tracker botsort or deepsort_bank only: link the cameras' identities on the device after every run call; every JSON line "
                         "gains \"global_ids\" parallel to \"tracks\" (-1 = not linked yet) and the overlay label shows the global id")
+    p.add_argument("--archive", type=int, default=0, metavar="CAPACITY",
+                   help="with --link_cameras: keep up to CAPACITY appearance rows of past tracks on the device; a person who comes back, on any "
+                        "camera, gets the identity they had, and every JSON line gains \"returning\": [[track id, archived key, distance], ...]")
+    p.add_argument("--archive_file", type=str, default=None, help="with --archive: load the archive from this .npz at the start if it exists, save it at the end")
+    p.add_argument("--archive_min_gap", type=int, default=1, help="with --archive: link passes a row must have been gone for before it counts as returning")
     p.add_argument("--zones", type=str, default=None,
                    help="JSON file {\"cameras\": [{\"zones\": [[[x, y], ...], ...], \"lines\": [[[x, y], [x, y]], ...]}, ...]} in integer pixels, one entry per "
                         "source (a single entry serves every source): zone entries, dwell and line crossings are counted on the device and every "
@@ -101,6 +106,12 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--gmc needs --tracker botsort")
     if args.link_cameras and (args.inputs is None or args.tracker not in ("botsort", "deepsort_bank")):
         p.error("--link_cameras needs --inputs a,b,c --tracker botsort or deepsort_bank")
+    if args.archive < 0 or args.archive > (1 << 24) or args.archive_min_gap < 0:
+        p.error("--archive CAPACITY is in 1..2^24, --archive_min_gap is >= 0")
+    if args.archive and not args.link_cameras:
+        p.error("--archive needs --link_cameras")
+    if (args.archive_file is not None or args.archive_min_gap != 1) and not args.archive:
+        p.error("--archive_file and --archive_min_gap need --archive CAPACITY")
     if args.tracker == "deepsort_bank" and args.inputs is None:
         p.error("--tracker deepsort_bank needs --inputs a,b,c (one source: --tracker deepsort)")
     if args.draw_zones and not args.zones:
@@ -392,6 +403,14 @@ def main_streams(args, cv2):
             outs[k] = open(str(stem) + ".jsonl", "w")
             writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None, **yuv_out)
     pipe.link_after_run = bool(args.link_cameras)
+    archive = None
+    if args.archive:
+        try:
+            archive = _attach_archive(args, pipe, dev)
+        except Exception as e:
+            print(f"Error setting up --archive: {e}")
+            pipe.close()
+            return 1
     zones = None
     if args.zones:
         try:
@@ -434,6 +453,8 @@ def main_streams(args, cv2):
                 line = {"frame": idx, "tracks": tracks}
                 if gids is not None:
                     line["global_ids"] = gids
+                if archive is not None:
+                    line["returning"] = [[t, key, d] for c, t, key, d in pipe.xcam.returning() if c == k]
                 if zones is not None:
                     line["zones"] = zones.line(tracks)
                 outs[k].write(json.dumps(line) + "\n")
@@ -447,6 +468,11 @@ def main_streams(args, cv2):
             zones.close()
         if output is not None:
             output.close()
+        if archive is not None:
+            if args.archive_file:
+                archive.save(args.archive_file)
+            pipe.xcam.attach_archive(None)
+            archive.close()
         pipe.close()
     total = time.time() - t0
     print("\n--- Processing Summary ---")
@@ -454,6 +480,24 @@ def main_streams(args, cv2):
     print(f"Total time: {total:.2f} seconds; average FPS over all streams: {n / total if total > 0 else 0:.2f}")
     print("AICamera finished.")
     return 0
+
+
+def _attach_archive(args, pipe, dev):
+    """--archive: the pipeline's cross-camera object, made now so that the archive can be attached before the first pass."""
+    from .archive import IdentityArchive
+    from .xcam import CrossCamera
+    if pipe.tracker_kind == "deepsort":
+        p, dim, thr = pipe.tracker_params, int(pipe.reid.out_dim), pipe.tracker_params.max_cosine_distance
+    else:
+        p, dim, thr = pipe.botsort_params, pipe.botsort_params.feature_dim or 512, config.DEEPSORT_MAX_DIST
+    archive = IdentityArchive(args.archive, dim, device=dev)
+    if args.archive_file and Path(args.archive_file).exists():
+        archive.load(args.archive_file)
+    pipe.xcam = CrossCamera(pipe.streams, p.max_tracks or 512, dim, thr, device=dev)
+    pipe.xcam.option("min_gap", args.archive_min_gap)
+    pipe.archive = archive
+    pipe.xcam.attach_archive(archive)
+    return archive
 
 
 def main(argv=None):

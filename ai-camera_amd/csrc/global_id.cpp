@@ -56,6 +56,19 @@ int64_t GidTable::lookup(int rank, int track_id) {
     return it == first.end() ? -1 : (int64_t)find(it->second);
 }
 
+int64_t GidTable::find_key(int64_t k) {
+    auto it = k < 0 ? first.end() : first.find((uint64_t)k);
+    return it == first.end() ? -1 : (int64_t)find(it->second);
+}
+
+bool GidTable::link_keys(int64_t a, int64_t b) {
+    auto ia = a < 0 ? first.end() : first.find((uint64_t)a), ib = b < 0 ? first.end() : first.find((uint64_t)b);
+    AIC_REQUIRE(ia != first.end() && ib != first.end(), AIC_ERR_INVALID, "link_keys: a key that was never filed");
+    if (!unite(ia->second, ib->second)) return false;
+    links += 1;
+    return true;
+}
+
 }  // namespace aic
 
 using namespace aic;
@@ -96,6 +109,21 @@ int aic_gid_forget_rank(aic_gid* g, int rank) {
     return guarded([&] {
         AIC_REQUIRE(g, AIC_ERR_INVALID, "NULL argument");
         g->t.forget_rank(rank);
+    });
+}
+
+int aic_gid_find_key(aic_gid* g, int64_t key, int64_t* global_id) {
+    return guarded([&] {
+        AIC_REQUIRE(g && global_id, AIC_ERR_INVALID, "NULL argument");
+        *global_id = g->t.find_key(key);
+    });
+}
+
+int aic_gid_link_keys(aic_gid* g, int64_t key_a, int64_t key_b, int32_t* linked) {
+    return guarded([&] {
+        AIC_REQUIRE(g, AIC_ERR_INVALID, "NULL argument");
+        const bool l = g->t.link_keys(key_a, key_b);
+        if (linked) *linked = l;
     });
 }
 

@@ -47,6 +47,10 @@ struct GidTable {
     // one nearest-neighbour table (aic_gallery_annotate's arrays, or the bank pass of xcam.cpp) -> new links
     int update(int world_, int t_max, const int32_t* track_id, const int32_t* near_row, const float* near_dist, double max_cosine_distance);
     int64_t lookup(int rank, int track_id);
+    // by the key itself, whatever the rank's generation is now (the archive keeps keys of generations past): -1 = never filed
+    int64_t find_key(int64_t k);
+    // two filed keys become one identity under the smaller root; true = two identities were merged
+    bool link_keys(int64_t a, int64_t b);
 };
 
 }  // namespace aic

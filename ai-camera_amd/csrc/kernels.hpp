@@ -165,6 +165,19 @@ void launch_xcam_nearest(const float* shards, const int* n_valid, int streams, i
                          int* near_row, float* near_dist, hipStream_t s);
 void launch_trk_cascade_test(const TrkDevParams& prm, const EpochScratch& scr, int T, int n, const int* state, const int* tsu,
                              int* out_mdet, int* out_err, int stage1_only, hipStream_t s);
+// the identity archive (kernels_archive.hip, archive.hpp): int8 rows at `pitch` bytes (dim rounded up to 64, zero padded), one scale a row,
+// metadata per slot (key < 0 = free).  Every per-slot array is allocated for the capacity rounded up to 16 (rows: plus 128 bytes).
+constexpr int ARCHIVE_MIN_BLOCK_ROWS = 64;
+// put: row src_index[i] (device list; NULL: i) of src (row_stride floats apart, payload at + offset) -> slot slots[i] (NULL: i); keys[i] < 0 or slots[i] < 0 skips the row;
+// mode 0 = check only.  *flag |= 1 for a row that has no code (all zero, non-finite).  key == NULL: no metadata (the queries' prologue)
+void launch_archive_put(const float* src, const int* src_index, long row_stride, int offset, int dim, int pitch, int n, const int* slots, const long long* keys,
+                        const int* cams, long long tick, int mode, signed char* rows, float* scale, int* camera, long long* t_last, long long* key,
+                        int* flag, hipStream_t s);
+int archive_block_rows(int hw, int n_queries);                 // R: the slots one block of the search owns (a multiple of 64)
+size_t archive_partial_keys(int hw, int n_queries, int k);     // 64-bit keys of `part` below
+void launch_archive_search(const signed char* rows, const float* scale, const int* camera, const long long* t_last, const long long* key, int hw,
+                           int pitch, const signed char* qrows, const float* qscale, const aic_archive_filter* flt, int n_queries, int k,
+                           unsigned long long* part, int* out_slot, float* out_dist, long long* out_key, hipStream_t s);
 
 
 }  // namespace aic

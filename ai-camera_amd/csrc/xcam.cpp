@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <map>
 
 namespace aic {
 
@@ -48,7 +50,48 @@ int XCam::pass(hipStream_t s, const int32_t* expect) {
             AIC_REQUIRE(nv[q] == expect[q], AIC_ERR_INVALID, "stream " + std::to_string(q) + ": n_valid differs from the shard's valid column");
     const int links = gid.update(n_streams, t_max, ids(), near_row(), near_dist(), max_cos);
     has_pass = true;
+    if (archive) archive_step();
     return links;
+}
+
+void XCam::archive_step() {
+    const int64_t tick = passes;
+    returning.clear();
+    std::vector<int64_t> keys(n, -1);
+    std::vector<int32_t> cams(n, 0), fresh;
+    for (int i = 0; i < n; ++i) {
+        if (ids()[i] < 0) continue;
+        keys[i] = (int64_t)gid.key(i / t_max, ids()[i]);
+        cams[i] = i / t_max;
+        if (archive->ix.find(keys[i]) < 0) fresh.push_back(i);
+    }
+    const int nf = (int)fresh.size();
+    if (nf && archive->ix.hw > 0) {
+        const aic_archive_filter f{-1, (float)max_cos, std::numeric_limits<int64_t>::min(), tick - 1 - min_gap, -1};
+        const std::vector<aic_archive_filter> flt(nf, f);
+        archive->search(d_shards.p, 2 + dim, 2, nf, AIC_DEVICE, 1, flt.data(), fresh.data());
+        const int32_t* rs = archive->res_slots();
+        const float* rd = archive->res_dist(nf, 1);
+        const int64_t* rk = archive->res_keys(nf, 1);
+        std::map<int32_t, int> winner;                 // archived slot -> index into fresh
+        for (int j = 0; j < nf; ++j) {
+            if (rs[j] < 0) continue;
+            auto it = winner.find(rs[j]);
+            if (it == winner.end()) winner.emplace(rs[j], j);
+            else if (rd[j] < rd[it->second]) it->second = j;   // distances are >= +0: the bits order like the values; a tie keeps the lower shard row
+        }
+        std::vector<int> won;
+        for (auto& w : winner) won.push_back(w.second);
+        std::sort(won.begin(), won.end());
+        for (int j : won) {
+            const int i = fresh[j];
+            gid.first.emplace((uint64_t)rk[j], (uint64_t)rk[j]);   // an imported archive may hold keys this table never saw
+            gid.link_keys(keys[i], rk[j]);
+            returning.push_back({i / t_max, ids()[i], rk[j], rd[j]});
+        }
+    }
+    archive->put(keys.data(), cams.data(), tick, d_shards.p, 2 + dim, 2, n, AIC_DEVICE);
+    passes = tick + 1;
 }
 
 template <class Bank>
@@ -132,6 +175,9 @@ int aic_xcam_option(aic_xcam* x, const char* key, int value) {
         if (k == "tile") {
             AIC_REQUIRE(value == 0 || value == 32 || value == 64, AIC_ERR_INVALID, "tile: 0 by size, 32 or 64 rows");
             x->x.tile = value;
+        } else if (k == "min_gap") {
+            AIC_REQUIRE(value >= 0, AIC_ERR_INVALID, "min_gap must be >= 0");
+            x->x.min_gap = value;
         } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown cross-camera option: " + k);
     });
 }
@@ -197,6 +243,44 @@ int aic_xcam_size(aic_xcam* x, int64_t* n_tracks, int64_t* n_identities, int64_t
         if (n_tracks) *n_tracks = (int64_t)t.first.size();
         if (n_identities) *n_identities = (int64_t)t.first.size() - (int64_t)t.parent.size();
         if (n_links) *n_links = t.links;
+    });
+}
+
+int aic_xcam_attach_archive(aic_xcam* x, aic_archive* a) {
+    return guarded([&] {
+        AIC_REQUIRE(x, AIC_ERR_INVALID, "NULL argument");
+        if (a) {
+            AIC_REQUIRE(a->a.dim == x->x.dim, AIC_ERR_INVALID, "the archive's dimension differs from the cross-camera object's");
+            AIC_REQUIRE(a->a.dev == x->x.dev, AIC_ERR_INVALID, "the archive lives on another device");
+        }
+        x->x.archive = a ? &a->a : nullptr;
+        if (!a) return;
+        // rows of an earlier run (an imported archive): the clock goes on behind their last deposit, and a camera whose archived keys this
+        // table never filed starts a generation above them, so that this run's (stream, track id) keys are not taken for theirs
+        const ArchiveIndex& ix = a->a.ix;
+        GidTable& g = x->x.gid;
+        if (!ix.by_age.empty()) x->x.passes = std::max(x->x.passes, ix.by_age.rbegin()->first + 1);
+        for (int s = 0; s < ix.hw; ++s) {
+            const int64_t k = ix.key[s];
+            if (k < 0 || g.first.count((uint64_t)k)) continue;
+            const int rank = (int)((k >> 32) & ((1 << GidTable::kRankBits) - 1));
+            const uint32_t gen = (uint32_t)(k >> (32 + GidTable::kRankBits));
+            if (rank < g.world && gen < GidTable::kGenMax && g.generation(rank) <= gen) g.gen[rank] = gen + 1;
+        }
+    });
+}
+
+int aic_xcam_returning(aic_xcam* x, int32_t* stream, int32_t* track_id, int64_t* archived_key, float* dist, int cap, int32_t* n) {
+    return guarded([&] {
+        AIC_REQUIRE(x && cap >= 0, AIC_ERR_INVALID, "bad argument");
+        const auto& r = x->x.returning;
+        if (n) *n = (int32_t)r.size();
+        for (int i = 0; i < cap && i < (int)r.size(); ++i) {
+            if (stream) stream[i] = r[i].stream;
+            if (track_id) track_id[i] = r[i].track_id;
+            if (archived_key) archived_key[i] = r[i].archived_key;
+            if (dist) dist[i] = r[i].dist;
+        }
     });
 }
 

@@ -6,6 +6,7 @@
 //
 // Device memory, allocated at the first pass: shards streams * t_max * (2 + dim) * 4 bytes (67 MB at 256 x 128 x 512), tables 20 bytes a row.
 #pragma once
+#include "archive.hpp"
 #include "botsort_host.hpp"
 #include "common.hpp"
 #include "deepsort_bank.hpp"
@@ -30,6 +31,12 @@ struct XCam {
     DevBuf<unsigned long long> d_best;       // [n] keys of the nearest kernel
     PinBuf<int> h_tab;                       // the read-back of d_tab: the last pass's tables
     bool has_pass = false;
+    // the identity archive (archive.hpp), not owned.  With one attached a pass ends with archive_step()
+    Archive* archive = nullptr;
+    int min_gap = 1;                         // an archived row answers a new track only when its last deposit is more than min_gap passes old
+    int64_t passes = 0;                      // completed passes with an archive attached = the next pass's tick
+    struct Returning { int32_t stream, track_id; int64_t archived_key; float dist; };
+    std::vector<Returning> returning;        // the last pass's winners, ascending shard row
 
     XCam(Device& d, int streams, int t_max_, int dim_, double max_cosine_distance);
     void ensure();
@@ -41,6 +48,9 @@ struct XCam {
     // d_shards, n_valid and flags are on their way (stream s): nearest rows, ONE read-back, ONE sync, then the policy on the host.
     // expect (may be NULL): the caller's n_valid, held against the device's counts before the policy sees the tables
     int pass(hipStream_t s, const int32_t* expect = nullptr);
+    // after the policy: the pass's new rows against the archive (k = 1; the queries are the shard rows on the device), one winner per
+    // archived row, link_keys for the winners, then every valid row of the pass is deposited
+    void archive_step();
     int link(DeepSortBank& b);
     int link(BotSortTracker& b);
     int link_shards(const float* shards, const int32_t* n_valid, int mem);

@@ -223,10 +223,13 @@ class TrackingPipeline:
         if self.xcam is not None:
             self.xcam.forget_stream(s)
 
-    def link_cameras(self, xcam=None):
+    archive = None
+
+    def link_cameras(self, xcam=None, archive=None):
         """botsort_bank and deepsort_bank pipelines, between run calls: one cross-camera pass over the bank's activated / confirmed tracks
         (xcam.py).  The first call creates and keeps a CrossCamera unless one is handed over (a DeepSORT bank links within its
-        max_cosine_distance); returns the identities merged by this call."""
+        max_cosine_distance); returns the identities merged by this call.  archive: an IdentityArchive (archive.py) the pass searches
+        for returning people and deposits its rows in; it stays attached."""
         if self.tracker_kind not in ("botsort", "deepsort") or not self.cameras:
             raise ValueError("link_cameras needs a TrackingPipeline.botsort_bank or deepsort_bank pipeline")
         from .xcam import CrossCamera
@@ -238,6 +241,10 @@ class TrackingPipeline:
         if self.xcam is None:
             p = self.botsort_params
             self.xcam = CrossCamera(self.streams, p.max_tracks or 512, p.feature_dim or 512, device=self._device)
+        if archive is not None:
+            self.archive = archive
+        if self.archive is not None and self.xcam.archive is not self.archive:
+            self.xcam.attach_archive(self.archive)
         return self.xcam.link_pipeline(self)
 
     def global_ids(self, stream, track_ids):

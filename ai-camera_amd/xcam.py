@@ -18,6 +18,8 @@ class CrossCamera:
     of the identity's first sighting; two tracks of different cameras that are each other's nearest neighbour within the threshold
     adopt the smaller one."""
 
+    archive = None
+
     def __init__(self, streams, t_max, dim, max_cosine_distance=config.DEEPSORT_MAX_DIST, device=0):
         self.streams, self.t_max, self.dim = int(streams), int(t_max), int(dim)
         self.max_cosine_distance = float(max_cosine_distance)
@@ -36,8 +38,24 @@ class CrossCamera:
             pass
 
     def option(self, key, value):
-        """"tile": 32 / 64 = rows per tile of the nearest kernel, 0 = by size.  Same results either way."""
+        """"tile": 32 / 64 = rows per tile of the nearest kernel, 0 = by size.  Same results either way.  "min_gap" (default 1): an
+        archived row answers a new track only when its last deposit is more than min_gap passes old."""
         L.call("aic_xcam_option", self._h, str(key).encode(), int(value))
+
+    def attach_archive(self, archive):
+        """Every link pass from now on ends with three more steps (archive.py; None detaches): the pass's rows whose key the archive does
+        not hold are searched in it, a match within the threshold that is older than min_gap passes gives the new track the archived
+        row's identity (one new track per archived row: the nearest), and every valid row of the pass is deposited."""
+        L.call("aic_xcam_attach_archive", self._h, None if archive is None else archive._h)
+        self.archive = archive
+
+    def returning(self):
+        """The last pass's returning tracks: [(stream, track id, archived key, distance)], ascending shard row."""
+        n = C.c_int32()
+        L.call("aic_xcam_returning", self._h, None, None, None, None, 0, C.byref(n))
+        st, ti, ak, di = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.int64), np.zeros(n.value, np.float32)
+        L.call("aic_xcam_returning", self._h, L.ptr(st), L.ptr(ti), L.ptr(ak), L.ptr(di), n.value, C.byref(n))
+        return [(int(a), int(b), int(c), float(d)) for a, b, c, d in zip(st, ti, ak, di)]
 
     def _link(self, name, *args):
         n = C.c_int32()
@@ -108,13 +126,16 @@ class CameraLinks:
     def _link_threshold(self):
         return config.DEEPSORT_MAX_DIST
 
-    def link_cameras(self, xcam=None):
+    def link_cameras(self, xcam=None, archive=None):
         """One cross-camera pass over the bank, between update calls.  The first call creates and keeps a CrossCamera (t_max = max_tracks:
-        every eligible track takes part) unless one is handed over; returns the identities merged by this call."""
+        every eligible track takes part) unless one is handed over; returns the identities merged by this call.  archive: an
+        IdentityArchive to attach to it (CrossCamera.attach_archive); it stays attached."""
         if xcam is not None:
             self.xcam = xcam
         if self.xcam is None:
             self.xcam = CrossCamera(self.streams, self.max_tracks or 512, self.feature_dim, self._link_threshold(), device=self._device)
+        if archive is not None and self.xcam.archive is not archive:
+            self.xcam.attach_archive(archive)
         return self.xcam.link_bank(self)
 
     def global_ids(self, stream, track_ids):

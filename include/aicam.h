@@ -754,6 +754,65 @@ int aic_xcam_forget_stream(aic_xcam* x, int stream);
  * calls; AIC_ERR_INVALID on any other pipeline. */
 int aic_pipeline_link_cameras(aic_pipeline* p, aic_xcam* x, int32_t* n_links);
 
+/* ------------------------------------------------------------------ identity archive
+ * The memory the link pass lacks: appearance rows of tracks that have ended, searched with int8 MFMA.  A row is known by an int64
+ * key >= 0 (for bank rows the global-id key generation << 44 | stream << 32 | track id) and carries a camera and the ticks of its first
+ * and last deposit.  Stored: int8 codes q_i = rint(v_i * (127 / m)), m = max |v_i|, half to even, and scale = m / 127; a distance is
+ * max(+0, 1 - (float(dot) * scale_row) * scale_query) with the exact int32 dot of the codes; results are ranked by
+ * (distance bits << 32 | slot).  The query is quantised the same way.
+ *
+ * aic_archive_index_*: the slot bookkeeping alone, HOST code, no device.  assign is an upsert of n keys at `tick`: a known key keeps its
+ * slot and t_first; a new key takes the lowest free slot, or, when all `capacity` slots are taken, the slot of the smallest
+ * (t_last, slot), whose key goes to evicted[i] (else -1).  Where one call names a slot twice the last row keeps it: the earlier rows get
+ * slots[i] = -1.  find: -1 = unknown.  remove: *slot = the freed slot or -1.
+ * aic_archive_*: create: capacity 1..2^24, dim a multiple of 4 in 4..1024 (checked before the device).  put: n fp32 rows [n, dim] in host
+ * or device memory; a row that is all zero, holds a non-finite element or has no finite 127 / m fails the call with AIC_ERR_INVALID
+ * and nothing of the call is stored.  search: n queries [n, dim], k in 1..32, filters[n] (NULL = none); outputs [n, k] on the host (any
+ * may be NULL), missing places -1 / -1 / 1e5; one read-back, one synchronisation.  A slot is eligible when it is occupied,
+ * camera != exclude_camera (-1 = none), t_lo <= t_last <= t_hi, key != exclude_key (-1 = none) and dist <= max_distance (fp32).
+ * export: *n = the high-water mark; arrays [n] (rows [n, pitch], pitch = dim rounded up to 64), free slots have key -1; every array may
+ * be NULL.  import replaces the contents with such arrays.  block_rows: the slots one block of a search of n_queries owns now. */
+typedef struct aic_archive_filter {
+    int32_t exclude_camera;
+    float max_distance;
+    int64_t t_lo, t_hi, exclude_key;
+} aic_archive_filter;
+typedef struct aic_archive_index aic_archive_index;
+int aic_archive_index_create(int64_t capacity, aic_archive_index** out);
+int aic_archive_index_destroy(aic_archive_index* ix);
+int aic_archive_index_assign(aic_archive_index* ix, const int64_t* keys, const int32_t* cameras, int64_t tick, int n, int32_t* slots,
+                             int64_t* evicted);
+int aic_archive_index_find(aic_archive_index* ix, int64_t key, int32_t* slot);
+int aic_archive_index_remove(aic_archive_index* ix, int64_t key, int32_t* slot);
+int aic_archive_index_size(aic_archive_index* ix, int64_t* n_rows, int64_t* high_water);
+typedef struct aic_archive aic_archive;
+int aic_archive_create(int device, int64_t capacity, int dim, aic_archive** out);
+int aic_archive_destroy(aic_archive* a);
+int aic_archive_put(aic_archive* a, const int64_t* keys, const int32_t* cameras, int64_t tick, const float* rows, int n, int mem);
+int aic_archive_remove(aic_archive* a, int64_t key);
+int aic_archive_search(aic_archive* a, const float* queries, int n, int mem, int k, const aic_archive_filter* filters, int64_t* out_keys,
+                       int32_t* out_slots, float* out_dist);
+int aic_archive_size(aic_archive* a, int64_t* n_rows, int64_t* high_water);
+int aic_archive_export(aic_archive* a, int64_t* keys, int32_t* cameras, int64_t* t_first, int64_t* t_last, float* scales, int8_t* rows,
+                       int64_t* n);
+int aic_archive_import(aic_archive* a, const int64_t* keys, const int32_t* cameras, const int64_t* t_first, const int64_t* t_last,
+                       const float* scales, const int8_t* rows, int64_t n);
+int aic_archive_clear(aic_archive* a);
+int aic_archive_block_rows(aic_archive* a, int n_queries, int32_t* rows);
+/* find_key: the global id of any filed key, whatever its rank's current generation (-1 = never filed).  link_keys: two filed keys become
+ * one identity under the smaller root; *linked = 1 when that merged two identities.  AIC_ERR_INVALID for a key that was never filed. */
+int aic_gid_find_key(aic_gid* g, int64_t key, int64_t* global_id);
+int aic_gid_link_keys(aic_gid* g, int64_t key_a, int64_t key_b, int32_t* linked);
+/* With an archive attached (same device, same dim), every link pass ends with three more steps at tick = passes so far: the pass's valid
+ * rows whose key the archive does not hold are searched (k = 1, t_hi = tick - 1 - min_gap, max_distance = the object's threshold; the
+ * queries stay on the device); where several name one archived row the smallest (distance bits, shard row) keeps it, and the winners'
+ * keys are linked to the archived keys; then every valid row of the pass is deposited.  option "min_gap" (default 1, >= 0).  returning:
+ * the last pass's winners, ascending shard row (*n = their number, at most cap are stored).  a == NULL detaches.  Attaching an archive that
+ * holds rows of an earlier run (aic_archive_import) moves the tick behind their last deposit and starts every camera whose archived keys
+ * the object never filed in a generation above them. */
+int aic_xcam_attach_archive(aic_xcam* x, aic_archive* a);
+int aic_xcam_returning(aic_xcam* x, int32_t* stream, int32_t* track_id, int64_t* archived_key, float* dist, int cap, int32_t* n);
+
 /* ---- zone entries, dwell and line crossings per camera (csrc/zones.hpp) -------------------------------------
  * A tracker-agnostic stage over the rows every tracker delivers (x1 y1 x2 y2 id cls, int32).  `streams` (1..256) cameras, each with
  * up to 32 zones (simple polygons of 3..32 integer-pixel vertices, either winding) and 32 directed lines A->B, and a table of
