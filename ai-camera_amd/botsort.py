@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib as L
 from . import config
-from .bytetrack import TrackerBank
+from .bytetrack import TrackerBank, export_tracks, frame_rows, output_tuples
 from .xcam import CameraLinks
 
 
@@ -106,15 +106,9 @@ class BoTSORT:
         L.call("aic_botsort_update_batch", self._h, k, L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), L.ptr(feat), L.ptr(valid),
                L.ptr(warps), cap, L.ptr(n_out), L.ptr(out6), L.ptr(oconf))
         self.frame_id += k
-        res = []
-        for f in range(k):
-            m = min(int(n_out[f]), cap)
-            res.append((out6[f, :m].copy(), oconf[f, :m].copy()))
-        return res
+        return frame_rows(n_out, out6, oconf, cap, 0, k)
 
-    @staticmethod
-    def _tuples(rows, conf):
-        return [(r[0], r[1], r[2], r[3], r[4], config.class_name(r[5]), cf) for r, cf in zip(rows.tolist(), conf.tolist())]
+    _tuples = staticmethod(output_tuples)
 
     def update(self, boxes_xyxy, scores, class_ids, features=None, warp=None):
         """One frame (BoTSORT.update). Empty inputs (np.array([])) are accepted."""
@@ -132,16 +126,7 @@ class BoTSORT:
 
     def export(self):
         """Live tracks in list order (tracked list, then lost list): dict of arrays + n_tracked (the tracked list's length)."""
-        n, nt = C.c_int32(), C.c_int32()
-        L.call("aic_botsort_export", self._h, 0, *([None] * 11), C.byref(n), C.byref(nt))
-        m = n.value
-        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
-                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
-                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32),
-                   has_feat=np.zeros(m, np.int32), smooth_feat=np.zeros((m, self.feature_dim), np.float32))
-        L.call("aic_botsort_export", self._h, m, *(L.ptr(v) for v in out.values()), C.byref(n), C.byref(nt))
-        out["n_tracked"] = nt.value
-        return out
+        return export_tracks("aic_botsort_export", self._h, feature_dim=self.feature_dim)
 
 
 class BoTSORTBank(CameraLinks, TrackerBank):
@@ -180,7 +165,7 @@ class BoTSORTBank(CameraLinks, TrackerBank):
         """One tick: `streams` entries (boxes_xyxy, scores, class_ids[, features[, warp]]), None = no frame from that camera this
         tick.  Returns `streams` lists of (x1, y1, x2, y2, track_id, class_name, conf) tuples, None for a stopped stream."""
         got = self.update_arrays([[] if d is None else [d] for d in per_stream_detections])
-        return [None if g is None else (BoTSORT._tuples(*g[0]) if g else []) for g in got]
+        return [None if g is None else (output_tuples(*g[0]) if g else []) for g in got]
 
     def counters(self, stream):
         """BoTSORT.counters() of one stream."""
@@ -192,13 +177,4 @@ class BoTSORTBank(CameraLinks, TrackerBank):
 
     def export(self, stream):
         """BoTSORT.export() of one stream; raises for a stopped stream."""
-        n, nt = C.c_int32(), C.c_int32()
-        L.call("aic_botsort_bank_export", self._h, int(stream), 0, *([None] * 11), C.byref(n), C.byref(nt))
-        m = n.value
-        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
-                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
-                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32),
-                   has_feat=np.zeros(m, np.int32), smooth_feat=np.zeros((m, self.feature_dim), np.float32))
-        L.call("aic_botsort_bank_export", self._h, int(stream), m, *(L.ptr(v) for v in out.values()), C.byref(n), C.byref(nt))
-        out["n_tracked"] = nt.value
-        return out
+        return export_tracks("aic_botsort_bank_export", self._h, int(stream), feature_dim=self.feature_dim)

@@ -23,6 +23,36 @@ def bytetrack_params(track_thresh=0.5, track_buffer=30, match_thresh=0.8, mot20=
                              fuse_score=0 if mot20 else 1, max_tracks=int(max_tracks), first_track_id=int(first_track_id))
 
 
+def output_tuples(rows, conf):
+    """Output rows and scores of one frame as DeepSORT.update's tuples (x1, y1, x2, y2, track_id, class_name, conf)."""
+    return [(r[0], r[1], r[2], r[3], r[4], config.class_name(r[5]), cf) for r, cf in zip(rows.tolist(), conf.tolist())]
+
+
+def frame_rows(n_out, out6, oconf, cap, first, count):
+    """Frames [first, first + count) of an update call's flat outputs as a list of (rows [m,6] int32, conf [m] fp32)."""
+    res = []
+    for f in range(first, first + count):
+        m = min(int(n_out[f]), cap)
+        res.append((out6[f, :m].copy(), oconf[f, :m].copy()))
+    return res
+
+
+_EXPORT = (("track_id", np.int32, ()), ("state", np.int32, ()), ("is_activated", np.int32, ()), ("start_frame", np.int32, ()),
+           ("end_frame", np.int32, ()), ("cls", np.int32, ()), ("score", np.float32, ()), ("mean", np.float32, (8,)), ("cov", np.float32, (8, 8)))
+
+
+def export_tracks(abi, *lead, feature_dim=None):
+    """aic_bytetrack_export and its kin (`abi`, called with the leading arguments `lead`): the live tracks in list order (tracked list,
+    then lost list) as a dict of arrays + n_tracked (the tracked list's length); with feature_dim, BoT-SORT's two columns on top."""
+    cols = _EXPORT + ((("has_feat", np.int32, ()), ("smooth_feat", np.float32, (feature_dim,))) if feature_dim else ())
+    n, nt = C.c_int32(), C.c_int32()
+    L.call(abi, *lead, 0, *([None] * len(cols)), C.byref(n), C.byref(nt))
+    out = {k: np.zeros((n.value,) + shape, dt) for k, dt, shape in cols}
+    L.call(abi, *lead, n.value, *(L.ptr(v) for v in out.values()), C.byref(n), C.byref(nt))
+    out["n_tracked"] = nt.value
+    return out
+
+
 class BYTETracker:
     """update(boxes_xyxy, scores, class_ids) -> [(x1, y1, x2, y2, track_id, class_name, conf), ...] as DeepSORT.update, for the
     activated tracks of the tracked list (ByteTrack's output_stracks).  Association is class-agnostic, as upstream."""
@@ -73,15 +103,9 @@ class BYTETracker:
         L.call("aic_bytetrack_update_batch", self._h, k, L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), cap, L.ptr(n_out),
                L.ptr(out6), L.ptr(oconf))
         self.frame_id += k
-        res = []
-        for f in range(k):
-            m = min(int(n_out[f]), cap)
-            res.append((out6[f, :m].copy(), oconf[f, :m].copy()))
-        return res
+        return frame_rows(n_out, out6, oconf, cap, 0, k)
 
-    @staticmethod
-    def _tuples(rows, conf):
-        return [(r[0], r[1], r[2], r[3], r[4], config.class_name(r[5]), cf) for r, cf in zip(rows.tolist(), conf.tolist())]
+    _tuples = staticmethod(output_tuples)
 
     def update(self, boxes_xyxy, scores, class_ids):
         """One frame (BYTETracker.update). Empty inputs (np.array([])) are accepted."""
@@ -100,17 +124,7 @@ class BYTETracker:
 
     def export(self):
         """Live tracks in list order (tracked list, then lost list): dict of arrays + n_tracked (the tracked list's length)."""
-        n, nt = C.c_int32(), C.c_int32()
-        L.call("aic_bytetrack_export", self._h, 0, None, None, None, None, None, None, None, None, None, C.byref(n), C.byref(nt))
-        m = n.value
-        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
-                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
-                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32))
-        L.call("aic_bytetrack_export", self._h, m, *(L.ptr(out[k]) for k in ("track_id", "state", "is_activated", "start_frame",
-                                                                           "end_frame", "cls", "score", "mean", "cov")),
-               C.byref(n), C.byref(nt))
-        out["n_tracked"] = nt.value
-        return out
+        return export_tracks("aic_bytetrack_export", self._h)
 
 
 class TrackerBank:
@@ -180,19 +194,16 @@ class TrackerBank:
         for s in range(self.streams):
             if status[s] and s not in self.failed:
                 self.failed[s] = f"stream {s} stopped with libaicam error {int(status[s])} (reset({s}) starts it afresh)"
-            rows = []
-            for _ in range(int(fps[s])):
-                m = min(int(n_out[f]), cap)
-                rows.append((out6[f, :m].copy(), oconf[f, :m].copy()))
-                f += 1
-            res.append(None if status[s] else rows)
+            k = int(fps[s])
+            res.append(None if status[s] else frame_rows(n_out, out6, oconf, cap, f, k))
+            f += k
         return res
 
     def update(self, per_stream_detections):
         """One tick: `streams` entries (boxes_xyxy, scores, class_ids), None = no frame from that camera this tick.  Returns
         `streams` lists of (x1, y1, x2, y2, track_id, class_name, conf) tuples ([] without a frame), None for a stopped stream."""
         got = self.update_arrays([[] if d is None else [d] for d in per_stream_detections])
-        return [None if g is None else (BYTETracker._tuples(*g[0]) if g else []) for g in got]
+        return [None if g is None else (output_tuples(*g[0]) if g else []) for g in got]
 
 
 class BYTETrackerBank(TrackerBank):
@@ -214,14 +225,4 @@ class BYTETrackerBank(TrackerBank):
 
     def export(self, stream):
         """BYTETracker.export() of one stream; raises for a stopped stream."""
-        n, nt = C.c_int32(), C.c_int32()
-        L.call("aic_bytetrack_bank_export", self._h, int(stream), 0, *([None] * 9), C.byref(n), C.byref(nt))
-        m = n.value
-        out = dict(track_id=np.zeros(m, np.int32), state=np.zeros(m, np.int32), is_activated=np.zeros(m, np.int32),
-                   start_frame=np.zeros(m, np.int32), end_frame=np.zeros(m, np.int32), cls=np.zeros(m, np.int32),
-                   score=np.zeros(m, np.float32), mean=np.zeros((m, 8), np.float32), cov=np.zeros((m, 8, 8), np.float32))
-        L.call("aic_bytetrack_bank_export", self._h, int(stream), m,
-               *(L.ptr(out[k]) for k in ("track_id", "state", "is_activated", "start_frame", "end_frame", "cls", "score", "mean", "cov")),
-               C.byref(n), C.byref(nt))
-        out["n_tracked"] = nt.value
-        return out
+        return export_tracks("aic_bytetrack_bank_export", self._h, int(stream))

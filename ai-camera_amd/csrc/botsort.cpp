@@ -44,17 +44,7 @@ BotSortTracker::BotSortTracker(Device& d, const BsParams& p, int first_id, int s
     HIP_CHECK(hipStreamSynchronize(dev->s_trk));
 }
 
-void BotSortTracker::launch(const BsParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                            const EpochOut& out, hipStream_t s) {
-    launch_botsort_epoch(d_tbl.p, stride, d_feat.p, feat_stride, n_streams, p, dets, warps, f0, k, stream_f0, stream_k, frame_stride, d_ext.p,
-                         out, s);
-}
-
-std::string BotSortTracker::err_text(int err) const {
-    if (err == 1) return "track capacity exhausted (raise max_tracks)";
-    if (err == 3) return "an assignment problem beyond the epoch kernel's capacity (tracks + detections > 512, or > 512 detections in a frame)";
-    return "the assignment problem has no finite solution";
-}
+void BotSortTracker::launch(const BsParams& p, const EpochCall& c, hipStream_t s) { launch_botsort_epoch(p, c, d_feat.p, feat_stride, warps, s); }
 
 // the raw features of every row of the call -> unit rows, once, before the epochs; the call's camera motion -> the launches
 void BotSortTracker::extra_staged(EpochDets& dets, const float* d_warps, float* d_feat_n, int rows, hipStream_t s) {
@@ -101,8 +91,7 @@ void BotSortTracker::counters(int stream, int64_t* n_fast, int64_t* n_lsap, int3
     if (cyc_all) *cyc_all = h.cyc_all;
 }
 
-int BotSortTracker::export_state(int stream, int cap_rows, int32_t* id, int32_t* state, int32_t* act, int32_t* start, int32_t* end, int32_t* cls,
-                                 float* score, float* mean, float* cov, int32_t* has_feat, float* smooth, int32_t* n_tracked) {
+int BotSortTracker::export_state(int stream, int cap_rows, const ByteExport& e, int32_t* has_feat, float* smooth, int32_t* n_tracked) {
     AIC_REQUIRE(stream >= 0 && stream < n_streams, AIC_ERR_INVALID, "stream outside the bank");
     // after an error the covariances hold the failing epoch's values and the rest the epoch before: there is no state to report
     AIC_REQUIRE(!stop_code[stream], AIC_ERR_INVALID, "BoT-SORT tracker stopped by an earlier error (no consistent state to export): " + stop_msg[stream]);
@@ -113,28 +102,14 @@ int BotSortTracker::export_state(int stream, int cap_rows, int32_t* id, int32_t*
         HIP_CHECK(hipMemcpy(hf.data(), d_feat.p + (size_t)stream * feat_stride, hf.size() * 4, hipMemcpyDeviceToHost));
     }
     const BsTable t = bs_table(h.data(), prm.cap, hf.data());
-    const int ntl = t.hdr->n_tracked, nll = t.hdr->n_lost, n = ntl + nll;
-    if (n_tracked) *n_tracked = ntl;
-    for (int i = 0; i < n && i < cap_rows; ++i) {
-        const int sl = i < ntl ? t.tl[i] : t.ll[i - ntl];
-        const BtTrack& r = t.trk[sl];
-        if (id) id[i] = r.id;
-        if (state) state[i] = r.state;
-        if (act) act[i] = r.act;
-        if (start) start[i] = r.start;
-        if (end) end[i] = r.end;
-        if (cls) cls[i] = r.cls;
-        if (score) score[i] = r.score;
-        if (mean) std::copy(t.mean + (size_t)sl * 8, t.mean + (size_t)sl * 8 + 8, mean + (size_t)i * 8);
-        if (cov) std::copy(t.cov + (size_t)sl * 64, t.cov + (size_t)sl * 64 + 64, cov + (size_t)i * 64);
+    return byte_export(t, cap_rows, e, n_tracked, [&](int i, int sl) {
         if (has_feat) has_feat[i] = t.hasf[sl];
         if (smooth) {                                             // a slot without a feature may hold a former track's: report zeros
             float* o = smooth + (size_t)i * prm.dim;
             if (t.hasf[sl]) std::copy(t.feat + (size_t)sl * prm.dim, t.feat + (size_t)(sl + 1) * prm.dim, o);
             else std::fill(o, o + prm.dim, 0.f);
         }
-    }
-    return n;
+    });
 }
 
 }  // namespace aic
@@ -180,7 +155,7 @@ int aic_botsort_export(aic_botsort* t, int cap, int32_t* track_id, int32_t* stat
                        int32_t* n_tracks, int32_t* n_tracked) {
     return guarded([&] {
         AIC_REQUIRE(t && cap >= 0, AIC_ERR_INVALID, "bad argument");
-        const int n = t->t.export_state(0, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, has_feat,
+        const int n = t->t.export_state(0, cap, {track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov}, has_feat,
                                         smooth_feat, n_tracked);
         if (n_tracks) *n_tracks = n;
     });
@@ -238,7 +213,7 @@ int aic_botsort_bank_export(aic_botsort_bank* b, int stream, int cap, int32_t* t
                             float* smooth_feat, int32_t* n_tracks, int32_t* n_tracked) {
     return guarded([&] {
         AIC_REQUIRE(b && cap >= 0, AIC_ERR_INVALID, "bad argument");
-        const int n = b->t.export_state(stream, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, has_feat,
+        const int n = b->t.export_state(stream, cap, {track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov}, has_feat,
                                         smooth_feat, n_tracked);
         if (n_tracks) *n_tracks = n;
     });

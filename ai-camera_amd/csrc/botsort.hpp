@@ -60,13 +60,10 @@ __host__ __device__ static inline BsTable bs_table(char* base, int cap, float* f
     return t;
 }
 
-// one launch, one block per stream: local frames [f0, f0 + k) of every stream, cut at stream_k[s]; local frame i of stream s is row
-// stream_f0[s] + i * frame_stride of dets, out and warps (stream_f0 == stream_k == NULL with one stream: row = local frame).
-// dets.feat_n (unit rows; NULL = no features) and dets.valid are read for the high band only, by detection row; warps = [rows, 6] camera
-// motion (r00 r01 t0 r10 r11 t1) or NULL; ext = [streams][TRK_DEV_NMAX^2] HBM scratch for extended matrices beyond the LDS
-void launch_botsort_epoch(char* bank, size_t table_stride, float* smooth, size_t smooth_stride, int streams, const BsParams& prm,
-                          const EpochDets& dets, const float* warps, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                          float* ext, const EpochOut& out, hipStream_t s);
+// one launch, one block per stream (EpochCall, trk_dev.hpp).  c.dets.feat_n (unit rows; NULL = no features) and c.dets.valid are read
+// for the high band only, by detection row; smooth = the streams' smoothed features, smooth_stride floats apart; warps = [rows, 6] camera
+// motion (r00 r01 t0 r10 r11 t1), rows as c.dets' frames, or NULL
+void launch_botsort_epoch(const BsParams& prm, const EpochCall& c, float* smooth, size_t smooth_stride, const float* warps, hipStream_t s);
 // out[r] = in[r] / |in[r]| in the order of kf8wh_math.hpp (one wavefront per row)
 void launch_botsort_normalize(const float* in, float* out, int rows, int dim, hipStream_t s);
 

@@ -3,8 +3,7 @@
 // the pipeline (aic_pipeline_create_botsort, aic_pipeline_create_botsort_bank).
 #pragma once
 #include "botsort.hpp"
-#include "common.hpp"
-#include "epoch_bank.hpp"
+#include "bytetrack_host.hpp"
 
 namespace aic {
 
@@ -17,9 +16,8 @@ struct BotSortTracker : EpochBank<BsHdr, BsParams> {
 
     BotSortTracker(Device& d, const BsParams& p, int first_id, int streams = 1);
     const char* name() const override { return "BoT-SORT"; }
-    void launch(const BsParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                const EpochOut& out, hipStream_t s) override;
-    std::string err_text(int err) const override;
+    void launch(const BsParams& p, const EpochCall& c, hipStream_t s) override;
+    std::string err_text(int err) const override { return byte_err_text(err); }
     void extra_staged(EpochDets& dets, const float* d_warps, float* d_feat_n, int rows, hipStream_t s) override;
     void set_streams(int) override { AIC_REQUIRE(false, AIC_ERR_INVALID, "the streams of a BoT-SORT bank are fixed at creation"); }
     void reset_stream(int s) override;   // also the stream's smoothed features
@@ -31,8 +29,7 @@ struct BotSortTracker : EpochBank<BsHdr, BsParams> {
     void update_batch(int k, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, const float* feat,
                       const int32_t* valid, const float* warps6, int cap_rows, int32_t* n_out, int32_t* out6, float* out_conf);
     void counters(int stream, int64_t* n_fast, int64_t* n_lsap, int32_t* max_side, int64_t* n_app, int64_t* cyc_cost, int64_t* cyc_all);
-    int export_state(int stream, int cap_rows, int32_t* id, int32_t* state, int32_t* act, int32_t* start, int32_t* end, int32_t* cls,
-                     float* score, float* mean, float* cov, int32_t* has_feat, float* smooth, int32_t* n_tracked);
+    int export_state(int stream, int cap_rows, const ByteExport& e, int32_t* has_feat, float* smooth, int32_t* n_tracked);
 };
 
 }  // namespace aic

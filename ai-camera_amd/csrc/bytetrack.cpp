@@ -32,12 +32,9 @@ BtParams bytetrack_params(const aic_bytetrack_params& p, int* first_id) {
 ByteTracker::ByteTracker(Device& d, const BtParams& p, int first_id, int streams)
     : EpochBank(d, p, first_id, streams, bt_table_bytes(p.cap), (size_t)TRK_DEV_NMAX * TRK_DEV_NMAX) {}
 
-void ByteTracker::launch(const BtParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                         const EpochOut& out, hipStream_t s) {
-    launch_bytetrack_epoch(d_tbl.p, stride, n_streams, p, dets, f0, k, stream_f0, stream_k, frame_stride, d_ext.p, out, s);
-}
+void ByteTracker::launch(const BtParams& p, const EpochCall& c, hipStream_t s) { launch_bytetrack_epoch(p, c, s); }
 
-std::string ByteTracker::err_text(int err) const {
+std::string byte_err_text(int err) {
     if (err == 1) return "track capacity exhausted (raise max_tracks)";
     if (err == 3) return "an assignment problem beyond the epoch kernel's capacity (tracks + detections > 512, or > 512 detections in a frame)";
     return "the assignment problem has no finite solution";
@@ -59,29 +56,12 @@ void ByteTracker::counters(int stream, int64_t* n_fast, int64_t* n_lsap, int32_t
     if (max_side) *max_side = h.max_side;
 }
 
-int ByteTracker::export_state(int stream, int cap_rows, int32_t* id, int32_t* state, int32_t* act, int32_t* start, int32_t* end, int32_t* cls,
-                              float* score, float* mean, float* cov, int32_t* n_tracked) {
+int ByteTracker::export_state(int stream, int cap_rows, const ByteExport& e, int32_t* n_tracked) {
     AIC_REQUIRE(stream >= 0 && stream < n_streams, AIC_ERR_INVALID, "stream outside the bank");
     // after an error the covariances hold the failing epoch's values and the rest the epoch before: there is no state to report
     AIC_REQUIRE(!stop_code[stream], AIC_ERR_INVALID, "ByteTrack tracker stopped by an earlier error (no consistent state to export): " + stop_msg[stream]);
     std::vector<char> h = fetch_table(stream, tbl_bytes);
-    const BtTable t = bt_table(h.data(), prm.cap);
-    const int ntl = t.hdr->n_tracked, nll = t.hdr->n_lost, n = ntl + nll;
-    if (n_tracked) *n_tracked = ntl;
-    for (int i = 0; i < n && i < cap_rows; ++i) {
-        const int sl = i < ntl ? t.tl[i] : t.ll[i - ntl];
-        const BtTrack& r = t.trk[sl];
-        if (id) id[i] = r.id;
-        if (state) state[i] = r.state;
-        if (act) act[i] = r.act;
-        if (start) start[i] = r.start;
-        if (end) end[i] = r.end;
-        if (cls) cls[i] = r.cls;
-        if (score) score[i] = r.score;
-        if (mean) std::copy(t.mean + (size_t)sl * 8, t.mean + (size_t)sl * 8 + 8, mean + (size_t)i * 8);
-        if (cov) std::copy(t.cov + (size_t)sl * 64, t.cov + (size_t)sl * 64 + 64, cov + (size_t)i * 64);
-    }
-    return n;
+    return byte_export(bt_table(h.data(), prm.cap), cap_rows, e, n_tracked, [](int, int) {});
 }
 
 }  // namespace aic
@@ -122,7 +102,7 @@ int aic_bytetrack_export(aic_bytetrack* t, int cap, int32_t* track_id, int32_t* 
                          int32_t* end_frame, int32_t* cls, float* score, float* mean, float* cov, int32_t* n_tracks, int32_t* n_tracked) {
     return guarded([&] {
         AIC_REQUIRE(t && cap >= 0, AIC_ERR_INVALID, "bad argument");
-        const int n = t->t.export_state(0, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, n_tracked);
+        const int n = t->t.export_state(0, cap, {track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov}, n_tracked);
         if (n_tracks) *n_tracks = n;
     });
 }
@@ -178,7 +158,7 @@ int aic_bytetrack_bank_export(aic_bytetrack_bank* b, int stream, int cap, int32_
                               int32_t* n_tracks, int32_t* n_tracked) {
     return guarded([&] {
         AIC_REQUIRE(b && cap >= 0, AIC_ERR_INVALID, "bad argument");
-        const int n = b->t.export_state(stream, cap, track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov, n_tracked);
+        const int n = b->t.export_state(stream, cap, {track_id, state, is_activated, start_frame, end_frame, cls, score, mean, cov}, n_tracked);
         if (n_tracks) *n_tracks = n;
     });
 }

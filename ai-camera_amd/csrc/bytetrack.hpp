@@ -62,10 +62,7 @@ __host__ __device__ static inline BtTable bt_table(char* base, int cap) {
     return t;
 }
 
-// one launch, one block per stream of the bank: local frames [f0, f0 + k) of every stream, cut at stream_k[s]; local frame i of stream s
-// is row stream_f0[s] + i * frame_stride of `dets` / `out` (stream_f0 = stream_k = NULL, streams = 1: row = local frame).
-// ext = [streams][TRK_DEV_NMAX * TRK_DEV_NMAX] HBM scratch for extended matrices that do not fit the LDS
-void launch_bytetrack_epoch(char* bank, size_t table_stride, int streams, const BtParams& prm, const EpochDets& dets, int f0, int k,
-                            const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s);
+// one launch, one block per stream of the bank (EpochCall, trk_dev.hpp); c.ext holds the extended matrices that do not fit the LDS
+void launch_bytetrack_epoch(const BtParams& prm, const EpochCall& c, hipStream_t s);
 
 }  // namespace aic

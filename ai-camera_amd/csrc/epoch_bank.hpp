@@ -1,6 +1,6 @@
 // epoch_bank.hpp -- a bank of epoch-tracker streams on one device: what ByteTracker, OcSortTracker and BotSortTracker share.  One allocation
-// holds the streams' tables `stride` bytes apart, every epoch launch runs one block per stream (kernels_bytetrack.hip / kernels_ocsort.hip /
-// kernels_botsort.hip), and a stream that meets a capacity error stops alone.  The single trackers of the C ABI and the pipeline's default
+// holds the streams' tables `stride` bytes apart, every epoch launch is one EpochCall (trk_dev.hpp) and runs one block per stream
+// (byte_epoch.hpp through kernels_bytetrack.hip / kernels_botsort.hip; kernels_ocsort.hip), and a stream that meets a capacity error stops alone.  The single trackers of the C ABI and the pipeline's default
 // are banks of one.  BoT-SORT stages features, validity and camera motion on top (BankExtra); the detector-only trackers pass none and
 // their staging layout and launches are what they were without it.
 #pragma once
@@ -48,8 +48,7 @@ struct EpochBank : EpochTracker {
         resize(streams);
     }
 
-    virtual void launch(const Prm& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                        const EpochOut& out, hipStream_t s) = 0;
+    virtual void launch(const Prm& p, const EpochCall& c, hipStream_t s) = 0;
     virtual std::string err_text(int err) const = 0;
     // update() with a BankExtra: the extras are on their way to the device (stream s), before the epochs.  dets.valid / dets.feat are set
     // where given; d_warps is NULL without camera motion, d_feat_n [rows, dim] is free device memory for the normalised features.
@@ -109,7 +108,7 @@ struct EpochBank : EpochTracker {
             const int k = std::min(kmax, kmax_s - f);
             {
                 Prof pr(*dev, PROF_TRK, s, 0, 0);
-                launch(p, dets, f, k, stream_f0, stream_k, frame_stride, out, s);
+                launch(p, EpochCall{d_tbl.p, stride, n_streams, frame_stride, dets, f, k, stream_f0, stream_k, d_ext.p, out}, s);
             }
             f += k;
         }

@@ -23,16 +23,8 @@
 namespace aic {
 
 struct OcArgs {
-    char* bank;                     // stream s: oc_table(bank + s * table_stride, cap)
-    size_t table_stride;
+    EpochCall c;                    // stream s: oc_table(c.bank + s * c.table_stride, cap); c.ext: cost matrices beyond the LDS arena
     OcParams prm;
-    EpochDets dets;
-    int f0, k;                      // local frames [f0, f0 + k) of every stream, cut at stream_k[s]
-    const int* stream_f0;           // [streams] local frame i of stream s = row stream_f0[s] + i * frame_stride of dets / out;
-    const int* stream_k;            // [streams] frames of stream s in the call.  Both NULL: one stream, row = local frame
-    int frame_stride;
-    float* ext;                     // [streams][TRK_DEV_NMAX * TRK_DEV_TMAX] cost matrices that do not fit the LDS arena
-    EpochOut out;
     int lds_bytes;
 };
 
@@ -82,6 +74,8 @@ __device__ __forceinline__ OcLds oc_carve(char* base, int total_bytes) {
     L.arena_floats = (int)((total_bytes - (p - base)) / 4);
     return L;
 }
+constexpr size_t OC_FIXED_LDS_BYTES = (3 * 8 + 6 * 4) * (size_t)TRK_DEV_NMAX + (size_t)TRK_DEV_NMAX * (23 * 4 + 4 + 16 + 8 + 32 + 16 + 16 + 16 + 4) + ((4 * (NW + W_N) + 15) & ~15);
+static_assert((159 * 1024 - OC_FIXED_LDS_BYTES) / 4 == 8428, "the LDS arena of the OC-SORT kernel");
 
 // One association problem, block-wide: rows = detections `rows[0..nr)`, columns = list positions `cols[0..nc)`.
 //   OC_STAGE1: cost -(IoU(det, prediction) + OCM term); upstream's read-off when every row and column has at most one IoU above the threshold
@@ -170,11 +164,12 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
     int* err = L.wcnt + NW + W_ERR;
     // ---- this block's stream: frame range, table, HBM scratch
     const int sid = blockIdx.x;
-    const int row0 = a.stream_f0 ? a.stream_f0[sid] : 0;
-    const int kend = a.stream_k ? min(a.f0 + a.k, a.stream_k[sid]) : a.f0 + a.k;
-    if (a.f0 >= kend) return;                                     // nothing for this stream in this epoch: its table is not touched
-    const OcTable tbl = oc_table(a.bank + (size_t)sid * a.table_stride, cap);
-    float* hbm = a.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_TMAX;
+    const EpochCall& c = a.c;
+    const int row0 = c.stream_f0 ? c.stream_f0[sid] : 0;
+    const int kend = c.stream_k ? min(c.f0 + c.k, c.stream_k[sid]) : c.f0 + c.k;
+    if (c.f0 >= kend) return;                                     // nothing for this stream in this epoch: its table is not touched
+    const OcTable tbl = oc_table(c.bank + (size_t)sid * c.table_stride, cap);
+    float* hbm = c.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_TMAX;
     if (tbl.hdr->err) return;                                   // an earlier epoch of the call failed: the table is not a frame boundary
 
     // ---- load the table
@@ -194,20 +189,20 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
     if (tid == 0) L.wcnt[NW + W_SIDE] = tbl.hdr->max_side, L.wcnt[NW + W_GAP] = tbl.hdr->max_gap;
     __syncthreads();
     float* cov = tbl.cov;
-    int fi = a.f0;
+    int fi = c.f0;
     for (; fi < kend; ++fi) {
-        const int f = row0 + fi * a.frame_stride;
+        const int f = row0 + fi * c.frame_stride;
         ++frame;
-        const int n = a.dets.frame_n[f], d0 = a.dets.frame_d0[f];
+        const int n = c.dets.frame_n[f], d0 = c.dets.frame_d0[f];
         if (n > TRK_DEV_NMAX) { if (tid == 0) *err = 3; break; }
         float s = 0.f;
         if (tid < n) {
-            const float* b = a.dets.tlwh + (size_t)(d0 + tid) * 4;
+            const float* b = c.dets.tlwh + (size_t)(d0 + tid) * 4;
             const float x = b[0], y = b[1], w = b[2], h = b[3];
             L.dbox[tid * 4 + 0] = x, L.dbox[tid * 4 + 1] = y, L.dbox[tid * 4 + 2] = x + w, L.dbox[tid * 4 + 3] = y + h;
-            s = a.dets.conf[d0 + tid];
+            s = c.dets.conf[d0 + tid];
             L.dconf[tid] = s;
-            L.dcls[tid] = a.dets.cls[d0 + tid];
+            L.dcls[tid] = c.dets.cls[d0 + tid];
         }
         L.dfree[tid] = 1;
         const int nh = block_compact(tid < n && s > P.det_thresh, tid, L.hi, L.wcnt);
@@ -392,16 +387,16 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
         // ---- outputs (the list reversed), then removal at time_since_update > max_age
         const int osl = tid < nt ? L.tl[nt - 1 - tid] : 0;
         const int no = block_compact(tid < nt && L.tsu[osl] < 1 && (L.streak[osl] >= P.min_hits || frame <= P.min_hits), osl, L.outl, L.wcnt);
-        if (tid == 0) a.out.n_tracks[f] = no;
-        if (tid < no && tid < a.out.max_rows) {
+        if (tid == 0) c.out.n_tracks[f] = no;
+        if (tid < no && tid < c.out.max_rows) {
             const int sl = L.outl[tid];
             float b[4];
             if (L.hobs[sl]) { b[0] = L.last[sl * 4], b[1] = L.last[sl * 4 + 1], b[2] = L.last[sl * 4 + 2], b[3] = L.last[sl * 4 + 3]; }
             else x_to_bbox(L.mean[sl * 8 + 0], L.mean[sl * 8 + 1], L.mean[sl * 8 + 2], L.mean[sl * 8 + 3], b);
-            int* r = a.out.rows + ((size_t)f * a.out.max_rows + tid) * 6;
+            int* r = c.out.rows + ((size_t)f * c.out.max_rows + tid) * 6;
             r[0] = (int)rintf(b[0]), r[1] = (int)rintf(b[1]), r[2] = (int)rintf(b[2]), r[3] = (int)rintf(b[3]);   // round half to even
             r[4] = L.id[sl], r[5] = L.cls[sl];
-            a.out.conf[(size_t)f * a.out.max_rows + tid] = L.score[sl];
+            c.out.conf[(size_t)f * c.out.max_rows + tid] = L.score[sl];
         }
         const int rsl = tid < nt ? L.tl[tid] : 0;
         const int nkeep = block_compact(tid < nt && !(L.tsu[rsl] > P.max_age), rsl, L.tl2, L.wcnt);
@@ -436,11 +431,10 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void ocsort_epoch_kernel(OcArgs a) {
 
 static int oc_lds_bytes() { return 159 * 1024; }
 
-void launch_ocsort_epoch(char* bank, size_t table_stride, int streams, const OcParams& prm, const EpochDets& dets, int f0, int k,
-                         const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s) {
+void launch_ocsort_epoch(const OcParams& prm, const EpochCall& c, hipStream_t s) {
     set_lds_limit(ocsort_epoch_kernel, oc_lds_bytes());
-    OcArgs a{bank, table_stride, prm, dets, f0, k, stream_f0, stream_k, frame_stride, ext, out, oc_lds_bytes()};
-    hipLaunchKernelGGL(ocsort_epoch_kernel, dim3(streams), dim3(TRK_DEV_TMAX), oc_lds_bytes(), s, a);
+    OcArgs a{c, prm, oc_lds_bytes()};
+    hipLaunchKernelGGL(ocsort_epoch_kernel, dim3(c.streams), dim3(TRK_DEV_TMAX), oc_lds_bytes(), s, a);
     KCHECK();
 }
 

@@ -31,10 +31,7 @@ OcParams ocsort_params(const aic_ocsort_params& p, int* first_id) {
 OcSortTracker::OcSortTracker(Device& d, const OcParams& p, int first_id, int streams)
     : EpochBank(d, p, first_id, streams, oc_table_bytes(p.cap), (size_t)TRK_DEV_NMAX * TRK_DEV_TMAX) {}
 
-void OcSortTracker::launch(const OcParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                           const EpochOut& out, hipStream_t s) {
-    launch_ocsort_epoch(d_tbl.p, stride, n_streams, p, dets, f0, k, stream_f0, stream_k, frame_stride, d_ext.p, out, s);
-}
+void OcSortTracker::launch(const OcParams& p, const EpochCall& c, hipStream_t s) { launch_ocsort_epoch(p, c, s); }
 
 std::string OcSortTracker::err_text(int err) const {
     if (err == 1) return "track capacity exhausted (raise max_tracks)";

@@ -70,9 +70,7 @@ __host__ __device__ static inline OcTable oc_table(char* base, int cap) {
     return t;
 }
 
-// one launch, one block per stream of the bank: frame ranges and rows as launch_bytetrack_epoch (bytetrack.hpp);
-// ext = [streams][TRK_DEV_NMAX * TRK_DEV_TMAX] HBM scratch for cost matrices that do not fit the LDS
-void launch_ocsort_epoch(char* bank, size_t table_stride, int streams, const OcParams& prm, const EpochDets& dets, int f0, int k,
-                         const int* stream_f0, const int* stream_k, int frame_stride, float* ext, const EpochOut& out, hipStream_t s);
+// one launch, one block per stream of the bank (EpochCall, trk_dev.hpp)
+void launch_ocsort_epoch(const OcParams& prm, const EpochCall& c, hipStream_t s);
 
 }  // namespace aic

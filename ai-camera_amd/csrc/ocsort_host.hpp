@@ -17,8 +17,7 @@ struct OcExport {                   // aic_ocsort_export's arrays, any may be NU
 struct OcSortTracker : EpochBank<OcHdr, OcParams> {
     OcSortTracker(Device& d, const OcParams& p, int first_id, int streams = 1);
     const char* name() const override { return "OC-SORT"; }
-    void launch(const OcParams& p, const EpochDets& dets, int f0, int k, const int* stream_f0, const int* stream_k, int frame_stride,
-                const EpochOut& out, hipStream_t s) override;
+    void launch(const OcParams& p, const EpochCall& c, hipStream_t s) override;
     std::string err_text(int err) const override;
     // the single tracker's call: k consecutive frames of stream 0 of a bank of one
     void update_batch(int k, const int32_t* counts, const float* xyxy, const float* conf, const int32_t* cls, int cap_rows,

@@ -67,6 +67,20 @@ struct EpochOut {                   // per frame of the launch group, device mem
     int32_t dbg_stride;             // > 0: dbg_match holds EVERY frame of the launch group, frame f at dbg_match + f * dbg_stride (aic_tracker_update_batch)
 };
 
+// One launch of an epoch tracker's bank (epoch_bank.hpp), one block per stream: what the ByteTrack, OC-SORT and BoT-SORT kernels are told.
+struct EpochCall {
+    char* bank;                     // stream s: the tracker's table at bank + s * table_stride
+    size_t table_stride;
+    int32_t streams;                // blocks of the launch
+    int32_t frame_stride;           // beside streams: the struct has no padding (see DESIGN.md section 37 on the kernels' stack frames)
+    EpochDets dets;
+    int32_t f0, k;                  // local frames [f0, f0 + k) of every stream, cut at stream_k[s]
+    const int32_t* stream_f0;       // [streams] local frame i of stream s = row stream_f0[s] + i * frame_stride of dets / out;
+    const int32_t* stream_k;        // [streams] frames of stream s in the call.  Both NULL: one stream, row = local frame
+    float* ext;                     // [streams][TRK_DEV_NMAX * TRK_DEV_TMAX] cost matrices that do not fit the LDS arena
+    EpochOut out;
+};
+
 struct EpochScratch {
     float* sm;                      // [cap, TRK_KMAX + 1, dn_pad]
     float* gram;                    // [dn_pad, dn_pad]

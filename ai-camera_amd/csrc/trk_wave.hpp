@@ -1,7 +1,9 @@
 // trk_wave.hpp -- block / wavefront building blocks of the one-block tracker epoch kernels (kernels_trk_dev.hip: DeepSORT,
-// kernels_bytetrack.hip: ByteTrack): ordered block compaction, DPP wave reductions and the three restatements of SciPy's
-// rectangular LSAP.  The LSAPs are templates over the caller's LDS carve: they read and write only its fields
-// u, v, dist (double[side]) and pred, rowof, colof, todo, pos, asg (int[side]).
+// byte_epoch.hpp: ByteTrack and BoT-SORT, kernels_ocsort.hip: OC-SORT): ordered block compaction, DPP wave reductions and the three
+// restatements of SciPy's rectangular LSAP.  The LSAPs are templates over the caller's LDS carve: they read and write only its fields
+// u, v, dist (double[side]) and pred, rowof, colof, todo, pos, asg (int[side]): LsapLds below, which the carve of byte_epoch.hpp starts
+// with.  The stream prologue of an EpochCall (trk_dev.hpp) and the writer of an output row are here as well; OC-SORT keeps copies of its
+// own for now (with the shared ones its kernel compiled differently and two cells of its benchmark slowed).
 #pragma once
 #include "kernels.hpp"
 #include "trk_dev.hpp"
@@ -34,6 +36,50 @@ __device__ __forceinline__ int block_compact(bool flag, int value, int* list, in
     if (flag) list[off + before] = value;
     __syncthreads();
     return tot;
+}
+
+// ---- the banked epoch kernels: LDS carve, stream prologue, output row ------------------------------------------------------------
+struct LdsTake {                        // the dynamic LDS handed out front to back, 16-byte steps
+    char* p;
+    __device__ __forceinline__ char* operator()(size_t bytes) { char* q = p; p += (bytes + 15) & ~(size_t)15; return q; }
+};
+
+struct LsapLds {                        // what the LSAPs below read and write, side <= TRK_DEV_NMAX
+    double *u, *v, *dist;
+    int *pred, *rowof, *colof, *todo, *pos, *asg;
+};
+constexpr size_t LSAP_LDS_BYTES = (3 * 8 + 6 * 4) * (size_t)TRK_DEV_NMAX;
+
+__device__ __forceinline__ void carve_lsap(LsapLds& L, LdsTake& take) {
+    const size_t M = TRK_DEV_NMAX;
+    static_assert(TRK_DEV_NMAX == TRK_DEV_TMAX, "one side for tracks, detections and LSAP");
+    // one statement per field: a table of pointers-to-fields walked in a loop lands in scratch
+    L.u = (double*)take(8 * M); L.v = (double*)take(8 * M); L.dist = (double*)take(8 * M);
+    L.pred = (int*)take(4 * M); L.rowof = (int*)take(4 * M); L.colof = (int*)take(4 * M);
+    L.todo = (int*)take(4 * M); L.pos = (int*)take(4 * M); L.asg = (int*)take(4 * M);
+}
+
+struct EpochStream {                    // this block's stream of an EpochCall
+    int row0, kend;                     // local frame i = row row0 + i * frame_stride of dets / out; local frames [f0, kend)
+    float* ext;                         // the stream's slice of the HBM scratch
+};
+
+// False: the block has nothing to do and returns.  table_err: err of the stream's table header.
+__device__ __forceinline__ bool epoch_stream(const EpochCall& c, const int32_t* table_err, EpochStream& st) {
+    const int sid = blockIdx.x;
+    st.row0 = c.stream_f0 ? c.stream_f0[sid] : 0;
+    st.kend = c.stream_k ? min(c.f0 + c.k, c.stream_k[sid]) : c.f0 + c.k;
+    if (c.f0 >= st.kend) return false;                           // nothing for this stream in this epoch: its table is not touched
+    st.ext = c.ext + (size_t)sid * TRK_DEV_NMAX * TRK_DEV_TMAX;
+    return *table_err == 0;                                      // an earlier epoch of the call failed: the table is not a frame boundary
+}
+
+// output row i (< max_rows) of frame row f: the corners, id, class; and the score
+__device__ __forceinline__ void write_row(const EpochOut& o, int f, int i, float x1, float y1, float x2, float y2, int id, int cls, float score) {
+    int* r = o.rows + ((size_t)f * o.max_rows + i) * 6;
+    r[0] = (int)rintf(x1), r[1] = (int)rintf(y1), r[2] = (int)rintf(x2), r[3] = (int)rintf(y2);   // round half to even
+    r[4] = id, r[5] = cls;
+    o.conf[(size_t)f * o.max_rows + i] = score;
 }
 
 __device__ __forceinline__ int block_min_int(int v, int* wcnt) {     // two barriers

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from . import config
-from .bytetrack import TrackerBank
+from .bytetrack import TrackerBank, frame_rows, output_tuples
 
 
 def ocsort_params(det_thresh=0.6, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3, inertia=0.2, use_byte=False,
@@ -75,15 +75,9 @@ class OCSort:
         L.call("aic_ocsort_update_batch", self._h, k, L.ptr(counts), L.ptr(xyxy), L.ptr(conf), L.ptr(cls), cap, L.ptr(n_out),
                L.ptr(out6), L.ptr(oconf))
         self.frame_count += k
-        res = []
-        for f in range(k):
-            m = min(int(n_out[f]), cap)
-            res.append((out6[f, :m].copy(), oconf[f, :m].copy()))
-        return res
+        return frame_rows(n_out, out6, oconf, cap, 0, k)
 
-    @staticmethod
-    def _tuples(rows, conf):
-        return [(r[0], r[1], r[2], r[3], r[4], config.class_name(r[5]), cf) for r, cf in zip(rows.tolist(), conf.tolist())]
+    _tuples = staticmethod(output_tuples)
 
     def update(self, boxes_xyxy, scores, class_ids):
         """One frame (OCSort.update). Empty inputs (np.array([])) are accepted."""
