@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "render", "gmc", "frames", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "bestshot", "render", "gmc", "frames", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
@@ -40,6 +40,8 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.archive").IdentityArchive
     if name == "ZoneCounter":
         return _importlib.import_module(f"{__name__}.zones").ZoneCounter
+    if name == "BestShots":
+        return _importlib.import_module(f"{__name__}.bestshot").BestShots
     if name == "Renderer":
         return _importlib.import_module(f"{__name__}.render").Renderer
     if name == "CameraMotionBank":

@@ -1,0 +1,183 @@
+"""Best shots: the best crop of every track, kept on the device, per camera (aic_bestshot_*, csrc/bestshot.hpp,
+csrc/kernels_bestshot.hip): the picture an operator is shown for "this is person 4711 again".  One
+tracker-agnostic stage over the frames and the rows every tracker here delivers (x1 y1 x2 y2 id cls, int32), for a bank of 1..256
+cameras per call.  Integer arithmetic only; tests/bestshot_oracle.py is the specification."""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib as L
+from . import config
+
+LIVE, EXPIRED, FLUSHED = 0, 1, 2
+REASONS = {LIVE: "live", EXPIRED: "expired", FLUSHED: "flushed"}
+MAX_ROWS = MAX_TRACKS = 512
+EVENT_FIELDS = ("reason", "stream", "id", "cls", "first_frame", "last_seen", "sightings", "has_shot", "best_frame", "score", "x0", "y0",
+                "x1", "y1", "slot")
+
+BestShotResult = namedtuple("BestShotResult", "n_final events thumbs pending status failed")
+BestShotResult.__doc__ = """n_final [S]; events [S, cap, 16] (EVENT_FIELDS, then 0), thumbs [S, cap, TH, TW, 3] BGR -- the n_final[s] first
+of stream s are filled, the rest zero; pending [S] = ENDED tracks still waiting for room (drain() fetches them); status [S] = 0 or the
+code a stream stopped with; failed = {stream: message}."""
+
+
+def finals(result):
+    """[(event dict, thumbnail [TH, TW, 3] BGR)] of a BestShotResult, stream by stream in emission order."""
+    out = []
+    for s, n in enumerate(result.n_final):
+        for k in range(int(n)):
+            out.append((dict(zip(EVENT_FIELDS, (int(v) for v in result.events[s, k]))), result.thumbs[s, k]))
+    return out
+
+
+def write_ppm(path, thumb_bgr):
+    """A thumbnail as a binary P6 file (RGB)."""
+    t = np.ascontiguousarray(thumb_bgr[:, :, ::-1])
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (t.shape[1], t.shape[0]))
+        f.write(t.tobytes())
+
+
+class BestShots:
+    """BestShots(streams, frame_hw, thumb=(64, 128), max_tracks=128, forget_after=70, region="box", head_q8=64, pad=0, min_w=8,
+    min_h=16, device=0).  thumb = (width, height), multiples of 8 in 16..128 x 16..256; region "box" or "head" (the upper head_q8 / 256
+    of the box, as the renderer's head mode).  The device is first touched by update / drain / flush; the resident thumbnails take
+    streams * max_tracks * TH * TW * 3 bytes there."""
+
+    def __init__(self, streams, frame_hw, thumb=(64, 128), max_tracks=128, forget_after=70, region="box", head_q8=64, pad=0, min_w=8,
+                 min_h=16, device=0):
+        if region not in ("box", "head"):
+            raise ValueError("region must be 'box' or 'head'")
+        self.streams, self.frame_h, self.frame_w = int(streams), int(frame_hw[0]), int(frame_hw[1])
+        self.thumb_w, self.thumb_h, self.max_tracks = int(thumb[0]), int(thumb[1]), int(max_tracks)
+        self.failed = {}                                         # stream -> message
+        cfg = L.BestShotConfig(self.streams, self.frame_h, self.frame_w, self.thumb_w, self.thumb_h, self.max_tracks, int(forget_after),
+                               0 if region == "box" else 1, int(head_q8), int(pad), int(min_w), int(min_h))
+        self._h = C.c_void_p()
+        L.call("aic_bestshot_create", config.resolve_device(device), C.byref(cfg), C.byref(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            L.load().aic_bestshot_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def option(self, key, value):
+        """"ticks_per_launch": 0 = as many ticks per launch as the budget allows (default), k = at most k; "launch_budget_mb"; "stats" 0 / 1
+        (counters()).  Same results."""
+        L.call("aic_bestshot_option", self._h, str(key).encode(), int(value))
+
+    def counters(self):
+        """After option("stats", 1): dict(rows, candidates, stored) since creation -- rows handed in, candidates scored, candidate
+        thumbnails the could-still-win filter let through."""
+        v = [C.c_int64() for _ in range(3)]
+        L.call("aic_bestshot_counters", self._h, *(C.byref(x) for x in v))
+        return dict(rows=v[0].value, candidates=v[1].value, stored=v[2].value)
+
+    def reset(self, stream):
+        """The stream forgets everything, pending finals included; a stop is cleared: a camera reconnecting."""
+        L.call("aic_bestshot_reset", self._h, int(stream))
+        self.failed.pop(int(stream), None)
+
+    def _outputs(self, cap):
+        S = self.streams
+        return (np.zeros(S, np.int32), np.zeros((S, cap, 16), np.int32), np.zeros((S, cap, self.thumb_h, self.thumb_w, 3), np.uint8),
+                np.zeros(S, np.int32), np.zeros(S, np.int32))
+
+    def _result(self, out):
+        for s in np.nonzero(out[4])[0]:
+            self.failed.setdefault(int(s), f"stream {s} stopped with libaicam error {int(out[4][s])} (reset({s}) starts it afresh)")
+        return BestShotResult(*out, dict(self.failed))
+
+    @staticmethod
+    def _memory(a, what, dtype):
+        """(pointer, AIC_HOST / AIC_DEVICE, keep-alive) of a NumPy array or a contiguous torch tensor."""
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return L.ptr(a), L.HOST, a
+        if str(a.dtype) != "torch." + np.dtype(dtype).name or not a.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {np.dtype(dtype).name} tensor")
+        if a.is_cuda:
+            import torch
+            torch.cuda.current_stream(a.device).synchronize()  # the library reads it on its own stream
+        return C.c_void_p(a.data_ptr()), L.DEVICE if a.is_cuda else L.HOST, a
+
+    def update(self, frames, rows, counts=None, cap=16):
+        """frames: uint8 [ticks, streams, H, W, 3] BGR, tick-major, a NumPy array or a torch tensor (host or device).  rows: per tick,
+        per stream an [n, 6] int32 array (x1 y1 x2 y2 id cls) -- or ONE array / torch tensor [rows, 6] holding them in that order, with
+        counts [ticks * streams] (an array, or a tensor in the same memory as the rows).  ticks = 0 only drains.  Returns a
+        BestShotResult; a stream that stopped is noted in .failed and delivers nothing until reset()."""
+        cap = int(cap)
+        shape = tuple(frames.shape)
+        if len(shape) != 5 or shape[1:] != (self.streams, self.frame_h, self.frame_w, 3):
+            raise ValueError(f"frames of shape {shape}, not [ticks, {self.streams}, {self.frame_h}, {self.frame_w}, 3]")
+        ticks = shape[0]
+        f_ptr, f_mem, f_keep = self._memory(frames, "frames", np.uint8)
+        if counts is None:
+            if len(rows) != ticks or any(len(r) != self.streams for r in rows):
+                raise ValueError(f"rows must be [ticks = {ticks}][streams = {self.streams}] arrays")
+            flat = [np.asarray(r, dtype=np.int32).reshape(-1, 6) for tick in rows for r in tick]
+            counts = np.array([len(r) for r in flat], np.int32)
+            rows = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 6), np.int32))
+        r_ptr, r_mem, r_keep = self._memory(rows, "rows", np.int32)
+        if getattr(counts, "is_cuda", False):                    # device counts: the library fetches them for its checks
+            if r_mem != L.DEVICE:
+                raise ValueError("counts on the device need rows on the device")
+            c_ptr, _, c_keep = self._memory(counts, "counts", np.int32)
+            n_counts = counts.numel()
+        else:
+            c_keep = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+            n_counts, total = len(c_keep), int(c_keep.sum())
+            n_rows = r_keep.size // 6 if isinstance(r_keep, np.ndarray) else r_keep.numel() // 6
+            if n_rows < total:
+                raise ValueError(f"{n_rows} rows, counts sum to {total}")
+            if r_mem == L.DEVICE:                                # counts and rows travel together
+                import torch
+                c_keep = torch.from_numpy(c_keep).to(rows.device)
+                c_ptr = C.c_void_p(c_keep.data_ptr())
+            else:
+                c_ptr = L.ptr(c_keep)
+        if n_counts != ticks * self.streams:
+            raise ValueError("counts must name every frame of the call")
+        out = self._outputs(cap)
+        L.call("aic_bestshot_update", self._h, f_ptr if ticks else None, f_mem, ticks, c_ptr if ticks else None, r_ptr, r_mem, cap,
+               *(L.ptr(x) for x in out))
+        return self._result(out)
+
+    def update_tuples(self, frames, tracks, cap=16):
+        """As update(), from the 7-tuples (x1, y1, x2, y2, track_id, class_name, conf) the trackers return: tracks[tick][stream] is a list
+        of tuples."""
+        ids = {n: i for i, n in enumerate(config.CLASSES)}
+        return self.update(frames, [[np.array([[t[0], t[1], t[2], t[3], t[4], ids.get(t[5], -1)] for t in fr], np.int64).reshape(-1, 6).astype(np.int32)
+                                     for fr in tick] for tick in tracks], cap=cap)
+
+    def drain(self, cap=16):
+        """The ENDED tracks still waiting (result.pending of an earlier call), at most cap per stream."""
+        out = self._outputs(int(cap))
+        L.call("aic_bestshot_update", self._h, None, L.HOST, 0, None, None, L.HOST, int(cap), *(L.ptr(x) for x in out))
+        return self._result(out)
+
+    def flush(self, stream=None, cap=None):
+        """Every live track of the stream (None: of every stream) ends with reason FLUSHED and is handed over with everything pending:
+        the end of a run.  cap defaults to max_tracks, which takes them all."""
+        cap = self.max_tracks if cap is None else int(cap)
+        out = self._outputs(cap)
+        L.call("aic_bestshot_flush", self._h, -1 if stream is None else int(stream), cap, *(L.ptr(x) for x in out))
+        return self._result(out)
+
+    def export(self, stream):
+        """(events [n, 16], thumbs [n, TH, TW, 3]) of every track the stream holds, in slot order, live ones with reason LIVE.  Changes
+        nothing."""
+        n = C.c_int32()
+        ev = np.zeros((self.max_tracks, 16), np.int32)
+        th = np.zeros((self.max_tracks, self.thumb_h, self.thumb_w, 3), np.uint8)
+        L.call("aic_bestshot_export", self._h, int(stream), C.byref(n), L.ptr(ev), L.ptr(th))
+        return ev[:n.value].copy(), th[:n.value].copy()

@@ -19,6 +19,9 @@ the tracks always go to a `.jsonl` next to it.  `--show_display` needs cv2 (imsh
 With `--inputs` the S frames of a tick and their tracks go through ONE `render.Renderer` call; `--redact
 {off,box,head}`, `--redact_style mosaic:16|...|fill`, `--masks FILE.json` and `--draw_zones` (with `--zones`) pixelate or fill the tracked
 objects, black out fixed regions and draw the zones, with `--input` as well; with none of them the written pixels are the overlay's.
+`--best_shots DIR [--best_shot_size WxH] [--best_shot_region box|head]`: the best crop of every track, kept on the
+device from the frames as ingested (before any `--redact`), written as `DIR/cam<S>_id<ID>_f<best_frame>.ppm` with a line in
+`DIR/index.jsonl` when the track ends and, for the tracks still alive, at the end of the run.
 
 Pixel formats: with `--batch N` (and `--inputs`) YUV frames cross PCIe as they are and the pipeline unpacks them
 into its BGR ring on the device; frames that are saved or shown come back through TrackingPipeline.read_frames.  With `--batch 1` each
@@ -80,6 +83,12 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help="JSON file {\"cameras\": [{\"zones\": [[[x, y], ...], ...], \"lines\": [[[x, y], [x, y]], ...]}, ...]} in integer pixels, one entry per "
                         "source (a single entry serves every source): zone entries, dwell and line crossings are counted on the device and every "
                         "JSON line gains \"zones\": {occupancy, zone_in, zone_out, line_pos, line_neg, events}")
+    p.add_argument("--best_shots", type=str, default=None, metavar="DIR",
+                   help="keep the best crop of every track on the device (the sharpest, largest, least occluded one seen while it lived) and "
+                        "write it when the track ends, and at the end of the run, as DIR/cam<S>_id<ID>_f<best_frame>.ppm with one line per "
+                        "file in DIR/index.jsonl; the crops come from the frames as ingested, before any --redact")
+    p.add_argument("--best_shot_size", type=str, default="64x128", metavar="WxH", help="with --best_shots: thumbnail size, multiples of 8 in 16..128 x 16..256")
+    p.add_argument("--best_shot_region", type=str, default="box", choices=("box", "head"), help="with --best_shots: the whole box or its head (the top quarter)")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -116,6 +125,14 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--tracker deepsort_bank needs --inputs a,b,c (one source: --tracker deepsort)")
     if args.draw_zones and not args.zones:
         p.error("--draw_zones needs --zones FILE.json")
+    if (args.best_shot_size != "64x128" or args.best_shot_region != "box") and not args.best_shots:
+        p.error("--best_shot_size and --best_shot_region need --best_shots DIR")
+    try:
+        args.best_shot_wh = tuple(int(v) for v in args.best_shot_size.lower().split("x"))
+        if len(args.best_shot_wh) != 2:
+            raise ValueError
+    except ValueError:
+        p.error("--best_shot_size is WxH, e.g. 64x128")
     if args.inputs is not None:
         if args.input is not None:
             p.error("--inputs and --input are mutually exclusive")
@@ -315,6 +332,52 @@ class _ZoneLines:
         self.counter.close()
 
 
+class _BestShotFiles:
+    """--best_shots DIR: a BestShots (bestshot.py) over the run's frames and tracks; every final becomes DIR/cam<S>_id<ID>_f<best_frame>.ppm
+    (binary P6, RGB) and a line of DIR/index.jsonl.  With a pipeline the stage is attached to it (one update per run call); frame by
+    frame (no pipeline) the frame and the tracker's tuples are handed over per frame.  close() flushes what still lives."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import bestshot
+        self.mod, self.pipe, self._res = bestshot, pipe, None
+        self.shots = bestshot.BestShots(streams, (size[1], size[0]), thumb=args.best_shot_wh, region=args.best_shot_region, device=device)
+        self.dir = Path(args.best_shots)
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.index = open(self.dir / "index.jsonl", "a")
+        self.link = bool(args.link_cameras)
+        if pipe is not None:
+            pipe.attach_best_shots(self.shots)
+
+    def _write(self, result):
+        for ev, thumb in self.mod.finals(result):
+            name = f"cam{ev['stream']}_id{ev['id']}_f{ev['best_frame']}.ppm" if ev["has_shot"] else None   # None: never large enough to show
+            if name:
+                self.mod.write_ppm(self.dir / name, thumb)
+            line = dict(ev, file=name, reason=self.mod.REASONS[ev["reason"]])
+            if self.link and self.pipe is not None and self.pipe.xcam is not None:
+                line["global_id"] = int(self.pipe.global_ids(ev["stream"], [ev["id"]])[0])
+            self.index.write(json.dumps(line) + "\n")
+
+    def after(self, frame, tracks):
+        """After every yielded frame: the finals of the run call it came from (once), or of this frame."""
+        if self.pipe is None:
+            self._write(self.shots.update_tuples(np.ascontiguousarray(frame)[None, None], [[tracks]]))
+        elif self.pipe.best_shot_result is not self._res:
+            self._res = self.pipe.best_shot_result
+            self._write(self._res)
+
+    def close(self):
+        try:
+            res = self.shots.flush()
+            self._write(res)
+            while int(res.pending.sum()):
+                res = self.shots.drain(cap=self.shots.max_tracks)
+                self._write(res)
+        finally:
+            self.index.close()
+            self.shots.close()
+
+
 class _Output:
     """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
     render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
@@ -419,6 +482,16 @@ def main_streams(args, cv2):
             print(f"Error reading --zones {args.zones}: {e}")
             pipe.close()
             return 1
+    shots = None
+    if args.best_shots:
+        try:
+            shots = _BestShotFiles(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --best_shots: {e}")
+            if zones is not None:
+                zones.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -438,6 +511,8 @@ def main_streams(args, cv2):
         for frame, tracks in pipe.stream(ticks, read_back=output is not None):   # (YUV sources: the frames drawn on come back from the ring)
             k, idx = n % S, n // S
             n += 1
+            if shots is not None:
+                shots.after(frame, tracks)
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
@@ -466,6 +541,8 @@ def main_streams(args, cv2):
                 f.close()
         if zones is not None:
             zones.close()
+        if shots is not None:
+            shots.close()
         if output is not None:
             output.close()
         if archive is not None:
@@ -586,6 +663,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    shots = None
+    if args.best_shots:
+        try:
+            shots = _BestShotFiles(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --best_shots: {e}")
+            for f in (out_f, writer, zones, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -628,6 +715,8 @@ def main(argv=None):
         for frame, tracks in (batched() if pipe is not None else per_frame()):
             frame_idx += 1
             display_fps = frame_idx / total if total > 0 else 0.0
+            if shots is not None:
+                shots.after(frame, tracks)
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
                 info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
                 vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info])[0]
@@ -654,6 +743,8 @@ def main(argv=None):
             writer.close()
         if zones is not None:
             zones.close()
+        if shots is not None:
+            shots.close()
         if output is not None:
             output.close()
         if pipe is not None:

@@ -1,0 +1,322 @@
+// bestshot.cpp -- the best-shot object (bestshot.hpp) and its C ABI.  Every argument is checked before the device is touched; the
+// arithmetic runs in kernels_bestshot.hip or the call raises.
+#include "bestshot.hpp"
+
+#include <algorithm>
+
+namespace aic {
+
+void bestshot_check_params(int device, const aic_bestshot_config* p) {
+    AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL argument");
+    AIC_REQUIRE(device >= 0, AIC_ERR_INVALID, "device id out of range");
+    AIC_REQUIRE(p->streams >= 1 && p->streams <= BS_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+    AIC_REQUIRE(p->frame_h >= 1 && p->frame_h <= BS_DIM_MAX && p->frame_w >= 1 && p->frame_w <= BS_DIM_MAX, AIC_ERR_INVALID,
+                "frame height and width must be in 1..16384");
+    AIC_REQUIRE(p->thumb_w >= 16 && p->thumb_w <= 128 && p->thumb_w % 8 == 0, AIC_ERR_INVALID, "thumb_w must be a multiple of 8 in 16..128");
+    AIC_REQUIRE(p->thumb_h >= 16 && p->thumb_h <= 256 && p->thumb_h % 8 == 0, AIC_ERR_INVALID, "thumb_h must be a multiple of 8 in 16..256");
+    AIC_REQUIRE(p->max_tracks >= 1 && p->max_tracks <= BS_TRACKS_MAX, AIC_ERR_INVALID, "max_tracks must be in 1..512");
+    AIC_REQUIRE(p->forget_after >= 0 && p->forget_after <= (1 << 24), AIC_ERR_INVALID, "forget_after must be in 0..2^24");
+    AIC_REQUIRE(p->region == BS_REGION_BOX || p->region == BS_REGION_HEAD, AIC_ERR_INVALID, "region must be 0 (box) or 1 (head)");
+    AIC_REQUIRE(p->head_q8 >= 1 && p->head_q8 <= 256, AIC_ERR_INVALID, "head_q8 must be in 1..256");
+    AIC_REQUIRE(p->pad >= 0 && p->pad <= 64, AIC_ERR_INVALID, "pad must be in 0..64");
+    AIC_REQUIRE(p->min_w >= 1 && p->min_w <= BS_DIM_MAX && p->min_h >= 1 && p->min_h <= BS_DIM_MAX, AIC_ERR_INVALID,
+                "min_w and min_h must be in 1..16384");
+}
+
+BestShot::BestShot(int device, const aic_bestshot_config& p)
+    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.thumb_w, p.thumb_h, p.max_tracks, p.forget_after, p.region, p.head_q8, p.pad, p.min_w, p.min_h},
+      reset_pending(p.streams, 1), stop(p.streams, 0) {}
+
+void BestShot::reset(int stream) {
+    AIC_REQUIRE(stream >= 0 && stream < g.streams, AIC_ERR_INVALID, "stream outside the best-shot bank");
+    stop[stream] = 0;
+    reset_pending[stream] = 1;
+}
+
+// grows a device buffer; a failed allocation is a capacity error of the call, not a runtime fault
+template <class B>
+static void grow(B& buf, size_t count, const char* what) {
+    if (count <= buf.n) return;
+    try {
+        buf.alloc(count);
+    } catch (const Error&) {
+        (void)hipGetLastError();
+        throw Error(AIC_ERR_CAPACITY, std::string("the device has no room for ") + what + " (" + std::to_string(count * sizeof(*buf.p) >> 20) + " MiB)");
+    }
+}
+
+void BestShot::touch_device() {
+    if (!dev) dev = &device(device_id);
+    dev->use();
+    if (!d_state.p) {
+        grow(d_slot_thumbs, (size_t)g.streams * g.max_tracks * thumb_bytes(), "the resident slot thumbnails");
+        grow(d_state, (size_t)g.streams * BS_ST_INTS, "the slot tables");
+        HIP_CHECK(hipMemsetAsync(d_state.p, 0, d_state.bytes(), dev->s_trk));
+    }
+}
+
+static void check_outputs(int cap, const int32_t* n_final, const int32_t* events, const uint8_t* thumbs, const int32_t* pending) {
+    AIC_REQUIRE(cap >= 0 && cap <= BS_CAP_MAX, AIC_ERR_INVALID, "cap must be in 0..4096");
+    AIC_REQUIRE(n_final && pending, AIC_ERR_INVALID, "NULL n_final or pending");
+    AIC_REQUIRE(cap == 0 || (events && thumbs), AIC_ERR_INVALID, "NULL events or thumbs");
+}
+
+// outputs of a call, ints: n_final[S] | pending[S] | status[S] | (16-byte aligned) events[S, cap, 16]
+static size_t out_events_at(int S) { return ((size_t)3 * S + 3) / 4 * 4; }
+
+void BestShot::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap,
+                      int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
+    const int S = g.streams;
+    AIC_REQUIRE(ticks >= 0 && ticks <= BS_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
+    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
+    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
+    check_outputs(cap, n_final, events, thumbs, pending);
+    const long F = (long)ticks * S;
+    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
+    AIC_REQUIRE(F == 0 || (frames && counts), AIC_ERR_INVALID, "NULL frames or counts");
+    auto check_counts = [&](const int32_t* c) {
+        long total = 0;
+        for (long f = 0; f < F; ++f) {
+            AIC_REQUIRE(c[f] >= 0, AIC_ERR_INVALID, "a negative row count");
+            AIC_REQUIRE(c[f] <= BS_ROWS_MAX, AIC_ERR_CAPACITY, "frame " + std::to_string(f) + " has more than 512 rows");
+            total += c[f];
+        }
+        AIC_REQUIRE(total == 0 || rows6, AIC_ERR_INVALID, "NULL rows");
+        AIC_REQUIRE(total <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
+        return total;
+    };
+    long total = 0;
+    if (rows_mem == AIC_HOST && F) total = check_counts(counts);
+
+    touch_device();
+    hipStream_t st = dev->s_trk;
+    if (rows_mem == AIC_DEVICE && F) {                                       // the counts decide the launches: one small copy brings them over
+        h_counts.resize(F);
+        HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts, F * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        counts = h_counts.data();
+        total = check_counts(counts);
+    }
+    // ---- staging: reset[S] | mode[S] | frame_off[F + 1] | rows (host memory only)
+    const size_t o_mode = S, o_off = 2 * (size_t)S, o_rows = o_off + F + 1;
+    const size_t n_stage = o_rows + (rows_mem == AIC_HOST ? (size_t)total * 6 : 0);
+    h_stage.ensure(n_stage);
+    grow(d_stage, n_stage, "the staged rows");
+    int* h = h_stage.p;
+    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[o_mode + s] = BS_MODE_DRAIN;
+    h[o_off] = 0;
+    for (long i = 0; i < F; ++i) h[o_off + i + 1] = h[o_off + i] + counts[i];
+    if (rows_mem == AIC_HOST && total) std::memcpy(h + o_rows, rows6, (size_t)total * 6 * sizeof(int));
+    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, n_stage * sizeof(int), hipMemcpyHostToDevice, st));
+    const int* d_rows = rows_mem == AIC_HOST ? d_stage.p + o_rows : rows6;
+    const int* d_off = d_stage.p + o_off;
+    grow(d_info, std::max<size_t>(8, (size_t)total * 8), "the scored rows");
+    const size_t o_ev = out_events_at(S);
+    grow(d_out, o_ev + (size_t)S * cap * BS_EVENT_INTS, "the events");
+    grow(d_out_thumbs, std::max<size_t>(16, (size_t)S * cap * thumb_bytes()), "the output thumbnails");
+    int* o = d_out.p;
+
+    {
+        Prof pr(*dev, PROF_TRK, st, 0, (double)total * thumb_bytes());
+        if (ticks == 0)
+            launch_bestshot_walk(d_off, 0, d_rows, d_info.p, d_cand.p, 0, d_stage.p, d_stage.p + o_mode, 1, g, d_state.p, d_slot_thumbs.p, cap, o, o + S,
+                                 o + 2 * S, o + o_ev, d_out_thumbs.p, st);
+        const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
+        for (int lo = 0; lo < ticks;) {
+            int hi = lo + 1;                                                 // one tick at the least
+            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) &&
+                   (size_t)(h[o_off + (size_t)(hi + 1) * S] - h[o_off + (size_t)lo * S]) * thumb_bytes() <= budget &&
+                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
+                ++hi;
+            const int base = h[o_off + (size_t)lo * S], rows = h[o_off + (size_t)hi * S] - base;
+            int max_rows = 0;
+            for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
+            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
+            if (frames_mem == AIC_HOST) {
+                grow(d_frames, (size_t)(hi - lo) * tick_bytes, "the staged frames");
+                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)(hi - lo) * tick_bytes, hipMemcpyHostToDevice, st));
+                d_fr = d_frames.p;
+            }
+            grow(d_cand, std::max<size_t>(16, (size_t)rows * thumb_bytes()), "the candidate thumbnails");
+            launch_bestshot_score(d_fr, d_off + (size_t)lo * S, (hi - lo) * S, max_rows, d_rows, d_state.p, d_stage.p, lo == 0, g, base, d_info.p, d_cand.p,
+                                  st);
+            launch_bestshot_walk(d_off + (size_t)lo * S, hi - lo, d_rows, d_info.p, d_cand.p, base, d_stage.p, d_stage.p + o_mode, lo == 0, g, d_state.p,
+                                 d_slot_thumbs.p, cap, o, o + S, o + 2 * S, o + o_ev, d_out_thumbs.p, st);
+            lo = hi;
+        }
+    }
+    if (stats && total) {
+        h_info.resize((size_t)total * 8);
+        HIP_CHECK(hipMemcpyAsync(h_info.data(), d_info.p, (size_t)total * 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    finish(cap, n_final, events, thumbs, pending, status);
+    if (stats && total) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        n_rows += total;
+        for (long i = 0; i < total; ++i) n_candidates += (h_info[i * 8] & BS_F_CAND) != 0, n_stored += (h_info[i * 8] & BS_F_STORED) != 0;
+    }
+}
+
+void BestShot::flush(int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
+    const int S = g.streams;
+    AIC_REQUIRE(stream >= -1 && stream < S, AIC_ERR_INVALID, "stream outside the best-shot bank (-1 = every stream)");
+    check_outputs(cap, n_final, events, thumbs, pending);
+    touch_device();
+    hipStream_t st = dev->s_trk;
+    h_stage.ensure(2 * (size_t)S + 1);
+    grow(d_stage, 2 * (size_t)S + 1, "the staging buffer");
+    int* h = h_stage.p;
+    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[S + s] = stream < 0 || stream == s ? BS_MODE_FLUSH : BS_MODE_NONE;
+    h[2 * S] = 0;
+    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, (2 * (size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    const size_t o_ev = out_events_at(S);
+    grow(d_out, o_ev + (size_t)S * cap * BS_EVENT_INTS, "the events");
+    grow(d_out_thumbs, std::max<size_t>(16, (size_t)S * cap * thumb_bytes()), "the output thumbnails");
+    int* o = d_out.p;
+    launch_bestshot_walk(d_stage.p + 2 * S, 0, nullptr, nullptr, nullptr, 0, d_stage.p, d_stage.p + S, 1, g, d_state.p, d_slot_thumbs.p, cap, o, o + S,
+                         o + 2 * S, o + o_ev, d_out_thumbs.p, st);
+    finish(cap, n_final, events, thumbs, pending, status);
+}
+
+void BestShot::finish(int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
+    const int S = g.streams;
+    hipStream_t st = dev->s_trk;
+    const size_t o_ev = out_events_at(S);
+    h_out.ensure(3 * (size_t)S);
+    HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, 3 * (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::fill(reset_pending.begin(), reset_pending.end(), (char)0);
+    const int* o = h_out.p;
+    bool any = false;
+    for (int s = 0; s < S; ++s) {                                            // only the filled entries come back
+        const int n = std::min(std::max(o[s], 0), cap);
+        n_final[s] = n, pending[s] = o[S + s], stop[s] = o[2 * S + s];
+        if (status) status[s] = stop[s];
+        if (!n) continue;
+        any = true;
+        HIP_CHECK(hipMemcpyAsync(events + (size_t)s * cap * BS_EVENT_INTS, d_out.p + o_ev + (size_t)s * cap * BS_EVENT_INTS,
+                                 (size_t)n * BS_EVENT_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(thumbs + (size_t)s * cap * thumb_bytes(), d_out_thumbs.p + (size_t)s * cap * thumb_bytes(), (size_t)n * thumb_bytes(),
+                                 hipMemcpyDeviceToHost, st));
+    }
+    if (any) HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void BestShot::export_stream(int stream, int32_t* n, int32_t* events, uint8_t* thumbs) {
+    AIC_REQUIRE(stream >= 0 && stream < g.streams, AIC_ERR_INVALID, "stream outside the best-shot bank");
+    AIC_REQUIRE(n && events && thumbs, AIC_ERR_INVALID, "NULL argument");
+    *n = 0;
+    if (!d_state.p || reset_pending[stream]) return;                         // nothing seen yet, or a reset the next call applies
+    dev->use();
+    hipStream_t st = dev->s_trk;
+    h_state.resize(BS_ST_INTS);
+    HIP_CHECK(hipMemcpyAsync(h_state.data(), d_state.p + (size_t)stream * BS_ST_INTS, BS_ST_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const int* a = h_state.data() + BS_ST_SLOTS;
+    auto at = [&](int arr, int t) { return a[arr * BS_TRACKS_MAX + t]; };
+    int k = 0;
+    for (int t = 0; t < g.max_tracks; ++t) {
+        const int state = at(BS_A_STATE, t);
+        if (!state) continue;
+        const int has = at(BS_A_HAS, t);
+        int32_t* ev = events + (size_t)k * BS_EVENT_INTS;
+        const int32_t row[BS_EVENT_INTS] = {state == 1 ? BS_LIVE : state == 3 ? BS_FLUSHED : BS_EXPIRED, stream, at(BS_A_ID, t), at(BS_A_CLS, t),
+                                            at(BS_A_FIRST, t), at(BS_A_LAST, t), at(BS_A_SIGHT, t), has, has ? at(BS_A_BFRAME, t) : 0,
+                                            has ? at(BS_A_SCORE, t) : 0, has ? at(BS_A_C0, t) : 0, has ? at(BS_A_C1, t) : 0, has ? at(BS_A_C2, t) : 0,
+                                            has ? at(BS_A_C3, t) : 0, t, 0};
+        std::copy(row, row + BS_EVENT_INTS, ev);
+        uint8_t* th = thumbs + (size_t)k * thumb_bytes();
+        if (has)
+            HIP_CHECK(hipMemcpyAsync(th, d_slot_thumbs.p + ((size_t)stream * g.max_tracks + t) * thumb_bytes(), thumb_bytes(), hipMemcpyDeviceToHost, st));
+        else std::memset(th, 0, thumb_bytes());
+        ++k;
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    *n = k;
+}
+
+}  // namespace aic
+
+using namespace aic;
+
+extern "C" {
+
+int aic_bestshot_params(int streams, int frame_h, int frame_w, aic_bestshot_config* out) {
+    return guarded([&] {
+        AIC_REQUIRE(out, AIC_ERR_INVALID, "NULL argument");
+        *out = aic_bestshot_config{streams, frame_h, frame_w, 64, 128, 128, 70, BS_REGION_BOX, 64, 0, 8, 16};
+    });
+}
+
+int aic_bestshot_create(int device, const aic_bestshot_config* params, aic_bestshot** out) {
+    return guarded([&] {
+        AIC_REQUIRE(out, AIC_ERR_INVALID, "NULL argument");
+        bestshot_check_params(device, params);
+        *out = new aic_bestshot(device, *params);
+    });
+}
+
+int aic_bestshot_destroy(aic_bestshot* b) {
+    return guarded([&] {
+        if (b && b->b.dev) { b->b.dev->use(); (void)hipStreamSynchronize(b->b.dev->s_trk); }
+        delete b;
+    });
+}
+
+int aic_bestshot_option(aic_bestshot* b, const char* key, int value) {
+    return guarded([&] {
+        AIC_REQUIRE(b && key, AIC_ERR_INVALID, "NULL argument");
+        const std::string k(key);
+        if (k == "ticks_per_launch") {
+            AIC_REQUIRE(value >= 0 && value <= BS_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
+            b->b.ticks_per_launch = value;
+        } else if (k == "launch_budget_mb") {
+            AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
+            b->b.launch_budget_mb = value;
+        } else if (k == "stats") {
+            AIC_REQUIRE(value == 0 || value == 1, AIC_ERR_INVALID, "stats must be 0 or 1");
+            b->b.stats = value;
+        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown best-shot option: " + k);
+    });
+}
+
+int aic_bestshot_reset(aic_bestshot* b, int stream) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+        b->b.reset(stream);
+    });
+}
+
+int aic_bestshot_update(aic_bestshot* b, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
+                        int rows_mem, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+        b->b.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap, n_final, events, thumbs, pending, status);
+    });
+}
+
+int aic_bestshot_flush(aic_bestshot* b, int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending,
+                       int32_t* status) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+        b->b.flush(stream, cap, n_final, events, thumbs, pending, status);
+    });
+}
+
+int aic_bestshot_counters(aic_bestshot* b, int64_t* rows, int64_t* candidates, int64_t* stored) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+        if (rows) *rows = b->b.n_rows;
+        if (candidates) *candidates = b->b.n_candidates;
+        if (stored) *stored = b->b.n_stored;
+    });
+}
+
+int aic_bestshot_export(aic_bestshot* b, int stream, int32_t* n, int32_t* events, uint8_t* thumbs) {
+    return guarded([&] {
+        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+        b->b.export_stream(stream, n, events, thumbs);
+    });
+}
+
+}  // extern "C"

@@ -282,6 +282,37 @@ class TrackingPipeline:
         off = np.concatenate([[0], np.cumsum(res.frames_per_stream)])
         self.zone_occupancy = [res.occupancy[off[s]:off[s + 1]] for s in range(S)]
 
+    _best_shots = best_shot_result = None
+    best_shot_cap = 16
+
+    def attach_best_shots(self, best_shots, cap=16):
+        """A BestShots (bestshot.py) of `.streams` streams for this frame size: after every run* call the call's frames and tracks -- all
+        ticks, all streams, ONE best_shots.update -- go through it and best_shot_result is that call's BestShotResult (at most `cap`
+        finals per stream per call; the rest wait, see .pending and best_shots.drain()).  Frames and rows reach the stage from the
+        host side: the host array of run*_from_host (a YUV format converted with frames.to_bgr, the arithmetic of the pipeline's own
+        unpack), read_frames(slot, count) for run / run_raw; with *_passes it sees the last pass only.  The tracks returned are
+        untouched.  None detaches."""
+        if best_shots is not None and (best_shots.streams != self.streams or (best_shots.frame_h, best_shots.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"best shots of {best_shots.streams} streams of {best_shots.frame_h}x{best_shots.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._best_shots, self.best_shot_cap, self.best_shot_result = best_shots, int(cap), None
+
+    def _feed_best_shots(self, nt, rows, slot=0, host_frames=None):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major; host_frames: what a *_from_host call was handed."""
+        b = self._best_shots
+        if b is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        if host_frames is None:
+            bgr = self.read_frames(slot, count)
+        elif self._pix[0] != L.PIX_BGR24:
+            bgr = frames.to_bgr(host_frames, self._pix[0], matrix=self._pix[1], range=self._pix[2], device=config.resolve_device(self._device))
+        else:
+            bgr = host_frames
+        self.best_shot_result = b.update(bgr.reshape(count // S, S, self.frame_h, self.frame_w, 3),
+                                         [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
+                                         cap=self.best_shot_cap)
+
     def close(self):
         for b in getattr(self, "_staging", []):
             try:
@@ -341,6 +372,7 @@ class TrackingPipeline:
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                L.ptr(db), L.ptr(ds), L.ptr(dl))
         self._feed_zones(nt, rows)
+        self._feed_best_shots(nt, rows, slot)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -361,6 +393,7 @@ class TrackingPipeline:
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                None, None, None)
         self._feed_zones(nt[:count], rows[:count])
+        self._feed_best_shots(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
@@ -368,6 +401,7 @@ class TrackingPipeline:
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_passes", self._h, int(slot), int(count), int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
+        self._feed_best_shots(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -385,6 +419,7 @@ class TrackingPipeline:
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host", self._h, L.ptr(f), int(slot), count, L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
+        self._feed_best_shots(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -395,6 +430,7 @@ class TrackingPipeline:
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host_passes", self._h, L.ptr(f), int(slot), count, int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
+        self._feed_best_shots(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

@@ -876,6 +876,52 @@ int aic_render_set_masks(aic_render* r, int camera, int n_polys, const int32_t* 
 int aic_render_rects(aic_render* r, const int32_t* rows6, int n_rows, int32_t* rects4, int* n_rects);
 int aic_render_frames(aic_render* r, uint8_t* frames_bgr, int n_frames, int h, int w, int mem, const int32_t* rows6, const int32_t* row_counts,
                       const int32_t* prims, const int32_t* prim_counts, const uint8_t* text, int text_bytes, const int32_t* cameras);
+
+/* ---- best shots: the best crop of every track, kept on the device, per camera (csrc/bestshot.hpp) -------------
+ * A tracker-agnostic stage over u8 BGR frames of one size and the rows every tracker delivers (x1 y1 x2 y2 id cls, int32), for
+ * `streams` (1..256) cameras per call.  Every counted row's region (box or head, the arithmetic of aic_render_rects, clipped to the
+ * frame) is resampled to a thumb_h x thumb_w x 3 thumbnail by an integer area average and scored; a table of max_tracks slots per
+ * stream keeps the best thumbnail per track id; a track unseen for more than forget_after ticks ENDS and is handed over with its shot.
+ * tests/bestshot_oracle.py is the specification -- counted rows, candidates, the thumbnail, the score, the order of a tick, the
+ * capacity rule -- and the device equals it bit for bit.
+ * aic_bestshot_config: frame_h, frame_w in 1..16384; thumb_w in 16..128, thumb_h in 16..256, both multiples of 8; max_tracks 1..512; forget_after
+ * 0..2^24; region 0 = box, 1 = head (head_q8 in 1..256); pad 0..64; min_w, min_h in 1..16384.  aic_bestshot_params fills the
+ * documented defaults (64 x 128 thumbnails, 128 tracks, forget_after 70, box, head_q8 64, pad 0, min 8 x 16) around streams / frame size.
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option and reset never touch it.  The resident slot
+ * thumbnails (streams * max_tracks * thumb_h * thumb_w * 3 bytes) are allocated by the first call that reaches the device; an
+ * allocation that does not fit fails that call with AIC_ERR_CAPACITY.
+ * update: `ticks` (0..65536) ticks; frames [ticks, streams, h, w, 3] tick-major in host or device memory (frames_mem); counts[ticks *
+ * streams] and rows6 [sum of counts, 6] in the same order, both in host or both in device memory (rows_mem).  A frame of more than
+ * 512 rows rejects the call with AIC_ERR_CAPACITY before anything is staged.  ticks = 0 only drains.  Outputs (host): n_final[streams],
+ * events[streams, cap, 16] = reason (0 LIVE, 1 EXPIRED, 2 FLUSHED), stream, id, cls, first_frame, last_seen, sightings, has_shot,
+ * best_frame, score, C.x0, C.y0, C.x1, C.y1, slot, 0; thumbs[streams, cap, thumb_h, thumb_w, 3] (only the n_final[s] first of a stream
+ * are written); pending[streams] = ENDED slots still waiting for room; status[streams] (may be NULL) = 0 or the code the stream
+ * stopped with.  cap in 0..4096 per stream per call; nothing is ever dropped.  A stream that needs more than max_tracks slots stops
+ * alone with AIC_ERR_CAPACITY: that tick is not committed and later ticks deliver nothing until aic_bestshot_reset; export, flush and
+ * a ticks = 0 drain still work.
+ * flush: stream (or -1 = all) -- every live slot ENDS with reason FLUSHED, then the ENDED slots are emitted as by update.
+ * export: every non-free slot of a stream in slot order (live ones with reason LIVE) into events[max_tracks, 16], thumbs[max_tracks,
+ * ...]; changes nothing.  reset: the stream forgets everything, pending slots included; a stop is cleared.
+ * option "ticks_per_launch": 0 (default) = as many ticks per launch as the budget allows, k = at most k; "launch_budget_mb" (1..65536,
+ * default 1024): the candidate thumbnails and the staged frames of one launch each stay below it, one tick at the least; "stats" 0 / 1
+ * (aic_bestshot_counters).  Same results. */
+typedef struct aic_bestshot aic_bestshot;
+typedef struct {
+    int32_t streams, frame_h, frame_w, thumb_w, thumb_h, max_tracks, forget_after, region, head_q8, pad, min_w, min_h;
+} aic_bestshot_config;
+int aic_bestshot_params(int streams, int frame_h, int frame_w, aic_bestshot_config* out);
+int aic_bestshot_create(int device, const aic_bestshot_config* params, aic_bestshot** out);
+int aic_bestshot_destroy(aic_bestshot* b);
+int aic_bestshot_option(aic_bestshot* b, const char* key, int value);
+int aic_bestshot_reset(aic_bestshot* b, int stream);
+int aic_bestshot_update(aic_bestshot* b, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
+                        int rows_mem, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status);
+int aic_bestshot_flush(aic_bestshot* b, int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending,
+                       int32_t* status);
+int aic_bestshot_export(aic_bestshot* b, int stream, int32_t* n, int32_t* events, uint8_t* thumbs);
+/* After option "stats" 1 (0 = default): since creation, the rows handed to update, the candidates among them that were scored, and the
+ * candidate thumbnails the could-still-win filter let through to the per-row buffer.  Any pointer may be NULL.  Host only. */
+int aic_bestshot_counters(aic_bestshot* b, int64_t* rows, int64_t* candidates, int64_t* stored);
 /* ---- 4:2:0 YUV frames in, NV12 out: pixel-format conversion of a bank of frames in one launch (csrc/yuv.hpp) -------
  * Decoders, RTSP stacks and camera SDKs deliver NV12 (sometimes I420) on pitched surfaces and encoders want the same back; everything else
  * in this library reads packed BGR24.  tests/yuv_oracle.py is the specification and the device equals it bit for bit in both directions:
