@@ -67,6 +67,10 @@ class BestShotConfig(C.Structure):
                                          "head_q8", "pad", "min_w", "min_h")]
 
 
+class SceneConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell")]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -265,6 +269,13 @@ _SIGS = {
     "aic_bestshot_flush": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "aic_bestshot_export": (_I, [_P, _I, _P, _P, _P]),
     "aic_bestshot_counters": (_I, [_P, _P, _P, _P]),
+    "aic_scene_config_default": (_I, [_I, _I, _I, _P]),
+    "aic_scene_create": (_I, [_I, _P, _P]),
+    "aic_scene_destroy": (_I, [_P]),
+    "aic_scene_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_scene_reset": (_I, [_P, _I]),
+    "aic_scene_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "aic_scene_export": (_I, [_P, _I, _P, _P, _P, _P]),
     "aic_yuv_coeffs": (_I, [_I, _I, _P, _P, _P]),
     "aic_frames_to_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
     "aic_frames_from_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),

@@ -22,6 +22,9 @@ objects, black out fixed regions and draw the zones, with `--input` as well; wit
 `--best_shots DIR [--best_shot_size WxH] [--best_shot_region box|head]`: the best crop of every track, kept on the
 device from the frames as ingested (before any `--redact`), written as `DIR/cam<S>_id<ID>_f<best_frame>.ppm` with a line in
 `DIR/index.jsonl` when the track ends and, for the tracks still alive, at the end of the run.
+`--scene_watch [--scene_cell {4,8,16}]`: a background model per camera on a coarse gray grid.  Every JSON line
+gains `"scene": {active, moving_cells, motion_box, alarms}` and `"moving"`, one value per track of the line (256 = every cell under its
+box moves, -1 = the box is off the frame); every alarm edge (dark, bright, defocus, scene, frozen) is printed as a line of its own.
 
 Pixel formats: with `--batch N` (and `--inputs`) YUV frames cross PCIe as they are and the pipeline unpacks them
 into its BGR ring on the device; frames that are saved or shown come back through TrackingPipeline.read_frames.  With `--batch 1` each
@@ -89,6 +92,10 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                         "file in DIR/index.jsonl; the crops come from the frames as ingested, before any --redact")
     p.add_argument("--best_shot_size", type=str, default="64x128", metavar="WxH", help="with --best_shots: thumbnail size, multiples of 8 in 16..128 x 16..256")
     p.add_argument("--best_shot_region", type=str, default="box", choices=("box", "head"), help="with --best_shots: the whole box or its head (the top quarter)")
+    p.add_argument("--scene_watch", action="store_true",
+                   help="watch every camera's scene on the device: every JSON line gains \"scene\": {active, moving_cells, motion_box, alarms} "
+                        "and \"moving\" (per track, 0..256), and every alarm edge (dark, bright, defocus, scene, frozen) is printed as its own line")
+    p.add_argument("--scene_cell", type=int, default=None, choices=(4, 8, 16), help="with --scene_watch: the grid's cell size in pixels (default 8)")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -127,6 +134,8 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--draw_zones needs --zones FILE.json")
     if (args.best_shot_size != "64x128" or args.best_shot_region != "box") and not args.best_shots:
         p.error("--best_shot_size and --best_shot_region need --best_shots DIR")
+    if args.scene_cell is not None and not args.scene_watch:
+        p.error("--scene_cell needs --scene_watch")
     try:
         args.best_shot_wh = tuple(int(v) for v in args.best_shot_size.lower().split("x"))
         if len(args.best_shot_wh) != 2:
@@ -378,6 +387,42 @@ class _BestShotFiles:
             self.shots.close()
 
 
+class _SceneLines:
+    """--scene_watch: a SceneWatch (scene.py) over the run's frames and tracks.  With a pipeline the stage is attached to it (one update
+    per run call, whose frames are then yielded in order); frame by frame (no pipeline) every frame is an update of its own."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import scene
+        self.mod, self.pipe, self._res, self._i, self.streams = scene, pipe, None, 0, streams
+        self.watch = scene.SceneWatch(streams, (size[1], size[0]), cell=args.scene_cell or 8, device=device)
+        self.ids = {n: i for i, n in enumerate(config.CLASSES)}
+        if pipe is not None:
+            pipe.attach_scene_watch(self.watch)
+
+    def after(self, frame, tracks):
+        """After every yielded frame: ({"active", "moving_cells", "motion_box", "alarms"}, the moving share per track); prints the
+        frame's alarm edges."""
+        if self.pipe is None:
+            rows = np.array([[t[0], t[1], t[2], t[3], t[4], self.ids.get(t[5], -1)] for t in tracks], np.int64).reshape(-1, 6).astype(np.int32)
+            self._res, self._i = self.watch.update(np.ascontiguousarray(frame)[None, None], [[rows]]), 0
+        elif self.pipe.scene_result is not self._res:
+            self._res, self._i = self.pipe.scene_result, 0
+        t, s = divmod(self._i, self.streams)
+        self._i += 1
+        res = self._res
+        rec = res.records[t, s]
+        for i, kind in enumerate(self.mod.KINDS):
+            for raised, bit in ((True, i), (False, 8 + i)):
+                if int(res.edges[t, s]) >> bit & 1:
+                    print(json.dumps({"alarm": kind, "raised": raised, "stream": s, "frame": int(res.frame[t, s])}))
+        scene = {"active": bool(res.active[t, s]), "moving_cells": int(res.n_moving[t, s]), "motion_box": [int(v) for v in res.motion_box[t, s]],
+                 "alarms": self.mod.alarm_names(res.alarms[t, s])}
+        return scene, [int(v) for v in res.rows_of(t, s)]
+
+    def close(self):
+        self.watch.close()
+
+
 class _Output:
     """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
     render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
@@ -492,6 +537,17 @@ def main_streams(args, cv2):
                 zones.close()
             pipe.close()
             return 1
+    watch = None
+    if args.scene_watch:
+        try:
+            watch = _SceneLines(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --scene_watch: {e}")
+            for f in (zones, shots):
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -513,6 +569,7 @@ def main_streams(args, cv2):
             n += 1
             if shots is not None:
                 shots.after(frame, tracks)
+            scene = watch.after(frame, tracks) if watch is not None else None
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
@@ -532,6 +589,8 @@ def main_streams(args, cv2):
                     line["returning"] = [[t, key, d] for c, t, key, d in pipe.xcam.returning() if c == k]
                 if zones is not None:
                     line["zones"] = zones.line(tracks)
+                if scene is not None:
+                    line["scene"], line["moving"] = scene
                 outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
@@ -543,6 +602,8 @@ def main_streams(args, cv2):
             zones.close()
         if shots is not None:
             shots.close()
+        if watch is not None:
+            watch.close()
         if output is not None:
             output.close()
         if archive is not None:
@@ -673,6 +734,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    watch = None
+    if args.scene_watch:
+        try:
+            watch = _SceneLines(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --scene_watch: {e}")
+            for f in (out_f, writer, zones, shots, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -717,6 +788,7 @@ def main(argv=None):
             display_fps = frame_idx / total if total > 0 else 0.0
             if shots is not None:
                 shots.after(frame, tracks)
+            scene = watch.after(frame, tracks) if watch is not None else None
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
                 info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
                 vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info])[0]
@@ -731,6 +803,8 @@ def main(argv=None):
                 line = {"frame": frame_idx - 1, "tracks": tracks}
                 if zones is not None:
                     line["zones"] = zones.line(tracks)
+                if scene is not None:
+                    line["scene"], line["moving"] = scene
                 out_f.write(json.dumps(line) + "\n")
             if frame_idx % 100 == 0:
                 print(f"Processed {frame_idx} frames. Current FPS: {display_fps:.2f}")
@@ -745,6 +819,8 @@ def main(argv=None):
             zones.close()
         if shots is not None:
             shots.close()
+        if watch is not None:
+            watch.close()
         if output is not None:
             output.close()
         if pipe is not None:

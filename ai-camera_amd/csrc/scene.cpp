@@ -1,0 +1,253 @@
+// scene.cpp -- the scene-watch object (scene.hpp) and its C ABI.  Every argument is checked before the device is touched; the
+// arithmetic runs in kernels_scene.hip or the call raises.
+#include "scene.hpp"
+
+#include <algorithm>
+
+namespace aic {
+
+void scene_check_config(int device, const aic_scene_config* p) {
+    AIC_REQUIRE(p, AIC_ERR_INVALID, "NULL argument");
+    AIC_REQUIRE(device >= 0, AIC_ERR_INVALID, "device id out of range");
+    AIC_REQUIRE(p->streams >= 1 && p->streams <= SC_STREAMS_MAX, AIC_ERR_INVALID, "streams must be in 1..256");
+    AIC_REQUIRE(p->frame_h >= 1 && p->frame_h <= SC_DIM_MAX && p->frame_w >= 1 && p->frame_w <= SC_DIM_MAX, AIC_ERR_INVALID,
+                "frame height and width must be in 1..16384");
+    AIC_REQUIRE(p->cell == 4 || p->cell == 8 || p->cell == 16, AIC_ERR_INVALID, "cell must be 4, 8 or 16");
+    AIC_REQUIRE(p->frame_h >= p->cell && p->frame_w >= p->cell, AIC_ERR_INVALID, "the frame is smaller than one cell");
+}
+
+Scene::Scene(int device, const aic_scene_config& p)
+    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.cell, p.frame_h / p.cell, p.frame_w / p.cell}, reset_pending(p.streams, 1) {}
+
+void Scene::option(const std::string& k, int value) {
+    struct Opt { const char* name; int ScOpts::*field; int lo, hi; };
+    static const Opt table[] = {
+        {"thresh", &ScOpts::thresh, 0, 255}, {"noise_k_q4", &ScOpts::noise_k_q4, 0, 4096}, {"warmup", &ScOpts::warmup, 1, 1 << 20},
+        {"big_thresh", &ScOpts::big_thresh, 0, 255}, {"learn_shift", &ScOpts::learn_shift, 1, 12}, {"slow_extra", &ScOpts::slow_extra, 0, 8},
+        {"dev_init_q8", &ScOpts::dev_init_q8, 0, 65280}, {"min_neighbours", &ScOpts::min_neighbours, 1, 9}, {"dark_luma", &ScOpts::dark_luma, 0, 256},
+        {"bright_luma", &ScOpts::bright_luma, 0, 255}, {"min_ref_q8", &ScOpts::min_ref_q8, 0, 1 << 20}, {"defocus_q8", &ScOpts::defocus_q8, 0, 256},
+        {"scene_q16", &ScOpts::scene_q16, 0, 65536}, {"ref_shift", &ScOpts::ref_shift, 1, 12}, {"hold", &ScOpts::hold, 1, 1 << 20},
+        {"gate_cells", &ScOpts::gate_cells, 1, 1 << 24}, {"gate_hold", &ScOpts::gate_hold, 0, 1 << 20}};
+    if (k == "ticks_per_launch") {
+        AIC_REQUIRE(value >= 0 && value <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
+        ticks_per_launch = value;
+        return;
+    }
+    if (k == "launch_budget_mb") {
+        AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
+        launch_budget_mb = value;
+        return;
+    }
+    for (const Opt& t : table) {
+        if (k != t.name) continue;
+        AIC_REQUIRE(value >= t.lo && value <= t.hi, AIC_ERR_INVALID, k + " must be in " + std::to_string(t.lo) + ".." + std::to_string(t.hi));
+        ScOpts n = o;
+        n.*t.field = value;
+        AIC_REQUIRE(n.learn_shift + n.slow_extra <= 14, AIC_ERR_INVALID, "learn_shift + slow_extra must not exceed 14");
+        o = n;
+        return;
+    }
+    AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown scene option: " + k);
+}
+
+void Scene::reset(int stream) {
+    AIC_REQUIRE(stream >= -1 && stream < g.streams, AIC_ERR_INVALID, "stream outside the scene bank (-1 = every stream)");
+    for (int s = 0; s < g.streams; ++s)
+        if (stream < 0 || stream == s) reset_pending[s] = 1;
+}
+
+// grows a device buffer; a failed allocation is a capacity error of the call, not a runtime fault
+template <class B>
+static void grow(B& buf, size_t count, const char* what) {
+    if (count <= buf.n) return;
+    try {
+        buf.alloc(count);
+    } catch (const Error&) {
+        (void)hipGetLastError();
+        throw Error(AIC_ERR_CAPACITY, std::string("the device has no room for ") + what + " (" + std::to_string(count * sizeof(*buf.p) >> 20) + " MiB)");
+    }
+}
+
+void Scene::touch_device() {
+    if (!dev) dev = &device(device_id);
+    dev->use();
+    if (!d_scalars.p) {
+        const size_t n = (size_t)g.streams * cells();
+        grow(d_bg, n, "the background model");
+        grow(d_dev, n, "the background model");
+        grow(d_prev, n, "the background model");
+        grow(d_scalars, (size_t)g.streams * SC_S_INTS, "the stream scalars");
+        HIP_CHECK(hipMemsetAsync(d_bg.p, 0, d_bg.bytes(), dev->s_trk));
+        HIP_CHECK(hipMemsetAsync(d_dev.p, 0, d_dev.bytes(), dev->s_trk));
+        HIP_CHECK(hipMemsetAsync(d_prev.p, 0, d_prev.bytes(), dev->s_trk));
+        HIP_CHECK(hipMemsetAsync(d_scalars.p, 0, d_scalars.bytes(), dev->s_trk));
+    }
+}
+
+void Scene::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int32_t* records,
+                   uint8_t* masks, int32_t* row_motion) {
+    const int S = g.streams;
+    AIC_REQUIRE(ticks >= 0 && ticks <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
+    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
+    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
+    const long F = (long)ticks * S;
+    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
+    AIC_REQUIRE(F == 0 || (frames && records), AIC_ERR_INVALID, "NULL frames or records");
+    const bool with_rows = counts != nullptr && F > 0;
+    AIC_REQUIRE(counts || !row_motion, AIC_ERR_INVALID, "row_motion without counts");
+    auto check_counts = [&](const int32_t* c) {
+        long total = 0;
+        for (long f = 0; f < F; ++f) {
+            AIC_REQUIRE(c[f] >= 0, AIC_ERR_INVALID, "a negative row count");
+            AIC_REQUIRE(c[f] <= SC_ROWS_MAX, AIC_ERR_CAPACITY, "frame " + std::to_string(f) + " has more than 512 rows");
+            total += c[f];
+        }
+        AIC_REQUIRE(total == 0 || rows6, AIC_ERR_INVALID, "NULL rows");
+        AIC_REQUIRE(total == 0 || row_motion, AIC_ERR_INVALID, "rows without row_motion");
+        return total;
+    };
+    long total = 0;
+    if (with_rows && rows_mem == AIC_HOST) total = check_counts(counts);
+
+    touch_device();
+    if (F == 0) return;
+    hipStream_t st = dev->s_trk;
+    if (with_rows && rows_mem == AIC_DEVICE) {                               // the counts decide the launches: one small copy brings them over
+        h_counts.resize(F);
+        HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts, F * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        counts = h_counts.data();
+        total = check_counts(counts);
+    }
+    // ---- staging: reset[S] | frame_off[F + 1] | rows (host memory only)
+    const size_t o_off = S, o_rows = o_off + F + 1;
+    const size_t n_stage = o_rows + (with_rows && rows_mem == AIC_HOST ? (size_t)total * 6 : 0);
+    h_stage.ensure(n_stage);
+    grow(d_stage, n_stage, "the staged rows");
+    int* h = h_stage.p;
+    for (int s = 0; s < S; ++s) h[s] = reset_pending[s];
+    h[o_off] = 0;
+    for (long i = 0; i < F; ++i) h[o_off + i + 1] = h[o_off + i] + (with_rows ? counts[i] : 0);
+    if (with_rows && rows_mem == AIC_HOST && total) std::memcpy(h + o_rows, rows6, (size_t)total * 6 * sizeof(int));
+    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, n_stage * sizeof(int), hipMemcpyHostToDevice, st));
+    const int* d_rows = rows_mem == AIC_HOST ? d_stage.p + o_rows : rows6;
+    const int* d_off = d_stage.p + o_off;
+    grow(d_rec, (size_t)F * SC_RECORD_INTS, "the records");
+    grow(d_rm, std::max<size_t>(8, (size_t)total), "the row motion");
+
+    const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
+    const size_t tick_cells = cells() * S;
+    {
+        Prof pr(*dev, PROF_MISC, st, 0, (double)F * frame_bytes);
+        for (int lo = 0; lo < ticks;) {
+            int hi = lo + 1;                                                 // one tick at the least
+            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) && (size_t)(hi + 1 - lo) * tick_cells <= budget &&
+                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
+                ++hi;
+            const int n = hi - lo, n_frames = n * S;
+            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
+            if (frames_mem == AIC_HOST) {
+                grow(d_frames, (size_t)n * tick_bytes, "the staged frames");
+                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)n * tick_bytes, hipMemcpyHostToDevice, st));
+                d_fr = d_frames.p;
+            }
+            grow(d_gray, (size_t)n * tick_cells, "the gray grids");
+            grow(d_bits, (size_t)n * tick_cells, "the model bits");
+            grow(d_mask, (size_t)n * tick_cells, "the masks");
+            grow(d_acc, (size_t)n_frames * SC_A_INTS, "the tick sums");
+            HIP_CHECK(hipMemsetAsync(d_acc.p, 0, (size_t)n_frames * SC_A_INTS * sizeof(int), st));
+            launch_scene_gray(d_fr, n_frames, g, d_gray.p, st);
+            launch_scene_model(d_gray.p, n, g, o, d_scalars.p, d_stage.p, lo == 0, d_bg.p, d_dev.p, d_prev.p, d_bits.p, st);
+            launch_scene_stats(d_gray.p, d_bits.p, n_frames, g, o, d_mask.p, d_acc.p, st);
+            if (total) {
+                int max_rows = 0;
+                for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
+                launch_scene_rows(d_mask.p, d_off + (size_t)lo * S, n_frames, max_rows, d_rows, g, d_rm.p, st);
+            }
+            launch_scene_walk(d_acc.p, n, g, o, d_stage.p, lo == 0, d_scalars.p, d_rec.p + (size_t)lo * S * SC_RECORD_INTS, st);
+            if (masks) HIP_CHECK(hipMemcpyAsync(masks + (size_t)lo * tick_cells, d_mask.p, (size_t)n * tick_cells, hipMemcpyDeviceToHost, st));
+            lo = hi;
+        }
+    }
+    HIP_CHECK(hipMemcpyAsync(records, d_rec.p, (size_t)F * SC_RECORD_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (total) HIP_CHECK(hipMemcpyAsync(row_motion, d_rm.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::fill(reset_pending.begin(), reset_pending.end(), (char)0);
+}
+
+void Scene::export_stream(int stream, int32_t* bg, int32_t* dv, int32_t* prev, int32_t* scalars) {
+    AIC_REQUIRE(stream >= 0 && stream < g.streams, AIC_ERR_INVALID, "stream outside the scene bank");
+    AIC_REQUIRE(bg && dv && prev && scalars, AIC_ERR_INVALID, "NULL argument");
+    const size_t n = cells();
+    std::fill(bg, bg + n, 0), std::fill(dv, dv + n, 0), std::fill(prev, prev + n, 0), std::fill(scalars, scalars + SC_S_INTS, 0);
+    if (!d_scalars.p || reset_pending[stream]) return;                       // nothing seen yet, or a reset the next call applies
+    dev->use();
+    hipStream_t st = dev->s_trk;
+    std::vector<uint16_t> hb(n), hd(n);
+    std::vector<uint8_t> hp(n);
+    HIP_CHECK(hipMemcpyAsync(hb.data(), d_bg.p + stream * n, n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hd.data(), d_dev.p + stream * n, n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hp.data(), d_prev.p + stream * n, n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(scalars, d_scalars.p + (size_t)stream * SC_S_INTS, SC_S_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::copy(hb.begin(), hb.end(), bg), std::copy(hd.begin(), hd.end(), dv), std::copy(hp.begin(), hp.end(), prev);
+}
+
+}  // namespace aic
+
+using namespace aic;
+
+extern "C" {
+
+int aic_scene_config_default(int streams, int frame_h, int frame_w, aic_scene_config* out) {
+    return guarded([&] {
+        AIC_REQUIRE(out, AIC_ERR_INVALID, "NULL argument");
+        *out = aic_scene_config{streams, frame_h, frame_w, 8};
+    });
+}
+
+int aic_scene_create(int device, const aic_scene_config* config, aic_scene** out) {
+    return guarded([&] {
+        AIC_REQUIRE(out, AIC_ERR_INVALID, "NULL argument");
+        scene_check_config(device, config);
+        *out = new aic_scene(device, *config);
+    });
+}
+
+int aic_scene_destroy(aic_scene* s) {
+    return guarded([&] {
+        if (s && s->s.dev) { s->s.dev->use(); (void)hipStreamSynchronize(s->s.dev->s_trk); }
+        delete s;
+    });
+}
+
+int aic_scene_option(aic_scene* s, const char* key, int value) {
+    return guarded([&] {
+        AIC_REQUIRE(s && key, AIC_ERR_INVALID, "NULL argument");
+        s->s.option(key, value);
+    });
+}
+
+int aic_scene_reset(aic_scene* s, int stream) {
+    return guarded([&] {
+        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
+        s->s.reset(stream);
+    });
+}
+
+int aic_scene_update(aic_scene* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
+                     int rows_mem, int32_t* records, uint8_t* masks, int32_t* row_motion) {
+    return guarded([&] {
+        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
+        s->s.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, records, masks, row_motion);
+    });
+}
+
+int aic_scene_export(aic_scene* s, int stream, int32_t* bg, int32_t* dev, int32_t* prev, int32_t* scalars) {
+    return guarded([&] {
+        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
+        s->s.export_stream(stream, bg, dev, prev, scalars);
+    });
+}
+
+}  // extern "C"

@@ -303,15 +303,43 @@ class TrackingPipeline:
         if b is None:
             return
         S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.best_shot_result = b.update(self._host_bgr(slot, count, host_frames),
+                                         [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
+                                         cap=self.best_shot_cap)
+
+    def _host_bgr(self, slot, count, host_frames):
+        """The BGR frames of a run call on the host, [ticks, streams, H, W, 3]: the array a *_from_host call was handed (a YUV format
+        converted with frames.to_bgr), else the ring read back."""
         if host_frames is None:
             bgr = self.read_frames(slot, count)
         elif self._pix[0] != L.PIX_BGR24:
             bgr = frames.to_bgr(host_frames, self._pix[0], matrix=self._pix[1], range=self._pix[2], device=config.resolve_device(self._device))
         else:
             bgr = host_frames
-        self.best_shot_result = b.update(bgr.reshape(count // S, S, self.frame_h, self.frame_w, 3),
-                                         [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
-                                         cap=self.best_shot_cap)
+        return bgr.reshape(count // self.streams, self.streams, self.frame_h, self.frame_w, 3)
+
+    _scene_watch = scene_result = None
+
+    def attach_scene_watch(self, scene_watch):
+        """A SceneWatch (scene.py) of `.streams` streams for this frame size: after every run* call the call's frames and tracks -- all
+        ticks, all streams, ONE scene_watch.update -- go through it and scene_result is that call's SceneResult (records, row_motion
+        per track row; no masks).  Frames and rows reach the stage from the host side, exactly as for attach_best_shots; with *_passes
+        it sees the last pass only.  The tracks returned are untouched, and the detector still runs on idle cameras: `.active` is what
+        a later change will read.  None detaches."""
+        w = scene_watch
+        if w is not None and (w.streams != self.streams or (w.frame_h, w.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"a scene watch of {w.streams} streams of {w.frame_h}x{w.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._scene_watch, self.scene_result = w, None
+
+    def _feed_scene(self, nt, rows, slot=0, host_frames=None):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major; host_frames: what a *_from_host call was handed."""
+        w = self._scene_watch
+        if w is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.scene_result = w.update(self._host_bgr(slot, count, host_frames),
+                                     [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)])
 
     def close(self):
         for b in getattr(self, "_staging", []):
@@ -373,6 +401,7 @@ class TrackingPipeline:
                L.ptr(db), L.ptr(ds), L.ptr(dl))
         self._feed_zones(nt, rows)
         self._feed_best_shots(nt, rows, slot)
+        self._feed_scene(nt, rows, slot)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -394,6 +423,7 @@ class TrackingPipeline:
                None, None, None)
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot)
+        self._feed_scene(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
@@ -402,6 +432,7 @@ class TrackingPipeline:
         L.call("aic_pipeline_run_passes", self._h, int(slot), int(count), int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot)
+        self._feed_scene(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -420,6 +451,7 @@ class TrackingPipeline:
         L.call("aic_pipeline_run_from_host", self._h, L.ptr(f), int(slot), count, L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
+        self._feed_scene(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -431,6 +463,7 @@ class TrackingPipeline:
         L.call("aic_pipeline_run_from_host_passes", self._h, L.ptr(f), int(slot), count, int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
+        self._feed_scene(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

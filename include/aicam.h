@@ -922,6 +922,41 @@ int aic_bestshot_export(aic_bestshot* b, int stream, int32_t* n, int32_t* events
 /* After option "stats" 1 (0 = default): since creation, the rows handed to update, the candidates among them that were scored, and the
  * candidate thumbnails the could-still-win filter let through to the per-row buffer.  Any pointer may be NULL.  Host only. */
 int aic_bestshot_counters(aic_bestshot* b, int64_t* rows, int64_t* candidates, int64_t* stored);
+/* ---- scene watch: motion masks, an activity gate and tamper alarms per camera (csrc/scene.hpp) ----------------
+ * A tracker-agnostic stage that looks at frames as scenes, for `streams` (1..256) cameras of one frame size per call.  Every u8 BGR
+ * frame is reduced to a gray grid of cells of `cell` x `cell` pixels (cell 4, 8 or 16; the grid is frame_h / cell x frame_w / cell,
+ * both >= 1, remainder rows and columns are not read); a per-cell background model (bg, dev in Q8, prev) marks the raw cells, a 3 x 3
+ * vote cleans them, and per-stream counters turn the tick's statistics into the activity gate and five alarms.
+ * tests/scene_oracle.py is the specification -- the order of a tick, every shift and threshold -- and the device equals it bit for bit.
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option and reset never touch it.  Device buffers are
+ * allocated by the first call that reaches the device; an allocation that does not fit fails that call with AIC_ERR_CAPACITY.
+ * update: `ticks` (0..65536) ticks; frames [ticks, streams, h, w, 3] tick-major in host or device memory (frames_mem), a device pointer
+ * of any alignment.  counts (may be NULL: no rows) [ticks * streams] and rows6 [sum of counts, 6] = x1 y1 x2 y2 id cls in the same order,
+ * both in host or both in device memory (rows_mem); a frame of more than 512 rows rejects the call with AIC_ERR_CAPACITY before anything
+ * is staged.  Outputs (host): records [ticks, streams, 16] = frame, ready, active, n_moving, n_raw, x0, y0, x1, y1 (the clean cells' box
+ * in pixels, x1 y1 exclusive, all -1 = none), mean_luma, sharp, ref_q8, n_changed, cond, alarms, edges (raised bits | cleared bits << 8;
+ * bit 0 DARK, 1 BRIGHT, 2 DEFOCUS, 3 SCENE, 4 FROZEN); masks (may be NULL) [ticks, streams, grid_h, grid_w] u8, bit 0 clean, bit 1 raw;
+ * row_motion (may be NULL) [sum of counts] = 256 * moving / covered cells of the row's box, -1 for an invalid or empty box.
+ * reset: stream, or -1 = every stream, starts again at age 0.  export: bg, dev, prev as int32 [grid_h, grid_w] and scalars[16] = age,
+ * quiet, ref_q8, alarms, on[5], off[5], 0, 0; changes nothing; all zeros for a stream that has seen no tick since create / reset.
+ * option: thresh 0..255, noise_k_q4 0..4096, warmup 1..2^20, big_thresh 0..255, learn_shift 1..12, slow_extra 0..8 (their sum <= 14),
+ * dev_init_q8 0..65280, min_neighbours 1..9, dark_luma 0..256, bright_luma 0..255, min_ref_q8 0..2^20, defocus_q8 0..256, scene_q16
+ * 0..65536, ref_shift 1..12, hold 1..2^20, gate_cells 1..2^24, gate_hold 0..2^20 (defaults: DESIGN.md section 39); none of them sizes a
+ * buffer, so they may change between calls.  "ticks_per_launch": 0 (default) = as many ticks per launch as the budget allows, k = at
+ * most k; "launch_budget_mb" (1..65536, default 1024): the gray grids and the staged frames of one launch each stay below it, one tick
+ * at the least.  Same results. */
+typedef struct aic_scene aic_scene;
+typedef struct {
+    int32_t streams, frame_h, frame_w, cell;
+} aic_scene_config;
+int aic_scene_config_default(int streams, int frame_h, int frame_w, aic_scene_config* out);
+int aic_scene_create(int device, const aic_scene_config* config, aic_scene** out);
+int aic_scene_destroy(aic_scene* s);
+int aic_scene_option(aic_scene* s, const char* key, int value);
+int aic_scene_reset(aic_scene* s, int stream);
+int aic_scene_update(aic_scene* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
+                     int rows_mem, int32_t* records, uint8_t* masks, int32_t* row_motion);
+int aic_scene_export(aic_scene* s, int stream, int32_t* bg, int32_t* dev, int32_t* prev, int32_t* scalars);
 /* ---- 4:2:0 YUV frames in, NV12 out: pixel-format conversion of a bank of frames in one launch (csrc/yuv.hpp) -------
  * Decoders, RTSP stacks and camera SDKs deliver NV12 (sometimes I420) on pitched surfaces and encoders want the same back; everything else
  * in this library reads packed BGR24.  tests/yuv_oracle.py is the specification and the device equals it bit for bit in both directions:
