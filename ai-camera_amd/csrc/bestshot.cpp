@@ -1,6 +1,7 @@
 // bestshot.cpp -- the best-shot object (bestshot.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_bestshot.hip or the call raises.
 #include "bestshot.hpp"
+#include "row_stage.hpp"
 
 #include <algorithm>
 
@@ -33,18 +34,6 @@ void BestShot::reset(int stream) {
     reset_pending[stream] = 1;
 }
 
-// grows a device buffer; a failed allocation is a capacity error of the call, not a runtime fault
-template <class B>
-static void grow(B& buf, size_t count, const char* what) {
-    if (count <= buf.n) return;
-    try {
-        buf.alloc(count);
-    } catch (const Error&) {
-        (void)hipGetLastError();
-        throw Error(AIC_ERR_CAPACITY, std::string("the device has no room for ") + what + " (" + std::to_string(count * sizeof(*buf.p) >> 20) + " MiB)");
-    }
-}
-
 void BestShot::touch_device() {
     if (!dev) dev = &device(device_id);
     dev->use();
@@ -75,13 +64,7 @@ void BestShot::update(const void* frames, int frames_mem, int ticks, const int32
     AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
     AIC_REQUIRE(F == 0 || (frames && counts), AIC_ERR_INVALID, "NULL frames or counts");
     auto check_counts = [&](const int32_t* c) {
-        long total = 0;
-        for (long f = 0; f < F; ++f) {
-            AIC_REQUIRE(c[f] >= 0, AIC_ERR_INVALID, "a negative row count");
-            AIC_REQUIRE(c[f] <= BS_ROWS_MAX, AIC_ERR_CAPACITY, "frame " + std::to_string(f) + " has more than 512 rows");
-            total += c[f];
-        }
-        AIC_REQUIRE(total == 0 || rows6, AIC_ERR_INVALID, "NULL rows");
+        const long total = check_row_counts(c, F, BS_ROWS_MAX, rows6);
         AIC_REQUIRE(total <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
         return total;
     };
@@ -90,25 +73,17 @@ void BestShot::update(const void* frames, int frames_mem, int ticks, const int32
 
     touch_device();
     hipStream_t st = dev->s_trk;
-    if (rows_mem == AIC_DEVICE && F) {                                       // the counts decide the launches: one small copy brings them over
-        h_counts.resize(F);
-        HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts, F * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        counts = h_counts.data();
-        total = check_counts(counts);
-    }
-    // ---- staging: reset[S] | mode[S] | frame_off[F + 1] | rows (host memory only)
-    const size_t o_mode = S, o_off = 2 * (size_t)S, o_rows = o_off + F + 1;
-    const size_t n_stage = o_rows + (rows_mem == AIC_HOST ? (size_t)total * 6 : 0);
-    h_stage.ensure(n_stage);
-    grow(d_stage, n_stage, "the staged rows");
+    if (rows_mem == AIC_DEVICE && F) total = check_counts(counts = fetch_counts(h_counts, counts, F, st));   // the counts decide the launches
+    // ---- staging: reset[S] | mode[S] | frame_off[F + 1] | rows (host memory only; row_stage.hpp)
+    const size_t o_mode = S, o_off = 2 * (size_t)S;
+    const RowStage rs(o_off, o_off + F + 1, total, rows_mem == AIC_HOST);
+    h_stage.ensure(rs.n_ints);
+    grow(d_stage, rs.n_ints, "the staged rows");
     int* h = h_stage.p;
     for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[o_mode + s] = BS_MODE_DRAIN;
-    h[o_off] = 0;
-    for (long i = 0; i < F; ++i) h[o_off + i + 1] = h[o_off + i] + counts[i];
-    if (rows_mem == AIC_HOST && total) std::memcpy(h + o_rows, rows6, (size_t)total * 6 * sizeof(int));
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, n_stage * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* d_rows = rows_mem == AIC_HOST ? d_stage.p + o_rows : rows6;
+    rs.fill(h, counts, F, rows6);
+    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
+    const int* d_rows = rs.d_rows(d_stage.p, rows6);
     const int* d_off = d_stage.p + o_off;
     grow(d_info, std::max<size_t>(8, (size_t)total * 8), "the scored rows");
     const size_t o_ev = out_events_at(S);

@@ -120,23 +120,33 @@ void DeepSortBank::size_scratch(const BankPlan& pl) {
     d_sm.ensure(sm_stride * S), d_gram.ensure(gram_stride * S), d_cost.ensure(cost_stride * S), d_sub.ensure(sub_stride * S);
 }
 
-void DeepSortBank::launch_epochs(const BankPlan& pl, const EpochStreamPlan* d_plan, const int* d_map, const int* d_e0, const int* d_f0,
-                                 const int* d_k, const EpochDets& dets, const EpochOut& out, hipStream_t s) {
+// the plan block of a call (DeepSortPlanBlock, epoch_stage.hpp) into the start of its staging buffer
+static void fill_plan(char* h, const DeepSortPlanBlock& b, const BankPlan& pl) {
+    std::memcpy(h, pl.plans.data(), b.o_map);
+    if (!pl.row_map.empty()) std::memcpy(h + b.o_map, pl.row_map.data(), pl.row_map.size() * 4);
+    std::memcpy(h + b.o_e0, pl.e0.data(), pl.e0.size() * 4);
+    std::memcpy(h + b.o_f0, pl.stream_f0.data(), pl.stream_f0.size() * 4);
+    std::memcpy(h + b.o_k, pl.stream_k.data(), pl.stream_k.size() * 4);
+}
+
+void DeepSortBank::launch_epochs(const BankPlan& pl, const char* d_base, const DeepSortPlanBlock& b, const EpochDets& dets, const EpochOut& out,
+                                 hipStream_t s) {
     const int S = n_streams;
+    auto ints = [&](size_t o) { return reinterpret_cast<const int*>(d_base + o); };
     EpochBankArgs bk{};
     bk.tbl = d_tbl.p, bk.tbl_stride = tbl_stride;
     bk.mean_stride = (size_t)cap * 8, bk.cov_stride = (size_t)cap * 64, bk.gal_stride = gal_stride;
     bk.sm_stride = sm_stride, bk.gram_stride = gram_stride, bk.cost_stride = cost_stride, bk.sub_stride = sub_stride;
-    bk.stream_f0 = d_f0, bk.stream_k = d_k;
+    bk.stream_f0 = ints(b.o_f0), bk.stream_k = ints(b.o_k);
     bk.frame_stride = pl.frame_stride;
-    bk.row_map = d_map;
-    bk.frame_e0 = d_e0;
+    bk.row_map = ints(b.o_map);
+    bk.frame_e0 = ints(b.o_e0);
     TrkDevParams p = prm;
     p.no_fast = lsap_fast ? 0 : 1, p.no_wave = wave_cascade ? 0 : 1;
     const EpochScratch scr{d_sm.p, d_gram.p, d_cost.p, d_sub.p, d_appends.p};
     for (size_t e = 0; e < pl.epochs.size(); ++e) {
         const BankPlan::Epoch& ep = pl.epochs[e];
-        bk.plan = d_plan + e * S;
+        bk.plan = reinterpret_cast<const EpochStreamPlan*>(d_base) + e * S;
         if (ep.dn_pad_max > 0) {
             Prof pr(*dev, PROF_TRK, s, 0, 0);
             launch_trk_epoch_prep_bank(bk, S, d_gal_n.p, gmax, dim, cap, dets.feat_n, ep.dn_pad_max, ep.f0, ep.k, d_sm.p, d_gram.p, s);
@@ -174,24 +184,16 @@ void DeepSortBank::run_group(const EpochDets& dets, const int* h_n, const int* h
     pl.row_map.reserve(n);
     // the crop validity lives in HBM: a stream's SM / GRAM are built whenever it has rows (Tracker::run_epochs)
     plan_epochs(pl, h_n, h_d0, dets.feat_n != nullptr, nullptr);
-    const size_t E = pl.epochs.size(), k = (size_t)frames;
-    auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-    const size_t o_map = E * S * sizeof(EpochStreamPlan), o_e0 = o_map + n * 4, o_f0 = up(o_e0 + k * 4), o_k = o_f0 + (size_t)S * 4;
-    const size_t o_hdr = up(o_k + (size_t)S * 4), bytes = o_hdr + (size_t)S * sizeof(DevTrkHdr);
+    StageCursor c; const DeepSortPlanBlock b(c, pl.epochs.size(), S, (size_t)frames, n);
+    const size_t o_hdr = c.take((size_t)S * sizeof(DevTrkHdr), true), bytes = c.at;
     if (bytes > h_grp.n) {                                         // (the caller synced s behind the previous group)
         HIP_CHECK(hipStreamSynchronize(s));
         h_grp.alloc(bytes + bytes / 4), d_grp.alloc(bytes + bytes / 4);
     }
     size_scratch(pl);
-    std::memcpy(h_grp.p, pl.plans.data(), o_map);
-    if (n) std::memcpy(h_grp.p + o_map, pl.row_map.data(), n * 4);
-    std::memcpy(h_grp.p + o_e0, pl.e0.data(), k * 4);
-    std::memcpy(h_grp.p + o_f0, pl.stream_f0.data(), (size_t)S * 4);
-    std::memcpy(h_grp.p + o_k, pl.stream_k.data(), (size_t)S * 4);
+    fill_plan(h_grp.p, b, pl);
     HIP_CHECK(hipMemcpyAsync(d_grp.p, h_grp.p, o_hdr, hipMemcpyHostToDevice, s));
-    launch_epochs(pl, reinterpret_cast<const EpochStreamPlan*>(d_grp.p), reinterpret_cast<const int*>(d_grp.p + o_map),
-                  reinterpret_cast<const int*>(d_grp.p + o_e0), reinterpret_cast<const int*>(d_grp.p + o_f0),
-                  reinterpret_cast<const int*>(d_grp.p + o_k), dets, out, s);
+    launch_epochs(pl, d_grp.p, b, dets, out, s);
     HIP_CHECK(hipMemcpy2DAsync(d_grp.p + o_hdr, sizeof(DevTrkHdr), d_tbl.p, tbl_stride, sizeof(DevTrkHdr), S, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(h_grp.p + o_hdr, d_grp.p + o_hdr, (size_t)S * sizeof(DevTrkHdr), hipMemcpyDeviceToHost, s));
     grp_hdr = o_hdr;
@@ -216,114 +218,57 @@ void DeepSortBank::update(const int32_t* frames_per_stream, const int32_t* count
     dev->use();
     AIC_REQUIRE(cap_rows >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
     const int S = n_streams;
-    long F = 0;
-    int kmax_s = 0;
-    for (int q = 0; q < S; ++q) {
-        AIC_REQUIRE(frames_per_stream[q] >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
-        F += frames_per_stream[q];
-        kmax_s = std::max(kmax_s, (int)frames_per_stream[q]);
-    }
-    AIC_REQUIRE(F <= (1 << 24), AIC_ERR_INVALID, "too many frames in one call");
-    long total = 0;
-    int nmax_call = 1;
-    for (long f = 0; f < F; ++f) {
-        AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative detection count");
-        AIC_REQUIRE(counts[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "DeepSORT bank: more than 512 detections in one frame");
-        total += counts[f];
-        nmax_call = std::max(nmax_call, (int)counts[f]);
-    }
-    AIC_REQUIRE(total < (1l << 30), AIC_ERR_INVALID, "too many detections in one call");
-    AIC_REQUIRE(total == 0 || (det_tlwh && conf && cls), AIC_ERR_INVALID, "NULL detection arrays");
+    const CallShape sh = check_call("DeepSORT bank", S, frames_per_stream, counts, det_tlwh && conf && cls, 1l << 30);
+    AIC_REQUIRE(sh.err.empty(), sh.capacity ? AIC_ERR_CAPACITY : AIC_ERR_INVALID, sh.err);
     if (status) std::copy(stop_code.begin(), stop_code.end(), status);
     const std::vector<int> before = stop_code;
     int bad = -1;
-    if (F > 0) {
+    if (sh.F > 0) {
         hipStream_t s = dev->s_trk;
-        const size_t k = (size_t)F, n = (size_t)total;
+        const size_t k = (size_t)sh.F, n = (size_t)sh.total;
         const bool feats = feat != nullptr && n > 0;
 
         // ---- the call's epochs (plan_epochs: shared with run_group)
         BankPlan pl;
         pl.stream_f0.resize(S), pl.stream_k.assign(frames_per_stream, frames_per_stream + S);
         for (int q = 0, f = 0; q < S; ++q) { pl.stream_f0[q] = f; f += frames_per_stream[q]; }
-        pl.frame_stride = 1, pl.kmax_s = kmax_s, pl.nmax_call = nmax_call;
+        pl.frame_stride = 1, pl.kmax_s = sh.kmax_s, pl.nmax_call = std::max(1, sh.nmax);
         std::vector<int> d0(k);
         { int d = 0; for (size_t f = 0; f < k; ++f) { d0[f] = d; d += counts[f]; } }
         pl.e0.resize(k);
         pl.row_map.reserve(n);
         plan_epochs(pl, counts, d0.data(), feats, valid);
-        const std::vector<int>& f0s = pl.stream_f0;
-        const std::vector<int>& e0 = pl.e0;
-        const std::vector<int>& row_map = pl.row_map;
-        const std::vector<EpochStreamPlan>& plans = pl.plans;
-        const size_t E = pl.epochs.size();
 
-        // ---- staging (host == device layout):
-        //   plan[E*S] | row_map[n] | frame_e0[F] | stream_f0[S] | stream_k[S] | frame_n[F] | frame_d0[F] | tlwh[n*4] | conf[n] | cls[n] | valid[n] | feat[n*dim]
-        //   || n_tracks[F] | rows[F*cap*6] | conf[F*cap] | headers[S]        and, device only, feat_n[n*dim] behind them
-        auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-        const size_t o_map = E * S * sizeof(EpochStreamPlan), o_e0 = o_map + n * 4, o_f0 = up(o_e0 + k * 4), o_k = o_f0 + (size_t)S * 4, o_n = up(o_k + (size_t)S * 4);
-        const size_t o_d0 = o_n + k * 4, o_tlwh = up(o_d0 + k * 4), o_conf = o_tlwh + n * 16, o_cls = o_conf + n * 4, o_valid = o_cls + n * 4;
-        const size_t o_feat = up(o_valid + n * 4), feat_bytes = feats ? n * (size_t)dim * 4 : 0;
-        const size_t o_out = up(o_feat + feat_bytes);
-        const size_t o_rows = o_out + up(k * 4), o_oconf = o_rows + k * cap_rows * 24, o_hdr = up(o_oconf + k * cap_rows * 4);
-        const size_t bytes = o_hdr + (size_t)S * sizeof(DevTrkHdr), o_featn = up(bytes);
+        // ---- the one staging layout (epoch_stage.hpp); this caller's own: the plan block in front, feat behind valid, the headers behind the outputs
+        StageCursor c; const DeepSortPlanBlock pb(c, pl.epochs.size(), S, k, n);
+        const CallStage L = deepsort_stage(c, S, k, n, cap_rows, feats, dim);
         HIP_CHECK(hipStreamSynchronize(s));
-        h_api.ensure(bytes);
-        d_api.ensure(o_featn + feat_bytes);
+        h_api.ensure(L.bytes);
+        d_api.ensure(L.o_featn + L.feat_bytes);
         size_scratch(pl);
-
-        std::memcpy(h_api.p, plans.data(), o_map);
-        if (n) std::memcpy(h_api.p + o_map, row_map.data(), n * 4);
-        std::memcpy(h_api.p + o_e0, e0.data(), k * 4);
-        int* hf0 = reinterpret_cast<int*>(h_api.p + o_f0);
-        int* hk = reinterpret_cast<int*>(h_api.p + o_k);
-        for (int q = 0; q < S; ++q) hf0[q] = f0s[q], hk[q] = frames_per_stream[q];
-        std::memcpy(h_api.p + o_n, counts, k * 4);
-        std::memcpy(h_api.p + o_d0, d0.data(), k * 4);
-        if (n) {
-            std::memcpy(h_api.p + o_tlwh, det_tlwh, n * 16);
-            std::memcpy(h_api.p + o_conf, conf, n * 4);
-            std::memcpy(h_api.p + o_cls, cls, n * 4);
-            int* hv = reinterpret_cast<int*>(h_api.p + o_valid);
-            for (size_t j = 0; j < n; ++j) hv[j] = (feats && (!valid || valid[j])) ? 1 : 0;
-            if (feats) std::memcpy(h_api.p + o_feat, feat, feat_bytes);
-        }
-        HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
-        EpochDets dets{reinterpret_cast<const int*>(d_api.p + o_n), reinterpret_cast<const int*>(d_api.p + o_d0),
-                       reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
-                       reinterpret_cast<const int*>(d_api.p + o_cls), reinterpret_cast<const int*>(d_api.p + o_valid), nullptr, nullptr};
+        fill_plan(h_api.p, pb, pl);
+        L.det.fill(h_api.p, counts, det_tlwh, false, conf, cls);
+        L.det.fill_valid(h_api.p, feats, valid);
+        if (feats) std::memcpy(h_api.p + L.o_feat, feat, L.feat_bytes);
+        HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, L.out.o_out, hipMemcpyHostToDevice, s));
+        EpochDets dets = L.det.dets(d_api.p);
         if (feats) {
-            float* fn = reinterpret_cast<float*>(d_api.p + o_featn);
-            dets.feat = reinterpret_cast<const float*>(d_api.p + o_feat);
+            float* fn = reinterpret_cast<float*>(d_api.p + L.o_featn);
+            dets.feat = reinterpret_cast<const float*>(d_api.p + L.o_feat);
             launch_normalize_rows(dets.feat, fn, (int)n, dim, s);  // once over all rows of the call
             dets.feat_n = fn;
         }
-        EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows), reinterpret_cast<float*>(d_api.p + o_oconf),
-                     cap_rows, nullptr, nullptr, 0};
-        launch_epochs(pl, reinterpret_cast<const EpochStreamPlan*>(d_api.p), reinterpret_cast<const int*>(d_api.p + o_map),
-                      reinterpret_cast<const int*>(d_api.p + o_e0), reinterpret_cast<const int*>(d_api.p + o_f0),
-                      reinterpret_cast<const int*>(d_api.p + o_k), dets, out, s);
-        HIP_CHECK(hipMemcpy2DAsync(d_api.p + o_hdr, sizeof(DevTrkHdr), d_tbl.p, tbl_stride, sizeof(DevTrkHdr), S, hipMemcpyDeviceToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
+        launch_epochs(pl, d_api.p, pb, dets, L.out.out(d_api.p), s);
+        HIP_CHECK(hipMemcpy2DAsync(d_api.p + L.o_tail, sizeof(DevTrkHdr), d_tbl.p, tbl_stride, sizeof(DevTrkHdr), S, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(h_api.p + L.out.o_out, d_api.p + L.out.o_out, L.bytes - L.out.o_out, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        const DevTrkHdr* hh = reinterpret_cast<const DevTrkHdr*>(h_api.p + o_hdr);
+        const DevTrkHdr* hh = reinterpret_cast<const DevTrkHdr*>(h_api.p + L.o_tail);
         note_stops(hh);
-        const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
-        const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
-        const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
-        for (int q = 0, f = 0; q < S; ++q) {
-            // a stream stopped before the call delivers nothing; one that stopped in it, the frames before the failing one
-            const int good = before[q] ? 0 : stop_code[q] ? hh[q].err_frame : frames_per_stream[q];
-            for (int i = 0; i < frames_per_stream[q]; ++i, ++f) {
-                const int m = i < good ? on[f] : 0;
-                const int kk = std::min(m, cap_rows);
-                if (n_out) n_out[f] = m;                          // the true count: rows beyond cap_rows are not stored
-                if (out6) std::copy(rows + (size_t)f * cap_rows * 6, rows + ((size_t)f * cap_rows + kk) * 6, out6 + (size_t)f * cap_rows * 6);
-                if (out_conf) std::copy(oc + (size_t)f * cap_rows, oc + (size_t)f * cap_rows + kk, out_conf + (size_t)f * cap_rows);
-            }
-            if (bad < 0 && stop_code[q] && frames_per_stream[q] > 0) bad = q;
-        }
+        // a stream stopped before the call delivers nothing; one that stopped in it, the frames before the failing one
+        auto good = [&](int q, int i) { return i < (before[q] ? 0 : stop_code[q] ? hh[q].err_frame : frames_per_stream[q]); };
+        deliver(L.out.host(h_api.p), cap_rows, S, frames_per_stream, good, n_out, out6, out_conf);
+        for (int q = S - 1; q >= 0; --q)
+            if (stop_code[q] && frames_per_stream[q] > 0) bad = q;
     }
     if (status) std::copy(stop_code.begin(), stop_code.end(), status);
     else AIC_REQUIRE(bad < 0, stop_code[bad], "DeepSORT bank: " + stop_msg[bad]);

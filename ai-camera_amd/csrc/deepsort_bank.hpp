@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "epoch_stage.hpp"
 #include "kernels.hpp"
 #include "trk_dev.hpp"
 
@@ -89,9 +90,9 @@ struct DeepSortBank {
     // rows of the epoch stay within TRK_DEV_DNMAX.  valid (host, may be NULL = all): a stream's SM / GRAM are built when it has a valid row
     void plan_epochs(BankPlan& pl, const int32_t* counts, const int* d0, bool feats, const int32_t* valid) const;
     void size_scratch(const BankPlan& pl);
-    // prep + epoch + commit of every epoch; d_plan / d_map / d_e0 / d_f0 / d_k: the uploaded plan
-    void launch_epochs(const BankPlan& pl, const EpochStreamPlan* d_plan, const int* d_map, const int* d_e0, const int* d_f0, const int* d_k,
-                       const EpochDets& dets, const EpochOut& out, hipStream_t s);
+    // prep + epoch + commit of every epoch; the uploaded plan lies at d_base as b says
+    void launch_epochs(const BankPlan& pl, const char* d_base, const DeepSortPlanBlock& b, const EpochDets& dets, const EpochOut& out,
+                       hipStream_t s);
     void note_stops(const DevTrkHdr* hh);
     std::vector<char> fetch_table(int s);
     int export_state(int stream, int cap_rows, int32_t* id, int32_t* state, int32_t* hits, int32_t* age, int32_t* tsu, int32_t* cls,

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "epoch_stage.hpp"
 #include "epoch_tracker.hpp"
 
 namespace aic {
@@ -154,96 +155,41 @@ struct EpochBank : EpochTracker {
         dev->use();
         AIC_REQUIRE(cap_rows >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
         const int S = n_streams;
-        long F = 0;
-        int kmax_s = 0;
-        for (int q = 0; q < S; ++q) {
-            AIC_REQUIRE(frames_per_stream[q] >= 0, AIC_ERR_INVALID, "negative frame count / row capacity");
-            F += frames_per_stream[q];
-            kmax_s = std::max(kmax_s, (int)frames_per_stream[q]);
-        }
-        AIC_REQUIRE(F <= (1 << 24), AIC_ERR_INVALID, "too many frames in one call");
-        long total = 0;
-        for (long f = 0; f < F; ++f) {
-            AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "negative detection count");
-            AIC_REQUIRE(counts[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, std::string(name()) + ": more than 512 detections in one frame");
-            total += counts[f];
-        }
-        AIC_REQUIRE(total == 0 || (xyxy && conf && cls), AIC_ERR_INVALID, "NULL detection arrays");
+        const CallShape sh = check_call(name(), S, frames_per_stream, counts, xyxy && conf && cls);
+        AIC_REQUIRE(sh.err.empty(), sh.capacity ? AIC_ERR_CAPACITY : AIC_ERR_INVALID, sh.err);
         if (status) std::copy(stop_code.begin(), stop_code.end(), status);
         const std::vector<int> before = stop_code;
         int bad = -1;
-        if (F > 0) {
+        if (sh.F > 0) {
             hipStream_t s = dev->s_trk;
-            const size_t k = (size_t)F, n = (size_t)total;
-            auto up = [](size_t x) { return (x + 15) / 16 * 16; };
-            // staging (host == device layout): stream_f0[S] | stream_k[S] | frame_n[F] | frame_d0[F] | tlwh[n*4] | conf[n] | cls[n]
-            //                                  || n_tracks[F] | rows[F*cap*6] | conf[F*cap]
-            // with a BankExtra, between cls and ||: valid[n] | warps[F*6] | feat[n*dim], and, device only, feat_n[n*dim] behind the outputs
-            const size_t o_n = up((size_t)S * 8), o_d0 = o_n + k * 4, o_tlwh = up(o_d0 + k * 4), o_conf = o_tlwh + n * 16, o_cls = o_conf + n * 4;
-            size_t in_end = o_cls + n * 4, o_valid = 0, o_warp = 0, o_feat = 0, feat_bytes = 0;
-            if (x) {
-                if (x->valid) o_valid = in_end, in_end += n * 4;
-                if (x->warps6) o_warp = up(in_end), in_end = o_warp + k * 24;
-                if (x->feat && n) o_feat = up(in_end), feat_bytes = n * (size_t)x->dim * 4, in_end = o_feat + feat_bytes;
-            }
-            const size_t o_out = up(in_end);
-            const size_t o_rows = o_out + up(k * 4), o_oconf = o_rows + k * cap_rows * 24;
-            const size_t bytes = o_oconf + k * cap_rows * 4;
-            const size_t o_featn = up(bytes);
+            const size_t n = (size_t)sh.total;
+            // the one staging layout (epoch_stage.hpp); this caller's own: the stream plan in front, the BankExtra fields around the outputs
+            const CallStage L = bank_stage(S, (size_t)sh.F, n, cap_rows, x && x->valid, x && x->warps6, x && x->feat, x ? x->dim : 0);
             HIP_CHECK(hipStreamSynchronize(s));
-            h_api.ensure(bytes);
-            d_api.ensure(x ? o_featn + feat_bytes : bytes);
+            h_api.ensure(L.bytes);
+            d_api.ensure(x ? L.o_featn + L.feat_bytes : L.bytes);
             int* hp = reinterpret_cast<int*>(h_api.p);
             for (int q = 0, f = 0; q < S; ++q) { hp[q] = f; hp[S + q] = frames_per_stream[q]; f += frames_per_stream[q]; }
-            int* hn = reinterpret_cast<int*>(h_api.p + o_n);
-            int* hd = reinterpret_cast<int*>(h_api.p + o_d0);
-            int d0 = 0;
-            for (size_t f = 0; f < k; ++f) { hn[f] = counts[f]; hd[f] = d0; d0 += counts[f]; }
-            float* ht = reinterpret_cast<float*>(h_api.p + o_tlwh);
-            for (size_t j = 0; j < n; ++j) {                      // xyxy -> tlwh, fp32: the detection format of every tracker here
-                const float* b = xyxy + j * 4;
-                ht[j * 4 + 0] = b[0], ht[j * 4 + 1] = b[1], ht[j * 4 + 2] = b[2] - b[0], ht[j * 4 + 3] = b[3] - b[1];
-            }
-            if (n) {
-                std::memcpy(h_api.p + o_conf, conf, n * 4);
-                std::memcpy(h_api.p + o_cls, cls, n * 4);
-                if (o_valid) std::memcpy(h_api.p + o_valid, x->valid, n * 4);
-                if (o_feat) std::memcpy(h_api.p + o_feat, x->feat, feat_bytes);
-            }
-            if (o_warp) std::memcpy(h_api.p + o_warp, x->warps6, k * 24);
-            HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
-            EpochDets dets{reinterpret_cast<const int*>(d_api.p + o_n), reinterpret_cast<const int*>(d_api.p + o_d0),
-                           reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
-                           reinterpret_cast<const int*>(d_api.p + o_cls), nullptr, nullptr, nullptr};
-            EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows),
-                         reinterpret_cast<float*>(d_api.p + o_oconf), cap_rows, nullptr, nullptr, 0};
-            if (x) {
-                if (o_valid) dets.valid = reinterpret_cast<const int*>(d_api.p + o_valid);
-                if (o_feat) dets.feat = reinterpret_cast<const float*>(d_api.p + o_feat);
-                extra_staged(dets, o_warp ? reinterpret_cast<const float*>(d_api.p + o_warp) : nullptr,
-                             reinterpret_cast<float*>(d_api.p + o_featn), (int)n, s);
-            }
+            L.det.fill(h_api.p, counts, xyxy, true, conf, cls);
+            if (n && L.det.has_valid) std::memcpy(h_api.p + L.det.o_valid, x->valid, n * 4);
+            if (L.has_feat) std::memcpy(h_api.p + L.o_feat, x->feat, L.feat_bytes);
+            if (L.has_warps) std::memcpy(h_api.p + L.o_warp, x->warps6, (size_t)sh.F * 24);
+            HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, L.out.o_out, hipMemcpyHostToDevice, s));
+            EpochDets dets = L.det.dets(d_api.p, L.has_feat ? reinterpret_cast<const float*>(d_api.p + L.o_feat) : nullptr);
+            if (x)
+                extra_staged(dets, L.has_warps ? reinterpret_cast<const float*>(d_api.p + L.o_warp) : nullptr,
+                             reinterpret_cast<float*>(d_api.p + L.o_featn), (int)n, s);
             const int* dp = reinterpret_cast<const int*>(d_api.p);
-            if (S == 1) run_bank(dets, kmax_s, nullptr, nullptr, 1, out, s);
-            else run_bank(dets, kmax_s, dp, dp + S, 1, out, s);
-            HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
+            if (S == 1) run_bank(dets, sh.kmax_s, nullptr, nullptr, 1, L.out.out(d_api.p), s);
+            else run_bank(dets, sh.kmax_s, dp, dp + S, 1, L.out.out(d_api.p), s);
+            HIP_CHECK(hipMemcpyAsync(h_api.p + L.out.o_out, d_api.p + L.out.o_out, L.bytes - L.out.o_out, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
             collect();
-            const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
-            const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
-            const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
-            for (int q = 0, f = 0; q < S; ++q) {
-                // a stream stopped before the call delivers nothing; one that stopped in it, the frames before the failing one
-                const int good = before[q] ? 0 : stop_code[q] ? host_hdr(q).err_frame : frames_per_stream[q];
-                for (int i = 0; i < frames_per_stream[q]; ++i, ++f) {
-                    const int m = i < good ? on[f] : 0;
-                    const int kk = std::min(m, cap_rows);
-                    if (n_out) n_out[f] = m;                      // the true count: rows beyond cap_rows are not stored
-                    if (out6) std::copy(rows + (size_t)f * cap_rows * 6, rows + ((size_t)f * cap_rows + kk) * 6, out6 + (size_t)f * cap_rows * 6);
-                    if (out_conf) std::copy(oc + (size_t)f * cap_rows, oc + (size_t)f * cap_rows + kk, out_conf + (size_t)f * cap_rows);
-                }
-                if (bad < 0 && stop_code[q] && frames_per_stream[q] > 0) bad = q;
-            }
+            // a stream stopped before the call delivers nothing; one that stopped in it, the frames before the failing one
+            auto good = [&](int q, int i) { return i < (before[q] ? 0 : stop_code[q] ? host_hdr(q).err_frame : frames_per_stream[q]); };
+            deliver(L.out.host(h_api.p), cap_rows, S, frames_per_stream, good, n_out, out6, out_conf);
+            for (int q = S - 1; q >= 0; --q)
+                if (stop_code[q] && frames_per_stream[q] > 0) bad = q;
         }
         if (status) std::copy(stop_code.begin(), stop_code.end(), status);
         else AIC_REQUIRE(bad < 0, stop_code[bad], std::string(name()) + ": " + stop_msg[bad]);

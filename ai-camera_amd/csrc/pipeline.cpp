@@ -762,15 +762,14 @@ struct Pipeline {
         const double t0 = now();
         hipStream_t s = dev->s_trk;
         const int mp = prm.max_persons;
-        const size_t o_rows = (((size_t)c.frames * 4 + 15) / 16) * 16, o_conf = o_rows + (size_t)c.frames * mp * 24;
-        const size_t obytes = o_conf + (size_t)c.frames * mp * 4;
+        StageCursor cur; const OutBlock ob(cur, c.frames, mp);   // the output half of the one staging layout (epoch_stage.hpp), alone in h_out / d_out
+        const size_t obytes = ob.end;
         if (obytes > c.h_out.n) { c.h_out.alloc(obytes), c.d_out.alloc(obytes); }
         if (!bt && !dsb) trk.ensure_dim(dim);
         HIP_CHECK(hipStreamWaitEvent(s, c.done, 0));           // the group's embeddings, crop validity and detection arrays are in HBM
         const int *h_n, *h_d0;
         EpochDets dets = group_dets(c, h_n, h_d0);
-        EpochOut eo{reinterpret_cast<int*>(c.d_out.p), reinterpret_cast<int*>(c.d_out.p + o_rows), reinterpret_cast<float*>(c.d_out.p + o_conf),
-                    mp, nullptr, nullptr, 0};
+        const EpochOut eo = ob.out(c.d_out.p);
         if (bt) {
             for (int f = 0; f < c.frames; ++f)
                 AIC_REQUIRE(h_n[f] <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, bt_name() + ": more than 512 detections in one frame");
@@ -799,18 +798,12 @@ struct Pipeline {
         }
         const double t2 = now();
         t_wait += t2 - t1;
-        const int* on = reinterpret_cast<const int*>(c.h_out.p);
-        const int* orow = reinterpret_cast<const int*>(c.h_out.p + o_rows);
-        const float* oc = reinterpret_cast<const float*>(c.h_out.p + o_conf);
+        const OutViews ov = ob.host(c.h_out.p);
         const int S = dsb ? dsb->t.n_streams : 1;
         for (int f = 0; f < c.frames; ++f) {
             const int o = out_base + f;
-            const int m = dsb && f / S >= dsb->t.grp_good[f % S] ? 0 : on[f];   // a stopped camera: nothing from its failing frame on
-            const int k = std::min(m, mp);
-            if (out.n_tracks) out.n_tracks[o] = m;             // the true count: rows beyond max_persons are not stored
-            if (m > mp) n_rows_clipped += 1;
-            if (out.tracks6) std::copy(orow + (size_t)f * mp * 6, orow + ((size_t)f * mp + k) * 6, out.tracks6 + (size_t)o * mp * 6);
-            if (out.track_conf) std::copy(oc + (size_t)f * mp, oc + (size_t)f * mp + k, out.track_conf + (size_t)o * mp);
+            const bool good = !(dsb && f / S >= dsb->t.grp_good[f % S]);   // a stopped camera: nothing from its failing frame on
+            if (deliver_frame(ov, mp, f, good, o, out.n_tracks, out.tracks6, out.track_conf) > mp) n_rows_clipped += 1;
             emit_dets(c, f, o, out);
         }
         if (final_group && (!bt || reid)) read_last_emb(c);   // (a detector-only pipeline computes no embeddings)

@@ -546,32 +546,22 @@ void Tracker::check_epochs() {
     AIC_REQUIRE(false, AIC_ERR_RUNTIME, "device association: the assignment problem has no finite solution" + at);
 }
 
-// aic_tracker_update through the device path: one frame = one epoch of length 1.
-void Tracker::update_device(const float* det_tlwh, const float* conf, const int32_t* cls, const float* feat, int feat_mem,
-                            const uint8_t* has_feat, int n, int dim_in) {
-    AIC_REQUIRE(n >= 0 && n <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "device association: more than 512 detections in one frame");
-    hipStream_t s = dev->s_trk;
+static constexpr int kDbgStride = 2 * TRK_DEV_TMAX + 8;   // update_batch: ints of one frame's debug pairs
+
+// What update_device and update_batch share: the call's k frames through the one staging layout (epoch_stage.hpp; this caller's own: update_batch's
+// per-frame debug pairs behind the outputs), the features up and normalised, the epochs queued on s.  The read-back and the sync are the caller's.
+CallStage Tracker::stage_epochs(int k, const int32_t* counts, long total, const float* det_tlwh, const float* conf, const int32_t* cls,
+                                   const float* feat, int feat_mem, const uint8_t* has_feat, int cap_rows, bool single, hipStream_t s) {
+    const int n = (int)total, stride = single ? 0 : kDbgStride;
     const bool any_feat = feat != nullptr && n > 0;
-    const int max_rows = TRK_DEV_TMAX;
-    // staging layout (host == device): n | d0 | tlwh[n*4] | conf[n] | cls[n] | valid[n] || out: n_tracks | rows[max_rows*6] | conf[max_rows]
-    const size_t o_tlwh = 16, o_conf = o_tlwh + (size_t)n * 16, o_cls = o_conf + (size_t)n * 4, o_valid = o_cls + (size_t)n * 4;
-    const size_t o_out = ((o_valid + (size_t)n * 4 + 15) / 16) * 16, o_rows = o_out + 16, o_oconf = o_rows + (size_t)max_rows * 24;
-    const size_t bytes = o_oconf + (size_t)max_rows * 4;
+    const CallStage L = tracker_stage(k, n, cap_rows, stride);
     HIP_CHECK(hipStreamSynchronize(s));
-    h_api.ensure(bytes);
-    d_api.ensure(bytes);
-    int* hi = reinterpret_cast<int*>(h_api.p);
-    hi[0] = n, hi[1] = 0;
-    if (n) {
-        std::memcpy(h_api.p + o_tlwh, det_tlwh, (size_t)n * 16);
-        std::memcpy(h_api.p + o_conf, conf, (size_t)n * 4);
-        std::memcpy(h_api.p + o_cls, cls, (size_t)n * 4);
-        int* hv = reinterpret_cast<int*>(h_api.p + o_valid);
-        for (int j = 0; j < n; ++j) hv[j] = (any_feat && (!has_feat || has_feat[j])) ? 1 : 0;
-    }
-    HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
-    const float* d_featp = nullptr;
-    const float* d_featn = nullptr;
+    h_api.ensure(L.bytes);
+    d_api.ensure(L.bytes);
+    L.det.fill(h_api.p, counts, det_tlwh, false, conf, cls);
+    L.det.fill_valid(h_api.p, any_feat, has_feat);
+    HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, L.out.o_out, hipMemcpyHostToDevice, s));
+    const float *d_featp = nullptr, *d_featn = nullptr;
     if (any_feat) {
         if (feat_mem == AIC_DEVICE) d_featp = feat;
         else {
@@ -583,27 +573,36 @@ void Tracker::update_device(const float* det_tlwh, const float* conf, const int3
         launch_normalize_rows(d_featp, d_detn.p, n, dim, s);
         d_featn = d_detn.p;
     }
-    EpochDets dets{reinterpret_cast<const int*>(d_api.p), reinterpret_cast<const int*>(d_api.p + 4),
-                   reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
-                   reinterpret_cast<const int*>(d_api.p + o_cls), reinterpret_cast<const int*>(d_api.p + o_valid), d_featp, d_featn};
     d_dbg.ensure(16 + 2 * TRK_DEV_TMAX);
-    EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows), reinterpret_cast<float*>(d_api.p + o_oconf),
-                 max_rows, d_dbg.p + 8, d_dbg.p, 0};
-    const int zero = 0;
-    run_epochs(dets, &n, &zero, 1, out, s, true);
-    HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
+    // one frame: the debug pairs and T, N of the frame go to d_dbg; k frames: every frame's pairs, in the tail of d_api
+    const EpochOut out = single ? L.out.out(d_api.p, d_dbg.p + 8, d_dbg.p, 0)
+                                : L.out.out(d_api.p, reinterpret_cast<int*>(d_api.p + L.o_tail), nullptr, stride);
+    run_epochs(L.det.dets(d_api.p, d_featp, d_featn), L.det.host_n(h_api.p), L.det.host_d0(h_api.p), k, out, s, single);
+    return L;
+}
+
+// the rows of the call's last frame, as aic_tracker_update hands them out
+void Tracker::keep_outputs(const OutViews& v, int k, int cap_rows) {
+    outputs.clear();
+    const int kl = std::min(v.n[k - 1], cap_rows);
+    for (int r = 0; r < kl; ++r) {
+        const int* q = v.rows + ((size_t)(k - 1) * cap_rows + r) * 6;
+        outputs.push_back(TrackOut{q[0], q[1], q[2], q[3], q[4], q[5], v.conf[(size_t)(k - 1) * cap_rows + r]});
+    }
+}
+
+// aic_tracker_update through the device path: one frame = one epoch of length 1, its rows at TRK_DEV_TMAX.
+void Tracker::update_device(const float* det_tlwh, const float* conf, const int32_t* cls, const float* feat, int feat_mem,
+                            const uint8_t* has_feat, int n, int dim_in) {
+    AIC_REQUIRE(n >= 0 && n <= TRK_DEV_NMAX, AIC_ERR_CAPACITY, "device association: more than 512 detections in one frame");
+    hipStream_t s = dev->s_trk;
+    const CallStage L = stage_epochs(1, &n, n, det_tlwh, conf, cls, feat, feat_mem, has_feat, TRK_DEV_TMAX, true, s);
+    HIP_CHECK(hipMemcpyAsync(h_api.p + L.out.o_out, d_api.p + L.out.o_out, L.bytes - L.out.o_out, hipMemcpyDeviceToHost, s));
     std::vector<int> dbg(16 + 2 * TRK_DEV_TMAX);
     HIP_CHECK(hipMemcpyAsync(dbg.data(), d_dbg.p, dbg.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     check_epochs();
-    const int no = *reinterpret_cast<const int*>(h_api.p + o_out);
-    const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
-    const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
-    outputs.clear();
-    for (int k2 = 0; k2 < no && k2 < max_rows; ++k2) {
-        const int* r = rows + (size_t)k2 * 6;
-        outputs.push_back(TrackOut{r[0], r[1], r[2], r[3], r[4], r[5], oc[k2]});
-    }
+    keep_outputs(L.out.host(h_api.p), 1, TRK_DEV_TMAX);
     last_t = dbg[0], last_n = dbg[1];
     last_matches.clear();
     for (int m = 0; m < dbg[8]; ++m) last_matches.emplace_back(dbg[9 + 2 * m], dbg[10 + 2 * m]);
@@ -636,71 +635,22 @@ void Tracker::update_batch(int k, const int32_t* counts, const float* det_tlwh, 
     if (any_feat) ensure_dim(dim_in);
     AIC_REQUIRE(dev_capable(), AIC_ERR_INVALID, "update_batch runs on the device: needs nn_budget > 0, max_tracks <= 512 and a feature dimension divisible by 4");
     hipStream_t s = dev->s_trk;
-    const int n = (int)total, stride = 2 * TRK_DEV_TMAX + 8;
-    // staging (host == device layout): frame_n[k] | frame_d0[k] | tlwh[n*4] | conf[n] | cls[n] | valid[n] || n_tracks[k] | rows[k*cap*6] | conf[k*cap] | matches[k*stride]
-    const size_t o_d0 = (size_t)k * 4, o_tlwh = (((size_t)k * 8 + 15) / 16) * 16, o_conf = o_tlwh + (size_t)n * 16, o_cls = o_conf + (size_t)n * 4;
-    const size_t o_valid = o_cls + (size_t)n * 4, o_out = ((o_valid + (size_t)n * 4 + 15) / 16) * 16;
-    const size_t o_rows = o_out + (((size_t)k * 4 + 15) / 16) * 16, o_oconf = o_rows + (size_t)k * cap_rows * 24;
-    const size_t o_dbg = ((o_oconf + (size_t)k * cap_rows * 4 + 15) / 16) * 16, bytes = o_dbg + (size_t)k * stride * 4;
-    HIP_CHECK(hipStreamSynchronize(s));
-    h_api.ensure(bytes);
-    d_api.ensure(bytes);
-    int* hn = reinterpret_cast<int*>(h_api.p);
-    int* hd = reinterpret_cast<int*>(h_api.p + o_d0);
-    int d0 = 0;
-    for (int f = 0; f < k; ++f) { hn[f] = counts[f]; hd[f] = d0; d0 += counts[f]; }
-    if (n) {
-        std::memcpy(h_api.p + o_tlwh, det_tlwh, (size_t)n * 16);
-        std::memcpy(h_api.p + o_conf, conf, (size_t)n * 4);
-        std::memcpy(h_api.p + o_cls, cls, (size_t)n * 4);
-        int* hv = reinterpret_cast<int*>(h_api.p + o_valid);
-        for (int j = 0; j < n; ++j) hv[j] = (any_feat && (!has_feat || has_feat[j])) ? 1 : 0;
-    }
-    HIP_CHECK(hipMemcpyAsync(d_api.p, h_api.p, o_out, hipMemcpyHostToDevice, s));
-    const float* d_featp = nullptr;
-    const float* d_featn = nullptr;
-    if (any_feat) {
-        if (feat_mem == AIC_DEVICE) d_featp = feat;
-        else {
-            d_feat.ensure((size_t)n * dim);
-            HIP_CHECK(hipMemcpyAsync(d_feat.p, feat, (size_t)n * dim * 4, hipMemcpyHostToDevice, s));
-            d_featp = d_feat.p;
-        }
-        d_detn.ensure((size_t)n * dim);
-        launch_normalize_rows(d_featp, d_detn.p, n, dim, s);
-        d_featn = d_detn.p;
-    }
-    EpochDets dets{reinterpret_cast<const int*>(d_api.p), reinterpret_cast<const int*>(d_api.p + o_d0),
-                   reinterpret_cast<const float*>(d_api.p + o_tlwh), reinterpret_cast<const float*>(d_api.p + o_conf),
-                   reinterpret_cast<const int*>(d_api.p + o_cls), reinterpret_cast<const int*>(d_api.p + o_valid), d_featp, d_featn};
-    EpochOut out{reinterpret_cast<int*>(d_api.p + o_out), reinterpret_cast<int*>(d_api.p + o_rows), reinterpret_cast<float*>(d_api.p + o_oconf),
-                 cap_rows, reinterpret_cast<int*>(d_api.p + o_dbg), nullptr, stride};
-    run_epochs(dets, hn, hd, k, out, s, false);
-    HIP_CHECK(hipMemcpyAsync(h_api.p + o_out, d_api.p + o_out, bytes - o_out, hipMemcpyDeviceToHost, s));
+    const CallStage L = stage_epochs(k, counts, total, det_tlwh, conf, cls, feat, feat_mem, has_feat, cap_rows, false, s);
+    HIP_CHECK(hipMemcpyAsync(h_api.p + L.out.o_out, d_api.p + L.out.o_out, L.bytes - L.out.o_out, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     check_epochs();
-    const int* on = reinterpret_cast<const int*>(h_api.p + o_out);
-    const int* rows = reinterpret_cast<const int*>(h_api.p + o_rows);
-    const float* oc = reinterpret_cast<const float*>(h_api.p + o_oconf);
-    const int* dbg = reinterpret_cast<const int*>(h_api.p + o_dbg);
+    const OutViews v = L.out.host(h_api.p);
+    deliver(v, cap_rows, 1, &k, [](int, int) { return true; }, n_out, out6, out_conf);
+    const int* dbg = reinterpret_cast<const int*>(h_api.p + L.o_tail);
     for (int f = 0; f < k; ++f) {
-        const int kk = std::min(on[f], cap_rows);
-        if (n_out) n_out[f] = on[f];                       // the true count: rows beyond cap_rows are not stored
-        if (out6) std::copy(rows + (size_t)f * cap_rows * 6, rows + ((size_t)f * cap_rows + kk) * 6, out6 + (size_t)f * cap_rows * 6);
-        if (out_conf) std::copy(oc + (size_t)f * cap_rows, oc + (size_t)f * cap_rows + kk, out_conf + (size_t)f * cap_rows);
-        const int* dm = dbg + (size_t)f * stride;
+        const int* dm = dbg + (size_t)f * kDbgStride;
         if (n_match) n_match[f] = dm[0];
         for (int m = 0; m < dm[0] && m < cap_rows; ++m) {
             if (match_tid) match_tid[(size_t)f * cap_rows + m] = dm[1 + 2 * m];
             if (match_det) match_det[(size_t)f * cap_rows + m] = dm[2 + 2 * m];
         }
     }
-    outputs.clear();
-    const int kl = std::min(on[k - 1], cap_rows);
-    for (int r = 0; r < kl; ++r) {
-        const int* q = rows + ((size_t)(k - 1) * cap_rows + r) * 6;
-        outputs.push_back(TrackOut{q[0], q[1], q[2], q[3], q[4], q[5], oc[(size_t)(k - 1) * cap_rows + r]});
-    }
+    keep_outputs(v, k, cap_rows);
 }
 
 // aic_tracker_import_state: the inverse of aic_tracker_export + aic_tracker_export_gallery.

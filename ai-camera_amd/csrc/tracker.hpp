@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdlib>
 
+#include "epoch_stage.hpp"
 #include "kernels.hpp"
 #include "trk_dev.hpp"
 
@@ -93,6 +94,10 @@ struct Tracker {
                       const float* galleries, int dim_in, int next_track_id);
     void update_device(const float* det_tlwh, const float* conf, const int32_t* cls, const float* feat, int feat_mem,
                        const uint8_t* has_feat, int n, int dim_in);
+    // what those two share: staging, feature upload and normalisation, the epochs (single: one frame with the debug read-back's buffers)
+    CallStage stage_epochs(int k, const int32_t* counts, long total, const float* det_tlwh, const float* conf, const int32_t* cls,
+                           const float* feat, int feat_mem, const uint8_t* has_feat, int cap_rows, bool single, hipStream_t s);
+    void keep_outputs(const OutViews& v, int k, int cap_rows);
 
     Tracker(Device& d, const aic_tracker_params& p);
     void ensure_dim(int d);

@@ -1,6 +1,7 @@
 // zones.cpp -- the zone / line counting object (zones.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_zones.hip or the call raises.
 #include "zones.hpp"
+#include "row_stage.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -68,13 +69,7 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
     AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
     AIC_REQUIRE(F == 0 || (counts && n_events && occupancy), AIC_ERR_INVALID, "NULL counts, n_events or occupancy");
     AIC_REQUIRE(F == 0 || cap == 0 || events, AIC_ERR_INVALID, "NULL events");
-    long total = 0;
-    for (long f = 0; f < F; ++f) {
-        AIC_REQUIRE(counts[f] >= 0, AIC_ERR_INVALID, "a negative row count");
-        AIC_REQUIRE(counts[f] <= ZONES_ROWS_MAX, AIC_ERR_CAPACITY, "frame " + std::to_string(f) + " has more than 512 rows");
-        total += counts[f];
-    }
-    AIC_REQUIRE(total == 0 || rows6, AIC_ERR_INVALID, "NULL rows");
+    const long total = check_row_counts(counts, F, ZONES_ROWS_MAX, rows6);
     AIC_REQUIRE((size_t)F * (size_t)cap * 8 <= ((size_t)1 << 28), AIC_ERR_INVALID, "frames * cap_events * 8 exceeds 2^28 ints");
 
     if (!dev) dev = &device(device_id);
@@ -87,11 +82,11 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
         d_geo.alloc((size_t)S * ZONES_GEO_INTS);
         h_cnt.alloc(ZONES_CNT);
     }
-    // ---- staging: fps[S] | fstart[S] | reset[S] | frame_off[F + 1] | frame_stream[F] | rows (host memory only)
-    const size_t o_fstart = S, o_reset = 2 * (size_t)S, o_off = 3 * (size_t)S, o_fs = o_off + F + 1, o_rows = o_fs + F;
-    const size_t n_stage = o_rows + (mem == AIC_HOST ? (size_t)total * 6 : 0);
-    h_stage.ensure(n_stage);
-    d_stage.ensure(n_stage);
+    // ---- staging: fps[S] | fstart[S] | reset[S] | frame_off[F + 1] | frame_stream[F] | rows (host memory only; row_stage.hpp)
+    const size_t o_fstart = S, o_reset = 2 * (size_t)S, o_off = 3 * (size_t)S, o_fs = o_off + F + 1;
+    const RowStage rs(o_off, o_fs + F, total, mem == AIC_HOST);
+    h_stage.ensure(rs.n_ints);
+    d_stage.ensure(rs.n_ints);
     d_cls4.ensure(std::max<size_t>(4, (size_t)total * 4));
     int* h = h_stage.p;
     long f = 0;
@@ -99,10 +94,8 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
         h[s] = fps[s], h[o_fstart + s] = (int)f, h[o_reset + s] = reset_pending[s];
         for (int k = 0; k < fps[s]; ++k) h[o_fs + f++] = s;
     }
-    h[o_off] = 0;
-    for (long i = 0; i < F; ++i) h[o_off + i + 1] = h[o_off + i] + counts[i];
-    if (mem == AIC_HOST && total) std::memcpy(h + o_rows, rows6, (size_t)total * 6 * sizeof(int));
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, n_stage * sizeof(int), hipMemcpyHostToDevice, st));
+    rs.fill(h, counts, F, rows6);
+    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
     // ---- geometry that changed since the last update
     const long n_dirty = std::count(geo_dirty.begin(), geo_dirty.end(), (char)1);
     if (n_dirty > 8) HIP_CHECK(hipMemcpyAsync(d_geo.p, h_geo.data(), h_geo.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -117,7 +110,7 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
     d_out.ensure(n_out);
     h_out.ensure(n_out);
     HIP_CHECK(hipMemsetAsync(d_out.p, 0, n_out * sizeof(int), st));
-    const int* d_rows = mem == AIC_HOST ? d_stage.p + o_rows : rows6;
+    const int* d_rows = rs.d_rows(d_stage.p, rows6);
     {
         Prof pr(*dev, PROF_TRK, st, 0, (double)total * 40);
         if (total) launch_zones_classify(d_stage.p + o_off, d_stage.p + o_fs, (int)F, d_rows, d_geo.p, anchor, d_cls4.p, st);
