@@ -71,6 +71,10 @@ class SceneConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell")]
 
 
+class JpegConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -276,6 +280,16 @@ _SIGS = {
     "aic_scene_reset": (_I, [_P, _I]),
     "aic_scene_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
     "aic_scene_export": (_I, [_P, _I, _P, _P, _P, _P]),
+    "aic_jpeg_tables": (_I, [_I, _P, _P]),
+    "aic_jpeg_header": (_I, [_I, _I, _I, _I, _I, _P, _I, _P]),
+    "aic_jpeg_config_default": (_I, [_I, _I, _P]),
+    "aic_jpeg_create": (_I, [_I, _P, _P]),
+    "aic_jpeg_destroy": (_I, [_P]),
+    "aic_jpeg_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_jpeg_worst_case_bytes": (_I, [_P, _P]),
+    "aic_jpeg_encode": (_I, [_P, _P, _I, _I, _P, _I, C.c_int64, _P, _P]),
+    "aic_jpeg_coefficients": (_I, [_P, _P, _I, _I, _P]),
+    "aic_jpeg_counters": (_I, [_P, _P, _P, _P]),
     "aic_yuv_coeffs": (_I, [_I, _I, _P, _P, _P]),
     "aic_frames_to_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
     "aic_frames_from_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),

@@ -41,6 +41,22 @@ def write_ppm(path, thumb_bgr):
         f.write(t.tobytes())
 
 
+def write_jpeg(path, data):
+    """A thumbnail's JFIF file as encode_finals() delivered it."""
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def encode_finals(result, encoder):
+    """The JFIF file (bytes; None for one beyond the encoder's max_bytes) of every final of a BestShotResult, in finals() order: all
+    thumbnails go through one JpegEncoder.encode call (jpeg.py; more than its max_images: one call per max_images)."""
+    thumbs = [t for _, t in finals(result)]
+    out = []
+    for lo in range(0, len(thumbs), encoder.max_images):
+        out += encoder.encode(np.stack(thumbs[lo:lo + encoder.max_images]))
+    return out
+
+
 class BestShots:
     """BestShots(streams, frame_hw, thumb=(64, 128), max_tracks=128, forget_after=70, region="box", head_q8=64, pad=0, min_w=8,
     min_h=16, device=0).  thumb = (width, height), multiples of 8 in 16..128 x 16..256; region "box" or "head" (the upper head_q8 / 256

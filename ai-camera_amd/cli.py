@@ -30,6 +30,9 @@ Pixel formats: with `--batch N` (and `--inputs`) YUV fram
 into its BGR ring on the device; frames that are saved or shown come back through TrackingPipeline.read_frames.  With `--batch 1` each
 frame goes through frames.to_bgr before the plugin classes, whose signatures stay BGR.  `--output_pixel_format nv12` makes the headerless
 writer append NV12 frames (`.nv12`, converted by frames.from_bgr after rendering) -- what an encoder takes.
+`--output_codec mjpeg [--jpeg_quality N] [--jpeg_restart N]` encodes the annotated frames on the device instead and
+appends them as JFIF files to `<name>.mjpeg` (+ `.json` with every frame's byte offset); `--best_shot_format jpg` writes the best shots
+as `.jpg` (4:4:4 at `--jpeg_quality`).
 """
 from __future__ import annotations
 
@@ -92,6 +95,8 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                         "file in DIR/index.jsonl; the crops come from the frames as ingested, before any --redact")
     p.add_argument("--best_shot_size", type=str, default="64x128", metavar="WxH", help="with --best_shots: thumbnail size, multiples of 8 in 16..128 x 16..256")
     p.add_argument("--best_shot_region", type=str, default="box", choices=("box", "head"), help="with --best_shots: the whole box or its head (the top quarter)")
+    p.add_argument("--best_shot_format", type=str, default="ppm", choices=("ppm", "jpg"),
+                   help="with --best_shots: ppm (raw P6) or jpg (JFIF, 4:4:4 at --jpeg_quality, encoded on the device)")
     p.add_argument("--scene_watch", action="store_true",
                    help="watch every camera's scene on the device: every JSON line gains \"scene\": {active, moving_cells, motion_box, alarms} "
                         "and \"moving\" (per track, 0..256), and every alarm edge (dark, bright, defocus, scene, frozen) is printed as its own line")
@@ -113,7 +118,25 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--yuv_range", type=str, default="limited", choices=("limited", "full"), help="YUV range of --pixel_format / --output_pixel_format")
     p.add_argument("--output_pixel_format", type=str, default="bgr24", choices=("bgr24", "nv12"),
                    help="nv12: the annotated frames are appended as NV12 to a headerless <name>.nv12 file (+ .json) instead of BGR24")
+    p.add_argument("--output_codec", type=str, default="auto", choices=("auto", "mjpeg"),
+                   help="mjpeg: the annotated frames are encoded on the device and appended as JFIF files to <name>.mjpeg (+ .json with the "
+                        "byte offset of every frame); auto: a video file when OpenCV is importable, else headerless frames")
+    p.add_argument("--jpeg_quality", type=int, default=None, metavar="N", help="with --output_codec mjpeg or --best_shot_format jpg: 1..100 (default 85)")
+    p.add_argument("--jpeg_restart", type=int, default=None, metavar="N",
+                   help="with --output_codec mjpeg: MCUs per restart interval, 1..65535, or 0 = one MCU row (default)")
     args = p.parse_args(argv)
+    if args.best_shot_format != "ppm" and not args.best_shots:
+        p.error("--best_shot_format needs --best_shots DIR")
+    if args.jpeg_quality is not None and args.output_codec != "mjpeg" and args.best_shot_format != "jpg":
+        p.error("--jpeg_quality needs --output_codec mjpeg or --best_shot_format jpg")
+    if args.jpeg_restart is not None and args.output_codec != "mjpeg":
+        p.error("--jpeg_restart needs --output_codec mjpeg")
+    if args.output_codec == "mjpeg" and args.output_pixel_format != "bgr24":
+        p.error("--output_codec mjpeg and --output_pixel_format nv12 are mutually exclusive")
+    args.jpeg_quality = 85 if args.jpeg_quality is None else args.jpeg_quality
+    args.jpeg_restart = 0 if args.jpeg_restart is None else args.jpeg_restart
+    if not 1 <= args.jpeg_quality <= 100 or not 0 <= args.jpeg_restart <= 65535:
+        p.error("--jpeg_quality is in 1..100, --jpeg_restart in 0..65535")
     if args.pixel_format != "bgr24":
         specs = args.inputs.split(",") if args.inputs is not None else [args.input]
         if not all(spec and spec.startswith("raw:") for spec in specs):
@@ -217,13 +240,21 @@ def frame_source(spec, webcam_id=0, cv2=None, pixel_format="bgr24"):
 
 class FrameWriter:
     """Annotated frames: cv2.VideoWriter when cv2 is there (mp4v / XVID as aicamera_tracker.py:155-156), else headerless BGR24.
-    pixel_format="nv12": always headerless, NV12 (frames.from_bgr with the given matrix / range), suffix .nv12."""
+    pixel_format="nv12": always headerless, NV12 (frames.from_bgr with the given matrix / range), suffix .nv12.
+    mjpeg=dict(quality, restart, device): always Motion-JPEG -- the frames' JFIF files back to back, suffix .mjpeg, the side
+    file lists every frame's byte offset; write() encodes a frame with the writer's own JpegEncoder, write_encoded() appends a file
+    that a shared encoder made (the S frames of a tick in one call)."""
 
-    def __init__(self, path_stem: Path, size, cv2=None, filename=None, pixel_format="bgr24", yuv_matrix="bt601", yuv_range="limited"):
+    def __init__(self, path_stem: Path, size, cv2=None, filename=None, pixel_format="bgr24", yuv_matrix="bt601", yuv_range="limited", mjpeg=None):
         self.cv2, self.raw, self.vw, self.frames = cv2, None, None, 0
         self.yuv = None if pixel_format == "bgr24" else (pixel_format, yuv_matrix, yuv_range)
+        self.mjpeg, self.encoder, self.offsets = mjpeg, None, [0]
         w, h, fps = size
-        if cv2 is not None and self.yuv is None:
+        if mjpeg is not None:
+            self.path = path_stem.parent / ((filename or path_stem.name) + ".mjpeg")
+            self.raw = open(self.path, "wb")
+            self.meta = dict(width=w, height=h, fps=fps, codec="mjpeg", quality=mjpeg["quality"], restart=mjpeg["restart"], subsampling="420")
+        elif cv2 is not None and self.yuv is None:
             name = filename or path_stem.name + ".mp4"
             if not name.lower().endswith((".mp4", ".avi")):
                 name += ".mp4"
@@ -241,7 +272,16 @@ class FrameWriter:
                 self.meta.update(yuv_matrix=yuv_matrix, yuv_range=yuv_range)
         print(f"Output video will be saved to: {self.path}")
 
+    def write_encoded(self, data):
+        self.raw.write(data)
+        self.offsets.append(self.offsets[-1] + len(data))
+        self.frames += 1
+
     def write(self, frame):
+        if self.mjpeg is not None:
+            if self.encoder is None:
+                self.encoder = mjpeg_encoder(frame.shape[:2], 1, self.mjpeg)
+            return self.write_encoded(self.encoder.encode(np.ascontiguousarray(frame)[None])[0])
         if self.vw is not None:
             self.vw.write(frame)
         elif self.raw is not None and self.yuv is not None:
@@ -253,9 +293,24 @@ class FrameWriter:
     def close(self):
         if self.vw is not None:
             self.vw.release()
+        if self.encoder is not None:
+            self.encoder.close()
         if self.raw is not None:
             self.raw.close()
+            if self.mjpeg is not None:
+                self.meta["offsets"] = self.offsets
             json.dump(dict(self.meta, frames=self.frames), open(str(self.path) + ".json", "w"))
+
+
+def mjpeg_encoder(hw, max_images, opts):
+    """The JpegEncoder of --output_codec mjpeg: 4:2:0, and no frame is ever dropped for its size."""
+    from .jpeg import JpegEncoder
+    return JpegEncoder(hw, max_images=max_images, quality=opts["quality"], restart=opts["restart"], subsampling="420", max_bytes="worst",
+                       device=opts["device"])
+
+
+def mjpeg_options(args):
+    return dict(quality=args.jpeg_quality, restart=args.jpeg_restart, device=config.resolve_device(args.device)) if args.output_codec == "mjpeg" else None
 
 
 class _FrameFree:
@@ -354,13 +409,23 @@ class _BestShotFiles:
         self.dir.mkdir(parents=True, exist_ok=True)
         self.index = open(self.dir / "index.jsonl", "a")
         self.link = bool(args.link_cameras)
+        self.encoder = None
+        if args.best_shot_format == "jpg":                       # thumbnails are small: 4:4:4, and none is dropped for its size
+            from .jpeg import JpegEncoder
+            self.encoder = JpegEncoder((args.best_shot_wh[1], args.best_shot_wh[0]), max_images=256, quality=args.jpeg_quality, subsampling="444",
+                                       max_bytes="worst", device=device)
         if pipe is not None:
             pipe.attach_best_shots(self.shots)
 
     def _write(self, result):
-        for ev, thumb in self.mod.finals(result):
-            name = f"cam{ev['stream']}_id{ev['id']}_f{ev['best_frame']}.ppm" if ev["has_shot"] else None   # None: never large enough to show
-            if name:
+        finals = self.mod.finals(result)
+        files = self.mod.encode_finals(result, self.encoder) if self.encoder is not None and finals else None   # all of them in one call
+        ext = "ppm" if self.encoder is None else "jpg"
+        for i, (ev, thumb) in enumerate(finals):
+            name = f"cam{ev['stream']}_id{ev['id']}_f{ev['best_frame']}.{ext}" if ev["has_shot"] else None   # None: never large enough to show
+            if name and files is not None:
+                self.mod.write_jpeg(self.dir / name, files[i])
+            elif name:
                 self.mod.write_ppm(self.dir / name, thumb)
             line = dict(ev, file=name, reason=self.mod.REASONS[ev["reason"]])
             if self.link and self.pipe is not None and self.pipe.xcam is not None:
@@ -385,6 +450,8 @@ class _BestShotFiles:
         finally:
             self.index.close()
             self.shots.close()
+            if self.encoder is not None:
+                self.encoder.close()
 
 
 class _SceneLines:
@@ -509,7 +576,8 @@ def main_streams(args, cv2):
         for k, (name, _, _) in enumerate(sources):
             stem = out_dir / f"{name}_tracked_{stamp}_s{k}"
             outs[k] = open(str(stem) + ".jsonl", "w")
-            writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None, **yuv_out)
+            writers[k] = FrameWriter(stem, size, cv2, f"{args.output_filename}_s{k}" if args.output_filename else None, **yuv_out,
+                                     mjpeg=mjpeg_options(args))
     pipe.link_after_run = bool(args.link_cameras)
     archive = None
     if args.archive:
@@ -563,6 +631,7 @@ def main_streams(args, cv2):
     n, t0 = 0, time.time()
     tick = []                                                                     # the tick's (tracks, labelled tracks) so far
     batch = np.empty((S, size[1], size[0], 3), np.uint8) if output is not None else None      # its frames: copied as they arrive
+    encoder = mjpeg_encoder((size[1], size[0]), S, mjpeg_options(args)) if output is not None and args.output_codec == "mjpeg" else None
     try:
         for frame, tracks in pipe.stream(ticks, read_back=output is not None):   # (YUV sources: the frames drawn on come back from the ring)
             k, idx = n % S, n // S
@@ -578,8 +647,12 @@ def main_streams(args, cv2):
                 if len(tick) == S:                                                # the tick's S frames in ONE render call
                     drawn = output.draw(batch, [t[0] for t in tick], [t[1] for t in tick],
                                         [[label, f"Input: {sources[c][0]} (stream {c})"] for c in range(S)])
-                    for c in range(S):
-                        writers[c].write(drawn[c])
+                    if encoder is not None:                                       # ... and in ONE encode call
+                        for c, data in enumerate(encoder.encode(np.ascontiguousarray(drawn))):
+                            writers[c].write_encoded(data)
+                    else:
+                        for c in range(S):
+                            writers[c].write(drawn[c])
                     tick = []
             if outs[k]:
                 line = {"frame": idx, "tracks": tracks}
@@ -606,6 +679,8 @@ def main_streams(args, cv2):
             watch.close()
         if output is not None:
             output.close()
+        if encoder is not None:
+            encoder.close()
         if archive is not None:
             if args.archive_file:
                 archive.save(args.archive_file)
@@ -709,7 +784,7 @@ def main(argv=None):
         out_dir.mkdir(parents=True, exist_ok=True)
         stem = out_dir / f"{name}_tracked_{time.strftime('%Y%m%d-%H%M%S')}"
         out_f = open(str(stem) + ".jsonl", "w")
-        writer = FrameWriter(stem, size, cv2, args.output_filename, args.output_pixel_format, args.yuv_matrix, args.yuv_range)
+        writer = FrameWriter(stem, size, cv2, args.output_filename, args.output_pixel_format, args.yuv_matrix, args.yuv_range, mjpeg_options(args))
     if args.show_display and cv2 is None:
         print("--show_display ignored: no display backend (cv2) here.")
     frame_idx, total, display_fps = 0, 0.0, 0.0

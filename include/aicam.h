@@ -957,6 +957,38 @@ int aic_scene_reset(aic_scene* s, int stream);
 int aic_scene_update(aic_scene* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
                      int rows_mem, int32_t* records, uint8_t* masks, int32_t* row_motion);
 int aic_scene_export(aic_scene* s, int stream, int32_t* bg, int32_t* dev, int32_t* prev, int32_t* scalars);
+/* ---- JPEG out: a bank of equally sized BGR24 images to complete JFIF files in one call (csrc/jpeg.hpp) ---------
+ * Baseline sequential DCT, 8 bit, YCbCr full range, 4:2:0 (subsampling 420) or 4:4:4 (444), the Annex K Huffman tables, restart markers
+ * always on (restart = MCUs per interval, 1..65535; 0 = one MCU row).  Integer arithmetic only; tests/jpeg_oracle.py is the
+ * specification and the device's bytes equal it bit for bit.  Every file starts with the same 629 header bytes.
+ * aic_jpeg_tables / aic_jpeg_header (host only, no device): the quantisation tables of a quality (1..100) in natural order; the header
+ * (*n = 629; AIC_ERR_CAPACITY when cap is smaller).
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option and worst_case_bytes never touch it.
+ * config: max_images 1..4096, height and width 1..16384, quality 1..100, restart 0..65535, subsampling 420 / 444, max_bytes >= 631 per
+ * image (default 629 + 3 * padded_w * padded_h + 2 * intervals + 2; worst_case_bytes = 629 + 416 * blocks + 2 * intervals + 2 always fits).
+ * encode: n (0..max_images) images [n, height, width, 3] in host or device memory (frames_mem; a device pointer of any alignment); the
+ * files are packed back to back into out (out_mem; out_cap bytes): file i is out[offsets[i] .. offsets[i + 1]).  An image whose file is
+ * larger than max_bytes gets status[i] = AIC_ERR_CAPACITY and zero length, its neighbours are unaffected.  When the packed total
+ * exceeds out_cap the call returns AIC_ERR_CAPACITY with offsets and status filled and nothing written: the caller retries with room.
+ * option: "quality", "restart" (legal between calls), "launch_budget_mb" (1..65536, default 1024): a bank is cut into launches whose
+ * staged frames and coefficients each stay below it, one image at the least; same bytes.
+ * coefficients (debugging): the quantised coefficients of n images, int16 [n, MCUs, blocks per MCU, 64] in zigzag order, to the host. */
+typedef struct aic_jpeg aic_jpeg;
+typedef struct {
+    int32_t max_images, height, width, quality, restart, subsampling;
+    int64_t max_bytes;
+} aic_jpeg_config;
+int aic_jpeg_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
+int aic_jpeg_header(int height, int width, int quality, int restart, int subsampling, uint8_t* out, int cap, int* n);
+int aic_jpeg_config_default(int height, int width, aic_jpeg_config* out);
+int aic_jpeg_create(int device, const aic_jpeg_config* config, aic_jpeg** out);
+int aic_jpeg_destroy(aic_jpeg* j);
+int aic_jpeg_option(aic_jpeg* j, const char* key, int value);
+int aic_jpeg_worst_case_bytes(aic_jpeg* j, int64_t* bytes);
+int aic_jpeg_encode(aic_jpeg* j, const uint8_t* frames_bgr, int frames_mem, int n, uint8_t* out, int out_mem, int64_t out_cap,
+                    int64_t* offsets, int32_t* status);
+int aic_jpeg_coefficients(aic_jpeg* j, const uint8_t* frames_bgr, int frames_mem, int n, int16_t* out);
+int aic_jpeg_counters(aic_jpeg* j, int64_t* images, int64_t* bytes_in, int64_t* bytes_out);
 /* ---- 4:2:0 YUV frames in, NV12 out: pixel-format conversion of a bank of frames in one launch (csrc/yuv.hpp) -------
  * Decoders, RTSP stacks and camera SDKs deliver NV12 (sometimes I420) on pitched surfaces and encoders want the same back; everything else
  * in this library reads packed BGR24.  tests/yuv_oracle.py is the specification and the device equals it bit for bit in both directions:
