@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "bestshot", "scene", "render", "jpeg", "gmc", "frames", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "bestshot", "scene", "render", "jpeg", "jpegdec", "gmc", "frames", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
@@ -48,6 +48,8 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.render").Renderer
     if name == "JpegEncoder":
         return _importlib.import_module(f"{__name__}.jpeg").JpegEncoder
+    if name == "JpegDecoder":
+        return _importlib.import_module(f"{__name__}.jpegdec").JpegDecoder
     if name == "CameraMotionBank":
         return _importlib.import_module(f"{__name__}.gmc").CameraMotionBank
     if name == "CameraMotion":

@@ -75,6 +75,15 @@ class JpegConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
 
 
+class JpegdecConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width")]
+
+
+class JpegdecInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "reason", "width", "height", "components", "sampling", "restart", "intervals")] + [
+        ("entropy_offset", C.c_int64), ("entropy_bytes", C.c_int64)]
+
+
 class PipelineParams(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("batch", C.c_int32), ("ring_frames", C.c_int32),
                 ("max_persons", C.c_int32), ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
@@ -290,6 +299,14 @@ _SIGS = {
     "aic_jpeg_encode": (_I, [_P, _P, _I, _I, _P, _I, C.c_int64, _P, _P]),
     "aic_jpeg_coefficients": (_I, [_P, _P, _I, _I, _P]),
     "aic_jpeg_counters": (_I, [_P, _P, _P, _P]),
+    "aic_jpegdec_probe": (_I, [_P, C.c_int64, _P]),
+    "aic_jpegdec_create": (_I, [_I, _P, _P]),
+    "aic_jpegdec_destroy": (_I, [_P]),
+    "aic_jpegdec_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_jpegdec_decode": (_I, [_P, _P, _I, _P, _I, _P, _I, _P, _P]),
+    "aic_jpegdec_coefficients": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "aic_jpegdec_counters": (_I, [_P, _P, _P, _P, _P]),
+    "aic_pipeline_upload_jpeg": (_I, [_P, _I, _P, _I, _P, _I, _P, _P]),
     "aic_yuv_coeffs": (_I, [_I, _I, _P, _P, _P]),
     "aic_frames_to_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),
     "aic_frames_from_bgr": (_I, [_I, _P, _I, _I, _I, _I, C.c_int64, C.c_int64, _I, _I, _I, _P]),

@@ -8,6 +8,9 @@ Frame sources (`--input`; the step BEFORE the path):
     raw:WxH:path                                        headerless BGR24 frames (memory-mapped), e.g. `ffmpeg -pix_fmt bgr24 -f rawvideo`;
                                                         with `--pixel_format nv12|i420` (`--yuv_matrix`, `--yuv_range`) tightly packed 4:2:0
                                                         frames, memory-mapped as [T, H*3/2, W] (`ffmpeg -pix_fmt nv12 -f rawvideo`)
+    path/to/clip.mjpeg                                  JFIF files back to back (what `--output_codec mjpeg` writes, what cameras send),
+                                                        decoded on the device, 16 files per call; a file the
+                                                        decoder refuses prints a line and the previous frame takes its place
 The loop body is the reference's (detect -> tracker update, timed the same way, aicamera_tracker.py:175,201-207).  `--batch N`
 (N > 1, not a reference flag) runs the same loop through the batched pipeline with double-buffered page-locked staging
 (TrackingPipeline.stream) instead of one synchronous call pair per frame.
@@ -59,7 +62,7 @@ def probe_cv2():
 
 def parse_arguments(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="AICamera: Real-time Object Detection & Tracking (MI355X engine)")
-    p.add_argument("--input", type=str, default=None, help="video file (cv2), synthetic:WxH:persons:frames[:seed], frames.npy or raw:WxH:path")
+    p.add_argument("--input", type=str, default=None, help="video file (cv2), synthetic:WxH:persons:frames[:seed], frames.npy, raw:WxH:path or clip.mjpeg (decoded on the device)")
     p.add_argument("--inputs", type=str, default=None,
                    help="comma-separated sources of one frame size (as --input), --tracker bytetrack|ocsort|botsort|deepsort_bank only: one pipeline with one tracker "
                         "stream per source; the shortest source ends the run, one output per stream (suffix _s<k>)")
@@ -188,9 +191,50 @@ def raw_frames(path, w, h, pixel_format="bgr24"):
     return np.memmap(path, np.uint8, "r").reshape(size // fb, h * 3 // 2, w)
 
 
-def frame_source(spec, webcam_id=0, cv2=None, pixel_format="bgr24"):
+MJPEG_CHUNK = 16          # files per decode call of a .mjpeg source
+
+
+def mjpeg_source(path, device=0):
+    """A Motion-JPEG file (JFIF files back to back, as --output_codec mjpeg writes them) decoded on the device (jpegdec.JpegDecoder,
+    DESIGN.md section 43), MJPEG_CHUNK files per call.  A file the decoder refuses prints one line with the reason and the previous
+    frame takes its place (black before the first), so the frame count stays the file's."""
+    import json
+    from . import jpegdec
+    if not Path(path).exists():
+        raise SystemExit(f"Error: Input video file not found: {path}")
+    buf, off = jpegdec.split_mjpeg(path)
+    n = off.size - 1
+    heads = (jpegdec.probe(buf[off[k]:off[k + 1]]) for k in range(n))
+    head = next((h for h in heads if h["status"] == 0), None)
+    if head is None:
+        raise SystemExit(f"Error: {path} holds no JPEG file this decoder accepts (baseline, 8 bit, gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0)")
+    w, h, fps = head["width"], head["height"], float(config.DEFAULT_OUTPUT_FPS)
+    side = Path(str(path) + ".json")
+    if side.exists():
+        fps = float(json.loads(side.read_text()).get("fps", fps))
+    name = Path(path).stem
+
+    def frames():
+        dec = jpegdec.JpegDecoder(h, w, max_images=MJPEG_CHUNK, device=device)
+        prev = np.zeros((h, w, 3), np.uint8)
+        for lo in range(0, n, MJPEG_CHUNK):
+            hi = min(n, lo + MJPEG_CHUNK)
+            bgr, status, reason = dec.decode_packed(buf[off[lo]:off[hi]], off[lo:hi + 1] - off[lo])
+            for k in range(hi - lo):
+                if status[k]:
+                    print(f"{name}: frame {lo + k} refused ({jpegdec.REASONS[reason[k]]}); the previous frame takes its place")
+                else:
+                    prev = bgr[k]
+                yield prev
+        dec.close()
+    return name, frames(), (w, h, fps)
+
+
+def frame_source(spec, webcam_id=0, cv2=None, pixel_format="bgr24", device=0):
     """-> (name, frame iterator, (width, height, fps) or None when unknown before the first frame).  pixel_format: of raw: sources, whose
-    frames are then [H*3/2, W]."""
+    frames are then [H*3/2, W].  device: where a .mjpeg source is decoded."""
+    if spec is not None and spec.endswith(".mjpeg"):
+        return mjpeg_source(spec, device)
     if spec is not None and spec.startswith("synthetic:"):
         parts = spec.split(":")
         w, h = (int(v) for v in parts[1].lower().split("x"))
@@ -534,7 +578,7 @@ def main_streams(args, cv2):
     """--inputs: the sources as the streams of ONE pipeline (TrackingPipeline(streams=S), or TrackingPipeline.botsort_bank /
     deepsort_bank for --tracker botsort / deepsort_bank), their frames interleaved tick by tick."""
     from .pipeline import TrackingPipeline
-    sources = [frame_source(spec, args.webcam_id, cv2, args.pixel_format) for spec in args.inputs.split(",") if spec]
+    sources = [frame_source(spec, args.webcam_id, cv2, args.pixel_format, config.resolve_device(args.device)) for spec in args.inputs.split(",") if spec]
     yuv_in = dict(pixel_format=args.pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
     yuv_out = dict(pixel_format=args.output_pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
     S = len(sources)
@@ -721,7 +765,7 @@ def main(argv=None):
     if args.inputs is not None:
         return main_streams(args, cv2)
     print("Initializing YOLOv8 Detector...")
-    name, frames, size = frame_source(args.input, args.webcam_id, cv2, args.pixel_format)
+    name, frames, size = frame_source(args.input, args.webcam_id, cv2, args.pixel_format, config.resolve_device(args.device))
     yuv_in = dict(pixel_format=args.pixel_format, yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
     if args.pixel_format != "bgr24" and args.batch <= 1:       # the plugin classes' signatures stay BGR: convert frame by frame
         frames = (pixfmt.to_bgr(f, args.pixel_format, matrix=args.yuv_matrix, range=args.yuv_range)[0] for f in frames)

@@ -22,6 +22,7 @@
 #include "deepsort_bank.hpp"
 #include "conv_common.hpp"
 #include "yuv.hpp"
+#include "jpegdec.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -213,6 +214,7 @@ struct Pipeline {
     // copied into yuv_ring (one slot per ring slot, allocated on first use) and unpacked into the BGR ring slot on the copy stream, directly
     // behind their copy (yuv.hpp); the ring itself stays BGR and nothing after it changes.
     int pix_format = AIC_PIX_BGR24, yuv_matrix = AIC_YUV_BT601, yuv_range = AIC_YUV_LIMITED;
+    std::unique_ptr<Jpegdec> jpegdec;    // aic_pipeline_upload_jpeg: created by its first call, ring_frames images of the pipeline's frame size
     DevBuf<uint8_t> yuv_ring;
     size_t host_frame_bytes() const { return pix_format == AIC_PIX_BGR24 ? frame_bytes : frame_bytes / 2; }
     // `count` host frames (in the pipeline's pixel format) into the ring slots from `slot` on, on stream st
@@ -1043,6 +1045,19 @@ int aic_pipeline_upload(aic_pipeline* p, int slot, const uint8_t* frames, int co
         if (count == 0) return;
         q.copy_frames_in(slot, frames, count, q.s_copy);
         HIP_CHECK(hipStreamSynchronize(q.s_copy));
+    });
+}
+
+int aic_pipeline_upload_jpeg(aic_pipeline* p, int slot, const uint8_t* files, int files_mem, const int64_t* offsets, int count, int32_t* status,
+                             int32_t* reason) {
+    return guarded([&] {
+        AIC_REQUIRE(p && count >= 0, AIC_ERR_INVALID, "bad argument");
+        Pipeline& q = p->p;
+        AIC_REQUIRE(slot >= 0 && slot + count <= q.prm.ring_frames, AIC_ERR_INVALID, "slot range outside the ring");
+        AIC_REQUIRE(q.pix_format == AIC_PIX_BGR24, AIC_ERR_INVALID, "upload_jpeg decodes to BGR24: the pipeline's pixel_format must be 0");
+        AIC_REQUIRE(q.prm.ring_frames <= JPEGDEC_IMAGES_MAX, AIC_ERR_INVALID, "upload_jpeg takes a ring of 4096 frames at the most");
+        if (!q.jpegdec) q.jpegdec.reset(new Jpegdec(q.dev->id, aic_jpegdec_config{q.prm.ring_frames, q.prm.frame_h, q.prm.frame_w}));
+        q.jpegdec->decode(files, files_mem, offsets, count, q.ring.p + (size_t)slot * q.frame_bytes, AIC_DEVICE, status, reason);
     });
 }
 

@@ -376,6 +376,33 @@ class TrackingPipeline:
         assert f.shape[1:] == self.host_frame_shape, f.shape
         L.call("aic_pipeline_upload", self._h, int(slot), L.ptr(f), len(f))
 
+    def upload_jpeg(self, slot, files):
+        """Decode JPEG files (a list of bytes, or a (buffer, offsets) pair as jpegdec.pack makes it; the buffer in host or device memory)
+        straight into ring slots [slot, slot + n): the counterpart of upload for frames that arrive compressed (BGR24 pipelines only;
+        every picture must have the pipeline's frame size).  Returns (status [n], reason [n]): a refused file leaves its slot as it
+        was, its neighbours are unaffected."""
+        from . import jpegdec as J
+        buf, off = files if isinstance(files, tuple) else J.pack(files)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = off.size - 1
+        if isinstance(buf, np.ndarray):
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            ptr, mem = (L.ptr(buf) if buf.size else None), L.HOST
+        else:
+            if buf.is_cuda:
+                import torch
+                torch.cuda.current_stream(buf.device).synchronize()           # the library reads it on its own stream
+            ptr, mem = C.c_void_p(buf.data_ptr()), L.DEVICE if buf.is_cuda else L.HOST
+        status, reason = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        L.call("aic_pipeline_upload_jpeg", self._h, int(slot), ptr, mem, L.ptr(off), n, L.ptr(status), L.ptr(reason))
+        return status, reason
+
+    def run_from_jpeg(self, files, slot=0, want_dets=False):
+        """upload_jpeg, then run over the same slots: (tracks, dets, status, reason)."""
+        status, reason = self.upload_jpeg(slot, files)
+        tracks, dets = self.run(slot, len(status), want_dets)
+        return tracks, dets, status, reason
+
     def inject(self, slot, detections):
         """detections: list (one per frame) of (boxes_xyxy [n,4], conf [n], class_ids [n])."""
         k, mp = len(detections), self.max_persons

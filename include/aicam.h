@@ -989,6 +989,58 @@ int aic_jpeg_encode(aic_jpeg* j, const uint8_t* frames_bgr, int frames_mem, int 
                     int64_t* offsets, int32_t* status);
 int aic_jpeg_coefficients(aic_jpeg* j, const uint8_t* frames_bgr, int frames_mem, int n, int16_t* out);
 int aic_jpeg_counters(aic_jpeg* j, int64_t* images, int64_t* bytes_in, int64_t* bytes_out);
+/* ---- JPEG in: a bank of JPEG files of one picture size to [n, height, width, 3] BGR24 in one call (csrc/jpegdec.hpp) --
+ * Baseline sequential DCT (SOF0), 8 bit, one interleaved scan; 1 component (gray) or 3 (Y, Cb, Cr) at 4:4:4, 4:2:2 or 4:2:0; any 8-bit
+ * quantisation tables, any Huffman tables (ids 0 and 1; a file without any DHT uses the Annex K tables), any restart interval; APPn and
+ * COM are skipped.  Every image of a call may have its own tables, sampling and restart interval; only the picture size is the handle's.
+ * Integer arithmetic only: tests/jpegdec_oracle.py is the specification and the device's pixels equal it byte for byte (libjpeg's ISLOW
+ * inverse DCT, triangle upsampling and fixed-point colour conversion).
+ * Anything else is refused per image: the call still returns AIC_OK, status[i] = AIC_ERR_FORMAT, reason[i] = an AIC_JPEGDEC_* value, the
+ * output slot of that image is not written and its neighbours are unaffected.
+ * Every argument error is AIC_ERR_INVALID before the device is touched (NULL, n outside 0..max_images, offsets not ascending, a file of
+ * more than 64 MB, an unknown mem); create, option and probe never touch it; n = 0 succeeds without touching it.
+ * config: max_images 1..4096, height and width 1..16384.
+ * probe (host only): the header of one file; status / reason as decode would report them for the header alone (every other field zero
+ * when refused; no size is asked for); intervals = the restart intervals the header implies.
+ * decode: file i is files[offsets[i] .. offsets[i + 1]) in host or device memory (files_mem; offsets always in host memory); out_bgr in
+ * host or device memory (out_mem; a device pointer of any alignment).
+ * option: "launch_budget_mb" (1..65536, default 1024): a bank is cut into launches whose staged files and coefficients each stay below
+ * it, one image at the least; same bytes.
+ * coefficients (debugging): image `image` of the bank, int16 [MCUs, blocks per MCU, 64] in natural order, MCU-interleaved, to the host;
+ * AIC_ERR_FORMAT for an image that decode would refuse.
+ * aic_pipeline_upload_jpeg: the counterpart of aic_pipeline_upload -- decodes `count` files straight into ring slots slot .. slot + count
+ * of a BGR24 pipeline whose frame size is the files'; a refused image leaves its slot as it was. */
+#define AIC_JPEGDEC_TRUNCATED 1
+#define AIC_JPEGDEC_NOT_JPEG 2
+#define AIC_JPEGDEC_NOT_BASELINE 3
+#define AIC_JPEGDEC_PRECISION 4
+#define AIC_JPEGDEC_COMPONENTS 5
+#define AIC_JPEGDEC_SAMPLING 6
+#define AIC_JPEGDEC_SIZE_MISMATCH 7
+#define AIC_JPEGDEC_BAD_TABLE 8
+#define AIC_JPEGDEC_MISSING_TABLE 9
+#define AIC_JPEGDEC_BAD_SCAN 10
+#define AIC_JPEGDEC_RESTART_SEQUENCE 11
+#define AIC_JPEGDEC_BAD_CODE 12
+#define AIC_JPEGDEC_OVERRUN 13
+typedef struct aic_jpegdec aic_jpegdec;
+typedef struct {
+    int32_t max_images, height, width;
+} aic_jpegdec_config;
+typedef struct {
+    int32_t status, reason, width, height, components, sampling /* 400 444 422 420 */, restart, intervals;
+    int64_t entropy_offset, entropy_bytes;
+} aic_jpegdec_info;
+int aic_jpegdec_probe(const uint8_t* file, int64_t bytes, aic_jpegdec_info* out);
+int aic_jpegdec_create(int device, const aic_jpegdec_config* config, aic_jpegdec** out);
+int aic_jpegdec_destroy(aic_jpegdec* d);
+int aic_jpegdec_option(aic_jpegdec* d, const char* key, int value);
+int aic_jpegdec_decode(aic_jpegdec* d, const uint8_t* files, int files_mem, const int64_t* offsets, int n, uint8_t* out_bgr, int out_mem,
+                       int32_t* status, int32_t* reason);
+int aic_jpegdec_coefficients(aic_jpegdec* d, const uint8_t* files, int files_mem, const int64_t* offsets, int n, int image, int16_t* out);
+int aic_jpegdec_counters(aic_jpegdec* d, int64_t* images, int64_t* refused, int64_t* bytes_in, int64_t* bytes_out);
+int aic_pipeline_upload_jpeg(aic_pipeline* p, int slot, const uint8_t* files, int files_mem, const int64_t* offsets, int count,
+                             int32_t* status, int32_t* reason);
 /* ---- 4:2:0 YUV frames in, NV12 out: pixel-format conversion of a bank of frames in one launch (csrc/yuv.hpp) -------
  * Decoders, RTSP stacks and camera SDKs deliver NV12 (sometimes I420) on pitched surfaces and encoders want the same back; everything else
  * in this library reads packed BGR24.  tests/yuv_oracle.py is the specification and the device equals it bit for bit in both directions:
