@@ -71,6 +71,10 @@ class SceneConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell")]
 
 
+class LeftConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell", "max_objects")]
+
+
 class JpegConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
 
@@ -289,6 +293,13 @@ _SIGS = {
     "aic_scene_reset": (_I, [_P, _I]),
     "aic_scene_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
     "aic_scene_export": (_I, [_P, _I, _P, _P, _P, _P]),
+    "aic_left_config_default": (_I, [_I, _I, _I, _P]),
+    "aic_left_create": (_I, [_I, _P, _P]),
+    "aic_left_destroy": (_I, [_P]),
+    "aic_left_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_left_reset": (_I, [_P, _I]),
+    "aic_left_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "aic_left_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "aic_jpeg_tables": (_I, [_I, _P, _P]),
     "aic_jpeg_header": (_I, [_I, _I, _I, _I, _I, _P, _I, _P]),
     "aic_jpeg_config_default": (_I, [_I, _I, _P]),

@@ -25,6 +25,9 @@ objects, black out fixed regions and draw the zones, with `--input` as well; wit
 `--best_shots DIR [--best_shot_size WxH] [--best_shot_region box|head]`: the best crop of every track, kept on the
 device from the frames as ingested (before any `--redact`), written as `DIR/cam<S>_id<ID>_f<best_frame>.ppm` with a line in
 `DIR/index.jsonl` when the track ends and, for the tracks still alive, at the end of the run.
+`--left_objects [--left_cell {4,8,16}] [--left_after TICKS]`: abandoned and removed objects per camera.  Every
+JSON line gains `"left_objects": [{uid, kind, box, owner, age}]` for the alarmed objects, every event (appeared, raised, ended) is
+printed as a line of its own, and the output stage of --redact / --masks / --draw_zones draws them.
 `--scene_watch [--scene_cell {4,8,16}]`: a background model per camera on a coarse gray grid.  Every JSON line
 gains `"scene": {active, moving_cells, motion_box, alarms}` and `"moving"`, one value per track of the line (256 = every cell under its
 box moves, -1 = the box is off the frame); every alarm edge (dark, bright, defocus, scene, frozen) is printed as a line of its own.
@@ -104,6 +107,12 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help="watch every camera's scene on the device: every JSON line gains \"scene\": {active, moving_cells, motion_box, alarms} "
                         "and \"moving\" (per track, 0..256), and every alarm edge (dark, bright, defocus, scene, frozen) is printed as its own line")
     p.add_argument("--scene_cell", type=int, default=None, choices=(4, 8, 16), help="with --scene_watch: the grid's cell size in pixels (default 8)")
+    p.add_argument("--left_objects", action="store_true",
+                   help="report abandoned and removed objects on the device: every JSON line gains \"left_objects\": [{uid, kind, box, owner, age}] "
+                        "for the alarmed ones, and every event (appeared, raised, ended) is printed as its own line")
+    p.add_argument("--left_cell", type=int, default=None, choices=(4, 8, 16), help="with --left_objects: the grid's cell size in pixels (default 8)")
+    p.add_argument("--left_after", type=int, default=None, metavar="TICKS",
+                   help="with --left_objects: frames a change must rest before it is a candidate (min_ticks, default 50)")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -162,6 +171,10 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--best_shot_size and --best_shot_region need --best_shots DIR")
     if args.scene_cell is not None and not args.scene_watch:
         p.error("--scene_cell needs --scene_watch")
+    if (args.left_cell is not None or args.left_after is not None) and not args.left_objects:
+        p.error("--left_cell and --left_after need --left_objects")
+    if args.left_after is not None and not 1 <= args.left_after <= 65534:
+        p.error("--left_after must be in 1..65534")
     try:
         args.best_shot_wh = tuple(int(v) for v in args.best_shot_size.lower().split("x"))
         if len(args.best_shot_wh) != 2:
@@ -534,6 +547,39 @@ class _SceneLines:
         self.watch.close()
 
 
+class _LeftLines:
+    """--left_objects: a LeftObjects (leftobj.py) over the run's frames and tracks, attached to the pipeline or fed frame by frame as
+    _SceneLines is."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import leftobj
+        self.mod, self.pipe, self._res, self._i, self.streams = leftobj, pipe, None, 0, streams
+        options = {} if args.left_after is None else dict(min_ticks=args.left_after)
+        self.stage = leftobj.LeftObjects(streams, (size[1], size[0]), cell=args.left_cell or 8, device=device, **options)
+        self.ids = {n: i for i, n in enumerate(config.CLASSES)}
+        if pipe is not None:
+            pipe.attach_left_objects(self.stage)
+
+    def after(self, frame, tracks):
+        """After every yielded frame: ([{uid, kind, box, owner, age}] of the alarmed objects, (result, stream, tick) for the output
+        stage); prints the frame's events."""
+        if self.pipe is None:
+            rows = np.array([[t[0], t[1], t[2], t[3], t[4], self.ids.get(t[5], -1)] for t in tracks], np.int64).reshape(-1, 6).astype(np.int32)
+            self._res, self._i = self.stage.update(np.ascontiguousarray(frame)[None, None], [[rows]]), 0
+        elif self.pipe.left_result is not self._res:
+            self._res, self._i = self.pipe.left_result, 0
+        t, s = divmod(self._i, self.streams)
+        self._i += 1
+        res = self._res
+        for e in res.events_of(s, t):
+            print(json.dumps({"left_object": self.mod.EVENT_NAMES[int(e[2])], "stream": s, "frame": int(e[11]), "uid": int(e[3]),
+                              "kind": self.mod.KIND_NAMES[int(e[4])], "box": [int(v) for v in e[5:9]], "owner": int(e[9]), "area": int(e[10])}))
+        return res.alarmed(s, t), (res, s, t)
+
+    def close(self):
+        self.stage.close()
+
+
 class _Output:
     """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
     render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
@@ -557,7 +603,7 @@ class _Output:
             self.renderer.close()
             raise
 
-    def draw(self, frames, tracks, shown, infos):
+    def draw(self, frames, tracks, shown, infos, left=None):
         """frames: S arrays [H, W, 3] of cameras 0..S-1, or one uint8 array [S, H, W, 3] (drawn in place) -> uint8 [S, H, W, 3] annotated.  tracks: the trackers' tuples (redaction), shown: the
         tuples as labelled, infos: the info panel's lines per frame."""
         batch = frames if isinstance(frames, np.ndarray) else np.ascontiguousarray(np.stack(frames), dtype=np.uint8)
@@ -567,6 +613,8 @@ class _Output:
             pl = visualization.PrimList()
             if self.geometry is not None:
                 visualization.zone_prims(pl, *self.geometry[c])
+            if left is not None and left[c] is not None:                      # (LeftResult, stream, tick): the objects under the labels
+                left[c][0].prims(left[c][1], left[c][2], pl)
             prims.append(visualization.info_prims(visualization.track_prims(pl, sh), list(info)))
         return self.renderer.render(batch, np.concatenate(rows).astype(np.int32), [len(r) for r in rows], prims)
 
@@ -660,6 +708,17 @@ def main_streams(args, cv2):
                     f.close()
             pipe.close()
             return 1
+    left = None
+    if args.left_objects:
+        try:
+            left = _LeftLines(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --left_objects: {e}")
+            for f in (zones, shots, watch):
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -683,14 +742,15 @@ def main_streams(args, cv2):
             if shots is not None:
                 shots.after(frame, tracks)
             scene = watch.after(frame, tracks) if watch is not None else None
+            lost = left.after(frame, tracks) if left is not None else None
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
                 batch[k] = frame
-                tick.append((tracks, shown))
+                tick.append((tracks, shown, lost[1] if lost is not None else None))
                 if len(tick) == S:                                                # the tick's S frames in ONE render call
                     drawn = output.draw(batch, [t[0] for t in tick], [t[1] for t in tick],
-                                        [[label, f"Input: {sources[c][0]} (stream {c})"] for c in range(S)])
+                                        [[label, f"Input: {sources[c][0]} (stream {c})"] for c in range(S)], [t[2] for t in tick])
                     if encoder is not None:                                       # ... and in ONE encode call
                         for c, data in enumerate(encoder.encode(np.ascontiguousarray(drawn))):
                             writers[c].write_encoded(data)
@@ -708,6 +768,8 @@ def main_streams(args, cv2):
                     line["zones"] = zones.line(tracks)
                 if scene is not None:
                     line["scene"], line["moving"] = scene
+                if lost is not None:
+                    line["left_objects"] = lost[0]
                 outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
@@ -721,6 +783,8 @@ def main_streams(args, cv2):
             shots.close()
         if watch is not None:
             watch.close()
+        if left is not None:
+            left.close()
         if output is not None:
             output.close()
         if encoder is not None:
@@ -863,6 +927,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    left = None
+    if args.left_objects:
+        try:
+            left = _LeftLines(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --left_objects: {e}")
+            for f in (out_f, writer, zones, shots, watch, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -908,9 +982,10 @@ def main(argv=None):
             if shots is not None:
                 shots.after(frame, tracks)
             scene = watch.after(frame, tracks) if watch is not None else None
+            lost = left.after(frame, tracks) if left is not None else None
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
                 info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
-                vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info])[0]
+                vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info], [lost[1] if lost is not None else None])[0]
                 if args.show_display and cv2 is not None:
                     cv2.imshow("AICamera Tracking", vis)
                     if cv2.waitKey(1) & 0xFF == ord("q"):
@@ -924,6 +999,8 @@ def main(argv=None):
                     line["zones"] = zones.line(tracks)
                 if scene is not None:
                     line["scene"], line["moving"] = scene
+                if lost is not None:
+                    line["left_objects"] = lost[0]
                 out_f.write(json.dumps(line) + "\n")
             if frame_idx % 100 == 0:
                 print(f"Processed {frame_idx} frames. Current FPS: {display_fps:.2f}")
@@ -940,6 +1017,8 @@ def main(argv=None):
             shots.close()
         if watch is not None:
             watch.close()
+        if left is not None:
+            left.close()
         if output is not None:
             output.close()
         if pipe is not None:

@@ -341,6 +341,30 @@ class TrackingPipeline:
         self.scene_result = w.update(self._host_bgr(slot, count, host_frames),
                                      [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)])
 
+    _left_objects = left_result = None
+    left_cap_events = 256
+
+    def attach_left_objects(self, left_objects, cap_events=256):
+        """A LeftObjects (leftobj.py) of `.streams` streams for this frame size: after every run* call the call's frames and tracks --
+        all ticks, all streams, ONE left_objects.update -- go through it and left_result is that call's LeftResult (records, objects,
+        at most `cap_events` events; no masks).  Frames and rows reach the stage from the host side, exactly as for attach_scene_watch;
+        with *_passes it sees the last pass only.  The tracks returned are untouched.  None detaches."""
+        w = left_objects
+        if w is not None and (w.streams != self.streams or (w.frame_h, w.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"left objects of {w.streams} streams of {w.frame_h}x{w.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._left_objects, self.left_cap_events, self.left_result = w, int(cap_events), None
+
+    def _feed_left(self, nt, rows, slot=0, host_frames=None):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major; host_frames: what a *_from_host call was handed."""
+        w = self._left_objects
+        if w is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.left_result = w.update(self._host_bgr(slot, count, host_frames),
+                                    [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
+                                    cap_events=self.left_cap_events)
+
     def close(self):
         for b in getattr(self, "_staging", []):
             try:
@@ -429,6 +453,7 @@ class TrackingPipeline:
         self._feed_zones(nt, rows)
         self._feed_best_shots(nt, rows, slot)
         self._feed_scene(nt, rows, slot)
+        self._feed_left(nt, rows, slot)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -451,6 +476,7 @@ class TrackingPipeline:
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot)
         self._feed_scene(nt[:count], rows[:count], slot)
+        self._feed_left(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
@@ -460,6 +486,7 @@ class TrackingPipeline:
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot)
         self._feed_scene(nt[:count], rows[:count], slot)
+        self._feed_left(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -479,6 +506,7 @@ class TrackingPipeline:
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
         self._feed_scene(nt[:count], rows[:count], slot, f)
+        self._feed_left(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -491,6 +519,7 @@ class TrackingPipeline:
         self._feed_zones(nt[:count], rows[:count])
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
         self._feed_scene(nt[:count], rows[:count], slot, f)
+        self._feed_left(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

@@ -957,6 +957,44 @@ int aic_scene_reset(aic_scene* s, int stream);
 int aic_scene_update(aic_scene* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
                      int rows_mem, int32_t* records, uint8_t* masks, int32_t* row_motion);
 int aic_scene_export(aic_scene* s, int stream, int32_t* bg, int32_t* dev, int32_t* prev, int32_t* scalars);
+/* ---- left objects: abandoned and removed items per camera (csrc/left.hpp) ------------------------------------
+ * A tracker-agnostic stage for `streams` (1..256) cameras of one frame size per call, on the gray grid of the scene watch (cell 4, 8 or
+ * 16; a grid of more than 32768 cells is refused at create with AIC_ERR_CAPACITY).  Per cell a fast and a slow background (Q8), a
+ * `still` counter and the last tracker id that covered it; the cells that stayed changed while nobody stood on them are candidates,
+ * their 8-connected blobs (labelled by their smallest cell index y * grid_w + x) are matched from tick to tick against `max_objects`
+ * (1..64) slots per stream, alarmed as LEFT or REMOVED after alarm_hold sightings and ended after gone_ticks misses.
+ * tests/left_oracle.py is the specification -- the order of a tick, every shift and threshold -- and the device equals it bit for bit.
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option and reset never touch it.  Device buffers are
+ * allocated by the first call that reaches the device; an allocation that does not fit fails that call with AIC_ERR_CAPACITY.
+ * update: frames, counts, rows6 and their memory kinds as for aic_scene_update (counts NULL: no rows; a frame of more than 512 rows is
+ * AIC_ERR_CAPACITY before anything is staged).  Outputs (host): records [ticks, streams, 8] = frame, ready, n_cand, n_blobs (kept, at
+ * most 64), n_objects, n_alarmed, flags (bit 0: more than 64 blobs of a kept size, bit 1: blobs dropped for want of a slot), dropped;
+ * objects [ticks, streams, max_objects, 12] = uid (0 = free slot, all zeros), kind (0, 1 LEFT, 2 REMOVED), alarmed, x0 y0 x1 y1 in
+ * pixels (x1 y1 exclusive), owner (a tracker id or -1), born, area (cells), seen, missing; events [cap_events, 12] = tick of the call,
+ * stream, type (1 APPEARED, 2 RAISED, 3 ENDED), uid, kind, x0 y0 x1 y1, owner, area, age, ordered by tick, stream, slot; *n_events = the
+ * true count.  When it exceeds cap_events the first cap_events are delivered and the state has advanced all the same: *status (may be
+ * NULL) = AIC_ERR_CAPACITY and the call returns AIC_OK, with status NULL the call returns AIC_ERR_CAPACITY.  cand (may be NULL) [ticks,
+ * streams, grid_h, grid_w] u8; labels (may be NULL) the same shape in int32, -1 = no candidate (a blob of a size not kept has its label).
+ * reset: stream, or -1 = every stream, starts again at age 0 with uids from 1.  export: fast, slow, still, last_id, last_tick as int32
+ * [grid_h, grid_w], slots [max_objects, 12] as in objects, scalars[4] = age, uids issued, 0, 0; changes nothing; all zeros for a stream
+ * that has seen no tick since create / reset.
+ * option: fast_shift 1..8, slow_shift 1..12, thresh 1..255, warmup 1..2^20, decay 0..64, min_ticks 1..65534, absorb_ticks min_ticks + 1
+ * ..65535, pad_cells 0..8, owner_window 0..2^20, min_cells 1..32768, max_cells min_cells..32768, alarm_hold 1..2^20, gone_ticks 0..2^20
+ * (defaults: DESIGN.md section 44); none sizes a buffer.  "ticks_per_launch" and "launch_budget_mb" as for aic_scene_option. */
+typedef struct aic_left aic_left;
+typedef struct {
+    int32_t streams, frame_h, frame_w, cell, max_objects;
+} aic_left_config;
+int aic_left_config_default(int streams, int frame_h, int frame_w, aic_left_config* out);
+int aic_left_create(int device, const aic_left_config* config, aic_left** out);
+int aic_left_destroy(aic_left* s);
+int aic_left_option(aic_left* s, const char* key, int value);
+int aic_left_reset(aic_left* s, int stream);
+int aic_left_update(aic_left* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem,
+                    int cap_events, int32_t* records, int32_t* objects, int32_t* events, int32_t* n_events, int32_t* status, uint8_t* cand,
+                    int32_t* labels);
+int aic_left_export(aic_left* s, int stream, int32_t* fast, int32_t* slow, int32_t* still, int32_t* last_id, int32_t* last_tick, int32_t* slots,
+                    int32_t* scalars);
 /* ---- JPEG out: a bank of equally sized BGR24 images to complete JFIF files in one call (csrc/jpeg.hpp) ---------
  * Baseline sequential DCT, 8 bit, YCbCr full range, 4:2:0 (subsampling 420) or 4:4:4 (444), the Annex K Huffman tables, restart markers
  * always on (restart = MCUs per interval, 1..65535; 0 = one MCU row).  Integer arithmetic only; tests/jpeg_oracle.py is the
