@@ -75,6 +75,11 @@ class LeftConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell", "max_objects")]
 
 
+class ColoursConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "max_tracks", "forget_after", "torso0", "torso1", "legs0", "legs1",
+                                         "inset_q8", "min_w", "min_h", "max_cover_q8")]
+
+
 class JpegConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
 
@@ -300,6 +305,15 @@ _SIGS = {
     "aic_left_reset": (_I, [_P, _I]),
     "aic_left_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "aic_left_export": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "aic_colours_config_default": (_I, [_I, _I, _I, _P]),
+    "aic_colours_create": (_I, [_I, _P, _P]),
+    "aic_colours_destroy": (_I, [_P]),
+    "aic_colours_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_colours_reset": (_I, [_P, _I]),
+    "aic_colours_update": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "aic_colours_flush": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "aic_colours_export": (_I, [_P, _I, _P, _P]),
+    "aic_colours_classify": (_I, [_P, _I, _P]),
     "aic_jpeg_tables": (_I, [_I, _P, _P]),
     "aic_jpeg_header": (_I, [_I, _I, _I, _I, _I, _P, _I, _P]),
     "aic_jpeg_config_default": (_I, [_I, _I, _P]),

@@ -28,6 +28,9 @@ device from the frames as ingested (before any `--redact`), written as `DIR/cam<
 `--left_objects [--left_cell {4,8,16}] [--left_after TICKS]`: abandoned and removed objects per camera.  Every
 JSON line gains `"left_objects": [{uid, kind, box, owner, age}]` for the alarmed objects, every event (appeared, raised, ended) is
 printed as a line of its own, and the output stage of --redact / --masks / --draw_zones draws them.
+`--colours [--colours_file FILE.jsonl]`: what each track wears.  Every JSON line gains `"colours"`, one
+`[upper, lower]` pair of colour names (or null) per track of the line; every ended track is appended to FILE as one JSON object with
+its histograms, and the tracks still alive at the end of the run are flushed into it.
 `--scene_watch [--scene_cell {4,8,16}]`: a background model per camera on a coarse gray grid.  Every JSON line
 gains `"scene": {active, moving_cells, motion_box, alarms}` and `"moving"`, one value per track of the line (256 = every cell under its
 box moves, -1 = the box is off the frame); every alarm edge (dark, bright, defocus, scene, frozen) is printed as a line of its own.
@@ -113,6 +116,11 @@ def parse_arguments(argv=None) -> argparse.Namespace:
     p.add_argument("--left_cell", type=int, default=None, choices=(4, 8, 16), help="with --left_objects: the grid's cell size in pixels (default 8)")
     p.add_argument("--left_after", type=int, default=None, metavar="TICKS",
                    help="with --left_objects: frames a change must rest before it is a candidate (min_ticks, default 50)")
+    p.add_argument("--colours", action="store_true",
+                   help="name what every track wears on the device: every JSON line gains \"colours\": one [upper, lower] pair of colour names "
+                        "(or null) per track")
+    p.add_argument("--colours_file", type=str, default=None, metavar="FILE.jsonl",
+                   help="with --colours: append every ended track's descriptor (names, histograms) to FILE as one JSON object")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -171,6 +179,8 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--best_shot_size and --best_shot_region need --best_shots DIR")
     if args.scene_cell is not None and not args.scene_watch:
         p.error("--scene_cell needs --scene_watch")
+    if args.colours_file is not None and not args.colours:
+        p.error("--colours_file needs --colours")
     if (args.left_cell is not None or args.left_after is not None) and not args.left_objects:
         p.error("--left_cell and --left_after need --left_objects")
     if args.left_after is not None and not 1 <= args.left_after <= 65534:
@@ -580,6 +590,49 @@ class _LeftLines:
         self.stage.close()
 
 
+class _ColourLines:
+    """--colours [--colours_file FILE]: a TrackColours (colours.py) over the run's frames and tracks, attached to the pipeline or fed
+    frame by frame as _SceneLines is.  Every ended track goes to FILE as one JSON object; close() flushes what still lives."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import colours
+        self.mod, self.pipe, self._res, self._i, self._at, self.streams = colours, pipe, None, 0, 0, streams
+        self.stage = colours.TrackColours(streams, (size[1], size[0]), device=device)
+        self.file = open(args.colours_file, "a") if args.colours_file else None
+        if pipe is not None:
+            pipe.attach_colours(self.stage)
+
+    def _write(self, result):
+        if self.file is not None:
+            for ev in self.mod.finals(result):
+                self.file.write(json.dumps(dict(ev, reason=self.mod.REASONS[ev["reason"]])) + "\n")
+
+    def after(self, frame, tracks):
+        """After every yielded frame: one [upper, lower] pair of names (or None) per track, in the order of the tracks."""
+        if self.pipe is None:
+            self._res, self._i, self._at = self.stage.update_tuples(np.ascontiguousarray(frame)[None, None], [[tracks]]), 0, 0
+            self._write(self._res)
+        elif self.pipe.colour_result is not self._res:
+            self._res, self._i, self._at = self.pipe.colour_result, 0, 0
+            self._write(self._res)
+        self._i += 1
+        tags = self._res.row_tags[self._at:self._at + len(tracks)]           # the call's rows lie frame after frame, as they were yielded
+        self._at += len(tracks)
+        return [[self.mod.name_of(int(t[0])), self.mod.name_of(int(t[1]))] for t in tags]
+
+    def close(self):
+        try:
+            res = self.stage.flush()
+            self._write(res)
+            while int(res.pending.sum()):
+                res = self.stage.drain(cap=self.stage.max_tracks)
+                self._write(res)
+        finally:
+            if self.file is not None:
+                self.file.close()
+            self.stage.close()
+
+
 class _Output:
     """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
     render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
@@ -719,6 +772,17 @@ def main_streams(args, cv2):
                     f.close()
             pipe.close()
             return 1
+    worn = None
+    if args.colours:
+        try:
+            worn = _ColourLines(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --colours: {e}")
+            for f in (zones, shots, watch, left):
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -743,6 +807,7 @@ def main_streams(args, cv2):
                 shots.after(frame, tracks)
             scene = watch.after(frame, tracks) if watch is not None else None
             lost = left.after(frame, tracks) if left is not None else None
+            wears = worn.after(frame, tracks) if worn is not None else None
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
@@ -770,6 +835,8 @@ def main_streams(args, cv2):
                     line["scene"], line["moving"] = scene
                 if lost is not None:
                     line["left_objects"] = lost[0]
+                if wears is not None:
+                    line["colours"] = wears
                 outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
@@ -785,6 +852,8 @@ def main_streams(args, cv2):
             watch.close()
         if left is not None:
             left.close()
+        if worn is not None:
+            worn.close()
         if output is not None:
             output.close()
         if encoder is not None:
@@ -937,6 +1006,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    worn = None
+    if args.colours:
+        try:
+            worn = _ColourLines(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --colours: {e}")
+            for f in (out_f, writer, zones, shots, watch, left, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -983,6 +1062,7 @@ def main(argv=None):
                 shots.after(frame, tracks)
             scene = watch.after(frame, tracks) if watch is not None else None
             lost = left.after(frame, tracks) if left is not None else None
+            wears = worn.after(frame, tracks) if worn is not None else None
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
                 info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
                 vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info], [lost[1] if lost is not None else None])[0]
@@ -1001,6 +1081,8 @@ def main(argv=None):
                     line["scene"], line["moving"] = scene
                 if lost is not None:
                     line["left_objects"] = lost[0]
+                if wears is not None:
+                    line["colours"] = wears
                 out_f.write(json.dumps(line) + "\n")
             if frame_idx % 100 == 0:
                 print(f"Processed {frame_idx} frames. Current FPS: {display_fps:.2f}")
@@ -1019,6 +1101,8 @@ def main(argv=None):
             watch.close()
         if left is not None:
             left.close()
+        if worn is not None:
+            worn.close()
         if output is not None:
             output.close()
         if pipe is not None:

@@ -365,6 +365,31 @@ class TrackingPipeline:
                                     [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
                                     cap_events=self.left_cap_events)
 
+    _colours = colour_result = None
+    colour_cap = 16
+
+    def attach_colours(self, stage, cap=16):
+        """A TrackColours (colours.py) of `.streams` streams for this frame size: after every run* call the call's frames and tracks --
+        all ticks, all streams, ONE stage.update -- go through it and colour_result is that call's ColourResult (row_tags per track
+        row, at most `cap` ended tracks per stream per call; the rest wait, see .pending and stage.drain()).  Frames and rows reach the
+        stage from the host side, exactly as for attach_best_shots; with *_passes it sees the last pass only.  The tracks returned are
+        untouched.  None detaches."""
+        w = stage
+        if w is not None and (w.streams != self.streams or (w.frame_h, w.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"track colours of {w.streams} streams of {w.frame_h}x{w.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._colours, self.colour_cap, self.colour_result = w, int(cap), None
+
+    def _feed_colours(self, nt, rows, slot=0, host_frames=None):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major; host_frames: what a *_from_host call was handed."""
+        w = self._colours
+        if w is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.colour_result = w.update(self._host_bgr(slot, count, host_frames),
+                                      [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
+                                      cap=self.colour_cap)
+
     def close(self):
         for b in getattr(self, "_staging", []):
             try:
@@ -454,6 +479,7 @@ class TrackingPipeline:
         self._feed_best_shots(nt, rows, slot)
         self._feed_scene(nt, rows, slot)
         self._feed_left(nt, rows, slot)
+        self._feed_colours(nt, rows, slot)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -477,6 +503,7 @@ class TrackingPipeline:
         self._feed_best_shots(nt[:count], rows[:count], slot)
         self._feed_scene(nt[:count], rows[:count], slot)
         self._feed_left(nt[:count], rows[:count], slot)
+        self._feed_colours(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
@@ -487,6 +514,7 @@ class TrackingPipeline:
         self._feed_best_shots(nt[:count], rows[:count], slot)
         self._feed_scene(nt[:count], rows[:count], slot)
         self._feed_left(nt[:count], rows[:count], slot)
+        self._feed_colours(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -507,6 +535,7 @@ class TrackingPipeline:
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
         self._feed_scene(nt[:count], rows[:count], slot, f)
         self._feed_left(nt[:count], rows[:count], slot, f)
+        self._feed_colours(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -520,6 +549,7 @@ class TrackingPipeline:
         self._feed_best_shots(nt[:count], rows[:count], slot, f)
         self._feed_scene(nt[:count], rows[:count], slot, f)
         self._feed_left(nt[:count], rows[:count], slot, f)
+        self._feed_colours(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

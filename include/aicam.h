@@ -995,6 +995,45 @@ int aic_left_update(aic_left* s, const uint8_t* frames_bgr, int frames_mem, int 
                     int32_t* labels);
 int aic_left_export(aic_left* s, int stream, int32_t* fast, int32_t* slow, int32_t* still, int32_t* last_id, int32_t* last_tick, int32_t* slots,
                     int32_t* scalars);
+/* ---- clothing colours: what each track wears, per camera (csrc/colours.hpp) -----------------------------------
+ * A tracker-agnostic stage over u8 BGR frames of one size and the rows every tracker delivers (x1 y1 x2 y2 id cls, int32), for
+ * `streams` (1..256) cameras per call.  The pixels of a torso part and a legs part of every counted row's box (fractions torso0..torso1
+ * and legs0..legs1 of its height in q8, inset by inset_q8 of its width on either side, clipped to the frame) are named with one of 12
+ * colours (0 BLACK, GRAY, WHITE, RED, ORANGE, YELLOW, GREEN, CYAN, BLUE, PURPLE, PINK, 11 BROWN) and histogrammed; a part smaller than
+ * min_w x min_h or covered by more than max_cover_q8 by one nearer box is not sampled.  A table of max_tracks slots per stream
+ * accumulates every sample's shares (q8) per track id; a track unseen for more than forget_after ticks ENDS and is handed over as a
+ * 48-int descriptor.  tests/colours_oracle.py is the specification -- valid and counted rows, the parts, the pixel rule, the order of a
+ * tick, the capacity rule -- and the device equals it bit for bit.
+ * aic_colours_config: frame_h, frame_w in 1..16384; max_tracks 1..512; forget_after 0..2^24; 0 <= torso0 < torso1 <= 256 and legs alike;
+ * inset_q8 0..127; min_w, min_h in 1..16384; max_cover_q8 0..256.  aic_colours_config_default fills the documented defaults (128 tracks,
+ * forget_after 70, torso 51..128, legs 141..230, inset 64, min 4 x 4, max_cover 64) around streams / frame size.
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option and reset never touch it.  Device buffers are
+ * allocated by the first call that reaches the device; an allocation that does not fit fails that call with AIC_ERR_CAPACITY.
+ * update: frames, counts, rows6, their memory kinds, ticks and cap as for aic_bestshot_update (a frame of more than 512 rows is
+ * AIC_ERR_CAPACITY before anything is staged; ticks = 0 only drains).  Outputs (host): n_final[streams]; events[streams, cap, 48] =
+ * reason (0 LIVE, 1 EXPIRED, 2 FLUSHED), stream, id, cls, first_frame, last_seen, sightings, samples_upper, samples_lower, top_upper,
+ * second_upper, top_lower, second_lower, slot, 0, 0, hist_upper[12], hist_lower[12] (q8 shares, 0..256), 8 zeros -- top = the largest
+ * bin (-1 without samples), second = the largest other bin with at least a quarter of it (else -1); only the n_final[s] first of a
+ * stream are written; row_tags (may be NULL) [sum of counts, 4] = top_upper, top_lower and their shares from the row's slot after its
+ * tick (-1 / 0 for a part without samples, four times -1 for a row not counted or of a stopped stream); pending[streams]; status[streams]
+ * (may be NULL).  A stream that needs more than max_tracks slots stops alone with AIC_ERR_CAPACITY as a best-shot stream does.
+ * flush, export (events[max_tracks, 48]), reset: as for aic_bestshot_*.  option "ticks_per_launch" and "launch_budget_mb" (the sampled
+ * rows, 128 bytes each, and the staged frames of one launch each stay below it): same results.
+ * aic_colours_classify (host only, no device): bins[i] = the colour of pixel bgr[3 i .. 3 i + 2], the rule the kernel applies. */
+typedef struct aic_colours aic_colours;
+typedef struct {
+    int32_t streams, frame_h, frame_w, max_tracks, forget_after, torso0, torso1, legs0, legs1, inset_q8, min_w, min_h, max_cover_q8;
+} aic_colours_config;
+int aic_colours_config_default(int streams, int frame_h, int frame_w, aic_colours_config* out);
+int aic_colours_create(int device, const aic_colours_config* config, aic_colours** out);
+int aic_colours_destroy(aic_colours* c);
+int aic_colours_option(aic_colours* c, const char* key, int value);
+int aic_colours_reset(aic_colours* c, int stream);
+int aic_colours_update(aic_colours* c, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
+                       int rows_mem, int cap, int32_t* n_final, int32_t* events, int32_t* row_tags, int32_t* pending, int32_t* status);
+int aic_colours_flush(aic_colours* c, int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
+int aic_colours_export(aic_colours* c, int stream, int32_t* n, int32_t* events);
+int aic_colours_classify(const uint8_t* bgr, int n, uint8_t* bins);
 /* ---- JPEG out: a bank of equally sized BGR24 images to complete JFIF files in one call (csrc/jpeg.hpp) ---------
  * Baseline sequential DCT, 8 bit, YCbCr full range, 4:2:0 (subsampling 420) or 4:4:4 (444), the Annex K Huffman tables, restart markers
  * always on (restart = MCUs per interval, 1..65535; 0 = one MCU row).  Integer arithmetic only; tests/jpeg_oracle.py is the
