@@ -115,6 +115,10 @@ _SIGS = {
     "aic_model_conv_plan": (_I, [_P, _I, _I, _P]),
     "aic_model_conv_plan_live": (_I, [_P, _I, _I, _P]),
     "aic_model_row_band": (_I, [_P, _I, _I, _I, _P]),
+    "aic_model_sparse_box": (_I, [_P, _I, _P]),
+    "aic_model_read_det": (_I, [_P, _I, _P, _P, _P]),
+    "aic_detect_decode": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
+    "aic_detect_live": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "aic_model_destroy": (_I, [_P]),
     "aic_model_info": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "aic_yolo_infer": (_I, [_P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P]),

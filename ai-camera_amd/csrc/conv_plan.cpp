@@ -258,7 +258,22 @@ static ConvPlan plan_tail(const ConvArgs& a) {
     return p;
 }
 
+// A launch with a pixel list (ConvArgs::pix_list) takes the LDS-DMA implicit GEMM and nothing else: its rows are gathered one by one,
+// the patch forms need whole tiles of neighbours.  One tile, 128 px x 64 ch on four waves that each own every channel of their pixels --
+// with a tail that is the NT == 4 form tail_1x1 decodes boxes in.  The K order is not touched here: it is the layer's (conv_k_order),
+// which is what makes a listed pixel's output the bits of whatever dense form its batch would have selected.
+static ConvPlan plan_list(int dtype, const ConvArgs& a) {
+    AIC_REQUIRE(dtype == AIC_F16 && a.pix_count && a.Cout == 64 && a.Cin % 32 == 0 && !a.xs && !a.x2 && !a.win_rows && !a.out_f32 &&
+                    a.M < (1 << 26),                            // (fast_divmod's range, as for the dense launch)
+                AIC_ERR_INVALID, "conv with a pixel list: unsupported shape");
+    if (a.w_tail) AIC_REQUIRE(a.act == 1 && a.res_mode == 0, AIC_ERR_INVALID, "conv with a pixel list and a 1x1 tail: unsupported lead");
+    ConvPlan p = tile(ConvForm::Dma, 2, 4, 4, 1, 4);
+    p.tail = a.w_tail != nullptr, p.list = true;
+    return p;
+}
+
 ConvPlan plan_conv(int dtype, const ConvArgs& a, int cu_budget) {
+    if (a.pix_list) return plan_list(dtype, a);
     if (a.x2) AIC_REQUIRE(a.k_order == 1 && a.Cout % 128 == 0 && !a.w_tail, AIC_ERR_INVALID, "conv with a second source: unsupported shape (check conv_x2_supported)");
     if (a.xs) AIC_REQUIRE(a.k_order == 0 && a.KH == 1 && a.KW == 1 && !a.w_tail && a.Kp < 16 * (dtype == AIC_F16 ? 32 : 16), AIC_ERR_INVALID,
                           "conv with a split source: unsupported shape (check conv_xs_supported)");

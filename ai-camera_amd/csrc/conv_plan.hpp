@@ -75,6 +75,13 @@ struct ConvArgs {
     // take it (conv3x3_c16, conv3x3_c32s2_tail, conv3x3_patch, conv1x1_stream, and c2f16_fused through its cv2's arguments); plan_conv
     // does not look at it.  win_rows == 0: the full map.
     int win_y0, win_rows;
+    // ---- optional PIXEL LIST (conv_igemm_dma_kernel only, fp16; plan_conv sends a listed launch nowhere else): GEMM row m stands for
+    // output pixel pix_list[m] -- a linear index img * Ho * Wo + oy * Wo + ox of the FULL map -- instead of pixel m.  The row is gathered,
+    // stored, and (with a tail) decoded at that pixel's own position, every row independently of its tile neighbours, in the layer's K
+    // order: the listed pixels get the bits the dense launch gives them and every other pixel of y is left as it is.  The live rows are
+    // min(pix_count[0], M) with M = N * Ho * Wo still the map's size (the grid is sized for it: a list never holds more); an entry outside
+    // [0, M) is a dead row -- it reads the zero page and stores nothing.  Both are DEVICE pointers.  pix_list == NULL: none.
+    const int* pix_list; const int* pix_count;
 };
 
 // CUs the persistent (one-block-per-CU) conv kernels size their grids for: all of them, minus the one the association epoch
@@ -110,6 +117,7 @@ struct ConvPlan {
     int g = 0;                            // Wide: K-steps per group
     bool tail = false;                    // the kernel runs a.w_tail's 1x1 in its epilogue
     bool x2 = false;                      // the kernel walks a second source (ConvArgs::x2)
+    bool list = false;                    // Dma: the pixel-list form (ConvArgs::pix_list)
     int run = 1;                          // PpPatch, SpPatch, S2Patch: tiles per block
     long blocks = 0;                      // PpPatch, SpPatch, S2Patch, C64Resident: grid size
 };

@@ -393,6 +393,14 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
         d_ncand.alloc(max_items), d_numdets.alloc(max_items);
         d_out_boxes.alloc((size_t)max_items * max_det_cap * 4), d_out_boxes_orig.alloc((size_t)max_items * max_det_cap * 4);
         d_out_scores.alloc((size_t)max_items * max_det_cap), d_out_labels.alloc((size_t)max_items * max_det_cap);
+        plan_sparse_box();
+        if (sbx.ok) {                           // every list holds a whole map: no count can overflow one
+            for (int l = 0; l < 4; ++l) d_sp_list[l].alloc((size_t)max_items * outs[l % 3].v[3] * outs[l % 3].v[4]);
+            d_sp_count.alloc(4), h_sp_count.alloc(4);
+            HIP_CHECK(hipMemsetAsync(d_sp_count.p, 0, 16, d.s_main));
+            HIP_CHECK(hipEventCreateWithFlags(&sp_ev, hipEventDisableTiming));
+            sp_force = getenv("AICAM_SPARSE_BOX_FORCE") != nullptr;
+        }
     } else {
         out_dim = outs[0].v[1];
         AIC_REQUIRE(bufs[outs[0].v[0]].f32, AIC_ERR_FORMAT, "embedding buffer must be fp32");
@@ -402,10 +410,104 @@ Model::Model(Device& d, const void* blob, size_t nbytes, int dtype_, int max_ite
 }
 
 Model::~Model() {
+    if (sp_ev) (void)hipEventDestroy(sp_ev);
     for (int i = 0; i < 2; ++i) {
         if (side_fork[i]) (void)hipEventDestroy(side_fork[i]);
         if (side_join[i]) (void)hipEventDestroy(side_join[i]);
     }
+}
+
+// The launches a run may list (engine.hpp, SparseBox): graph properties only, asked once at load time.
+void Model::plan_sparse_box() {
+    sbx = SparseBox{};
+    if (kind != KIND_YOLO || dtype != AIC_F16 || outs.size() != 3 || meta[1] != 16) return;
+    for (int l = 0; l < 3; ++l) {
+        for (size_t i = 0; i + 1 < ops.size(); ++i) {
+            if (ops[i].fuse != 3 || ops[i + 1].v[0] != OP_CONV) continue;
+            if (ops[i + 1].v[4] == outs[l].v[0]) sbx.box_tail[l] = (int)i;
+            if (ops[i + 1].v[4] == outs[l].v[1]) sbx.cls_tail[l] = (int)i;
+        }
+        if (sbx.box_tail[l] < 0 || sbx.cls_tail[l] < 0) return;
+    }
+    // level 0's lead: the conv that writes exactly the slice 22.box0.1 reads -- 3x3 / 1 / 1 SiLU, 64 channels, nothing folded into it --
+    // into a buffer nobody else reads or writes (levels whose first convs were merged into one 144-channel launch have no such op)
+    const int* t = ops[sbx.box_tail[0]].v;
+    const int buf = t[1];
+    int lead = -1;
+    for (int k = 0; k < sbx.box_tail[0]; ++k) {
+        const int* u = ops[k].v;
+        if (u[0] == OP_CONV && ops[k].fuse == 0 && u[4] == buf && u[5] == t[2] && u[6] == t[3] && u[6] == 64 && u[7] == 3 && u[8] == 3 && u[9] == 1 &&
+            u[10] == 1 && u[11] == 1 && u[14] == 0 && u[16] == 0 && ops[k].xs_buf < 0 && u[3] % 32 == 0 && !bufs[buf].f32 && bufs[buf].c == 64)
+            lead = k;
+    }
+    for (size_t j = 0; j < ops.size() && lead >= 0; ++j) {
+        const int* u = ops[j].v;
+        if (ops[j].fuse == 2) continue;
+        if ((int)j != lead && u[4] == buf) lead = -1;
+        else if ((int)j != sbx.box_tail[0] && (u[1] == buf || (u[0] == OP_CONV && u[14] && u[12] == buf) || ops[j].xs_buf == buf || (u[0] == OP_CONV && u[16] - 1 == buf))) lead = -1;
+    }
+    for (auto& o : outs)
+        if (o.v[0] == buf || o.v[1] == buf) lead = -1;
+    sbx.lead0 = lead;
+    sbx.ok = true;
+}
+
+// Whether this run can list its box branches (engine.hpp): the switch, the arming, and what conv_step plans for the six branches at n.
+bool Model::sp_eligible(size_t op0, int n) {
+    static const bool off = getenv("AICAM_NO_SPARSE_BOX") != nullptr;      // the dense head, always: A/B runs, the reference of the equality tests
+    if (off || !sbx.ok || !reduce_cls || dtype != AIC_F16) return false;
+    int first = sbx.lead0 >= 0 ? sbx.lead0 : (int)ops.size();
+    for (int l = 0; l < 3; ++l) first = std::min(first, std::min(sbx.box_tail[l], sbx.cls_tail[l]));
+    if ((int)op0 > first) return false;
+    for (int l = 0; l < 3; ++l) {
+        sp_steps[l] = conv_step((size_t)sbx.box_tail[l], ops.size(), n);
+        if (sp_steps[l].kind != ConvStep::Tail || sp_steps[l].box_bits != (1u << l) || sp_steps[l].cls_bits) return false;   // the box tail decodes in place (t_box)
+        const ConvStep c = conv_step((size_t)sbx.cls_tail[l], ops.size(), n);
+        if (c.kind != ConvStep::Tail || c.cls_bits != (1u << l)) return false;                                               // the max logits come from the class tails
+        if (rb_now && (rb_now->win[sbx.box_tail[l]].rows > 0 || rb_now->win[sbx.cls_tail[l]].rows > 0)) return false;
+    }
+    if (sbx.lead0 >= 0) {
+        sp_steps[3] = conv_step((size_t)sbx.lead0, (size_t)sbx.lead0 + 1, n);
+        if (sp_steps[3].kind != ConvStep::Single || (rb_now && rb_now->win[sbx.lead0].rows > 0)) return false;
+    }
+    return true;
+}
+
+// The candidate pass at `thr` over n frames and, with `lists`, the launches run_ops left out, on its lists (engine.hpp).
+void Model::sparse_box_pass(int n, float thr, bool lists, const int* n_dev, hipStream_t s) {
+    BoxListArgs b{};
+    b.max_logit = d_maxlogit.p, b.logit_thr = thr, b.batch = n, b.n_anchors = n_anchors, b.n_dev = n_dev, b.count = d_sp_count.p;
+    int a0 = 0;
+    for (int l = 0; l < 3; ++l) {
+        b.h[l] = outs[l].v[3], b.w[l] = outs[l].v[4], b.a0[l] = a0;
+        a0 += b.h[l] * b.w[l];
+    }
+    for (int l = 0; l < 4; ++l) b.list[l] = d_sp_list[l].p;
+    {
+        Prof pr(*dev, PROF_DET, s, 0, (double)n * n_anchors * 4);
+        launch_box_candidates(b, s);
+    }
+    sp_pass = true, sp_thr = thr, sp_n = n;
+    if (!lists) return;
+    const bool prof_conv = (dev->prof_mask >> PROF_CONV) & 1u;
+    if (prof_conv) dev->prof_begin(PROF_CONV, s, 0, 0);
+    try {
+        for (int k = sbx.lead0 >= 0 ? 3 : 0; ; k = k == 3 ? 0 : k + 1) {      // level 0's lead on the neighbour list, then the three tail pairs
+            ConvArgs a = sp_steps[k].a[0];
+            a.pix_list = d_sp_list[k].p, a.pix_count = d_sp_count.p + k, a.n_dev = n_dev;
+            // accounted with the last counts read back (what ran, never the dense layer's FLOPs); nothing known yet: nothing
+            const double share = sp_known_n > 0 ? std::min(1.0, (double)sp_known[k] / ((double)sp_known_n * a.Ho * a.Wo)) : 0.0;
+            if (prof_conv) dev->prof_account(PROF_CONV, sp_steps[k].fl * share, sp_steps[k].by * share);
+            launch_conv_igemm(dtype, a, s);
+            if (k == 2) break;
+        }
+    } catch (...) {
+        if (prof_conv) dev->prof_end(PROF_CONV, s);
+        throw;
+    }
+    if (prof_conv) dev->prof_end(PROF_CONV, s);
+    box_decoded |= 7u;
+    sp_listed = true;
 }
 
 // Which ops may leave the main stream (engine.hpp, side_heads).  An op's slices: what it reads (source, residual, second source, split
@@ -498,7 +600,57 @@ void Model::plan_side_heads() {
 
 void Model::run_ops(size_t op0, int n, hipStream_t s) {
     const bool prof_conv = (dev->prof_mask >> PROF_CONV) & 1u;            // the HIP-event brackets describe one stream: measured runs stay on it
-    if (!side_ok || side_heads.empty() || n > side_max_items || prof_conv || n_items_dev || op0 > side_heads[0].cut || s != dev->s_main) {
+    const bool one_stream = !side_ok || side_heads.empty() || n > side_max_items || prof_conv || n_items_dev || op0 > side_heads[0].cut || s != dev->s_main;
+    // ---- sparse box branches (engine.hpp).  The arming holds for this run only; what the last run listed is void from here on
+    const bool armed = sp_armed;
+    const float thr = sp_arm_thr;
+    sp_armed = sp_pass = sp_listed = false;
+    last_n = n;
+    if (armed && sp_eligible(op0, n)) {
+        if (sp_ev_pending) {                                              // the counts of the last decoded run, if they have arrived
+            // (the very first ones are waited for, once per engine: the second launch of a stream of frames already knows its path)
+            if ((sp_known_n > 0 ? hipEventQuery(sp_ev) : hipEventSynchronize(sp_ev)) == hipSuccess) {
+                std::copy(h_sp_count.p, h_sp_count.p + 4, sp_known);
+                sp_known_n = sp_ev_n, sp_ev_pending = false;
+            } else {
+                (void)hipGetLastError();                                  // (not ready is no error)
+            }
+        }
+        // Which path: time only, both give the same bits.  Large launches whose last known counts leave every list at most a quarter of
+        // its map: the lead runs on the neighbour list, so level 0 breaks even where that list is the 6 400-pixel map, and a quarter leaves
+        // room for the gathered rows costing more per pixel than the direct forms' tiles.  For isolated candidates, 9 listed pixels each,
+        // that is ~170 candidates per frame; a trained detector's candidates cluster (the bench: 278 per frame in 762 pixels).  No counts
+        // yet: dense.  Seeded heads list thousands of candidates per frame and stay dense
+        const bool big = n >= 32 && one_stream;
+        bool few = sp_known_n > 0;
+        for (int k = 0; k < 4 && few; ++k) few = 4l * sp_known[k] <= (long)sp_known_n * outs[k % 3].v[3] * outs[k % 3].v[4];
+        static const bool dbg = getenv("AICAM_SPARSE_DBG") != nullptr;
+        if (dbg)
+            fprintf(stderr, "[aicam] sparse box: n %d, last counts %d %d %d + %d neighbours over %d frames -> %s\n", n, sp_known[0], sp_known[1], sp_known[2],
+                    sp_known[3], sp_known_n, sp_force || (big && few) ? "lists" : "dense");
+        if (sp_force || (big && few)) {
+            sp_skip.assign(ops.size(), 0);
+            for (int l = 0; l < 3; ++l) sp_skip[sbx.box_tail[l]] = sp_skip[sbx.box_tail[l] + 1] = 1;
+            if (sbx.lead0 >= 0) sp_skip[sbx.lead0] = 1;
+            try {
+                run_range(op0, ops.size(), n, s);
+            } catch (...) {
+                sp_skip.clear();
+                throw;
+            }
+            sp_skip.clear();
+            sparse_box_pass(n, thr, true, n_items_dev, s);
+            return;
+        }
+        // dense, and counted for the next launch -- every launch until counts are known, then every 16th: a head that lists thousands of
+        // candidates per frame (seeded weights) pays for the pass and gets nothing back
+        if (big && (sp_known_n == 0 || ++sp_dense_runs % 16 == 0)) {
+            run_range(op0, ops.size(), n, s);
+            sparse_box_pass(n, thr, false, n_items_dev, s);
+            return;
+        }
+    }
+    if (one_stream) {
         run_range(op0, ops.size(), n, s);
         return;
     }
@@ -821,7 +973,7 @@ void Model::run_range(size_t op0, size_t op1, int n, hipStream_t s) {
         const int* v = o.v;
         const BufDesc& sb = bufs[v[1]];
         const BufDesc& db = bufs[v[4]];
-        if (o.fuse == 2) continue;
+        if (o.fuse == 2 || (!sp_skip.empty() && sp_skip[oi])) continue;     // absorbed at load time, or listed behind the head by run_ops
         if (o.fuse == 1 || v[0] != OP_CONV) span_close();
         if (o.fuse == 1) {
             const ConvWeights& w = weights[v[15]];
@@ -893,7 +1045,7 @@ DetArgs Model::det_args(int batch, float conf, float iou, int max_det, const Let
     }
     a.n_levels = (int)outs.size(), a.n_anchors = n_anchors, a.nc = meta[0], a.reg_max = meta[1], a.batch = batch;
     a.fast_exp = dtype == AIC_F16;
-    a.logit_thr = (float)std::log((double)conf / (1.0 - (double)conf));
+    a.logit_thr = logit_of(conf);
     a.iou_thr = iou, a.max_det = max_det;
     a.pad_w = g ? g->pad_w : 0.f, a.pad_h = g ? g->pad_h : 0.f, a.ratio = g ? g->ratio : 1.f;
     a.orig_w = g ? g->src_w : in_w, a.orig_h = g ? g->src_h : in_h;
@@ -913,9 +1065,19 @@ void Model::decode_nms(int batch, float conf, float iou, int max_det, const Lett
         a.out_scores = reinterpret_cast<float*>(host_out + (size_t)batch * 4 + (size_t)batch * max_det * 16);
         a.out_labels = reinterpret_cast<int*>(host_out + (size_t)batch * 4 + (size_t)batch * max_det * 20);
     }
-    Prof pr(*dev, PROF_DET, s, 0, (double)batch * n_anchors * (4 * meta[1] + meta[0]) * 4);
-    launch_decode(a, s);
-    launch_select_sort_nms(a, s);
+    // a run that listed its box branches left boxes at the candidates of ITS threshold: a call at or above it reads a subset of them, a
+    // call below it lists and computes again at its own threshold first (the neck's outputs are still in place, every buffer has its own storage)
+    if (sp_listed && a.logit_thr < sp_thr) sparse_box_pass(sp_n, a.logit_thr, true, nullptr, s);
+    {
+        Prof pr(*dev, PROF_DET, s, 0, (double)batch * n_anchors * (4 * meta[1] + meta[0]) * 4);
+        launch_decode(a, s);
+        launch_select_sort_nms(a, s);
+    }
+    if (sp_pass) {                              // the four counts come back with the detections: 16 bytes behind the NMS on its stream
+        HIP_CHECK(hipMemcpyAsync(h_sp_count.p, d_sp_count.p, 16, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipEventRecord(sp_ev, s));
+        sp_ev_pending = true, sp_ev_n = sp_n;
+    }
 }
 
 }  // namespace aic
@@ -1383,9 +1545,10 @@ int aic_crop_resize(int device_id, const uint8_t* frame, int h, int w, const flo
     });
 }
 
-int aic_detect(aic_model* mm, const uint8_t* frames, int batch, int h, int w, int mem, float conf, float iou, int max_det,
-               int32_t* num_dets, float* boxes, float* scores, int32_t* labels) {
-    return guarded([&] {
+// aic_detect; n_live >= 0 (aic_detect_live): with a device-side frame count holding n_live in force
+static void detect_frames(aic_model* mm, const uint8_t* frames, int batch, int h, int w, int mem, float conf, float iou, int max_det,
+                          int32_t* num_dets, float* boxes, float* scores, int32_t* labels, int n_live) {
+    {
         AIC_REQUIRE(mm && frames && batch > 0 && h > 0 && w > 0, AIC_ERR_INVALID, "bad argument");
         Model& m = mm->m;
         AIC_REQUIRE(m.kind == KIND_YOLO, AIC_ERR_INVALID, "not a YOLO engine");
@@ -1394,10 +1557,29 @@ int aic_detect(aic_model* mm, const uint8_t* frames, int batch, int h, int w, in
         hipStream_t s = m.dev->s_main;
         const uint8_t* df = stage_frames(m, frames, (size_t)batch * h * w * 3, mem, s, batch == 1);
         const LetterboxGeom g = letterbox_geometry(h, w, m.in_h, m.in_w);
+        DevBuf<int> d_live;
+        const int live_host = n_live;                                     // the upload's source: lives until the stream is through
+        if (n_live >= 0) {
+            d_live.alloc(1);
+            HIP_CHECK(hipMemcpyAsync(d_live.p, &live_host, 4, hipMemcpyHostToDevice, s));
+            m.n_items_dev = d_live.p;
+        }
         m.reduce_cls = true;
+        m.arm_sparse_box(conf);                 // the box branches may run at the anchors this call's NMS will read, and nowhere else
         m.side_ok = true;
-        m.run_frames(df, batch, g, s);
-        m.side_ok = false;
+        try {
+            m.run_frames(df, batch, g, s);
+        } catch (...) {
+            m.side_ok = false, m.n_items_dev = nullptr;
+            (void)hipStreamSynchronize(s);
+            throw;
+        }
+        m.side_ok = false, m.n_items_dev = nullptr;
+        if (n_live >= 0) batch = std::min(batch, n_live);                 // frames at and past the live count were not computed
+        if (batch == 0) {
+            HIP_CHECK(hipStreamSynchronize(s));
+            return;
+        }
         if (batch <= 4 && num_dets && boxes && scores && labels) {
             // the per-frame plugin loop: the NMS kernel stores what it keeps into page-locked host memory itself
             const size_t per = (size_t)max_det * 24;
@@ -1423,6 +1605,67 @@ int aic_detect(aic_model* mm, const uint8_t* frames, int batch, int h, int w, in
         copy_out(scores, m.d_out_scores.p, (size_t)batch * max_det * 4, AIC_HOST, s);
         copy_out(labels, m.d_out_labels.p, (size_t)batch * max_det * 4, AIC_HOST, s);
         HIP_CHECK(hipStreamSynchronize(s));
+    }
+}
+
+int aic_detect(aic_model* mm, const uint8_t* frames, int batch, int h, int w, int mem, float conf, float iou, int max_det,
+               int32_t* num_dets, float* boxes, float* scores, int32_t* labels) {
+    return guarded([&] { detect_frames(mm, frames, batch, h, w, mem, conf, iou, max_det, num_dets, boxes, scores, labels, -1); });
+}
+
+int aic_detect_live(aic_model* mm, const uint8_t* frames, int batch, int n_live, int h, int w, int mem, float conf, float iou, int max_det,
+                    int32_t* num_dets, float* boxes, float* scores, int32_t* labels) {
+    return guarded([&] {
+        AIC_REQUIRE(n_live >= 0, AIC_ERR_INVALID, "bad argument");
+        detect_frames(mm, frames, batch, h, w, mem, conf, iou, max_det, num_dets, boxes, scores, labels, n_live);
+    });
+}
+
+int aic_detect_decode(aic_model* mm, int batch, int h, int w, float conf, float iou, int max_det, int32_t* num_dets, float* boxes,
+                      float* scores, int32_t* labels) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && batch > 0 && h > 0 && w > 0, AIC_ERR_INVALID, "bad argument");
+        Model& m = mm->m;
+        AIC_REQUIRE(m.kind == KIND_YOLO, AIC_ERR_INVALID, "not a YOLO engine");
+        AIC_REQUIRE(m.reduce_cls && batch <= m.last_n, AIC_ERR_INVALID, "no detect run on that many frames to decode again");
+        m.dev->use();
+        hipStream_t s = m.dev->s_main;
+        const LetterboxGeom g = letterbox_geometry(h, w, m.in_h, m.in_w);
+        m.decode_nms(batch, conf, iou, max_det, &g, s);
+        copy_out(num_dets, m.d_numdets.p, (size_t)batch * 4, AIC_HOST, s);
+        copy_out(boxes, m.d_out_boxes_orig.p, (size_t)batch * max_det * 16, AIC_HOST, s);
+        copy_out(scores, m.d_out_scores.p, (size_t)batch * max_det * 4, AIC_HOST, s);
+        copy_out(labels, m.d_out_labels.p, (size_t)batch * max_det * 4, AIC_HOST, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int aic_model_sparse_box(aic_model* mm, int force, int32_t* out) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && mm->m.kind == KIND_YOLO, AIC_ERR_INVALID, "not a YOLO engine");
+        Model& m = mm->m;
+        if (force >= 0) m.sp_force = force != 0;
+        if (!out) return;
+        std::fill(out, out + 8, 0);
+        out[0] = m.sp_listed, out[5] = m.sp_pass, out[6] = m.sbx.ok, out[7] = m.sbx.ok && m.sbx.lead0 >= 0;
+        if (m.sp_pass) {                        // the counts themselves, from the device (what the path choice knows may be a run older)
+            m.dev->use();
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(out + 1, m.d_sp_count.p, 16, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int aic_model_read_det(aic_model* mm, int n, float* boxes, float* max_logit, int32_t* labels) {
+    return guarded([&] {
+        AIC_REQUIRE(mm && mm->m.kind == KIND_YOLO && n > 0 && n <= mm->m.max_items, AIC_ERR_INVALID, "bad argument");
+        Model& m = mm->m;
+        m.dev->use();
+        HIP_CHECK(hipDeviceSynchronize());
+        const size_t ba = (size_t)n * m.n_anchors;
+        if (boxes) HIP_CHECK(hipMemcpy(boxes, m.d_boxes.p, ba * 16, hipMemcpyDeviceToHost));
+        if (max_logit) HIP_CHECK(hipMemcpy(max_logit, m.d_maxlogit.p, ba * 4, hipMemcpyDeviceToHost));
+        if (labels) HIP_CHECK(hipMemcpy(labels, m.d_labels.p, ba * 4, hipMemcpyDeviceToHost));
     });
 }
 

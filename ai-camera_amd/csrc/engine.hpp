@@ -3,6 +3,7 @@
 #include "kernels.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <vector>
 
@@ -134,6 +135,40 @@ struct Model {
     const RowPlan* rb_now = nullptr;              // set around run_ops() by run_frames: the windows in force
     std::vector<char> rb_ran;                     // per op: the last run_frames ran it windowed
     std::vector<RowWindow> rb_ran_win;            // per op: the window it had (the launch's)
+    // ---- sparse box branches: NMS reads boxes[anchor] only at anchors whose max class logit passes its threshold, a few dozen
+    // of a trained detector's 8 400 per frame.  A run ARMED with that threshold (arm_sparse_box: aic_detect, the pipeline) leaves the
+    // box branches' launches out of their place -- level 0's lead and its tail pair, levels 1 and 2's tail pairs -- and, behind the last
+    // head op, lists the candidates on the device from the class tails' max logits (launch_box_candidates) and runs those launches on
+    // the lists (ConvArgs::pix_list): the same layer, the same K order, each pixel's own operand column -- the bits of the dense launch at
+    // every anchor NMS can read.  Nothing the host knows decides a value: the lists hold a whole map, the counts stay on the device.
+    struct SparseBox {
+        bool ok = false;                          // a three-level head whose six branches end in tail pairs
+        int box_tail[3] = {-1, -1, -1};           // op of 22.box{l}.1 (its 1x1 follows)
+        int cls_tail[3] = {-1, -1, -1};           // op of 22.cls{l}.1
+        int lead0 = -1;                           // op of 22.box0.0 where it is a launch of its own that only box0.1 reads; -1: merged, stays dense
+    } sbx;
+    void plan_sparse_box();
+    static float logit_of(float conf) { return (float)std::log((double)conf / (1.0 - (double)conf)); }   // NMS's threshold on the raw logit: ONE function for det_args and the candidate pass
+    void arm_sparse_box(float conf) { sp_armed = conf > 0.f && conf < 1.f, sp_arm_thr = sp_armed ? logit_of(conf) : 0.f; }   // holds for the next run only
+    bool sp_armed = false;
+    int last_n = 0;                               // items of the last run
+    float sp_arm_thr = 0.f;
+    int sp_force = 0;                             // 1: take the lists at any launch size and any count (tests; AICAM_SPARSE_BOX_FORCE=1 sets it at load)
+    DevBuf<int> d_sp_list[4], d_sp_count;         // launch_box_candidates' lists and counts
+    PinBuf<int> h_sp_count;                       // the counts of the last decoded run, copied back behind its NMS ...
+    hipEvent_t sp_ev = nullptr;                   // ... complete once this event is
+    bool sp_ev_pending = false;
+    int sp_dense_runs = 0;                        // large dense launches since load: every 16th is counted again
+    int sp_ev_n = 0;                              // frames the counts in flight were counted over
+    int sp_known[4] = {0, 0, 0, 0}, sp_known_n = 0;   // the last counts read back and the frames they were counted over (0: none yet)
+    // the last run: whether its candidate pass ran (at sp_thr, over sp_n frames), whether it took the lists, and the launches it listed
+    bool sp_pass = false, sp_listed = false;
+    float sp_thr = 0.f;
+    int sp_n = 0;
+    std::vector<char> sp_skip;                    // per op, set around run_range: a launch run_ops leaves out of its place
+    ConvStep sp_steps[4];                         // [l]: level l's box tail pair, [3]: level 0's lead -- as conv_step planned them for the last eligible run
+    bool sp_eligible(size_t op0, int n);          // whether a run of ops [op0, end) on n frames can list its box branches; fills sp_steps
+    void sparse_box_pass(int n, float thr, bool lists, const int* n_dev, hipStream_t s);
     ~Model();
     // YOLO post-processing on the buffers left by run()
     DetArgs det_args(int batch, float conf, float iou, int max_det, const LetterboxGeom* g);

@@ -83,6 +83,20 @@ struct DetArgs {
     int* out_labels;   // [B,max_det]
 };
 void launch_decode(const DetArgs& a, hipStream_t s);
+// The candidate pass of the sparse box branches (three-level heads): from the max logits of a run, the pixels whose boxes NMS will read
+// at logit_thr.  list[l], l < 3: level l's candidate pixels; list[3]: the in-map pixels of the 3 x 3 neighbourhoods of level 0's
+// candidates, each once.  Entries are linear pixels img * h * w + cell of the level's full map (ConvArgs::pix_list), in no fixed order;
+// count[4] (device) is zeroed and filled by the launch.  list[l] holds batch * h[l] * w[l] entries, list[3] as many as list[0].
+struct BoxListArgs {
+    const float* max_logit;        // [batch, n_anchors]
+    float logit_thr;
+    int batch, n_anchors;
+    const int* n_dev;              // optional device-side live frame count: frames at or past it contribute nothing
+    int h[3], w[3], a0[3];
+    int* list[4];
+    int* count;
+};
+void launch_box_candidates(const BoxListArgs& a, hipStream_t s);
 // deepsort_tracker.py:88-101 on the device: order-preserving confidence / class filter of a launch group's NMS outputs, compacted
 // into the arrays crop + ReID + the association epochs read (kernels_det.hip)
 struct DetFilterArgs {

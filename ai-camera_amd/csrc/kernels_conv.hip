@@ -32,7 +32,10 @@ namespace aic {
 //  * im2col address = per-row base pointer + one per-thread tap offset; in-bounds is a precomputed
 //    bit per (row, tap).
 //  * TAIL: the conv's output feeds a 1x1 conv (a.w_tail) that runs in this kernel's epilogue (tail_1x1, conv_common.hpp)
-template <typename T, int MT, int NT, int WM, int WN, int NSTAGE, bool TAIL = false>
+//  * LIST: GEMM row m stands for output pixel a.pix_list[m] of the full map (ConvArgs::pix_list), the first a.pix_count[0] rows are live.
+//    Only the row set-up and the epilogue's pixel indices know: a row's im2col base, its tap-validity bits, its stores and its tail's
+//    anchor are those of its own pixel, wherever its tile neighbours lie; K walk, zero page and MFMA sequence are the dense kernel's
+template <typename T, int MT, int NT, int WM, int WN, int NSTAGE, bool TAIL = false, bool LIST = false>
 __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const ConvArgs a) {
     constexpr int CH = 16 / (int)sizeof(T);
     constexpr int BKE = 4 * CH;
@@ -53,7 +56,15 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
     const int lane = t & 63, wv = t >> 6;
     const int slot = t & 3, r0 = t >> 2;
     const int kc = slot ^ lds_swz(r0);         // K-chunk this thread fetches (source-side swizzle)
-    const int M = a.n_dev ? min(a.M, min(a.n_dev[0], a.M / (a.Ho * a.Wo)) * (a.Ho * a.Wo)) : a.M;     // device-side item count: the grid was sized for a bound
+    const int Mmap = a.n_dev ? min(a.M, min(a.n_dev[0], a.M / (a.Ho * a.Wo)) * (a.Ho * a.Wo)) : a.M;     // device-side item count: the grid was sized for a bound
+    const int M = LIST ? max(0, min(a.pix_count[0], Mmap)) : Mmap;      // LIST: live rows of the list; pixels live in [0, Mmap)
+    const int lim = LIST ? Mmap : M;                                    // a row's pixel index is live below this
+    // LIST: the pixel of GEMM row m; a dead row -- past the live count, or an entry outside the map -- answers Mmap
+    auto list_row = [&](int m) -> int {
+        if (m >= M) return Mmap;
+        const int p = a.pix_list[m];
+        return (unsigned)p < (unsigned)Mmap ? p : Mmap;
+    };
     int tbx, tby;
     if (!xcd_tile_xy_live(a.xcd_map, (M + BM - 1) / BM, tbx, tby)) return;
     const int m0 = tbx * BM;
@@ -70,10 +81,11 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
     const float inv_howo = 1.0f / (float)HoWo, inv_wo = 1.0f / (float)a.Wo;
 #pragma unroll
     for (int i = 0; i < A_PER; ++i) {
-        const int m = m0 + r0 + RP * i;
+        int m = m0 + r0 + RP * i;
+        if constexpr (LIST) m = list_row(m);
         unsigned mk = 0;
         const T* rp = zero;
-        if (m < M) {
+        if (m < lim) {
             int img, rem, oh, ow;
             fast_divmod(m, HoWo, inv_howo, img, rem);
             fast_divmod(rem, a.Wo, inv_wo, oh, ow);
@@ -168,8 +180,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
         // split source (ConvArgs::xs; 1x1 / 1 / 0, memory order only): K-steps 0 .. ssteps - 1 read the half-resolution tensor
         const int ssteps = (a.xs && !cmaj) ? a.Cs / BKE : 0;
         auto xs_row = [&](int i) -> const T* {
-            const int m = m0 + r0 + RP * i;
-            if (m >= M) return zero;
+            int m = m0 + r0 + RP * i;
+            if constexpr (LIST) m = list_row(m);
+            if (m >= lim) return zero;
             int img, rem, oh, ow;
             fast_divmod(m, HoWo, inv_howo, img, rem);
             fast_divmod(rem, a.Wo, inv_wo, oh, ow);
@@ -184,9 +197,10 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
                 const int c2 = cc - 1;
 #pragma unroll
                 for (int i = 0; i < A_PER; ++i) {
-                    const int m = m0 + r0 + RP * i;
+                    int m = m0 + r0 + RP * i;
+                    if constexpr (LIST) m = list_row(m);
                     const T* p = zero;
-                    if (m < M) {
+                    if (m < lim) {
                         int img, rem, oh, ow;
                         fast_divmod(m, HoWo, inv_howo, img, rem);
                         fast_divmod(rem, a.Wo, inv_wo, oh, ow);
@@ -340,8 +354,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
     int mrow[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-        const int m = m0 + (wm * MT + i) * 16 + r;
-        mrow[i] = m < M ? m : -1;
+        int m = m0 + (wm * MT + i) * 16 + r;
+        if constexpr (LIST) m = list_row(m);                       // mrow is the PIXEL: stores, residual and the tail's anchor land at its true position
+        mrow[i] = m < lim ? m : -1;
     }
     if constexpr (TAIL) {
         static_assert(sizeof(T) == 2 && WN == 1, "the tail needs fp16 and a wave that owns every channel of its pixels");
@@ -351,13 +366,14 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_dma_kernel(const Conv
     }
 }
 
-template <typename T, int MT, int NT, int WM, int WN, int NSTAGE, bool TAIL = false>
+template <typename T, int MT, int NT, int WM, int WN, int NSTAGE, bool TAIL = false, bool LIST = false>
 static void launch_dma(const ConvArgs& a, hipStream_t s) {
     constexpr int RP = 16 * WM * WN;
     constexpr int BM = WM * MT * 16, BN = WN * NT * 16, BNP = (BN + RP - 1) / RP * RP;
     dim3 grid(ceil_div(a.M, BM), ceil_div(a.Cout, BN));
     const size_t lds = (size_t)NSTAGE * (BM + BNP) * 64;
-    auto kfn = conv_igemm_dma_kernel<T, MT, NT, WM, WN, NSTAGE, TAIL>;
+    AIC_REQUIRE(LIST == (a.pix_list != nullptr) && (!LIST || a.pix_count), AIC_ERR_INVALID, "conv plan: pixel list and kernel form disagree");
+    auto kfn = conv_igemm_dma_kernel<T, MT, NT, WM, WN, NSTAGE, TAIL, LIST>;
     if (lds > 64 * 1024) set_lds_limit(kfn, lds);
     hipLaunchKernelGGL(kfn, grid, dim3(64 * WM * WN), lds, s, a);
     KCHECK();
@@ -369,6 +385,11 @@ static void launch_dma(const ConvArgs& a, hipStream_t s) {
 // The LDS-DMA tiles plan_conv hands out (conv_plan.cpp): fp32 engines run the 4-wave tiles only, the 8-wave and 144-channel ones and the
 // tail forms are fp16.
 static void launch_conv_dma(int dtype, const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+    if (p.list) {                               // the pixel-list forms (ConvArgs::pix_list): 128 px x 64 ch, with and without the decoding tail
+        AIC_REQUIRE(dtype == AIC_F16 && p.mt == 2 && p.nt == 4 && p.wm == 4 && p.wn == 1 && p.nstage == 4, AIC_ERR_INVALID, "conv plan: no pixel-list instantiation for this tile");
+        if (p.tail) return launch_dma<half_t, 2, 4, 4, 1, 4, true, true>(a, s);
+        return launch_dma<half_t, 2, 4, 4, 1, 4, false, true>(a, s);
+    }
 #define DMA(T, MT, NT, WM, WN, NS, TAIL)                                                                                        \
     if (sizeof(T) == (dtype == AIC_F16 ? 2u : 4u) && p.mt == MT && p.nt == NT && p.wm == WM && p.wn == WN && p.nstage == NS && \
         p.tail == TAIL)                                                                                                        \

@@ -94,6 +94,65 @@ __global__ void decode_kernel(const DetArgs a) {
     a.labels[idx] = arg;
 }
 
+// ---- candidate pass of the sparse box branches (BoxListArgs, kernels.hpp): one thread per (image, anchor) over the max logits the class
+// tails left.  An anchor NMS will select (max logit >= logit_thr: select_sort_nms_kernel's own compare) appends its pixel to its level's
+// list; a level-0 pixel with such an anchor in its 3 x 3 neighbourhood (itself included) appends itself to the neighbour list -- every
+// pixel is written by its own thread, once, so the lists hold no duplicates without any mark array.  Appends are counted per block in
+// LDS and claimed with one global atomic per block and list: the order inside a list varies from run to run, its set does not.
+// Frames at or past the live count contribute nothing.  The lists hold a whole map each, so no count can overflow one.
+__global__ __launch_bounds__(256) void box_candidates_kernel(const BoxListArgs a) {
+    __shared__ int s_n[4], s_base[4];
+    const int t = threadIdx.x, lane = t & 63;
+    if (t < 4) s_n[t] = 0;
+    __syncthreads();
+    const long idx = (long)blockIdx.x * blockDim.x + t;
+    const int live = a.n_dev ? min(max(a.n_dev[0], 0), a.batch) : a.batch;
+    const bool in = idx < (long)a.batch * a.n_anchors;
+    const int img = in ? (int)(idx / a.n_anchors) : 0;
+    const int an = in ? (int)(idx - (long)img * a.n_anchors) : 0;
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < 3; ++k)
+        if (an >= a.a0[k]) l = k;
+    const int cell = an - a.a0[l];
+    const bool on = in && img < live;
+    const float* ml = a.max_logit + (size_t)img * a.n_anchors;
+    const bool cand = on && ml[an] >= a.logit_thr;
+    bool nb = false;
+    if (on && l == 0) {
+        const int gy = cell / a.w[0], gx = cell - gy * a.w[0];
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int y = gy + dy, x = gx + dx;
+                if (y >= 0 && y < a.h[0] && x >= 0 && x < a.w[0] && ml[a.a0[0] + y * a.w[0] + x] >= a.logit_thr) nb = true;
+            }
+    }
+    int pos[2] = {-1, -1};                      // place inside the block's share of [0] the level list, [1] the neighbour list
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool pass = k < 3 ? (cand && l == k) : nb;
+        const unsigned long long bal = __ballot(pass);
+        int base = 0;
+        if (lane == 0 && bal) base = atomicAdd(&s_n[k], __popcll(bal));
+        base = __shfl(base, 0);
+        if (pass) pos[k == 3] = base + __popcll(bal & ((1ull << lane) - 1ull));
+    }
+    __syncthreads();
+    if (t < 4 && s_n[t]) s_base[t] = atomicAdd(&a.count[t], s_n[t]);
+    __syncthreads();
+    const int pix = img * (a.h[l] * a.w[l]) + cell;       // linear pixel of the level's full map (ConvArgs::pix_list)
+    if (cand) a.list[l][s_base[l] + pos[0]] = pix;
+    if (nb) a.list[3][s_base[3] + pos[1]] = pix;
+}
+
+void launch_box_candidates(const BoxListArgs& a, hipStream_t s) {
+    const long tot = (long)a.batch * a.n_anchors;
+    if (tot <= 0) return;
+    HIP_CHECK(hipMemsetAsync(a.count, 0, 4 * sizeof(int), s));
+    hipLaunchKernelGGL(box_candidates_kernel, dim3(ceil_div(tot, 256)), dim3(256), 0, s, a);
+    KCHECK();
+}
+
 __device__ __forceinline__ unsigned int ordered_bits(float f) {
     unsigned int u = __float_as_uint(f);
     if (u == 0x80000000u) u = 0u;                        // -0.0 == +0.0: the two zeros tie and the anchor index decides (nets_oracle.nms)

@@ -400,6 +400,7 @@ struct Pipeline {
         const uint8_t* f0 = ring.p + (size_t)slot * frame_bytes;
         if (pipe_times) HIP_CHECK(hipEventRecord(c.t_begin, s));
         c.ln->yolo->reduce_cls = true;           // the pipeline only ever decodes: the class tails store max logit + label themselves
+        c.ln->yolo->arm_sparse_box(prm.conf_thresh);     // ... at this threshold: the box branches may run at NMS's candidates only (engine.hpp)
         c.ln->yolo->run_frames(f0, frames, geom, s);
         if (gmc) {                               // the group's gray levels, while its ring slots are this group's (this context is idle)
             c.d_gray.ensure((size_t)frames * gmc->g.level);

@@ -210,7 +210,22 @@ class HipEngine:
         return {"full": bool(out[0]), "lo": int(out[1]), "hi": int(out[2]), "rows": int(out[3]), "windowed": bool(out[4]),
                 "win_y0": int(out[5]), "win_rows": int(out[6]), "slots": int(out[7])}
 
-    def detect_np(self, frames_bgr, conf=None, iou=None, max_det=None):
+    def sparse_box(self, force=None):
+        """What the last run did with the detector's box branches (aic_model_sparse_box, include/aicam.h); force: True / False sets
+        whether every eligible run takes the lists."""
+        out = np.zeros(8, np.int32)
+        L.call("aic_model_sparse_box", self._h, -1 if force is None else int(bool(force)), L.ptr(out))
+        return {"listed": bool(out[0]), "counts": tuple(int(v) for v in out[1:5]), "counted": bool(out[5]), "shape_ok": bool(out[6]),
+                "lead0": bool(out[7])}
+
+    def read_det_np(self, n):
+        """-> (boxes [n, A, 4], max logit [n, A], labels [n, A]) of the detector workspace after the last run (aic_model_read_det)."""
+        b, m, l = np.zeros((n, self.n_anchors, 4), np.float32), np.zeros((n, self.n_anchors), np.float32), np.zeros((n, self.n_anchors), np.int32)
+        L.call("aic_model_read_det", self._h, int(n), L.ptr(b), L.ptr(m), L.ptr(l))
+        return b, m, l
+
+    def detect_np(self, frames_bgr, conf=None, iou=None, max_det=None, n_live=None):
+        """n_live: with a device-side frame count holding n_live in force (aic_detect_live; tests)."""
         f = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
         if f.ndim == 3:
             f = f[None]
@@ -218,7 +233,20 @@ class HipEngine:
         md = int(max_det or self.max_det)
         nd = np.zeros(b, np.int32)
         boxes, scores, labels = np.zeros((b, md, 4), np.float32), np.zeros((b, md), np.float32), np.zeros((b, md), np.int32)
-        L.call("aic_detect", self._h, L.ptr(f), b, h, w, L.HOST, float(conf if conf is not None else self.conf_thresh),
+        tail = (float(conf if conf is not None else self.conf_thresh), float(iou if iou is not None else self.iou_thresh), md,
+                L.ptr(nd), L.ptr(boxes), L.ptr(scores), L.ptr(labels))
+        if n_live is None:
+            L.call("aic_detect", self._h, L.ptr(f), b, h, w, L.HOST, *tail)
+        else:
+            L.call("aic_detect_live", self._h, L.ptr(f), b, int(n_live), h, w, L.HOST, *tail)
+        return nd, boxes, scores, labels
+
+    def detect_decode_np(self, n, hw, conf=None, iou=None, max_det=None):
+        """Decode + NMS of the last detect_np run again at other thresholds, frames 0 .. n-1 of hw = (h, w) (aic_detect_decode)."""
+        md = int(max_det or self.max_det)
+        nd = np.zeros(n, np.int32)
+        boxes, scores, labels = np.zeros((n, md, 4), np.float32), np.zeros((n, md), np.float32), np.zeros((n, md), np.int32)
+        L.call("aic_detect_decode", self._h, int(n), int(hw[0]), int(hw[1]), float(conf if conf is not None else self.conf_thresh),
                float(iou if iou is not None else self.iou_thresh), md, L.ptr(nd), L.ptr(boxes), L.ptr(scores), L.ptr(labels))
         return nd, boxes, scores, labels
 

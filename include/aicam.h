@@ -96,6 +96,16 @@ int aic_model_conv_plan_live(aic_model* m, int op, int n, int32_t* out);
  * frames ran the launch that covers this op on a row window, [5] / [6] that window's first row and row count, [7] item slots whose
  * constant rows are in place (0: the next run on frames computes the full maps). */
 int aic_model_row_band(aic_model* m, int op, int src_h, int src_w, int32_t* out);
+/* Sparse box branches (csrc/engine.hpp): a detect run (aic_detect, the pipeline) may run the detector's box branches only at the anchors
+ * its NMS will read, from lists made on the device -- the same bits at those anchors, which path a run took changes time only.
+ * force: 1 = every eligible run takes the lists, at any launch size and any count (tests), 0 = the library chooses, < 0 = leave as it is.
+ * out (may be NULL) [8], about the last run of the engine: [0] 1 = its box branches ran on the lists, [1..3] candidates of levels
+ * 0 .. 2 and [4] listed neighbourhood pixels of level 0, as the device counted them (0 when no candidate pass ran), [5] 1 = a
+ * candidate pass ran, [6] 1 = the engine's head has the shape the lists need, [7] 1 = level 0's first box conv is listed as well. */
+int aic_model_sparse_box(aic_model* m, int force, int32_t* out);
+/* Tests: the detector workspace as the last run and its decode left it, frames 0 .. n-1 (host outputs, each may be NULL):
+ * boxes[n,A,4], max class logit[n,A], label[n,A].  After a run that took the lists only candidate anchors hold that run's boxes. */
+int aic_model_read_det(aic_model* m, int n, float* boxes, float* max_logit, int32_t* labels);
 int aic_model_destroy(aic_model* m);
 /* kind, input H/W, classes (YOLO) or feature dim (ReID), anchors per image, conv FLOPs per item */
 int aic_model_info(const aic_model* m, int* kind, int* in_h, int* in_w, int* out_dim,
@@ -166,6 +176,15 @@ int aic_crop_resize(int device, const uint8_t* frame_bgr, int h, int w, const fl
 int aic_detect(aic_model* yolo, const uint8_t* frames_bgr, int batch, int h, int w, int mem,
                float conf_thresh, float iou_thresh, int max_det, int32_t* num_dets, float* boxes_xyxy,
                float* scores, int32_t* labels);
+/* Decode + NMS of the last aic_detect run again, at another threshold, on what that run left on the device (no conv runs): the outputs
+ * aic_detect would have given at these thresholds for frames 0 .. batch-1 of that run (frames of h x w). */
+int aic_detect_decode(aic_model* yolo, int batch, int h, int w, float conf_thresh, float iou_thresh, int max_det,
+                      int32_t* num_dets, float* boxes_xyxy, float* scores, int32_t* labels);
+/* Tests: aic_detect with a device-side frame count holding n_live in force, as launches sized for a bound run (ConvArgs::n_dev):
+ * frames at and past n_live are not computed and their outputs are left as the caller passed them. */
+int aic_detect_live(aic_model* yolo, const uint8_t* frames_bgr, int batch, int n_live, int h, int w, int mem,
+                    float conf_thresh, float iou_thresh, int max_det, int32_t* num_dets, float* boxes_xyxy,
+                    float* scores, int32_t* labels);
 
 /* crop -> ReID engine (deepsort_tracker.py:104-113 + reid_model.py:67-126) for one frame. */
 int aic_reid_embed(aic_model* reid, const uint8_t* frame_bgr, int h, int w, int mem,

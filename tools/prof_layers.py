@@ -122,6 +122,14 @@ def main(d, frames=16, crops=480, top=30, fused_stem=1, fused_yolo_stem=1, fused
             else:
                 merged.append(L)
         layers = merged
+    if fused_block and not os.environ.get("AICAM_NO_SPARSE_BOX"):     # sparse box branches: level 0's box lead and the three box tail pairs run behind the last head op, on the candidate lists
+        listed = ["22.box0.0", "22.box0.1+.2", "22.box1.1+.2", "22.box2.1+.2"]
+        moved = {L[1]: L for L in layers if L[0] == "yolo" and L[1] in listed}
+        if len(moved) == len(listed):
+            last = max(i for i, L in enumerate(layers) if L[0] == "yolo")
+            keep = [L for L in layers[:last + 1] if L[1] not in moved]
+            # M = 0: the rows a list launch runs are counted on the device, the trace does not show them (no rate for these rows)
+            layers = keep + [("yolo", n + " (list)", 0, moved[n][3], moved[n][4]) for n in listed] + layers[last + 1:]
     per = len(layers)
     # a launch group starts at its (fused) YOLO stem; groups of other sizes (tapered tail of a call: fewer frames, and below
     # the fused-block threshold two more launches) are dropped: keep the groups with `per` conv launches and the modal grid
