@@ -32,6 +32,11 @@ Deliberate changes from upstream (also in DESIGN.md, section 17):
      anti-diagonal (0.58 > 0.35) and the IoU check then drops both pairs.  Both modes are specified here and the device follows each.
 
 Every threshold is rounded to fp32 once and every comparison is made in fp32.
+
+Recording hook (tests/ocsort_edge_cases.py): ``OCSort(record=[])`` appends one dict per non-empty association problem -- frame, stage
+("stage1" / "byte" / "ocr"), the IoU matrix, the OCM term (stage 1), the cost matrix, the threshold, how it was solved ("read_off" /
+"lsap" / "gate_shut": the BYTE / OCR gate ``max > th`` stayed shut) and the rows' detection indices and columns' track ids.  It
+changes no result.
 """
 from __future__ import annotations
 
@@ -296,16 +301,20 @@ def ocm_term(dets, scores, prev, valid, vel, inertia):
     return np.where(np.asarray(valid, dtype=bool)[None, :], t, F32(0)).astype(F32)
 
 
-def associate(dets, scores, trks, thr, vel, prev, valid, inertia, lsap_fast=True, stats=None):
-    """Stage 1.  Returns det -> track (or -1) for each detection."""
+def associate(dets, scores, trks, thr, vel, prev, valid, inertia, lsap_fast=True, stats=None, record=None):
+    """Stage 1.  Returns det -> track (or -1) for each detection.  `record` (a list, test hook) takes one dict per non-empty problem."""
     n, t = len(dets), len(trks)
     m = np.full(n, -1, dtype=np.int64)
     if n == 0 or t == 0:
         return m
     iou = iou_matrix(dets, trks)
     pairs = read_off(iou, thr) if lsap_fast else None
+    ocm = ocm_term(dets, scores, prev, valid, vel, inertia) if pairs is None or record is not None else None
+    cost = None if ocm is None else -(iou + ocm)
+    if record is not None:
+        record.append(dict(stage="stage1", iou=iou.copy(), ocm=ocm, cost=cost, th=F32(thr), solved="lsap" if pairs is None else "read_off"))
     if pairs is None:
-        pairs = linear_assignment(-(iou + ocm_term(dets, scores, prev, valid, vel, inertia)))
+        pairs = linear_assignment(cost)
         if stats is not None:
             stats["n_lsap"] += 1
             stats["max_side"] = max(stats["max_side"], n, t)
@@ -319,18 +328,23 @@ def associate(dets, scores, trks, thr, vel, prev, valid, inertia, lsap_fast=True
 
 class OCSort:
     def __init__(self, det_thresh=0.6, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3, inertia=0.2, use_byte=False,
-                 first_track_id=1, lsap_fast=True, oru=True):
+                 first_track_id=1, lsap_fast=True, oru=True, record=None):
         self.det_thresh, self.iou_threshold, self.inertia = F32(det_thresh), F32(iou_threshold), F32(inertia)
         self.max_age, self.min_hits, self.delta_t, self.use_byte = int(max_age), int(min_hits), int(delta_t), bool(use_byte)
         self.trackers = []
         self.frame_count = 0
         self.next_id = first_track_id
         self.lsap_fast, self.oru = lsap_fast, oru
+        self.record = record                                      # test hook: a list that takes every non-empty association problem
         self.stats = dict(n_fast=0, n_lsap=0, max_side=0, n_oru=0, max_gap=0, n_ocr=0, n_byte=0)
 
-    def _second(self, iou, rows, cols, take):
+    def _second(self, iou, rows, cols, take, stage=None):
         """BYTE / OCR stage: gate on the best IoU, LSAP on -iou, keep pairs at or above the threshold."""
-        if iou.size == 0 or not iou.max() > self.iou_threshold:
+        shut = iou.size == 0 or not iou.max() > self.iou_threshold
+        if self.record is not None and iou.size:
+            self.record.append(dict(frame=self.frame_count, stage=stage, iou=iou.copy(), ocm=None, cost=-iou, th=self.iou_threshold,
+                                    solved="gate_shut" if shut else "lsap", dets=np.array(rows), tracks=[self.trackers[c].id for c in cols]))
+        if shut:
             return 0
         self.stats["n_lsap"] += 1
         self.stats["max_side"] = max(self.stats["max_side"], *iou.shape)
@@ -369,7 +383,9 @@ class OCSort:
         last = np.array([t.last_observation for t in keep], dtype=F32).reshape(-1, 4)
 
         tdet = np.full(T, -1, dtype=np.int64)                     # track -> detection (index into the frame)
-        m = associate(box[hi], scores[hi], trks, self.iou_threshold, vel, prev, valid, self.inertia, self.lsap_fast, self.stats)
+        m = associate(box[hi], scores[hi], trks, self.iou_threshold, vel, prev, valid, self.inertia, self.lsap_fast, self.stats, self.record)
+        if self.record and "frame" not in self.record[-1]:
+            self.record[-1].update(frame=self.frame_count, dets=hi.copy(), tracks=[t.id for t in keep])
         for r, c in enumerate(m):
             if c >= 0:
                 tdet[c] = hi[r]
@@ -383,11 +399,11 @@ class OCSort:
         if self.use_byte and len(lo) > 0:
             ut = np.flatnonzero(tdet < 0)
             if len(ut):
-                self.stats["n_byte"] += self._second(iou_matrix(box[lo], trks[ut]), lo, ut, take)
+                self.stats["n_byte"] += self._second(iou_matrix(box[lo], trks[ut]), lo, ut, take, "byte")
         ud = np.array([d for d in hi if dfree[d]], dtype=np.int64)
         ut = np.flatnonzero(tdet < 0)
         if len(ud) and len(ut):
-            self.stats["n_ocr"] += self._second(iou_matrix(box[ud], last[ut]), ud, ut, take)
+            self.stats["n_ocr"] += self._second(iou_matrix(box[ud], last[ut]), ud, ut, take, "ocr")
 
         for t, d in zip(keep, tdet):
             if d < 0:
