@@ -9,6 +9,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _bank_io as IO
 from . import _lib as L
 from . import config
 
@@ -119,19 +120,6 @@ class TrackColours:
             self.failed.setdefault(int(s), f"stream {s} stopped with libaicam error {int(out[4][s])} (reset({s}) starts it afresh)")
         return ColourResult(*out, dict(self.failed))
 
-    @staticmethod
-    def _memory(a, what, dtype):
-        """(pointer, AIC_HOST / AIC_DEVICE, keep-alive) of a NumPy array or a contiguous torch tensor."""
-        if isinstance(a, np.ndarray):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            return L.ptr(a), L.HOST, a
-        if str(a.dtype) != "torch." + np.dtype(dtype).name or not a.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous {np.dtype(dtype).name} tensor")
-        if a.is_cuda:
-            import torch
-            torch.cuda.current_stream(a.device).synchronize()  # the library reads it on its own stream
-        return C.c_void_p(a.data_ptr()), L.DEVICE if a.is_cuda else L.HOST, a
-
     def update(self, frames, rows, counts=None, cap=16):
         """frames: uint8 [ticks, streams, H, W, 3] BGR, tick-major, a NumPy array or a torch tensor (host or device).  rows: per tick,
         per stream an [n, 6] int32 array (x1 y1 x2 y2 id cls) -- or ONE array / torch tensor [rows, 6] holding them in that order, with
@@ -142,35 +130,11 @@ class TrackColours:
         if len(shape) != 5 or shape[1:] != (self.streams, self.frame_h, self.frame_w, 3):
             raise ValueError(f"frames of shape {shape}, not [ticks, {self.streams}, {self.frame_h}, {self.frame_w}, 3]")
         ticks = shape[0]
-        f_ptr, f_mem, f_keep = self._memory(frames, "frames", np.uint8)
+        f_ptr, f_mem, f_keep = IO.memory(frames, "frames", np.uint8)
         if counts is None:
-            if len(rows) != ticks or any(len(r) != self.streams for r in rows):
-                raise ValueError(f"rows must be [ticks = {ticks}][streams = {self.streams}] arrays")
-            flat = [np.asarray(r, dtype=np.int32).reshape(-1, 6) for tick in rows for r in tick]
-            counts = np.array([len(r) for r in flat], np.int32)
-            rows = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 6), np.int32))
-        r_ptr, r_mem, r_keep = self._memory(rows, "rows", np.int32)
-        n_rows = r_keep.size // 6 if isinstance(r_keep, np.ndarray) else r_keep.numel() // 6
-        if getattr(counts, "is_cuda", False):                    # device counts: the library fetches them for its checks
-            if r_mem != L.DEVICE:
-                raise ValueError("counts on the device need rows on the device")
-            c_ptr, _, c_keep = self._memory(counts, "counts", np.int32)
-            n_counts, total = counts.numel(), int(counts.sum().item())
-            if n_rows < total:
-                raise ValueError(f"{n_rows} rows, counts sum to {total}")
-        else:
-            c_keep = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-            n_counts, total = len(c_keep), int(c_keep.sum())
-            if n_rows < total:
-                raise ValueError(f"{n_rows} rows, counts sum to {total}")
-            if r_mem == L.DEVICE:                                # counts and rows travel together
-                import torch
-                c_keep = torch.from_numpy(c_keep).to(rows.device)
-                c_ptr = C.c_void_p(c_keep.data_ptr())
-            else:
-                c_ptr = L.ptr(c_keep)
-        if n_counts != ticks * self.streams:
-            raise ValueError("counts must name every frame of the call")
+            rows, counts = IO.flat_rows(rows, ticks, self.streams)
+        r_ptr, r_mem, r_keep = IO.memory(rows, "rows", np.int32)
+        c_ptr, c_keep, total = IO.counts_for(r_keep, counts, r_mem, ticks, self.streams, need_total=True)   # row_tags is sized by it
         out = self._outputs(cap, total)
         L.call("aic_colours_update", self._h, f_ptr if ticks else None, f_mem, ticks, c_ptr if ticks else None, r_ptr, r_mem, cap,
                *(L.ptr(x) for x in out))
@@ -179,9 +143,7 @@ class TrackColours:
     def update_tuples(self, frames, tracks, cap=16):
         """As update(), from the 7-tuples (x1, y1, x2, y2, track_id, class_name, conf) the trackers return: tracks[tick][stream] is a list
         of tuples."""
-        ids = {n: i for i, n in enumerate(config.CLASSES)}
-        return self.update(frames, [[np.array([[t[0], t[1], t[2], t[3], t[4], ids.get(t[5], -1)] for t in fr], np.int64).reshape(-1, 6).astype(np.int32)
-                                     for fr in tick] for tick in tracks], cap=cap)
+        return self.update(frames, IO.rows_from_tuples(tracks), cap=cap)
 
     def drain(self, cap=16):
         """The ENDED tracks still waiting (result.pending of an earlier call), at most cap per stream."""

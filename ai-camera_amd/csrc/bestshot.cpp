@@ -1,7 +1,6 @@
 // bestshot.cpp -- the best-shot object (bestshot.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_bestshot.hip or the call raises.
 #include "bestshot.hpp"
-#include "row_stage.hpp"
 
 #include <algorithm>
 
@@ -25,18 +24,11 @@ void bestshot_check_params(int device, const aic_bestshot_config* p) {
 }
 
 BestShot::BestShot(int device, const aic_bestshot_config& p)
-    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.thumb_w, p.thumb_h, p.max_tracks, p.forget_after, p.region, p.head_q8, p.pad, p.min_w, p.min_h},
-      reset_pending(p.streams, 1), stop(p.streams, 0) {}
-
-void BestShot::reset(int stream) {
-    AIC_REQUIRE(stream >= 0 && stream < g.streams, AIC_ERR_INVALID, "stream outside the best-shot bank");
-    stop[stream] = 0;
-    reset_pending[stream] = 1;
-}
+    : SlotBank(device, p.streams, p.frame_h, p.frame_w),
+      g{p.streams, p.frame_h, p.frame_w, p.thumb_w, p.thumb_h, p.max_tracks, p.forget_after, p.region, p.head_q8, p.pad, p.min_w, p.min_h} {}
 
 void BestShot::touch_device() {
-    if (!dev) dev = &device(device_id);
-    dev->use();
+    use_device();
     if (!d_state.p) {
         grow(d_slot_thumbs, (size_t)g.streams * g.max_tracks * thumb_bytes(), "the resident slot thumbnails");
         grow(d_state, (size_t)g.streams * BS_ST_INTS, "the slot tables");
@@ -50,75 +42,44 @@ static void check_outputs(int cap, const int32_t* n_final, const int32_t* events
     AIC_REQUIRE(cap == 0 || (events && thumbs), AIC_ERR_INVALID, "NULL events or thumbs");
 }
 
-// outputs of a call, ints: n_final[S] | pending[S] | status[S] | (16-byte aligned) events[S, cap, 16]
-static size_t out_events_at(int S) { return ((size_t)3 * S + 3) / 4 * 4; }
+SlotOut BestShot::outputs(int cap) {
+    const SlotOut so = out(cap, BS_EVENT_INTS);
+    grow(d_out_thumbs, std::max<size_t>(16, (size_t)g.streams * cap * thumb_bytes()), "the output thumbnails");
+    return so;
+}
+
+void BestShot::walk(const int* d_off, int n_ticks, const int* d_rows, int cand_base, const BankStage& bs, int first, int cap, const SlotOut& so) {
+    int* o = d_out.p;
+    launch_bestshot_walk(d_off, n_ticks, d_rows, d_info.p, d_cand.p, cand_base, d_stage.p, d_stage.p + bs.o_mode, first, g, d_state.p, d_slot_thumbs.p,
+                         cap, o, o + so.o_pending, o + so.o_status, o + so.o_events, d_out_thumbs.p, dev->s_trk);
+}
 
 void BestShot::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap,
                       int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
     const int S = g.streams;
-    AIC_REQUIRE(ticks >= 0 && ticks <= BS_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
-    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
-    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
+    const long F = check_call(ticks, BS_TICKS_MAX, frames_mem, rows_mem);
     check_outputs(cap, n_final, events, thumbs, pending);
-    const long F = (long)ticks * S;
-    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
     AIC_REQUIRE(F == 0 || (frames && counts), AIC_ERR_INVALID, "NULL frames or counts");
-    auto check_counts = [&](const int32_t* c) {
-        const long total = check_row_counts(c, F, BS_ROWS_MAX, rows6);
-        AIC_REQUIRE(total <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
-        return total;
-    };
-    long total = 0;
-    if (rows_mem == AIC_HOST && F) total = check_counts(counts);
-
-    touch_device();
+    const long total = count_rows(counts, F > 0, F, BS_ROWS_MAX, rows6, rows_mem, [&] { touch_device(); }, [](long t) {
+        AIC_REQUIRE(t <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
+    });
     hipStream_t st = dev->s_trk;
-    if (rows_mem == AIC_DEVICE && F) total = check_counts(counts = fetch_counts(h_counts, counts, F, st));   // the counts decide the launches
-    // ---- staging: reset[S] | mode[S] | frame_off[F + 1] | rows (host memory only; row_stage.hpp)
-    const size_t o_mode = S, o_off = 2 * (size_t)S;
-    const RowStage rs(o_off, o_off + F + 1, total, rows_mem == AIC_HOST);
-    h_stage.ensure(rs.n_ints);
-    grow(d_stage, rs.n_ints, "the staged rows");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[o_mode + s] = BS_MODE_DRAIN;
-    rs.fill(h, counts, F, rows6);
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* d_rows = rs.d_rows(d_stage.p, rows6);
-    const int* d_off = d_stage.p + o_off;
+    const BankStage bs = upload_update(F, counts, total, rows6, rows_mem == AIC_HOST);
+    const int* d_rows = bs.d_rows(d_stage.p, rows6);
+    const int* d_off = d_stage.p + bs.o_off;
     grow(d_info, std::max<size_t>(8, (size_t)total * 8), "the scored rows");
-    const size_t o_ev = out_events_at(S);
-    grow(d_out, o_ev + (size_t)S * cap * BS_EVENT_INTS, "the events");
-    grow(d_out_thumbs, std::max<size_t>(16, (size_t)S * cap * thumb_bytes()), "the output thumbnails");
-    int* o = d_out.p;
-
+    const SlotOut so = outputs(cap);
     {
         Prof pr(*dev, PROF_TRK, st, 0, (double)total * thumb_bytes());
-        if (ticks == 0)
-            launch_bestshot_walk(d_off, 0, d_rows, d_info.p, d_cand.p, 0, d_stage.p, d_stage.p + o_mode, 1, g, d_state.p, d_slot_thumbs.p, cap, o, o + S,
-                                 o + 2 * S, o + o_ev, d_out_thumbs.p, st);
-        const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
-        for (int lo = 0; lo < ticks;) {
-            int hi = lo + 1;                                                 // one tick at the least
-            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) &&
-                   (size_t)(h[o_off + (size_t)(hi + 1) * S] - h[o_off + (size_t)lo * S]) * thumb_bytes() <= budget &&
-                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
-                ++hi;
-            const int base = h[o_off + (size_t)lo * S], rows = h[o_off + (size_t)hi * S] - base;
-            int max_rows = 0;
-            for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
-            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
-            if (frames_mem == AIC_HOST) {
-                grow(d_frames, (size_t)(hi - lo) * tick_bytes, "the staged frames");
-                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)(hi - lo) * tick_bytes, hipMemcpyHostToDevice, st));
-                d_fr = d_frames.p;
-            }
-            grow(d_cand, std::max<size_t>(16, (size_t)rows * thumb_bytes()), "the candidate thumbnails");
-            launch_bestshot_score(d_fr, d_off + (size_t)lo * S, (hi - lo) * S, max_rows, d_rows, d_state.p, d_stage.p, lo == 0, g, base, d_info.p, d_cand.p,
-                                  st);
-            launch_bestshot_walk(d_off + (size_t)lo * S, hi - lo, d_rows, d_info.p, d_cand.p, base, d_stage.p, d_stage.p + o_mode, lo == 0, g, d_state.p,
-                                 d_slot_thumbs.p, cap, o, o + S, o + 2 * S, o + o_ev, d_out_thumbs.p, st);
-            lo = hi;
-        }
+        if (ticks == 0) walk(d_off, 0, d_rows, 0, bs, 1, cap, so);
+        launches(frames, frames_mem, ticks, [&](int lo, int hi) { return bs.rows_of(h_stage.p, lo, hi) * thumb_bytes(); },
+                 [&](int lo, int hi, const uint8_t* d_fr) {
+                     const int base = h_stage.p[bs.o_off + (size_t)lo * S];
+                     grow(d_cand, std::max<size_t>(16, bs.rows_of(h_stage.p, lo, hi) * thumb_bytes()), "the candidate thumbnails");
+                     launch_bestshot_score(d_fr, d_off + (size_t)lo * S, (hi - lo) * S, max_rows(counts, lo, hi), d_rows, d_state.p, d_stage.p, lo == 0, g,
+                                           base, d_info.p, d_cand.p, st);
+                     walk(d_off + (size_t)lo * S, hi - lo, d_rows, base, bs, lo == 0, cap, so);
+                 });
     }
     if (stats && total) {
         h_info.resize((size_t)total * 8);
@@ -133,48 +94,19 @@ void BestShot::update(const void* frames, int frames_mem, int ticks, const int32
 }
 
 void BestShot::flush(int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
-    const int S = g.streams;
-    AIC_REQUIRE(stream >= -1 && stream < S, AIC_ERR_INVALID, "stream outside the best-shot bank (-1 = every stream)");
+    AIC_REQUIRE(stream >= -1 && stream < g.streams, AIC_ERR_INVALID, "stream outside the best-shot bank (-1 = every stream)");
     check_outputs(cap, n_final, events, thumbs, pending);
     touch_device();
-    hipStream_t st = dev->s_trk;
-    h_stage.ensure(2 * (size_t)S + 1);
-    grow(d_stage, 2 * (size_t)S + 1, "the staging buffer");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[S + s] = stream < 0 || stream == s ? BS_MODE_FLUSH : BS_MODE_NONE;
-    h[2 * S] = 0;
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, (2 * (size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    const size_t o_ev = out_events_at(S);
-    grow(d_out, o_ev + (size_t)S * cap * BS_EVENT_INTS, "the events");
-    grow(d_out_thumbs, std::max<size_t>(16, (size_t)S * cap * thumb_bytes()), "the output thumbnails");
-    int* o = d_out.p;
-    launch_bestshot_walk(d_stage.p + 2 * S, 0, nullptr, nullptr, nullptr, 0, d_stage.p, d_stage.p + S, 1, g, d_state.p, d_slot_thumbs.p, cap, o, o + S,
-                         o + 2 * S, o + o_ev, d_out_thumbs.p, st);
+    const BankStage bs = upload_flush(stream);
+    walk(d_stage.p + bs.o_off, 0, nullptr, 0, bs, 1, cap, outputs(cap));
     finish(cap, n_final, events, thumbs, pending, status);
 }
 
 void BestShot::finish(int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
-    const int S = g.streams;
-    hipStream_t st = dev->s_trk;
-    const size_t o_ev = out_events_at(S);
-    h_out.ensure(3 * (size_t)S);
-    HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, 3 * (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    std::fill(reset_pending.begin(), reset_pending.end(), (char)0);
-    const int* o = h_out.p;
-    bool any = false;
-    for (int s = 0; s < S; ++s) {                                            // only the filled entries come back
-        const int n = std::min(std::max(o[s], 0), cap);
-        n_final[s] = n, pending[s] = o[S + s], stop[s] = o[2 * S + s];
-        if (status) status[s] = stop[s];
-        if (!n) continue;
-        any = true;
-        HIP_CHECK(hipMemcpyAsync(events + (size_t)s * cap * BS_EVENT_INTS, d_out.p + o_ev + (size_t)s * cap * BS_EVENT_INTS,
-                                 (size_t)n * BS_EVENT_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+    SlotBank::finish(cap, BS_EVENT_INTS, n_final, events, pending, status, [&](int s, int n) {
         HIP_CHECK(hipMemcpyAsync(thumbs + (size_t)s * cap * thumb_bytes(), d_out_thumbs.p + (size_t)s * cap * thumb_bytes(), (size_t)n * thumb_bytes(),
-                                 hipMemcpyDeviceToHost, st));
-    }
-    if (any) HIP_CHECK(hipStreamSynchronize(st));
+                                 hipMemcpyDeviceToHost, dev->s_trk));
+    });
 }
 
 void BestShot::export_stream(int stream, int32_t* n, int32_t* events, uint8_t* thumbs) {
@@ -231,56 +163,35 @@ int aic_bestshot_create(int device, const aic_bestshot_config* params, aic_bests
     });
 }
 
-int aic_bestshot_destroy(aic_bestshot* b) {
-    return guarded([&] {
-        if (b && b->b.dev) { b->b.dev->use(); (void)hipStreamSynchronize(b->b.dev->s_trk); }
-        delete b;
-    });
-}
+int aic_bestshot_destroy(aic_bestshot* b) { return destroy_handle(b, b ? b->b.dev : nullptr); }
 
 int aic_bestshot_option(aic_bestshot* b, const char* key, int value) {
-    return guarded([&] {
-        AIC_REQUIRE(b && key, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(b, [&] {
+        AIC_REQUIRE(key, AIC_ERR_INVALID, "NULL argument");
         const std::string k(key);
-        if (k == "ticks_per_launch") {
-            AIC_REQUIRE(value >= 0 && value <= BS_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
-            b->b.ticks_per_launch = value;
-        } else if (k == "launch_budget_mb") {
-            AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
-            b->b.launch_budget_mb = value;
-        } else if (k == "stats") {
-            AIC_REQUIRE(value == 0 || value == 1, AIC_ERR_INVALID, "stats must be 0 or 1");
-            b->b.stats = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown best-shot option: " + k);
+        if (b->b.launch_option(k, value, BS_TICKS_MAX)) return;
+        AIC_REQUIRE(k == "stats", AIC_ERR_INVALID, "unknown best-shot option: " + k);
+        AIC_REQUIRE(value == 0 || value == 1, AIC_ERR_INVALID, "stats must be 0 or 1");
+        b->b.stats = value;
     });
 }
 
 int aic_bestshot_reset(aic_bestshot* b, int stream) {
-    return guarded([&] {
-        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
-        b->b.reset(stream);
-    });
+    return with_handle(b, [&] { b->b.reset(stream); });
 }
 
 int aic_bestshot_update(aic_bestshot* b, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
                         int rows_mem, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status) {
-    return guarded([&] {
-        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
-        b->b.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap, n_final, events, thumbs, pending, status);
-    });
+    return with_handle(b, [&] { b->b.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap, n_final, events, thumbs, pending, status); });
 }
 
 int aic_bestshot_flush(aic_bestshot* b, int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending,
                        int32_t* status) {
-    return guarded([&] {
-        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
-        b->b.flush(stream, cap, n_final, events, thumbs, pending, status);
-    });
+    return with_handle(b, [&] { b->b.flush(stream, cap, n_final, events, thumbs, pending, status); });
 }
 
 int aic_bestshot_counters(aic_bestshot* b, int64_t* rows, int64_t* candidates, int64_t* stored) {
-    return guarded([&] {
-        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(b, [&] {
         if (rows) *rows = b->b.n_rows;
         if (candidates) *candidates = b->b.n_candidates;
         if (stored) *stored = b->b.n_stored;
@@ -288,10 +199,7 @@ int aic_bestshot_counters(aic_bestshot* b, int64_t* rows, int64_t* candidates, i
 }
 
 int aic_bestshot_export(aic_bestshot* b, int stream, int32_t* n, int32_t* events, uint8_t* thumbs) {
-    return guarded([&] {
-        AIC_REQUIRE(b, AIC_ERR_INVALID, "NULL argument");
-        b->b.export_stream(stream, n, events, thumbs);
-    });
+    return with_handle(b, [&] { b->b.export_stream(stream, n, events, thumbs); });
 }
 
 }  // extern "C"

@@ -11,30 +11,28 @@
 // AIC_ERR_CAPACITY.  A call's ticks are cut into launches so that the candidate buffer and the staged frames each stay below
 // launch_budget_mb (option, default 1024), one tick per launch at the least.  create, option and reset never touch the device.
 #pragma once
-#include "common.hpp"
+#include "bank_stage.hpp"
 
 namespace aic {
 
 constexpr int BS_STREAMS_MAX = 256;
 constexpr int BS_ROWS_MAX = 512;           // rows per frame = threads of the walk block
-constexpr int BS_TRACKS_MAX = 512;         // slots per stream
+constexpr int BS_TRACKS_MAX = SLOT_TRACKS; // slots per stream
 constexpr int BS_COORD_MAX = 1 << 20;
 constexpr int BS_DIM_MAX = 16384;
 constexpr int BS_CAP_MAX = 4096;           // finals per stream per call
 constexpr int BS_TICKS_MAX = 1 << 16;
 constexpr int BS_EVENT_INTS = 16;
 
-enum { BS_LIVE = 0, BS_EXPIRED = 1, BS_FLUSHED = 2 };
+enum { BS_LIVE = SLOT_LIVE, BS_EXPIRED = SLOT_EXPIRED, BS_FLUSHED = SLOT_FLUSHED };
 enum { BS_REGION_BOX = 0, BS_REGION_HEAD = 1 };
 // flags of a scored row
-enum { BS_F_VALID = 1, BS_F_FIRST = 2, BS_F_NONEMPTY = 4, BS_F_CAND = 8, BS_F_TRUNC = 16, BS_F_STORED = 32 };
-// what a launch without ticks does to a stream
-enum { BS_MODE_NONE = 0, BS_MODE_DRAIN = 1, BS_MODE_FLUSH = 2 };
-
-// state of one stream, ints: frame, status, 6 unused | 13 arrays of 512: id, state (0 free, 1 live, 2 ENDED expired, 3 ENDED flushed),
-// last_seen, cls, first_frame, sightings, has_shot, best_frame, score, C.x0, C.y0, C.x1, C.y1
-constexpr int BS_ST_SLOTS = 8;
-enum { BS_A_ID = 0, BS_A_STATE, BS_A_LAST, BS_A_CLS, BS_A_FIRST, BS_A_SIGHT, BS_A_HAS, BS_A_BFRAME, BS_A_SCORE, BS_A_C0, BS_A_C1, BS_A_C2, BS_A_C3, BS_ARRAYS };
+enum { BS_F_VALID = SLOT_F_VALID, BS_F_FIRST = SLOT_F_FIRST, BS_F_NONEMPTY = SLOT_F_NONEMPTY, BS_F_CAND = 8, BS_F_TRUNC = 16, BS_F_STORED = 32 };
+// state of one stream, ints: frame, status, 6 unused | 13 arrays of 512: the six of every slot table (bank_call.hpp: id, state,
+// last_seen, cls, first_frame, sightings), has_shot, best_frame, score, C.x0, C.y0, C.x1, C.y1
+constexpr int BS_ST_SLOTS = SLOT_ST_SLOTS;
+enum { BS_A_ID = SLOT_A_ID, BS_A_STATE = SLOT_A_STATE, BS_A_LAST = SLOT_A_LAST, BS_A_CLS = SLOT_A_CLS, BS_A_FIRST = SLOT_A_FIRST,
+       BS_A_SIGHT = SLOT_A_SIGHT, BS_A_HAS = SLOT_A_SHARED, BS_A_BFRAME, BS_A_SCORE, BS_A_C0, BS_A_C1, BS_A_C2, BS_A_C3, BS_ARRAYS };
 constexpr int BS_ST_INTS = BS_ST_SLOTS + BS_ARRAYS * BS_TRACKS_MAX;
 
 struct BsGeom {                            // what the kernels need of aic_bestshot_config
@@ -56,24 +54,17 @@ void launch_bestshot_walk(const int* frame_off, int n_ticks, const int* rows6, c
 // the checks of aic_bestshot_create: nothing is touched before they pass
 void bestshot_check_params(int device, const aic_bestshot_config* p);
 
-struct BestShot {
-    int device_id;
-    Device* dev = nullptr;                       // resolved by the first call that reaches the device
+struct BestShot : SlotBank {
     BsGeom g;
-    int ticks_per_launch = 0;                    // 0: as many ticks per launch as launch_budget_mb allows; k: at most k
-    int launch_budget_mb = 1024;
     int stats = 0;                               // option "stats": 1 = every update reads its scored rows back and counts them
     int64_t n_rows = 0, n_candidates = 0, n_stored = 0;   // rows handed in, candidates scored, thumbnails the filter let through
-    std::vector<char> reset_pending;
-    std::vector<int> stop;                       // 0 or the code a stream stopped with
-    DevBuf<int> d_state, d_stage, d_info, d_out, d_counts;
-    DevBuf<uint8_t> d_slot_thumbs, d_cand, d_frames, d_out_thumbs;
-    PinBuf<int> h_stage, h_out;
-    std::vector<int> h_counts, h_state, h_info;
+    DevBuf<int> d_state, d_info;
+    DevBuf<uint8_t> d_slot_thumbs, d_cand, d_out_thumbs;
+    std::vector<int> h_state, h_info;
 
     BestShot(int device, const aic_bestshot_config& p);
     size_t thumb_bytes() const { return (size_t)g.tw * g.th * 3; }
-    void reset(int stream);
+    void reset(int stream) { reset_stream(stream, "stream outside the best-shot bank"); }
     void update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap, int32_t* n_final,
                 int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status);
     void flush(int stream, int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status);
@@ -81,6 +72,8 @@ struct BestShot {
 
 private:
     void touch_device();
+    SlotOut outputs(int cap);
+    void walk(const int* d_off, int n_ticks, const int* d_rows, int cand_base, const BankStage& bs, int first, int cap, const SlotOut& so);
     void finish(int cap, int32_t* n_final, int32_t* events, uint8_t* thumbs, int32_t* pending, int32_t* status);
 };
 

@@ -1,7 +1,6 @@
 // colours.cpp -- the clothing-colour object (colours.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_colours.hip or the call raises.  aic_colours_classify is the host's copy of the pixel rule.
 #include "colours.hpp"
-#include "row_stage.hpp"
 
 #include <algorithm>
 
@@ -24,19 +23,12 @@ void colours_check_params(int device, const aic_colours_config* p) {
 }
 
 Colours::Colours(int device, const aic_colours_config& p)
-    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.max_tracks, p.forget_after, p.torso0, p.torso1, p.legs0, p.legs1, p.inset_q8, p.min_w,
-                           p.min_h, p.max_cover_q8},
-      reset_pending(p.streams, 1), stop(p.streams, 0) {}
-
-void Colours::reset(int stream) {
-    AIC_REQUIRE(stream >= 0 && stream < g.streams, AIC_ERR_INVALID, "stream outside the colour bank");
-    stop[stream] = 0;
-    reset_pending[stream] = 1;
-}
+    : SlotBank(device, p.streams, p.frame_h, p.frame_w),
+      g{p.streams, p.frame_h, p.frame_w, p.max_tracks, p.forget_after, p.torso0, p.torso1, p.legs0, p.legs1, p.inset_q8, p.min_w, p.min_h,
+        p.max_cover_q8} {}
 
 void Colours::touch_device() {
-    if (!dev) dev = &device(device_id);
-    dev->use();
+    use_device();
     if (!d_state.p) {
         grow(d_state, (size_t)g.streams * CL_ST_INTS, "the slot tables");
         HIP_CHECK(hipMemsetAsync(d_state.p, 0, d_state.bytes(), dev->s_trk));
@@ -49,122 +41,56 @@ static void check_outputs(int cap, const int32_t* n_final, const int32_t* events
     AIC_REQUIRE(cap == 0 || events, AIC_ERR_INVALID, "NULL events");
 }
 
-// outputs of a call, ints: n_final[S] | pending[S] | status[S] | (16-byte aligned) events[S, cap, 48]
-static size_t out_events_at(int S) { return ((size_t)3 * S + 3) / 4 * 4; }
+void Colours::walk(const int* d_off, int n_ticks, const int* d_rows, int info_base, const BankStage& bs, int first, int cap, const SlotOut& so,
+                   int* d_rt) {
+    int* o = d_out.p;
+    launch_colours_walk(d_off, n_ticks, d_rows, d_info.p, info_base, d_stage.p, d_stage.p + bs.o_mode, first, g, d_state.p, cap, o,
+                        o + so.o_pending, o + so.o_status, o + so.o_events, d_rt, dev->s_trk);
+}
 
 void Colours::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap,
                      int32_t* n_final, int32_t* events, int32_t* row_tags, int32_t* pending, int32_t* status) {
     const int S = g.streams;
-    AIC_REQUIRE(ticks >= 0 && ticks <= CL_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
-    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
-    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
+    const long F = check_call(ticks, CL_TICKS_MAX, frames_mem, rows_mem);
     check_outputs(cap, n_final, events, pending);
-    const long F = (long)ticks * S;
-    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
     AIC_REQUIRE(F == 0 || (frames && counts), AIC_ERR_INVALID, "NULL frames or counts");
-    auto check_counts = [&](const int32_t* c) {
-        const long total = check_row_counts(c, F, CL_ROWS_MAX, rows6);
-        AIC_REQUIRE(total <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
-        return total;
-    };
-    long total = 0;
-    if (rows_mem == AIC_HOST && F) total = check_counts(counts);
-
-    touch_device();
+    const long total = count_rows(counts, F > 0, F, CL_ROWS_MAX, rows6, rows_mem, [&] { touch_device(); }, [](long t) {
+        AIC_REQUIRE(t <= (1 << 24), AIC_ERR_INVALID, "more than 2^24 rows in one call");
+    });
     hipStream_t st = dev->s_trk;
-    if (rows_mem == AIC_DEVICE && F) total = check_counts(counts = fetch_counts(h_counts, counts, F, st));   // the counts decide the launches
-    // ---- staging: reset[S] | mode[S] | frame_off[F + 1] | rows (host memory only; row_stage.hpp)
-    const size_t o_mode = S, o_off = 2 * (size_t)S;
-    const RowStage rs(o_off, o_off + F + 1, total, rows_mem == AIC_HOST);
-    h_stage.ensure(rs.n_ints);
-    grow(d_stage, rs.n_ints, "the staged rows");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[o_mode + s] = CL_MODE_DRAIN;
-    rs.fill(h, counts, F, rows6);
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* d_rows = rs.d_rows(d_stage.p, rows6);
-    const int* d_off = d_stage.p + o_off;
-    const size_t o_ev = out_events_at(S);
-    grow(d_out, o_ev + (size_t)S * cap * CL_EVENT_INTS, "the events");
+    const BankStage bs = upload_update(F, counts, total, rows6, rows_mem == AIC_HOST);
+    const int* d_rows = bs.d_rows(d_stage.p, rows6);
+    const int* d_off = d_stage.p + bs.o_off;
+    const SlotOut so = out(cap, CL_EVENT_INTS);
     int* d_rt = nullptr;
     if (row_tags && total) {
         grow(d_tags, (size_t)total * 4, "the row tags");
         d_rt = d_tags.p;
     }
-    int* o = d_out.p;
-
     {
-        Prof pr(*dev, PROF_TRK, st, 0, (double)total * CL_INFO_INTS * sizeof(int));
-        if (ticks == 0)
-            launch_colours_walk(d_off, 0, d_rows, nullptr, 0, d_stage.p, d_stage.p + o_mode, 1, g, d_state.p, cap, o, o + S, o + 2 * S, o + o_ev, nullptr,
-                                st);
-        const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
         const size_t info_bytes = CL_INFO_INTS * sizeof(int);
-        for (int lo = 0; lo < ticks;) {
-            int hi = lo + 1;                                                 // one tick at the least
-            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) &&
-                   (size_t)(h[o_off + (size_t)(hi + 1) * S] - h[o_off + (size_t)lo * S]) * info_bytes <= budget &&
-                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
-                ++hi;
-            const int base = h[o_off + (size_t)lo * S], rows = h[o_off + (size_t)hi * S] - base;
-            int max_rows = 0;
-            for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
-            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
-            if (frames_mem == AIC_HOST) {
-                grow(d_frames, (size_t)(hi - lo) * tick_bytes, "the staged frames");
-                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)(hi - lo) * tick_bytes, hipMemcpyHostToDevice, st));
-                d_fr = d_frames.p;
-            }
-            grow(d_info, std::max<size_t>(CL_INFO_INTS, (size_t)rows * CL_INFO_INTS), "the sampled rows");
-            launch_colours_sample(d_fr, d_off + (size_t)lo * S, (hi - lo) * S, max_rows, d_rows, d_state.p, d_stage.p, lo == 0, g, base, d_info.p, st);
-            launch_colours_walk(d_off + (size_t)lo * S, hi - lo, d_rows, d_info.p, base, d_stage.p, d_stage.p + o_mode, lo == 0, g, d_state.p, cap, o, o + S,
-                                o + 2 * S, o + o_ev, d_rt, st);
-            lo = hi;
-        }
+        Prof pr(*dev, PROF_TRK, st, 0, (double)total * info_bytes);
+        if (ticks == 0) walk(d_off, 0, d_rows, 0, bs, 1, cap, so, nullptr);
+        launches(frames, frames_mem, ticks, [&](int lo, int hi) { return bs.rows_of(h_stage.p, lo, hi) * info_bytes; },
+                 [&](int lo, int hi, const uint8_t* d_fr) {
+                     const int base = h_stage.p[bs.o_off + (size_t)lo * S];
+                     grow(d_info, std::max<size_t>(CL_INFO_INTS, bs.rows_of(h_stage.p, lo, hi) * CL_INFO_INTS), "the sampled rows");
+                     launch_colours_sample(d_fr, d_off + (size_t)lo * S, (hi - lo) * S, max_rows(counts, lo, hi), d_rows, d_state.p, d_stage.p, lo == 0, g,
+                                           base, d_info.p, st);
+                     walk(d_off + (size_t)lo * S, hi - lo, d_rows, base, bs, lo == 0, cap, so, d_rt);
+                 });
     }
     if (d_rt) HIP_CHECK(hipMemcpyAsync(row_tags, d_rt, (size_t)total * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    finish(cap, n_final, events, pending, status);
+    finish(cap, CL_EVENT_INTS, n_final, events, pending, status, [](int, int) {});
 }
 
 void Colours::flush(int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status) {
-    const int S = g.streams;
-    AIC_REQUIRE(stream >= -1 && stream < S, AIC_ERR_INVALID, "stream outside the colour bank (-1 = every stream)");
+    AIC_REQUIRE(stream >= -1 && stream < g.streams, AIC_ERR_INVALID, "stream outside the colour bank (-1 = every stream)");
     check_outputs(cap, n_final, events, pending);
     touch_device();
-    hipStream_t st = dev->s_trk;
-    h_stage.ensure(2 * (size_t)S + 1);
-    grow(d_stage, 2 * (size_t)S + 1, "the staging buffer");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s], h[S + s] = stream < 0 || stream == s ? CL_MODE_FLUSH : CL_MODE_NONE;
-    h[2 * S] = 0;
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, (2 * (size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    const size_t o_ev = out_events_at(S);
-    grow(d_out, o_ev + (size_t)S * cap * CL_EVENT_INTS, "the events");
-    int* o = d_out.p;
-    launch_colours_walk(d_stage.p + 2 * S, 0, nullptr, nullptr, 0, d_stage.p, d_stage.p + S, 1, g, d_state.p, cap, o, o + S, o + 2 * S, o + o_ev, nullptr, st);
-    finish(cap, n_final, events, pending, status);
-}
-
-void Colours::finish(int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status) {
-    const int S = g.streams;
-    hipStream_t st = dev->s_trk;
-    const size_t o_ev = out_events_at(S);
-    h_out.ensure(3 * (size_t)S);
-    HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, 3 * (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    std::fill(reset_pending.begin(), reset_pending.end(), (char)0);
-    const int* o = h_out.p;
-    bool any = false;
-    for (int s = 0; s < S; ++s) {                                            // only the filled entries come back
-        const int n = std::min(std::max(o[s], 0), cap);
-        n_final[s] = n, pending[s] = o[S + s], stop[s] = o[2 * S + s];
-        if (status) status[s] = stop[s];
-        if (!n) continue;
-        any = true;
-        HIP_CHECK(hipMemcpyAsync(events + (size_t)s * cap * CL_EVENT_INTS, d_out.p + o_ev + (size_t)s * cap * CL_EVENT_INTS,
-                                 (size_t)n * CL_EVENT_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    if (any) HIP_CHECK(hipStreamSynchronize(st));
+    const BankStage bs = upload_flush(stream);
+    walk(d_stage.p + bs.o_off, 0, nullptr, 0, bs, 1, cap, out(cap, CL_EVENT_INTS), nullptr);
+    finish(cap, CL_EVENT_INTS, n_final, events, pending, status, [](int, int) {});
 }
 
 void Colours::export_stream(int stream, int32_t* n, int32_t* events) {
@@ -219,54 +145,31 @@ int aic_colours_create(int device, const aic_colours_config* config, aic_colours
     });
 }
 
-int aic_colours_destroy(aic_colours* c) {
-    return guarded([&] {
-        if (c && c->c.dev) { c->c.dev->use(); (void)hipStreamSynchronize(c->c.dev->s_trk); }
-        delete c;
-    });
-}
+int aic_colours_destroy(aic_colours* c) { return destroy_handle(c, c ? c->c.dev : nullptr); }
 
 int aic_colours_option(aic_colours* c, const char* key, int value) {
-    return guarded([&] {
-        AIC_REQUIRE(c && key, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(c, [&] {
+        AIC_REQUIRE(key, AIC_ERR_INVALID, "NULL argument");
         const std::string k(key);
-        if (k == "ticks_per_launch") {
-            AIC_REQUIRE(value >= 0 && value <= CL_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
-            c->c.ticks_per_launch = value;
-        } else if (k == "launch_budget_mb") {
-            AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
-            c->c.launch_budget_mb = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown colours option: " + k);
+        AIC_REQUIRE(c->c.launch_option(k, value, CL_TICKS_MAX), AIC_ERR_INVALID, "unknown colours option: " + k);
     });
 }
 
 int aic_colours_reset(aic_colours* c, int stream) {
-    return guarded([&] {
-        AIC_REQUIRE(c, AIC_ERR_INVALID, "NULL argument");
-        c->c.reset(stream);
-    });
+    return with_handle(c, [&] { c->c.reset(stream); });
 }
 
 int aic_colours_update(aic_colours* c, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
                        int rows_mem, int cap, int32_t* n_final, int32_t* events, int32_t* row_tags, int32_t* pending, int32_t* status) {
-    return guarded([&] {
-        AIC_REQUIRE(c, AIC_ERR_INVALID, "NULL argument");
-        c->c.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap, n_final, events, row_tags, pending, status);
-    });
+    return with_handle(c, [&] { c->c.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap, n_final, events, row_tags, pending, status); });
 }
 
 int aic_colours_flush(aic_colours* c, int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status) {
-    return guarded([&] {
-        AIC_REQUIRE(c, AIC_ERR_INVALID, "NULL argument");
-        c->c.flush(stream, cap, n_final, events, pending, status);
-    });
+    return with_handle(c, [&] { c->c.flush(stream, cap, n_final, events, pending, status); });
 }
 
 int aic_colours_export(aic_colours* c, int stream, int32_t* n, int32_t* events) {
-    return guarded([&] {
-        AIC_REQUIRE(c, AIC_ERR_INVALID, "NULL argument");
-        c->c.export_stream(stream, n, events);
-    });
+    return with_handle(c, [&] { c->c.export_stream(stream, n, events); });
 }
 
 int aic_colours_classify(const uint8_t* bgr, int n, uint8_t* bins) {

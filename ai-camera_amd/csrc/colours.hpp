@@ -10,13 +10,13 @@
 // not fit fails that call with AIC_ERR_CAPACITY.  A call's ticks are cut into launches so that the samples and the staged frames each
 // stay below launch_budget_mb (option, default 1024), one tick per launch at the least.  create, option and reset never touch the device.
 #pragma once
-#include "common.hpp"
+#include "bank_stage.hpp"
 
 namespace aic {
 
 constexpr int CL_STREAMS_MAX = 256;
 constexpr int CL_ROWS_MAX = 512;           // rows per frame = threads of the walk block
-constexpr int CL_TRACKS_MAX = 512;         // slots per stream
+constexpr int CL_TRACKS_MAX = SLOT_TRACKS; // slots per stream
 constexpr int CL_COORD_MAX = 1 << 20;
 constexpr int CL_DIM_MAX = 16384;
 constexpr int CL_CAP_MAX = 4096;           // finals per stream per call
@@ -26,17 +26,15 @@ constexpr int CL_INFO_INTS = 32;           // a sampled row: flags, n_upper, n_l
 constexpr int CL_BINS = 12;
 constexpr int CL_SAMPLES_MAX = 1 << 20;    // samples per part and slot: acc <= 256 * 2^20 = 2^28 stays inside int32
 
-enum { CL_LIVE = 0, CL_EXPIRED = 1, CL_FLUSHED = 2 };
+enum { CL_LIVE = SLOT_LIVE, CL_EXPIRED = SLOT_EXPIRED, CL_FLUSHED = SLOT_FLUSHED };
 enum { CL_BLACK = 0, CL_GRAY, CL_WHITE, CL_RED, CL_ORANGE, CL_YELLOW, CL_GREEN, CL_CYAN, CL_BLUE, CL_PURPLE, CL_PINK, CL_BROWN };
 // flags of a sampled row
-enum { CL_F_VALID = 1, CL_F_FIRST = 2, CL_F_NONEMPTY = 4, CL_F_UPPER = 8, CL_F_LOWER = 16 };
-// what a launch without ticks does to a stream
-enum { CL_MODE_NONE = 0, CL_MODE_DRAIN = 1, CL_MODE_FLUSH = 2 };
-
-// state of one stream, ints: frame, status, 6 unused | 8 arrays of 512: id, state (0 free, 1 live, 2 ENDED expired, 3 ENDED flushed),
-// last_seen, cls, first_frame, sightings, samples_upper, samples_lower | acc [512 slots][2 parts][12 bins]
-constexpr int CL_ST_SLOTS = 8;
-enum { CL_A_ID = 0, CL_A_STATE, CL_A_LAST, CL_A_CLS, CL_A_FIRST, CL_A_SIGHT, CL_A_NU, CL_A_NL, CL_ARRAYS };
+enum { CL_F_VALID = SLOT_F_VALID, CL_F_FIRST = SLOT_F_FIRST, CL_F_NONEMPTY = SLOT_F_NONEMPTY, CL_F_UPPER = 8, CL_F_LOWER = 16 };
+// state of one stream, ints: frame, status, 6 unused | 8 arrays of 512: the six of every slot table (bank_call.hpp: id, state, last_seen,
+// cls, first_frame, sightings), samples_upper, samples_lower | acc [512 slots][2 parts][12 bins]
+constexpr int CL_ST_SLOTS = SLOT_ST_SLOTS;
+enum { CL_A_ID = SLOT_A_ID, CL_A_STATE = SLOT_A_STATE, CL_A_LAST = SLOT_A_LAST, CL_A_CLS = SLOT_A_CLS, CL_A_FIRST = SLOT_A_FIRST,
+       CL_A_SIGHT = SLOT_A_SIGHT, CL_A_NU = SLOT_A_SHARED, CL_A_NL, CL_ARRAYS };
 constexpr int CL_ST_ACC = CL_ST_SLOTS + CL_ARRAYS * CL_TRACKS_MAX;
 constexpr int CL_ST_INTS = CL_ST_ACC + CL_TRACKS_MAX * 2 * CL_BINS;
 
@@ -110,21 +108,13 @@ void launch_colours_walk(const int* frame_off, int n_ticks, const int* rows6, co
 // the checks of aic_colours_create: nothing is touched before they pass
 void colours_check_params(int device, const aic_colours_config* p);
 
-struct Colours {
-    int device_id;
-    Device* dev = nullptr;                       // resolved by the first call that reaches the device
+struct Colours : SlotBank {
     ColGeom g;
-    int ticks_per_launch = 0;                    // 0: as many ticks per launch as launch_budget_mb allows; k: at most k
-    int launch_budget_mb = 1024;
-    std::vector<char> reset_pending;
-    std::vector<int> stop;                       // 0 or the code a stream stopped with
-    DevBuf<int> d_state, d_stage, d_info, d_out, d_tags;
-    DevBuf<uint8_t> d_frames;
-    PinBuf<int> h_stage, h_out;
-    std::vector<int> h_counts, h_state;
+    DevBuf<int> d_state, d_info, d_tags;
+    std::vector<int> h_state;
 
     Colours(int device, const aic_colours_config& p);
-    void reset(int stream);
+    void reset(int stream) { reset_stream(stream, "stream outside the colour bank"); }
     void update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap, int32_t* n_final,
                 int32_t* events, int32_t* row_tags, int32_t* pending, int32_t* status);
     void flush(int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
@@ -132,7 +122,7 @@ struct Colours {
 
 private:
     void touch_device();
-    void finish(int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
+    void walk(const int* d_off, int n_ticks, const int* d_rows, int info_base, const BankStage& bs, int first, int cap, const SlotOut& so, int* d_rt);
 };
 
 }  // namespace aic

@@ -10,10 +10,12 @@
 //                        The thumbnail goes to the per-row candidate buffer only when the row could still win: its id is not in a live
 //                        slot that is certain to survive up to this tick, or that slot has no shot, or the score beats the slot's best
 //                        as it stood when the launch began (a best score only rises while a slot lives).
-// bestshot_walk_kernel   one block of 512 threads per stream, the launch's ticks in order.  The slot table lives in LDS for the launch.
+// bestshot_walk_kernel   one block of 512 threads per stream, the launch's ticks in order: the life cycle is slot_walk.hpp's, BestshotWalk
+//                        states what is this stage's.  The slot table lives in LDS for the launch.
 //                        A thread is slot t of the table AND row t of the frame.  Thumbnails move with 16-byte copies by the whole block:
 //                        ENDED slots to the output list, winning candidates to their slots.
 #include "bestshot.hpp"
+#include "slot_walk.hpp"
 
 namespace aic {
 
@@ -22,24 +24,6 @@ namespace {
 constexpr int T = BS_TRACKS_MAX;
 
 struct Rect { int x0, y0, x1, y1; };
-
-__device__ __forceinline__ bool coord_ok(int v) { return v >= -BS_COORD_MAX && v <= BS_COORD_MAX; }
-__device__ __forceinline__ bool row_valid(int x1, int y1, int x2, int y2) {
-    return coord_ok(x1) && coord_ok(y1) && coord_ok(x2) && coord_ok(y2) && x2 >= x1 && y2 >= y1;
-}
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = imax(v, __shfl_xor(v, d));
-    return v;
-}
 
 __device__ __forceinline__ int gray_at(const uint8_t* th, int idx) {
     return (29 * th[3 * idx] + 150 * th[3 * idx + 1] + 77 * th[3 * idx + 2] + 128) >> 8;
@@ -65,7 +49,7 @@ __global__ __launch_bounds__(256) void bestshot_score_kernel(const uint8_t* __re
     }
     const int* row = rows6 + (size_t)(off + r) * 6;
     const int x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3], rid = row[4];
-    if (!row_valid(x1, y1, x2, y2)) {
+    if (!row_valid(x1, y1, x2, y2, BS_COORD_MAX)) {
         if (tid == 0) out[0] = make_int4(0, 0, 0, 0), out[1] = make_int4(0, 0, 0, 0);
         return;
     }
@@ -75,7 +59,7 @@ __global__ __launch_bounds__(256) void bestshot_score_kernel(const uint8_t* __re
     bool dup = false;
     for (int j = tid; j < r; j += 256) {
         const int* q = rows6 + (size_t)(off + j) * 6;
-        dup = dup || (q[4] == rid && row_valid(q[0], q[1], q[2], q[3]));
+        dup = dup || (q[4] == rid && row_valid(q[0], q[1], q[2], q[3], BS_COORD_MAX));
     }
     if (dup) s_flag = 1;
     __syncthreads();
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(256) void bestshot_score_kernel(const uint8_t* __re
     for (int j = tid; j < n; j += 256) {
         const int* q = rows6 + (size_t)(off + j) * 6;
         const int qx1 = q[0], qy1 = q[1], qx2 = q[2], qy2 = q[3];
-        if (q[4] == rid || !row_valid(qx1, qy1, qx2, qy2)) continue;
+        if (q[4] == rid || !row_valid(qx1, qy1, qx2, qy2, BS_COORD_MAX)) continue;
         if (!(qy2 > y2 || (qy2 == y2 && j < r))) continue;
         const int bx0 = imax(qx1, 0), by0 = imax(qy1, 0), bx1 = imin(qx2, g.w - 1), by1 = imin(qy2, g.h - 1);
         const int iw = imin(c.x1, bx1) - imax(c.x0, bx0) + 1, ih = imin(c.y1, by1) - imax(c.y0, by0) + 1;
@@ -179,28 +163,74 @@ __global__ __launch_bounds__(256) void bestshot_score_kernel(const uint8_t* __re
     if (tid == 0) out[0] = make_int4(flags, score, c.x0, c.y0), out[1] = make_int4(c.x1, c.y1, 0, 0);
 }
 
-// exclusive prefix sum over the 512 threads of the block; total = the block's sum.  s_w: 8 ints of LDS, free again on return
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
+// what the best-shot stage states of the slot walk (slot_walk.hpp): a shot's seven ints a slot, the resident thumbnails, their copies
+struct BestshotWalk {
+    static constexpr int ARRAYS = BS_ARRAYS, ST_INTS = BS_ST_INTS, EVENT_INTS = BS_EVENT_INTS;
+    struct Row {
+        int flags, score, c0, c1, c2, c3;
+        bool win;
+    };
+    const int4* info;
+    const uint4* cand16;
+    int cand_base, tq;                                                       // tq: 16-byte words of a thumbnail
+    uint4 *slots16, *outs16;                                                 // the stream's resident thumbnails and its output list
+    int* s_list2;
+
+    __device__ __forceinline__ Row load_row(int r, bool in) const {
+        Row x{0, 0, 0, 0, 0, 0, false};
+        if (in) {
+            const int4 a = info[(size_t)r * 2], b = info[(size_t)r * 2 + 1];
+            x.flags = a.x, x.score = a.y, x.c0 = a.z, x.c1 = a.w, x.c2 = b.x, x.c3 = b.y;
+        }
+        return x;
     }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int t = s_w[i];
-        base += i < w ? t : 0;
-        tot += t;
+    __device__ __forceinline__ void fresh(const SlotLds& L, int slot) const {
+        L.tab[BS_A_HAS][slot] = 0, L.tab[BS_A_BFRAME][slot] = 0, L.tab[BS_A_SCORE][slot] = 0;
+        L.tab[BS_A_C0][slot] = 0, L.tab[BS_A_C1][slot] = 0, L.tab[BS_A_C2][slot] = 0, L.tab[BS_A_C3][slot] = 0;
     }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
-}
+    __device__ __forceinline__ void commit(const SlotLds& L, Row& row, int slot, bool fresh_slot, int frame) const {
+        row.win = (row.flags & BS_F_CAND) && (!L.tab[BS_A_HAS][slot] || row.score > L.tab[BS_A_SCORE][slot]);
+        if (row.win) {
+            L.tab[BS_A_HAS][slot] = 1, L.tab[BS_A_SCORE][slot] = row.score, L.tab[BS_A_BFRAME][slot] = frame;
+            L.tab[BS_A_C0][slot] = row.c0, L.tab[BS_A_C1][slot] = row.c1, L.tab[BS_A_C2][slot] = row.c2, L.tab[BS_A_C3][slot] = row.c3;
+        }
+    }
+    __device__ __forceinline__ void event(const SlotLds& L, int4* ev, int s, int e_rank) const {
+        const int tid = threadIdx.x;
+        L.list[e_rank] = tid;
+        const int has = L.tab[BS_A_HAS][tid];
+        slot_event_head(L, ev, s, has);
+        ev[2] = make_int4(has ? L.tab[BS_A_BFRAME][tid] : 0, has ? L.tab[BS_A_SCORE][tid] : 0, has ? L.tab[BS_A_C0][tid] : 0, has ? L.tab[BS_A_C1][tid] : 0);
+        ev[3] = make_int4(has ? L.tab[BS_A_C2][tid] : 0, has ? L.tab[BS_A_C3][tid] : 0, tid, 0);
+    }
+    __device__ __forceinline__ void post_emit(const SlotLds& L, bool em, int n_emit, int n_out) const {
+        __syncthreads();
+        for (int i = 0; i < n_emit; ++i) {
+            const int slot = L.list[i];
+            const bool has = L.tab[BS_A_HAS][slot] != 0;
+            const uint4* src = slots16 + (size_t)slot * tq;
+            uint4* dst = outs16 + (size_t)(n_out + i) * tq;
+            for (int q = threadIdx.x; q < tq; q += T) dst[q] = has ? src[q] : make_uint4(0, 0, 0, 0);
+        }
+        __syncthreads();                                                     // the copies are done before a row may take the slot
+        if (em) L.tab[BS_A_STATE][threadIdx.x] = 0;
+        __syncthreads();
+    }
+    __device__ __forceinline__ void post_tick(const SlotLds& L, const Row& row, int slot, int off, int n, int& stopped) const {
+        int n_win, n_lost;
+        const int win_rank = block_scan(row.win, L.w, n_win);
+        block_scan(row.win && !(row.flags & BS_F_STORED), L.w, n_lost);
+        if (row.win) L.live[win_rank] = off + threadIdx.x - cand_base, s_list2[win_rank] = slot;
+        __syncthreads();
+        for (int i = 0; i < n_win; ++i) {
+            const uint4* src = cand16 + (size_t)L.live[i] * tq;
+            uint4* dst = slots16 + (size_t)s_list2[i] * tq;
+            for (int q = threadIdx.x; q < tq; q += T) dst[q] = src[q];
+        }
+        if (n_lost) stopped = AIC_ERR_RUNTIME;                               // a winner whose thumbnail the score kernel withheld: never
+    }
+    __device__ __forceinline__ void tail(const SlotCall& c, int kk) const {}
+};
 
 __global__ __launch_bounds__(512) void bestshot_walk_kernel(const int* __restrict__ frame_off, int n_ticks, const int* __restrict__ rows6,
                                                             const int4* __restrict__ info, const uint8_t* __restrict__ cand, int cand_base,
@@ -208,141 +238,13 @@ __global__ __launch_bounds__(512) void bestshot_walk_kernel(const int* __restric
                                                             int* __restrict__ state_all, uint8_t* __restrict__ slot_thumbs, int cap,
                                                             int* __restrict__ n_final, int* __restrict__ pending, int* __restrict__ status,
                                                             int* __restrict__ events, uint8_t* __restrict__ out_thumbs) {
-    __shared__ int s_tab[BS_ARRAYS][T];
-    __shared__ int s_live[T], s_list[T], s_list2[T];
-    __shared__ int s_w[8];
-    int* s_id = s_tab[BS_A_ID];
-    int* s_state = s_tab[BS_A_STATE];
-    int* s_last = s_tab[BS_A_LAST];
-    int* s_has = s_tab[BS_A_HAS];
-    int* s_score = s_tab[BS_A_SCORE];
-    const int s = blockIdx.x, tid = threadIdx.x, S = g.streams;
-    int* st = state_all + (size_t)s * BS_ST_INTS;
-    const bool fresh = first && reset[s];
-    int frame = fresh ? 0 : st[0];
-    int stopped = fresh ? 0 : st[1];
-#pragma unroll
-    for (int a = 0; a < BS_ARRAYS; ++a) s_tab[a][tid] = fresh ? 0 : st[BS_ST_SLOTS + a * T + tid];
-    int n_out = first ? 0 : n_final[s];
-    const int tq = g.tw * g.th * 3 / 16;                                     // 16-byte words of a thumbnail
-    uint4* slots16 = reinterpret_cast<uint4*>(slot_thumbs) + (size_t)s * g.max_tracks * tq;
-    uint4* outs16 = reinterpret_cast<uint4*>(out_thumbs) + (size_t)s * cap * tq;
-    const uint4* cand16 = reinterpret_cast<const uint4*>(cand);
-    __syncthreads();
-
-    // ENDED slots (E, ranked e_rank in slot order) leave for the output list while it has room; they become free
-    auto emit = [&](bool E, int e_rank, int n_E) {
-        const int room = cap - n_out;
-        const bool em = E && e_rank < room;
-        if (em) {
-            s_list[e_rank] = tid;
-            int4* ev = reinterpret_cast<int4*>(events + ((size_t)s * cap + n_out + e_rank) * BS_EVENT_INTS);
-            const int has = s_tab[BS_A_HAS][tid];
-            ev[0] = make_int4(s_state[tid] == 3 ? BS_FLUSHED : BS_EXPIRED, s, s_id[tid], s_tab[BS_A_CLS][tid]);
-            ev[1] = make_int4(s_tab[BS_A_FIRST][tid], s_last[tid], s_tab[BS_A_SIGHT][tid], has);
-            ev[2] = make_int4(has ? s_tab[BS_A_BFRAME][tid] : 0, has ? s_score[tid] : 0, has ? s_tab[BS_A_C0][tid] : 0, has ? s_tab[BS_A_C1][tid] : 0);
-            ev[3] = make_int4(has ? s_tab[BS_A_C2][tid] : 0, has ? s_tab[BS_A_C3][tid] : 0, tid, 0);
-        }
-        __syncthreads();
-        const int n_emit = n_E < room ? n_E : (room > 0 ? room : 0);
-        for (int i = 0; i < n_emit; ++i) {
-            const int slot = s_list[i];
-            const bool has = s_has[slot] != 0;
-            const uint4* src = slots16 + (size_t)slot * tq;
-            uint4* dst = outs16 + (size_t)(n_out + i) * tq;
-            for (int q = tid; q < tq; q += T) dst[q] = has ? src[q] : make_uint4(0, 0, 0, 0);
-        }
-        __syncthreads();                                                     // the copies are done before a row may take the slot
-        if (em) s_state[tid] = 0;
-        n_out += n_emit;
-        __syncthreads();
-    };
-
-    if (n_ticks == 0) {
-        const int m = mode[s];
-        if (m == BS_MODE_FLUSH && s_state[tid] == 1) s_state[tid] = 3;
-        if (m != BS_MODE_NONE) {
-            const bool E = tid < g.max_tracks && s_state[tid] >= 2;
-            int n_E;
-            const int e_rank = block_scan(E, s_w, n_E);
-            emit(E, e_rank, n_E);
-        }
-    }
-    for (int kk = 0; kk < n_ticks && !stopped; ++kk) {
-        const int x = kk * S + s;
-        const int off = frame_off[x], n = frame_off[x + 1] - off;            // 0..512, checked by the host
-        // ---- this thread as row tid
-        int flags = 0, score = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, rid = 0, rcls = 0;
-        if (tid < n) {
-            const int4 a = info[(size_t)(off + tid) * 2], b = info[(size_t)(off + tid) * 2 + 1];
-            flags = a.x, score = a.y, c0 = a.z, c1 = a.w, c2 = b.x, c3 = b.y;
-            rid = rows6[(size_t)(off + tid) * 6 + 4], rcls = rows6[(size_t)(off + tid) * 6 + 5];
-        }
-        const int need = BS_F_VALID | BS_F_FIRST | BS_F_NONEMPTY;
-        const bool counted = (flags & need) == need;
-        // ---- this thread as slot tid
-        const int state = tid < g.max_tracks ? s_state[tid] : 0;
-        const bool expiring = state == 1 && frame - s_last[tid] > g.forget_after;
-        const bool E = state >= 2 || expiring;
-        s_live[tid] = state == 1 && !expiring;
-        __syncthreads();
-        int slot = -1;
-        if (counted)
-            for (int t = 0; t < g.max_tracks; ++t)
-                if (s_live[t] && s_id[t] == rid) slot = t;
-        const bool is_new = counted && slot < 0;
-        int n_new, n_E, n_live, n_old, n_unfit;
-        const int new_rank = block_scan(is_new, s_w, n_new);
-        const int e_rank = block_scan(E, s_w, n_E);
-        block_scan(s_live[tid], s_w, n_live);
-        block_scan(state >= 2, s_w, n_old);
-        block_scan(expiring && e_rank >= cap - n_out, s_w, n_unfit);         // ENDED now, no room in the list: the slot stays taken
-        if (n_live + n_old + n_unfit + n_new > g.max_tracks) {               // nothing of this tick is committed
-            stopped = AIC_ERR_CAPACITY;
-            break;
-        }
-        if (expiring) s_state[tid] = 2;
-        emit(E, e_rank, n_E);
-        const bool is_free = tid < g.max_tracks && s_state[tid] == 0;
-        int n_free;
-        const int free_rank = block_scan(is_free, s_w, n_free);
-        if (is_free) s_list[free_rank] = tid;
-        __syncthreads();
-        bool win = false;
-        if (counted) {
-            if (slot < 0) {                                                  // the k-th new row takes the k-th lowest free slot
-                slot = s_list[new_rank];
-                s_id[slot] = rid, s_state[slot] = 1, s_tab[BS_A_FIRST][slot] = frame, s_tab[BS_A_SIGHT][slot] = 0, s_has[slot] = 0;
-                s_tab[BS_A_BFRAME][slot] = 0, s_score[slot] = 0;
-                s_tab[BS_A_C0][slot] = 0, s_tab[BS_A_C1][slot] = 0, s_tab[BS_A_C2][slot] = 0, s_tab[BS_A_C3][slot] = 0;
-            }
-            s_last[slot] = frame, s_tab[BS_A_CLS][slot] = rcls, s_tab[BS_A_SIGHT][slot] += 1;
-            win = (flags & BS_F_CAND) && (!s_has[slot] || score > s_score[slot]);
-            if (win) {
-                s_has[slot] = 1, s_score[slot] = score, s_tab[BS_A_BFRAME][slot] = frame;
-                s_tab[BS_A_C0][slot] = c0, s_tab[BS_A_C1][slot] = c1, s_tab[BS_A_C2][slot] = c2, s_tab[BS_A_C3][slot] = c3;
-            }
-        }
-        int n_win, n_lost;
-        const int win_rank = block_scan(win, s_w, n_win);
-        block_scan(win && !(flags & BS_F_STORED), s_w, n_lost);
-        if (win) s_live[win_rank] = off + tid - cand_base, s_list2[win_rank] = slot;
-        __syncthreads();
-        for (int i = 0; i < n_win; ++i) {
-            const uint4* src = cand16 + (size_t)s_live[i] * tq;
-            uint4* dst = slots16 + (size_t)s_list2[i] * tq;
-            for (int q = tid; q < tq; q += T) dst[q] = src[q];
-        }
-        ++frame;
-        if (n_lost) stopped = AIC_ERR_RUNTIME;                               // a winner whose thumbnail the score kernel withheld: never
-        __syncthreads();
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < BS_ARRAYS; ++a) st[BS_ST_SLOTS + a * T + tid] = s_tab[a][tid];
-    int n_pend;
-    block_scan(tid < g.max_tracks && s_state[tid] >= 2, s_w, n_pend);
-    if (tid == 0) st[0] = frame, st[1] = stopped, n_final[s] = n_out, pending[s] = n_pend, status[s] = stopped;
+    __shared__ int s_list2[T];
+    const SlotCall c{frame_off, n_ticks, rows6, reset, mode, first, g.streams, g.max_tracks, g.forget_after, state_all, cap, n_final, pending, status,
+                     events};
+    const int s = blockIdx.x, tq = g.tw * g.th * 3 / 16;
+    BestshotWalk v{info, reinterpret_cast<const uint4*>(cand), cand_base, tq, reinterpret_cast<uint4*>(slot_thumbs) + (size_t)s * g.max_tracks * tq,
+                   reinterpret_cast<uint4*>(out_thumbs) + (size_t)s * cap * tq, s_list2};
+    slot_walk(c, v);
 }
 
 }  // namespace

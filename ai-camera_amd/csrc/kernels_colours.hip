@@ -12,32 +12,20 @@
 //                        WITHOUT atomics and without LDS histograms: a ballot per bin and a popcount -- the counts are wave-uniform
 //                        scalars, 36 scalar instructions per 64 pixels beside some 60 vector instructions per pixel of classification,
 //                        where an LDS histogram would serialise on the few colours clothing really has (one bin takes most pixels).
-// colours_walk_kernel    one block of 512 threads per stream, the launch's ticks in order.  A thread is slot t of the table AND row t
-//                        of the frame.  The eight small arrays of the table live in LDS for the launch (16 KiB); the accumulators
-//                        (24 ints a slot, 48 KiB a stream) stay in HBM: a tick touches only the slots of its counted rows, some 30 of
+// colours_walk_kernel    one block of 512 threads per stream, the launch's ticks in order: the life cycle is slot_walk.hpp's, ColoursWalk
+//                        states what is this stage's.  A thread is slot t of the table AND row t of the frame.  The eight small
+//                        arrays of the table live in LDS for the launch (16 KiB); the accumulators (24 ints a slot, 48 KiB a stream) stay in HBM: a tick touches only the slots of its counted rows, some 30 of
 //                        512, so loading and storing all of them per launch would move more bytes than it saves, and 64 KiB of LDS
 //                        would leave one block per CU.  A slot's accumulators are written by the thread of its row and read by the
 //                        thread of its slot only across a block barrier.
 #include "colours.hpp"
+#include "slot_walk.hpp"
 
 namespace aic {
 
 namespace {
 
 constexpr int T = CL_TRACKS_MAX;
-
-__device__ __forceinline__ bool coord_ok(int v) { return v >= -CL_COORD_MAX && v <= CL_COORD_MAX; }
-__device__ __forceinline__ bool row_valid(int x1, int y1, int x2, int y2) {
-    return coord_ok(x1) && coord_ok(y1) && coord_ok(x2) && coord_ok(y2) && x2 >= x1 && y2 >= y1;
-}
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = imax(v, __shfl_xor(v, d));
-    return v;
-}
 
 __global__ __launch_bounds__(256) void colours_sample_kernel(const uint8_t* __restrict__ frames, const int* __restrict__ frame_off,
                                                              const int* __restrict__ rows6, const int* __restrict__ state_all,
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(256) void colours_sample_kernel(const uint8_t* __re
     const int* row = rows6 + (size_t)(off + r) * 6;
     const int x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3], rid = row[4];
     int flags = 0;
-    bool go = (fresh || st[1] == 0) && row_valid(x1, y1, x2, y2);            // a stopped stream commits nothing
+    bool go = (fresh || st[1] == 0) && row_valid(x1, y1, x2, y2, CL_COORD_MAX);            // a stopped stream commits nothing
     if (go) {
         // ---- the first valid row of its id?
         if (tid == 0) s_flag = 0;
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(256) void colours_sample_kernel(const uint8_t* __re
         bool dup = false;
         for (int j = tid; j < r; j += 256) {
             const int* q = rows6 + (size_t)(off + j) * 6;
-            dup = dup || (q[4] == rid && row_valid(q[0], q[1], q[2], q[3]));
+            dup = dup || (q[4] == rid && row_valid(q[0], q[1], q[2], q[3], CL_COORD_MAX));
         }
         if (dup) s_flag = 1;
         __syncthreads();
@@ -98,7 +86,7 @@ __global__ __launch_bounds__(256) void colours_sample_kernel(const uint8_t* __re
         for (int j = tid; j < n; j += 256) {
             const int* q = rows6 + (size_t)(off + j) * 6;
             const int qx1 = q[0], qy1 = q[1], qx2 = q[2], qy2 = q[3];
-            if (q[4] == rid || !row_valid(qx1, qy1, qx2, qy2)) continue;
+            if (q[4] == rid || !row_valid(qx1, qy1, qx2, qy2, CL_COORD_MAX)) continue;
             if (!(qy2 > y2 || (qy2 == y2 && j < r))) continue;
             const int bx0 = imax(qx1, 0), by0 = imax(qy1, 0), bx1 = imin(qx2, g.w - 1), by1 = imin(qy2, g.h - 1);
             const int iw = imin(px1, bx1) - imax(px0, bx0) + 1, ih = imin(py1, by1) - imax(py0, by0) + 1;
@@ -162,29 +150,6 @@ __global__ __launch_bounds__(256) void colours_sample_kernel(const uint8_t* __re
     if (tid == 0) out[0] = make_int4(flags, n_part[0], n_part[1], 0), out[7] = make_int4(0, 0, 0, 0);
 }
 
-// exclusive prefix sum over the 512 threads of the block; total = the block's sum.  s_w: 8 ints of LDS, free again on return
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int t = s_w[i];
-        base += i < w ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
-}
-
 // the bin of the largest of 12 accumulators in memory, lowest index on ties
 __device__ __forceinline__ int top_of(const int* acc) {
     int t = 0, best = acc[0];
@@ -196,150 +161,90 @@ __device__ __forceinline__ int top_of(const int* acc) {
     return t;
 }
 
+// what the colour stage states of the slot walk (slot_walk.hpp): two sample counts a slot, the accumulators in HBM, the row tags
+struct ColoursWalk {
+    static constexpr int ARRAYS = CL_ARRAYS, ST_INTS = CL_ST_INTS, EVENT_INTS = CL_EVENT_INTS;
+    struct Row {
+        int flags;
+        const int4* inf;
+        int4 tag;
+    };
+    const int4* info;
+    int info_base;
+    int* acc_all;                                                            // [slot][part][bin] of the stream
+    int4* row_tags;
+
+    __device__ __forceinline__ Row load_row(int r, bool in) const {
+        Row x;
+        x.inf = info + (size_t)(r - info_base) * (CL_INFO_INTS / 4);
+        x.flags = in ? x.inf[0].x : 0;
+        x.tag = make_int4(-1, -1, -1, -1);
+        return x;
+    }
+    __device__ __forceinline__ void fresh(const SlotLds& L, int slot) const { L.tab[CL_A_NU][slot] = 0, L.tab[CL_A_NL][slot] = 0; }
+    __device__ __forceinline__ void commit(const SlotLds& L, Row& row, int slot, bool fresh_slot, int frame) const {
+        int4* acc4 = reinterpret_cast<int4*>(acc_all + slot * 2 * CL_BINS);
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            int& ns = L.tab[part ? CL_A_NL : CL_A_NU][slot];
+            const bool add = (row.flags & (part ? CL_F_LOWER : CL_F_UPPER)) && ns < CL_SAMPLES_MAX;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                int4 a = fresh_slot ? make_int4(0, 0, 0, 0) : acc4[part * 3 + q];
+                if (add) {
+                    const int4 v = row.inf[1 + part * 3 + q];
+                    a.x += v.x, a.y += v.y, a.z += v.z, a.w += v.w;
+                }
+                if (add || fresh_slot) acc4[part * 3 + q] = a;
+            }
+            if (add) ns += 1;
+        }
+        const int* acc = acc_all + slot * 2 * CL_BINS;
+        const int nu = L.tab[CL_A_NU][slot], nl = L.tab[CL_A_NL][slot];
+        int4& tag = row.tag;
+        if (nu > 0) tag.x = top_of(acc), tag.z = acc[tag.x] / nu;
+        else tag.z = 0;
+        if (nl > 0) tag.y = top_of(acc + CL_BINS), tag.w = acc[CL_BINS + tag.y] / nl;
+        else tag.w = 0;
+    }
+    __device__ __forceinline__ void event(const SlotLds& L, int4* ev, int s, int e_rank) const {
+        const int tid = threadIdx.x;
+        const int* acc = acc_all + tid * 2 * CL_BINS;
+        const int nu = L.tab[CL_A_NU][tid], nl = L.tab[CL_A_NL][tid];
+        int tu, su, tl, sl;
+        cl_describe(acc, nu, &tu, &su, reinterpret_cast<int*>(ev + 4));
+        cl_describe(acc + CL_BINS, nl, &tl, &sl, reinterpret_cast<int*>(ev + 7));
+        slot_event_head(L, ev, s, nu);
+        ev[2] = make_int4(nl, tu, su, tl);
+        ev[3] = make_int4(sl, tid, 0, 0);
+        ev[10] = make_int4(0, 0, 0, 0), ev[11] = make_int4(0, 0, 0, 0);
+    }
+    __device__ __forceinline__ void post_emit(const SlotLds& L, bool em, int n_emit, int n_out) const {
+        if (em) L.tab[CL_A_STATE][threadIdx.x] = 0;
+        __syncthreads();                                                     // the accumulators are read before a row may take the slot
+    }
+    __device__ __forceinline__ void post_tick(const SlotLds& L, const Row& row, int slot, int off, int n, int& stopped) const {
+        if (row_tags && (int)threadIdx.x < n) row_tags[off + threadIdx.x] = row.tag;
+    }
+    __device__ __forceinline__ void tail(const SlotCall& c, int kk) const {
+        if (row_tags)                                                        // a stopped stream's rows: the tick it stopped at and all after
+            for (; kk < c.n_ticks; ++kk) {
+                const int x = kk * c.streams + blockIdx.x;
+                const int off = c.frame_off[x], n = c.frame_off[x + 1] - off;
+                if ((int)threadIdx.x < n) row_tags[off + threadIdx.x] = make_int4(-1, -1, -1, -1);
+            }
+    }
+};
+
 __global__ __launch_bounds__(512) void colours_walk_kernel(const int* __restrict__ frame_off, int n_ticks, const int* __restrict__ rows6,
                                                            const int4* __restrict__ info, int info_base, const int* __restrict__ reset,
                                                            const int* __restrict__ mode, int first, ColGeom g, int* state_all, int cap,
                                                            int* __restrict__ n_final, int* __restrict__ pending, int* __restrict__ status,
                                                            int* __restrict__ events, int4* __restrict__ row_tags) {
-    __shared__ int s_tab[CL_ARRAYS][T];
-    __shared__ int s_live[T], s_list[T];
-    __shared__ int s_w[8];
-    int* s_id = s_tab[CL_A_ID];
-    int* s_state = s_tab[CL_A_STATE];
-    int* s_last = s_tab[CL_A_LAST];
-    const int s = blockIdx.x, tid = threadIdx.x, S = g.streams;
-    int* st = state_all + (size_t)s * CL_ST_INTS;
-    int* acc_all = st + CL_ST_ACC;                                           // [slot][part][bin]
-    const bool fresh = first && reset[s];
-    int frame = fresh ? 0 : st[0];
-    int stopped = fresh ? 0 : st[1];
-#pragma unroll
-    for (int a = 0; a < CL_ARRAYS; ++a) s_tab[a][tid] = fresh ? 0 : st[CL_ST_SLOTS + a * T + tid];
-    int n_out = first ? 0 : n_final[s];
-    __syncthreads();
-
-    // ENDED slots (E, ranked e_rank in slot order) leave for the output list while it has room; they become free
-    auto emit = [&](bool E, int e_rank, int n_E) {
-        const int room = cap - n_out;
-        const bool em = E && e_rank < room;
-        if (em) {
-            int4* ev = reinterpret_cast<int4*>(events + ((size_t)s * cap + n_out + e_rank) * CL_EVENT_INTS);
-            const int* acc = acc_all + tid * 2 * CL_BINS;
-            const int nu = s_tab[CL_A_NU][tid], nl = s_tab[CL_A_NL][tid];
-            int tu, su, tl, sl;
-            cl_describe(acc, nu, &tu, &su, reinterpret_cast<int*>(ev + 4));
-            cl_describe(acc + CL_BINS, nl, &tl, &sl, reinterpret_cast<int*>(ev + 7));
-            ev[0] = make_int4(s_state[tid] == 3 ? CL_FLUSHED : CL_EXPIRED, s, s_id[tid], s_tab[CL_A_CLS][tid]);
-            ev[1] = make_int4(s_tab[CL_A_FIRST][tid], s_last[tid], s_tab[CL_A_SIGHT][tid], nu);
-            ev[2] = make_int4(nl, tu, su, tl);
-            ev[3] = make_int4(sl, tid, 0, 0);
-            ev[10] = make_int4(0, 0, 0, 0), ev[11] = make_int4(0, 0, 0, 0);
-            s_state[tid] = 0;
-        }
-        const int n_emit = n_E < room ? n_E : (room > 0 ? room : 0);
-        n_out += n_emit;
-        __syncthreads();                                                     // the accumulators are read before a row may take the slot
-    };
-
-    if (n_ticks == 0) {
-        const int m = mode[s];
-        if (m == CL_MODE_FLUSH && s_state[tid] == 1) s_state[tid] = 3;
-        if (m != CL_MODE_NONE) {
-            const bool E = tid < g.max_tracks && s_state[tid] >= 2;
-            int n_E;
-            const int e_rank = block_scan(E, s_w, n_E);
-            emit(E, e_rank, n_E);
-        }
-    }
-    int kk = 0;
-    for (; kk < n_ticks && !stopped; ++kk) {
-        const int x = kk * S + s;
-        const int off = frame_off[x], n = frame_off[x + 1] - off;            // 0..512, checked by the host
-        // ---- this thread as row tid
-        int flags = 0, rid = 0, rcls = 0;
-        const int4* inf = info + (size_t)(off + tid - info_base) * (CL_INFO_INTS / 4);
-        if (tid < n) {
-            flags = inf[0].x;
-            rid = rows6[(size_t)(off + tid) * 6 + 4], rcls = rows6[(size_t)(off + tid) * 6 + 5];
-        }
-        const int need = CL_F_VALID | CL_F_FIRST | CL_F_NONEMPTY;
-        const bool counted = (flags & need) == need;
-        // ---- this thread as slot tid
-        const int state = tid < g.max_tracks ? s_state[tid] : 0;
-        const bool expiring = state == 1 && frame - s_last[tid] > g.forget_after;
-        const bool E = state >= 2 || expiring;
-        s_live[tid] = state == 1 && !expiring;
-        __syncthreads();
-        int slot = -1;
-        if (counted)
-            for (int t = 0; t < g.max_tracks; ++t)
-                if (s_live[t] && s_id[t] == rid) slot = t;
-        const bool is_new = counted && slot < 0;
-        int n_new, n_E, n_live, n_old, n_unfit;
-        const int new_rank = block_scan(is_new, s_w, n_new);
-        const int e_rank = block_scan(E, s_w, n_E);
-        block_scan(s_live[tid], s_w, n_live);
-        block_scan(state >= 2, s_w, n_old);
-        block_scan(expiring && e_rank >= cap - n_out, s_w, n_unfit);         // ENDED now, no room in the list: the slot stays taken
-        if (n_live + n_old + n_unfit + n_new > g.max_tracks) {               // nothing of this tick is committed
-            stopped = AIC_ERR_CAPACITY;
-            break;
-        }
-        if (expiring) s_state[tid] = 2;
-        emit(E, e_rank, n_E);
-        const bool is_free = tid < g.max_tracks && s_state[tid] == 0;
-        int n_free;
-        const int free_rank = block_scan(is_free, s_w, n_free);
-        if (is_free) s_list[free_rank] = tid;
-        __syncthreads();
-        int4 tag = make_int4(-1, -1, -1, -1);
-        if (counted) {
-            const bool fresh_slot = slot < 0;
-            if (fresh_slot) {                                                // the k-th new row takes the k-th lowest free slot
-                slot = s_list[new_rank];
-                s_id[slot] = rid, s_state[slot] = 1, s_tab[CL_A_FIRST][slot] = frame, s_tab[CL_A_SIGHT][slot] = 0;
-                s_tab[CL_A_NU][slot] = 0, s_tab[CL_A_NL][slot] = 0;
-            }
-            s_last[slot] = frame, s_tab[CL_A_CLS][slot] = rcls, s_tab[CL_A_SIGHT][slot] += 1;
-            int4* acc4 = reinterpret_cast<int4*>(acc_all + slot * 2 * CL_BINS);
-#pragma unroll
-            for (int part = 0; part < 2; ++part) {
-                int& ns = s_tab[part ? CL_A_NL : CL_A_NU][slot];
-                const bool add = (flags & (part ? CL_F_LOWER : CL_F_UPPER)) && ns < CL_SAMPLES_MAX;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    int4 a = fresh_slot ? make_int4(0, 0, 0, 0) : acc4[part * 3 + q];
-                    if (add) {
-                        const int4 v = inf[1 + part * 3 + q];
-                        a.x += v.x, a.y += v.y, a.z += v.z, a.w += v.w;
-                    }
-                    if (add || fresh_slot) acc4[part * 3 + q] = a;
-                }
-                if (add) ns += 1;
-            }
-            const int* acc = acc_all + slot * 2 * CL_BINS;
-            const int nu = s_tab[CL_A_NU][slot], nl = s_tab[CL_A_NL][slot];
-            if (nu > 0) tag.x = top_of(acc), tag.z = acc[tag.x] / nu;
-            else tag.z = 0;
-            if (nl > 0) tag.y = top_of(acc + CL_BINS), tag.w = acc[CL_BINS + tag.y] / nl;
-            else tag.w = 0;
-        }
-        if (row_tags && tid < n) row_tags[off + tid] = tag;
-        ++frame;
-        __syncthreads();
-    }
-    __syncthreads();
-    if (row_tags)                                                            // a stopped stream's rows: the tick it stopped at and all after
-        for (; kk < n_ticks; ++kk) {
-            const int x = kk * S + s;
-            const int off = frame_off[x], n = frame_off[x + 1] - off;
-            if (tid < n) row_tags[off + tid] = make_int4(-1, -1, -1, -1);
-        }
-#pragma unroll
-    for (int a = 0; a < CL_ARRAYS; ++a) st[CL_ST_SLOTS + a * T + tid] = s_tab[a][tid];
-    int n_pend;
-    block_scan(tid < g.max_tracks && s_state[tid] >= 2, s_w, n_pend);
-    if (tid == 0) st[0] = frame, st[1] = stopped, n_final[s] = n_out, pending[s] = n_pend, status[s] = stopped;
+    const SlotCall c{frame_off, n_ticks, rows6, reset, mode, first, g.streams, g.max_tracks, g.forget_after, state_all, cap, n_final, pending, status,
+                     events};
+    ColoursWalk v{info, info_base, state_all + (size_t)blockIdx.x * CL_ST_INTS + CL_ST_ACC, row_tags};
+    slot_walk(c, v);
 }
 
 }  // namespace

@@ -17,22 +17,13 @@
 // left_walk_kernel       one thread per stream: matching, slots, alarms and events, tick by tick; writes records, objects, events.
 // left_events_kernel     one block: packs the per-frame event lists of a launch in frame order behind the call's earlier ones.
 #include "left.hpp"
+#include "stage_dev.hpp"
 
 namespace aic {
 
 namespace {
 
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int iabs(int a) { return a < 0 ? -a : a; }
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ bool coord_ok(int v) { return v >= -SC_COORD_MAX && v <= SC_COORD_MAX; }
 
 __global__ __launch_bounds__(256) void left_occupancy_kernel(const int* __restrict__ frame_off, int row_blocks, const int* __restrict__ rows6, ScGeom g,
                                                              int pad, uint8_t* __restrict__ occ, int* __restrict__ occ_id) {
@@ -43,7 +34,7 @@ __global__ __launch_bounds__(256) void left_occupancy_kernel(const int* __restri
     if (r >= n) return;
     const int* row = rows6 + (size_t)(off + r) * 6;
     const int x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3], id = row[4];
-    const bool valid = coord_ok(x1) && coord_ok(y1) && coord_ok(x2) && coord_ok(y2) && x2 >= x1 && y2 >= y1;
+    const bool valid = row_valid(x1, y1, x2, y2, SC_COORD_MAX);
     const int X0 = imax(x1, 0), Y0 = imax(y1, 0), X1 = imin(x2, g.wc * g.c - 1), Y1 = imin(y2, g.hc * g.c - 1);
     if (!valid || X1 < X0 || Y1 < Y0) return;
     const int cx0 = imax(X0 / g.c - pad, 0), cy0 = imax(Y0 / g.c - pad, 0), cx1 = imin(X1 / g.c + pad, g.wc - 1), cy1 = imin(Y1 / g.c + pad, g.hc - 1);

@@ -15,24 +15,11 @@
 // scene_rows_kernel   one wave per tracker row: the moving share of the cells its box covers.
 // scene_walk_kernel   one thread per stream: conditions, alarms and the gate, tick by tick; writes the records.
 #include "scene.hpp"
+#include "stage_dev.hpp"
 
 namespace aic {
 
 namespace {
-
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = imax(v, __shfl_xor(v, d));
-    return v;
-}
 
 // weights of the four bytes of a dword whose first byte is channel p (0 B, 1 G, 2 R), lowest byte first
 __device__ __forceinline__ unsigned weight_word(int p) { return p == 0 ? 0x1D4D961Du : p == 1 ? 0x961D4D96u : 0x4D961D4Du; }
@@ -205,8 +192,6 @@ __global__ __launch_bounds__(256) void scene_stats_kernel(const uint8_t* __restr
     }
 }
 
-__device__ __forceinline__ bool coord_ok(int v) { return v >= -SC_COORD_MAX && v <= SC_COORD_MAX; }
-
 __global__ __launch_bounds__(256) void scene_rows_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ frame_off, int row_blocks,
                                                          const int* __restrict__ rows6, ScGeom g, int* __restrict__ row_motion) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -217,7 +202,7 @@ __global__ __launch_bounds__(256) void scene_rows_kernel(const uint8_t* __restri
     const int* row = rows6 + (size_t)(off + r) * 6;
     const int x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
     int out = -1;
-    const bool valid = coord_ok(x1) && coord_ok(y1) && coord_ok(x2) && coord_ok(y2) && x2 >= x1 && y2 >= y1;
+    const bool valid = row_valid(x1, y1, x2, y2, SC_COORD_MAX);
     const int X0 = imax(x1, 0), Y0 = imax(y1, 0), X1 = imin(x2, g.wc * g.c - 1), Y1 = imin(y2, g.hc * g.c - 1);
     if (valid && X1 >= X0 && Y1 >= Y0) {
         const int cx0 = X0 / g.c, cy0 = Y0 / g.c, cw = X1 / g.c - cx0 + 1, ch = Y1 / g.c - cy0 + 1, covered = cw * ch;

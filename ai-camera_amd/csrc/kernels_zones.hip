@@ -7,6 +7,7 @@
 //                        launch (enter frames stay in global memory: they are touched by events only).  A thread is slot t of the
 //                        table AND row t of the frame.
 #include "zones.hpp"
+#include "stage_dev.hpp"
 
 namespace aic {
 
@@ -55,29 +56,6 @@ __global__ __launch_bounds__(256) void zones_classify_kernel(const int* __restri
         const unsigned long long b = __ballot(in);
         if (act && z == 0) cls4[off + r] = make_int4(px, py, (int)(unsigned)(b >> (32 * ((tid & 63) >> 5))), valid ? 1 : 0);
     }
-}
-
-// exclusive prefix sum over the 512 threads of the block; total = the block's sum.  s_w: 8 ints of LDS, free again on return
-__device__ __forceinline__ int block_scan(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int t = s_w[i];
-        base += i < w ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
 }
 
 __device__ __forceinline__ void put_event(int* __restrict__ ev, int e, int cap, int kind, int index, int id, int cls, int frame, int value, int ax, int ay) {

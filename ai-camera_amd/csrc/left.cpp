@@ -1,7 +1,6 @@
 // left.cpp -- the left-objects stage (left.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_left.hip (and launch_scene_gray) or the call raises.
 #include "left.hpp"
-#include "row_stage.hpp"
 
 #include <algorithm>
 
@@ -21,49 +20,26 @@ void left_check_config(int device, const aic_left_config* p) {
 }
 
 Left::Left(int device, const aic_left_config& p)
-    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.cell, p.frame_h / p.cell, p.frame_w / p.cell}, max_objects(p.max_objects),
-      reset_pending(p.streams, 1) {}
+    : FrameBank(device, p.streams, p.frame_h, p.frame_w), g{p.streams, p.frame_h, p.frame_w, p.cell, p.frame_h / p.cell, p.frame_w / p.cell},
+      max_objects(p.max_objects) {}
 
 void Left::option(const std::string& k, int value) {
-    struct Opt { const char* name; int LfOpts::*field; int lo, hi; };
-    static const Opt table[] = {
+    static const IntOpt<LfOpts> table[] = {
         {"fast_shift", &LfOpts::fast_shift, 1, 8}, {"slow_shift", &LfOpts::slow_shift, 1, 12}, {"thresh", &LfOpts::thresh, 1, 255},
         {"warmup", &LfOpts::warmup, 1, 1 << 20}, {"decay", &LfOpts::decay, 0, 64}, {"min_ticks", &LfOpts::min_ticks, 1, 65534},
         {"absorb_ticks", &LfOpts::absorb_ticks, 2, 65535}, {"pad_cells", &LfOpts::pad_cells, 0, 8}, {"owner_window", &LfOpts::owner_window, 0, 1 << 20},
         {"min_cells", &LfOpts::min_cells, 1, LF_CELLS_MAX}, {"max_cells", &LfOpts::max_cells, 1, LF_CELLS_MAX},
         {"alarm_hold", &LfOpts::alarm_hold, 1, 1 << 20}, {"gone_ticks", &LfOpts::gone_ticks, 0, 1 << 20}};
-    if (k == "ticks_per_launch") {
-        AIC_REQUIRE(value >= 0 && value <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
-        ticks_per_launch = value;
-        return;
-    }
-    if (k == "launch_budget_mb") {
-        AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
-        launch_budget_mb = value;
-        return;
-    }
-    for (const Opt& t : table) {
-        if (k != t.name) continue;
-        AIC_REQUIRE(value >= t.lo && value <= t.hi, AIC_ERR_INVALID, k + " must be in " + std::to_string(t.lo) + ".." + std::to_string(t.hi));
-        LfOpts n = o;
-        n.*t.field = value;
+    if (launch_option(k, value, SC_TICKS_MAX)) return;
+    const bool known = table_option(table, o, k, value, [&](const LfOpts& n) {
         AIC_REQUIRE(n.absorb_ticks > n.min_ticks, AIC_ERR_INVALID, k + ": absorb_ticks must exceed min_ticks");
         AIC_REQUIRE(n.max_cells >= n.min_cells, AIC_ERR_INVALID, k + ": max_cells must not be below min_cells");
-        o = n;
-        return;
-    }
-    AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown left-objects option: " + k);
-}
-
-void Left::reset(int stream) {
-    AIC_REQUIRE(stream >= -1 && stream < g.streams, AIC_ERR_INVALID, "stream outside the bank (-1 = every stream)");
-    for (int s = 0; s < g.streams; ++s)
-        if (stream < 0 || stream == s) reset_pending[s] = 1;
+    });
+    AIC_REQUIRE(known, AIC_ERR_INVALID, "unknown left-objects option: " + k);
 }
 
 void Left::touch_device() {
-    if (!dev) dev = &device(device_id);
-    dev->use();
+    use_device();
     if (!d_scalars.p) {
         const size_t n = (size_t)g.streams * cells();
         hipStream_t st = dev->s_trk;
@@ -88,56 +64,32 @@ void Left::touch_device() {
 void Left::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap_events,
                   int32_t* records, int32_t* objects, int32_t* events, int32_t* n_events, int32_t* status, uint8_t* cand, int32_t* labels) {
     const int S = g.streams, M = max_objects;
-    AIC_REQUIRE(ticks >= 0 && ticks <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
-    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
-    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
+    const long F = check_call(ticks, SC_TICKS_MAX, frames_mem, rows_mem);
     AIC_REQUIRE(cap_events >= 0 && cap_events <= (1 << 24), AIC_ERR_INVALID, "cap_events must be in 0..2^24");
     AIC_REQUIRE(n_events, AIC_ERR_INVALID, "NULL n_events");
     AIC_REQUIRE(cap_events == 0 || events, AIC_ERR_INVALID, "NULL events");
-    const long F = (long)ticks * S;
-    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
     AIC_REQUIRE(F == 0 || (frames && records && objects), AIC_ERR_INVALID, "NULL frames, records or objects");
     const bool with_rows = counts != nullptr && F > 0;
-    long total = 0;
-    if (with_rows && rows_mem == AIC_HOST) total = check_row_counts(counts, F, SC_ROWS_MAX, rows6);
-
-    touch_device();
-    *n_events = 0;
-    if (status) *status = AIC_OK;
+    const long total = count_rows(counts, with_rows, F, SC_ROWS_MAX, rows6, rows_mem, [&] {
+        touch_device();
+        *n_events = 0;
+        if (status) *status = AIC_OK;
+    }, [](long) {});
     if (F == 0) return;
     hipStream_t st = dev->s_trk;
-    if (with_rows && rows_mem == AIC_DEVICE) total = check_row_counts(counts = fetch_counts(h_counts, counts, F, st), F, SC_ROWS_MAX, rows6);
-    // ---- staging: reset[S] | frame_off[F + 1] | rows (host memory only; row_stage.hpp)
-    const size_t o_off = S;
-    const RowStage rs(o_off, o_off + F + 1, total, with_rows && rows_mem == AIC_HOST);
-    h_stage.ensure(rs.n_ints);
-    grow(d_stage, rs.n_ints, "the staged rows");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s];
-    rs.fill(h, with_rows ? counts : nullptr, F, rows6);
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* d_rows = rs.d_rows(d_stage.p, rows6);
-    const int* d_off = d_stage.p + o_off;
+    const BankStage bs = upload(F, with_rows ? counts : nullptr, total, rows6, with_rows && rows_mem == AIC_HOST);
+    const int* d_rows = bs.d_rows(d_stage.p, rows6);
+    const int* d_off = d_stage.p + bs.o_off;
     grow(d_events, std::max<size_t>(1, (size_t)cap_events * LF_EVENT_INTS), "the events");
     HIP_CHECK(hipMemsetAsync(d_total.p, 0, sizeof(int), st));
 
-    const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
     const size_t tick_cells = cells() * S, cell_bytes = labels ? 20 : 16;
     {
         Prof pr(*dev, PROF_MISC, st, 0, (double)F * frame_bytes);
-        for (int lo = 0; lo < ticks;) {
-            int hi = lo + 1;                                                 // one tick at the least
-            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) && (size_t)(hi + 1 - lo) * tick_cells * cell_bytes <= budget &&
-                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
-                ++hi;
+        const auto launch_bytes = [&](int lo, int hi) { return (size_t)(hi - lo) * tick_cells * cell_bytes; };
+        launches(frames, frames_mem, ticks, launch_bytes, [&](int lo, int hi, const uint8_t* d_fr) {
             const int n = hi - lo, n_frames = n * S;
             const size_t nc = (size_t)n * tick_cells;
-            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
-            if (frames_mem == AIC_HOST) {
-                grow(d_frames, (size_t)n * tick_bytes, "the staged frames");
-                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)n * tick_bytes, hipMemcpyHostToDevice, st));
-                d_fr = d_frames.p;
-            }
             grow(d_gray, nc, "the gray grids");
             grow(d_occ, nc, "the occupancy");
             grow(d_occ_id, nc, "the occupancy");
@@ -157,8 +109,7 @@ void Left::update(const void* frames, int frames_mem, int ticks, const int32_t* 
             HIP_CHECK(hipMemsetAsync(d_occ.p, 0, nc, st));
             launch_scene_gray(d_fr, n_frames, g, d_gray.p, st);
             if (total) {
-                int max_rows = 0;
-                for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
+                const int max_rows = this->max_rows(counts, lo, hi);
                 if (max_rows) HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_occ_id.p), LF_NONE, nc, st));
                 launch_left_occupancy(d_off + (size_t)lo * S, n_frames, max_rows, d_rows, g, o.pad_cells, d_occ.p, d_occ_id.p, st);
             }
@@ -172,8 +123,7 @@ void Left::update(const void* frames, int frames_mem, int ticks, const int32_t* 
                                      hipMemcpyDeviceToHost, st));
             if (cand) HIP_CHECK(hipMemcpyAsync(cand + (size_t)lo * tick_cells, d_cand.p, nc, hipMemcpyDeviceToHost, st));
             if (labels) HIP_CHECK(hipMemcpyAsync(labels + (size_t)lo * tick_cells, d_labels.p, nc * sizeof(int), hipMemcpyDeviceToHost, st));
-            lo = hi;
-        }
+        });
     }
     int n_ev = 0;
     HIP_CHECK(hipMemcpyAsync(&n_ev, d_total.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -239,42 +189,30 @@ int aic_left_create(int device, const aic_left_config* config, aic_left** out) {
     });
 }
 
-int aic_left_destroy(aic_left* s) {
-    return guarded([&] {
-        if (s && s->s.dev) { s->s.dev->use(); (void)hipStreamSynchronize(s->s.dev->s_trk); }
-        delete s;
-    });
-}
+int aic_left_destroy(aic_left* s) { return destroy_handle(s, s ? s->s.dev : nullptr); }
 
 int aic_left_option(aic_left* s, const char* key, int value) {
-    return guarded([&] {
-        AIC_REQUIRE(s && key, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(s, [&] {
+        AIC_REQUIRE(key, AIC_ERR_INVALID, "NULL argument");
         s->s.option(key, value);
     });
 }
 
 int aic_left_reset(aic_left* s, int stream) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
-        s->s.reset(stream);
-    });
+    return with_handle(s, [&] { s->s.reset(stream); });
 }
 
 int aic_left_update(aic_left* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem,
                     int cap_events, int32_t* records, int32_t* objects, int32_t* events, int32_t* n_events, int32_t* status, uint8_t* cand,
                     int32_t* labels) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(s, [&] {
         s->s.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, cap_events, records, objects, events, n_events, status, cand, labels);
     });
 }
 
 int aic_left_export(aic_left* s, int stream, int32_t* fast, int32_t* slow, int32_t* still, int32_t* last_id, int32_t* last_tick, int32_t* slots,
                     int32_t* scalars) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
-        s->s.export_stream(stream, fast, slow, still, last_id, last_tick, slots, scalars);
-    });
+    return with_handle(s, [&] { s->s.export_stream(stream, fast, slow, still, last_id, last_tick, slots, scalars); });
 }
 
 }  // extern "C"

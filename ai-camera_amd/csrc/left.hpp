@@ -70,26 +70,19 @@ void launch_left_events(const int* ev_count, const int* ev, int n_frames, int ma
 
 void left_check_config(int device, const aic_left_config* p);
 
-struct Left {
-    int device_id;
-    Device* dev = nullptr;                       // resolved by the first call that reaches the device
+struct Left : FrameBank {
     ScGeom g;
     int max_objects;
     LfOpts o;
-    int ticks_per_launch = 0;                    // 0: as many ticks per launch as launch_budget_mb allows; k: at most k
-    int launch_budget_mb = 1024;
-    std::vector<char> reset_pending;
     DevBuf<uint16_t> d_fast, d_slow, d_still;
-    DevBuf<uint8_t> d_gray, d_occ, d_cand, d_slow8, d_frames;
-    DevBuf<int> d_last_id, d_last_tick, d_occ_id, d_own_tick, d_own_id, d_labels, d_scalars, d_slots, d_stage, d_head, d_blobs, d_rec, d_obj,
-        d_evc, d_ev, d_events, d_total;
-    PinBuf<int> h_stage;
-    std::vector<int> h_counts;
+    DevBuf<uint8_t> d_gray, d_occ, d_cand, d_slow8;
+    DevBuf<int> d_last_id, d_last_tick, d_occ_id, d_own_tick, d_own_id, d_labels, d_scalars, d_slots, d_head, d_blobs, d_rec, d_obj, d_evc, d_ev,
+        d_events, d_total;
 
     Left(int device, const aic_left_config& p);
     size_t cells() const { return (size_t)g.hc * g.wc; }
     void option(const std::string& key, int value);
-    void reset(int stream);
+    void reset(int stream) { reset_streams(stream, "stream outside the bank (-1 = every stream)"); }
     void update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap_events,
                 int32_t* records, int32_t* objects, int32_t* events, int32_t* n_events, int32_t* status, uint8_t* cand, int32_t* labels);
     void export_stream(int stream, int32_t* fast, int32_t* slow, int32_t* still, int32_t* last_id, int32_t* last_tick, int32_t* slots,

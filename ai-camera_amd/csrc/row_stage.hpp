@@ -1,5 +1,6 @@
-// row_stage.hpp -- what the analytics stages (zones.cpp, bestshot.cpp, scene.cpp) share around a call's row lists: the check of the per-frame
-// counts, their prefix sums in the stage's int staging buffer with host rows riding behind, and the buffer growth that reports a capacity error.
+// row_stage.hpp -- the small steps every stage with row lists or growing device buffers takes (bank_stage.hpp and through it zones.cpp,
+// bestshot.cpp, colours.cpp, scene.cpp, left.cpp; jpeg.cpp, jpegdec.cpp): the check of the per-frame counts, the fetch of counts that lie in
+// device memory, and the buffer growth that reports a capacity error.  Where the rows lie in a staging buffer is bank_call.hpp's.
 #pragma once
 #include <string>
 #include <vector>
@@ -27,21 +28,6 @@ inline const int32_t* fetch_counts(std::vector<int>& h, const int32_t* d_counts,
     HIP_CHECK(hipStreamSynchronize(st));
     return h.data();
 }
-
-// frame_off[F + 1] at int o_off of a stage's staging buffer and, for rows in host memory, the rows at o_rows (the buffer's end)
-struct RowStage {
-    size_t o_off, o_rows, n_ints;   // n_ints: the whole staging buffer
-    bool staged;
-    RowStage(size_t off, size_t rows, long total, bool host_rows)
-        : o_off(off), o_rows(rows), n_ints(rows + (host_rows ? (size_t)total * 6 : 0)), staged(host_rows) {}
-    void fill(int* h, const int32_t* counts, long F, const int32_t* rows6) const {   // counts NULL: a call without rows
-        h[o_off] = 0;
-        for (long i = 0; i < F; ++i) h[o_off + i + 1] = h[o_off + i] + (counts ? counts[i] : 0);
-        if (n_ints > o_rows) std::memcpy(h + o_rows, rows6, (n_ints - o_rows) * sizeof(int));
-    }
-    // the rows on the device: the staged copy, or the caller's pointer
-    const int* d_rows(const int* d_stage, const int32_t* rows6) const { return staged ? d_stage + o_rows : rows6; }
-};
 
 // grows a device buffer; a failed allocation is a capacity error of the call, not a runtime fault
 template <class B>

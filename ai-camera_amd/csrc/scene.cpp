@@ -1,7 +1,6 @@
 // scene.cpp -- the scene-watch object (scene.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_scene.hip or the call raises.
 #include "scene.hpp"
-#include "row_stage.hpp"
 
 #include <algorithm>
 
@@ -18,48 +17,25 @@ void scene_check_config(int device, const aic_scene_config* p) {
 }
 
 Scene::Scene(int device, const aic_scene_config& p)
-    : device_id(device), g{p.streams, p.frame_h, p.frame_w, p.cell, p.frame_h / p.cell, p.frame_w / p.cell}, reset_pending(p.streams, 1) {}
+    : FrameBank(device, p.streams, p.frame_h, p.frame_w), g{p.streams, p.frame_h, p.frame_w, p.cell, p.frame_h / p.cell, p.frame_w / p.cell} {}
 
 void Scene::option(const std::string& k, int value) {
-    struct Opt { const char* name; int ScOpts::*field; int lo, hi; };
-    static const Opt table[] = {
+    static const IntOpt<ScOpts> table[] = {
         {"thresh", &ScOpts::thresh, 0, 255}, {"noise_k_q4", &ScOpts::noise_k_q4, 0, 4096}, {"warmup", &ScOpts::warmup, 1, 1 << 20},
         {"big_thresh", &ScOpts::big_thresh, 0, 255}, {"learn_shift", &ScOpts::learn_shift, 1, 12}, {"slow_extra", &ScOpts::slow_extra, 0, 8},
         {"dev_init_q8", &ScOpts::dev_init_q8, 0, 65280}, {"min_neighbours", &ScOpts::min_neighbours, 1, 9}, {"dark_luma", &ScOpts::dark_luma, 0, 256},
         {"bright_luma", &ScOpts::bright_luma, 0, 255}, {"min_ref_q8", &ScOpts::min_ref_q8, 0, 1 << 20}, {"defocus_q8", &ScOpts::defocus_q8, 0, 256},
         {"scene_q16", &ScOpts::scene_q16, 0, 65536}, {"ref_shift", &ScOpts::ref_shift, 1, 12}, {"hold", &ScOpts::hold, 1, 1 << 20},
         {"gate_cells", &ScOpts::gate_cells, 1, 1 << 24}, {"gate_hold", &ScOpts::gate_hold, 0, 1 << 20}};
-    if (k == "ticks_per_launch") {
-        AIC_REQUIRE(value >= 0 && value <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks_per_launch: 0 = as many as the budget allows, or 1..65536");
-        ticks_per_launch = value;
-        return;
-    }
-    if (k == "launch_budget_mb") {
-        AIC_REQUIRE(value >= 1 && value <= 65536, AIC_ERR_INVALID, "launch_budget_mb must be in 1..65536");
-        launch_budget_mb = value;
-        return;
-    }
-    for (const Opt& t : table) {
-        if (k != t.name) continue;
-        AIC_REQUIRE(value >= t.lo && value <= t.hi, AIC_ERR_INVALID, k + " must be in " + std::to_string(t.lo) + ".." + std::to_string(t.hi));
-        ScOpts n = o;
-        n.*t.field = value;
+    if (launch_option(k, value, SC_TICKS_MAX)) return;
+    const bool known = table_option(table, o, k, value, [](const ScOpts& n) {
         AIC_REQUIRE(n.learn_shift + n.slow_extra <= 14, AIC_ERR_INVALID, "learn_shift + slow_extra must not exceed 14");
-        o = n;
-        return;
-    }
-    AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown scene option: " + k);
-}
-
-void Scene::reset(int stream) {
-    AIC_REQUIRE(stream >= -1 && stream < g.streams, AIC_ERR_INVALID, "stream outside the scene bank (-1 = every stream)");
-    for (int s = 0; s < g.streams; ++s)
-        if (stream < 0 || stream == s) reset_pending[s] = 1;
+    });
+    AIC_REQUIRE(known, AIC_ERR_INVALID, "unknown scene option: " + k);
 }
 
 void Scene::touch_device() {
-    if (!dev) dev = &device(device_id);
-    dev->use();
+    use_device();
     if (!d_scalars.p) {
         const size_t n = (size_t)g.streams * cells();
         grow(d_bg, n, "the background model");
@@ -76,56 +52,26 @@ void Scene::touch_device() {
 void Scene::update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int32_t* records,
                    uint8_t* masks, int32_t* row_motion) {
     const int S = g.streams;
-    AIC_REQUIRE(ticks >= 0 && ticks <= SC_TICKS_MAX, AIC_ERR_INVALID, "ticks must be in 0..65536");
-    AIC_REQUIRE(frames_mem == AIC_HOST || frames_mem == AIC_DEVICE, AIC_ERR_INVALID, "frames_mem must be AIC_HOST or AIC_DEVICE");
-    AIC_REQUIRE(rows_mem == AIC_HOST || rows_mem == AIC_DEVICE, AIC_ERR_INVALID, "rows_mem must be AIC_HOST or AIC_DEVICE");
-    const long F = (long)ticks * S;
-    AIC_REQUIRE(F <= (1 << 20), AIC_ERR_INVALID, "more than 2^20 frames in one call");
+    const long F = check_call(ticks, SC_TICKS_MAX, frames_mem, rows_mem);
     AIC_REQUIRE(F == 0 || (frames && records), AIC_ERR_INVALID, "NULL frames or records");
     const bool with_rows = counts != nullptr && F > 0;
     AIC_REQUIRE(counts || !row_motion, AIC_ERR_INVALID, "row_motion without counts");
-    auto check_counts = [&](const int32_t* c) {
-        const long total = check_row_counts(c, F, SC_ROWS_MAX, rows6);
-        AIC_REQUIRE(total == 0 || row_motion, AIC_ERR_INVALID, "rows without row_motion");
-        return total;
-    };
-    long total = 0;
-    if (with_rows && rows_mem == AIC_HOST) total = check_counts(counts);
-
-    touch_device();
+    const long total = count_rows(counts, with_rows, F, SC_ROWS_MAX, rows6, rows_mem, [&] { touch_device(); }, [&](long t) {
+        AIC_REQUIRE(t == 0 || row_motion, AIC_ERR_INVALID, "rows without row_motion");
+    });
     if (F == 0) return;
     hipStream_t st = dev->s_trk;
-    if (with_rows && rows_mem == AIC_DEVICE) total = check_counts(counts = fetch_counts(h_counts, counts, F, st));   // the counts decide the launches
-    // ---- staging: reset[S] | frame_off[F + 1] | rows (host memory only; row_stage.hpp)
-    const size_t o_off = S;
-    const RowStage rs(o_off, o_off + F + 1, total, with_rows && rows_mem == AIC_HOST);
-    h_stage.ensure(rs.n_ints);
-    grow(d_stage, rs.n_ints, "the staged rows");
-    int* h = h_stage.p;
-    for (int s = 0; s < S; ++s) h[s] = reset_pending[s];
-    rs.fill(h, with_rows ? counts : nullptr, F, rows6);
-    HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* d_rows = rs.d_rows(d_stage.p, rows6);
-    const int* d_off = d_stage.p + o_off;
+    const BankStage bs = upload(F, with_rows ? counts : nullptr, total, rows6, with_rows && rows_mem == AIC_HOST);
+    const int* d_rows = bs.d_rows(d_stage.p, rows6);
+    const int* d_off = d_stage.p + bs.o_off;
     grow(d_rec, (size_t)F * SC_RECORD_INTS, "the records");
     grow(d_rm, std::max<size_t>(8, (size_t)total), "the row motion");
 
-    const size_t budget = (size_t)launch_budget_mb << 20, frame_bytes = (size_t)g.h * g.w * 3, tick_bytes = frame_bytes * S;
     const size_t tick_cells = cells() * S;
     {
         Prof pr(*dev, PROF_MISC, st, 0, (double)F * frame_bytes);
-        for (int lo = 0; lo < ticks;) {
-            int hi = lo + 1;                                                 // one tick at the least
-            while (hi < ticks && (ticks_per_launch == 0 || hi - lo < ticks_per_launch) && (size_t)(hi + 1 - lo) * tick_cells <= budget &&
-                   (frames_mem == AIC_DEVICE || (size_t)(hi + 1 - lo) * tick_bytes <= budget))
-                ++hi;
+        launches(frames, frames_mem, ticks, [&](int lo, int hi) { return (size_t)(hi - lo) * tick_cells; }, [&](int lo, int hi, const uint8_t* d_fr) {
             const int n = hi - lo, n_frames = n * S;
-            const uint8_t* d_fr = static_cast<const uint8_t*>(frames) + (size_t)lo * tick_bytes;
-            if (frames_mem == AIC_HOST) {
-                grow(d_frames, (size_t)n * tick_bytes, "the staged frames");
-                HIP_CHECK(hipMemcpyAsync(d_frames.p, d_fr, (size_t)n * tick_bytes, hipMemcpyHostToDevice, st));
-                d_fr = d_frames.p;
-            }
             grow(d_gray, (size_t)n * tick_cells, "the gray grids");
             grow(d_bits, (size_t)n * tick_cells, "the model bits");
             grow(d_mask, (size_t)n * tick_cells, "the masks");
@@ -134,15 +80,10 @@ void Scene::update(const void* frames, int frames_mem, int ticks, const int32_t*
             launch_scene_gray(d_fr, n_frames, g, d_gray.p, st);
             launch_scene_model(d_gray.p, n, g, o, d_scalars.p, d_stage.p, lo == 0, d_bg.p, d_dev.p, d_prev.p, d_bits.p, st);
             launch_scene_stats(d_gray.p, d_bits.p, n_frames, g, o, d_mask.p, d_acc.p, st);
-            if (total) {
-                int max_rows = 0;
-                for (long f = (long)lo * S; f < (long)hi * S; ++f) max_rows = std::max(max_rows, (int)counts[f]);
-                launch_scene_rows(d_mask.p, d_off + (size_t)lo * S, n_frames, max_rows, d_rows, g, d_rm.p, st);
-            }
+            if (total) launch_scene_rows(d_mask.p, d_off + (size_t)lo * S, n_frames, max_rows(counts, lo, hi), d_rows, g, d_rm.p, st);
             launch_scene_walk(d_acc.p, n, g, o, d_stage.p, lo == 0, d_scalars.p, d_rec.p + (size_t)lo * S * SC_RECORD_INTS, st);
             if (masks) HIP_CHECK(hipMemcpyAsync(masks + (size_t)lo * tick_cells, d_mask.p, (size_t)n * tick_cells, hipMemcpyDeviceToHost, st));
-            lo = hi;
-        }
+        });
     }
     HIP_CHECK(hipMemcpyAsync(records, d_rec.p, (size_t)F * SC_RECORD_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
     if (total) HIP_CHECK(hipMemcpyAsync(row_motion, d_rm.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -189,40 +130,26 @@ int aic_scene_create(int device, const aic_scene_config* config, aic_scene** out
     });
 }
 
-int aic_scene_destroy(aic_scene* s) {
-    return guarded([&] {
-        if (s && s->s.dev) { s->s.dev->use(); (void)hipStreamSynchronize(s->s.dev->s_trk); }
-        delete s;
-    });
-}
+int aic_scene_destroy(aic_scene* s) { return destroy_handle(s, s ? s->s.dev : nullptr); }
 
 int aic_scene_option(aic_scene* s, const char* key, int value) {
-    return guarded([&] {
-        AIC_REQUIRE(s && key, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(s, [&] {
+        AIC_REQUIRE(key, AIC_ERR_INVALID, "NULL argument");
         s->s.option(key, value);
     });
 }
 
 int aic_scene_reset(aic_scene* s, int stream) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
-        s->s.reset(stream);
-    });
+    return with_handle(s, [&] { s->s.reset(stream); });
 }
 
 int aic_scene_update(aic_scene* s, const uint8_t* frames_bgr, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6,
                      int rows_mem, int32_t* records, uint8_t* masks, int32_t* row_motion) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
-        s->s.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, records, masks, row_motion);
-    });
+    return with_handle(s, [&] { s->s.update(frames_bgr, frames_mem, ticks, counts, rows6, rows_mem, records, masks, row_motion); });
 }
 
 int aic_scene_export(aic_scene* s, int stream, int32_t* bg, int32_t* dev, int32_t* prev, int32_t* scalars) {
-    return guarded([&] {
-        AIC_REQUIRE(s, AIC_ERR_INVALID, "NULL argument");
-        s->s.export_stream(stream, bg, dev, prev, scalars);
-    });
+    return with_handle(s, [&] { s->s.export_stream(stream, bg, dev, prev, scalars); });
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 // AIC_ERR_CAPACITY.  A call's ticks are cut into launches so that the gray buffer and the staged frames each stay below
 // launch_budget_mb (option, default 1024), one tick per launch at the least.  create, option and reset never touch the device.
 #pragma once
-#include "common.hpp"
+#include "bank_stage.hpp"
 
 namespace aic {
 
@@ -59,24 +59,17 @@ void launch_scene_walk(const int* acc, int n_ticks, const ScGeom& g, const ScOpt
 
 void scene_check_config(int device, const aic_scene_config* p);
 
-struct Scene {
-    int device_id;
-    Device* dev = nullptr;                       // resolved by the first call that reaches the device
+struct Scene : FrameBank {
     ScGeom g;
     ScOpts o;
-    int ticks_per_launch = 0;                    // 0: as many ticks per launch as launch_budget_mb allows; k: at most k
-    int launch_budget_mb = 1024;
-    std::vector<char> reset_pending;
     DevBuf<uint16_t> d_bg, d_dev;
-    DevBuf<uint8_t> d_prev, d_gray, d_bits, d_mask, d_frames;
-    DevBuf<int> d_scalars, d_stage, d_acc, d_rec, d_rm;
-    PinBuf<int> h_stage;
-    std::vector<int> h_counts;
+    DevBuf<uint8_t> d_prev, d_gray, d_bits, d_mask;
+    DevBuf<int> d_scalars, d_acc, d_rec, d_rm;
 
     Scene(int device, const aic_scene_config& p);
     size_t cells() const { return (size_t)g.hc * g.wc; }
     void option(const std::string& key, int value);
-    void reset(int stream);
+    void reset(int stream) { reset_streams(stream, "stream outside the scene bank (-1 = every stream)"); }
     void update(const void* frames, int frames_mem, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int32_t* records,
                 uint8_t* masks, int32_t* row_motion);
     void export_stream(int stream, int32_t* bg, int32_t* dv, int32_t* prev, int32_t* scalars);

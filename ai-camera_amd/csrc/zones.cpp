@@ -1,7 +1,7 @@
 // zones.cpp -- the zone / line counting object (zones.hpp) and its C ABI.  Every argument is checked before the device is touched; the
 // arithmetic runs in kernels_zones.hip or the call raises.
 #include "zones.hpp"
-#include "row_stage.hpp"
+#include "bank_stage.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -82,9 +82,9 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
         d_geo.alloc((size_t)S * ZONES_GEO_INTS);
         h_cnt.alloc(ZONES_CNT);
     }
-    // ---- staging: fps[S] | fstart[S] | reset[S] | frame_off[F + 1] | frame_stream[F] | rows (host memory only; row_stage.hpp)
+    // ---- staging: fps[S] | fstart[S] | reset[S] | frame_off[F + 1] | frame_stream[F] | rows (host memory only; bank_call.hpp)
     const size_t o_fstart = S, o_reset = 2 * (size_t)S, o_off = 3 * (size_t)S, o_fs = o_off + F + 1;
-    const RowStage rs(o_off, o_fs + F, total, mem == AIC_HOST);
+    const BankStage rs(S, F, o_off, o_fs + F, total, mem == AIC_HOST);
     h_stage.ensure(rs.n_ints);
     d_stage.ensure(rs.n_ints);
     d_cls4.ensure(std::max<size_t>(4, (size_t)total * 4));
@@ -94,7 +94,7 @@ void Zones::update(const int32_t* fps, const int32_t* counts, const int32_t* row
         h[s] = fps[s], h[o_fstart + s] = (int)f, h[o_reset + s] = reset_pending[s];
         for (int k = 0; k < fps[s]; ++k) h[o_fs + f++] = s;
     }
-    rs.fill(h, counts, F, rows6);
+    rs.fill(h, counts, rows6);
     HIP_CHECK(hipMemcpyAsync(d_stage.p, h, rs.n_ints * sizeof(int), hipMemcpyHostToDevice, st));
     // ---- geometry that changed since the last update
     const long n_dirty = std::count(geo_dirty.begin(), geo_dirty.end(), (char)1);
@@ -165,50 +165,32 @@ int aic_zones_create(int device_id, int streams, int max_tracks, int forget_afte
     });
 }
 
-int aic_zones_destroy(aic_zones* z) {
-    return guarded([&] {
-        if (z && z->z.dev) { z->z.dev->use(); (void)hipStreamSynchronize(z->z.dev->s_trk); }
-        delete z;
-    });
-}
+int aic_zones_destroy(aic_zones* z) { return destroy_handle(z, z ? z->z.dev : nullptr); }
 
 int aic_zones_set(aic_zones* z, int stream, int n_zones, const int32_t* zone_nvert, const int32_t* zone_xy, int n_lines, const int32_t* line_xy) {
-    return guarded([&] {
-        AIC_REQUIRE(z, AIC_ERR_INVALID, "NULL argument");
-        z->z.set(stream, n_zones, zone_nvert, zone_xy, n_lines, line_xy);
-    });
+    return with_handle(z, [&] { z->z.set(stream, n_zones, zone_nvert, zone_xy, n_lines, line_xy); });
 }
 
 int aic_zones_update(aic_zones* z, const int32_t* frames_per_stream, const int32_t* counts, const int32_t* rows6, int mem, int cap_events,
                      int32_t* n_events, int32_t* events, int32_t* occupancy, int32_t* status) {
-    return guarded([&] {
-        AIC_REQUIRE(z, AIC_ERR_INVALID, "NULL argument");
-        z->z.update(frames_per_stream, counts, rows6, mem, cap_events, n_events, events, occupancy, status);
-    });
+    return with_handle(z, [&] { z->z.update(frames_per_stream, counts, rows6, mem, cap_events, n_events, events, occupancy, status); });
 }
 
 int aic_zones_counters(aic_zones* z, int stream, int64_t* zone_in, int64_t* zone_out, int64_t* line_pos, int64_t* line_neg) {
-    return guarded([&] {
-        AIC_REQUIRE(z, AIC_ERR_INVALID, "NULL argument");
-        z->z.counters(stream, zone_in, zone_out, line_pos, line_neg);
-    });
+    return with_handle(z, [&] { z->z.counters(stream, zone_in, zone_out, line_pos, line_neg); });
 }
 
 int aic_zones_reset(aic_zones* z, int stream) {
-    return guarded([&] {
-        AIC_REQUIRE(z, AIC_ERR_INVALID, "NULL argument");
-        z->z.reset(stream);
-    });
+    return with_handle(z, [&] { z->z.reset(stream); });
 }
 
 int aic_zones_option(aic_zones* z, const char* key, int value) {
-    return guarded([&] {
-        AIC_REQUIRE(z && key, AIC_ERR_INVALID, "NULL argument");
+    return with_handle(z, [&] {
+        AIC_REQUIRE(key, AIC_ERR_INVALID, "NULL argument");
         const std::string k(key);
-        if (k == "frames_per_launch") {
-            AIC_REQUIRE(value >= 0 && value <= (1 << 20), AIC_ERR_INVALID, "frames_per_launch: 0 = a call's frames in one launch, or 1..2^20");
-            z->z.frames_per_launch = value;
-        } else AIC_REQUIRE(false, AIC_ERR_INVALID, "unknown zone counter option: " + k);
+        AIC_REQUIRE(k == "frames_per_launch", AIC_ERR_INVALID, "unknown zone counter option: " + k);
+        AIC_REQUIRE(value >= 0 && value <= (1 << 20), AIC_ERR_INVALID, "frames_per_launch: 0 = a call's frames in one launch, or 1..2^20");
+        z->z.frames_per_launch = value;
     });
 }
 

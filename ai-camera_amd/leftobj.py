@@ -8,6 +8,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _bank_io as IO
 from . import _lib as L
 from . import config
 from .scene import SceneWatch
@@ -119,27 +120,9 @@ class LeftObjects:
         r_mem = L.HOST
         if rows is not None:
             if counts is None:
-                if len(rows) != ticks or any(len(r) != S for r in rows):
-                    raise ValueError(f"rows must be [ticks = {ticks}][streams = {S}] arrays")
-                flat = [np.asarray(r, dtype=np.int32).reshape(-1, 6) for tick in rows for r in tick]
-                counts = np.array([len(r) for r in flat], np.int32)
-                rows = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 6), np.int32))
+                rows, counts = IO.flat_rows(rows, ticks, S)
             r_ptr, r_mem, r_keep = SceneWatch._memory(rows, "rows", np.int32)
-            n_rows = r_keep.size // 6 if isinstance(r_keep, np.ndarray) else r_keep.numel() // 6
-            host_counts = counts.cpu().numpy() if hasattr(counts, "is_cuda") else counts
-            host_counts = np.ascontiguousarray(host_counts, dtype=np.int32).reshape(-1)
-            if len(host_counts) != ticks * S:
-                raise ValueError("counts must name every frame of the call")
-            total = int(host_counts.sum())
-            if (host_counts < 0).any() or n_rows < total:
-                raise ValueError(f"{n_rows} rows, counts sum to {total}")
-            if r_mem == L.DEVICE:                                # counts and rows travel together
-                import torch
-                c_keep = counts if getattr(counts, "is_cuda", False) else torch.from_numpy(host_counts).to(rows.device)
-                c_ptr, _, c_keep = SceneWatch._memory(c_keep, "counts", np.int32)
-            else:
-                c_keep = host_counts
-                c_ptr = L.ptr(c_keep)
+            c_ptr, c_keep, _ = IO.counts_on_host(r_keep, counts, r_mem, ticks, S)
         rec = np.zeros((ticks, S, 8), np.int32)
         obj = np.zeros((ticks, S, M, 12), np.int32)
         ev = np.zeros((max(cap_events, 0), 12), np.int32)

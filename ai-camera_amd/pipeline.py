@@ -271,6 +271,14 @@ class TrackingPipeline:
             raise RuntimeError("attach_zones() has not run yet")
         return [self._zones.counters(s) for s in range(self.streams)]
 
+    def _feed_stages(self, nt, rows, slot=0, host_frames=None):
+        """What every run hands the attached analytics stages, in this order."""
+        self._feed_zones(nt, rows)
+        self._feed_best_shots(nt, rows, slot, host_frames)
+        self._feed_scene(nt, rows, slot, host_frames)
+        self._feed_left(nt, rows, slot, host_frames)
+        self._feed_colours(nt, rows, slot, host_frames)
+
     def _feed_zones(self, nt, rows, cap_events=256):
         """nt [count], rows [count, max_persons, 6] of a run call, tick-major (frame i is tick i // streams of stream i % streams)."""
         z = self._zones
@@ -475,11 +483,7 @@ class TrackingPipeline:
         dl = np.zeros((count, md), np.int32) if want_dets else None
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                L.ptr(db), L.ptr(ds), L.ptr(dl))
-        self._feed_zones(nt, rows)
-        self._feed_best_shots(nt, rows, slot)
-        self._feed_scene(nt, rows, slot)
-        self._feed_left(nt, rows, slot)
-        self._feed_colours(nt, rows, slot)
+        self._feed_stages(nt, rows, slot)
         tracks = [[(int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), config.class_name(int(r[5])), float(c))
                    for r, c in zip(rows[f, :nt[f]], tconf[f, :nt[f]])] for f in range(count)]
         dets = None
@@ -499,22 +503,14 @@ class TrackingPipeline:
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run", self._h, int(slot), int(count), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd),
                None, None, None)
-        self._feed_zones(nt[:count], rows[:count])
-        self._feed_best_shots(nt[:count], rows[:count], slot)
-        self._feed_scene(nt[:count], rows[:count], slot)
-        self._feed_left(nt[:count], rows[:count], slot)
-        self._feed_colours(nt[:count], rows[:count], slot)
+        self._feed_stages(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_passes(self, slot, count, passes):
         """`passes` consecutive walks over the same ring range as ONE call (a looped clip streamed continuously)."""
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_passes", self._h, int(slot), int(count), int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
-        self._feed_zones(nt[:count], rows[:count])
-        self._feed_best_shots(nt[:count], rows[:count], slot)
-        self._feed_scene(nt[:count], rows[:count], slot)
-        self._feed_left(nt[:count], rows[:count], slot)
-        self._feed_colours(nt[:count], rows[:count], slot)
+        self._feed_stages(nt[:count], rows[:count], slot)
         return nt[:count], rows[:count], nd[:count]
 
     def stats(self, reset=False):
@@ -531,11 +527,7 @@ class TrackingPipeline:
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host", self._h, L.ptr(f), int(slot), count, L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
-        self._feed_zones(nt[:count], rows[:count])
-        self._feed_best_shots(nt[:count], rows[:count], slot, f)
-        self._feed_scene(nt[:count], rows[:count], slot, f)
-        self._feed_left(nt[:count], rows[:count], slot, f)
-        self._feed_colours(nt[:count], rows[:count], slot, f)
+        self._feed_stages(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_raw_from_host_passes(self, frames_bgr, passes, slot=0):
@@ -545,11 +537,7 @@ class TrackingPipeline:
         count = len(f)
         nt, rows, tconf, nd = self._raw_bufs()
         L.call("aic_pipeline_run_from_host_passes", self._h, L.ptr(f), int(slot), count, int(passes), L.ptr(nt), L.ptr(rows), L.ptr(tconf), L.ptr(nd))
-        self._feed_zones(nt[:count], rows[:count])
-        self._feed_best_shots(nt[:count], rows[:count], slot, f)
-        self._feed_scene(nt[:count], rows[:count], slot, f)
-        self._feed_left(nt[:count], rows[:count], slot, f)
-        self._feed_colours(nt[:count], rows[:count], slot, f)
+        self._feed_stages(nt[:count], rows[:count], slot, f)
         return nt[:count], rows[:count], nd[:count]
 
     def run_from_host(self, frames_bgr, slot=0):

@@ -7,6 +7,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _bank_io as IO
 from . import _lib as L
 from . import config
 
@@ -96,18 +97,7 @@ class SceneWatch:
         """The stream (None: every stream) starts again at age 0: a camera reconnecting or re-aimed."""
         L.call("aic_scene_reset", self._h, -1 if stream is None else int(stream))
 
-    @staticmethod
-    def _memory(a, what, dtype):
-        """(pointer, AIC_HOST / AIC_DEVICE, keep-alive) of a NumPy array or a contiguous torch tensor."""
-        if isinstance(a, np.ndarray):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            return L.ptr(a), L.HOST, a
-        if str(a.dtype) != "torch." + np.dtype(dtype).name or not a.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous {np.dtype(dtype).name} tensor")
-        if a.is_cuda:
-            import torch
-            torch.cuda.current_stream(a.device).synchronize()  # the library reads it on its own stream
-        return C.c_void_p(a.data_ptr()), L.DEVICE if a.is_cuda else L.HOST, a
+    _memory = staticmethod(IO.memory)                            # (leftobj.py and callers reach it by this name)
 
     def update(self, frames, rows=None, counts=None, want_masks=False):
         """frames: uint8 [ticks, streams, H, W, 3] BGR, tick-major, a NumPy array or a torch tensor (host or device, any alignment).
@@ -123,27 +113,10 @@ class SceneWatch:
         r_mem = L.HOST
         if rows is not None:
             if counts is None:
-                if len(rows) != ticks or any(len(r) != S for r in rows):
-                    raise ValueError(f"rows must be [ticks = {ticks}][streams = {S}] arrays")
-                flat = [np.asarray(r, dtype=np.int32).reshape(-1, 6) for tick in rows for r in tick]
-                counts = np.array([len(r) for r in flat], np.int32)
-                rows = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 6), np.int32))
+                rows, counts = IO.flat_rows(rows, ticks, S)
             r_ptr, r_mem, r_keep = self._memory(rows, "rows", np.int32)
-            n_rows = r_keep.size // 6 if isinstance(r_keep, np.ndarray) else r_keep.numel() // 6
-            host_counts = counts.cpu().numpy() if hasattr(counts, "is_cuda") else counts
-            host_counts = np.ascontiguousarray(host_counts, dtype=np.int32).reshape(-1)
-            if len(host_counts) != ticks * S:
-                raise ValueError("counts must name every frame of the call")
+            c_ptr, c_keep, host_counts = IO.counts_on_host(r_keep, counts, r_mem, ticks, S)
             total = int(host_counts.sum())
-            if (host_counts < 0).any() or n_rows < total:
-                raise ValueError(f"{n_rows} rows, counts sum to {total}")
-            if r_mem == L.DEVICE:                                # counts and rows travel together
-                import torch
-                c_keep = counts if getattr(counts, "is_cuda", False) else torch.from_numpy(host_counts).to(rows.device)
-                c_ptr, _, c_keep = self._memory(c_keep, "counts", np.int32)
-            else:
-                c_keep = host_counts
-                c_ptr = L.ptr(c_keep)
             offsets = np.concatenate([[0], np.cumsum(host_counts)]).astype(np.int64)
             rm = np.full(max(total, 1), -1, np.int32)
         rec = np.zeros((ticks, S, 16), np.int32)

@@ -10,6 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _bank_io as IO
 from . import _lib as L
 from . import config
 
@@ -163,9 +164,7 @@ class ZoneCounter:
     def update_tuples(self, frames, cap_events=256):
         """As update(), from the 7-tuples (x1, y1, x2, y2, track_id, class_name, conf) DeepSORT.update and the other trackers return:
         `streams` lists of frames, a frame being a list of tuples."""
-        ids = {n: i for i, n in enumerate(config.CLASSES)}
-        return self.update([[np.array([[t[0], t[1], t[2], t[3], t[4], ids.get(t[5], -1)] for t in fr], np.int64).reshape(-1, 6).astype(np.int32)
-                              for fr in stream] for stream in frames], cap_events=cap_events)
+        return self.update(IO.rows_from_tuples(frames), cap_events=cap_events)
 
     def counters(self, stream):
         """dict(zone_in, zone_out [n_zones], line_pos, line_neg [n_lines]): cumulative int64 counts since set_zones / reset."""
