@@ -1,4 +1,4 @@
-"""What the analytics classes (BestShots, TrackColours, SceneWatch, LeftObjects, ZoneCounter) share in front of a library call: the
+"""What the analytics classes (BestShots, TrackColours, HeatMaps, SceneWatch, LeftObjects, ZoneCounter) share in front of a library call: the
 memory of an argument, nested row lists made flat, the counts that travel with the rows, tracker tuples made rows.
 Each class keeps its own checks; what differs between them is an argument here, not a copy there."""
 import ctypes as C

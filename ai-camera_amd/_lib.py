@@ -80,6 +80,10 @@ class ColoursConfig(C.Structure):
                                          "inset_q8", "min_w", "min_h", "max_cover_q8")]
 
 
+class HeatConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell", "max_tracks", "forget_after", "anchor", "min_move")]
+
+
 class JpegConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
 
@@ -318,6 +322,20 @@ _SIGS = {
     "aic_colours_flush": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "aic_colours_export": (_I, [_P, _I, _P, _P]),
     "aic_colours_classify": (_I, [_P, _I, _P]),
+    "aic_heat_config_default": (_I, [_I, _I, _I, _P]),
+    "aic_heat_create": (_I, [_I, _P, _P]),
+    "aic_heat_destroy": (_I, [_P]),
+    "aic_heat_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_heat_reset": (_I, [_P, _I]),
+    "aic_heat_update": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "aic_heat_flush": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "aic_heat_export": (_I, [_P, _I, _P, _P]),
+    "aic_heat_decay": (_I, [_P, _I, _I, _I]),
+    "aic_heat_export_layers": (_I, [_P, _I, _I, _P]),
+    "aic_heat_import_layers": (_I, [_P, _I, _I, _P]),
+    "aic_heat_set_lut": (_I, [_P, _P]),
+    "aic_heat_lut": (_I, [_P]),
+    "aic_heat_render": (_I, [_P, _P, _I, _I, _P, _I]),
     "aic_jpeg_tables": (_I, [_I, _P, _P]),
     "aic_jpeg_header": (_I, [_I, _I, _I, _I, _I, _P, _I, _P]),
     "aic_jpeg_config_default": (_I, [_I, _I, _P]),

@@ -31,6 +31,11 @@ printed as a line of its own, and the output stage of --redact / --masks / --dra
 `--colours [--colours_file FILE.jsonl]`: what each track wears.  Every JSON line gains `"colours"`, one
 `[upper, lower]` pair of colour names (or null) per track of the line; every ended track is appended to FILE as one JSON object with
 its histograms, and the tracks still alive at the end of the run are flushed into it.
+`--heat_maps DIR [--heat_cell {4,8,16,32}] [--heat_layer NAME] [--heat_paths FILE.jsonl] [--heat_overlay]`: where
+people go.  At the end of the run each camera's twelve layers are written as `DIR/cam<S>_layers.npy` ([12, GH, GW] int32, the order of
+heatmap.LAYERS) and the chosen layer (default dwell) over the camera's last frame as `DIR/cam<S>_<layer>.jpg`; `--heat_paths` appends
+one JSON line per ended track (start, end, path length, cells, ...); `--heat_overlay` blends the layer into every saved frame before
+boxes and labels are drawn.
 `--scene_watch [--scene_cell {4,8,16}]`: a background model per camera on a coarse gray grid.  Every JSON line
 gains `"scene": {active, moving_cells, motion_box, alarms}` and `"moving"`, one value per track of the line (256 = every cell under its
 box moves, -1 = the box is off the frame); every alarm edge (dark, bright, defocus, scene, frozen) is printed as a line of its own.
@@ -56,6 +61,9 @@ from . import config, synthetic, visualization
 from . import frames as pixfmt
 from .detector import YOLODetector
 from .deepsort_tracker import DeepSORT
+
+
+HEAT_LAYERS = ("visits", "dwell", "starts", "ends", "dir0", "dir1", "dir2", "dir3", "dir4", "dir5", "dir6", "dir7")      # heatmap.LAYERS
 
 
 def probe_cv2():
@@ -121,6 +129,14 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                         "(or null) per track")
     p.add_argument("--colours_file", type=str, default=None, metavar="FILE.jsonl",
                    help="with --colours: append every ended track's descriptor (names, histograms) to FILE as one JSON object")
+    p.add_argument("--heat_maps", type=str, default=None, metavar="DIR",
+                   help="accumulate footfall, dwell, flow and start / end maps per camera on the device; at the end of the run write every "
+                        "camera's layers as DIR/cam<S>_layers.npy and one layer over its last frame as DIR/cam<S>_<layer>.jpg")
+    p.add_argument("--heat_cell", type=int, default=None, choices=(4, 8, 16, 32), help="with --heat_maps: the grid's cell size in pixels (default 16)")
+    p.add_argument("--heat_layer", type=str, default=None, metavar="NAME",
+                   help="with --heat_maps: the layer that is drawn (visits, dwell, starts, ends, dir0..dir7; default dwell)")
+    p.add_argument("--heat_paths", type=str, default=None, metavar="FILE.jsonl", help="with --heat_maps: append one JSON line per ended track to FILE")
+    p.add_argument("--heat_overlay", action="store_true", help="with --heat_maps: blend the layer into every saved frame, under boxes and labels")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -181,6 +197,10 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--scene_cell needs --scene_watch")
     if args.colours_file is not None and not args.colours:
         p.error("--colours_file needs --colours")
+    if (args.heat_cell is not None or args.heat_layer is not None or args.heat_paths is not None or args.heat_overlay) and not args.heat_maps:
+        p.error("--heat_cell, --heat_layer, --heat_paths and --heat_overlay need --heat_maps DIR")
+    if args.heat_layer is not None and args.heat_layer not in HEAT_LAYERS:
+        p.error("--heat_layer is one of " + ", ".join(HEAT_LAYERS))
     if (args.left_cell is not None or args.left_after is not None) and not args.left_objects:
         p.error("--left_cell and --left_after need --left_objects")
     if args.left_after is not None and not 1 <= args.left_after <= 65534:
@@ -633,6 +653,69 @@ class _ColourLines:
             self.stage.close()
 
 
+class _HeatFiles:
+    """--heat_maps DIR [--heat_cell N] [--heat_layer NAME] [--heat_paths FILE] [--heat_overlay]: a HeatMaps (heatmap.py) over the run's
+    tracks, attached to the pipeline or fed frame by frame.  Every ended track goes to FILE as one JSON line; close() flushes what still
+    lives, then writes every camera's layers and the chosen layer over its last frame."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import heatmap
+        self.mod, self.pipe, self._res, self.streams, self.device = heatmap, pipe, None, streams, device
+        self.layer, self.overlay_on = args.heat_layer or "dwell", args.heat_overlay
+        self.dir = Path(args.heat_maps)
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.stage = heatmap.HeatMaps(streams, (size[1], size[0]), cell=args.heat_cell or 16, device=device)
+        self.file = open(args.heat_paths, "a") if args.heat_paths else None
+        self.last = np.zeros((streams, size[1], size[0], 3), np.uint8)      # every camera's last frame
+        self.quality = args.jpeg_quality
+        if pipe is not None:
+            pipe.attach_heat_maps(self.stage)
+
+    def _write(self, result):
+        if self.file is not None:
+            for ev in self.mod.paths(result):
+                self.file.write(json.dumps(ev) + "\n")
+
+    def after(self, frame, tracks, camera=0):
+        """After every yielded frame."""
+        if self.pipe is None:
+            self._res = self.stage.update_tuples([[tracks]])
+            self._write(self._res)
+        elif self.pipe.heat_result is not self._res:
+            self._res = self.pipe.heat_result
+            self._write(self._res)
+        self.last[camera] = frame
+
+    def overlay(self, frames, cameras=None):
+        """uint8 [n, H, W, 3] frames with the layer blended in (--heat_overlay), or as they came."""
+        if not self.overlay_on:
+            return frames
+        return self.stage.render(np.ascontiguousarray(frames, dtype=np.uint8), cameras=cameras, layer=self.layer)
+
+    def close(self):
+        from .jpeg import JpegEncoder
+        try:
+            res = self.stage.flush()
+            self._write(res)
+            while int(res.pending.sum()):
+                res = self.stage.drain(cap=self.stage.max_tracks)
+                self._write(res)
+            for c in range(self.streams):
+                lay = self.stage.layers(c)
+                np.save(self.dir / f"cam{c}_layers.npy", np.stack([lay[n] for n in self.mod.LAYERS]))
+            drawn = self.stage.render(self.last, cameras=list(range(self.streams)), layer=self.layer)
+            enc = JpegEncoder(drawn.shape[1:3], max_images=self.streams, quality=self.quality, subsampling="420", max_bytes="worst", device=self.device)
+            try:
+                for c, data in enumerate(enc.encode(drawn)):
+                    (self.dir / f"cam{c}_{self.layer}.jpg").write_bytes(bytes(data))
+            finally:
+                enc.close()
+        finally:
+            if self.file is not None:
+                self.file.close()
+            self.stage.close()
+
+
 class _Output:
     """The saved frames' last stage.  With --redact / --masks / --draw_zones, or for the S frames of a tick of --inputs, ONE
     render.Renderer call: redaction, static masks, the zones' outlines, labels and the info panel.  Classes travel as config.CLASSES ids,
@@ -783,6 +866,17 @@ def main_streams(args, cv2):
                     f.close()
             pipe.close()
             return 1
+    heat = None
+    if args.heat_maps:
+        try:
+            heat = _HeatFiles(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --heat_maps: {e}")
+            for f in (zones, shots, watch, left, worn):
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -808,12 +902,16 @@ def main_streams(args, cv2):
             scene = watch.after(frame, tracks) if watch is not None else None
             lost = left.after(frame, tracks) if left is not None else None
             wears = worn.after(frame, tracks) if worn is not None else None
+            if heat is not None:
+                heat.after(frame, tracks, k)
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
                 batch[k] = frame
                 tick.append((tracks, shown, lost[1] if lost is not None else None))
                 if len(tick) == S:                                                # the tick's S frames in ONE render call
+                    if heat is not None:
+                        batch[:] = heat.overlay(batch)
                     drawn = output.draw(batch, [t[0] for t in tick], [t[1] for t in tick],
                                         [[label, f"Input: {sources[c][0]} (stream {c})"] for c in range(S)], [t[2] for t in tick])
                     if encoder is not None:                                       # ... and in ONE encode call
@@ -854,6 +952,8 @@ def main_streams(args, cv2):
             left.close()
         if worn is not None:
             worn.close()
+        if heat is not None:
+            heat.close()
         if output is not None:
             output.close()
         if encoder is not None:
@@ -1016,6 +1116,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    heat = None
+    if args.heat_maps:
+        try:
+            heat = _HeatFiles(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --heat_maps: {e}")
+            for f in (out_f, writer, zones, shots, watch, left, worn, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -1063,7 +1173,11 @@ def main(argv=None):
             scene = watch.after(frame, tracks) if watch is not None else None
             lost = left.after(frame, tracks) if left is not None else None
             wears = worn.after(frame, tracks) if worn is not None else None
+            if heat is not None:
+                heat.after(frame, tracks)
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
+                if heat is not None and heat.overlay_on:
+                    frame = heat.overlay(np.ascontiguousarray(frame)[None])[0]
                 info = ["AICamera: YOLOv8 + " + ("ByteTrack" if bytetrack else "OC-SORT" if ocsort else "BoT-SORT" if botsort else "DeepSORT"), f"Input: {name}", f"FPS: {display_fps:.2f}"]
                 vis = visualization.draw_frame(frame.copy(), tracks, info, dev) if output is None else output.draw([frame], [tracks], [tracks], [info], [lost[1] if lost is not None else None])[0]
                 if args.show_display and cv2 is not None:
@@ -1103,6 +1217,8 @@ def main(argv=None):
             left.close()
         if worn is not None:
             worn.close()
+        if heat is not None:
+            heat.close()
         if output is not None:
             output.close()
         if pipe is not None:

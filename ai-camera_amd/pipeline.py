@@ -278,6 +278,7 @@ class TrackingPipeline:
         self._feed_scene(nt, rows, slot, host_frames)
         self._feed_left(nt, rows, slot, host_frames)
         self._feed_colours(nt, rows, slot, host_frames)
+        self._feed_heat(nt, rows)
 
     def _feed_zones(self, nt, rows, cap_events=256):
         """nt [count], rows [count, max_persons, 6] of a run call, tick-major (frame i is tick i // streams of stream i % streams)."""
@@ -397,6 +398,29 @@ class TrackingPipeline:
         self.colour_result = w.update(self._host_bgr(slot, count, host_frames),
                                       [[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
                                       cap=self.colour_cap)
+
+    _heat = heat_result = None
+    heat_cap = 16
+
+    def attach_heat_maps(self, stage, cap=16):
+        """A HeatMaps (heatmap.py) of `.streams` streams for this frame size: after every run* call the call's tracks -- all ticks, all
+        streams, ONE stage.update -- go through it and heat_result is that call's HeatResult (row_tags per track row, at most `cap`
+        ended tracks per stream per call; the rest wait, see .pending and stage.drain()); stage.layers() / stage.render() show what
+        has accumulated.  The stage reads rows only: they reach it from the host side, as for attach_colours; with *_passes it sees the
+        last pass only.  The tracks returned are untouched.  None detaches."""
+        w = stage
+        if w is not None and (w.streams != self.streams or (w.frame_h, w.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"heat maps of {w.streams} streams of {w.frame_h}x{w.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._heat, self.heat_cap, self.heat_result = w, int(cap), None
+
+    def _feed_heat(self, nt, rows):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major."""
+        w = self._heat
+        if w is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.heat_result = w.update([[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)], cap=self.heat_cap)
 
     def close(self):
         for b in getattr(self, "_staging", []):

@@ -1053,6 +1053,57 @@ int aic_colours_update(aic_colours* c, const uint8_t* frames_bgr, int frames_mem
 int aic_colours_flush(aic_colours* c, int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
 int aic_colours_export(aic_colours* c, int stream, int32_t* n, int32_t* events);
 int aic_colours_classify(const uint8_t* bgr, int n, uint8_t* bins);
+/* ---- heat maps: footfall, dwell, flow and paths per camera (csrc/heat.hpp) ---------------------------------------
+ * A tracker-agnostic stage over the rows every tracker delivers (x1 y1 x2 y2 id cls, int32), for `streams` (1..256) cameras per call;
+ * only render touches frames.  Every camera holds twelve int32 layers [GH, GW] over cells of cell x cell pixels (GW = ceil(frame_w /
+ * cell), GH alike): 0 VISITS (a track entered the cell), 1 DWELL (a track stood in it, per tick), 2 STARTS, 3 ENDS (tracks first / last
+ * seen there), 4..11 DIR0..DIR7 (steps of at least min_move doubled pixels by octant, clockwise from east, y down).  A counted row's
+ * anchor is the middle of its bottom edge (anchor 0, foot) or of its box (1, centre) in doubled pixels, clamped into the frame.  A table
+ * of max_tracks slots per stream remembers where each track stood last; a track unseen for more than forget_after ticks ENDS and is
+ * handed over as a 16-int path summary.  ENDS is counted when the event leaves the table (so a track still `pending` is not in it yet).
+ * Every layer cell and slot counter stops at 2^30.  tests/heat_oracle.py is the specification and the device equals it bit for bit.
+ * aic_heat_config: frame_h, frame_w in 1..16384; cell 4, 8, 16 or 32; max_tracks 1..512; forget_after 0..2^24; anchor 0 / 1; min_move
+ * 1..2^20; aic_heat_config_default fills cell 16, 128 tracks, forget_after 70, foot, min_move 4.  More than 32768 cells is
+ * AIC_ERR_CAPACITY at create.  Resident memory: 48 bytes per cell and camera plus 32.8 KB of slot table per camera.
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option, reset, set_lut, lut and the range check of
+ * import_layers never touch it.  Device buffers are allocated by the first call that reaches the device; an allocation that does not
+ * fit fails that call with AIC_ERR_CAPACITY.
+ * update: counts[ticks * streams] and rows6 (tick-major; both host or both device, rows_mem), ticks 0..65536 (0 only drains), cap
+ * 0..4096; a frame of more than 512 rows is AIC_ERR_CAPACITY before anything is staged.  Outputs (host): n_final[streams];
+ * events[streams, cap, 16] = reason (0 LIVE, 1 EXPIRED, 2 FLUSHED), stream, id, cls, first_frame, last_seen, sightings, cells, start_fx,
+ * start_fy, end_fx, end_fy, path, max_step, moving, last cell (cy * GW + cx) -- only the n_final[s] first of a stream are written;
+ * row_tags (may be NULL) [sum of counts, 4] = cell, ticks in that cell, step, octant or -1 for a counted row (-1, 0, 0, -1 for every
+ * other row and for a stopped stream); pending[streams]; status[streams] (may be NULL).  A stream that needs more than max_tracks slots
+ * stops alone with AIC_ERR_CAPACITY as a colour stream does, and that tick adds nothing to its layers.
+ * flush, export (events[max_tracks, 16]), reset (the stream's table and layers): as for aic_colours_*.
+ * decay: v >>= shift (1..31) on the layers of layer_mask (bit l = layer l) of one stream or of all (-1).  export_layers /
+ * import_layers: int32 [popcount(layer_mask), GH, GW] of one stream, in layer order; import refuses a value outside 0..2^30 and takes
+ * effect in call order, as a reset does.
+ * render: n_frames (0..65536) BGR24 frames of frame_h x frame_w, packed, in host or device memory (mem; any alignment), changed in
+ * place; frame f shows camera cameras[f] (NULL: f % streams).  The layer's cells become levels relative to the camera's maximum M
+ * (M = 0: the camera's frames are untouched), are interpolated bilinearly between cell centres to L in 0..255, and a pixel with L >=
+ * floor becomes (in * (256 - alpha_q8) + LUT[L] * alpha_q8 + 128) >> 8.  set_lut: 256 x 3 bytes BGR; aic_heat_lut (host only): the default.
+ * option: "scale" (0 linear, 1 log, the default), "alpha_q8" (0..256, default 160), "floor" (0..255, default 8), "chunk_frames" (0 = a
+ * call's frames at once, or at most k per upload / launch / download), "ticks_per_launch", "launch_budget_mb": same results. */
+typedef struct aic_heat aic_heat;
+typedef struct {
+    int32_t streams, frame_h, frame_w, cell, max_tracks, forget_after, anchor, min_move;
+} aic_heat_config;
+int aic_heat_config_default(int streams, int frame_h, int frame_w, aic_heat_config* out);
+int aic_heat_create(int device, const aic_heat_config* config, aic_heat** out);
+int aic_heat_destroy(aic_heat* h);
+int aic_heat_option(aic_heat* h, const char* key, int value);
+int aic_heat_reset(aic_heat* h, int stream);
+int aic_heat_update(aic_heat* h, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap, int32_t* n_final, int32_t* events,
+                    int32_t* row_tags, int32_t* pending, int32_t* status);
+int aic_heat_flush(aic_heat* h, int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
+int aic_heat_export(aic_heat* h, int stream, int32_t* n, int32_t* events);
+int aic_heat_decay(aic_heat* h, int stream, int layer_mask, int shift);
+int aic_heat_export_layers(aic_heat* h, int stream, int layer_mask, int32_t* out);
+int aic_heat_import_layers(aic_heat* h, int stream, int layer_mask, const int32_t* layers);
+int aic_heat_set_lut(aic_heat* h, const uint8_t* bgr);
+int aic_heat_lut(uint8_t* bgr);
+int aic_heat_render(aic_heat* h, uint8_t* frames_bgr, int n_frames, int mem, const int32_t* cameras, int layer);
 /* ---- JPEG out: a bank of equally sized BGR24 images to complete JFIF files in one call (csrc/jpeg.hpp) ---------
  * Baseline sequential DCT, 8 bit, YCbCr full range, 4:2:0 (subsampling 420) or 4:4:4 (444), the Annex K Huffman tables, restart markers
  * always on (restart = MCUs per interval, 1..65535; 0 = one MCU row).  Integer arithmetic only; tests/jpeg_oracle.py is the
