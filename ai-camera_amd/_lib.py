@@ -120,6 +120,7 @@ _SIGS = {
     "aic_model_conv_plan_live": (_I, [_P, _I, _I, _P]),
     "aic_model_row_band": (_I, [_P, _I, _I, _I, _P]),
     "aic_model_sparse_box": (_I, [_P, _I, _P]),
+    "aic_debug_alloc_probe": (_I, [_I, _P, _P, _P, _P]),
     "aic_model_read_det": (_I, [_P, _I, _P, _P, _P]),
     "aic_detect_decode": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "aic_detect_live": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
@@ -427,6 +428,14 @@ def device_count() -> int:
     n = C.c_int(0)
     call("aic_device_count", C.byref(n))
     return n.value
+
+
+def debug_alloc_probe(device=0):
+    """Tests: the first four elements of fresh, unwritten float / int32 / uint8 device buffers and of a page-locked uint8 buffer
+    (aic_debug_alloc_probe, include/aicam.h): what AICAM_POISON_ALLOC filled them with in this process."""
+    out = {"f32": np.zeros(4, np.float32), "i32": np.zeros(4, np.int32), "u8": np.zeros(4, np.uint8), "pinned_u8": np.zeros(4, np.uint8)}
+    call("aic_debug_alloc_probe", int(device), *(ptr(out[k]) for k in ("f32", "i32", "u8", "pinned_u8")))
+    return out
 
 
 def prof_read(device=0):

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -14,6 +15,7 @@
 
 #include "../../include/aicam.h"
 #include "assoc_host.hpp"
+#include "poison_pattern.hpp"
 
 namespace aic {
 
@@ -24,6 +26,27 @@ namespace aic {
             throw ::aic::Error(AIC_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(_e) + \
                                                     " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
     } while (0)
+
+// AICAM_POISON_ALLOC=zero|big|nan (poison_pattern.hpp; tests): every fresh DevBuf / PinBuf allocation is filled before alloc returns,
+// so that a read of memory nobody wrote gives the same wrong bytes in every process.  Unset: nothing is filled.
+inline poison::Mode poison_mode() {
+    static const poison::Mode m = poison::parse(getenv("AICAM_POISON_ALLOC"));
+    return m;
+}
+
+// the device synchronise keeps every stream behind the fill: a buffer's intended initialisation still lands after it
+inline void poison_fill_device(void* p, size_t bytes, poison::Fill f) {
+    if (f.width == 1) {
+        HIP_CHECK(hipMemset(p, (int)f.value, bytes));
+    } else if (f.width == 4) {
+        HIP_CHECK(hipMemsetD32((hipDeviceptr_t)p, (int)f.value, bytes / 4));
+    } else {
+        std::vector<unsigned char> h(bytes);
+        poison::fill_host(h.data(), bytes, f);
+        HIP_CHECK(hipMemcpy(p, h.data(), bytes, hipMemcpyHostToDevice));
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+}
 
 template <class T>
 struct DevBuf {
@@ -43,6 +66,10 @@ struct DevBuf {
         release();
         n = count;
         if (count) HIP_CHECK(hipMalloc((void**)&p, count * sizeof(T)));
+        if (count && poison_mode() != poison::OFF) {
+            AIC_REQUIRE(poison_mode() != poison::BAD, AIC_ERR_INVALID, "AICAM_POISON_ALLOC: zero, big or nan");
+            poison_fill_device(p, count * sizeof(T), poison::pattern<T>(poison_mode()));
+        }
     }
     void ensure(size_t count) { if (count > n) alloc(count); }
     void release() { if (p) { (void)hipFree(p); p = nullptr; } n = 0; }
@@ -61,6 +88,10 @@ struct PinBuf {
         release();
         n = count;
         if (count) HIP_CHECK(hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault));
+        if (count && poison_mode() != poison::OFF) {
+            AIC_REQUIRE(poison_mode() != poison::BAD, AIC_ERR_INVALID, "AICAM_POISON_ALLOC: zero, big or nan");
+            poison::fill_host(p, count * sizeof(T), poison::pattern<T>(poison_mode()));
+        }
     }
     void ensure(size_t count) { if (count > n) alloc(count); }
     void release() { if (p) { (void)hipHostFree(p); p = nullptr; } n = 0; }

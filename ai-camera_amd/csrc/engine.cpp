@@ -1094,6 +1094,38 @@ void copy_out(void* dst, const void* src, size_t bytes, int mem, hipStream_t s) 
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, mem == AIC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
 }
 
+// The detections of a call into the caller's host arrays (each may be NULL), from the staged block decode_nms's host_out names:
+// counts[batch] | boxes[batch, max_det, 4] | scores[batch, max_det] | labels[batch, max_det].  One contract at every batch size
+// (include/aicam.h, aic_detect): the first min(count, max_det) rows of a frame are written, rows past a frame's count are left as
+// the caller passed them -- the NMS kernel stores only the rows it keeps, what lies behind them in the block is nobody's.
+void scatter_dets(const char* h, int batch, int max_det, int32_t* num_dets, float* boxes, float* scores, int32_t* labels) {
+    const int32_t* hn = reinterpret_cast<const int32_t*>(h);
+    const char* hb = h + (size_t)batch * 4;
+    const char* hs = hb + (size_t)batch * max_det * 16;
+    const char* hl = hb + (size_t)batch * max_det * 20;
+    for (int b = 0; b < batch; ++b) {
+        const int n = std::min(std::max(hn[b], 0), max_det);
+        if (num_dets) num_dets[b] = hn[b];
+        if (boxes) std::memcpy(boxes + (size_t)b * max_det * 4, hb + (size_t)b * max_det * 16, (size_t)n * 16);
+        if (scores) std::memcpy(scores + (size_t)b * max_det, hs + (size_t)b * max_det * 4, (size_t)n * 4);
+        if (labels) std::memcpy(labels + (size_t)b * max_det, hl + (size_t)b * max_det * 4, (size_t)n * 4);
+    }
+}
+
+// ... of a decode_nms that stored on the device: staged through the engine's page-locked block, then as above.  Waits for the stream.
+void copy_out_dets(Model& m, int batch, int max_det, const float* d_boxes, int32_t* num_dets, float* boxes, float* scores,
+                   int32_t* labels, hipStream_t s) {
+    const size_t rows = (size_t)batch * max_det;
+    m.h_det.ensure((size_t)batch * 4 + rows * 24 + 16);
+    char* h = m.h_det.p;
+    copy_out(h, m.d_numdets.p, (size_t)batch * 4, AIC_HOST, s);
+    copy_out(h + (size_t)batch * 4, d_boxes, rows * 16, AIC_HOST, s);
+    copy_out(h + (size_t)batch * 4 + rows * 16, m.d_out_scores.p, rows * 4, AIC_HOST, s);
+    copy_out(h + (size_t)batch * 4 + rows * 20, m.d_out_labels.p, rows * 4, AIC_HOST, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    scatter_dets(h, batch, max_det, num_dets, boxes, scores, labels);
+}
+
 void load_input_nchw(Model& m, const float* images, int n, int mem, hipStream_t s) {
     const size_t cnt = (size_t)n * 3 * m.in_h * m.in_w;
     const float* src = images;
@@ -1159,6 +1191,23 @@ int aic_model_load(const char* path, int device_id, int dtype, int max_items, ai
         f.read(blob.data(), (std::streamsize)n);
         AIC_REQUIRE(f.good(), AIC_ERR_FORMAT, std::string("cannot read engine file: ") + path);
         *out = new aic_model(device(device_id), blob.data(), n, dtype, max_items);
+    });
+}
+
+int aic_debug_alloc_probe(int device_id, float* f32_out, int32_t* i32_out, uint8_t* u8_out, uint8_t* pinned_u8_out) {
+    return guarded([&] {
+        AIC_REQUIRE(f32_out && i32_out && u8_out && pinned_u8_out, AIC_ERR_INVALID, "NULL argument");
+        device(device_id).use();
+        DevBuf<float> df(64);                   // fresh, and nothing below writes them: an uninitialised read by construction
+        DevBuf<int> di(64);
+        DevBuf<uint8_t> du(64);
+        PinBuf<uint8_t> hu;
+        hu.alloc(64);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(f32_out, df.p, 16, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(i32_out, di.p, 16, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(u8_out, du.p, 4, hipMemcpyDeviceToHost));
+        std::memcpy(pinned_u8_out, hu.p, 4);
     });
 }
 
@@ -1278,6 +1327,10 @@ int aic_yolo_infer(aic_model* mm, const float* images, int batch, int mem, float
         m.run(batch, s);
         m.side_ok = false;
         m.decode_nms(batch, conf, iou, max_det, nullptr, s);
+        if (mem == AIC_HOST) {                  // rows past a frame's count stay the caller's, as in aic_detect
+            copy_out_dets(m, batch, max_det, m.d_out_boxes.p, num_dets, bboxes, scores, labels, s);
+            return;
+        }
         copy_out(num_dets, m.d_numdets.p, (size_t)batch * 4, mem, s);
         copy_out(bboxes, m.d_out_boxes.p, (size_t)batch * max_det * 16, mem, s);
         copy_out(scores, m.d_out_scores.p, (size_t)batch * max_det * 4, mem, s);
@@ -1586,25 +1639,11 @@ static void detect_frames(aic_model* mm, const uint8_t* frames, int batch, int h
             m.h_det.ensure((size_t)batch * (4 + per) + 16);
             m.decode_nms(batch, conf, iou, max_det, &g, s, m.h_det.p);
             HIP_CHECK(hipStreamSynchronize(s));
-            const int32_t* hn = reinterpret_cast<const int32_t*>(m.h_det.p);
-            const char* hb = m.h_det.p + (size_t)batch * 4;
-            const char* hs = hb + (size_t)batch * max_det * 16;
-            const char* hl = hb + (size_t)batch * max_det * 20;
-            for (int b = 0; b < batch; ++b) {          // rows past a frame's count are left as the caller passed them
-                const int n = std::min(std::max(hn[b], 0), max_det);
-                num_dets[b] = hn[b];
-                std::memcpy(boxes + (size_t)b * max_det * 4, hb + (size_t)b * max_det * 16, (size_t)n * 16);
-                std::memcpy(scores + (size_t)b * max_det, hs + (size_t)b * max_det * 4, (size_t)n * 4);
-                std::memcpy(labels + (size_t)b * max_det, hl + (size_t)b * max_det * 4, (size_t)n * 4);
-            }
+            scatter_dets(m.h_det.p, batch, max_det, num_dets, boxes, scores, labels);
             return;
         }
         m.decode_nms(batch, conf, iou, max_det, &g, s);
-        copy_out(num_dets, m.d_numdets.p, (size_t)batch * 4, AIC_HOST, s);
-        copy_out(boxes, m.d_out_boxes_orig.p, (size_t)batch * max_det * 16, AIC_HOST, s);
-        copy_out(scores, m.d_out_scores.p, (size_t)batch * max_det * 4, AIC_HOST, s);
-        copy_out(labels, m.d_out_labels.p, (size_t)batch * max_det * 4, AIC_HOST, s);
-        HIP_CHECK(hipStreamSynchronize(s));
+        copy_out_dets(m, batch, max_det, m.d_out_boxes_orig.p, num_dets, boxes, scores, labels, s);
     }
 }
 
@@ -1632,11 +1671,7 @@ int aic_detect_decode(aic_model* mm, int batch, int h, int w, float conf, float 
         hipStream_t s = m.dev->s_main;
         const LetterboxGeom g = letterbox_geometry(h, w, m.in_h, m.in_w);
         m.decode_nms(batch, conf, iou, max_det, &g, s);
-        copy_out(num_dets, m.d_numdets.p, (size_t)batch * 4, AIC_HOST, s);
-        copy_out(boxes, m.d_out_boxes_orig.p, (size_t)batch * max_det * 16, AIC_HOST, s);
-        copy_out(scores, m.d_out_scores.p, (size_t)batch * max_det * 4, AIC_HOST, s);
-        copy_out(labels, m.d_out_labels.p, (size_t)batch * max_det * 4, AIC_HOST, s);
-        HIP_CHECK(hipStreamSynchronize(s));
+        copy_out_dets(m, batch, max_det, m.d_out_boxes_orig.p, num_dets, boxes, scores, labels, s);
     });
 }
 

@@ -657,10 +657,13 @@ struct Pipeline {
     // frame f's detector outputs (on the host behind ev_det) -> row o of the caller's arrays
     void emit_dets(const Chunk& c, int f, int o, const RunOut& out) const {
         const size_t md = prm.max_det;
+        // the frame's first n rows: the NMS kernel stores only the rows it keeps, what lies behind them is stale device memory and
+        // stays here -- rows past a frame's count are left as the caller passed them (aic_detect's contract, include/aicam.h)
+        const size_t n = (size_t)std::min(std::max(c.h_numdets.p[f], 0), prm.max_det);
         if (out.n_dets) out.n_dets[o] = c.h_numdets.p[f];
-        if (out.det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f + 1) * md * 4, out.det_boxes + (size_t)o * md * 4);
-        if (out.det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + (f + 1) * md, out.det_scores + (size_t)o * md);
-        if (out.det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + (f + 1) * md, out.det_labels + (size_t)o * md);
+        if (out.det_boxes) std::copy(c.h_detboxes.p + f * md * 4, c.h_detboxes.p + (f * md + n) * 4, out.det_boxes + (size_t)o * md * 4);
+        if (out.det_scores) std::copy(c.h_scores.p + f * md, c.h_scores.p + f * md + n, out.det_scores + (size_t)o * md);
+        if (out.det_labels) std::copy(c.h_labels.p + f * md, c.h_labels.p + f * md + n, out.det_labels + (size_t)o * md);
     }
 
     // aic_pipeline_last_embeddings: the embeddings of the group's last frame (a blocking copy: the call's final group only, see final_group)

@@ -26,6 +26,9 @@ void XCam::ensure() {
     dev->use();
     if (d_tab.p) return;
     d_shards.alloc((size_t)n * (2 + dim));
+    // the pack kernels write a row's embedding only when the row is valid: aic_xcam_shards returns every row, so the rows no pass has
+    // packed yet hold zeros, not what the allocation held
+    HIP_CHECK(hipMemset(d_shards.p, 0, d_shards.bytes()));
     d_tab.alloc(3 * (size_t)n + 2 * (size_t)n_streams);
     d_best.alloc(n);
     h_tab.alloc(3 * (size_t)n + 2 * (size_t)n_streams);

@@ -66,6 +66,11 @@ const char* aic_last_error(void);
 int aic_abi_version(void);
 int aic_device_count(int* count);
 int aic_device_sync(int device);
+/* Tests only: allocates one fresh device buffer of float, of int32 and of uint8 and one page-locked uint8 buffer through the library's
+ * allocators, writes nothing into them and copies their first four elements out (host outputs of 4 elements each).  With
+ * AICAM_POISON_ALLOC=zero|big|nan in the environment of the process (read once; csrc/poison_pattern.hpp) every fresh allocation of
+ * the library is filled before use, and this call shows the fill; unset, it returns whatever the memory held. */
+int aic_debug_alloc_probe(int device, float* f32_out, int32_t* i32_out, uint8_t* u8_out, uint8_t* pinned_u8_out);
 
 /* ------------------------------------------------------------------ engines
  * Replaces TRTEngine (src/trt_utils/trt_engine.py:15-216): deserialise an engine file
@@ -77,7 +82,7 @@ int aic_model_load_mem(const void* blob, size_t nbytes, int device, int dtype, i
                        aic_model** out);
 /* debugging / tests: the first `bytes` bytes of activation buffer `buf` (engine-file buffer index; NHWC, the engine's activation dtype,
  * items of the last run first) -- what a TensorRT user gets by marking a layer as an output (src/trt_utils/trt_engine.py:62-120 lists
- * only the marked I/O tensors). */
+ * only the marked I/O tensors).  A buffer, or the items of one, that no op of the last run wrote holds stale data. */
 int aic_model_read_buffer(aic_model* m, int buf, void* out, size_t bytes);
 /* Read-only: what a launch of n items runs at op `op` of the engine's op list, decided by the code the launch itself goes through.
  * out[24]: [0] -1 = no conv launch of its own (not a conv, or absorbed at load time), -2 = runs inside the launch that starts at op
@@ -172,7 +177,10 @@ int aic_crop_resize(int device, const uint8_t* frame_bgr, int h, int w, const fl
 
 /* YOLODetector.detect (src/detector/yolo_detector.py:68-149) for a batch of same-size frames:
  * letterbox -> engine -> decode+NMS -> score filter -> scale_bboxes
- * (image_processing.py:141-183). boxes are xyxy in original-frame pixels, clipped. */
+ * (image_processing.py:141-183). boxes are xyxy in original-frame pixels, clipped.
+ * Outputs are host arrays num_dets[B], boxes_xyxy[B,max_det,4], scores[B,max_det], labels[B,max_det].  At every batch size the call
+ * writes num_dets[b] and the first min(num_dets[b], max_det) rows of frame b; rows past a frame's count are left as the caller
+ * passed them.  aic_detect_decode, aic_detect_live and aic_yolo_infer with host outputs follow the same contract. */
 int aic_detect(aic_model* yolo, const uint8_t* frames_bgr, int batch, int h, int w, int mem,
                float conf_thresh, float iou_thresh, int max_det, int32_t* num_dets, float* boxes_xyxy,
                float* scores, int32_t* labels);
@@ -673,7 +681,8 @@ int aic_pipeline_inject(aic_pipeline* p, int slot, int count, const int32_t* cou
 /* Process ring slots [slot, slot+count) in order. Per frame outputs (any may be NULL):
  * n_tracks[count] (the true number of confirmed tracks of the frame; when it exceeds max_persons only the first
  * max_persons rows are stored), tracks[count,max_persons,6] + track_conf as aic_tracker_outputs;
- * n_dets[count], det_boxes[count,max_det,4], det_scores, det_labels from the detector. */
+ * n_dets[count], det_boxes[count,max_det,4], det_scores, det_labels from the detector: the first min(n_dets, max_det) rows of a
+ * frame, rows past a frame's count are left as the caller passed them (as aic_detect). */
 int aic_pipeline_run(aic_pipeline* p, int slot, int count, int32_t* n_tracks, int32_t* tracks6,
                      float* track_conf, int32_t* n_dets, float* det_boxes, float* det_scores,
                      int32_t* det_labels);
@@ -754,7 +763,8 @@ int aic_gid_forget_rank(aic_gid* g, int rank);
  * rejected with AIC_ERR_INVALID.  n_valid[streams] (host; may be NULL) is the caller's statement of those counts: a value outside
  * 0..t_max, or one that differs from the valid column, is AIC_ERR_INVALID and nothing is linked (host memory: before the device is
  * touched; device memory: after the pass's read-back, before the policy).
- * tables: the last pass's arrays over all streams * t_max rows, as aic_gallery_annotate's (any may be NULL).  shards: its shard array.
+ * tables: the last pass's arrays over all streams * t_max rows, as aic_gallery_annotate's (any may be NULL).  shards: its shard array;
+ * a row past a stream's valid prefix holds (0, 0) and the embedding an earlier pass of this object packed there, zeros before any did.
  * global_ids: -1 = never seen.  size: as aic_gid_size.  forget_stream: aic_gid_forget_rank for a camera that was reset.
  * option "tile": 32 / 64 = rows per tile of the nearest kernel, 0 (default) = by size; same results either way. */
 typedef struct aic_xcam aic_xcam;
