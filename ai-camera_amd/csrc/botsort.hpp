@@ -64,7 +64,8 @@ __host__ __device__ static inline BsTable bs_table(char* base, int cap, float* f
 // for the high band only, by detection row; smooth = the streams' smoothed features, smooth_stride floats apart; warps = [rows, 6] camera
 // motion (r00 r01 t0 r10 r11 t1), rows as c.dets' frames, or NULL
 void launch_botsort_epoch(const BsParams& prm, const EpochCall& c, float* smooth, size_t smooth_stride, const float* warps, hipStream_t s);
-// out[r] = in[r] / |in[r]| in the order of kf8wh_math.hpp (one wavefront per row)
+// out[r] = in[r] / |in[r]| in the order of kf8wh_math.hpp (one wavefront per row); out[r][0] = NaN marks a row that is not finite in
+// every element, which the epoch kernel takes as a row without a feature
 void launch_botsort_normalize(const float* in, float* out, int rows, int dim, hipStream_t s);
 
 }  // namespace aic

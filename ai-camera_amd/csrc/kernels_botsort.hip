@@ -52,7 +52,8 @@ struct BsVariant {
     static __device__ __forceinline__ float low(const BsParams& P) { return P.low; }
     static __device__ __forceinline__ void detection(const Lds& L, const Args& a, Ctx& x, int i, int row, float bx, float by, float w, float h) {
         L.meas[i * 4 + 0] = bx + w / 2.0f, L.meas[i * 4 + 1] = by + h / 2.0f, L.meas[i * 4 + 2] = w, L.meas[i * 4 + 3] = h;
-        L.dhas[i] = x.reid && (a.c.dets.valid == nullptr || a.c.dets.valid[row] != 0);
+        // a row that did not normalise to finite values is no feature: botsort_normalize_kernel leaves a NaN in its element 0
+        L.dhas[i] = x.reid && (a.c.dets.valid == nullptr || a.c.dets.valid[row] != 0) && !isnan(a.c.dets.feat_n[(size_t)row * a.prm.dim]);
     }
     // track box: [cx - w / 2, cy - h / 2, w, h]
     static __device__ __forceinline__ void mean_box(const float* m, float b[4]) {
@@ -82,6 +83,9 @@ struct BsVariant {
     }
     // The appearance term, for the pairs that pass the proximity veto (taken on the IoU distance before score fusion) and have a feature on
     // both sides: a wavefront takes 64 pairs, finds the ones that need a dot product and walks them, 16-byte loads straight from HBM / L2.
+    // Non-finite features (tests/botsort_oracle.py, change 7): a detection whose normalised row is not finite in every element has no
+    // feature (detection() above), so it is never compared, never enters a smoothed vector and does not set has_feat; it still matches
+    // by IoU.  No NaN therefore reaches a dot product from a detection's side, where fmaxf would turn it into a distance of 0.
     static __device__ __forceinline__ void cost_pass(const Lds& L, const Args& a, const Table& tbl, Ctx& x, float* ext, int S, const int* rows, int nr,
                                                      const int* cols, int nc, int d0, bool app) {
         if (!(app && x.reid)) return;
@@ -182,17 +186,21 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void botsort_epoch_kernel(BsArgs a) {
     byte_epoch<BsVariant>(a, smem, s_lds, x);
 }
 
-// out[r] = in[r] / |in[r]|: one wavefront per row, four rows per block
+// out[r] = in[r] / |in[r]|: one wavefront per row, four rows per block.  A row with an element that is not finite after the division (a
+// zero row: 0 / 0; an overflowed element: inf / inf beside zeros) is marked by a NaN in its element 0, the flag BsVariant::detection reads
 __global__ __launch_bounds__(256) void botsort_normalize_kernel(const float* in, float* out, int rows, int dim) {
     const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     const float* x = in + (size_t)r * dim;
     const float nrm = sqrtf(wave_dot(x, x, dim, lane));
+    bool finite = true;
     for (int e = lane * 4; e < dim; e += 256) {
         float4 v = *reinterpret_cast<const float4*>(x + e);
         v.x = v.x / nrm, v.y = v.y / nrm, v.z = v.z / nrm, v.w = v.w / nrm;
+        finite = finite && isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
         *reinterpret_cast<float4*>(out + (size_t)r * dim + e) = v;
     }
+    if (__any(!finite) && lane == 0) out[(size_t)r * dim] = __builtin_nanf("");      // lane 0 wrote element 0 above: program order
 }
 
 void launch_botsort_epoch(const BsParams& prm, const EpochCall& c, float* smooth, size_t smooth_stride, const float* warps, hipStream_t s) {

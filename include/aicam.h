@@ -531,8 +531,10 @@ int aic_botsort_destroy(aic_botsort* t);
 int aic_botsort_option(aic_botsort* t, const char* key, int value);
 /* k consecutive frames, each one BoTSORT.update(): arrays and outputs as aic_bytetrack_update_batch, plus feat[sum, feature_dim] raw
  * embeddings (normalised on the device; NULL = no features, the call then runs as with_reid = 0), valid[sum] (0 = the row has no
- * feature; NULL = all have one) and warps[k, 6] (per frame r00 r01 t0 r10 r11 t1; NULL = no camera motion).  The output rows are ALL
- * tracks of the tracked list, as upstream.  Errors as aic_bytetrack_update_batch. */
+ * feature; NULL = all have one) and warps[k, 6] (per frame r00 r01 t0 r10 r11 t1; NULL = no camera motion).  A feat row that does not
+ * normalise to finite values in every element (a zero row, an inf or a NaN in it) is a row without a feature, as if valid were 0: it is
+ * never compared, never enters a track's smoothed feature and does not set has_feat, and its detection still matches by IoU.  The
+ * output rows are ALL tracks of the tracked list, as upstream.  Errors as aic_bytetrack_update_batch. */
 int aic_botsort_update_batch(aic_botsort* t, int k, const int32_t* counts, const float* boxes_xyxy, const float* conf,
                              const int32_t* cls, const float* feat, const int32_t* valid, const float* warps, int cap_rows,
                              int32_t* n_out, int32_t* out6, float* out_conf);

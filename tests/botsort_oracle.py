@@ -20,8 +20,11 @@ Deliberate changes from upstream (also in DESIGN.md, section 18):
   6. A 512-term dot product is ``wave_sum`` below: 64 partial sums (lane l takes elements 256 c + 4 l + q, in the order c, q)
      folded by a butterfly (distances 32, 16, 8, 4, 2, 1).  ``|f|`` is the square root of the same sum over ``f * f``.
   7. A detection's feature is normalised once (upstream normalises it again inside ``update_features``: a no-op up to rounding).
-     ``d_emb`` is set to 1 unless ``d_emb <= appearance_thresh`` (upstream: where ``d_emb > appearance_thresh``; the two differ for a
-     NaN only, which then cannot win a ``min``).  The 50-deep feature deque is never read by upstream's algorithm and is left out.
+     A detection whose normalised feature is not finite in every element (a zero embedding gives 0 / 0, one overflowed element
+     inf / inf) counts as having no feature (``has_feature``): it is never compared, never enters a smoothed vector and does not set
+     ``has_feat``; it still matches by IoU.  Upstream would carry the NaN into the track's smoothed feature for good.  ``d_emb`` is
+     set to 1 unless ``d_emb <= appearance_thresh`` (upstream: where ``d_emb > appearance_thresh``; the same for every finite value,
+     and no detection brings a NaN).  The 50-deep feature deque is never read by upstream's algorithm and is left out.
   8. Only high-band detections carry a feature; a low-band detection's feature is never read (as upstream, which embeds the high band
      only).
   9. Output: EVERY track of the tracked list, as upstream's ``output_stracks = [track for track in self.tracked_stracks]`` (its
@@ -67,6 +70,11 @@ def normalise(f):
     f = np.asarray(f, dtype=F32)
     with np.errstate(all="ignore"):
         return (f / np.sqrt(wave_sum(f * f))[..., None]).astype(F32)
+
+
+def has_feature(unit):
+    """Change 7: a normalised row counts as a feature only if every element is finite."""
+    return bool(np.isfinite(unit).all())
 
 
 # ----------------------------------------------------------------------------------------------------------------- the xywh filter
@@ -152,8 +160,9 @@ class STrack:
         self.alpha = F32(alpha)
         self.smooth_feat = None
         self.curr_feat = None
-        if feat is not None:
-            self.update_features(normalise(feat))
+        unit = None if feat is None else normalise(feat)
+        if unit is not None and has_feature(unit):
+            self.update_features(unit)
 
     def update_features(self, f):
         """f is unit length (change 7)."""
