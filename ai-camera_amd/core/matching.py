@@ -1,5 +1,5 @@
 """Cost functions with the signatures of src/tracker/core/matching.py:13-217, computed by the HIP
-kernels iou_cost_kernel / cosine_min_kernel (csrc/kernels_trk.hip) through the C ABI."""
+kernels iou_cost_kernel / cosine_min_mfma_kernel (csrc/kernels_trk.hip) through the C ABI."""
 import numpy as np
 
 from .. import _lib as L

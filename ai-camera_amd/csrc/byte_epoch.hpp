@@ -29,6 +29,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "trk_dev.hpp"
+#include "trk_math.hpp"
 #include "trk_wave.hpp"
 #include "bytetrack.hpp"
 
@@ -81,18 +82,7 @@ __device__ __forceinline__ typename V::Lds byte_carve(char* base, int total_byte
     return L;
 }
 
-// 1 - IoU of box b against candidate c (tlwh), matching.py:13-106 (union floored at 1e-7), fp32
-__device__ __forceinline__ float iou_dist(const float b[4], const float* c) {
-    const float brx = b[0] + b[2], bry = b[1] + b[3];
-    const float crx = c[0] + c[2], cry = c[1] + c[3];
-    const float iw = fmaxf(0.f, fminf(brx, crx) - fmaxf(b[0], c[0]));
-    const float ih = fmaxf(0.f, fminf(bry, cry) - fmaxf(b[1], c[1]));
-    const float inter = iw * ih;
-    const float uni = b[2] * b[3] + c[2] * c[3] - inter;
-    return 1.0f - inter / fmaxf(uni, 1e-7f);
-}
-
-// the IoU distance of slot's box to detection j, fused with the detection's score: 1 - (1 - d) * s
+// the IoU distance (iou_dist of trk_math.hpp) of slot's box to detection j, fused with the detection's score: 1 - (1 - d) * s
 template <class V>
 __device__ __forceinline__ float byte_cost(const typename V::Lds& L, int slot, int j, bool fuse) {
     float b[4];

@@ -114,25 +114,19 @@ void launch_det_filter(const DetFilterArgs& a, hipStream_t s);
 void launch_select_sort_nms(const DetArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ tracker (kernels_trk.hip)
-void launch_kf_initiate(const float* z, int n, float* mean, float* cov, const int* slots, hipStream_t s);
-void launch_kf_initiate_idx(const float* z, const int* zidx, int n, float* mean, float* cov, const int* slots, hipStream_t s);
+void launch_kf_initiate(const float* z, int n, float* mean, float* cov, hipStream_t s);
 void launch_kf_predict(float* mean, float* cov, const int* slots, int n, hipStream_t s, float dt = 1.f);
 void launch_kf_project(const float* mean, const float* cov, int n, float* pmean, float* pcov, hipStream_t s);
-void launch_kf_update(float* mean, float* cov, const int* slots, const float* z, const int* zidx, int n,
-                      float* out_tlwh, hipStream_t s);
+void launch_kf_update(float* mean, float* cov, const float* z, int n, hipStream_t s);
 void launch_kf_gating(const float* mean, const float* cov, const int* slots, int n, const float* zs, int m,
                       int shared_z, int only_position, float* d2, hipStream_t s);
 void launch_iou_cost(const float* trk_tlwh, const float* mean, const int* slots, int t, const float* det_tlwh,
                      int n, float* cost, hipStream_t s);
 void launch_fill(float* p, float v, size_t n, hipStream_t s);
 void launch_normalize_rows(const float* src, float* dst, int n, int dim, hipStream_t s, const int* n_dev = nullptr);
-// galleries: base [slots][gmax][dim]; per row t: slot index + valid length; det_n normalised rows.
-void launch_cosine_min(const float* gal, const int* slots, const int* glen, int t, int gmax, int dim,
-                       const float* det_n, const unsigned char* has_feat, int n, float* cost, hipStream_t s);
-void launch_gallery_append(float* gal, int gmax, int dim, const int* slot, const int* pos, const int* det,
-                           const float* feat, int count, hipStream_t s);
 
 // fused per-frame tracker kernels
+// galleries: base [slots][gmax][dim], rows normalised; per row t: slot index + valid length; det_n normalised rows.
 void launch_cosine_min_mfma(const float* gal_n, const int* slots, const int* glen, int t, int gmax, int dim, const float* det_n,
                             const unsigned char* has_feat, int n, float* cost, hipStream_t s);
 void launch_trk_assoc_all(float* mean, float* cov, const int* slots, const int* glen, int t, int do_predict, const float* det_tlwh,

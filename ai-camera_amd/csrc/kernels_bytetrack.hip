@@ -37,11 +37,7 @@ struct BtVariant {
         L.meas[i * 4 + 0] = x + w / 2.0f, L.meas[i * 4 + 1] = y + h / 2.0f, L.meas[i * 4 + 2] = h > 0.f ? w / h : 0.f, L.meas[i * 4 + 3] = h;
     }
     // track box (mean_to_tlwh of deepsort_oracle.py / track.py:133-151)
-    static __device__ __forceinline__ void mean_box(const float* m, float b[4]) {
-        float bw = 0.f, bh = m[3];
-        if (bh > 0.f) bw = m[2] * bh; else bh = fmaxf(0.f, bh);
-        b[0] = m[0] - bw / 2.0f, b[1] = m[1] - bh / 2.0f, b[2] = bw, b[3] = bh;
-    }
+    static __device__ __forceinline__ void mean_box(const float* m, float b[4]) { aic::mean_box(m, b); }
     static __device__ __forceinline__ void zero_velocity(float* m) { m[7] = 0.f; }
     static __device__ __forceinline__ void predict(const Lds& L, const Args&, const Table& tbl, int, int np, int) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

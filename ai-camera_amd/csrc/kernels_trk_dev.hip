@@ -20,63 +20,19 @@
 
 namespace aic {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr float kInfty = 1e5f;                               // linear_assignment.py:9
 constexpr float kChi2_4 = (float)9.487729036781154;          // kalman_filter.py:16, compared in fp32
 constexpr float kBig = 3.0e38f;
 
-// ------------------------------------------------------------------------------------------------ prep kernel
-// One wave = one 16-row x 32-detection tile of cosine distances, K walked exactly like cosine_min_mfma_kernel /
-// trk_assoc_all_kernel (lane (r, q): 16 bytes of its row per 16-deep slice, MFMA e consumes element e of both operands).
-__device__ __forceinline__ void cos_tile(const float* __restrict__ grow, const float* __restrict__ pa, const float* __restrict__ pb,
-                                         int dim, int q, floatx4& acc0, floatx4& acc1) {
-    acc0 = floatx4{0.f, 0.f, 0.f, 0.f};
-    acc1 = acc0;
-    int k0 = 0;
-    for (; k0 + 64 <= dim; k0 += 64) {
-        floatx4 a[4], b0[4], b1[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 16 * u + 4 * q;
-            a[u] = *reinterpret_cast<const floatx4*>(grow + k);
-            b0[u] = *reinterpret_cast<const floatx4*>(pa + k);
-            b1[u] = *reinterpret_cast<const floatx4*>(pb + k);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][e], b0[u][e], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][e], b1[u][e], acc1, 0, 0, 0);
-            }
-    }
-    for (; k0 < dim; k0 += 16) {                 // tail: any dimension, element-guarded
-        const int k = k0 + 4 * q;
-        floatx4 a = {0.f, 0.f, 0.f, 0.f}, b0 = a, b1 = a;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (k + e < dim) { a[e] = grow[k + e]; b0[e] = pa[k + e]; b1[e] = pb[k + e]; }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b0[e], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b1[e], acc1, 0, 0, 0);
-        }
-    }
-}
-
-__device__ __forceinline__ float cos_dist(float dot) {       // matching.py:136-141
-    const float x = 1.0f - dot;
-    return x > 0.f ? x : 0.f;
-}
-
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ prep kernel
 // grid: any (wave-task loop); block 256 = 4 waves, each with its own 16 x 36 LDS tile (row pitch 36 floats: the four row groups
 // a lane quartet writes land in disjoint bank ranges).
+// GRAM task = one 16-row x 32-detection tile of cosine distances between the epoch's detections: cos_tile (trk_math.hpp), K walked
+// exactly as in cosine_min_mfma_kernel / trk_assoc_all_kernel.  Rows are 16-byte aligned on this path (dim % 4 == 0).
 // SM task = (track, 32 detections): K is the OUTER loop and up to SMG = 7 gallery row groups (112 rows) are accumulated side by
 // side, so the detection features cross L2 -> registers once per task instead of once per row group (36 loads per 224 MFMAs
 // instead of 84); the accumulation order of every single dot product is unchanged (k ascending), so the values are
@@ -118,7 +74,7 @@ __global__ __launch_bounds__(256) void trk_epoch_prep_kernel(const DevTrkHdr* __
             const int a0 = rowi * 16;
             if (a0 >= d_base + 32) continue;                      // rows all later than the columns: never read (an appended row only meets LATER frames)
             floatx4 acc0, acc1;
-            cos_tile(frow(min(a0 + r, dn - 1)), pa, pb, dim, q, acc0, acc1);
+            cos_tile(frow(min(a0 + r, dn - 1)), pa, pb, 0, dim, true, q, acc0, acc1);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float* o = gram + (size_t)(a0 + 4 * q + e) * dn_pad + d_base;
@@ -432,19 +388,9 @@ __device__ void match_block(const Lds& L, const EpochArgs& a, const FrameCosts& 
 
 __device__ __forceinline__ float iou_pair(const Lds& L, const float* mean_hbm, int t, int j) {
     const int slot = L.slot[t];
-    const float* m = slot < KF_SLOTS ? L.kf + slot * 72 + 64 : mean_hbm + (size_t)slot * 8;
-    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
-    float bw = 0.f, bh = m3;
-    if (bh > 0.f) bw = m2 * bh; else bh = fmaxf(0.f, bh);
-    const float bx = m0 - bw / 2.0f, by = m1 - bh / 2.0f;
-    const float brx = bx + bw, bry = by + bh;
-    const float* c = L.tlwh + j * 4;
-    const float crx = c[0] + c[2], cry = c[1] + c[3];
-    const float iw = fmaxf(0.f, fminf(brx, crx) - fmaxf(bx, c[0]));
-    const float ih = fmaxf(0.f, fminf(bry, cry) - fmaxf(by, c[1]));
-    const float inter = iw * ih;
-    const float uni = bw * bh + c[2] * c[3] - inter;
-    return 1.0f - inter / fmaxf(uni, 1e-7f);
+    float b[4];
+    mean_box(slot < KF_SLOTS ? L.kf + slot * 72 + 64 : mean_hbm + (size_t)slot * 8, b);
+    return iou_dist(b, L.tlwh + j * 4);
 }
 
 typedef __attribute__((address_space(3))) const float lds_cfloat;
@@ -762,11 +708,10 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) g[4 * i + jj] = Lc[i][jj];
-                const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
-                float bw = 0.f, bh = m3;
-                if (bh > 0.f) bw = m2 * bh; else bh = fmaxf(0.f, bh);
-                g[16] = m0, g[17] = m1, g[18] = m2, g[19] = m3;
-                g[20] = bw, g[21] = bh, g[22] = ok ? 1.f : 0.f;
+                float b[4];
+                mean_box(m, b);
+                g[16] = m[0], g[17] = m[1], g[18] = m[2], g[19] = m[3];
+                g[20] = b[2], g[21] = b[3], g[22] = ok ? 1.f : 0.f;
             }
         }
         if (T > 0 && n > 0) {
@@ -802,23 +747,10 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj) Lc[i][jj] = g[4 * i + jj];
-                    const float m0 = g[16], m1 = g[17], m2 = g[18], m3 = g[19], bw = g[20], bh = g[21];
-                    const bool ok = g[22] != 0.f;
-                    const float bx = m0 - bw / 2.0f, by = m1 - bh / 2.0f;
-                    const float brx = bx + bw, bry = by + bh;
-                    const float* z = L.xyah + j * 4;
-                    float d[4], y[4];
-                    d[0] = z[0] - m0, d[1] = z[1] - m1, d[2] = z[2] - m2, d[3] = z[3] - m3;
-                    fwd_solve<4>(Lc, d, y);
-                    float acc = y[0] * y[0];
-                    acc = acc + y[1] * y[1];
-                    acc = acc + y[2] * y[2];
-                    acc = acc + y[3] * y[3];
-                    const float mh = ok ? acc : __builtin_inff();
+                    const float mh = maha4(Lc, g[22] != 0.f, g + 16, L.xyah + j * 4);
                     const float gx = mh > kChi2_4 ? kInfty : c_app[e];     // (this thread wrote c_app[e] above) linear_assignment.py:187-210
                     c_app[e] = gx;
-                    if (gx <= a.prm.max_cos) L.feas[t] = 1;
-                    (void)bx, (void)by, (void)brx, (void)bry;              // the IoU of a pair is worked out where stage 2 asks for it (iou_pair)
+                    if (gx <= a.prm.max_cos) L.feas[t] = 1;               // (the IoU of a pair is worked out where stage 2 asks for it: iou_pair)
                 }
             }
             if (!gate_lds)
@@ -829,29 +761,13 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
                 float S[4][4], Lc[4][4];
                 innovation_cov(P, m[3], S);
                 const bool ok = cholesky<4>(S, Lc);
-                const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
-                float bw = 0.f, bh = m3;
-                if (bh > 0.f) bw = m2 * bh; else bh = fmaxf(0.f, bh);
-                const float bx = m0 - bw / 2.0f, by = m1 - bh / 2.0f;
-                const float brx = bx + bw, bry = by + bh;
+                const float mu[4] = {m[0], m[1], m[2], m[3]};
+                float b[4];
+                mean_box(mu, b);
                 for (int j = lane; j < n; j += 64) {
-                    const float* z = L.xyah + j * 4;
-                    float d[4], y[4];
-                    d[0] = z[0] - m0, d[1] = z[1] - m1, d[2] = z[2] - m2, d[3] = z[3] - m3;
-                    fwd_solve<4>(Lc, d, y);
-                    float acc = y[0] * y[0];
-                    acc = acc + y[1] * y[1];
-                    acc = acc + y[2] * y[2];
-                    acc = acc + y[3] * y[3];
                     const size_t o = (size_t)t * n + j;
-                    c_maha[o] = ok ? acc : __builtin_inff();
-                    const float* c = L.tlwh + j * 4;
-                    const float crx = c[0] + c[2], cry = c[1] + c[3];
-                    const float iw = fmaxf(0.f, fminf(brx, crx) - fmaxf(bx, c[0]));
-                    const float ih = fmaxf(0.f, fminf(bry, cry) - fmaxf(by, c[1]));
-                    const float inter = iw * ih;
-                    const float uni = bw * bh + c[2] * c[3] - inter;
-                    c_iou[o] = 1.0f - inter / fmaxf(uni, 1e-7f);
+                    c_maha[o] = maha4(Lc, ok, mu, L.xyah + j * 4);
+                    c_iou[o] = iou_dist(b, L.tlwh + j * 4);
                 }
             }
         }
@@ -941,7 +857,8 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
         // lanes each repeat the innovation covariance, its Cholesky factor and two triangular solves (~600 instructions, four rounds at 30
         // tracks: 19.8 k of a frame's 68 k shader cycles).  Here the gain row K[i], S K[i] and the new mean element are worked out once per
         // (track, row) -- all tracks' rows at once, one per thread -- and the 64 covariance elements of a track then take four
-        // multiply-adds each.  Same functions, same operations and order per value as kf_update_wave.
+        // multiply-adds each.  Both forms are written on the same pieces of trk_math.hpp (kf_gain_row, kf_s_gain, kf_mean_elem, kf_cov_elem):
+        // the same operations in the same order per value, by construction.
         if (72 * T <= L.arena_floats) {
             float* ks = L.arena;                                   // [T][8][9]: K[i][0..3], (S K[i])[0..3], new mean[i]  (the cost matrices are dead)
             for (int idx = tid; idx < 8 * T; idx += BT) {
@@ -952,29 +869,15 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
                 const float* P = kP(slot);
                 const float* m = kM(slot);
                 const float* zz = L.xyah + det * 4;
-                float S[4][4], Lc[4][4];
+                float S[4][4], Lc[4][4], Ki[4], u[4];
                 innovation_cov(P, m[3], S);
                 cholesky<4>(S, Lc);
-                float bi[4], y[4], Ki[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) bi[q] = P[i * 8 + q];
-                fwd_solve<4>(Lc, bi, y); bwd_solve(Lc, y, Ki);
+                kf_gain_row(Lc, P, i, Ki);
+                kf_s_gain(S, Ki, u);
                 float* o = ks + idx * 9;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float u = 0.f;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) u = u + S[q][c] * Ki[c];
-                    o[q] = Ki[q], o[4 + q] = u;
-                }
-                float mi = m[i];
-                {
-                    float dot = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dot = dot + Ki[q] * (zz[q] - m[q]);
-                    mi = mi + dot;
-                }
-                o[8] = mi;
+                for (int q = 0; q < 4; ++q) o[q] = Ki[q], o[4 + q] = u[q];
+                o[8] = kf_mean_elem(m, zz, Ki, i);
             }
             __threadfence_block();
             __syncthreads();
@@ -984,36 +887,18 @@ __global__ __launch_bounds__(TRK_DEV_TMAX) void trk_epoch_kernel(EpochArgs a_in)
                 const int slot = L.slot[t];
                 float* P = kP(slot);
                 const float* ki = ks + (t * 8 + i) * 9;
-                const float* uj = ks + (t * 8 + j) * 9 + 4;
-                float acc = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc = acc + ki[q] * uj[q];
-                P[i * 8 + j] = P[i * 8 + j] - acc;
+                P[i * 8 + j] = kf_cov_elem(P[i * 8 + j], ki, ks + (t * 8 + j) * 9 + 4);
                 if (j == 0) kM(slot)[i] = ki[8];
             }
             __threadfence_block();
             __syncthreads();
-            if (tid < T && L.mdet[tid] >= 0) {
-                const float* m = kM(L.slot[tid]);
-                const float cx = m[0], cy = m[1], ar = m[2], hh = m[3];
-                float w = 0.f, h2 = hh;
-                if (hh > 0.f) w = ar * hh; else h2 = fmaxf(0.f, hh);
-                float* o = L.tbox + tid * 4;
-                o[0] = cx - w / 2.0f; o[1] = cy - h2 / 2.0f; o[2] = w; o[3] = h2;
-            }
+            if (tid < T && L.mdet[tid] >= 0) mean_box(kM(L.slot[tid]), L.tbox + tid * 4);
         } else
         for (int t = wv; t < T; t += NW) {
             const int det = L.mdet[t];
             if (det < 0) continue;
             const int slot = L.slot[t];
-            const float mi = kf_update_wave(kP(slot), kM(slot), L.xyah + det * 4, lane);
-            const float cx = __shfl(mi, 0), cy = __shfl(mi, 8), ar = __shfl(mi, 16), hh = __shfl(mi, 24);
-            if (lane == 0) {
-                float w = 0.f, h2 = hh;
-                if (hh > 0.f) w = ar * hh; else h2 = fmaxf(0.f, hh);
-                float* o = L.tbox + t * 4;
-                o[0] = cx - w / 2.0f; o[1] = cy - h2 / 2.0f; o[2] = w; o[3] = h2;
-            }
+            kf_update_box_wave(kP(slot), kM(slot), L.xyah + det * 4, lane, L.tbox + t * 4);
         }
         for (int r = wv; r < U; r += NW) {                         // _initiate_track, tracker_core.py:180-194
             const int det = L.cols[r];

@@ -749,7 +749,7 @@ int aic_kf_initiate(int device_id, const float* z, int n, float* mean, float* co
         float* dz = t.up(z, (size_t)n * 4);
         float* dm = t.raw<float>((size_t)n * 8);
         float* dc = t.raw<float>((size_t)n * 64);
-        launch_kf_initiate(dz, n, dm, dc, nullptr, d.s_trk);
+        launch_kf_initiate(dz, n, dm, dc, d.s_trk);
         t.down(mean, dm, (size_t)n * 8);
         t.down(cov, dc, (size_t)n * 64);
         t.sync();
@@ -797,7 +797,7 @@ int aic_kf_update(int device_id, float* mean, float* cov, const float* z, int n)
         float* dm = t.up(mean, (size_t)n * 8);
         float* dc = t.up(cov, (size_t)n * 64);
         float* dz = t.up(z, (size_t)n * 4);
-        launch_kf_update(dm, dc, nullptr, dz, nullptr, n, nullptr, d.s_trk);
+        launch_kf_update(dm, dc, dz, n, d.s_trk);
         t.down(mean, dm, (size_t)n * 8);
         t.down(cov, dc, (size_t)n * 64);
         t.sync();

@@ -1,12 +1,17 @@
-"""Every device copy of the xyah Kalman filter, element by element against float64 (tests/kf_ref.py) and bit for bit against its siblings.
+"""Every device path of the xyah Kalman filter, element by element against float64 (tests/kf_ref.py) and bit for bit against its siblings.
+The arithmetic has one home, csrc/trk_math.hpp: kf_predict_wave / kf_update_wave / kf_initiate_wave (a per-lane compute part, then the
+fenced stores) and the update's pieces kf_gain_row / kf_s_gain / kf_mean_elem / kf_cov_elem.  The forms are the kernels that call it, each
+with its own way of choosing the track, the measurement and where the state lives (tests/test_trk_math_host.py runs the same header on
+the CPU):
 
-  form 1   kf_*_kernel of kernels_trk.hip through the aic_kf_* entries                         test_form1_*, test_gating_*
+  form 1   kf_*_kernel of kernels_trk.hip (one kf_*_wave call each) through the aic_kf_* entries    test_form1_*, test_gating_*
   form 2   trk_commit_kernel: TrackerCore.update_arrays on the host path                       test_planted_frame[host]
-  form 4   kf_predict_wave / kf_update_wave / kf_initiate_wave of trk_math.hpp: ByteTrack's epoch kernel, and the DeepSORT epoch kernel
+  form 4   the kf_*_wave functions inside an epoch kernel: ByteTrack's, and the DeepSORT epoch kernel
            once 72 T floats no longer fit its LDS arena (193 tracks, derived in kf_ref.epoch_arena_floats)
                                                                                                test_bytetrack_*, test_epoch_kernel_both_update_forms
-  form 5   the DeepSORT epoch kernel's thread-per-row update: device_assoc = 1 frame by frame (three full cost matrices in HBM), and
-           update_batch (the lean cost matrix in the arena the update then overwrites)         test_planted_frame[device], [batch]
+  form 5   the DeepSORT epoch kernel's thread-per-row update, written on the update's pieces: device_assoc = 1 frame by frame (three full
+           cost matrices in HBM), and update_batch (the lean cost matrix in the arena the update then overwrites)
+                                                                                               test_planted_frame[device], [batch]
   form 6   the same kernel as block 1 of a two-stream bank launch                              test_bank_stream_*
   form 3   the commit in front of trk_assoc_all_kernel (launch_trk_step) runs only when a PIPELINE on the host chain hands the next
            frame's detections to Tracker::update; no entry of the tracker's own C ABI reaches it (aic_tracker_update_batch always runs
