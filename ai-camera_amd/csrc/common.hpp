@@ -123,18 +123,8 @@ struct Device {
     double flops[AIC_PROF_CLASSES] = {0};
     double bytes[AIC_PROF_CLASSES] = {0};
 
-    // The per-frame plugin loop hands the SAME frame to two engines (YOLODetector.detect(frame), then DeepSORT.update(.., frame) -- the
-    // reference even passes frame.copy(), src/aicamera_tracker.py:180,194): the second call finds the frame already on the device.  Keyed by
-    // CONTENT, not by address: size + 64 lines of 64 bytes spread evenly over the frame (4 KB compared on the host, ~0.2 us, against a 2.76 MB
-    // upload).  A frame that differs from the previous one only outside every sampled line would be taken for it -- sensor noise makes that
-    // a non-event for camera frames; AICAM_NO_FRAME_CACHE=1 switches the cache off.  Both engines run on s_main: the copy is stream-ordered.
-    struct FrameCache {
-        const uint8_t* dev = nullptr;   // inside `owner`'s staging buffer
-        const void* owner = nullptr;
-        size_t bytes = 0;
-        uint8_t sample[64 * 64];
-    } frame_cache;
-    long frame_cache_hits = 0;
+    // (No frame is shared between engines: the per-frame plugin loop hands the same frame to two engines, and each call uploads the
+    // frame it is handed into its own engine's staging buffer -- a result depends on the call's arguments only.  DESIGN.md section 53.)
 
     void use() const { HIP_CHECK(hipSetDevice(id)); }
     void prof_begin(int cls, hipStream_t s, double fl, double by);

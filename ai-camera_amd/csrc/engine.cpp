@@ -1139,33 +1139,11 @@ void load_input_nchw(Model& m, const float* images, int n, int mem, hipStream_t 
     launch_nchw_to_nhwc8(m.dtype, src, m.input(), n, m.in_h, m.in_w, s);
 }
 
-static void frame_sample(const uint8_t* f, size_t bytes, uint8_t* out) {
-    const size_t step = (bytes - 64) / 63;
-    for (int i = 0; i < 64; ++i) std::memcpy(out + 64 * i, f + (size_t)i * step, 64);
-}
-
-// `single`: one frame handed over in host memory -- the plugin loop's calls; see Device::FrameCache
-const uint8_t* stage_frames(Model& m, const uint8_t* frames, size_t bytes, int mem, hipStream_t s, bool single = false) {
+// Every call uploads the frames it is handed into its own engine's staging buffer: nothing is shared with another engine's call.
+const uint8_t* stage_frames(Model& m, const uint8_t* frames, size_t bytes, int mem, hipStream_t s) {
     if (mem == AIC_DEVICE) return frames;
-    static const bool cache_on = getenv("AICAM_NO_FRAME_CACHE") == nullptr;
-    Device::FrameCache& fc = m.dev->frame_cache;
-    uint8_t smp[64 * 64];
-    const bool cacheable = cache_on && single && bytes >= 64 * 64 && s == m.dev->s_main;
-    if (cacheable) {
-        frame_sample(frames, bytes, smp);
-        if (fc.dev && fc.owner != &m && fc.bytes == bytes && std::memcmp(smp, fc.sample, sizeof smp) == 0) {
-            m.dev->frame_cache_hits += 1;
-            return fc.dev;                   // uploaded by the other engine's call a moment ago
-        }
-    }
     m.d_frames.ensure(bytes + 16);           // (slack: the fused crop reads aligned 12-byte groups that may end past the last pixel)
     HIP_CHECK(hipMemcpyAsync(m.d_frames.p, frames, bytes, hipMemcpyHostToDevice, s));
-    if (cacheable) {
-        fc.dev = m.d_frames.p, fc.owner = &m, fc.bytes = bytes;
-        std::memcpy(fc.sample, smp, sizeof smp);
-    } else if (fc.owner == &m) {
-        fc.dev = nullptr;                    // this engine's staging buffer now holds something else
-    }
     return m.d_frames.p;
 }
 
@@ -1293,7 +1271,6 @@ int aic_model_destroy(aic_model* m) {
         if (m) {
             m->m.dev->use();
             (void)hipDeviceSynchronize();
-            if (m->m.dev->frame_cache.owner == &m->m) m->m.dev->frame_cache = Device::FrameCache{};     // its staging buffer goes away
         }
         delete m;
     });
@@ -1608,7 +1585,7 @@ static void detect_frames(aic_model* mm, const uint8_t* frames, int batch, int h
         AIC_REQUIRE(batch <= m.max_items, AIC_ERR_CAPACITY, "batch exceeds the engine's max_items");
         m.dev->use();
         hipStream_t s = m.dev->s_main;
-        const uint8_t* df = stage_frames(m, frames, (size_t)batch * h * w * 3, mem, s, batch == 1);
+        const uint8_t* df = stage_frames(m, frames, (size_t)batch * h * w * 3, mem, s);
         const LetterboxGeom g = letterbox_geometry(h, w, m.in_h, m.in_w);
         DevBuf<int> d_live;
         const int live_host = n_live;                                     // the upload's source: lives until the stream is through
@@ -1714,7 +1691,7 @@ int aic_reid_embed(aic_model* mm, const uint8_t* frame, int h, int w, int mem, c
         AIC_REQUIRE(m.kind == KIND_REID, AIC_ERR_INVALID, "not a ReID engine");
         m.dev->use();
         hipStream_t s = m.dev->s_main;
-        const uint8_t* df = stage_frames(m, frame, (size_t)h * w * 3, mem, s, true);
+        const uint8_t* df = stage_frames(m, frame, (size_t)h * w * 3, mem, s);
         m.d_crop_boxes.ensure((size_t)n * 4);
         m.d_valid.ensure(n);
         HIP_CHECK(hipMemcpyAsync(m.d_crop_boxes.p, boxes, (size_t)n * 16, hipMemcpyHostToDevice, s));

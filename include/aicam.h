@@ -180,7 +180,9 @@ int aic_crop_resize(int device, const uint8_t* frame_bgr, int h, int w, const fl
  * (image_processing.py:141-183). boxes are xyxy in original-frame pixels, clipped.
  * Outputs are host arrays num_dets[B], boxes_xyxy[B,max_det,4], scores[B,max_det], labels[B,max_det].  At every batch size the call
  * writes num_dets[b] and the first min(num_dets[b], max_det) rows of frame b; rows past a frame's count are left as the caller
- * passed them.  aic_detect_decode, aic_detect_live and aic_yolo_infer with host outputs follow the same contract. */
+ * passed them.  aic_detect_decode, aic_detect_live and aic_yolo_infer with host outputs follow the same contract.
+ * The result depends on the arguments only: every call uploads the frames it is handed, and no frame that this or another handle
+ * was handed earlier is ever used in their place, however alike the two are. */
 int aic_detect(aic_model* yolo, const uint8_t* frames_bgr, int batch, int h, int w, int mem,
                float conf_thresh, float iou_thresh, int max_det, int32_t* num_dets, float* boxes_xyxy,
                float* scores, int32_t* labels);
@@ -194,7 +196,9 @@ int aic_detect_live(aic_model* yolo, const uint8_t* frames_bgr, int batch, int n
                     float conf_thresh, float iou_thresh, int max_det, int32_t* num_dets, float* boxes_xyxy,
                     float* scores, int32_t* labels);
 
-/* crop -> ReID engine (deepsort_tracker.py:104-113 + reid_model.py:67-126) for one frame. */
+/* crop -> ReID engine (deepsort_tracker.py:104-113 + reid_model.py:67-126) for one frame.  The result depends on the arguments only:
+ * the crops come from frame_bgr as handed to this call, never from a frame an earlier call (aic_detect on the same frame a moment
+ * before, say) left on the device. */
 int aic_reid_embed(aic_model* reid, const uint8_t* frame_bgr, int h, int w, int mem,
                    const float* boxes_xyxy, int n, float* embeddings, int32_t* valid);
 

@@ -229,7 +229,8 @@ def test_no_conv_kernel_spills():
 
 def test_switches_match_design_table():
     """The environment switches the library reads are exactly the ones DESIGN.md §11 lists, and every switch a test or tool names is one
-    the library reads: a reference-path test whose switch no longer exists would compare a path with itself and still pass."""
+    the library reads: a reference-path test whose switch no longer exists would compare a path with itself and still pass.  The one
+    exception is written into the table: a row of class "retired" (a switch whose effect is now unconditional) is read nowhere."""
     name = re.compile(r"\bAICAM_[A-Z0-9][A-Z0-9_]*")
     src = os.path.join(ROOT, "ai-camera_amd")
     read = set()
@@ -246,7 +247,11 @@ def test_switches_match_design_table():
                 read |= set(re.findall(r"""os\.(?:environ\.get\(|environ\[|getenv\()\s*["'](""" + name.pattern[2:] + ")", text))
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     table = design[design.index("\n## 11."):design.index("\n## 12.")]
-    listed = set(name.findall("\n".join(l for l in table.splitlines() if l.startswith("|"))))
+    rows = [l for l in table.splitlines() if l.startswith("|")]
+    # a row of class "retired": a variable that had an effect once and has none now -- the library must not read it any more
+    retired = set(name.findall("\n".join(l for l in rows if l.split("|")[2].strip() == "retired")))
+    listed = set(name.findall("\n".join(rows))) - retired
+    assert not (retired & read), sorted(retired & read)
     assert read == listed, (sorted(read - listed), sorted(listed - read))
     named = {}
     for d in ("tests", "tools"):
@@ -255,5 +260,5 @@ def test_switches_match_design_table():
                 if f.endswith((".py", ".sh")):
                     for n in name.findall(open(os.path.join(dirpath, f)).read()):
                         named.setdefault(n, os.path.relpath(os.path.join(dirpath, f), ROOT))
-    stale = {n: f for n, f in named.items() if n not in read}
+    stale = {n: f for n, f in named.items() if n not in read and n not in retired}
     assert not stale, stale

@@ -23,7 +23,7 @@ TEMPLATE = r"""| Quantity | Value | Source |
 | tracker stream per 512-frame group (beside the convs) | @TRK_MS@ ms | `profiles/@TAG@_kernel_summary.txt` |
 | **own detections on the TRAINED detector** (inject = 0: the reference's data flow; same clip, same span, streams as the headline) | **@OWN_FPS@ frames/s = @OWN_FRAC@ of `value`**; association frames (device, host) = (@OWN_DEV@, 0); detector recall of the planted boxes @OWN_RECALL@; fp16 vs fp32 of the same engines on their own detections: @OWN_REPRO@ of the track outputs reproduced, @OWN_IDSW@ id switches in 256 frames (test scene, 300 frames: 100 %, 0) | `profiles/@TAG@_bench.json` (`config.own_detections_trained_detector…`), `tests/test_trained_detector.py` |
 | own detections, seeded texture scene (stress leg: 100–258 detections in a fifth of the frames) | @TEX_DEV@ / @TEX_HOST@ frames/s (filter per group / on the host) | same |
-| per-frame plugin loop (`YOLODetector.detect` + `DeepSORT.update` on the detector's own boxes, one frame per call, host arrays in and out) | **@PLUG_FPS@ frames/s, p50 @PLUG_P50@ ms** (round 4: 532, 1.87) | `profiles/@TAG@_bench.json` (`config.plugin_loop`) |
+| per-frame plugin loop (`YOLODetector.detect` + `DeepSORT.update` on the detector's own boxes, one frame per call, host arrays in and out) | **@PLUG_FPS@ frames/s, p50 @PLUG_P50@ ms** (round 4: 532, 1.87) — measured with one upload per frame; since §53 each of the two calls uploads the frame it is handed (`AICAM_NO_FRAME_CACHE` is a no-op), 729 against 742 frames/s in `tools/plugin_ab.py 200` | `profiles/@TAG@_bench.json` (`config.plugin_loop`) |
 | launch groups of 16 / 64 / 128 / 256 / 512 frames: frames/s (p50 latency) | @CURVE@ | same |
 | CPU oracle chain on the box's 16 cores / 1 thread | @CPU16@ / @CPU1@ frames/s | same |
 | YOLOv8m fp32 boxes vs the fp64 evaluation of the same engine (33 600 coordinates) | rms 5.3e-5 px, 99.9th percentile 5.2e-4, max 1.05e-3 (1 coordinate above 1e-3); round 4: max 1.6e-3 | `gpurun_out/r5_v8m_err.txt`, `tests/test_gpu_configs.py` |
