@@ -174,10 +174,217 @@ __global__ __launch_bounds__(256) void trk_epoch_prep_kernel(const DevTrkHdr* __
     }
 }
 
+// ------------------------------------------------------------------------------------------------ prep kernel, second form
+// The same tables from the same dot products (same MFMA, gallery row as A, detection as B, k ascending in 64-wide slices and the
+// element-guarded 16-wide tail), dealt differently.  A block owns ONE 32-detection chunk and every P-th track (blockIdx.x = chunk * P + p):
+//   - the chunk's 32 detection rows go to LDS once (row pitch dim + 4 floats: the sixteen rows a 16-byte read touches start four banks
+//     apart) and every unit of the block reads its B fragments from there, so a detection row crosses L2 once per block;
+//   - a UNIT is one 16-row group against the chunk: (track, row group) for SM, (16 epoch rows) for GRAM.  The block's units of a pass
+//     (PREP_NTB tracks, plus the block's GRAM units in the first pass) form one list that the four waves walk round robin, so a track's
+//     row groups spread over the waves and the ragged last round is one unit deep;
+//   - the A fragments of the NEXT slice -- or of the next unit's first slice -- are requested before the 32 MFMAs of this one, into a
+//     second register set; the B fragments of the next slice likewise from LDS.  Nothing waits on L2 between MFMAs;
+//   - the suffix minima are merged when the pass's units are done: fminf over finite values is exact and order-free, so a row group
+//     that lies wholly behind row k only leaves its column minima (per wave, no atomics), the groups that hold a row <= k leave their
+//     tile, and one wave per track walks those rows newest first, exactly as the first form does.
+constexpr int PREP_NTB = 8;                     // tracks of a block per pass
+constexpr int PREP_GCAP = 16;                   // row groups of a gallery: gmax <= 256 (launch_trk_epoch_prep sends larger budgets to the first form)
+constexpr int PREP_TG = TRK_KMAX / 16 + 1;      // row groups that can hold a row <= k
+
+static size_t prep2_lds_bytes(int dim) {
+    return ((size_t)32 * (dim + 4) + (size_t)PREP_NTB * PREP_TG * 16 * 36 + PREP_NTB * 4 * 32) * 4 + (3 * PREP_NTB + PREP_NTB * PREP_GCAP + 4) * 4;
+}
+
+__global__ __launch_bounds__(256) void trk_epoch_prep2_kernel(const DevTrkHdr* __restrict__ hdr, const DevTrack* __restrict__ trk,
+                                                              const float* __restrict__ gal_n, int gmax, int dim,
+                                                              const float* __restrict__ featn, int dn, int dn_pad, int k,
+                                                              float* __restrict__ sm, float* __restrict__ gram, int f0, int P, EpochBankArgs bk) {
+    extern __shared__ floatx4 prep_lds[];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+    const int pitch = dim + 4;
+    float* bst = reinterpret_cast<float*>(prep_lds);                    // [32][pitch] the chunk's detection rows
+    float* tiles = bst + 32 * pitch;                                    // [NTB][TG][16][36] distances of the row groups that hold a row <= k
+    float* rest = tiles + PREP_NTB * PREP_TG * 16 * 36;                 // [NTB][4 waves][32] column minima of the other row groups
+    int* l_slot = reinterpret_cast<int*>(rest + PREP_NTB * 4 * 32);     // the pass's tracks
+    int* l_glen = l_slot + PREP_NTB;
+    int* l_ghead = l_glen + PREP_NTB;
+    int* utab = l_ghead + PREP_NTB;                                     // [NTB * GCAP] SM unit -> local track << 8 | row group
+    const int* rmap = nullptr;
+    if (bk.stream_k) {
+        const size_t sid = blockIdx.y;
+        const EpochStreamPlan pl = bk.plan[sid];
+        hdr = reinterpret_cast<const DevTrkHdr*>(bk.tbl + sid * bk.tbl_stride);
+        if (!pl.has_sm || bk.stream_k[sid] <= f0 || hdr->err) return;      // what the epoch kernel's block of this stream will not read
+        trk = reinterpret_cast<const DevTrack*>(hdr + 1);
+        gal_n += sid * bk.gal_stride, sm += sid * bk.sm_stride, gram += sid * bk.gram_stride;
+        dn = pl.dn, dn_pad = pl.dn_pad;
+        rmap = bk.row_map + pl.map0;
+    }
+    auto frow = [&](int i) -> const float* { return featn + (size_t)(rmap ? rmap[i] : i) * dim; };
+    const int T0 = hdr->n_tracks;
+    const int c = blockIdx.x / P, p = blockIdx.x - c * P;
+    if (c >= dn_pad / 32) return;
+    const int d_base = c * 32;
+    const int ngr = 2 * c + 1 >= p ? (2 * c + 1 - p) / P + 1 : 0;       // GRAM row groups p, p + P, ... <= 2 c + 1 (later rows never meet these columns)
+    const int ntr = T0 > p ? (T0 - p + P - 1) / P : 0;                  // tracks p, p + P, ... < T0
+    if (ngr == 0 && ntr == 0) return;
+    {                                                                   // the chunk to LDS: a wave per row, 16 bytes per lane
+        const int d4 = dim >> 2;
+        for (int row = wv; row < 32; row += 4) {
+            const floatx4* src = reinterpret_cast<const floatx4*>(frow(min(d_base + row, dn - 1)));
+            floatx4* dst = reinterpret_cast<floatx4*>(bst + row * pitch);
+            for (int i = lane; i < d4; i += 64) dst[i] = src[i];
+        }
+    }
+    const float* bA = bst + r * pitch + 4 * q;                          // detection d_base + r, d_base + 16 + r: this lane's 16 bytes of a 16-deep slice
+    const float* bB = bst + (16 + r) * pitch + 4 * q;
+    const int ns = dim / 64;
+    for (int t0 = 0; t0 == 0 || t0 < ntr; t0 += PREP_NTB) {
+        const int nt = max(0, min(PREP_NTB, ntr - t0));
+        __syncthreads();                                                // the pass before has been read out
+        if (tid < nt) {
+            const DevTrack* tr = trk + p + (size_t)(t0 + tid) * P;
+            l_slot[tid] = tr->slot, l_glen[tid] = tr->glen, l_ghead[tid] = tr->ghead;
+        }
+        for (int i = tid; i < PREP_NTB * 4 * 32; i += 256) rest[i] = kBig;
+        __syncthreads();
+        int nsm = 0;
+        {
+            const int tl = tid / PREP_GCAP, g = tid - tl * PREP_GCAP;   // threads 0 .. NTB * GCAP - 1: one candidate unit each
+            int before = 0;
+            for (int i = 0; i < nt; ++i) {
+                const int G = min((l_glen[i] + 15) / 16, PREP_GCAP);
+                if (i < tl) before += G;
+                if (i == tl && g < G) utab[before + g] = tl << 8 | g;
+                nsm += G;
+            }
+        }
+        __syncthreads();
+        const int nu = nsm + (t0 == 0 ? ngr : 0);
+        auto unit_a = [&](int u) -> const float* {                      // this lane's A row of unit u
+            if (u >= nsm) return frow(min((p + (u - nsm) * P) * 16 + r, dn - 1));
+            const int e = utab[u], tl = e >> 8;
+            const int j = min(16 * (e & 255) + r, l_glen[tl] - 1);      // rows past the end alias the last one (masked below)
+            int pos = l_ghead[tl] + j;
+            if (pos >= gmax) pos -= gmax;
+            return gal_n + ((size_t)l_slot[tl] * gmax + pos) * dim;
+        };
+        floatx4 a[4], b0[4], b1[4], a2[4], b20[4], b21[4];
+        const float* gp = wv < nu ? unit_a(wv) : nullptr;
+        if (gp && ns > 0) {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                a[v] = *reinterpret_cast<const floatx4*>(gp + 16 * v + 4 * q);
+                b0[v] = *reinterpret_cast<const floatx4*>(bA + 16 * v);
+                b1[v] = *reinterpret_cast<const floatx4*>(bB + 16 * v);
+            }
+        }
+        for (int u = wv; u < nu; u += 4) {
+            const float* gpn = u + 4 < nu ? unit_a(u + 4) : gp;
+            floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+            // slice s from (ca, cb0, cb1) while slice s + 1 -- the next unit's slice 0 behind the last -- arrives in (na, nb0, nb1).  The
+            // scheduling barrier keeps the requests in front of the MFMAs; the two register sets swap roles, nothing is copied.
+            auto slice = [&](int s, const floatx4 (&ca)[4], const floatx4 (&cb0)[4], const floatx4 (&cb1)[4], floatx4 (&na)[4], floatx4 (&nb0)[4],
+                             floatx4 (&nb1)[4]) {
+                const bool wrap = s + 1 == ns;
+                const float* an_p = (wrap ? gpn : gp + 64 * (s + 1)) + 4 * q;
+                const int kb = wrap ? 0 : 64 * (s + 1);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    na[v] = *reinterpret_cast<const floatx4*>(an_p + 16 * v);
+                    nb0[v] = *reinterpret_cast<const floatx4*>(bA + kb + 16 * v);
+                    nb1[v] = *reinterpret_cast<const floatx4*>(bB + kb + 16 * v);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ca[v][e], cb0[v][e], acc0, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ca[v][e], cb1[v][e], acc1, 0, 0, 0);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            int s = 0;
+            for (; s + 2 <= ns; s += 2) {
+                slice(s, a, b0, b1, a2, b20, b21);
+                slice(s + 1, a2, b20, b21, a, b0, b1);
+            }
+            if (s < ns) {                                               // an odd slice count: one copy per unit
+                slice(s, a, b0, b1, a2, b20, b21);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) a[v] = a2[v], b0[v] = b20[v], b1[v] = b21[v];
+            }
+            for (int k0 = ns * 64; k0 < dim; k0 += 16) {                // tail: any dimension, element-guarded
+                const int kk = k0 + 4 * q;
+                floatx4 ta = {0.f, 0.f, 0.f, 0.f}, tb0 = ta, tb1 = ta;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (kk + e < dim) { ta[e] = gp[kk + e]; tb0[e] = bA[k0 + e]; tb1[e] = bB[k0 + e]; }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[e], tb0[e], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[e], tb1[e], acc1, 0, 0, 0);
+                }
+            }
+            if (u >= nsm) {                                             // GRAM: straight to the table
+                const int a0 = (p + (u - nsm) * P) * 16;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float* o = gram + (size_t)(a0 + 4 * q + e) * dn_pad + d_base;
+                    o[r] = cos_dist(acc0[e]);
+                    o[16 + r] = cos_dist(acc1[e]);
+                }
+            } else {
+                const int en = utab[u], tl = en >> 8, g = en & 255;
+                if (16 * g <= k) {                                      // holds a row <= k: the merge needs the rows one by one
+                    float* tile = tiles + (tl * PREP_TG + g) * 16 * 36;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        tile[(4 * q + e) * 36 + r] = cos_dist(acc0[e]);
+                        tile[(4 * q + e) * 36 + 16 + r] = cos_dist(acc1[e]);
+                    }
+                } else {
+                    float m0, m1;
+                    cos_tile_min(acc0, acc1, 16 * g, q, l_glen[tl], m0, m1);
+                    float* rw = rest + (tl * 4 + wv) * 32;              // this wave's own line: no other wave writes it
+                    if (q == 0) {
+                        rw[r] = fminf(rw[r], m0);
+                        rw[16 + r] = fminf(rw[16 + r], m1);
+                    }
+                    wave_lds_sync();
+                }
+            }
+            gp = gpn;
+        }
+        __syncthreads();
+        if (lane < 32) {
+            for (int tl = wv; tl < nt; tl += 4) {                       // suffix minima, newest rows first
+                const int glen0 = l_glen[tl];
+                float* smt = sm + ((size_t)p + (size_t)(t0 + tl) * P) * (TRK_KMAX + 1) * dn_pad + d_base;
+                for (int e = glen0; e <= k; ++e) smt[(size_t)e * dn_pad + lane] = kBig;       // empty suffix
+                const float* rw = rest + tl * 4 * 32;
+                float R = fminf(fminf(rw[lane], rw[32 + lane]), fminf(rw[64 + lane], rw[96 + lane]));
+                const int G = min((glen0 + 15) / 16, PREP_GCAP);
+                for (int g = min(G, k / 16 + 1) - 1; g >= 0; --g) {
+                    const float* tile = tiles + (tl * PREP_TG + g) * 16 * 36;
+                    for (int jj = 15; jj >= 0; --jj) {
+                        const int row = 16 * g + jj;
+                        if (row < glen0) {
+                            R = fminf(R, tile[jj * 36 + lane]);
+                            if (row <= k) smt[(size_t)row * dn_pad + lane] = R;     // min over FIFO rows >= row
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ epoch kernel
 namespace {
 
-struct Lds {                        // carved out of the dynamic LDS block by lds_carve()
+struct Lds {                     // carved out of the dynamic LDS block by lds_carve()
     // track table (SoA), list order
     int *id, *state, *hits, *age, *tsu, *cls, *slot, *glen, *ghead, *sm, *napp, *glen0;
     float* conf;
@@ -1229,7 +1436,7 @@ void launch_gallery_shard(const DevTrkHdr* hdr, const DevTrack* trk, const float
 
 // ------------------------------------------------------------------------------------------------ gallery commit
 // The rows an epoch appended to the galleries (list left by trk_epoch_kernel: slot, ring position, epoch row; length behind the list),
-// raw + unit, one row per block and pass.
+// raw + unit, one row per wave and pass.
 // A bank (gal_stride > 0 with more than one grid row): blockIdx.y = stream, whose list holds detection rows themselves (d_begin = 0).
 __global__ __launch_bounds__(256) void gallery_commit_kernel(const int* __restrict__ appends, const float* __restrict__ feat, const float* __restrict__ feat_n,
                                                              int d_begin, int dim, int gmax, float* __restrict__ gal_raw, float* __restrict__ gal_n,
@@ -1241,22 +1448,56 @@ __global__ __launch_bounds__(256) void gallery_commit_kernel(const int* __restri
     const floatx4* fn = reinterpret_cast<const floatx4*>(feat_n + (size_t)d_begin * dim);
     floatx4* graw = reinterpret_cast<floatx4*>(gal_raw);
     floatx4* gn = reinterpret_cast<floatx4*>(gal_n);
-    for (int i = blockIdx.x; i < na; i += gridDim.x) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int i = blockIdx.x * 4 + wv; i < na; i += gridDim.x * 4) {
         const int slot = appends[i * 3], pos = appends[i * 3 + 1], er = appends[i * 3 + 2];
         const size_t dst = ((size_t)slot * gmax + pos) * d4, src = (size_t)er * d4;
-        for (int c = threadIdx.x; c < 2 * d4; c += 256) {
+        for (int c = lane; c < 2 * d4; c += 64) {
             if (c < d4) graw[dst + c] = fr[src + c];
             else gn[dst + c - d4] = fn[src + c - d4];
         }
     }
 }
 
+// blocks of gallery_commit_kernel for a list of at most `rows` entries: four rows per block and pass, no block without a row
+static int commit_blocks(long rows, int most) { return (int)std::max<long>(1, std::min<long>(most, (std::min<long>(rows, TRK_DEV_DNMAX) + 3) / 4)); }
+
 // ------------------------------------------------------------------------------------------------ launchers
 static int epoch_lds_bytes() { return 159 * 1024; }
+
+// AICAM_TRK_PREP_V1=1: the first form of the prep kernel (A/B runs, the reference of tests/test_gpu_trk_prep.py).  It also takes what the
+// second form does not hold: gallery budgets above 16 * PREP_GCAP rows and dimensions whose 32-row chunk does not fit the LDS.
+static bool prep_second_form(int gmax, int dim) {
+    static const bool v1 = [] { const char* e = getenv("AICAM_TRK_PREP_V1"); return e && atoi(e) != 0; }();
+    if (v1 || dim % 4 != 0 || gmax > 16 * PREP_GCAP || prep2_lds_bytes(dim) > (size_t)160 * 1024) return false;
+    set_lds_limit(trk_epoch_prep2_kernel, (size_t)160 * 1024);
+    return true;
+}
+
+// Blocks per 32-detection chunk of the second form: about 36 units (nine per wave) for the tracks the epoch is LIKELY to have (about as
+// many live tracks as detections per frame), each with a full gallery; `most` blocks in all.  The bench (30 tracks, 15 chunks) gets 6,
+// 90 blocks; 3, 4, 10 and 15 per chunk measured the same frames/s within the run-to-run spread.
+static int prep2_split(int gmax, int dn_pad, int k, long most) {
+    const int groups = std::max(1, (gmax + 15) / 16), per_block = std::max(1, 36 / groups);
+    const long likely = std::max(1, dn_pad / std::max(k, 1));
+    return (int)std::max<long>(1, std::min<long>((likely + per_block - 1) / per_block, most / (dn_pad / 32)));
+}
 
 void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const float* gal_n, int gmax, int dim, int cap, const float* featn,
                            int dn, int dn_pad, int k, float* sm, float* gram, hipStream_t s) {
     if (dn <= 0) return;
+    // AICAM_TRK_PREP_REPEAT=n (diagnostic): the launch is issued n times; the later ones rewrite the same tables with the same values.
+    // What a second launch costs end to end is the price of one prep's worth of CU time.
+    static const int repeat = [] { const char* e = getenv("AICAM_TRK_PREP_REPEAT"); return e ? std::max(1, std::min(atoi(e), 16)) : 1; }();
+    if (prep_second_form(gmax, dim)) {
+        const int P = prep2_split(gmax, dn_pad, k, 512);
+        for (int i = 0; i < repeat; ++i) {
+            hipLaunchKernelGGL(trk_epoch_prep2_kernel, dim3(dn_pad / 32 * P), dim3(256), prep2_lds_bytes(dim), s, hdr, trk, gal_n, gmax, dim, featn, dn, dn_pad, k,
+                               sm, gram, 0, P, EpochBankArgs{});
+            KCHECK();
+        }
+        return;
+    }
     const long tasks = ((long)cap + dn_pad / 16) * (dn_pad / 32);
     // Blocks: enough for the tasks the epoch is LIKELY to have (about as many live tracks as detections per frame), nine wave-tasks
     // each, not one block per four tasks of the worst case (every slot of the table alive).  Every block of this launch has to find
@@ -1274,6 +1515,13 @@ void launch_trk_epoch_prep(const DevTrkHdr* hdr, const DevTrack* trk, const floa
 void launch_trk_epoch_prep_bank(const EpochBankArgs& bk, int streams, const float* gal_n, int gmax, int dim, int cap, const float* featn,
                                 int dn_pad_max, int f0, int k, float* sm, float* gram, hipStream_t s) {
     if (dn_pad_max <= 0 || streams <= 0) return;
+    if (prep_second_form(gmax, dim)) {
+        const int P = prep2_split(gmax, dn_pad_max, k, std::max<long>(8, 1024 / streams));      // S streams share the 256 CUs
+        hipLaunchKernelGGL(trk_epoch_prep2_kernel, dim3(dn_pad_max / 32 * P, streams), dim3(256), prep2_lds_bytes(dim), s, (const DevTrkHdr*)nullptr,
+                           (const DevTrack*)nullptr, gal_n, gmax, dim, featn, 0, 0, k, sm, gram, f0, P, bk);
+        KCHECK();
+        return;
+    }
     const long tasks = ((long)cap + dn_pad_max / 16) * (dn_pad_max / 32);
     const long likely = ((long)dn_pad_max / std::max(k, 1) + dn_pad_max / 16) * (dn_pad_max / 32);
     // one stream: the single tracker's grid.  S streams share the 256 CUs: at least 8 blocks each, about 1024 in all
@@ -1331,7 +1579,7 @@ void launch_trk_epoch(DevTrkHdr* hdr, DevTrack* trk, int* free_slots, float* mea
     hipLaunchKernelGGL(trk_epoch_kernel<false>, dim3(1), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
     KCHECK();
     if (a.commit_ext) {
-        hipLaunchKernelGGL(gallery_commit_kernel, dim3(256), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n,
+        hipLaunchKernelGGL(gallery_commit_kernel, dim3(commit_blocks(dn_pad, 256)), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, d_begin, prm.dim, prm.gmax, gal_raw, gal_n,
                            (size_t)0);
         KCHECK();
     }
@@ -1357,7 +1605,7 @@ void launch_trk_epoch_bank(const EpochBankArgs& bk, int streams, float* mean, fl
     hipLaunchKernelGGL(trk_epoch_kernel<true>, dim3(streams), dim3(TRK_DEV_TMAX), (size_t)epoch_lds_bytes(), s, a);
     KCHECK();
     if (dets.feat != nullptr && dets.feat_n != nullptr) {
-        hipLaunchKernelGGL(gallery_commit_kernel, dim3(std::max(8, 256 / streams), streams), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, 0, prm.dim,
+        hipLaunchKernelGGL(gallery_commit_kernel, dim3(commit_blocks((long)std::max(nmax_call, 1) * k, std::max(8, 256 / streams)), streams), dim3(256), 0, s, scr.appends, dets.feat, dets.feat_n, 0, prm.dim,
                            prm.gmax, gal_raw, gal_n, bk.gal_stride);
         KCHECK();
     }

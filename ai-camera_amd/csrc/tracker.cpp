@@ -935,6 +935,74 @@ int aic_match_cascade_device(int device_id, const float* app, const float* maha,
     });
 }
 
+// The epoch prep kernel alone on caller-provided tables (tests/test_gpu_trk_prep.py): SM and GRAM as the epoch kernel would read them.
+int aic_trk_prep_test(int device_id, int streams, int cap, const int32_t* n_tracks, const int32_t* slot_glen_ghead, const float* gal_n, int gmax,
+                      int dim, const float* feat_n, int rows, const int32_t* stream_dn, const int32_t* row_map, const int32_t* has_sm, int k,
+                      int dn_pad, float* sm, float* gram) {
+    return guarded([&] {
+        AIC_REQUIRE(n_tracks && slot_glen_ghead && gal_n && feat_n && stream_dn && sm && gram, AIC_ERR_INVALID, "NULL argument");
+        AIC_REQUIRE(streams >= 0 && streams <= 64 && cap >= 1 && cap <= TRK_DEV_TMAX && gmax >= 1 && dim >= 4 && dim % 4 == 0 && rows >= 1 && k >= 1 &&
+                    k <= TRK_KMAX && dn_pad >= 32 && dn_pad % 32 == 0 && dn_pad <= TRK_DEV_DNMAX, AIC_ERR_INVALID, "prep test: shape out of range");
+        const int S = std::max(streams, 1);
+        AIC_REQUIRE(streams == 0 || (row_map && has_sm), AIC_ERR_INVALID, "prep test: a bank needs row_map and has_sm");
+        const size_t tbl_stride = sizeof(DevTrkHdr) + (size_t)cap * sizeof(DevTrack) + (size_t)cap * 4;
+        std::vector<char> tbl(tbl_stride * S, 0);
+        std::vector<EpochStreamPlan> plan(S);
+        std::vector<int> sk(S, k);
+        int map_n = 0;
+        for (int s = 0; s < S; ++s) {
+            AIC_REQUIRE(n_tracks[s] >= 0 && n_tracks[s] <= cap, AIC_ERR_INVALID, "prep test: n_tracks out of range");
+            DevTrkHdr* h = reinterpret_cast<DevTrkHdr*>(tbl.data() + tbl_stride * s);
+            DevTrack* tr = reinterpret_cast<DevTrack*>(h + 1);
+            h->n_tracks = n_tracks[s];
+            for (int i = 0; i < n_tracks[s]; ++i) {
+                const int32_t* e = slot_glen_ghead + ((size_t)s * cap + i) * 3;
+                AIC_REQUIRE(e[0] >= 0 && e[0] < cap && e[1] >= 0 && e[1] <= gmax && e[2] >= 0 && e[2] < gmax, AIC_ERR_INVALID, "prep test: track out of range");
+                tr[i].slot = e[0], tr[i].glen = e[1], tr[i].ghead = e[2];
+            }
+            const int dn = stream_dn[s];
+            AIC_REQUIRE(dn >= (streams ? 0 : 1) && dn <= dn_pad && (streams || dn <= rows), AIC_ERR_INVALID, "prep test: detection rows out of range");
+            plan[s] = EpochStreamPlan{};
+            plan[s].dn = dn, plan[s].dn_pad = std::max(32, (dn + 31) / 32 * 32), plan[s].nmax = 1, plan[s].map0 = map_n;
+            plan[s].has_sm = streams ? (has_sm[s] && dn > 0) : 1;
+            if (streams) {
+                for (int i = 0; i < dn; ++i) AIC_REQUIRE(row_map[map_n + i] >= 0 && row_map[map_n + i] < rows, AIC_ERR_INVALID, "prep test: row_map out of range");
+                map_n += dn;
+            }
+        }
+        AIC_REQUIRE(streams || plan[0].dn_pad == dn_pad, AIC_ERR_INVALID, "prep test: dn_pad must be the padded row count");
+        Device& d = device(device_id);
+        d.use();
+        hipStream_t st = d.s_trk;
+        const size_t gal_stride = (size_t)cap * gmax * dim, sm_stride = (size_t)cap * (TRK_KMAX + 1) * dn_pad, gram_stride = (size_t)dn_pad * dn_pad;
+        DevBuf<char> d_tbl(tbl.size());
+        DevBuf<float> d_gal(gal_stride * S), d_feat((size_t)rows * dim), d_sm(sm_stride * S), d_gram(gram_stride * S);
+        DevBuf<EpochStreamPlan> d_plan(S);
+        DevBuf<int> d_sk(S), d_map(std::max(map_n, 1));
+        std::vector<float> fill(std::max(sm_stride, gram_stride) * S, -1.0f);      // what the kernel leaves alone compares equal
+        HIP_CHECK(hipMemcpyAsync(d_tbl.p, tbl.data(), tbl.size(), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_gal.p, gal_n, gal_stride * S * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_feat.p, feat_n, (size_t)rows * dim * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_sm.p, fill.data(), sm_stride * S * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_gram.p, fill.data(), gram_stride * S * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_plan.p, plan.data(), sizeof(EpochStreamPlan) * S, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(d_sk.p, sk.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+        if (map_n) HIP_CHECK(hipMemcpyAsync(d_map.p, row_map, (size_t)map_n * 4, hipMemcpyHostToDevice, st));
+        if (streams) {
+            EpochBankArgs bk{};
+            bk.tbl = d_tbl.p, bk.tbl_stride = tbl_stride, bk.gal_stride = gal_stride, bk.sm_stride = sm_stride, bk.gram_stride = gram_stride;
+            bk.stream_k = d_sk.p, bk.plan = d_plan.p, bk.row_map = d_map.p;
+            launch_trk_epoch_prep_bank(bk, S, d_gal.p, gmax, dim, cap, d_feat.p, dn_pad, 0, k, d_sm.p, d_gram.p, st);
+        } else {
+            launch_trk_epoch_prep(reinterpret_cast<const DevTrkHdr*>(d_tbl.p), reinterpret_cast<const DevTrack*>(d_tbl.p + sizeof(DevTrkHdr)), d_gal.p, gmax,
+                                  dim, cap, d_feat.p, stream_dn[0], dn_pad, k, d_sm.p, d_gram.p, st);
+        }
+        HIP_CHECK(hipMemcpyAsync(sm, d_sm.p, sm_stride * S * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(gram, d_gram.p, gram_stride * S * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
 int aic_tracker_predict(aic_tracker* t) {
     return guarded([&] {
         AIC_REQUIRE(t, AIC_ERR_INVALID, "NULL tracker");

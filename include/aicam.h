@@ -280,6 +280,17 @@ int aic_match_cascade_device(int device, const float* app, const float* maha, co
                              double max_iou_distance, int max_age, int flags, int32_t* match_det_of_track,
                              int32_t* n_fast_lsap);
 
+/* The epoch prep kernel of the device association alone (csrc/kernels_trk_dev.hip), on caller-provided tables: test entry point.
+ * streams = 0: the single tracker's launch on rows [0, stream_dn[0]) of feat_n[rows, dim]; streams = S >= 1: the bank launch, stream s
+ * reading rows row_map[...] (the streams' maps one behind the other, stream_dn[s] entries each) and skipped when has_sm[s] = 0.  Per
+ * stream: n_tracks[s] tracks, track i = slot_glen_ghead[s][i][3] (gallery slot, length, ring head) into gal_n[s][cap][gmax][dim] (unit
+ * rows).  dn_pad: pitch the tables are sized for (a multiple of 32, >= every stream's padded row count; streams = 0: equal to it).
+ * Outputs, filled with -1 where the kernel writes nothing: sm[s][cap][17][dn_pad] and gram[s][dn_pad][dn_pad] floats, a stream's own
+ * tables at its own padded pitch from the start of its slice. */
+int aic_trk_prep_test(int device, int streams, int cap, const int32_t* n_tracks, const int32_t* slot_glen_ghead,
+                      const float* gal_n, int gmax, int dim, const float* feat_n, int rows, const int32_t* stream_dn,
+                      const int32_t* row_map, const int32_t* has_sm, int k, int dn_pad, float* sm, float* gram);
+
 /* ------------------------------------------------------------------ tracker
  * TrackerCore (src/tracker/core/tracker_core.py:11-198) + Track lifecycle
  * (src/tracker/core/track.py:16-171).  Kalman state and feature galleries live in HBM;
