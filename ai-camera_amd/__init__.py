@@ -14,7 +14,7 @@ __version__ = "0.1.0"
 PKG = __name__
 
 _LAZY = ("config", "synthetic", "engine_file", "_lib", "hip_engine", "image_processing",
-         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "bestshot", "scene", "leftobj", "colours", "heatmap", "render", "jpeg", "jpegdec", "gmc", "frames", "core", "pipeline", "distributed", "cli")
+         "detector", "reid_model", "deepsort_tracker", "bytetrack", "ocsort", "botsort", "deepsort_bank", "xcam", "archive", "zones", "bestshot", "scene", "leftobj", "colours", "heatmap", "proximity", "render", "jpeg", "jpegdec", "gmc", "frames", "core", "pipeline", "distributed", "cli")
 
 
 def __getattr__(name):
@@ -50,6 +50,8 @@ def __getattr__(name):
         return _importlib.import_module(f"{__name__}.colours").TrackColours
     if name == "HeatMaps":
         return _importlib.import_module(f"{__name__}.heatmap").HeatMaps
+    if name == "Proximity":
+        return _importlib.import_module(f"{__name__}.proximity").Proximity
     if name == "Renderer":
         return _importlib.import_module(f"{__name__}.render").Renderer
     if name == "JpegEncoder":

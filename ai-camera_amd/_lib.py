@@ -84,6 +84,11 @@ class HeatConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "cell", "max_tracks", "forget_after", "anchor", "min_move")]
 
 
+class ProxConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("streams", "frame_h", "frame_w", "max_tracks", "forget_after", "metric", "near", "height_ratio_q8",
+                                         "link_ticks", "unlink_ticks", "speed_shift", "still_speed", "run_speed")]
+
+
 class JpegConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("max_images", "height", "width", "quality", "restart", "subsampling")] + [("max_bytes", C.c_int64)]
 
@@ -338,6 +343,16 @@ _SIGS = {
     "aic_heat_set_lut": (_I, [_P, _P]),
     "aic_heat_lut": (_I, [_P]),
     "aic_heat_render": (_I, [_P, _P, _I, _I, _P, _I]),
+    "aic_prox_config_default": (_I, [_I, _I, _I, _P]),
+    "aic_prox_create": (_I, [_I, _P, _P]),
+    "aic_prox_destroy": (_I, [_P]),
+    "aic_prox_option": (_I, [_P, C.c_char_p, _I]),
+    "aic_prox_reset": (_I, [_P, _I]),
+    "aic_prox_set_ground": (_I, [_P, _I, _P, _I]),
+    "aic_prox_update": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "aic_prox_flush": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "aic_prox_export": (_I, [_P, _I, _P, _P]),
+    "aic_prox_export_pairs": (_I, [_P, _I, _P, _P]),
     "aic_jpeg_tables": (_I, [_I, _P, _P]),
     "aic_jpeg_header": (_I, [_I, _I, _I, _I, _I, _P, _I, _P]),
     "aic_jpeg_config_default": (_I, [_I, _I, _P]),

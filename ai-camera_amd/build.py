@@ -14,9 +14,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libaicam.so")
-SOURCES = ["runtime.cpp", "lsap.cpp", "assoc_host.cpp", "global_id.cpp", "tracker.cpp", "bytetrack.cpp", "ocsort.cpp", "botsort.cpp", "deepsort_bank.cpp", "xcam.cpp", "archive.cpp", "zones.cpp", "bestshot.cpp", "scene.cpp", "left.cpp", "colours.cpp", "heat.cpp", "jpeg_host.cpp", "jpeg.cpp", "jpegdec_host.cpp", "jpegdec.cpp","render_host.cpp", "render.cpp", "gmc.cpp", "yuv.cpp", "engine.cpp", "pipeline.cpp", "conv_plan.cpp", "row_band.cpp",
+SOURCES = ["runtime.cpp", "lsap.cpp", "assoc_host.cpp", "global_id.cpp", "tracker.cpp", "bytetrack.cpp", "ocsort.cpp", "botsort.cpp", "deepsort_bank.cpp", "xcam.cpp", "archive.cpp", "zones.cpp", "bestshot.cpp", "scene.cpp", "left.cpp", "colours.cpp", "heat.cpp", "prox.cpp", "jpeg_host.cpp", "jpeg.cpp", "jpegdec_host.cpp", "jpegdec.cpp","render_host.cpp", "render.cpp", "gmc.cpp", "yuv.cpp", "engine.cpp", "pipeline.cpp", "conv_plan.cpp", "row_band.cpp",
            "kernels_conv.hip", "kernels_conv_pp.hip", "kernels_conv_sp.hip", "kernels_conv_wide.hip", "kernels_conv_direct.hip", "kernels_conv_block.hip", "kernels_conv_c2f.hip", "kernels_elt.hip",
-           "kernels_pre.hip", "kernels_det.hip", "kernels_trk.hip", "kernels_trk_dev.hip", "kernels_bytetrack.hip", "kernels_ocsort.hip", "kernels_botsort.hip", "kernels_gmc.hip", "kernels_overlay.hip", "kernels_xcam.hip", "kernels_archive.hip", "kernels_zones.hip", "kernels_bestshot.hip", "kernels_scene.hip", "kernels_left.hip", "kernels_colours.hip", "kernels_heat.hip", "kernels_render.hip", "kernels_yuv.hip", "kernels_jpeg.hip", "kernels_jpegdec.hip"]
+           "kernels_pre.hip", "kernels_det.hip", "kernels_trk.hip", "kernels_trk_dev.hip", "kernels_bytetrack.hip", "kernels_ocsort.hip", "kernels_botsort.hip", "kernels_gmc.hip", "kernels_overlay.hip", "kernels_xcam.hip", "kernels_archive.hip", "kernels_zones.hip", "kernels_bestshot.hip", "kernels_scene.hip", "kernels_left.hip", "kernels_colours.hip", "kernels_heat.hip", "kernels_prox.hip", "kernels_render.hip", "kernels_yuv.hip", "kernels_jpeg.hip", "kernels_jpegdec.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable", "-DNDEBUG"] + os.environ.get("AICAM_EXTRA_FLAGS", "").split()
 

@@ -36,6 +36,11 @@ people go.  At the end of the run each camera's twelve layers are written as `DI
 heatmap.LAYERS) and the chosen layer (default dwell) over the camera's last frame as `DIR/cam<S>_<layer>.jpg`; `--heat_paths` appends
 one JSON line per ended track (start, end, path length, cells, ...); `--heat_overlay` blends the layer into every saved frame before
 boxes and labels are drawn.
+`--proximity [--ground FILE.json] [--near N] [--proximity_file FILE.jsonl]`: who is with whom and how fast.  Every
+JSON line gains `"parties"` (lists of track ids, parties of two or more first), `"units"` (parties + singles) and `"speed"`, one q8 value
+per track of the line (-1 before the first measurement); every LINK / UNLINK of a pair is printed as a line of its own.  `--ground` holds
+per camera `{"H": [9 ints], "shift": s}` or `{"pixels": [...], "ground": [...]}` (through proximity.homography) and selects the
+ground-plane metric, `--near` is then in ground units; `--proximity_file` appends one JSON line per ended track.
 `--scene_watch [--scene_cell {4,8,16}]`: a background model per camera on a coarse gray grid.  Every JSON line
 gains `"scene": {active, moving_cells, motion_box, alarms}` and `"moving"`, one value per track of the line (256 = every cell under its
 box moves, -1 = the box is off the frame); every alarm edge (dark, bright, defocus, scene, frozen) is printed as a line of its own.
@@ -137,6 +142,16 @@ def parse_arguments(argv=None) -> argparse.Namespace:
                    help="with --heat_maps: the layer that is drawn (visits, dwell, starts, ends, dir0..dir7; default dwell)")
     p.add_argument("--heat_paths", type=str, default=None, metavar="FILE.jsonl", help="with --heat_maps: append one JSON line per ended track to FILE")
     p.add_argument("--heat_overlay", action="store_true", help="with --heat_maps: blend the layer into every saved frame, under boxes and labels")
+    p.add_argument("--proximity", action="store_true",
+                   help="who is with whom and how fast (DESIGN.md section 55): every JSON line gains \"parties\" (lists of track ids, parties of two "
+                        "or more first), \"units\" and \"speed\" (one q8 value per track, -1 before the first measurement); every LINK / UNLINK of "
+                        "a pair is printed as its own line")
+    p.add_argument("--ground", type=str, default=None, metavar="FILE.json",
+                   help="with --proximity: per camera {\"H\": [9 ints], \"shift\": s} or {\"pixels\": [[x, y], ..], \"ground\": [[X, Y], ..]} "
+                        "(one object, or a list with one per camera); selects the ground-plane metric, --near is then in ground units")
+    p.add_argument("--near", type=int, default=None, metavar="N",
+                   help="with --proximity: how near is near -- per mille of the mean body height (default 700), or ground units with --ground")
+    p.add_argument("--proximity_file", type=str, default=None, metavar="FILE.jsonl", help="with --proximity: append one JSON line per ended track to FILE")
     p.add_argument("--redact", type=str, default="off", choices=("off", "box", "head"),
                    help="privacy redaction of every tracked object on the saved frames: its whole box, or its head (the top quarter)")
     p.add_argument("--redact_style", type=str, default="mosaic:16",
@@ -199,6 +214,12 @@ def parse_arguments(argv=None) -> argparse.Namespace:
         p.error("--colours_file needs --colours")
     if (args.heat_cell is not None or args.heat_layer is not None or args.heat_paths is not None or args.heat_overlay) and not args.heat_maps:
         p.error("--heat_cell, --heat_layer, --heat_paths and --heat_overlay need --heat_maps DIR")
+    if (args.ground is not None or args.near is not None or args.proximity_file is not None) and not args.proximity:
+        p.error("--ground, --near and --proximity_file need --proximity")
+    if args.near is not None and not 1 <= args.near <= (1 << 24 if args.ground else 4096):
+        p.error("--near is 1..4096 per mille of body height, or 1..2^24 ground units with --ground")
+    if args.ground is not None and args.near is None:
+        p.error("--ground needs --near N, in ground units")
     if args.heat_layer is not None and args.heat_layer not in HEAT_LAYERS:
         p.error("--heat_layer is one of " + ", ".join(HEAT_LAYERS))
     if (args.left_cell is not None or args.left_after is not None) and not args.left_objects:
@@ -653,6 +674,65 @@ class _ColourLines:
             self.stage.close()
 
 
+class _ProxLines:
+    """--proximity [--ground FILE.json] [--near N] [--proximity_file FILE.jsonl]: a Proximity (proximity.py) over the run's tracks,
+    attached to the pipeline or fed frame by frame as _ColourLines is.  Every LINK / UNLINK is printed as a line of its own; every ended
+    track goes to FILE as one JSON object; close() flushes what still lives."""
+
+    def __init__(self, args, streams, size, device, pipe=None):
+        from . import proximity
+        self.mod, self.pipe, self._res, self._i, self._at, self.streams = proximity, pipe, None, 0, 0, streams
+        maps = None
+        if args.ground:
+            with open(args.ground) as f:
+                maps = json.load(f)
+            maps = [maps] * streams if isinstance(maps, dict) else list(maps)
+            if len(maps) != streams:
+                raise ValueError(f"{args.ground} holds {len(maps)} ground maps for {streams} cameras")
+        self.stage = proximity.Proximity(streams, (size[1], size[0]), metric="ground" if maps else "body", near=args.near, device=device)
+        for s, m in enumerate(maps or []):
+            H, shift = (m["H"], int(m.get("shift", 0))) if "H" in m else proximity.homography(m["pixels"], m["ground"])
+            self.stage.set_ground(H, shift, stream=s)
+        self.file = open(args.proximity_file, "a") if args.proximity_file else None
+        if pipe is not None:
+            pipe.attach_proximity(self.stage)
+
+    def _write(self, result):
+        if self.file is not None:
+            for ev in result.ended():
+                self.file.write(json.dumps(ev) + "\n")
+
+    def after(self, frame, tracks):
+        """After every yielded frame: (parties, units, the q8 speed per track, in the order of the tracks); prints the frame's pair events."""
+        if self.pipe is None:
+            self._res, self._i, self._at = self.stage.update_tuples([[tracks]]), 0, 0
+            self._write(self._res)
+        elif self.pipe.proximity_result is not self._res:
+            self._res, self._i, self._at = self.pipe.proximity_result, 0, 0
+            self._write(self._res)
+        t, s = divmod(self._i, self.streams)
+        self._i += 1
+        res = self._res
+        for e in res.pairs(t, s):
+            print(json.dumps({"pair": e["kind"], "stream": s, "frame": e["frame"], "ids": list(e["ids"]), "duration": e["duration"],
+                              "distance": e["distance"], "ticks": e["ticks"]}))
+        tags = res.row_tags[self._at:self._at + len(tracks)]                 # the call's rows lie frame after frame, as they were yielded
+        self._at += len(tracks)
+        return res.parties(t, s), int(res.records[t, s, 9]), [int(v) for v in tags[:, 2]]
+
+    def close(self):
+        try:
+            res = self.stage.flush()
+            self._write(res)
+            while int(res.pending.sum()):
+                res = self.stage.drain(cap=self.stage.max_tracks)
+                self._write(res)
+        finally:
+            if self.file is not None:
+                self.file.close()
+            self.stage.close()
+
+
 class _HeatFiles:
     """--heat_maps DIR [--heat_cell N] [--heat_layer NAME] [--heat_paths FILE] [--heat_overlay]: a HeatMaps (heatmap.py) over the run's
     tracks, attached to the pipeline or fed frame by frame.  Every ended track goes to FILE as one JSON line; close() flushes what still
@@ -877,6 +957,17 @@ def main_streams(args, cv2):
                     f.close()
             pipe.close()
             return 1
+    prox = None
+    if args.proximity:
+        try:
+            prox = _ProxLines(args, S, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --proximity: {e}")
+            for f in (zones, shots, watch, left, worn, heat):
+                if f is not None:
+                    f.close()
+            pipe.close()
+            return 1
     output = None
     if not args.no_save:
         try:
@@ -904,6 +995,7 @@ def main_streams(args, cv2):
             wears = worn.after(frame, tracks) if worn is not None else None
             if heat is not None:
                 heat.after(frame, tracks, k)
+            together = prox.after(frame, tracks) if prox is not None else None
             gids = pipe.global_ids(k, [t[4] for t in tracks]).tolist() if args.link_cameras else None
             if output is not None:
                 shown = tracks if gids is None else [t[:4] + (f"{t[4]} G{(g >> 32) & 0xfff}.{g & 0xffffffff}" if g >= 0 else t[4],) + t[5:] for t, g in zip(tracks, gids)]
@@ -935,6 +1027,8 @@ def main_streams(args, cv2):
                     line["left_objects"] = lost[0]
                 if wears is not None:
                     line["colours"] = wears
+                if together is not None:
+                    line["parties"], line["units"], line["speed"] = together
                 outs[k].write(json.dumps(line) + "\n")
     except KeyboardInterrupt:
         print("Processing interrupted by user.")
@@ -954,6 +1048,8 @@ def main_streams(args, cv2):
             worn.close()
         if heat is not None:
             heat.close()
+        if prox is not None:
+            prox.close()
         if output is not None:
             output.close()
         if encoder is not None:
@@ -1126,6 +1222,16 @@ def main(argv=None):
                 if f is not None:
                     f.close()
             return 1
+    prox = None
+    if args.proximity:
+        try:
+            prox = _ProxLines(args, 1, size, dev, pipe)
+        except Exception as e:
+            print(f"Error setting up --proximity: {e}")
+            for f in (out_f, writer, zones, shots, watch, left, worn, heat, pipe):
+                if f is not None:
+                    f.close()
+            return 1
 
     output = None
     if args.redact != "off" or args.masks or args.draw_zones or args.redact_style != "mosaic:16":
@@ -1175,6 +1281,7 @@ def main(argv=None):
             wears = worn.after(frame, tracks) if worn is not None else None
             if heat is not None:
                 heat.after(frame, tracks)
+            together = prox.after(frame, tracks) if prox is not None else None
             if writer is not None or (args.show_display and cv2 is not None):      # aicamera_tracker.py:211-236
                 if heat is not None and heat.overlay_on:
                     frame = heat.overlay(np.ascontiguousarray(frame)[None])[0]
@@ -1197,6 +1304,8 @@ def main(argv=None):
                     line["left_objects"] = lost[0]
                 if wears is not None:
                     line["colours"] = wears
+                if together is not None:
+                    line["parties"], line["units"], line["speed"] = together
                 out_f.write(json.dumps(line) + "\n")
             if frame_idx % 100 == 0:
                 print(f"Processed {frame_idx} frames. Current FPS: {display_fps:.2f}")
@@ -1219,6 +1328,8 @@ def main(argv=None):
             worn.close()
         if heat is not None:
             heat.close()
+        if prox is not None:
+            prox.close()
         if output is not None:
             output.close()
         if pipe is not None:

@@ -279,6 +279,7 @@ class TrackingPipeline:
         self._feed_left(nt, rows, slot, host_frames)
         self._feed_colours(nt, rows, slot, host_frames)
         self._feed_heat(nt, rows)
+        self._feed_proximity(nt, rows)
 
     def _feed_zones(self, nt, rows, cap_events=256):
         """nt [count], rows [count, max_persons, 6] of a run call, tick-major (frame i is tick i // streams of stream i % streams)."""
@@ -421,6 +422,30 @@ class TrackingPipeline:
             return
         S, mp, count = self.streams, rows.shape[1], len(nt)
         self.heat_result = w.update([[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)], cap=self.heat_cap)
+
+    _prox = proximity_result = None
+    proximity_cap, proximity_cap_pairs = 16, 64
+
+    def attach_proximity(self, stage, cap=16, cap_pairs=64):
+        """A Proximity (proximity.py) of `.streams` streams for this frame size: after every run* call the call's tracks -- all ticks, all
+        streams, ONE stage.update -- go through it and proximity_result is that call's ProximityResult (records, row tags per track row,
+        at most `cap_pairs` pair events per frame and `cap` ended tracks per stream per call; the rest wait, see .pending and
+        stage.drain()).  The stage reads rows only: they reach it from the host side, as for attach_heat_maps; with *_passes it sees the
+        last pass only.  The tracks returned are untouched.  None detaches."""
+        w = stage
+        if w is not None and (w.streams != self.streams or (w.frame_h, w.frame_w) != (self.frame_h, self.frame_w)):
+            raise ValueError(f"proximity of {w.streams} streams of {w.frame_h}x{w.frame_w} for a pipeline of "
+                             f"{self.streams} of {self.frame_h}x{self.frame_w}")
+        self._prox, self.proximity_cap, self.proximity_cap_pairs, self.proximity_result = w, int(cap), int(cap_pairs), None
+
+    def _feed_proximity(self, nt, rows):
+        """nt [count], rows [count, max_persons, 6] of a run call, tick-major."""
+        w = self._prox
+        if w is None:
+            return
+        S, mp, count = self.streams, rows.shape[1], len(nt)
+        self.proximity_result = w.update([[rows[t * S + s, :min(int(nt[t * S + s]), mp)] for s in range(S)] for t in range(count // S)],
+                                         cap=self.proximity_cap, cap_pairs=self.proximity_cap_pairs)
 
     def close(self):
         for b in getattr(self, "_staging", []):

@@ -1131,6 +1131,58 @@ int aic_heat_import_layers(aic_heat* h, int stream, int layer_mask, const int32_
 int aic_heat_set_lut(aic_heat* h, const uint8_t* bgr);
 int aic_heat_lut(uint8_t* bgr);
 int aic_heat_render(aic_heat* h, uint8_t* frames_bgr, int n_frames, int mem, const int32_t* cameras, int layer);
+/* ---- proximity: ground plane, speed, pairs and parties per camera (csrc/prox.hpp) --------------------------------
+ * A tracker-agnostic stage over the rows every tracker delivers (x1 y1 x2 y2 id cls, int32), for `streams` (1..256) cameras per call; no
+ * frames.  A counted row (VALID, FIRST of its id, NONEMPTY, as for aic_heat_*) has the foot anchor fx = clamp(x1 + x2, 0, 2 W - 1), fy =
+ * clamp(2 y2, 0, 2 H - 1) in doubled pixels and the height hc = clamp(y2 - y1, 1, 32767).  metric 0 (ground plane) places it at gx =
+ * floor(((H0 fx + H1 fy + 2 H2) << shift) / den), gy from H3..H5, den = H6 fx + H7 fy + 2 H8, when den > 0 and |gx|, |gy| <= 2^24; with
+ * |H[k]| <= 2^30 and shift <= 14 every intermediate fits int64 (|n| < 2^47, shifted < 2^61).  metric 1 (relative to body height) places
+ * every counted row at (fx, fy).  Two placed rows are NEAR when dgx^2 + dgy^2 <= near^2 (metric 0), or when 256 max(hc) <=
+ * height_ratio_q8 min(hc) and 1 000 000 (dfx^2 + dfy^2) <= near^2 (hc_i + hc_j)^2 (metric 1; all below 2^57).  A table of max_tracks
+ * slots per stream holds each track's last place, its smoothed speed v_q8 (ground units, or per mille of body height, per tick; q8), its
+ * gait (0 none yet, 1 still, 2 moving, 3 running), the distance it moved and its parties; a resident table holds linked / on / off /
+ * since per PAIR of slots: a pair judged near link_ticks ticks in a row LINKS, a linked pair judged far unlink_ticks ticks in a row
+ * UNLINKS, a pair with a row missing is frozen, and a slot taken by a new track inherits nothing.  Parties are the connected components
+ * of the linked graph over the tick's placed rows.  tests/prox_oracle.py is the specification and the device equals it bit for bit.
+ * aic_prox_config: frame_h, frame_w 1..16384; max_tracks 1..512; forget_after 0..2^24; metric 0 / 1; near 1..2^24 (metric 0) or 1..4096
+ * (metric 1); height_ratio_q8 256..65536; link_ticks, unlink_ticks 1..32767; speed_shift 0..12; 0 <= still_speed <= run_speed <= 2^20.
+ * aic_prox_config_default fills 128 tracks, forget_after 70, metric 1, near 700, height_ratio_q8 384, link_ticks 30, unlink_ticks 60,
+ * speed_shift 2, still_speed 5, run_speed 70.  Resident memory: 32.8 KB of slot table per camera plus 8 bytes per slot pair, 4
+ * max_tracks (max_tracks - 1) bytes per camera (65 KB at 128 tracks, 1.05 MB at 512).
+ * Every argument error is AIC_ERR_INVALID before the device is touched; create, option, reset and set_ground never touch it.  Device
+ * buffers are allocated by the first call that reaches the device; an allocation that does not fit fails that call with AIC_ERR_CAPACITY.
+ * set_ground: H[9] (|H[k]| <= 2^30) and shift 0..14 of one stream or of all (-1); the default is the identity with shift 0.
+ * update: counts[ticks * streams] and rows6 (tick-major; both host or both device, rows_mem), ticks 0..65536 (0 only drains), cap 0..4096,
+ * cap_pairs 0..4096; a frame of more than 512 rows is AIC_ERR_CAPACITY before anything is staged.  Outputs (host): n_final[streams];
+ * events[streams, cap, 16] = reason (0 LIVE, 1 EXPIRED, 2 FLUSHED), stream, id, cls, first_frame, last_seen, sightings, links, dist,
+ * max_v_q8, v_q8, party_ticks, max_party, last gx, last gy, last gait -- only the n_final[s] first of a stream are written;
+ * pending[streams]; status[streams] (may be NULL); records[ticks * streams, 16] = frame, n_counted, n_placed, n_near_pairs, largest_near,
+ * n_linked_pairs, n_parties, n_singles, largest_party, n_units, n_running, n_still, n_link, n_unlink, 0, 0; row_tags[sum of counts, 8] =
+ * gx, gy, v_q8 (-1 without a measurement), gait, party (the smallest id of the row's party, -1 when not placed), party_size, n_near, flags
+ * (1 VALID, 2 FIRST, 4 NONEMPTY, 8 PLACED, 16 NEW); n_pair_events[ticks * streams] (the true counts); pair_events[ticks * streams,
+ * cap_pairs, 8] = kind (1 LINK, 2 UNLINK), frame, id_lo, id_hi, duration, distance, on or off, 0, zero-filled.  The records and tags of
+ * ticks a stopped stream did not walk are all -1.  A stream that needs more than max_tracks slots stops alone with AIC_ERR_CAPACITY.
+ * flush, export (events[max_tracks, 16]), reset: as for aic_heat_*.  export_pairs: out6[max_tracks (max_tracks - 1) / 2, 6] = id_a id_b
+ * linked on off since of the nonzero entries among live slots, in (slot_lo, slot_hi) order.
+ * option: "forget_after", "metric", "near", "height_ratio_q8", "link_ticks", "unlink_ticks", "speed_shift", "still_speed", "run_speed"
+ * (legal between calls), "ticks_per_launch", "launch_budget_mb": same results. */
+typedef struct aic_prox aic_prox;
+typedef struct {
+    int32_t streams, frame_h, frame_w, max_tracks, forget_after, metric, near, height_ratio_q8, link_ticks, unlink_ticks, speed_shift, still_speed,
+        run_speed;
+} aic_prox_config;
+int aic_prox_config_default(int streams, int frame_h, int frame_w, aic_prox_config* out);
+int aic_prox_create(int device, const aic_prox_config* config, aic_prox** out);
+int aic_prox_destroy(aic_prox* h);
+int aic_prox_option(aic_prox* h, const char* key, int value);
+int aic_prox_reset(aic_prox* h, int stream);
+int aic_prox_set_ground(aic_prox* h, int stream, const int32_t* H, int shift);
+int aic_prox_update(aic_prox* h, int ticks, const int32_t* counts, const int32_t* rows6, int rows_mem, int cap, int cap_pairs, int32_t* n_final,
+                    int32_t* events, int32_t* pending, int32_t* status, int32_t* records, int32_t* row_tags, int32_t* n_pair_events,
+                    int32_t* pair_events);
+int aic_prox_flush(aic_prox* h, int stream, int cap, int32_t* n_final, int32_t* events, int32_t* pending, int32_t* status);
+int aic_prox_export(aic_prox* h, int stream, int32_t* n, int32_t* events);
+int aic_prox_export_pairs(aic_prox* h, int stream, int32_t* n, int32_t* out6);
 /* ---- JPEG out: a bank of equally sized BGR24 images to complete JFIF files in one call (csrc/jpeg.hpp) ---------
  * Baseline sequential DCT, 8 bit, YCbCr full range, 4:2:0 (subsampling 420) or 4:4:4 (444), the Annex K Huffman tables, restart markers
  * always on (restart = MCUs per interval, 1..65535; 0 = one MCU row).  Integer arithmetic only; tests/jpeg_oracle.py is the
